@@ -2,15 +2,18 @@
 all-reduce + clip/Adam) of the attention-GRU decoder at BASELINE.json configs[1]:
 2-layer attention-GRU h=1024, batch=64 per GPU, T_enc=200, T_dec=800, fp32, synthetic data.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: launched by torch.distributed.run, one rank per GPU, RCCL all-reduce of the flat gradient)
 
-Prints ONE JSON line on rank 0 (see the driver contract).  Besides the contract fields it carries
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run sets up, warms up, times the K steps and prints
+the line; --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy (dump_outputs).  Everything
+else is measured only with --full, and the line's fields for it are null otherwise.  With --full the line also carries
   roofline     -- the recurrent-step kernel family (sk_kernel): algorithmic flops of all its dispatches
                   in one training step / summed dispatch time, measured with HIP events attached to
                   every dispatch (hipExtLaunchKernelGGL) on the stream they run on, vs the f32 MFMA peak;
   cpu_baseline -- the oracle restatement of the reference (torch-CPU fp32, all host cores) timed on
-                  a bounded sample of the same workload, on rank 0 at N=1 only.
+                  a bounded sample of the same workload, on rank 0 at N=1 only;
+and allreduce_ms, dense, value_f32_mfma, parity_check and secondary (see main()).
 """
 from __future__ import annotations
 
@@ -33,6 +36,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (all-reduce time, roofline, dense "
+                         "and f32-MFMA runs, CPU baseline, parity, secondary configurations); the --no-* switches "
+                         "below thin this out")
     ap.add_argument("--T", type=int, default=800, help="decoder frames per window (T_dec)")
     ap.add_argument("--B", type=int, default=64, help="batch per GPU")
     ap.add_argument("--U", type=int, default=200, help="encoder timesteps (T_enc)")
@@ -116,6 +125,32 @@ def build_model(a, dev, use_graph=True):
     with torch.no_grad():
         m.get_parameter_dict()['/parrot/h1_to_att/fork_kappa.b'].fill_(a.kappa_bias)
     return m
+
+
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(path, cost, model, batch_size):
+    """What the last timed Trainer.step hands its caller, as .npy files: the cost it returned (float64), the parameters
+    after its clip + Adam update, the gradient it applied, and the TBPTT carry (h and c of every layer, w, kappa) the next
+    step starts from (float32).  Each array gets an equal share of DUMP_BYTES; a larger one is written as a fixed sample:
+    the sorted distinct flat indices drawn with seed 0, so two runs with the same arguments write the same elements."""
+    import numpy as np
+    carry = model._carry[batch_size]
+    arrays = {"cost": cost.detach().double().reshape(1), "parameters": model.flat_parameters,
+              "gradients": model.flat_gradients}
+    for l, (h, c) in enumerate(zip(carry['h'], carry['c'])):
+        arrays[f"state_h{l + 1}"], arrays[f"state_c{l + 1}"] = h, c
+    arrays["state_w"], arrays["state_k"] = carry['w'], carry['k']
+    share = DUMP_BYTES // (len(arrays) + 1)  # (the spare share covers the .npy headers)
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        cap = share // t.element_size()
+        if t.numel() > cap:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), size=cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def kernel_source_digest(root=ROOT):
@@ -581,16 +616,17 @@ def child_json(a, flag, extra=(), timeout=420):
 def secondary_subprocess(a):
     sec = child_json(a, "--secondary-only", timeout=300)
     if a.config == "cfg2":  # BASELINE configs[3] per GPU (the 8-GPU line's workload), bf16 operands
-        d = child_json(a, "--no-secondary", ["--config", "cfg4", "--no-cpu-baseline", "--no-dense", "--no-f32-gemm", "--no-parity",
-                                              "--steps", "3", "--warmup", "1", "--L", "3", "--H", "1536",
-                                              "--cell", "lstm", "--dtype", "bf16"], timeout=420)
+        d = child_json(a, "--full", ["--no-secondary", "--config", "cfg4", "--no-cpu-baseline", "--no-dense", "--no-f32-gemm",
+                                     "--no-parity", "--steps", "3", "--warmup", "1", "--L", "3", "--H", "1536",
+                                     "--cell", "lstm", "--dtype", "bf16"], timeout=420)
         sec["cfg4_bf16"] = ({"workload": d["config"]["workload"], "ms_per_step": d["ms_per_step"],
                              "frames_per_s": d["value"], "roofline": d.get("roofline")}
                             if "ms_per_step" in d else d)
         # the reference's own decoder depth (model.py:312-347: three GatedRecurrent layers, h = 1024), literal batch-axis
         # encoder, fp32: the one instance where "the reference's model" is literally defined
-        d = child_json(a, "--no-secondary", ["--L", "3", "--H", "1024", "--cell", "gru", "--dtype", "f32", "--no-cpu-baseline",
-                                              "--no-dense", "--no-f32-gemm", "--no-parity", "--steps", "3", "--warmup", "1"], timeout=420)
+        d = child_json(a, "--full", ["--no-secondary", "--L", "3", "--H", "1024", "--cell", "gru", "--dtype", "f32",
+                                     "--no-cpu-baseline", "--no-dense", "--no-f32-gemm", "--no-parity", "--steps", "3",
+                                     "--warmup", "1"], timeout=420)
         if "ms_per_step" in d:
             fwd_bytes = 99.9e6  # 21.26 M weights per decoder timestep, forward
             sec["ref_literal_3gru"] = {
@@ -738,8 +774,10 @@ def main():
 
     el, cost = timed(a.steps, a.warmup)
     final_cost = float(cost)
+    if a.dump_outputs and rank == 0:  # before the --full runs below step the same model further
+        dump_outputs(a.dump_outputs, cost, model, a.B)
     seen = ranks_seen(dev)
-    ar_ms = allreduce_ms([g_ for _, g_ in trainer.groups], dev)
+    ar_ms = allreduce_ms([g_ for _, g_ in trainer.groups], dev) if a.full else None
     try:  # the launch schedule the plan actually ran (after the library's fall-backs)
         from parrot_amd import _lib
         sched_id = int(_lib.load().parrot_decoder_schedule(next(iter(model._train_ws.values()))['plan']))
@@ -757,14 +795,14 @@ def main():
     if a.dtype == "bf16":
         gemm_mode = "bf16 operands (bf16-in kernels)"
     f32run = None
-    if not a.no_f32_gemm and a.dtype == "f32" and pops.full_precision() == pops.PRECISION_BF16X3:
+    if a.full and not a.no_f32_gemm and a.dtype == "f32" and pops.full_precision() == pops.PRECISION_BF16X3:
         prev_mode = pops.set_full_precision(pops.PRECISION_F32)
         el_f, _ = timed(a.steps, 1)
         pops.set_full_precision(prev_mode)
         f32run = {"value": round(world * a.B * a.T * a.steps / el_f, 1), "ms_per_step": round(1e3 * el_f / a.steps, 3)}
     # second timed run, outside the headline region: the attention kernels read ALL context rows (no window support)
     dense = None
-    if not a.no_dense and os.environ.get("PARROT_ATT_DENSE", "0") in ("", "0"):
+    if a.full and not a.no_dense and os.environ.get("PARROT_ATT_DENSE", "0") in ("", "0"):
         os.environ["PARROT_ATT_DENSE"] = "1"
         model.close()  # plans read the switch when they are built
         el_d, _ = timed(a.steps, 1)
@@ -773,11 +811,11 @@ def main():
         model.close()
 
     roof = cpu = parity = secondary = None
-    if rank == 0:
+    if a.full and rank == 0:
         if not a.no_roofline:
             roof = roofline_leg(a, dev, model.flat_parameters)
     model.close()
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         torch.cuda.synchronize()
         torch.cuda.empty_cache()
         if not a.no_cpu_baseline:

@@ -9,8 +9,9 @@ own `three_tier.compute_cost` (three_tier.py:534-636) fills -- the reference's d
   2. the other direction, checked when this script runs: parrot_amd.sampleRNN.lib.save_params writes a pickle, the
      reference's load_params reads it into its own registry, and every value must come back bit for bit.
 
-tests/test_ckpt_cpu.py loads the committed pickle with the PRODUCT's load_params and, when /root/reference is present
-(this container), repeats direction 2.  The Blocks `.tar` half of the bridge (train.py:157-173, sample.py:39-42, 83)
+tests/test_ckpt_cpu.py loads the committed pickle with the PRODUCT's load_params and checks direction 2 against what
+the reference's load_params does (pickle.load, then set_value by name).  The Blocks `.tar` half of the bridge
+(train.py:157-173, sample.py:39-42, 83)
 cannot be pinned this way: blocks.serialization is not in /root/reference, so parrot_amd/checkpoint.py stays validated
 against its own writer and the documented layout only.
 

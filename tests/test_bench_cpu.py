@@ -51,6 +51,38 @@ def test_repo_has_no_stale_traffic_figure():
         assert note is None or "stale" in note or "unreadable" in note
 
 
+def test_dump_outputs_budget_and_fixed_sample(tmp_path):
+    """--dump-outputs: every array of the last step as float32 / float64 .npy, below 64 MB in all; an array over its share
+    is a sample at the same sorted distinct indices on every run, a small one is written whole in its own shape."""
+    import types
+
+    import numpy as np
+    import torch
+    import bench
+    B, H, L = 4, 8, 2
+    n = 16_000_000  # 64 MB of float32 parameters (exact integers below 2**24): over budget on their own
+    model = types.SimpleNamespace(
+        flat_parameters=torch.arange(n, dtype=torch.float32), flat_gradients=torch.full((1000,), 0.5),
+        _carry={B: dict(h=[torch.randn(B, H) for _ in range(L)], c=[torch.randn(B, H) for _ in range(L)],
+                        w=torch.randn(B, 3), k=torch.randn(B, 5))})
+    cost = torch.tensor(1.25)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), cost, model, B)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["cost.npy", "parameters.npy", "gradients.npy", "state_w.npy", "state_k.npy"] +
+                           [f"state_{s}{l}.npy" for s in "hc" for l in range(1, L + 1)])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64_000_000
+    out = {f: np.load(tmp_path / "a" / f) for f in names}
+    assert all(v.dtype in (np.float32, np.float64) for v in out.values())
+    assert out["cost.npy"].dtype == np.float64 and out["cost.npy"].tolist() == [1.25]
+    p = out["parameters.npy"]
+    assert 0 < p.size < n and np.all(np.diff(p) > 0)  # the values are their indices: sorted and distinct
+    assert np.array_equal(p, np.load(tmp_path / "b" / "parameters.npy"))
+    assert np.array_equal(out["gradients.npy"], model.flat_gradients.numpy())
+    assert np.array_equal(out["state_h2.npy"], model._carry[B]['h'][1].numpy())
+    assert np.array_equal(out["state_k.npy"], model._carry[B]['k'].numpy())
+
+
 def test_bench_gpus2_starts_its_own_ranks():
     """`python bench.py --gpus 2` outside torchrun launches two ranks itself: the collective spans
     both (`ranks_seen` = all-reduce of ones) and the line says n_gpus 2.  CPU/gloo, no GPU step (--plumbing-only)."""

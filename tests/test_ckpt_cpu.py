@@ -1,11 +1,10 @@
 """Checkpoint bridge (scope row f3), SampleRNN half: a pickle WRITTEN BY THE REFERENCE's own lib.save_params
 (sampleRNN/lib/__init__.py:96-102, executed by tests/golden/make_ckpt_golden.py) is read by the product's load_params;
-and, where /root/reference exists, a pickle written by the product is read by the reference's own load_params (:104-109)."""
+and a pickle written by the product is one the reference's load_params (:104-109) reads into its own registry."""
 import os
 import pickle
 
 import numpy as np
-import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKL = os.path.join(HERE, "golden", "ref_samplernn_ckpt.pkl")
@@ -38,11 +37,36 @@ def test_product_loads_reference_written_pickle(tmp_path):
         lib.delete_all_params()
 
 
-@pytest.mark.skipif(not os.path.isdir(os.environ.get("PARROT_REFERENCE", "/root/reference")),
-                    reason="needs the reference checkout to execute its load_params")
-def test_reference_loads_product_written_pickle():
-    import sys
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import make_ckpt_golden as G
-    lib, vals = G.reference_registry()
-    assert G.product_roundtrip_through_reference(lib, vals) == 59
+def test_reference_loads_product_written_pickle(tmp_path):
+    """The reference's load_params is `pickle.load` followed by `_params[name].set_value(val)` for every entry, on the
+    registry whose names and shapes the reference-written fixture carries.  So the product's pickle must unpickle with no
+    global but NumPy's (and `_codecs.encode`, which protocol 2 writes for byte strings), and hold every registered name as
+    a float32 array of the registered shape, bit for bit.
+    (tests/golden/make_ckpt_golden.py also runs the reference's own load_params on it when it regenerates the fixture.)"""
+    from parrot_amd.sampleRNN import lib
+    with open(PKL, "rb") as f:
+        registry = {n: np.asarray(v).shape for n, v in pickle.load(f).items()}
+    rng = np.random.RandomState(7)
+    fresh = {n: rng.randn(*shape).astype(np.float32) for n, shape in registry.items()}
+    path = tmp_path / "product.pkl"
+    lib.delete_all_params()
+    lib.set_device("cpu")
+    try:
+        for n, v in fresh.items():
+            lib.param(n, v)
+        lib.save_params(str(path))
+    finally:
+        lib.delete_all_params()
+
+    class NumpyOnly(pickle.Unpickler):
+        def find_class(self, module, name):
+            if module.split(".")[0] != "numpy" and (module, name) != ("_codecs", "encode"):
+                raise pickle.UnpicklingError(f"{module}.{name}: not a NumPy class")
+            return super().find_class(module, name)
+    with open(path, "rb") as f:
+        blob = NumpyOnly(f).load()
+    assert len(blob) == 59 and set(blob) == set(registry)
+    for n, v in fresh.items():
+        got = blob[n]
+        assert isinstance(got, np.ndarray) and got.dtype == np.float32 and got.shape == v.shape, n
+        assert np.array_equal(got, v), n
