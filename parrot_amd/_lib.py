@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from .utils import env_str
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libparrot_hip.so")
 
@@ -217,7 +219,7 @@ def load():
     # the loader binds our DT_NEEDED libamdhip64.so to that one.  Loaded the other way round the process ends up
     # with two HIP runtimes and our launches on torch's pointers fail with hipErrorNoDevice (100).
     import torch  # noqa: F401
-    path = os.environ.get('PARROT_HIP_LIB', LIB_PATH)  # development knob: alternative builds of the same ABI
+    path = env_str('PARROT_HIP_LIB', LIB_PATH)  # development knob: alternative builds of the same ABI
     if not os.path.exists(path):
         raise HipLibraryMissing(
             f"{LIB_PATH} not found: build it with `python -m parrot_amd.build` "

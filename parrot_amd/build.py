@@ -11,6 +11,8 @@ import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
+from .utils import env_str
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libparrot_hip.so")
@@ -20,8 +22,8 @@ ARCH = "gfx950"
 SOURCES = ["skinny.hip", "biggemm.hip", "attention.hip", "elementwise.hip", "quantize.hip",
            "plans.hip", "plans_decode.hip", "capi.hip", "samplernn.hip", "persist.hip", "sr_persist.hip", "rowgru.hip", "trainops.hip"]
 EXTRA_FLAGS = {"quantize.hip": ["-ffp-contract=off"]}
-if os.environ.get("PARROT_PM_DEPTH"):  # development: ring depth of the persistent machine's K loop
-    EXTRA_FLAGS["persist.hip"] = ["-DPM_DEPTH=" + os.environ["PARROT_PM_DEPTH"]]
+if env_str("PARROT_PM_DEPTH"):  # development: ring depth of the persistent machine's K loop
+    EXTRA_FLAGS["persist.hip"] = ["-DPM_DEPTH=" + env_str("PARROT_PM_DEPTH")]
 
 
 def _hipcc() -> str:
@@ -47,7 +49,7 @@ def build(force: bool = False, verbose: bool = True, timers: bool = False) -> st
     if timers:
         OUT = os.path.join(HERE, "libparrot_hip_timers.so")
         OBJDIR = os.path.join(CSRC, "build_timers")
-    tag, extra = os.environ.get("PARROT_BUILD_TAG"), os.environ.get("PARROT_BUILD_FLAGS", "").split()
+    tag, extra = env_str("PARROT_BUILD_TAG"), env_str("PARROT_BUILD_FLAGS", "").split()
     if tag:  # development: a variant library (compile-time knobs, e.g. -DWK_PB_DEPTH=4), loaded through PARROT_HIP_LIB
         OUT = os.path.join(HERE, f"libparrot_hip_{tag}.so")
         OBJDIR = os.path.join(CSRC, f"build_{tag}")

@@ -20,6 +20,7 @@
 #include "att_fwd_body.h"
 #include "att_bwd_body.h"
 #include "elementwise.h"
+#include "switches.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -48,10 +49,7 @@ __global__ __launch_bounds__(ATTB_THREADS) void att_state_bwd_kernel(const AttBw
 
 
 int att_fwd_check(AttFwdArgs& g) {
-    {   // read per launch (launches happen once, at graph capture): tests toggle it between two plans
-        const char* e = getenv("PARROT_ATT_DENSE");
-        g.dense = e ? atoi(e) : 0;
-    }
+    g.dense = sw_att_dense();  // read per launch (launches happen once, at graph capture): tests toggle it between two plans
     if (g.A < 1 || g.A > ATT_MAXA || g.B < 1 || g.U < 1 || g.E < 1 || g.esplit < 1) return PH_ERR_BADARG;
     if (att_fwd_lds(g.U) > 160 * 1024) return PH_ERR_UNSUPPORTED;
     return 0;

@@ -4,8 +4,8 @@
 // the same kernel serves NN (x*W), NT (dy*W^T) and TN (x^T*dy, the deferred weight gradients of
 // the decoder scan) without transposed copies in HBM.
 //
-// Tiling: 128x128x16 per 256-thread workgroup (4 waves as 2x2, each 64x64 = 2x2 MFMA 32x32
-// blocks, 64 accumulator VGPRs).  Operands are staged global -> VGPR -> LDS in [k][m] / [k][n]
+// Tiling: 128x128x16 per 512-thread workgroup (8 waves as 2x4, each 64x32 = 2 MFMA 32x32 blocks,
+// 32 accumulator VGPRs).  Operands are staged global -> VGPR -> LDS in [k][m] / [k][n]
 // images (row pitch 132 floats) so that an MFMA fragment read is 32 consecutive floats per half
 // wave (conflict-free ds_read_b32); the next K-tile is prefetched into registers while the
 // current one is consumed (double-buffered LDS, one barrier per K-tile).  Workgroup ids are
@@ -41,165 +41,8 @@ __device__ __forceinline__ void bg_tile_of_block(int bid, int tiles_m, int tiles
     tn = first + rem % gsz;
 }
 
-// Loads the 128 x 16 slab of an operand whose element (x, k) sits at p[x*sx + k*sk].
-// XC = true : x is the contiguous index (sx == 1).  thread -> (xq = t&31, kr = t>>5), 2 passes.
-// XC = false: k is the contiguous index (sk == 1).  thread -> (x = t>>1, kq = t&1), 2 vectors.
-template <bool XC>
-__device__ __forceinline__ void bg_load(const float* __restrict__ p, int x0, int X, int k0, int kend,
-                                        long long sx, long long sk, bool vec, int t, f32x4 (&v)[2]) {
-    if (XC) {
-        const int xq = t & 31, kr = t >> 5;
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
-            const int k = k0 + kr + 8 * ps;
-            const int x = x0 + 4 * xq;
-            v[ps] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (k < kend) {
-                const float* q = p + (long long)k * sk + x;
-                if (vec && x + 3 < X) {
-                    v[ps] = *reinterpret_cast<const f32x4*>(q);
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (x + u < X) v[ps][u] = q[u];
-                }
-            }
-        }
-    } else {
-        const int x = x0 + (t >> 1), kq = t & 1;
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps) {
-            const int k = k0 + 8 * kq + 4 * ps;
-            v[ps] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            if (x < X) {
-                const float* q = p + (long long)x * sx + k;
-                if (vec && k + 3 < kend) {
-                    v[ps] = *reinterpret_cast<const f32x4*>(q);
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (k + u < kend) v[ps][u] = q[u];
-                }
-            }
-        }
-    }
-}
-
-template <bool XC>
-__device__ __forceinline__ void bg_store(float* __restrict__ s, int t, const f32x4 (&v)[2]) {
-    if (XC) {
-        const int xq = t & 31, kr = t >> 5;
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-            *reinterpret_cast<f32x4*>(s + (kr + 8 * ps) * PITCH + 4 * xq) = v[ps];
-    } else {
-        const int x = t >> 1, kq = t & 1;
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s[(8 * kq + 4 * ps + u) * PITCH + x] = v[ps][u];
-    }
-}
-
-template <bool AXC, bool BXC>
-__global__ __launch_bounds__(256) void bg_kernel(const BgArgs a, int vecA, int vecB, int tiles_m, int tiles_n) {
-    __shared__ __attribute__((aligned(16))) float As[2][BK * PITCH];
-    __shared__ __attribute__((aligned(16))) float Bs[2][BK * PITCH];
-
-    int tm, tn;
-    bg_tile_of_block(blockIdx.x, tiles_m, tiles_n, tm, tn);
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    const int z = blockIdx.y;
-    const int batch = z / a.splitk, ks = z % a.splitk;
-    int kchunk = (a.K + a.splitk - 1) / a.splitk;
-    kchunk = (kchunk + BK - 1) / BK * BK;
-    const int kbeg = ks * kchunk;
-    const int kend = min(a.K, kbeg + kchunk);
-
-    const float* A = a.A + (long long)batch * a.batchA;
-    const float* B = a.B + (long long)batch * a.batchB;
-    float* C = a.C + (long long)batch * a.batchC;
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int kk = lane >> 5, li = lane & 31;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
-
-    f32x4 ra[2], rb[2];
-    const int nk = (kend - kbeg + BK - 1) / BK;
-    if (nk > 0) {
-        bg_load<AXC>(A, m0, a.M, kbeg, kend, a.sam, a.sak, vecA, t, ra);
-        bg_load<BXC>(B, n0, a.N, kbeg, kend, a.sbn, a.sbk, vecB, t, rb);
-        bg_store<AXC>(As[0], t, ra);
-        bg_store<BXC>(Bs[0], t, rb);
-    }
-    __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) {
-            bg_load<AXC>(A, m0, a.M, kbeg + (kt + 1) * BK, kend, a.sam, a.sak, vecA, t, ra);
-            bg_load<BXC>(B, n0, a.N, kbeg + (kt + 1) * BK, kend, a.sbn, a.sbk, vecB, t, rb);
-        }
-        const float* as = As[cur] + wm * 64 + li;
-        const float* bs = Bs[cur] + wn * 64 + li;
-#pragma unroll
-        for (int kp = 0; kp < BK / 2; ++kp) {
-            const int row = (2 * kp + kk) * PITCH;
-            const float a0 = as[row], a1 = as[row + 32];
-            const float b0 = bs[row], b1 = bs[row + 32];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
-        if (kt + 1 < nk) {
-            bg_store<AXC>(As[cur ^ 1], t, ra);
-            bg_store<BXC>(Bs[cur ^ 1], t, rb);
-        }
-        __syncthreads();
-    }
-
-    // Epilogue.  32x32 C/D layout: col = lane & 31, row = (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5).
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int n = n0 + wn * 64 + j * 32 + li;
-            if (n >= a.N) continue;
-            const float bias = (a.bias && ks == 0) ? a.bias[n] : 0.f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int m = m0 + wm * 64 + i * 32 + (q & 3) + 8 * (q >> 2) + 4 * kk;
-                if (m >= a.M) continue;
-                float v = a.alpha * acc[i][j][q] + bias;
-                float* c = C + (long long)m * a.ldc + n;
-                if (a.splitk > 1) {
-                    a.ws[((long long)z * a.M + m) * a.N + n] = a.alpha * acc[i][j][q];  // bias added by the reducer
-                } else {
-                    if (a.accumulate) v += *c;
-                    if (a.act == 1) v = fmaxf(v, 0.f);
-                    else if (a.act == 2) v = tanhf(v);
-                    else if (a.act == 3) v = 1.f / (1.f + expf(-v));
-                    if (a.gate && !(a.gate[(long long)m * a.ldg + n] > 0.f)) v = 0.f;
-                    *c = v;
-                }
-            }
-        }
-}
-
-
-// ---- 8-wave variant (512 threads, same 128x128x16 tile): waves as 2 x 4, each 64 x 32 (2 MFMA blocks, 32
-// accumulator VGPRs), twice the waves per CU for the same LDS: the kernel that runs (the 4-wave
-// kernel above is kept for reference).  PMC on the 4-wave kernel: MFMA pipe 56 % busy, waves parked at s_waitcnt/barriers 45 % of
-// their cycles, no LDS bank conflicts -- more resident waves hide those waits.
+// ---- f32 kernel: 8 waves rather than 4 (2 x 2 of 64 x 64) hold twice the waves per CU for the same LDS and hide the
+// s_waitcnt / barrier stalls the 4-wave kernel measured (113-124 vs 87-102 TFLOP/s; profiles/r01d -> r01e).
 template <bool XC>
 __device__ __forceinline__ void bg_load8(const float* __restrict__ p, int x0, int X, int k0, int kend,
                                          long long sx, long long sk, bool vec, int t, f32x4& v) {
@@ -744,7 +587,7 @@ struct BgsOperand {
     }
 };
 
-template <bool AXC, bool BXC, int ROLES>
+template <bool AXC, bool BXC>
 __global__ __launch_bounds__(512) void bgs_kernel(const BgArgs a, int vecA, int vecB, int tiles_m, int tiles_n, int zmap) {
     typedef BgsOperand<AXC> OA;
     typedef BgsOperand<BXC> OB;
@@ -795,10 +638,10 @@ __global__ __launch_bounds__(512) void bgs_kernel(const BgArgs a, int vecA, int 
         }
     }
     __syncthreads();
-    // Waves w and w + 4 share a SIMD (a workgroup's waves are dealt to the SIMDs cyclically).  ROLES: the upper four
-    // split and store the next tile BEFORE their MFMAs, the lower four after, so that on every SIMD one wave's vector /
-    // LDS-store work runs beside the other's matrix work instead of all eight meeting in the same phase.
-    const bool early = ROLES && (wave >= 4);
+    // Waves w and w + 4 share a SIMD (a workgroup's waves are dealt to the SIMDs cyclically).  The upper four split and
+    // store the next tile BEFORE their MFMAs, the lower four after, so that on every SIMD one wave's vector / LDS-store
+    // work runs beside the other's matrix work instead of all eight meeting in the same phase.
+    const bool early = wave >= 4;
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         const __bf16* as = As + cur * OA::SZ;
@@ -936,27 +779,12 @@ static void bgh_go(const BgArgs& a, dim3 grid, int tm, int tn, hipStream_t strea
     hipLaunchKernelGGL((bgh_kernel<BKT, AX, BX>), grid, dim3(512), lds, stream, a, tm, tn);
 }
 
-static int bgs_roles() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("PARROT_GEMM_SPLIT_ROLES");
-        v = e ? atoi(e) : 1;
-    }
-    return v;
-}
-
-template <bool AX, bool BX, int ROLES>
-static void bgs_go2(const BgArgs& a, dim3 grid, int vecA, int vecB, int tm, int tn, int zmap, hipStream_t stream) {
-    static bool done = false;
-    bg_big_lds_once(bgs_kernel<AX, BX, ROLES>, done);
-    const size_t lds = (size_t)4 * (BgsOperand<AX>::SZ + BgsOperand<BX>::SZ);
-    hipLaunchKernelGGL((bgs_kernel<AX, BX, ROLES>), grid, dim3(512), lds, stream, a, vecA, vecB, tm, tn, zmap);
-}
-
 template <bool AX, bool BX>
 static void bgs_go(const BgArgs& a, dim3 grid, int vecA, int vecB, int tm, int tn, int zmap, hipStream_t stream) {
-    if (bgs_roles()) bgs_go2<AX, BX, 1>(a, grid, vecA, vecB, tm, tn, zmap, stream);
-    else bgs_go2<AX, BX, 0>(a, grid, vecA, vecB, tm, tn, zmap, stream);
+    static bool done = false;
+    bg_big_lds_once(bgs_kernel<AX, BX>, done);
+    const size_t lds = (size_t)4 * (BgsOperand<AX>::SZ + BgsOperand<BX>::SZ);
+    hipLaunchKernelGGL((bgs_kernel<AX, BX>), grid, dim3(512), lds, stream, a, vecA, vecB, tm, tn, zmap);
 }
 
 int bg_to_bf16_launch(const float* x, void* y, long long n, hipStream_t stream) {
@@ -983,7 +811,6 @@ int bg_launch(const BgArgs& a, hipStream_t stream) {
     const int vecB = bxc ? al(a.B, a.sbk, a.batchB) : al(a.B, a.sbn, a.batchB);
     const int tiles_m = ceil_div(a.M, BM), tiles_n = ceil_div(a.N, BN);
     dim3 grid(tiles_m * tiles_n, a.nbatch * a.splitk);
-    dim3 block(256);
     if (a.bf16 == 2) {  // operands ARE bf16 in memory (strides in bf16 elements): bgh_kernel, any "one stride is 1" layout
         if (a.act || a.gate || ((uintptr_t)a.A & 15) || ((uintptr_t)a.B & 15) || (a.batchA & 7) || (a.batchB & 7))
             return PH_ERR_UNSUPPORTED;
@@ -1029,18 +856,10 @@ int bg_launch(const BgArgs& a, hipStream_t stream) {
         else hipLaunchKernelGGL((bg_kernel_bf16<false, false>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
         return (int)hipGetLastError();
     }
-    constexpr bool w8 = true;  // measured on MI355X: 113-124 TFLOP/s vs 87-102 for the 4-wave kernel (kept below for reference)
-    if (w8) {
-        dim3 b8(512);
-        if (axc && bxc) hipLaunchKernelGGL((bg_kernel8<true, true>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-        else if (axc && !bxc) hipLaunchKernelGGL((bg_kernel8<true, false>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-        else if (!axc && bxc) hipLaunchKernelGGL((bg_kernel8<false, true>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-        else hipLaunchKernelGGL((bg_kernel8<false, false>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-        return (int)hipGetLastError();
-    }
-    if (axc && bxc) hipLaunchKernelGGL((bg_kernel<true, true>), grid, block, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-    else if (axc && !bxc) hipLaunchKernelGGL((bg_kernel<true, false>), grid, block, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-    else if (!axc && bxc) hipLaunchKernelGGL((bg_kernel<false, true>), grid, block, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
-    else hipLaunchKernelGGL((bg_kernel<false, false>), grid, block, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
+    const dim3 b8(512);
+    if (axc && bxc) hipLaunchKernelGGL((bg_kernel8<true, true>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
+    else if (axc && !bxc) hipLaunchKernelGGL((bg_kernel8<true, false>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
+    else if (!axc && bxc) hipLaunchKernelGGL((bg_kernel8<false, true>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
+    else hipLaunchKernelGGL((bg_kernel8<false, false>), grid, b8, pad, stream, a, vecA, vecB, tiles_m, tiles_n);
     return (int)hipGetLastError();
 }

@@ -5,14 +5,13 @@
 #include "elementwise.h"
 #include "quantize.h"
 #include "skinny.h"
+#include "switches.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
-#include <map>
-#include <mutex>
 
 static int gemm_target_wgs() {
     return 1024;  // 8-wave kernel: 1024..4096 measure the same; fewer slices = less partial-sum traffic
@@ -22,7 +21,7 @@ static int gemm_target_wgs() {
 // (PARROT_PRECISION_BF16X3: f32 operands, f32-grade results, 1.7-1.9 x the f32-input MFMA kernel's rate);
 // PARROT_GEMM_PRECISION=f32 in the environment restores the f32-input matrix instructions for everything.
 static int gemm_default_mode() {
-    const char* e = getenv("PARROT_GEMM_PRECISION");
+    const char* e = env_str("PARROT_GEMM_PRECISION");
     if (e && (!strcmp(e, "f32") || !strcmp(e, "0"))) return PARROT_PRECISION_F32;
     if (e && (!strcmp(e, "bf16") || !strcmp(e, "1"))) return PARROT_PRECISION_BF16;
     return PARROT_PRECISION_BF16X3;
@@ -57,31 +56,9 @@ long long parrot_profile_end2(double* total_us, double* flops, double* bytes, do
     return sk_profile_end2(total_us, flops, bytes, plain4);
 }
 
-// Split-K workspace, one per stream: products on different streams (the weight-gradient GEMMs that run beside the
-// backward scan, model.py's _backward) never share partial tiles.  Grows on demand, reused by later calls in stream
-// order.  Under stream capture (or when the memory cannot be had) there is none and the product runs unsplit, so no
-// graph ever holds a pointer into a workspace that a later, larger call may replace.
-static float* bg_workspace(hipStream_t st, size_t need) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cs);
-    if (cs != hipStreamCaptureStatusNone) return nullptr;
-    struct Ws { float* p; size_t floats; };
-    static std::mutex ws_mu;
-    static std::map<hipStream_t, Ws> ws_of;
-    std::lock_guard<std::mutex> lock(ws_mu);
-    Ws& w = ws_of[st];
-    if (need > w.floats) {
-        if (w.p) {
-            (void)hipStreamSynchronize(st);
-            (void)hipFree(w.p);
-            w.p = nullptr;
-            w.floats = 0;
-        }
-        if (hipMalloc(&w.p, need * sizeof(float)) == hipSuccess) w.floats = need;
-        else w.p = nullptr;
-    }
-    return (w.p && need <= w.floats) ? w.p : nullptr;
-}
+// Split-K workspace (products on different streams -- the weight-gradient GEMMs that run beside the backward scan,
+// model.py's _backward -- never share partial tiles).  Where there is none the product runs unsplit.
+static StreamScratch bg_workspace(0);
 
 // Auto split-K, the deterministic split-K workspace and the launch of one batched product (shared by parrot_gemm and
 // parrot_gemm_bf16in).
@@ -135,7 +112,7 @@ static int bg_run(BgArgs a, int split_k, hipStream_t st) {
         // them in slice order (results do not depend on scheduling).  The workspace grows on demand and is reused by
         // later calls in stream order.  Under stream capture or when the workspace cannot be had, the product runs
         // unsplit instead: there is no float-atomic combine any more.
-        float* ws = bg_workspace(st, (size_t)nbatch * a.splitk * M * N);
+        float* ws = bg_workspace.get(st, (size_t)nbatch * a.splitk * M * N);
         if (ws) {
             a.ws = ws;
             a.bias = nullptr;  // the reducer adds it

@@ -2,6 +2,49 @@
 #pragma once
 #include "common.h"
 
+#include <map>
+#include <mutex>
+
+// Library-owned scratch, ONE BUFFER PER STREAM (work on different streams runs concurrently and must not share
+// partials), grown on demand to at least min_floats and reused by later calls in stream order.  get() returns null
+// under stream capture -- no captured graph ever holds a pointer into a buffer that a later, larger call replaces -- and
+// when the memory cannot be had.  Growing synchronises the stream and frees the old buffer first.  (Internal to each
+// source file that keeps one: the library exports its C ABI only.)
+namespace {
+class StreamScratch {
+  public:
+    explicit StreamScratch(size_t min_floats) : min_floats_(min_floats) {}
+    float* get(hipStream_t stream, size_t floats) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        (void)hipStreamIsCapturing(stream, &cs);
+        if (cs != hipStreamCaptureStatusNone) return nullptr;
+        std::lock_guard<std::mutex> lock(mu_);
+        Buf& b = bufs_[stream];
+        if (floats > b.cap) {
+            if (b.p) {
+                (void)hipStreamSynchronize(stream);
+                (void)hipFree(b.p);
+                b.p = nullptr;
+                b.cap = 0;
+            }
+            const size_t want = floats < min_floats_ ? min_floats_ : floats;
+            if (hipMalloc(&b.p, want * sizeof(float)) != hipSuccess) {
+                b.p = nullptr;
+                return nullptr;
+            }
+            b.cap = want;
+        }
+        return b.p;
+    }
+
+  private:
+    struct Buf { float* p = nullptr; size_t cap = 0; };
+    const size_t min_floats_;
+    std::mutex mu_;
+    std::map<hipStream_t, Buf> bufs_;
+};
+}  // namespace
+
 struct GruStateBwdChain {
     const float* dh;     // [B,H] gradient wrt h_t
     const float* dh2;    // [B,H] optional second share of it (from the layers above) or null

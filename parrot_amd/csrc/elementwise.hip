@@ -5,9 +5,6 @@
 //    Blocks StepClipping -> Adam, Appendix A.1 of SURVEY.md)
 #include "elementwise.h"
 
-#include <map>
-#include <mutex>
-
 namespace {
 
 // dh: total gradient wrt h_t. Emits dC = dh*z*(1-c^2), dGz = dh*(c-hp)*z*(1-z),
@@ -296,31 +293,9 @@ __global__ __launch_bounds__(256) void norm_sum_kernel(const NormSumArgs a, floa
 
 }  // namespace
 
-// Library-owned scratch for the two-stage reductions, ONE PER STREAM (grown on demand; never from inside a captured scan
-// plan): since round 4 the encoder's backward runs on a side stream beside the weight-gradient products of the main
-// stream, and both take column sums -- a shared buffer would have the two finish passes read each other's partials.
-static float* ew_scratch(size_t floats, hipStream_t stream) {
-    struct Buf { float* p = nullptr; size_t cap = 0; };
-    static std::mutex mu;
-    static std::map<hipStream_t, Buf> bufs;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cs);
-    if (cs != hipStreamCaptureStatusNone) return nullptr;
-    std::lock_guard<std::mutex> lock(mu);
-    Buf& b = bufs[stream];
-    if (floats > b.cap) {
-        if (b.p) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipFree(b.p);
-            b.p = nullptr;
-            b.cap = 0;
-        }
-        const size_t want = floats < (1u << 20) ? (1u << 20) : floats;
-        if (hipMalloc(&b.p, want * sizeof(float)) != hipSuccess) return nullptr;
-        b.cap = want;
-    }
-    return b.p;
-}
+// Partials of the two-stage reductions (never from inside a captured scan plan): since round 4 the encoder's backward
+// runs on a side stream beside the weight-gradient products of the main stream, and both take column sums.
+static StreamScratch ew_scratch(1u << 20);
 
 
 int norm_sum_launch(const NormSumGroup* groups, int ngroups, int R, float eps, hipStream_t stream) {
@@ -381,7 +356,7 @@ int colsum_launch(const float* x, long long M, int N, int ld, float* out, int ac
         // one workgroup per CU: more row slices only lengthen the serial finish pass (8 column blocks x 128 slices
         // measured 19 us + 33 us of finish for [51200, 2048]; 32 slices: the finish reads a quarter)
         while (bx * ysplit < 256 && M / (ysplit * 2) >= 64) ysplit *= 2;
-        float* part = ysplit > 1 ? ew_scratch((size_t)ysplit * N, stream) : nullptr;
+        float* part = ysplit > 1 ? ew_scratch.get(stream, (size_t)ysplit * N) : nullptr;
         if (ysplit == 1 || part) {
             hipLaunchKernelGGL(colsum4_kernel, dim3(bx, ysplit), dim3(256), 0, stream, x, M, N, ld, ysplit > 1 ? part : out,
                                accumulate);
@@ -395,7 +370,7 @@ int colsum_launch(const float* x, long long M, int N, int ld, float* out, int ac
     const int bx = ceil_div(N, 64);
     while (bx * ysplit < 512 && M / (ysplit * 2) >= 256) ysplit *= 2;
     if (ysplit > 1) {  // row slices -> partial sums -> fixed-order finish (deterministic, no float atomics)
-        float* part = ew_scratch((size_t)ysplit * N, stream);
+        float* part = ew_scratch.get(stream, (size_t)ysplit * N);
         if (!part) ysplit = 1;
         else {
             hipLaunchKernelGGL(colsum_kernel, dim3(bx, ysplit), dim3(256), 0, stream, x, M, N, ld, part, 0);
@@ -413,7 +388,7 @@ int sumsq_launch(const float* x, size_t n, float* out, hipStream_t stream) {
     int bx = (int)((n / 4 + 255) / 256);
     if (bx < 1) bx = 1;
     if (bx > 2048) bx = 2048;
-    float* part = ew_scratch((size_t)bx, stream);
+    float* part = ew_scratch.get(stream, (size_t)bx);
     if (!part) return PH_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(sumsq_kernel, dim3(bx), dim3(256), 0, stream, x, n, part);
     hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, stream, part, bx, out);

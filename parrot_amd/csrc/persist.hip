@@ -1,5 +1,6 @@
 // Persistent phase machine for the decoder scan (see persist.h).  gfx950 only.
 #include "persist.h"
+#include "switches.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -814,7 +815,7 @@ int pm_status(const PmProgram& P) {
     PH_CHECK(hipMemcpy(&w, P.sync + PM_S_STICKY, sizeof(w), hipMemcpyDeviceToHost));
     if (w) {
         fprintf(stderr, "[parrot_amd] persistent launch gave up: sticky word 0x%x (site %u)\n", w, w & 15u);
-        if (getenv("PARROT_PM_DUMP_PLAN")) {  // development aid: the barrier words of the launch that gave up
+        if (sw_pm_dump_plan()) {  // development aid: the barrier words of the launch that gave up
             unsigned h[PM_SYNC_WORDS];
             if (hipMemcpy(h, P.sync, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
                 fprintf(stderr, "  nwg %d n_ticks %d n_slots %d  TOP %u TOTAL %u ABORT %u\n", P.nwg, P.n_ticks, P.n_slots, h[PM_S_TOP],

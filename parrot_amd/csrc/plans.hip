@@ -3,6 +3,7 @@
 // fused step kernels, captured once into a hipGraph and replayed per window (all pointers in a
 // plan are fixed, so a replay costs one hipGraphLaunch instead of thousands of host launches).
 #include "plans_common.h"
+#include "switches.h"
 
 namespace {
 
@@ -19,8 +20,7 @@ struct GruSeqPlan : PlanBase {
         if (tiled) (void)hipFree(tiled);
     }
     int setup_rowwise() {
-        const char* e = getenv("PARROT_GRU_ROWWISE");
-        rowwise = rowgru_supported(d.T, d.B, d.H, d.nchain) && !(e && atoi(e) == 0);
+        rowwise = rowgru_supported(d.T, d.B, d.H, d.nchain) && env_int("PARROT_GRU_ROWWISE", 1) != 0;
         for (int ch = 0; ch < d.nchain && rowwise; ++ch)  // (the tiling kernel wants 16-byte aligned matrices)
             if (!d.Wg[ch] || !d.Wc[ch] || ((uintptr_t)d.Wg[ch] & 15) || ((uintptr_t)d.Wc[ch] & 15)) rowwise = false;
         if (!rowwise) return 0;
@@ -228,8 +228,7 @@ struct DecoderPlan : PlanBase {
     }
 
     void choose_schedule() {
-        const char* e = getenv("PARROT_SCHEDULE");
-        int want = e ? atoi(e) : -1;
+        int want = env_int("PARROT_SCHEDULE", -1);
         bool pipe_ok = d.L >= 2;
         for (int l = 1; l < d.L; ++l)
             if (!d.seq_g[l] || (d.cell == 0 && !d.seq_c[l])) pipe_ok = false;
@@ -257,8 +256,8 @@ struct DecoderPlan : PlanBase {
         if (want >= 5 && d.layer_norm) want = 0;
         schedule = want;
         try_persist = want_persist && d.cell == 0 && !d.layer_norm && !d.bf16;
-        const char* c = getenv("PARROT_CHUNK");  // (tests: several chunks and a ragged last one on short windows)
-        if (c && atoi(c) > 0) chunk = atoi(c);
+        const int c = env_int("PARROT_CHUNK", 0);  // (tests: several chunks and a ragged last one on short windows)
+        if (c > 0) chunk = c;
     }
 
 
@@ -350,13 +349,6 @@ struct DecoderPlan : PlanBase {
             return q;
         };
 
-        // When the chip's LDS (nwg x PM_LDS_W) cannot hold all weights, some input-projection pieces are streamed:
-        // cut the H-row pieces in halves then (see above).
-        long long all_rows = 0;
-        for (int l = 0; l < L; ++l) all_rows += (long long)krows(l) * 3 * H / 16;
-        // (measured at cfg2: halves do not pay -- every unit carries ~3.5 us of fixed latency -- so off unless asked for)
-        const bool stream_split = false;
-        (void)all_rows;
         std::vector<PmReq> reqs;
         typedef PmReq Req;
         auto rm = [](float* p, long long st, int ld) { PmRM r; r.p = p; r.st = st; r.ld = ld; r.pad = 0; return r; };
@@ -411,13 +403,9 @@ struct DecoderPlan : PlanBase {
                     struct Piece { int c0, K; };
                     std::vector<Piece> pieces;
                     pieces.push_back({0, E});
-                    for (int j = 0; j < l; ++j) {
-                        const int cj = E / 16 + j * (H / 16);
-                        const bool split = stream_split && l >= 2 && (H % 32 == 0) &&
-                                           (int)pieces.size() + 2 <= PERSIST_MAXPIECES - (l - 1 - j);
-                        if (split) { pieces.push_back({cj, H / 2}); pieces.push_back({cj + H / 32, H / 2}); }
-                        else pieces.push_back({cj, H});
-                    }
+                    // (one piece per lower layer: halves of them measured slower at cfg2 -- every unit carries ~3.5 us of
+                    // fixed latency)
+                    for (int j = 0; j < l; ++j) pieces.push_back({E / 16 + j * (H / 16), H});
                     int na = 0;
                     for (size_t pi = 0; pi < pieces.size(); ++pi) {
                         Req qi;
@@ -466,10 +454,7 @@ struct DecoderPlan : PlanBase {
         a.wdst[a.nwdst++] = mkdst(XC[0], 1, kx[0], H / 16);
         for (int l = 1; l < L; ++l) a.wdst[a.nwdst++] = mkdst(XI[l], 0, ki[l], 0);  // ... and for the layers above
         a.B = B; a.H = H; a.A = d.A; a.U = d.U; a.E = E; a.att_type = d.att_type;
-        {
-            const char* e = getenv("PARROT_ATT_DENSE");
-            a.dense = e ? atoi(e) : 0;
-        }
+        a.dense = sw_att_dense();
         a.eps = d.eps; a.alignment = d.alignment; a.sharpening = d.sharpening; a.timing = d.timing;
         int ni = 0;
         auto add_init = [&](const float* src, int ld, int K, float* slab, long long kslab, int chunk) {
@@ -483,10 +468,7 @@ struct DecoderPlan : PlanBase {
         P.ninit = ni;
         // dataflow mode: everything a unit reads from another workgroup starts EMPTY (slot 0 of the histories is the
         // caller's: the states entering the window)
-        {
-            const char* e = getenv("PARROT_PM_DATAFLOW");
-            P.dataflow = e ? atoi(e) : 0;
-        }
+        P.dataflow = sw_pm_dataflow(0);
         auto add_fill = [&](void* q, long long nfloats) {
             if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
         };
@@ -645,8 +627,6 @@ struct DecoderPlan : PlanBase {
     //   C: attention(q) + input projections of layer l for step q - l (all l >= 1)
     // The pre-activation of an upper layer is now (recurrent sum) + (input sum) instead of one running sum over the
     // concatenated K: same terms, other rounding (not bit-identical to schedule 0; the oracle tests cover both).
-    int esplit5 = 1;
-    bool s5_split = true;  // LSTM input projections of l >= 2 as two K-balanced jobs (false: one job; measured slower)
     int lag5(int l) const { return l == 0 ? 0 : l + 1; }
     int nticks5() const { return d.T + lag5(d.L - 1); }
     // part 0: the whole projection; 1: the rows of w and h_0 .. h_{l-2} (ready a tick earlier); 2: the rows of h_{l-1},
@@ -674,21 +654,20 @@ struct DecoderPlan : PlanBase {
     // before the rows of h_{l-1}, rides in the gate launch (the gate block) and the candidate launch (the candidate block) of
     // the tick in between -- both are 1.5 rounds there and take the extra half round for nothing --, part 2 = the rows of
     // h_{l-1} stays in the attention launch and accumulates.  No job of a tick walks more than K = H + E.
-    bool s5_gru_split = true;
     // Round 6: the rows of w of an upper layer's input projection (K = E) ride in that layer's OWN gate / candidate job (a
     // second segment behind the recurrent block: w_{t+1} is two ticks old by then) instead of the attention launch's
     // projection jobs.  At two layers the gate launch holds K = H + E (layer 0) beside K = H (layer 1) workgroups, one per
     // CU, and the candidate launch likewise: the upper layers' workgroups walk the extra E rows while layer 0's are still
     // busy, and the attention launch -- bound by its GEMM workgroups since the attention chain shrank -- walks K = l H
     // instead of E + l H.
-    bool s5_w_in_step = getenv("PARROT_S5_WSTEP") ? atoi(getenv("PARROT_S5_WSTEP")) != 0 : true;
+    bool s5_w_in_step = env_int("PARROT_S5_WSTEP", 1) != 0;
     int fwd5(hipStream_t st) {
         const int Q = nticks5();
         const int cfull = 160;  // workgroup count at which the heterogeneous launch keeps 32 x 32 tiles (measured)
         // launches of a tick: <= L gate jobs (+ part 1 of the upper layers' gate projections), <= L candidate jobs (+ part 1
         // of the candidate projections), <= 3 input-projection jobs per upper layer
         static_assert(3 * (PARROT_MAX_LAYERS - 1) <= SK_MAXJOB && 2 * PARROT_MAX_LAYERS - 2 <= SK_MAXJOB, "fwd5: jobs[] too short");
-        const bool gsplit = d.cell == 0 && s5_gru_split && d.L >= 3;
+        const bool gsplit = d.cell == 0 && d.L >= 3;
         const bool wstep = s5_w_in_step;
         for (int q = 0; q < Q; ++q) {
             SkJob jobs[SK_MAXJOB];
@@ -726,7 +705,8 @@ struct DecoderPlan : PlanBase {
             n = 0;
             for (int l = 1; l < d.L; ++l) {
                 const int t = q - lag5(l) + 1;
-                const bool split = d.cell == 1 && l >= 2 && s5_split;
+                // LSTM input projections of l >= 2 as two K-balanced jobs (one job measured slower)
+                const bool split = d.cell == 1 && l >= 2;
                 const bool gs = gsplit && l >= 2;  // (part 1 was written by the gate / candidate launches of this tick)
                 if (t >= 0 && t < d.T) {
                     input_job(jobs[n++], l, t, 0, (split || gs) ? 2 : 0, wstep);
@@ -739,7 +719,7 @@ struct DecoderPlan : PlanBase {
             }
             if (q < d.T) {
                 AttFwdArgs ag = att_fwd_args(q);
-                if (n > 0) ag.esplit = esplit5;  // beside GEMM workgroups: one attention workgroup per batch row (measured)
+                if (n > 0) ag.esplit = 1;  // beside GEMM workgroups: one attention workgroup per batch row (measured)
                 PL_TRY(launch_jobs_att(jobs, n, ag, st, cfull));
             } else if (n > 0) PL_TRY(launch_jobs(jobs, n, st, full_wgs));
         }
@@ -798,7 +778,6 @@ struct DecoderPlan : PlanBase {
     // Gradient contributions that cross layers land in separate buffers (dhup[l] for the state, dw0
     // for layer 0's share of dw), so no two jobs of a launch update the same element: no atomics, and
     // the result is deterministic.  The consumers add the parts when they read.
-    bool bwd_split = true;  // false: the dC products stay in the Y launch (K = 3H jobs), as before round 3
     // schedule 7 with bf16 operands: the backward tick of LSTM layers as ONE launch (skinny.hip wkb_kernel); bwd_flags =
     // [ticks x 4 chains] arrival counters, plan-owned, zeroed at the head of the backward scan
     unsigned* att_flags = nullptr;  // [T + 2] arrival counters, one per tick (plan-owned, zeroed at the head of the scan)
@@ -958,43 +937,39 @@ struct DecoderPlan : PlanBase {
                     j.M = d.B; j.N = H; j.H = H; j.epi = SK_EPI_LINEAR; j.accumulate = 1;
                     j.out = d.dh[l] + t * BH; j.ldo = H;
                 }
-                // The products with dC (K = H) do not need the X launch's dG_r: with bwd_split they ride in the X launch
-                // and the Y launch keeps the dG products (K = 2H) only, so no workgroup of a tick walks K = 3H any more
-                // (a launch costs ~4.7 us + ~4.8 us per 1024 of its LONGEST K: 12.0 + 7.9 + 19.9 -> 12.0 + 9.5 + 14.3 us).
+                // The products with dC (K = H) do not need the X launch's dG_r: since round 3 they ride in the X launch and
+                // the Y launch keeps the dG products (K = 2H) only, so no workgroup of a tick walks K = 3H any more (a launch
+                // costs ~4.7 us + ~4.8 us per 1024 of its LONGEST K: 12.0 + 7.9 + 19.9 -> 12.0 + 9.5 + 14.3 us).
                 {   // attention context
                     float* out = (l == 0 ? d.dw0 + (size_t)t * BE : d.dw + (size_t)(t + 1) * BE);
                     SkJob& j = jy[ny++];
                     sk_job_init(j);
-                    j.nseg = bwd_split ? 1 : 2;
+                    j.nseg = 1;
                     j.seg[0] = rseg(dG, l, 0, H, 2 * H);
                     j.seg[1] = rseg(dC, l, 1, H, H);
                     j.M = d.B; j.N = E; j.H = H; j.epi = SK_EPI_LINEAR; j.accumulate = 1;
                     j.out = out; j.ldo = E;
-                    if (bwd_split) {
-                        SkJob& k = jx[nx++];
-                        sk_job_init(k);
-                        k.nseg = 1;
-                        k.seg[0] = rseg(dC, l, 1, H, H);
-                        k.M = d.B; k.N = E; k.H = H; k.epi = SK_EPI_LINEAR; k.accumulate = 1;
-                        k.out = out; k.ldo = E;
-                    }
+                    SkJob& k = jx[nx++];
+                    sk_job_init(k);
+                    k.nseg = 1;
+                    k.seg[0] = rseg(dC, l, 1, H, H);
+                    k.M = d.B; k.N = E; k.H = H; k.epi = SK_EPI_LINEAR; k.accumulate = 1;
+                    k.out = out; k.ldo = E;
                 }
                 for (int p = 0; p < l; ++p) {  // lower layers' states of the same step
                     SkJob& j = jy[ny++];
                     sk_job_init(j);
-                    j.nseg = bwd_split ? 1 : 2;
+                    j.nseg = 1;
                     j.seg[0] = rseg(dG, l, 0, H + E + p * H, 2 * H);
                     j.seg[1] = rseg(dC, l, 1, H + E + p * H, H);
                     j.M = d.B; j.N = H; j.H = H; j.epi = SK_EPI_LINEAR; j.accumulate = 1;
                     j.out = d.dhup[p] + (t + 1) * BH; j.ldo = H;  // separate buffer: no two jobs share a tile
-                    if (bwd_split) {
-                        SkJob& k = jx[nx++];
-                        sk_job_init(k);
-                        k.nseg = 1;
-                        k.seg[0] = rseg(dC, l, 1, H + E + p * H, H);
-                        k.M = d.B; k.N = H; k.H = H; k.epi = SK_EPI_LINEAR; k.accumulate = 1;
-                        k.out = d.dhup[p] + (t + 1) * BH; k.ldo = H;
-                    }
+                    SkJob& k = jx[nx++];
+                    sk_job_init(k);
+                    k.nseg = 1;
+                    k.seg[0] = rseg(dC, l, 1, H + E + p * H, H);
+                    k.M = d.B; k.N = H; k.H = H; k.epi = SK_EPI_LINEAR; k.accumulate = 1;
+                    k.out = d.dhup[p] + (t + 1) * BH; k.ldo = H;
                 }
             }
             if (ga.nchain == 0) continue;
@@ -1464,16 +1439,14 @@ int parrot_decoder_create(const ParrotDecoderDesc* desc, void** plan) { PH_ENTRY
     if (p->schedule == 7) {
         // bf16 operands: only the wide step kernel takes a launch with a waiting job (skinny.hip wk_try_launch): every
         // launch of the scan must qualify, the first tick's (layer 0 alone) included.  f32 operands run on ska_kernel.
-        const bool ok = p->tiled && desc->B <= 64 && (desc->bf16 ? sk_wide_takes(desc->B, 4 * desc->H, desc->H, desc->E)
-                                                                 : getenv("PARROT_SCHEDULE") != nullptr);
+        // (f32 operands reach schedule 7 only when PARROT_SCHEDULE asks for it: choose_schedule)
+        const bool ok = p->tiled && desc->B <= 64 && (!desc->bf16 || sk_wide_takes(desc->B, 4 * desc->H, desc->H, desc->E));
         if (!ok) p->schedule = 0;
     }
     if (p->schedule == 5 && desc->L < 2) p->schedule = 0;
-    p->bwd_split = true;                      // the dC products ride in the X launch of the backward tick (round 3)
-    p->esplit5 = 1; p->s5_split = true;       // schedule 5: one attention block per row, layer >= 2 projections in two jobs
     if (p->schedule == 7) {
         if (hipMalloc(&p->att_flags, sizeof(unsigned) * (size_t)(desc->T + 2)) != hipSuccess) {
-            if (!getenv("PARROT_TRACE_ONLY")) {  // (schedule tracing on a box without a GPU: a placeholder address)
+            if (!env_set("PARROT_TRACE_ONLY")) {  // (schedule tracing on a box without a GPU: a placeholder address)
                 delete p;
                 return PARROT_ERR_BADARG;
             }
@@ -1498,9 +1471,8 @@ int parrot_decoder_create(const ParrotDecoderDesc* desc, void** plan) { PH_ENTRY
     }
     if (p->try_persist) p->build_persist();  // persist_ok stays false when the shape / workspace does not qualify
     {   // the K-balanced backward tick (bwd8): 2-layer f32 GRU decoders with fragment-major weights and all accumulators
-        const char* e = getenv("PARROT_BWD_HETERO");
         bool ok = desc->cell == 0 && (desc->L == 2 || desc->L == 3) && !desc->bf16 && !desc->layer_norm && p->tiled && desc->B <= 64 &&
-                  desc->dw_b && desc->dw_c && desc->dw0_b && desc->dw0_c && (e ? atoi(e) != 0 : true);
+                  desc->dw_b && desc->dw_c && desc->dw0_b && desc->dw0_c && env_int("PARROT_BWD_HETERO", 1) != 0;
         for (int l = 0; l < desc->L; ++l)
             if (!desc->dh_b[l] || (l + 1 < desc->L && (!desc->dhup_b[l] || !desc->dhup_c[l]))) ok = false;
         p->bwd_hetero = ok;

@@ -3,6 +3,7 @@
 // 2L + 2 phases with every product cut along K by the age of its operands (round 4), 2L + 1 with the fed-back frame out
 // of the step's dependency chain (round 5).  The planner, its symbolic checker and the parrot_sample_* entry points.
 #include "plans_common.h"
+#include "switches.h"
 
 namespace {
 
@@ -58,8 +59,7 @@ struct SamplePlan : PlanBase {
 
     int build_persist() {
         persist_ok = false;
-        const char* e = getenv("PARROT_SAMPLE_PERSIST");
-        if (e && atoi(e) == 0) return 0;
+        if (env_int("PARROT_SAMPLE_PERSIST", 1) == 0) return 0;
         if (!persist_eligible(d) || !d.persist_ws) return 0;
         if (pieces_wanted(d)) {  // the step cut along K by the age of its operands (below); else the 2L + 3 whole-K phases
             build_persist_pieces(false, 0);
@@ -228,10 +228,7 @@ struct SamplePlan : PlanBase {
             add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)((kx[l] - 64) / 16));
         }
         P.ninit = ni;
-        {
-            const char* e2 = getenv("PARROT_PM_DATAFLOW");
-            P.dataflow = e2 ? atoi(e2) : 0;
-        }
+        P.dataflow = sw_pm_dataflow(0);
         auto add_fill = [&](void* q, long long nfloats) {
             if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
         };
@@ -285,8 +282,7 @@ struct SamplePlan : PlanBase {
            RES_PART = 100 };
     // Round 5: the attention projection folded into layer 0's candidate units (PmUnit::pw / pp, persist.hip)
     static bool attfold_wanted(const ParrotSampleDesc& d) {
-        const char* e = getenv("PARROT_PM_ATTFOLD");
-        return d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && !(e && atoi(e) == 0);
+        return d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && env_int("PARROT_PM_ATTFOLD", 1) != 0;
     }
     bool pieces_ok = false;
     bool fbc_on = false;
@@ -296,8 +292,7 @@ struct SamplePlan : PlanBase {
     // The output product then feeds nothing inside the loop: it runs beside the next step's gate phase, and a step is
     // 2L + 1 dependent phases (G_0 with K = H critical instead of K = 64, but one phase of ~5 us less).
     static bool fbc_wanted(const ParrotSampleDesc& d) {
-        const char* e = getenv("PARROT_PM_FBC");
-        if (e && atoi(e) == 0) return false;
+        if (env_int("PARROT_PM_FBC", 1) == 0) return false;
         if (d.L < 2 || !d.Wgx_t[0] || !d.Wcx_t[0] || !fb_rows(d, 0)) return false;
         for (int l = 1; l < d.L; ++l)
             if (fb_rows(d, l)) return false;
@@ -311,8 +306,7 @@ struct SamplePlan : PlanBase {
     static int slotG(int l) { return l == 0 ? 0 : 2 * l + 1; }
     static int slotC(int l) { return slotG(l) + 1; }
     static bool pieces_wanted(const ParrotSampleDesc& d) {
-        const char* e = getenv("PARROT_PM_PIECES");
-        return d.Wro_t && d.ro_const && !(e && atoi(e) == 0) && 2 * d.L + 2 <= PM_MAXSLOTS;
+        return d.Wro_t && d.ro_const && env_int("PARROT_PM_PIECES", 1) != 0 && 2 * d.L + 2 <= PM_MAXSLOTS;
     }
     static bool piece_groups(const ParrotSampleDesc& d, std::vector<PmGroup>& gs, bool fbc) {
         const int H = d.H, E = d.E, L = d.L, n = n_phases(d, fbc), sATT = 2, sOUT = fbc ? 0 : 2 * L + 1;
@@ -728,7 +722,7 @@ struct SamplePlan : PlanBase {
         init.push_back(acc(RES_XG, 0, hc, ec));
         init.push_back(acc(RES_XC, 0, hc, ec));
         init.push_back(acc(RES_KAPPA, 0, 0, 1));
-        if (getenv("PARROT_PM_DUMP_PLAN"))
+        if (sw_pm_dump_plan())
             for (const PmGroup& g : gs)
                 for (const PmPiece& p : g.pc)
                     fprintf(stderr, "[pieces] %s%d phase %d: chunks %d..%d (K %d) %s phase %d lag %d\n",
@@ -795,8 +789,7 @@ struct SamplePlan : PlanBase {
             // no grid barriers by default: with the step cut into pieces a phase is ~3 us of fixed latency + a short K
             // walk, and the barrier was a quarter of it (43.0 -> 36.1 us per step at configs[2]); the whole-K plan above
             // measured no gain (57.6 either way).  Bit-identical to the barrier mode (tests/test_gpu_persist.py)
-            const char* e2 = getenv("PARROT_PM_DATAFLOW");
-            P.dataflow = e2 ? atoi(e2) : 1;
+            P.dataflow = sw_pm_dataflow(1);
         }
         auto add_fill = [&](void* q, long long nfloats) {
             if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }

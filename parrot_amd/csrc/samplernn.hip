@@ -18,6 +18,7 @@
 #include "biggemm.h"
 #include "skinny.h"
 #include "sr_persist.h"
+#include "switches.h"
 
 namespace {
 
@@ -462,7 +463,7 @@ struct SrPlan {
                     sa.next_add = d.big_out + (size_t)(f + 1) * D; sa.next_ld_add = nfr * D;
                 }
                 {
-                    static const int timing = getenv("PARROT_SR_TIMING") ? atoi(getenv("PARROT_SR_TIMING")) : 0;
+                    static const int timing = env_int("PARROT_SR_TIMING", 0);
                     sa.pad = timing;
                 }
                 SR_TRY(srp_launch(sa, st));

@@ -24,6 +24,7 @@
 #include "att_fwd_body.h"
 #include "att_bwd_body.h"
 #include "elementwise.h"
+#include "switches.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -1374,8 +1375,7 @@ __global__ __launch_bounds__(ATTB_THREADS) void wkb_kernel(const WkLaunch L, con
 // Would wk_try_launch take a bf16 launch whose jobs have M rows, ncols output columns in total and K segments of H and E
 // rows?  (plans.hip asks before it commits a plan to a schedule only the wide kernel can run.)
 bool sk_wide_takes(int M, int ncols, int H, int E) {
-    const char* e = getenv("PARROT_WK");
-    const int enabled = e ? atoi(e) : 1;
+    const int enabled = sw_wk();
     if (!enabled || M < 1 || M > 64 || (H % WK_STAGE) || (E % WK_STAGE)) return false;
     return ncols >= 4096 || enabled >= 2;
 }
@@ -1386,8 +1386,7 @@ bool sk_wide_takes(int M, int ncols, int H, int E) {
 // nlead = workgroups that lead the grid beside / before the wide ones (attention blocks, state-backward rows);
 // lead_waiters: some job waits for them (then the non-waiting jobs are sized to fit beside them).
 static bool wk_build(const SkLaunch& Lin, int nlead, bool has_lead, WkLaunch& W, int& t, bool& any_flag) {
-    const char* e = getenv("PARROT_WK");  // 0: never; 1 (default): launches with >= 4096 output columns; 2: whenever legal
-    const int enabled = e ? atoi(e) : 1;
+    const int enabled = sw_wk();  // 0: never; 1 (default): launches with >= 4096 output columns; 2: whenever legal
     if (!enabled) return false;
     long long work = 0;
     for (int q = 0; q < Lin.njobs; ++q) {

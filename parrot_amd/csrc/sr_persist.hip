@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "sr_common.h"
+#include "switches.h"
 
 namespace {
 
@@ -385,8 +386,7 @@ size_t srp_lds_bytes(int D) {
 
 bool srp_eligible(int B, int D, int Q, int FS) {
     static int cus = -1;
-    const char* e = getenv("PARROT_SR_PERSIST");
-    const int enabled = e ? atoi(e) : 1;
+    const int enabled = env_int("PARROT_SR_PERSIST", 1);
     if (cus < 0) {
         hipDeviceProp_t prop;
         int dev = 0;

@@ -21,6 +21,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .utils import env_int, env_str
+
 COST_EPS = 1e-5  # model.py:784
 
 
@@ -34,7 +36,7 @@ def _force_one_rank():
     """PARROT_DIST_FORCE=1: a ONE-rank process group counts as distributed -- every collective of the training step is issued
     (and is the identity).  The only way to drive the RCCL path of Trainer.step on a box with a single GPU
     (tests/test_gpu_dp.py::test_one_rank_rccl_trainer_step_equals_plain_step)."""
-    return os.environ.get("PARROT_DIST_FORCE", "0") == "1"
+    return env_int("PARROT_DIST_FORCE", 0) == 1
 
 
 def init_process_group(backend=None):
@@ -42,7 +44,7 @@ def init_process_group(backend=None):
     if (world > 1 or _force_one_rank()) and not dist.is_initialized():
         if backend is None:
             # PARROT_DIST_BACKEND=gloo: plumbing test of the N > 1 path on a box with fewer GPUs than ranks
-            backend = os.environ.get("PARROT_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
+            backend = env_str("PARROT_DIST_BACKEND") or ("nccl" if torch.cuda.is_available() else "gloo")
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
         if backend == "nccl":

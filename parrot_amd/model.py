@@ -23,7 +23,6 @@ from __future__ import annotations
 
 import collections
 import ctypes as C
-import os
 from collections import OrderedDict
 
 import numpy
@@ -32,6 +31,7 @@ import torch
 from . import _lib, ops
 from .bricks import Brick, Constant, IsotropicGaussian
 from .params import ParamStore
+from .utils import env_int
 
 floatX = "float32"
 
@@ -166,7 +166,7 @@ class Parrot(Brick):
         # distinct shapes a run sees.  Only the most recent compute_cost can have a backward pending (self._saved is
         # a single slot) and its encoder + decoder workspaces are the two most recently used entries, so an
         # eviction never touches a workspace that is still needed (cap >= 4).
-        cap = max(4, int(os.environ.get('PARROT_WS_CACHE', '6')))
+        cap = max(4, env_int('PARROT_WS_CACHE', 6))
         self._train_ws = _LRU(cap, self._evict_train_ws)
         self._sample_ws = _LRU(max(2, cap // 2), self._evict_sample_ws)
         self._carry = {}
@@ -539,7 +539,7 @@ class Parrot(Brick):
             ws['seq_' + key] = [torch.zeros(T, B, wd, **f) if (l in self._fb_layers or self.use_speaker or l >= 2)
                                 else None for l in range(1, L + 1)]
         if (not lstm and L in (2, 3) and not self.compute_bf16 and not self.layer_norm and B <= 64 and H % 16 == 0 and E % 16 == 0
-                and os.environ.get('PARROT_BWD_HETERO', '1') != '0'):
+                and env_int('PARROT_BWD_HETERO', 1) != 0):
             # second / third accumulators of the K-balanced backward tick (ParrotDecoderDesc::dh_b ... dw0_c, plans.hip bwd8)
             ws.update(dh_b=[torch.zeros(T + 1, B, H, **f) for _ in range(L)],
                       dhup_b=[torch.zeros(T + 1, B, H, **f) if l < L - 1 else None for l in range(L)],
@@ -593,7 +593,7 @@ class Parrot(Brick):
                     getattr(d, f'W{key}_r')[l] = tl[(l, key, 'r')].data_ptr()
         ws['att_sup'] = torch.zeros(T, B, 2, device=self._dev(), dtype=torch.int32)
         d.att_sup = ws['att_sup'].data_ptr()
-        if os.environ.get('PARROT_SCHEDULE', '') == '4' and tl is not None:
+        if env_int('PARROT_SCHEDULE', -1) == 4 and tl is not None:
             # persistent forward scan: zero-filled workspace for the machine's slabs / unit table / barrier words
             n = int(_lib.load().parrot_decoder_persist_floats(C.byref(d)))
             if n > 0:
@@ -606,7 +606,7 @@ class Parrot(Brick):
             d.dw_b, d.dw0_b = ws['dw_b'].data_ptr(), ws['dw0_b'].data_ptr()
         if 'dw_c' in ws:
             d.dw_c, d.dw0_c = ws['dw_c'].data_ptr(), ws['dw0_c'].data_ptr()
-        if lstm and self._bf16_weight_grads(0, T, T) and os.environ.get('PARROT_BF16_DG16', '1') != '0':
+        if lstm and self._bf16_weight_grads(0, T, T) and env_int('PARROT_BF16_DG16', 1) != 0:
             # the backward scan leaves the pre-activation gradients in bf16 too (ParrotDecoderDesc::dG16): no conversion
             # pass over 3 x [T,B,4H] floats before the weight-gradient products
             cp = self._bf16_copies(ws, T, B)
@@ -1081,12 +1081,12 @@ class Parrot(Brick):
         instead of rounding f32 operands inside the product.  Same rounding (nearest even) of the same values."""
         H, E = self.rnn_h_dim, self.encoded_input_dim
         return (self.compute_bf16 and not self.layer_norm and t0 == 0 and t1 == T and H % 8 == 0 and E % 8 == 0
-                and os.environ.get('PARROT_BF16_DW', '1') != '0')
+                and env_int('PARROT_BF16_DW', 1) != 0)
 
     def _bf16_readouts(self, T, R):
         """bf16-operand decoders whose readout stack (model.py:739-755) runs on bf16 copies (parrot_gemm_bf16in_ex)."""
         return (self._bf16_weight_grads(0, T, T) and R % 8 == 0 and not self.use_speaker
-                and os.environ.get('PARROT_BF16_READOUT', '1') != '0')
+                and env_int('PARROT_BF16_READOUT', 1) != 0)
 
     def _bf16_copies(self, ws, T, B, convert=()):
         """bf16 copies of the scan's histories (allocated once per workspace).  convert: 'h' / 'w' (state and context
@@ -1243,7 +1243,7 @@ class Parrot(Brick):
         # copies of the packed layer matrices with the fed-back-output rows appended (padded to 64 rows), of the
         # readout stack and of the output projection (63 -> 64 columns); sample_model_device refreshes them per call.
         if (not lstm and not gmm and not self.layer_norm and N <= 64 and H % 16 == 0 and E % 16 == 0 and R % 16 == 0
-                and O <= 64 <= ldx and os.environ.get('PARROT_SAMPLE_PERSIST', '1') != '0'):
+                and O <= 64 <= ldx and env_int('PARROT_SAMPLE_PERSIST', 1) != 0):
             pm = dict(cat={}, tiled={})
             for l in range(L):
                 fb = 64 if (l + 1) in self._fb_layers else 0
@@ -1264,14 +1264,14 @@ class Parrot(Brick):
             pm['Wro'], pm['Wro_t'] = torch.empty(L * H + E, 64, **f), torch.empty(L * H + E, 64, **f)
             pm['ro_const'] = torch.zeros(N, 64, **f)
             d.Wro_t, d.ro_const = pm['Wro_t'].data_ptr(), pm['ro_const'].data_ptr()
-            if N <= 16 and 3 * A <= 32 and os.environ.get('PARROT_PM_ATTFOLD', '1') != '0':
+            if N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
                 # round 5: the attention projection as an [H, 32] matrix (fragment-major): layer 0's candidate units fold
                 # their tile's share of h_1 . Watt into their epilogue (ParrotSampleDesc::Watt_t)
                 pm['Watt_pad'], pm['Watt_t'] = torch.zeros(H, 32, **f), torch.empty(H, 32, **f)
                 d.Watt_t = pm['Watt_t'].data_ptr()
             # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
             # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
-            if L >= 2 and self._fb_layers == [1] and os.environ.get('PARROT_PM_FBC', '1') != '0':
+            if L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
                 for key, wd, suf, mat, rec in self._groups:
                     rows = H + E + 64 + H
                     pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)

@@ -8,6 +8,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from .utils import env_int, env_str
 
 ACT_NONE, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 
@@ -137,8 +138,7 @@ PRECISION_F32, PRECISION_BF16, PRECISION_BF16X3 = 0, 1, 2
 
 
 def _default_full_precision() -> int:
-    import os
-    return PRECISION_F32 if os.environ.get("PARROT_GEMM_PRECISION", "") in ("f32", "0") else PRECISION_BF16X3
+    return PRECISION_F32 if env_str("PARROT_GEMM_PRECISION", "") in ("f32", "0") else PRECISION_BF16X3
 
 
 _FULL_PRECISION = _default_full_precision()
@@ -284,8 +284,7 @@ def _int32(t: torch.Tensor, name: str, bound=None) -> torch.Tensor:
     return t32
 
 
-import os as _os
-_SKIP_INDEX_CHECK = _os.environ.get("PARROT_SKIP_INDEX_CHECK", "0") not in ("", "0")
+_SKIP_INDEX_CHECK = env_int("PARROT_SKIP_INDEX_CHECK", 0) != 0
 
 
 class _EmbedSumFn(torch.autograd.Function):

@@ -10,6 +10,7 @@ import torch
 
 from . import dist as pdist
 from . import ops
+from .utils import env_int
 
 
 class Trainer:
@@ -18,11 +19,10 @@ class Trainer:
         """bucketed (default: PARROT_DP_BUCKETS != 0): the decoder's gradient sum in two buckets, the readout / output share
         overlapped with the backward scan (dist.GradientExchange).  allreduce_dtype='bf16' (default: PARROT_ALLREDUCE_BF16):
         bf16 on the wire, f32 master gradients (opt-in; changes the arithmetic)."""
-        import os
         self.parrot = parrot.allocate()
         if bucketed is None:
-            bucketed = os.environ.get('PARROT_DP_BUCKETS', '1') != '0'
-        if allreduce_dtype is None and os.environ.get('PARROT_ALLREDUCE_BF16', '0') != '0':
+            bucketed = env_int('PARROT_DP_BUCKETS', 1) != 0
+        if allreduce_dtype is None and env_int('PARROT_ALLREDUCE_BF16', 0) != 0:
             allreduce_dtype = 'bf16'
         wire = torch.bfloat16 if allreduce_dtype in ('bf16', 'bfloat16', torch.bfloat16) else None
         self._wire = wire

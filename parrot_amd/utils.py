@@ -10,9 +10,28 @@ from __future__ import annotations
 
 import argparse
 import os
+import re
 
 SPTK_DIR = '/data/lisatmp4/kumarkun/merlin/tools/bin/SPTK-3.9/'   # utils.py:20
 WORLD_DIR = '/data/lisatmp4/kumarkun/merlin/tools/bin/WORLD/'     # utils.py:21
+
+
+_ATOI = re.compile(r'[ \t\n\v\f\r]*([+-]?[0-9]+)')
+
+
+def env_int(name, default):
+    """Integer / on-off PARROT_* switch, parsed like the HIP library's (csrc/switches.h, the table of every switch): C's
+    atoi -- optional leading blanks and sign, then the leading digits, anything else 0 -- and `default` when unset."""
+    v = os.environ.get(name)
+    if v is None:
+        return default
+    m = _ATOI.match(v)
+    return int(m.group(1)) if m else 0
+
+
+def env_str(name, default=None):
+    """String-valued PARROT_* switch (paths, flags, backend names): the value as set, `default` when unset."""
+    return os.environ.get(name, default)
 
 
 def _results_dir():
