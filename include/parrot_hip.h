@@ -406,14 +406,20 @@ typedef struct ParrotSampleDesc {
     float* ln_scratch;
     long long ln_scratch_floats;
     /* Optional: decode on the persistent phase machine (parrot_amd/csrc/persist.h) -- the whole S-step loop as one
-     * resident kernel, 2L + 3 barrier-separated phases per step instead of 2L + 3 launches.  GRU layers, MSE head, no
+     * resident kernel, 2L + 3 barrier-separated phases per step instead of 2L + 3 launches.  MSE head, no
      * layer_norm, B <= 64, O <= 64 <= ldx.  The caller provides fragment-major copies (parrot_tile_weights, mode 0) of
      *   Wg_t[l] / Wc_t[l]: [K_l + F_l, 2H] / [K_l + F_l, H] = the packed layer matrix with the feedback rows Wfg / Wfc
      *                      appended and zero-padded to F_l = 64 rows (F_l = 0 without feedback into the layer),
      *   Wr_t: [L*H + E, R],   Wo_t: [R, 64] (columns >= O zero),
      * bo_pad [64] (zeros beyond O), oadd_pad [B, 64] when oadd is used, and a ZERO-FILLED workspace of
      * parrot_sample_persist_floats(desc) floats.  Anything missing or non-qualifying: the per-step launches run.
-     * The h ping-pong buffers keep the initial state (slot 0) only; PARROT_SAMPLE_PERSIST=0 disables the machine. */
+     * The h ping-pong buffers keep the initial state (slot 0) only; PARROT_SAMPLE_PERSIST=0 disables the machine.
+     * LSTM layers (cell = 1): Wg_t[l] is [K_l + F_l, 4H] = the packed 4H-wide layer matrix with the feedback rows Wfg
+     * appended (zero-padded to F_l = 64), fragment-major with gate-interleaved columns = parrot_tile_weights(.., mode 0,
+     * lstm_H = H); Wc_t is ignored; bg / seq_g stay in their natural [i | f | o | g] order.  Wro_t and ro_const (below) are
+     * required: a step is L + 2 whole-K phases (layer 0, attention, layers 1 .. L-1, composed output); Wr_t / Wo_t /
+     * bo_pad / oadd_pad / Wgx_t / Wcx_t / Watt_t are not used.  The machine reads slot 0 of h[l] and cwork[l] (initial state
+     * and cell) and leaves both ping-pong buffers as they were; states and cells of the loop live in the workspace. */
     const float* Wg_t[PARROT_MAX_LAYERS];
     const float* Wc_t[PARROT_MAX_LAYERS];
     const float* Wr_t; const float* Wo_t; const float* bo_pad; const float* oadd_pad;
@@ -447,8 +453,8 @@ typedef struct ParrotSampleDesc {
 } ParrotSampleDesc;
 
 long long parrot_sample_persist_floats(const ParrotSampleDesc* desc);
-/* 0: per-step launches; 1: the machine with 2L + 3 whole-K phases; 2: the machine with the step cut along K (Wro_t given);
- * 3: the same with the fed-back frame out of the chain (Wgx_t / Wcx_t given, 2L + 1 phases) */
+/* 0: per-step launches; 1: the machine with whole-K phases (GRU: 2L + 3; LSTM: L + 2); 2: the machine with the step cut
+ * along K (GRU, Wro_t given); 3: the same with the fed-back frame out of the chain (Wgx_t / Wcx_t given, 2L + 1 phases) */
 int parrot_sample_is_persistent(void* plan);
 /* Plans the decode machine for `desc` with `nwg` workgroups WITHOUT touching device memory (pointers are only used for
  * address arithmetic) and replays the unit table symbolically: every read must find its value written in an earlier

@@ -4,7 +4,8 @@
 // Parrot.compute_cost (reference model.py:651-737).  One workgroup per CU stays resident for the whole window; a
 // tick = n_slots phases separated by grid barriers; in a phase every workgroup runs up to maxu work units from a
 // host-built table.  A unit is a 16-column tile of a recurrent-step GEMM over all batch rows with the GRU gate math
-// fused (the same algebra as sk_kernel's epilogues, Blocks GatedRecurrent / sampleRNN/lib/ops.py:364-393), or the
+// (decode: or the LSTM cell update) fused (the same algebra as sk_kernel's epilogues, Blocks GatedRecurrent /
+// sampleRNN/lib/ops.py:364-393), or the
 // GMM-window attention of one batch row (model.py:664-690).  What the launches could not do:
 //   * weights are STATIONARY: a unit's [K,16] weight slab is copied into the CU's LDS once per window (up to 144 KB per
 //     CU) and every step reads it from there; only what does not fit is streamed from the fragment-major copies;
@@ -20,7 +21,7 @@
 enum { PM_MAXENT = 12,   // unit descriptors per workgroup: n_slots * maxu <= PM_MAXENT (training 3 x 3, decode 9 x 1)
        PM_MAXSLOTS = 9, PM_THREADS = 512, PM_MAXINIT = 12, PM_MAXDST = 6, PM_MAXWDST = 8, PM_MAXFILL = 16 };
 enum { PM_NONE = 0, PM_GEMM = 1, PM_ATT = 2 };
-enum { PM_EPI_LINEAR = 0, PM_EPI_GATES = 1, PM_EPI_CAND = 2 };
+enum { PM_EPI_LINEAR = 0, PM_EPI_GATES = 1, PM_EPI_CAND = 2, PM_EPI_LSTM = 3 };
 
 // LDS map (floats): resident weights | scratch shared by the split-K reduction (8 partial 16x16 tiles, rows padded
 // to 20 floats) and the attention row (never live at the same time) | the workgroup's unit table | misc.
@@ -56,13 +57,19 @@ struct PmUnit {
     unsigned a_off, a_st;        // the activation slab the unit reads
     int a_nch, a_c0;             // chunks per row block of that slab / the unit's first chunk in it (K/16 chunks are read)
     const float* W;              // fragment-major weights of the unit: [K/16][256] floats
-    int epi, M, rtile, row;      // rtile: GATES tile of the reset gate; row: batch row of an ATT unit
+    int epi, M, rtile, row;      // rtile: GATES tile of the reset gate (LSTM: the tile's quarter of a block, below); row: batch row of an ATT unit
     const float* bias;           // 16 floats (the tile's columns) or null
     PmRM add[4];                 // additive pre-activation inputs (p == null: unused)
     PmRM e0, e1;                 // GATES (r tile): e0 = h_prev;  CAND: e0 = h_prev, e1 = z
     PmRM out, o1, o2;            // LINEAR: out;  GATES: o1 = z | o2 = r, out = r*h_prev;  CAND: o1 = c, out = h_new
-    int ndst, pad2;              // fragment-major copies of `out` for the consuming units
+    int ndst, gstr;              // fragment-major copies of `out` for the consuming units; gstr: LSTM gate stride (H)
     PmDst dst[PM_MAXDST];
+    // LSTM (decode): the unit's 16 columns are 4 hidden units x 4 gates in sk_col order (column 4 q + j = gate q of hidden
+    // unit 4 ct + j; i | f | o | g), its weights the tile ct of parrot_tile_weights(.., lstm_H = H).  bias / add[] stay in
+    // the natural gate-major order [4H] and point at column 4 ct: the finalising lane (kk, r16) holds gate kk and reads its
+    // quad at + kk * gstr.  e1 = c_prev, o1 = c_new, out = h_new (row-major, ld H, pointing at column 4 ct; both
+    // write-through).  The tile yields FOUR state columns = the 16 lanes kk' = rtile (= ct % 4) of block dst[].chunk
+    // (= first chunk of h in the slab + ct / 4): four units complete one fragment-major block.
     // Round 5 (decode, batch <= 16): the attention projection folded into layer 0's candidate units.  pw[jt] = the
     // fragment-major block of the padded projection matrix Watt [H, 32] for this unit's 16 state columns and output
     // column tile jt; the finalising wave multiplies the h_new tile it holds by them (8 MFMAs) and publishes the
@@ -108,6 +115,7 @@ struct PmFill {
 struct PmProgram {
     int T, n_ticks, nwg, MB, M, ninit, n_slots, maxu;  // a tick = n_slots phases of up to maxu units per workgroup
     int dataflow, nfill;
+    int lstm, pad;        // lstm: some units are PM_EPI_LSTM (selects the kernels compiled with that epilogue)
     PmFill fill[PM_MAXFILL];
     const PmUnit* units;  // device: [n_slots][nwg][maxu]
     unsigned* sync;       // device: PM_SYNC_WORDS + PM_DBG_WORDS unsigned, zeroed before every launch

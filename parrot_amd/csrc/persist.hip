@@ -177,7 +177,9 @@ __device__ __forceinline__ f32x4 pm_sigmoid4(f32x4 x) {
 // 8 waves = MB row blocks x KS = 8/MB contiguous K ranges.  Wave (rb, ks) owns row block rb of the 16-column tile
 // over its K range: per 16-deep chunk one fragment-major A block (1 KB, sc1 global load) and one B block (1 KB from
 // LDS, shared by the MB waves of the same ks; or a global load when the slab is streamed) feed 4 MFMA 16x16x4.
-template <int MB, bool DF>
+// LS: the program has LSTM units (PmProgram::lstm).  A template parameter, not a run-time branch: the kernels of the GRU
+// programs (LS = false) compile to what they were before the LSTM epilogue existed.
+template <int MB, bool DF, bool LS>
 __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds_w, float* lds_red,
                                         const __amdgpu_buffer_rsrc_t fm, unsigned long long* stage, unsigned* sync) {
     const unsigned long long ts0 = pm_clock();
@@ -201,6 +203,18 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
     const int kk = lane >> 4, r16 = lane & 15;
     const int m = 16 * rb + r16, n0 = 4 * kk;
     const bool row_ok = m < u.M;
+    // LSTM unit: the lane holds gate kk of four hidden units; its bias / additive quad sits kk * H further in the natural
+    // gate-major order, the cell quad is the same for the four lanes of a row (persist.h)
+    const bool lstm = LS && __builtin_amdgcn_readfirstlane(u.epi) == PM_EPI_LSTM;
+    // (recomputed from the lane number where they are used, behind an opaque copy: kept live across the K loop they
+    // cost two registers into scratch at MB = 1)
+    auto epi_cols = [&](int& nq, int& ne) {
+        if (!LS) { nq = n0; ne = n0; return; }
+        int l2 = lane;
+        asm volatile("" : "+v"(l2));
+        nq = lstm ? (l2 >> 4) * __builtin_amdgcn_readfirstlane(u.gstr) : 4 * (l2 >> 4);
+        ne = lstm ? 0 : 4 * (l2 >> 4);
+    };
     f32x4 p_bias = {0.f, 0.f, 0.f, 0.f}, p_add = {0.f, 0.f, 0.f, 0.f}, p_e0 = {0.f, 0.f, 0.f, 0.f},
           p_e1 = {0.f, 0.f, 0.f, 0.f};
     f32x4 p_in[4];  // the additive inputs, kept apart until the epilogue (dataflow mode may have to ask again)
@@ -214,15 +228,17 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
         pwb1 = *reinterpret_cast<const f32x4*>(u.pw[1] + (lane << 2));
     }
     if (fin && row_ok) {
-        if (u.bias) p_bias = *reinterpret_cast<const f32x4*>(u.bias + n0);
+        int nq, ne;
+        epi_cols(nq, ne);
+        if (u.bias) p_bias = *reinterpret_cast<const f32x4*>(u.bias + nq);
         // requested NOW in both modes: these operands come from phases before the one that produced the unit's A operand,
         // so they have almost always landed; asked for behind the K loop, one poll loop after the other, they cost a
         // memory round trip EACH on the step's critical chain (dataflow mode, round 4)
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (u.add[q].p) p_in[q] = pm_rm_load(u.add[q], t, m, n0);
+            if (u.add[q].p) p_in[q] = pm_rm_load(u.add[q], t, m, nq);
         if (u.e0.p) p_e0 = pm_rm_load(u.e0, t, m, n0);
-        if (u.e1.p) p_e1 = pm_rm_load(u.e1, t, m, n0);
+        if (u.e1.p) p_e1 = pm_rm_load(u.e1, t, m, ne);
     }
 
     const unsigned long long ts1 = pm_clock();
@@ -309,11 +325,13 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
     }
     const f32x4 part = acc0 + acc1;
     if (DF && fin && row_ok) {  // whatever had not landed when it was first asked for: poll it now
+        int nq, ne;
+        epi_cols(nq, ne);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-            if (u.add[q].p && pm_is_empty(p_in[q])) p_in[q] = pm_rm_take(u.add[q], t, m, n0, sync);
+            if (u.add[q].p && pm_is_empty(p_in[q])) p_in[q] = pm_rm_take(u.add[q], t, m, nq, sync);
         if (u.e0.p && pm_is_empty(p_e0)) p_e0 = pm_rm_take(u.e0, t, m, n0, sync);
-        if (u.e1.p && pm_is_empty(p_e1)) p_e1 = pm_rm_take(u.e1, t, m, n0, sync);
+        if (u.e1.p && pm_is_empty(p_e1)) p_e1 = pm_rm_take(u.e1, t, m, ne, sync);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) p_add += p_in[q];  // (fixed order, both modes)
@@ -335,7 +353,31 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
         for (int q = 0; q < KS; ++q)
             v += *reinterpret_cast<const f32x4*>(lds_red + (q * MB + rb) * 320 + r16 * 20 + n0);
         f32x4 fmv = {0.f, 0.f, 0.f, 0.f};  // value published to the consumers (zero in the padding rows)
-        if (row_ok) {
+        if (lstm) {
+            // the four gates of a hidden unit sit in four lanes 16 apart: exchanged through the wave's own partial tile
+            // (only this wave reads the tiles of row block rb, it has read them above, and a wave's LDS operations
+            // execute in order); then every lane holds i | f | o | g of row r16 and the lanes kk == 0 store
+            float* ex = lds_red + rb * 320 + r16 * 20;
+            *reinterpret_cast<f32x4*>(ex + n0) = v + p_bias + p_add;
+            __builtin_amdgcn_wave_barrier();
+            const f32x4 gi = pm_sigmoid4(*reinterpret_cast<const f32x4*>(ex));
+            const f32x4 gf = pm_sigmoid4(*reinterpret_cast<const f32x4*>(ex + 4));
+            const f32x4 go = pm_sigmoid4(*reinterpret_cast<const f32x4*>(ex + 8));
+            const f32x4 gp = *reinterpret_cast<const f32x4*>(ex + 12);
+            f32x4 cn, hn;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                cn[i] = p_e1[i] * gf[i] + tanhf(gp[i]) * gi[i];  // c' = c f + g i   (SK_EPI_LSTM, skinny.hip)
+                hn[i] = tanhf(cn[i]) * go[i];                    // h' = tanh(c') o
+            }
+            if (row_ok) {
+                fmv = hn;
+                if (kk == 0) {
+                    pm_rm_store<true>(u.o1, t, m, 0, cn);   // next step's cell operand
+                    pm_rm_store<true>(u.out, t, m, 0, hn);  // attention, next step
+                }
+            }
+        } else if (row_ok) {
             const f32x4 pre = v + p_bias + p_add;
             if (u.epi == PM_EPI_LINEAR) {
                 fmv = pre;
@@ -365,8 +407,11 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
             if (q < ndst) {
                 const PmDst ds = u.dst[q];
                 const unsigned so = ds.off + (unsigned)t * ds.st + ((unsigned)(rb * ds.nch + ds.chunk) << 10);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, fmv), fm, (unsigned)lane << 4,
-                                                       __builtin_amdgcn_readfirstlane(so), 16);
+                // (LSTM: the tile's four state columns are the 16 lanes kk' = rtile of the block)
+                if (!lstm || kk == 0)
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, fmv), fm,
+                                                           lstm ? (unsigned)(u.rtile * 16 + r16) << 4 : (unsigned)lane << 4,
+                                                           __builtin_amdgcn_readfirstlane(so), 16);
             }
         }
         if (fold) {
@@ -650,7 +695,7 @@ __device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* 
 }
 
 // ------------------------------------------------------------------------------------------------ kernel
-template <int MB, bool DF>
+template <int MB, bool DF, bool LS>
 __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lds_w = lds;
@@ -748,7 +793,7 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
                 if (kind == PM_NONE) continue;
                 const int t = tick - __builtin_amdgcn_readfirstlane(u.lag);
                 if (t < 0 || t >= P.T) continue;
-                if (kind == PM_GEMM) pm_gemm<MB, DF>(u, t, lds_w, lds_red, fmr, stage, sync);
+                if (kind == PM_GEMM) pm_gemm<MB, DF, LS>(u, t, lds_w, lds_red, fmr, stage, sync);
                 else pm_att_row<DF>(P.att, u.row, t, lds_att, P.fm_base, sync);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -853,23 +898,30 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     static bool attr_done = false;
     if (!attr_done) {
         const int l = (int)lds;
-        PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l));
-        PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l));
-        PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l));
-        PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l));
-        PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l));
-        PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l));
+#define PM_ATTR(MB_, DF_, LS_) \
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+        PM_ATTR(1, false, false); PM_ATTR(2, false, false); PM_ATTR(4, false, false);
+        PM_ATTR(1, true, false); PM_ATTR(2, true, false); PM_ATTR(4, true, false);
+        PM_ATTR(1, false, true); PM_ATTR(2, false, true); PM_ATTR(4, false, true);
+        PM_ATTR(1, true, true); PM_ATTR(2, true, true); PM_ATTR(4, true, true);
+#undef PM_ATTR
         attr_done = true;
     }
     const dim3 grid(P.nwg), block(PM_THREADS);
+#define PM_GO(MB_, DF_) \
+    do { \
+        if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true>), grid, block, lds, stream, P); \
+        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false>), grid, block, lds, stream, P); \
+    } while (0)
     switch (P.MB * 2 + (P.dataflow ? 1 : 0)) {
-        case 2: hipLaunchKernelGGL((pm_kernel<1, false>), grid, block, lds, stream, P); break;
-        case 3: hipLaunchKernelGGL((pm_kernel<1, true>), grid, block, lds, stream, P); break;
-        case 4: hipLaunchKernelGGL((pm_kernel<2, false>), grid, block, lds, stream, P); break;
-        case 5: hipLaunchKernelGGL((pm_kernel<2, true>), grid, block, lds, stream, P); break;
-        case 8: hipLaunchKernelGGL((pm_kernel<4, false>), grid, block, lds, stream, P); break;
-        case 9: hipLaunchKernelGGL((pm_kernel<4, true>), grid, block, lds, stream, P); break;
+        case 2: PM_GO(1, false); break;
+        case 3: PM_GO(1, true); break;
+        case 4: PM_GO(2, false); break;
+        case 5: PM_GO(2, true); break;
+        case 8: PM_GO(4, false); break;
+        case 9: PM_GO(4, true); break;
         default: return PH_ERR_BADARG;
     }
+#undef PM_GO
     return (int)hipGetLastError();
 }

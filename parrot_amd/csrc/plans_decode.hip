@@ -1,7 +1,8 @@
 // The decode loop of Parrot.sample_model_fun (model.py:882-1057) as a plan: per-step launches in one hipGraph, or the
 // whole loop as ONE resident kernel on the persistent phase machine (persist.h) -- 2L + 3 whole-K phases (round 2),
 // 2L + 2 phases with every product cut along K by the age of its operands (round 4), 2L + 1 with the fed-back frame out
-// of the step's dependency chain (round 5).  The planner, its symbolic checker and the parrot_sample_* entry points.
+// of the step's dependency chain (round 5); LSTM stacks: L + 2 whole-K phases (build_persist_lstm).  The planner, its
+// symbolic checker and the parrot_sample_* entry points.
 #include "plans_common.h"
 #include "switches.h"
 
@@ -28,19 +29,24 @@ struct SamplePlan : PlanBase {
     float* hist_h[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
 
     static bool persist_eligible_shape(const ParrotSampleDesc& d) {  // (no device query: the CPU tests plan too)
-        if (d.cell != 0 || d.layer_norm || d.gmm_K > 0 || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
+        if (d.layer_norm || d.gmm_K > 0 || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
             d.U > PM_ATT_MAXU || d.A > PM_ATT_MAXA || d.S < 1 || d.O > 64 || d.ldx < 64 || (d.ldx % 4))
             return false;
         for (int l = 0; l < d.L; ++l)
-            if (!d.Wg_t[l] || !d.Wc_t[l]) return false;
+            if (!d.Wg_t[l] || (d.cell == 0 && !d.Wc_t[l])) return false;
         return true;
+    }
+    // LSTM stacks (cell == 1): one phase per layer, readout and output composed (Wro_t / ro_const) -- build_persist_lstm
+    static bool lstm_eligible(const ParrotSampleDesc& d) {
+        return d.cell == 1 && d.Wro_t && d.ro_const && d.L + 2 <= PM_MAXSLOTS;
     }
     static bool legacy_eligible(const ParrotSampleDesc& d) {
         if (2 * d.L + 3 > PM_MAXSLOTS || !d.Wr_t || !d.Wo_t || !d.bo_pad) return false;
         return (d.oadd != nullptr) == (d.oadd_pad != nullptr);
     }
     static bool persist_eligible(const ParrotSampleDesc& d) {
-        if (!persist_eligible_shape(d) || !(legacy_eligible(d) || pieces_wanted(d))) return false;
+        if (!persist_eligible_shape(d)) return false;
+        if (d.cell == 1 ? !lstm_eligible(d) : !(legacy_eligible(d) || pieces_wanted(d))) return false;
         return pm_max_workgroups() >= 64;
     }
     static int fb_rows(const ParrotSampleDesc& d, int l) { return d.Wfg[l] ? 64 : 0; }
@@ -49,6 +55,13 @@ struct SamplePlan : PlanBase {
         const int MB = d.B <= 16 ? 1 : (d.B <= 32 ? 2 : 4);
         const long long rows = (long long)MB * 16, S = d.S;
         long long n = PM_SYNC_WORDS + PM_DBG_WORDS;
+        if (d.cell == 1) {  // one slab per layer, the composed output's slab, h and c histories (build_persist_lstm)
+            n += ((long long)(d.L + 2) * nwg * 2 * sizeof(PmUnit) + 3) / 4 + 64;
+            for (int l = 0; l < d.L; ++l) n += (S + 1) * rows * kslab(d, l);
+            n += S * rows * ((long long)d.L * d.H + d.E);
+            n += 2 * (long long)d.L * (S + 1) * d.B * d.H + S * d.B * d.A;
+            return n + 4096;
+        }
         n += ((long long)(2 * d.L + 3) * nwg * sizeof(PmUnit) + 3) / 4 + 64;
         for (int l = 0; l < d.L; ++l) n += 2 * (S + 1) * rows * kslab(d, l);
         n += S * rows * ((long long)d.L * d.H + d.E) + S * rows * d.R;
@@ -61,6 +74,7 @@ struct SamplePlan : PlanBase {
         persist_ok = false;
         if (env_int("PARROT_SAMPLE_PERSIST", 1) == 0) return 0;
         if (!persist_eligible(d) || !d.persist_ws) return 0;
+        if (d.cell == 1) return build_persist_lstm(false, 0);
         if (pieces_wanted(d)) {  // the step cut along K by the age of its operands (below); else the 2L + 3 whole-K phases
             build_persist_pieces(false, 0);
             if (persist_ok) return 0;
@@ -244,9 +258,202 @@ struct SamplePlan : PlanBase {
 
     int run_persist(hipStream_t st) {
         const size_t BH = (size_t)d.B * d.H;
-        for (int l = 0; l < d.L; ++l)  // row-major initial state for the epilogues (r * h_prev, state blend)
+        for (int l = 0; l < d.L; ++l) {  // row-major initial state for the epilogues (r * h_prev, state blend; LSTM: cells)
             PL_TRY((int)hipMemcpyAsync(hist_h[l], d.h[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (hist_c[l]) PL_TRY((int)hipMemcpyAsync(hist_c[l], d.cwork[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
         return pm_launch(pm_prog, st);
+    }
+
+    // ---- LSTM stacks on the machine ----------------------------------------------------------------------------------
+    // An LSTM layer is ONE product [h_l[t] ; w ; h_0[t+1] .. h_{l-1}[t+1] ; x[t]] . W over the gate-interleaved columns
+    // (sk_col order, Wg_t[l] = parrot_tile_weights(.., lstm_H = H)) with the cell update in the epilogue (PM_EPI_LSTM,
+    // persist.hip), so a step is L + 2 dependent phases: layer 0, attention, layers 1 .. L-1, composed output
+    // (x = XR . Wro + ro_const, as in the pieces plan).  Every product walks its whole K.  A layer has H / 4 tiles of 16
+    // columns; each yields four state columns = a quarter of a fragment-major block (PmUnit::rtile), four neighbouring
+    // units complete a block.  More tiles than workgroups (384 at H = 1536): two units per workgroup and phase (maxu 2).
+    // The cell history [S + 1, B, H] is row-major and write-once like the state history (dataflow mode polls it).
+    float* hist_c[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
+    bool lstm_ok = false;  // (dry runs: planned and checked)
+    static int slotL(int l) { return l == 0 ? 0 : l + 1; }
+    int build_persist_lstm(bool dry, int nwg_dry) {
+        lstm_ok = false;
+        if (!persist_eligible_shape(d) || !lstm_eligible(d)) return 0;
+        const int nwg = dry ? nwg_dry : pm_max_workgroups();
+        if (nwg < 64) return 0;
+        if (!dry && (!d.persist_ws || d.persist_ws_floats < persist_floats(d, nwg))) return 0;
+        const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S;
+        for (int l = 0; l < L && !dry; ++l)
+            if (!d.cwork[l]) return 0;
+        const int MB = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
+        const long long rows = (long long)MB * 16, BH = (long long)B * H;
+        const int n_slots = L + 2, sATT = 1, sOUT = L + 1, hc = H / 16, ec = E / 16;
+        const int maxu = std::max(H / 4, B) <= nwg ? 1 : 2;
+        if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT) return 0;
+        float* ws = dry ? reinterpret_cast<float*>((uintptr_t)0x10000000) : d.persist_ws;
+        auto take = [&](long long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
+        unsigned* sync = reinterpret_cast<unsigned*>(take(PM_SYNC_WORDS + PM_DBG_WORDS));
+        const size_t unit_bytes = (size_t)n_slots * nwg * maxu * sizeof(PmUnit);
+        PmUnit* units_dev = reinterpret_cast<PmUnit*>(take((long long)(unit_bytes + 3) / 4 + 16));
+        float* fm_base = ws;
+        float* XL[PARROT_MAX_LAYERS];
+        long long kx[PARROT_MAX_LAYERS];
+        for (int l = 0; l < L; ++l) {
+            kx[l] = kslab(d, l);
+            XL[l] = take((S + 1) * rows * kx[l]);
+        }
+        const long long kr = (long long)L * H + E;
+        float* XR = take(S * rows * kr);
+        if ((long long)(ws - fm_base) * 4 >= 0xfff00000ll) return 0;
+        float* const fm_end = ws;
+        for (int l = 0; l < L; ++l) hist_h[l] = take((S + 1) * BH);
+        for (int l = 0; l < L; ++l) hist_c[l] = take((S + 1) * BH);
+        float* b_hist = take((long long)S * B * d.A);
+
+        auto boff = [&](const float* p) { return (unsigned)((p - fm_base) * 4); };
+        auto mkdst = [&](float* slab, long long step0, long long ks, int chunk) {
+            PmDst q;
+            q.off = boff(slab + step0 * rows * ks); q.st = (unsigned)(rows * ks * 4); q.nch = (int)(ks / 16); q.chunk = chunk;
+            return q;
+        };
+        auto rm = [](const float* p, long long st, int ld) { PmRM r; r.p = const_cast<float*>(p); r.st = st; r.ld = ld; r.pad = 0; return r; };
+        auto acc = [](int res, int dstep, int c0, int nch) { PmAccess a; a.res = res; a.dstep = dstep; a.c0 = c0; a.nch = nch; return a; };
+        auto gemm_unit = [&](int slot, float* slab, long long ks) {
+            PmReq q;
+            memset(&q, 0, sizeof(q));
+            q.u.kind = PM_GEMM; q.u.M = B; q.u.w_lds = -1;
+            q.u.a_off = boff(slab); q.u.a_st = (unsigned)(rows * ks * 4); q.u.a_nch = (int)(ks / 16); q.u.K = (int)ks;
+            q.slot = slot; q.crit = 1; q.krows = (int)ks;
+            return q;
+        };
+        std::vector<PmReq> reqs;
+        std::vector<PmMeta> metas;  // the symbolic replay's view: slabs by chunk, histories as one element per step
+        for (int l = 0; l < L; ++l) {
+            const int nch = (int)(kx[l] / 16);
+            PmMeta m;
+            m.lag = 0; m.slot = slotL(l);
+            m.rd.push_back(acc(RES_XG + l, 0, 0, nch));
+            m.rd.push_back(acc(RES_C + l, 0, 0, 1));
+            m.wr.push_back(acc(RES_C + l, 1, 0, 1));
+            m.wr.push_back(acc(RES_H + l, 1, 0, 1));
+            m.wr.push_back(acc(RES_XG + l, 1, 0, hc));
+            for (int m2 = l + 1; m2 < L; ++m2) m.wr.push_back(acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
+            m.wr.push_back(acc(RES_XR, 0, l * hc, hc));
+            metas.push_back(m);
+            for (int ct = 0; ct < H / 4; ++ct) {
+                PmReq q = gemm_unit(slotL(l), XL[l], kx[l]);
+                PmUnit& u = q.u;
+                u.W = d.Wg_t[l] + (size_t)ct * nch * 256;
+                u.bias = d.bg[l] ? d.bg[l] + 4 * ct : nullptr;
+                if (d.seq_g[l]) u.add[0] = rm(d.seq_g[l] + 4 * ct, 0, 4 * H);
+                u.epi = PM_EPI_LSTM; u.gstr = H; u.rtile = ct & 3;
+                u.e1 = rm(hist_c[l] + 4 * ct, BH, H);
+                u.o1 = rm(hist_c[l] + BH + 4 * ct, BH, H);
+                u.out = rm(hist_h[l] + BH + 4 * ct, BH, H);
+                u.dst[u.ndst++] = mkdst(XL[l], 1, kx[l], ct / 4);
+                for (int m2 = l + 1; m2 < L; ++m2) u.dst[u.ndst++] = mkdst(XL[m2], 0, kx[m2], hc + ec + l * hc + ct / 4);
+                u.dst[u.ndst++] = mkdst(XR, 0, kr, l * hc + ct / 4);
+                if (u.ndst > PM_MAXDST) return 0;
+                reqs.push_back(q);
+            }
+        }
+        {
+            PmMeta m;
+            m.lag = 0; m.slot = sATT;
+            m.rd.push_back(acc(RES_H, 1, 0, 1));
+            m.rd.push_back(acc(RES_KAPPA, 0, 0, 1));
+            m.wr.push_back(acc(RES_KAPPA, 1, 0, 1));
+            m.wr.push_back(acc(RES_XG, 1, hc, ec));
+            for (int l = 1; l < L; ++l) m.wr.push_back(acc(RES_XG + l, 0, hc, ec));
+            m.wr.push_back(acc(RES_XR, 0, L * hc, ec));
+            metas.push_back(m);
+        }
+        for (int b = 0; b < B; ++b) {
+            PmReq q;
+            memset(&q, 0, sizeof(q));
+            q.u.kind = PM_ATT; q.u.row = b; q.u.w_lds = -1;
+            q.slot = sATT; q.crit = 1; q.krows = 0;
+            reqs.push_back(q);
+        }
+        {
+            PmMeta m;
+            m.lag = 0; m.slot = sOUT;
+            m.rd.push_back(acc(RES_XR, 0, 0, (int)(kr / 16)));
+            m.wr.push_back(acc(RES_X, 1, 0, 1));
+            for (int l = 0; l < L; ++l)
+                if (fb_rows(d, l)) m.wr.push_back(acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
+            metas.push_back(m);
+        }
+        for (int ct = 0; ct < 4; ++ct) {  // output frame x[t+1] (63 columns, padded to 64)
+            PmReq q = gemm_unit(sOUT, XR, kr);
+            PmUnit& u = q.u;
+            u.W = d.Wro_t + (size_t)ct * (kr / 16) * 256;
+            u.add[0] = rm(d.ro_const + 16 * ct, 0, 64);
+            u.epi = PM_EPI_LINEAR;
+            u.out = rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
+            for (int l = 0; l < L; ++l)
+                if (fb_rows(d, l)) u.dst[u.ndst++] = mkdst(XL[l], 1, kx[l], (int)(kx[l] / 16) - 4 + ct);
+            reqs.push_back(q);
+        }
+        std::vector<PmAccess> init;
+        for (int l = 0; l < L; ++l) {
+            init.push_back(acc(RES_XG + l, 0, 0, hc));
+            init.push_back(acc(RES_H + l, 0, 0, 1));
+            init.push_back(acc(RES_C + l, 0, 0, 1));
+            if (fb_rows(d, l)) init.push_back(acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
+        }
+        init.push_back(acc(RES_XG, 0, hc, ec));
+        init.push_back(acc(RES_KAPPA, 0, 0, 1));
+        const int chk = check_pieces(metas, init, n_slots, 4, 4);
+        memset(pieces_info, 0, sizeof(pieces_info));
+        pieces_info[0] = n_slots; pieces_info[2] = chk; pieces_info[3] = (int)reqs.size(); pieces_info[13] = maxu;
+        for (const PmReq& q : reqs) pieces_info[4 + q.slot] += 1;
+        if (chk != 0) return 0;
+        std::vector<PmUnit> table;
+        if (!pm_place(reqs, n_slots, maxu, nwg, table)) return 0;
+        for (const PmUnit& u : table)
+            if (u.kind == PM_GEMM && u.w_lds < 0) pieces_info[14] += 1;  // units that stream their weights
+        lstm_ok = true;
+        if (dry) return 0;
+        if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) return 0;
+
+        PmProgram& P = pm_prog;
+        memset(&P, 0, sizeof(P));
+        P.T = S; P.n_ticks = S; P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = n_slots; P.maxu = maxu;
+        P.units = units_dev; P.sync = sync; P.fm_base = fm_base;
+        PmAtt& a = P.att;
+        a.h1 = rm(hist_h[0], BH, H);
+        a.WattT = d.WattT; a.batt = d.batt; a.ctx = d.ctx;
+        a.kappa = d.kappa; a.a = d.a; a.b = b_hist; a.phi = d.phi; a.w = d.w; a.sup = nullptr;
+        a.B = B; a.H = H; a.A = d.A; a.U = d.U; a.E = E; a.att_type = d.att_type; a.dense = 0;
+        a.eps = d.eps; a.alignment = d.alignment; a.sharpening = d.sharpening; a.timing = d.timing;
+        a.wdst[a.nwdst++] = mkdst(XL[0], 1, kx[0], hc);
+        for (int l = 1; l < L; ++l) a.wdst[a.nwdst++] = mkdst(XL[l], 0, kx[l], hc);
+        a.wdst[a.nwdst++] = mkdst(XR, 0, kr, L * hc);
+        int ni = 0;
+        auto add_init = [&](const float* src, int ld, int K, float* slab, long long ks, int chunk) {
+            PmInit& in = P.init[ni++];
+            in.src = src; in.ld = ld; in.K = K; in.dst_off = boff(slab); in.nch = (int)(ks / 16); in.chunk = chunk; in.pad = 0;
+        };
+        for (int l = 0; l < L; ++l) add_init(d.h[l], H, H, XL[l], kx[l], 0);
+        add_init(d.w, E, E, XL[0], kx[0], hc);
+        for (int l = 0; l < L; ++l)  // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states
+            if (fb_rows(d, l)) add_init(d.x, d.ldx, 64, XL[l], kx[l], (int)(kx[l] / 16) - 4);
+        P.ninit = ni;
+        P.lstm = 1;
+        // no grid barriers with one unit per workgroup and phase (34.9 against 38.7 us per step at 2 x 1024, B 16); with two
+        // (H = 1536: 384 tiles on 256 workgroups, all weights streamed) the barriers measured faster: 114.8 against 124.9
+        P.dataflow = sw_pm_dataflow(maxu == 1 ? 1 : 0);
+        auto add_fill = [&](void* q, long long nfloats) {
+            if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
+        };
+        add_fill(fm_base, (long long)(fm_end - fm_base));
+        for (int l = 0; l < L; ++l) {
+            add_fill(hist_h[l] + BH, (long long)S * BH);
+            add_fill(hist_c[l] + BH, (long long)S * BH);
+        }
+        persist_ok = true;
+        return 0;
     }
 
     // ---- round 4: the decode step cut along K by the AGE of its operands ------------------------------------------
@@ -278,7 +485,7 @@ struct SamplePlan : PlanBase {
     };
     struct PmAccess { int res, dstep, c0, nch; };
     struct PmMeta { int lag, slot; std::vector<PmAccess> rd, wr; };
-    enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63,
+    enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63, RES_C = 70,
            RES_PART = 100 };
     // Round 5: the attention projection folded into layer 0's candidate units (PmUnit::pw / pp, persist.hip)
     static bool attfold_wanted(const ParrotSampleDesc& d) {
@@ -498,6 +705,7 @@ struct SamplePlan : PlanBase {
     // dry = true: plan, place and check only (no device memory is touched; nwg given by the caller) -- the CPU tests
     int build_persist_pieces(bool dry, int nwg_dry) {
         pieces_ok = false;
+        if (d.cell == 1) return build_persist_lstm(dry, nwg_dry);
         if (!pieces_wanted(d) || !persist_eligible_shape(d)) return 0;
         const int nwg = dry ? nwg_dry : pm_max_workgroups();
         if (nwg < 64) return 0;
@@ -1067,7 +1275,7 @@ int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* in
     p->d = *desc;
     p->build_persist_pieces(true, nwg);
     for (int i = 0; i < 16; ++i) info16[i] = p->pieces_info[i];
-    return p->pieces_ok ? 0 : PARROT_ERR_UNSUPPORTED;
+    return (p->pieces_ok || p->lstm_ok) ? 0 : PARROT_ERR_UNSUPPORTED;
 }
 int parrot_sample_run(void* plan, void* stream) { PH_ENTRY(); return static_cast<PlanBase*>(plan)->run(0, (hipStream_t)stream); }
 int parrot_sample_destroy(void* plan) { PH_ENTRY();

@@ -24,10 +24,12 @@
 // PARROT_ATT_DENSE         0        plan,    1: the attention reads every context row instead of walking    bench.py, tests
 //                                   launch   its support (same result)
 // PARROT_PM_DATAFLOW       0 / 1    plan     persistent machines: 1 = per-unit flags, 0 = grid barriers;    tests
-//                                            default 1 for the sampling plan cut in pieces, 0 otherwise
-// PARROT_SAMPLE_PERSIST    1        plan     0: sampling without the persistent machine (Python: no          tests, tools
-//                                            workspace)
+//                                            default 1 for the sampling plan cut in pieces and the LSTM
+//                                            sampling plan with one unit per workgroup, 0 otherwise
+// PARROT_SAMPLE_PERSIST    1        plan     0: sampling without the persistent machine, GRU and LSTM        tests, tools
+//                                            (Python: no workspace)
 // PARROT_PM_PIECES         1        plan     0: the sampling machine's whole-K phases instead of pieces      tests, tools
+//                                            (GRU; the LSTM plan is whole-K either way)
 // PARROT_PM_ATTFOLD        1        plan     0: attention projection not folded into the candidate units     development
 //                                            (Python: no folded matrix)
 // PARROT_PM_FBC            1        plan     0: fed-back frame kept in the step's chain (Python: no          tests

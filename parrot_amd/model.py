@@ -1242,7 +1242,8 @@ class Parrot(Brick):
         # Persistent phase machine (csrc/persist.h): the decode loop as one resident kernel.  It wants fragment-major
         # copies of the packed layer matrices with the fed-back-output rows appended (padded to 64 rows), of the
         # readout stack and of the output projection (63 -> 64 columns); sample_model_device refreshes them per call.
-        if (not lstm and not gmm and not self.layer_norm and N <= 64 and H % 16 == 0 and E % 16 == 0 and R % 16 == 0
+        # LSTM decoders: the one 4H-wide group, tiled in the gate-interleaved column order of the machine's LSTM units.
+        if (not gmm and not self.layer_norm and N <= 64 and H % 16 == 0 and E % 16 == 0 and R % 16 == 0
                 and O <= 64 <= ldx and env_int('PARROT_SAMPLE_PERSIST', 1) != 0):
             pm = dict(cat={}, tiled={})
             for l in range(L):
@@ -1264,14 +1265,14 @@ class Parrot(Brick):
             pm['Wro'], pm['Wro_t'] = torch.empty(L * H + E, 64, **f), torch.empty(L * H + E, 64, **f)
             pm['ro_const'] = torch.zeros(N, 64, **f)
             d.Wro_t, d.ro_const = pm['Wro_t'].data_ptr(), pm['ro_const'].data_ptr()
-            if N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
+            if not lstm and N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
                 # round 5: the attention projection as an [H, 32] matrix (fragment-major): layer 0's candidate units fold
                 # their tile's share of h_1 . Watt into their epilogue (ParrotSampleDesc::Watt_t)
                 pm['Watt_pad'], pm['Watt_t'] = torch.zeros(H, 32, **f), torch.empty(H, 32, **f)
                 d.Watt_t = pm['Watt_t'].data_ptr()
             # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
             # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
-            if L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
+            if not lstm and L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
                 for key, wd, suf, mat, rec in self._groups:
                     rows = H + E + 64 + H
                     pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)
@@ -1353,9 +1354,10 @@ class Parrot(Brick):
         pm, st = ws['pm'], self.store.storage
         H, E, L, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.output_dim
 
-        def tile(W, out):
-            _lib.call('parrot_tile_weights', W.data_ptr(), W.shape[0], W.shape[1], W.shape[1], out.data_ptr(), 0, 0,
+        def tile(W, out, lstm_H=0):
+            _lib.call('parrot_tile_weights', W.data_ptr(), W.shape[0], W.shape[1], W.shape[1], out.data_ptr(), 0, lstm_H,
                       ops._stream())
+        lstm_H = H if self.cell_type == 'lstm' else 0
         with torch.no_grad():
             for l in range(L):
                 for key, wd, suf, mat, rec in self._groups:
@@ -1364,7 +1366,7 @@ class Parrot(Brick):
                     cat[:kl].copy_(st[f'{mat}{l + 1}'])
                     if (l + 1) in self._fb_layers:
                         cat[kl:kl + O].copy_(self._p(f'/out_to_h{l + 1}/fork_rnn{l + 1}_{suf}.W'))
-                    tile(cat, pm['tiled'][(l, key)])
+                    tile(cat, pm['tiled'][(l, key)], lstm_H)
             tile(st['dec.Wr'], pm['Wr_t'])
             pm['Wo_pad'][:, :O].copy_(self._p('/readout_to_output.W'))
             tile(pm['Wo_pad'], pm['Wo_t'])

@@ -1,7 +1,14 @@
-"""Secondary measurements (BASELINE configs[2] decode latency, configs[4] SampleRNN sample loop, mu-law
-quantiser bandwidth).  Development / documentation aid; the driver's headline bench is bench.py."""
+"""Secondary measurements (BASELINE configs[2] decode latency, the same loop with LSTM decoders -- persistent machine
+against the per-step launches, alternating child processes --, configs[4] SampleRNN sample loop, mu-law quantiser
+bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
+
+  bench_extra.py                         everything, one JSON line
+  bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_lstm2_1024, decode_lstm3_1536, samplernn_cfg5, mulaw)
+  bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
+  bench_extra.py --reps N                on / off alternations of the LSTM decode entries (default 3)"""
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -9,55 +16,104 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
+
+def _arg(name, dflt=None):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else dflt
+
+
+ALL = ("decode_cfg3", "decode_lstm2_1024", "decode_lstm3_1536", "samplernn_cfg5", "mulaw")
+only = tuple(_arg("--only", ",".join(ALL)).split(","))
+assert all(n in ALL for n in only), only
+LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
+    "decode_lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024),
+    "decode_lstm3_1536": dict(num_layers=3, rnn_h_dim=1536, readouts_dim=1536),
+}
 dev = torch.device("cuda:0")
 out = {}
-
-# ---- configs[2]: autoregressive decode, batch 16, 1000 frames, MSE head (greedy), hipGraph
-from parrot_amd.model import Parrot
-m = Parrot(device=dev, num_layers=2, rnn_h_dim=1024, readouts_dim=1024, encoder_type='bidirectional',
-           weak_feedback=True, use_graph=True).initialize()
 g = torch.Generator().manual_seed(0)
-N, U, S = 16, 100, 1000
-lab = torch.randint(0, 43, (N, U), generator=g)
-lm = torch.ones(N, U)
-for rep in range(3):
-    torch.cuda.synchronize(); t0 = time.time()
-    outs = m.sample_model_device(lab, lm, None, N, S)
-    torch.cuda.synchronize(); dt = time.time() - t0
-out["decode_cfg3"] = {"batch": N, "frames": S, "seconds": round(dt, 4), "us_per_step": round(1e6 * dt / S, 2),
-                      "frames_per_s": round(N * S / dt, 1)}
-m.close()
+
+
+def decode(kw, dump=None):
+    """Autoregressive decode, batch 16, 1000 frames, MSE head (greedy), hipGraph: three runs, the last one reported."""
+    from parrot_amd import _lib
+    from parrot_amd.model import Parrot
+    m = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, **kw).initialize()
+    g = torch.Generator().manual_seed(0)
+    N, U, S = 16, 100, 1000
+    lab = torch.randint(0, 43, (N, U), generator=g)
+    lm = torch.ones(N, U)
+    for rep in range(3):
+        torch.cuda.synchronize(); t0 = time.time()
+        outs = m.sample_model_device(lab, lm, None, N, S)
+        torch.cuda.synchronize(); dt = time.time() - t0
+    if dump:
+        np.save(dump, outs[0].cpu().numpy())
+    ws = m._sample_ws[(S, N, U)]
+    res = {"batch": N, "frames": S, "seconds": round(dt, 4), "us_per_step": round(1e6 * dt / S, 2),
+           "frames_per_s": round(N * S / dt, 1), "machine": int(_lib.load().parrot_sample_is_persistent(ws['plan']))}
+    m.close()
+    return res
+
+
+if "--child" in sys.argv:  # one LSTM decode measurement under the caller's environment
+    print(json.dumps(decode(dict(LSTM_SHAPES[_arg("--child")], cell_type='lstm'))))
+    sys.exit(0)
+
+# ---- configs[2]: GRU decoder
+if "decode_cfg3" in only:
+    out["decode_cfg3"] = decode(dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024), _arg("--dump-sample"))
+
+# ---- LSTM decoders: the persistent machine (PARROT_SAMPLE_PERSIST=1, the default) against the per-step launches
+# (PARROT_SAMPLE_PERSIST=0), each run in a child process of its own, on / off alternating so the spread is visible
+for name in LSTM_SHAPES:
+    if name not in only:
+        continue
+    runs = {"machine": [], "launches": []}
+    for rep in range(int(_arg("--reps", "3"))):
+        for key, val in (("machine", "1"), ("launches", "0")):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name], capture_output=True, text=True,
+                               env=dict(os.environ, PARROT_SAMPLE_PERSIST=val), timeout=600)
+            if r.returncode != 0:  # (a fault in a child ends the measurement: nothing more is started on the device)
+                sys.stderr.write(r.stdout + r.stderr)
+                sys.exit(r.returncode)
+            res = json.loads(r.stdout.strip().splitlines()[-1])
+            assert (res["machine"] != 0) == (key == "machine"), (key, res)
+            runs[key].append(res["us_per_step"])
+    out[name] = {"batch": 16, "frames": 1000, "us_per_step_machine": runs["machine"], "us_per_step_launches": runs["launches"],
+                 "machine_faster": max(runs["machine"]) < min(runs["launches"])}
 
 # ---- configs[4]: SampleRNN 3-tier GRU D=1024, batch 32, greedy, 16 kHz mu-law
-from parrot_amd.sampleRNN import lib
-from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-lib.delete_all_params(); lib.set_device(dev)
-tt.configure(DIM=1024, EMB_SIZE=256)
-B, T = 32, 26  # 25 generated big frames = 2000 samples per stream
-seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-with torch.no_grad():  # registers all parameters with the reference initialisation
-    tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                    torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
-gen = tt.DeviceGenerator(B, T, temperature=0.0)
-feats = torch.randn(T, B, 63, generator=g).numpy()
-for rep in range(2):
-    torch.cuda.synchronize(); t0 = time.time()
-    s = gen.generate(feats)
-    torch.cuda.synchronize(); dt = time.time() - t0
-nsamp = (T - 1) * 80
-out["samplernn_cfg5"] = {"batch": B, "samples_per_stream": nsamp, "seconds": round(dt, 4),
-                         "us_per_sample_step": round(1e6 * dt / nsamp, 2),
-                         "samples_per_s": round(B * nsamp / dt, 1),
-                         "x_realtime_per_stream": round(nsamp / dt / 16000.0, 3)}
-gen.close()
+if "samplernn_cfg5" in only:
+    from parrot_amd.sampleRNN import lib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    lib.delete_all_params(); lib.set_device(dev)
+    tt.configure(DIM=1024, EMB_SIZE=256)
+    B, T = 32, 26  # 25 generated big frames = 2000 samples per stream
+    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+    with torch.no_grad():  # registers all parameters with the reference initialisation
+        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
+                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    gen = tt.DeviceGenerator(B, T, temperature=0.0)
+    feats = torch.randn(T, B, 63, generator=g).numpy()
+    for rep in range(2):
+        torch.cuda.synchronize(); t0 = time.time()
+        s = gen.generate(feats)
+        torch.cuda.synchronize(); dt = time.time() - t0
+    nsamp = (T - 1) * 80
+    out["samplernn_cfg5"] = {"batch": B, "samples_per_stream": nsamp, "seconds": round(dt, 4),
+                             "us_per_sample_step": round(1e6 * dt / nsamp, 2),
+                             "samples_per_s": round(B * nsamp / dt, 1),
+                             "x_realtime_per_stream": round(nsamp / dt / 16000.0, 3)}
+    gen.close()
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
-from parrot_amd import ops
-x = torch.randn(32, 128000, device=dev)
-for rep in range(3):
-    torch.cuda.synchronize(); t0 = time.time()
-    for _ in range(20):
-        q = ops.batch_quantize(x, 256, "mu-law")
-    torch.cuda.synchronize(); dt = (time.time() - t0) / 20
-out["mulaw"] = {"elements": x.numel(), "us": round(1e6 * dt, 1), "GBps_alg": round(x.numel() * 6 / dt * 1e-9, 1)}
+if "mulaw" in only:
+    from parrot_amd import ops
+    x = torch.randn(32, 128000, device=dev)
+    for rep in range(3):
+        torch.cuda.synchronize(); t0 = time.time()
+        for _ in range(20):
+            q = ops.batch_quantize(x, 256, "mu-law")
+        torch.cuda.synchronize(); dt = (time.time() - t0) / 20
+    out["mulaw"] = {"elements": x.numel(), "us": round(1e6 * dt, 1), "GBps_alg": round(x.numel() * 6 / dt * 1e-9, 1)}
 print(json.dumps(out))

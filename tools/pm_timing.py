@@ -1,6 +1,6 @@
 """Phase timers of the persistent phase machine: per slot, the time the workgroups spend in their units and at the
 barrier, per tick [us].  MODE=train (default): forward scan of the bench shape (PARROT_SCHEDULE=4); MODE=decode:
-BASELINE configs[2] (batch 16, H=1024, weak feedback)."""
+BASELINE configs[2] (batch 16, H=1024, weak feedback); CELL=lstm H=1536 L=3: the same loop for an LSTM stack (L + 2 phases)."""
 import os
 import sys
 import time
@@ -14,7 +14,8 @@ os.environ.setdefault("PARROT_SCHEDULE", "4")
 from parrot_amd.model import Parrot  # noqa: E402
 
 dev = torch.device("cuda:0")
-H, L = 1024, int(os.environ.get("L", "2"))
+H, L = int(os.environ.get("H", "1024")), int(os.environ.get("L", "2"))
+CELL = os.environ.get("CELL", "gru")
 g = torch.Generator().manual_seed(1234)
 if MODE == "train":
     T, B, U = 800, 64, 200
@@ -36,7 +37,7 @@ if MODE == "train":
 else:
     N, U, S = 16, 100, 1000
     m = Parrot(device=dev, use_graph=True, seed=1234, num_layers=L, rnn_h_dim=H, readouts_dim=H,
-               encoder_type='bidirectional', weak_feedback=True).initialize()
+               encoder_type='bidirectional', weak_feedback=True, cell_type=CELL).initialize()
     lab = torch.randint(0, 43, (N, U), generator=g)
     lm = torch.ones(N, U)
     for it in range(3):
@@ -50,7 +51,7 @@ else:
     pieces = os.environ.get("PARROT_PM_PIECES", "1") != "0"  # plans_decode.hip build_persist_pieces: 2L + 2 phases, S + 1 ticks
     from parrot_amd import _lib as _plib
     kind = int(_plib.load().parrot_sample_is_persistent(m._sample_ws.get((S, N, U))['plan']))
-    ticks, nslots = {3: (S + 2, 2 * L + 1), 2: (S + 1, 2 * L + 2)}.get(kind, (S, 2 * L + 3))
+    ticks, nslots = {3: (S + 2, 2 * L + 1), 2: (S + 1, 2 * L + 2)}.get(kind, (S, L + 2 if CELL == "lstm" else 2 * L + 3))
     print(f"plan kind {kind}: {nslots} phases per step")
 rawi = pw[1024:1024 + 256 * 48].view(torch.int64).cpu().reshape(256, 24)
 bad = [w for w in range(256) if rawi[w, 0] > 10**12 or rawi[w, 0] < 0]
