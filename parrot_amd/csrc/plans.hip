@@ -2,7 +2,7 @@
 // the reference (model.py:726-737, 1038-1057; ops.py:299-327) become fixed launch sequences of the
 // fused step kernels, captured once into a hipGraph and replayed per window (all pointers in a
 // plan are fixed, so a replay costs one hipGraphLaunch instead of thousands of host launches).
-#include "plans_common.h"
+#include "pm_builder.h"
 #include "switches.h"
 
 namespace {
@@ -269,14 +269,14 @@ struct DecoderPlan : PlanBase {
     // IG_l(q - 2l + 1).  Every unit's inputs were published at least one barrier earlier (see the lag arithmetic in
     // DESIGN.md).  Units are spread over the workgroups greedily; a unit's weight slab stays in the workgroup's LDS
     // for the whole window when it fits (critical recurrent units first), otherwise it is streamed.
+    // The carve-up of the workspace, the descriptors, the capacity checks, placement and upload are PmBuilder's
+    // (pm_builder.h, shared with the decode planners); build_persist says which slabs and units there are.
     bool persist_ok = false;
     enum { PERSIST_MAXPIECES = 4, TR_SLOTS = 3, TR_MAXU = 3 };
     PmProgram pm_prog;
     static long long persist_floats(const ParrotDecoderDesc& d, int nwg) {
-        const int MB = d.B <= 16 ? 1 : (d.B <= 32 ? 2 : 4);
-        const long long rows = (long long)MB * 16;
-        long long n = PM_SYNC_WORDS + PM_DBG_WORDS;
-        n += ((long long)TR_SLOTS * nwg * TR_MAXU * sizeof(PmUnit) + 3) / 4 + 64;
+        const long long rows = pm_rows(d.B);
+        long long n = pm_header_floats((long long)TR_SLOTS * nwg * TR_MAXU);
         n += 2 * (long long)(d.T + 1) * rows * (d.H + d.E);                       // XG0, XC0
         for (int l = 1; l < d.L; ++l)
             n += 2 * (long long)(d.T + 1) * rows * d.H + (long long)d.T * rows * (d.E + l * d.H);  // XG_l, XC_l, XI_l
@@ -298,15 +298,9 @@ struct DecoderPlan : PlanBase {
         const int nwg = pm_max_workgroups();
         if (d.persist_ws_floats < persist_floats(d, nwg)) return 0;
         const int H = d.H, E = d.E, B = d.B, L = d.L, T = d.T;
-        const int MB = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-        const long long rows = (long long)MB * 16;
         const long long BH = (long long)B * H;
-        // carve the workspace (16-byte aligned pieces)
-        float* ws = d.persist_ws;
-        auto take = [&](long long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
-        unsigned* sync = reinterpret_cast<unsigned*>(take(PM_SYNC_WORDS + PM_DBG_WORDS));
-        const size_t unit_bytes = (size_t)TR_SLOTS * nwg * TR_MAXU * sizeof(PmUnit);
-        PmUnit* units_dev = reinterpret_cast<PmUnit*>(take((long long)(unit_bytes + 3) / 4 + 16));
+        PmBuilder pb(pm_prog, false, d.persist_ws, d.persist_ws_floats, B, nwg, TR_SLOTS, TR_MAXU);
+        const long long rows = pb.rows;
         // activation slabs (fragment-major, one per consumer kind and step):
         //   XG[l][t] = A operand of G_l(t):  l = 0: [h_0[t] ; w[t]],  l >= 1: [h_l[t]]
         //   XC[l][t] = A operand of C_l(t):  l = 0: [r*h_0 ; w[t]],   l >= 1: [r*h_l]
@@ -315,43 +309,30 @@ struct DecoderPlan : PlanBase {
         float* XC[PARROT_MAX_LAYERS];
         float* XI[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
         long long kx[PARROT_MAX_LAYERS], ki[PARROT_MAX_LAYERS] = {0, 0, 0};
-        float* fm_base = ws;
         for (int l = 0; l < L; ++l) {
             kx[l] = l == 0 ? H + E : H;
-            XG[l] = take((long long)(T + 1) * rows * kx[l]);
-            XC[l] = take((long long)(T + 1) * rows * kx[l]);
+            XG[l] = pb.take((long long)(T + 1) * rows * kx[l]);
+            XC[l] = pb.take((long long)(T + 1) * rows * kx[l]);
             if (l >= 1) {
                 ki[l] = E + (long long)l * H;
-                XI[l] = take((long long)T * rows * ki[l]);
+                XI[l] = pb.take((long long)T * rows * ki[l]);
             }
         }
-        const long long fm_bytes = (long long)(ws - fm_base) * 4;
-        if (fm_bytes >= 0xfff00000ll) return 0;  // one 32-bit buffer resource addresses the slab region
+        pb.fm_end();
         // Input projections of the layers l >= 1 are cut into pieces (K ranges of the XI slab) that write separate
         // partial pre-activation buffers; the consuming recurrent unit adds them.  Pieces: the w rows, then per lower
-        // layer its H rows -- whole when the slab can stay LDS-resident, otherwise (streamed) in two halves so that
-        // no streamed unit is longer than a resident recurrent one.
+        // layer its H rows (one piece per lower layer: halves of them measured slower at cfg2 -- every unit carries
+        // ~3.5 us of fixed latency).
         float* pre[PARROT_MAX_LAYERS][2][PERSIST_MAXPIECES];
         memset(pre, 0, sizeof(pre));
-        float* const pre_begin = ws;
+        float* const pre_begin = pb.mark();
         for (int l = 1; l < L; ++l)
             for (int g = 0; g < 2; ++g)
                 for (int q = 0; q < (l == 1 ? PERSIST_MAXPIECES / 2 : PERSIST_MAXPIECES); ++q)
-                    pre[l][g][q] = take((long long)T * B * (g == 0 ? 2 * H : H));
-        float* const pre_end = ws;
-        auto boff = [&](const float* p) { return (unsigned)((p - fm_base) * 4); };
-        auto mkdst = [&](float* slab, long long step0, long long kslab, int chunk) {
-            PmDst q;
-            q.off = boff(slab + step0 * rows * kslab);
-            q.st = (unsigned)(rows * kslab * 4);
-            q.nch = (int)(kslab / 16);
-            q.chunk = chunk;
-            return q;
-        };
+                    pre[l][g][q] = pb.take((long long)T * B * (g == 0 ? 2 * H : H));
+        float* const pre_end = pb.mark();
+        if (pb.failed) return 0;
 
-        std::vector<PmReq> reqs;
-        typedef PmReq Req;
-        auto rm = [](float* p, long long st, int ld) { PmRM r; r.p = p; r.st = st; r.ld = ld; r.pad = 0; return r; };
         auto seq_on = [&](int l, const float* p) { return p && ((d.seq_init >> l) & 1); };
         for (int l = 0; l < L; ++l) {
             const int Kl = krows(l), nchK = Kl / 16;
@@ -362,123 +343,77 @@ struct DecoderPlan : PlanBase {
                 float* sq = g == 0 ? d.seq_g[l] : d.seq_c[l];
                 for (int ct = 0; ct < wd / 16; ++ct) {
                     // recurrent unit (layer 0: the whole product)
-                    Req q;
-                    memset(&q, 0, sizeof(q));
+                    PmReq q = pb.gemm(g, g == 0 ? XG[l] : XC[l], kx[l], 0, (int)kx[l], 2 * l);
                     PmUnit& u = q.u;
-                    u.kind = PM_GEMM; u.lag = 2 * l; u.M = B; u.w_lds = -1;
-                    float* slab = g == 0 ? XG[l] : XC[l];
-                    u.a_off = boff(slab); u.a_st = (unsigned)(rows * kx[l] * 4); u.K = (int)kx[l];
-                    u.a_nch = (int)(kx[l] / 16); u.a_c0 = 0;
                     u.W = Wf + (size_t)ct * nchK * 256;
                     if (l == 0) {
                         u.bias = bias ? bias + 16 * ct : nullptr;
-                        if (seq_on(l, sq)) u.add[0] = rm(sq + 16 * ct, (long long)B * wd, wd);
+                        if (seq_on(l, sq)) pb.add_operand(u, pm_rm(sq + 16 * ct, (long long)B * wd, wd));
                     }
                     if (g == 0) {
                         u.epi = PM_EPI_GATES;
                         u.rtile = 16 * ct >= H;
                         if (!u.rtile) {
-                            u.o1 = rm(d.z[l] + 16 * ct, BH, H);
+                            u.o1 = pm_rm(d.z[l] + 16 * ct, BH, H);
                         } else {
                             const int j0 = 16 * ct - H;
-                            u.o2 = rm(d.r[l] + j0, BH, H);
-                            u.e0 = rm(d.h[l] + j0, BH, H);
-                            u.out = rm(d.rh[l] + j0, BH, H);
-                            u.dst[u.ndst++] = mkdst(XC[l], 0, kx[l], j0 / 16);
+                            u.o2 = pm_rm(d.r[l] + j0, BH, H);
+                            u.e0 = pm_rm(d.h[l] + j0, BH, H);
+                            u.out = pm_rm(d.rh[l] + j0, BH, H);
+                            pb.add_dst(u, pb.dst(XC[l], 0, kx[l], j0 / 16));
                         }
                     } else {
                         u.epi = PM_EPI_CAND;
-                        u.e0 = rm(d.h[l] + 16 * ct, BH, H);
-                        u.e1 = rm(d.z[l] + 16 * ct, BH, H);
-                        u.o1 = rm(d.c[l] + 16 * ct, BH, H);
-                        u.out = rm(d.h[l] + BH + 16 * ct, BH, H);
-                        u.dst[u.ndst++] = mkdst(XG[l], 1, kx[l], ct);               // h_l[t+1] for G_l(t+1)
+                        u.e0 = pm_rm(d.h[l] + 16 * ct, BH, H);
+                        u.e1 = pm_rm(d.z[l] + 16 * ct, BH, H);
+                        u.o1 = pm_rm(d.c[l] + 16 * ct, BH, H);
+                        u.out = pm_rm(d.h[l] + BH + 16 * ct, BH, H);
+                        pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ct));                  // h_l[t+1] for G_l(t+1)
                         for (int m2 = l + 1; m2 < L; ++m2)                            // ... and for the layers above
-                            u.dst[u.ndst++] = mkdst(XI[m2], 0, ki[m2], E / 16 + l * (H / 16) + ct);
+                            pb.add_dst(u, pb.dst(XI[m2], 0, ki[m2], E / 16 + l * (H / 16) + ct));
                     }
-                    q.slot = g; q.crit = 1;
-                    q.krows = (int)kx[l];
-                    if (l == 0) { reqs.push_back(q); continue; }
-                    // input projection of the layer, one tick ahead of its consumer, in pieces
-                    struct Piece { int c0, K; };
-                    std::vector<Piece> pieces;
-                    pieces.push_back({0, E});
-                    // (one piece per lower layer: halves of them measured slower at cfg2 -- every unit carries ~3.5 us of
-                    // fixed latency)
-                    for (int j = 0; j < l; ++j) pieces.push_back({E / 16 + j * (H / 16), H});
-                    int na = 0;
-                    for (size_t pi = 0; pi < pieces.size(); ++pi) {
-                        Req qi;
-                        memset(&qi, 0, sizeof(qi));
+                    // input projection of the layer (l >= 1), one tick ahead of its consumer: piece 0 = the w rows,
+                    // piece 1 + j = the rows of h_j
+                    for (int pi = 0; l >= 1 && pi <= l; ++pi) {
+                        const int c0 = pi == 0 ? 0 : E / 16 + (pi - 1) * (H / 16), K = pi == 0 ? E : H;
+                        PmReq qi = pb.gemm(g == 0 ? 2 : 1, XI[l], ki[l], c0, K, 2 * l - 1);
                         PmUnit& v = qi.u;
-                        v.kind = PM_GEMM; v.lag = 2 * l - 1; v.M = B; v.w_lds = -1;
-                        v.a_off = boff(XI[l]); v.a_st = (unsigned)(rows * ki[l] * 4);
-                        v.a_nch = (int)(ki[l] / 16); v.a_c0 = pieces[pi].c0; v.K = pieces[pi].K;
-                        v.W = Wf + ((size_t)ct * nchK + H / 16 + pieces[pi].c0) * 256;
+                        v.W = Wf + ((size_t)ct * nchK + H / 16 + c0) * 256;
                         if (pi == 0) {
                             v.bias = bias ? bias + 16 * ct : nullptr;
-                            if (seq_on(l, sq)) v.add[0] = rm(sq + 16 * ct, (long long)B * wd, wd);
+                            if (seq_on(l, sq)) pb.add_operand(v, pm_rm(sq + 16 * ct, (long long)B * wd, wd));
                         }
                         v.epi = PM_EPI_LINEAR;
-                        v.out = rm(pre[l][g][pi] + 16 * ct, (long long)B * wd, wd);
-                        u.add[na++] = rm(pre[l][g][pi] + 16 * ct, (long long)B * wd, wd);
-                        qi.slot = g == 0 ? 2 : 1; qi.crit = 0;
-                        qi.krows = pieces[pi].K;
-                        reqs.push_back(qi);
+                        v.out = pm_rm(pre[l][g][pi] + 16 * ct, (long long)B * wd, wd);
+                        pb.add_operand(u, v.out);
+                        qi.crit = 0;
+                        pb.push(qi);
                     }
-                    reqs.push_back(q);
+                    pb.push(q);
                 }
             }
         }
-        for (int b = 0; b < B; ++b) {
-            Req q;
-            memset(&q, 0, sizeof(q));
-            q.u.kind = PM_ATT; q.u.lag = 0; q.u.row = b; q.u.w_lds = -1;
-            q.slot = 2; q.crit = 1; q.krows = 0;
-            reqs.push_back(q);
-        }
-        std::vector<PmUnit> table;
-        if (!pm_place(reqs, TR_SLOTS, TR_MAXU, nwg, table)) return 0;
-        if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) return 0;
+        pb.att_rows(2, 0);
 
-        PmProgram& P = pm_prog;
-        memset(&P, 0, sizeof(P));
-        P.T = T; P.n_ticks = T + 2 * (L - 1); P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = TR_SLOTS; P.maxu = TR_MAXU;
-        P.units = units_dev; P.sync = sync; P.fm_base = fm_base;
-        PmAtt& a = P.att;
-        a.h1 = rm(d.h[0], BH, H);
-        a.WattT = d.WattT; a.batt = d.batt; a.ctx = d.ctx;
-        a.kappa = d.kappa; a.a = d.a; a.b = d.b; a.phi = d.phi; a.w = d.w;
-        a.sup = d.att_sup;
-        a.wdst[a.nwdst++] = mkdst(XG[0], 1, kx[0], H / 16);   // w[t+1] for G_0(t+1) and C_0(t+1) ...
-        a.wdst[a.nwdst++] = mkdst(XC[0], 1, kx[0], H / 16);
-        for (int l = 1; l < L; ++l) a.wdst[a.nwdst++] = mkdst(XI[l], 0, ki[l], 0);  // ... and for the layers above
-        a.B = B; a.H = H; a.A = d.A; a.U = d.U; a.E = E; a.att_type = d.att_type;
-        a.dense = sw_att_dense();
-        a.eps = d.eps; a.alignment = d.alignment; a.sharpening = d.sharpening; a.timing = d.timing;
-        int ni = 0;
-        auto add_init = [&](const float* src, int ld, int K, float* slab, long long kslab, int chunk) {
-            PmInit& in = P.init[ni++];
-            in.src = src; in.ld = ld; in.K = K; in.dst_off = boff(slab); in.nch = (int)(kslab / 16); in.chunk = chunk;
-            in.pad = 0;
-        };
-        for (int l = 0; l < L; ++l) add_init(d.h[l], H, H, XG[l], kx[l], 0);  // states entering the window (slot 0)
-        add_init(d.w, E, E, XG[0], kx[0], H / 16);
-        add_init(d.w, E, E, XC[0], kx[0], H / 16);
-        P.ninit = ni;
+        pb.att_common(d, d.h[0]);
+        PmAtt& a = pm_prog.att;
+        a.b = d.b; a.sup = d.att_sup; a.dense = sw_att_dense();
+        pb.add_wdst(pb.dst(XG[0], 1, kx[0], H / 16));   // w[t+1] for G_0(t+1) and C_0(t+1) ...
+        pb.add_wdst(pb.dst(XC[0], 1, kx[0], H / 16));
+        for (int l = 1; l < L; ++l) pb.add_wdst(pb.dst(XI[l], 0, ki[l], 0));  // ... and for the layers above
+        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XG[l], kx[l], 0);  // states entering the window (slot 0)
+        pb.add_init(d.w, E, E, XG[0], kx[0], H / 16);
+        pb.add_init(d.w, E, E, XC[0], kx[0], H / 16);
         // dataflow mode: everything a unit reads from another workgroup starts EMPTY (slot 0 of the histories is the
         // caller's: the states entering the window)
-        P.dataflow = sw_pm_dataflow(0);
-        auto add_fill = [&](void* q, long long nfloats) {
-            if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
-        };
-        add_fill(fm_base, fm_bytes / 4);
-        add_fill(pre_begin, (long long)(pre_end - pre_begin));
+        pm_prog.dataflow = sw_pm_dataflow(0);
+        pb.fill_fm();
+        pb.add_fill(pre_begin, (long long)(pre_end - pre_begin));
         for (int l = 0; l < L; ++l) {
-            add_fill(d.h[l] + BH, (long long)T * BH);
-            add_fill(d.z[l], (long long)T * BH);
+            pb.add_fill(d.h[l] + BH, (long long)T * BH);
+            pb.add_fill(d.z[l], (long long)T * BH);
         }
-        persist_ok = true;
+        persist_ok = pb.finish(T, T + 2 * (L - 1));
         return 0;
     }
     int persist_status() const { return persist_ok ? pm_status(pm_prog) : 0; }

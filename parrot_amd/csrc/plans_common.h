@@ -1,6 +1,7 @@
 // Shared by the scan plans (plans.hip: training) and the decode planner (plans_decode.hip): the plan base class with its
 // hipGraph capture / replay, the schedule tracer behind parrot_decoder_trace, the traced launch helpers, and the unit
-// placement of the persistent phase machine.  Everything has internal linkage (one copy per translation unit).
+// placement of the persistent phase machine (the program builder on top of it: pm_builder.h).  Everything has internal
+// linkage (one copy per translation unit).
 #pragma once
 #include <stdlib.h>
 #include <string.h>

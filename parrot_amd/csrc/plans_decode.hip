@@ -1,12 +1,75 @@
 // The decode loop of Parrot.sample_model_fun (model.py:882-1057) as a plan: per-step launches in one hipGraph, or the
-// whole loop as ONE resident kernel on the persistent phase machine (persist.h) -- 2L + 3 whole-K phases (round 2),
-// 2L + 2 phases with every product cut along K by the age of its operands (round 4), 2L + 1 with the fed-back frame out
-// of the step's dependency chain (round 5); LSTM stacks: L + 2 whole-K phases (build_persist_lstm).  The planner, its
-// symbolic checker and the parrot_sample_* entry points.
-#include "plans_common.h"
+// whole loop as ONE resident kernel on the persistent phase machine (persist.h) -- 2L + 3 whole-K phases (round 2,
+// build_persist_whole), 2L + 2 phases with every product cut along K by the age of its operands (round 4), 2L + 1 with
+// the fed-back frame out of the step's dependency chain (round 5; both build_persist_pieces); LSTM stacks: L + 2 whole-K
+// phases (build_persist_lstm).  SamplePlan::plan_persist picks the program; every planner emits its slabs, units and
+// symbolic-replay metas through the shared builder (pm_builder.h), which carves the workspace within its bounds, checks
+// the table capacities, places and uploads.  Then the per-step launch path and the parrot_sample_* entry points.
+#include "pm_builder.h"
 #include "switches.h"
 
 namespace {
+
+// ----------------------------------------------------------------------------- planner vocabulary
+// A product cut along K (build_persist_pieces): a group is one product of the step, a piece a chunk range of its slab.
+struct PmPiece {
+    int c0, nch, gp;  // chunk range of the slab; position (phase index over two ticks) after which the operand exists
+    bool crit;
+    int lag, slot, pbuf;
+};
+struct PmGroup {
+    int kind, l, slot, N, res;  // kind 0 gates, 1 candidate, 2 output, 3 x_pre (fbc); res = checker resource id of the slab
+    int glag;                   // the group's critical unit runs `glag` ticks after the step's other main units
+    long long ks;
+    std::vector<PmPiece> pc;
+};
+// The symbolic replay's view of a program: per unit kind what it reads and writes, slabs by chunk, histories as one
+// element per step.
+struct PmAccess { int res, dstep, c0, nch; };
+struct PmMeta { int lag, slot; std::vector<PmAccess> rd, wr; };
+enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63, RES_C = 70,
+       RES_PART = 100 };
+PmAccess pm_acc(int res, int dstep, int c0, int nch) { PmAccess a; a.res = res; a.dstep = dstep; a.c0 = c0; a.nch = nch; return a; }
+
+// symbolic replay over S steps: 0 = every read finds its value written in an earlier phase and nothing is written twice
+int check_pieces(const std::vector<PmMeta>& metas, const std::vector<PmAccess>& init, int n_slots, int S,
+                        int n_ticks) {
+    std::vector<std::array<int, 3>> written;  // (res, step, chunk), kept sorted
+    auto has = [&](int r, int t, int c) {
+        const std::array<int, 3> k = {r, t, c};
+        return std::binary_search(written.begin(), written.end(), k);
+    };
+    auto put = [&](int r, int t, int c) {
+        const std::array<int, 3> k = {r, t, c};
+        auto it = std::lower_bound(written.begin(), written.end(), k);
+        if (it != written.end() && *it == k) return false;
+        written.insert(it, k);
+        return true;
+    };
+    for (const PmAccess& a : init)
+        for (int c = a.c0; c < a.c0 + a.nch; ++c)
+            if (!put(a.res, a.dstep, c)) return 1;
+    for (int tick = 0; tick < n_ticks; ++tick)
+        for (int s = 0; s < n_slots; ++s) {
+            for (const PmMeta& m : metas) {
+                const int t = tick - m.lag;
+                if (m.slot != s || t < 0 || t >= S) continue;
+                for (const PmAccess& a : m.rd)
+                    for (int c = a.c0; c < a.c0 + a.nch; ++c)
+                        if (!has(a.res, t + a.dstep, c)) return 2;
+            }
+            for (const PmMeta& m : metas) {
+                const int t = tick - m.lag;
+                if (m.slot != s || t < 0 || t >= S) continue;
+                for (const PmAccess& a : m.wr)
+                    for (int c = a.c0; c < a.c0 + a.nch; ++c)
+                        if (!put(a.res, t + a.dstep, c)) return 3;
+            }
+        }
+    for (int t = 1; t <= S; ++t)
+        if (!has(RES_X, t, 0)) return 4;
+    return 0;
+}
 
 // ----------------------------------------------------------------------------- decoder (sampling)
 struct SamplePlan : PlanBase {
@@ -52,206 +115,165 @@ struct SamplePlan : PlanBase {
     static int fb_rows(const ParrotSampleDesc& d, int l) { return d.Wfg[l] ? 64 : 0; }
     static long long kslab(const ParrotSampleDesc& d, int l) { return d.H + d.E + (long long)l * d.H + fb_rows(d, l); }
     static long long persist_floats(const ParrotSampleDesc& d, int nwg) {
-        const int MB = d.B <= 16 ? 1 : (d.B <= 32 ? 2 : 4);
-        const long long rows = (long long)MB * 16, S = d.S;
-        long long n = PM_SYNC_WORDS + PM_DBG_WORDS;
+        const long long rows = pm_rows(d.B), S = d.S;
         if (d.cell == 1) {  // one slab per layer, the composed output's slab, h and c histories (build_persist_lstm)
-            n += ((long long)(d.L + 2) * nwg * 2 * sizeof(PmUnit) + 3) / 4 + 64;
+            long long n = pm_header_floats((long long)(d.L + 2) * nwg * 2);
             for (int l = 0; l < d.L; ++l) n += (S + 1) * rows * kslab(d, l);
             n += S * rows * ((long long)d.L * d.H + d.E);
             n += 2 * (long long)d.L * (S + 1) * d.B * d.H + S * d.B * d.A;
             return n + 4096;
         }
-        n += ((long long)(2 * d.L + 3) * nwg * sizeof(PmUnit) + 3) / 4 + 64;
+        long long n = pm_header_floats((long long)(2 * d.L + 3) * nwg);
         for (int l = 0; l < d.L; ++l) n += 2 * (S + 1) * rows * kslab(d, l);
         n += S * rows * ((long long)d.L * d.H + d.E) + S * rows * d.R;
         n += (long long)d.L * (S + 1) * d.B * d.H + (long long)d.L * S * d.B * d.H;   // h and z histories (row-major)
         n += S * d.B * d.R + S * d.B * d.A;
         return n + piece_floats(d) + 4096;
     }
+    // the bound of a planner's carve-up: the caller's workspace; dry runs carve what the size query asks for
+    long long ws_limit(bool dry, int nwg) const { return dry ? persist_floats(d, nwg) : d.persist_ws_floats; }
 
+    // The one planning entry: the program the descriptor and the switches ask for.  dry: plan, place and check only, on
+    // nwg_dry workgroups, no device memory is touched (parrot_sample_plan_pieces_dry: the CPU tests; the whole-K phases
+    // have no dry mode).
+    void plan_persist(bool dry, int nwg_dry) {
+        if (d.cell == 1) {
+            build_persist_lstm(dry, nwg_dry);
+            return;
+        }
+        if (pieces_wanted(d)) build_persist_pieces(dry, nwg_dry);  // the step cut along K by the age of its operands
+        if (!persist_ok && !dry) build_persist_whole();            // else the 2L + 3 whole-K phases
+    }
     int build_persist() {
         persist_ok = false;
         if (env_int("PARROT_SAMPLE_PERSIST", 1) == 0) return 0;
         if (!persist_eligible(d) || !d.persist_ws) return 0;
-        if (d.cell == 1) return build_persist_lstm(false, 0);
-        if (pieces_wanted(d)) {  // the step cut along K by the age of its operands (below); else the 2L + 3 whole-K phases
-            build_persist_pieces(false, 0);
-            if (persist_ok) return 0;
-        }
+        plan_persist(false, 0);
+        return 0;
+    }
+
+    int build_persist_whole() {
         if (!legacy_eligible(d)) return 0;
         const int nwg = pm_max_workgroups();
         if (d.persist_ws_floats < persist_floats(d, nwg)) return 0;
         const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S, R = d.R;
-        const int MB = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-        const long long rows = (long long)MB * 16, BH = (long long)B * H;
-        const int n_slots = 2 * L + 3;
-        float* ws = d.persist_ws;
-        auto take = [&](long long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
-        unsigned* sync = reinterpret_cast<unsigned*>(take(PM_SYNC_WORDS + PM_DBG_WORDS));
-        const size_t unit_bytes = (size_t)n_slots * nwg * sizeof(PmUnit);
-        PmUnit* units_dev = reinterpret_cast<PmUnit*>(take((long long)(unit_bytes + 3) / 4 + 16));
-        float* fm_base = ws;
+        const long long BH = (long long)B * H;
+        PmBuilder pb(pm_prog, false, d.persist_ws, d.persist_ws_floats, B, nwg, 2 * L + 3, 1);
+        const long long rows = pb.rows;
         float* XG[PARROT_MAX_LAYERS];
         float* XC[PARROT_MAX_LAYERS];
         long long kx[PARROT_MAX_LAYERS];
         for (int l = 0; l < L; ++l) {
             kx[l] = kslab(d, l);
-            XG[l] = take((S + 1) * rows * kx[l]);
-            XC[l] = take((S + 1) * rows * kx[l]);
+            XG[l] = pb.take((S + 1) * rows * kx[l]);
+            XC[l] = pb.take((S + 1) * rows * kx[l]);
         }
         const long long kr = (long long)L * H + E;
-        float* XR = take(S * rows * kr);
-        float* XO = take(S * rows * R);
-        if ((long long)(ws - fm_base) * 4 >= 0xfff00000ll) return 0;
-        float* const fm_end = ws;
+        float* XR = pb.take(S * rows * kr);
+        float* XO = pb.take(S * rows * R);
+        pb.fm_end();
         float* zh[PARROT_MAX_LAYERS];
-        for (int l = 0; l < L; ++l) hist_h[l] = take((S + 1) * BH);
-        for (int l = 0; l < L; ++l) zh[l] = take(S * BH);
-        float* ro_hist = take((long long)S * B * R);
-        float* b_hist = take((long long)S * B * d.A);
+        for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
+        for (int l = 0; l < L; ++l) zh[l] = pb.take(S * BH);
+        float* ro_hist = pb.take((long long)S * B * R);
+        float* b_hist = pb.take((long long)S * B * d.A);
+        if (pb.failed) return 0;
 
-        auto boff = [&](const float* p) { return (unsigned)((p - fm_base) * 4); };
-        auto mkdst = [&](float* slab, long long step0, long long ks, int chunk) {
-            PmDst q;
-            q.off = boff(slab + step0 * rows * ks); q.st = (unsigned)(rows * ks * 4); q.nch = (int)(ks / 16); q.chunk = chunk;
-            return q;
-        };
-        auto rm = [](const float* p, long long st, int ld) { PmRM r; r.p = const_cast<float*>(p); r.st = st; r.ld = ld; r.pad = 0; return r; };
-        std::vector<PmReq> reqs;
-        auto gemm_unit = [&](int slot, float* slab, long long ks) {
-            PmReq q;
-            memset(&q, 0, sizeof(q));
-            q.u.kind = PM_GEMM; q.u.M = B; q.u.w_lds = -1;
-            q.u.a_off = boff(slab); q.u.a_st = (unsigned)(rows * ks * 4); q.u.a_nch = (int)(ks / 16); q.u.K = (int)ks;
-            q.slot = slot; q.crit = 1; q.krows = (int)ks;
-            return q;
-        };
         for (int l = 0; l < L; ++l) {
-            const int sg = l == 0 ? 0 : 2 * l + 1, sc = sg + 1;
+            const int sg = slotG(l), sc = slotC(l);
             const int nch = (int)(kx[l] / 16);
             for (int ct = 0; ct < 2 * H / 16; ++ct) {     // gates
-                PmReq q = gemm_unit(sg, XG[l], kx[l]);
+                PmReq q = pb.gemm(sg, XG[l], kx[l]);
                 PmUnit& u = q.u;
                 u.W = d.Wg_t[l] + (size_t)ct * nch * 256;
                 u.bias = d.bg[l] ? d.bg[l] + 16 * ct : nullptr;
-                if (d.seq_g[l]) u.add[0] = rm(d.seq_g[l] + 16 * ct, 0, 2 * H);
+                if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 16 * ct, 0, 2 * H));
                 u.epi = PM_EPI_GATES;
                 u.rtile = 16 * ct >= H;
                 if (!u.rtile) {
-                    u.o1 = rm(zh[l] + 16 * ct, BH, H);
+                    u.o1 = pm_rm(zh[l] + 16 * ct, BH, H);
                 } else {
                     const int j0 = 16 * ct - H;
-                    u.e0 = rm(hist_h[l] + j0, BH, H);
-                    u.dst[u.ndst++] = mkdst(XC[l], 0, kx[l], j0 / 16);
+                    u.e0 = pm_rm(hist_h[l] + j0, BH, H);
+                    pb.add_dst(u, pb.dst(XC[l], 0, kx[l], j0 / 16));
                 }
-                reqs.push_back(q);
+                pb.push(q);
             }
             for (int ct = 0; ct < H / 16; ++ct) {         // candidate -> h_l[t+1]
-                PmReq q = gemm_unit(sc, XC[l], kx[l]);
+                PmReq q = pb.gemm(sc, XC[l], kx[l]);
                 PmUnit& u = q.u;
                 u.W = d.Wc_t[l] + (size_t)ct * nch * 256;
                 u.bias = d.bc[l] ? d.bc[l] + 16 * ct : nullptr;
-                if (d.seq_c[l]) u.add[0] = rm(d.seq_c[l] + 16 * ct, 0, H);
+                if (d.seq_c[l]) pb.add_operand(u, pm_rm(d.seq_c[l] + 16 * ct, 0, H));
                 u.epi = PM_EPI_CAND;
-                u.e0 = rm(hist_h[l] + 16 * ct, BH, H);
-                u.e1 = rm(zh[l] + 16 * ct, BH, H);
-                u.out = rm(hist_h[l] + BH + 16 * ct, BH, H);
-                u.dst[u.ndst++] = mkdst(XG[l], 1, kx[l], ct);
+                u.e0 = pm_rm(hist_h[l] + 16 * ct, BH, H);
+                u.e1 = pm_rm(zh[l] + 16 * ct, BH, H);
+                u.out = pm_rm(hist_h[l] + BH + 16 * ct, BH, H);
+                pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ct));
                 for (int m2 = l + 1; m2 < L; ++m2) {
                     const int ch = (H + E) / 16 + l * (H / 16) + ct;
-                    u.dst[u.ndst++] = mkdst(XG[m2], 0, kx[m2], ch);
-                    u.dst[u.ndst++] = mkdst(XC[m2], 0, kx[m2], ch);
+                    pb.add_dst(u, pb.dst(XG[m2], 0, kx[m2], ch));
+                    pb.add_dst(u, pb.dst(XC[m2], 0, kx[m2], ch));
                 }
-                u.dst[u.ndst++] = mkdst(XR, 0, kr, l * (H / 16) + ct);
-                if (u.ndst > PM_MAXDST) return 0;
-                reqs.push_back(q);
+                pb.add_dst(u, pb.dst(XR, 0, kr, l * (H / 16) + ct));
+                pb.push(q);
             }
         }
-        for (int b = 0; b < B; ++b) {
-            PmReq q;
-            memset(&q, 0, sizeof(q));
-            q.u.kind = PM_ATT; q.u.row = b; q.u.w_lds = -1;
-            q.slot = 2; q.crit = 1; q.krows = 0;
-            reqs.push_back(q);
-        }
+        pb.att_rows(2, 0);
         for (int ct = 0; ct < R / 16; ++ct) {             // readout
-            PmReq q = gemm_unit(2 * L + 1, XR, kr);
+            PmReq q = pb.gemm(2 * L + 1, XR, kr);
             PmUnit& u = q.u;
             u.W = d.Wr_t + (size_t)ct * (kr / 16) * 256;
             u.bias = d.br ? d.br + 16 * ct : nullptr;
-            if (d.radd) u.add[0] = rm(d.radd + 16 * ct, 0, R);
+            if (d.radd) pb.add_operand(u, pm_rm(d.radd + 16 * ct, 0, R));
             u.epi = PM_EPI_LINEAR;
-            u.out = rm(ro_hist + 16 * ct, (long long)B * R, R);
-            u.dst[u.ndst++] = mkdst(XO, 0, R, ct);
-            reqs.push_back(q);
+            u.out = pm_rm(ro_hist + 16 * ct, (long long)B * R, R);
+            pb.add_dst(u, pb.dst(XO, 0, R, ct));
+            pb.push(q);
         }
         for (int ct = 0; ct < 4; ++ct) {                  // output frame x[t+1] (63 columns, padded to 64)
-            PmReq q = gemm_unit(2 * L + 2, XO, R);
+            PmReq q = pb.gemm(2 * L + 2, XO, R);
             PmUnit& u = q.u;
             u.W = d.Wo_t + (size_t)ct * (R / 16) * 256;
             u.bias = d.bo_pad + 16 * ct;
-            if (d.oadd_pad) u.add[0] = rm(d.oadd_pad + 16 * ct, 0, 64);
+            if (d.oadd_pad) pb.add_operand(u, pm_rm(d.oadd_pad + 16 * ct, 0, 64));
             u.epi = PM_EPI_LINEAR;
-            u.out = rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
+            u.out = pm_rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
             for (int l = 0; l < L; ++l) {
                 if (!fb_rows(d, l)) continue;
                 const int ch = (int)((kx[l] - 64) / 16) + ct;
-                u.dst[u.ndst++] = mkdst(XG[l], 1, kx[l], ch);
-                u.dst[u.ndst++] = mkdst(XC[l], 1, kx[l], ch);
+                pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ch));
+                pb.add_dst(u, pb.dst(XC[l], 1, kx[l], ch));
             }
-            if (u.ndst > PM_MAXDST) return 0;
-            reqs.push_back(q);
+            pb.push(q);
         }
-        std::vector<PmUnit> table;
-        if (!pm_place(reqs, n_slots, 1, nwg, table)) return 0;
-        if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) return 0;
 
-        PmProgram& P = pm_prog;
-        memset(&P, 0, sizeof(P));
-        P.T = S; P.n_ticks = S; P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = n_slots; P.maxu = 1;
-        P.units = units_dev; P.sync = sync; P.fm_base = fm_base;
-        PmAtt& a = P.att;
-        a.h1 = rm(hist_h[0], BH, H);
-        a.WattT = d.WattT; a.batt = d.batt; a.ctx = d.ctx;
-        a.kappa = d.kappa; a.a = d.a; a.b = b_hist; a.phi = d.phi; a.w = d.w; a.sup = nullptr;
-        a.B = B; a.H = H; a.A = d.A; a.U = d.U; a.E = E; a.att_type = d.att_type; a.dense = 0;
-        a.eps = d.eps; a.alignment = d.alignment; a.sharpening = d.sharpening; a.timing = d.timing;
-        a.wdst[a.nwdst++] = mkdst(XG[0], 1, kx[0], H / 16);
-        a.wdst[a.nwdst++] = mkdst(XC[0], 1, kx[0], H / 16);
+        pb.att_common(d, hist_h[0]);
+        pm_prog.att.b = b_hist;
+        pb.add_wdst(pb.dst(XG[0], 1, kx[0], H / 16));
+        pb.add_wdst(pb.dst(XC[0], 1, kx[0], H / 16));
         for (int l = 1; l < L; ++l) {
-            a.wdst[a.nwdst++] = mkdst(XG[l], 0, kx[l], H / 16);
-            a.wdst[a.nwdst++] = mkdst(XC[l], 0, kx[l], H / 16);
+            pb.add_wdst(pb.dst(XG[l], 0, kx[l], H / 16));
+            pb.add_wdst(pb.dst(XC[l], 0, kx[l], H / 16));
         }
-        a.wdst[a.nwdst++] = mkdst(XR, 0, kr, L * (H / 16));
-        if (a.nwdst > PM_MAXWDST) return 0;
-        int ni = 0;
-        auto add_init = [&](const float* src, int ld, int K, float* slab, long long ks, int chunk) {
-            PmInit& in = P.init[ni++];
-            in.src = src; in.ld = ld; in.K = K; in.dst_off = boff(slab); in.nch = (int)(ks / 16); in.chunk = chunk; in.pad = 0;
-        };
-        for (int l = 0; l < L; ++l) add_init(d.h[l], H, H, XG[l], kx[l], 0);   // initial states (slot 0 of the ping-pong)
-        add_init(d.w, E, E, XG[0], kx[0], H / 16);
-        add_init(d.w, E, E, XC[0], kx[0], H / 16);
+        pb.add_wdst(pb.dst(XR, 0, kr, L * (H / 16)));
+        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XG[l], kx[l], 0);   // initial states (slot 0 of the ping-pong)
+        pb.add_init(d.w, E, E, XG[0], kx[0], H / 16);
+        pb.add_init(d.w, E, E, XC[0], kx[0], H / 16);
         // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states (the slabs start EMPTY in
         // dataflow mode, so "stays at the zero fill" is not enough)
         for (int l = 0; l < L; ++l) {
             if (!fb_rows(d, l)) continue;
-            if (ni + 2 > PM_MAXINIT) return 0;
-            add_init(d.x, d.ldx, 64, XG[l], kx[l], (int)((kx[l] - 64) / 16));
-            add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)((kx[l] - 64) / 16));
+            pb.add_init(d.x, d.ldx, 64, XG[l], kx[l], (int)((kx[l] - 64) / 16));
+            pb.add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)((kx[l] - 64) / 16));
         }
-        P.ninit = ni;
-        P.dataflow = sw_pm_dataflow(0);
-        auto add_fill = [&](void* q, long long nfloats) {
-            if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
-        };
-        add_fill(fm_base, (long long)(fm_end - fm_base));
+        pm_prog.dataflow = sw_pm_dataflow(0);  // (measured no gain without barriers: 57.6 us per step either way at configs[2])
+        pb.fill_fm();
         for (int l = 0; l < L; ++l) {
-            add_fill(hist_h[l] + BH, (long long)S * BH);
-            add_fill(zh[l], (long long)S * BH);
+            pb.add_fill(hist_h[l] + BH, (long long)S * BH);
+            pb.add_fill(zh[l], (long long)S * BH);
         }
-        persist_ok = true;
+        persist_ok = pb.finish(S, S);
         return 0;
     }
     int persist_status() const { return persist_ok ? pm_status(pm_prog) : 0; }
@@ -285,174 +307,120 @@ struct SamplePlan : PlanBase {
         const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S;
         for (int l = 0; l < L && !dry; ++l)
             if (!d.cwork[l]) return 0;
-        const int MB = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-        const long long rows = (long long)MB * 16, BH = (long long)B * H;
+        const long long BH = (long long)B * H;
         const int n_slots = L + 2, sATT = 1, sOUT = L + 1, hc = H / 16, ec = E / 16;
         const int maxu = std::max(H / 4, B) <= nwg ? 1 : 2;
         if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT) return 0;
-        float* ws = dry ? reinterpret_cast<float*>((uintptr_t)0x10000000) : d.persist_ws;
-        auto take = [&](long long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
-        unsigned* sync = reinterpret_cast<unsigned*>(take(PM_SYNC_WORDS + PM_DBG_WORDS));
-        const size_t unit_bytes = (size_t)n_slots * nwg * maxu * sizeof(PmUnit);
-        PmUnit* units_dev = reinterpret_cast<PmUnit*>(take((long long)(unit_bytes + 3) / 4 + 16));
-        float* fm_base = ws;
+        PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, maxu);
+        const long long rows = pb.rows;
         float* XL[PARROT_MAX_LAYERS];
         long long kx[PARROT_MAX_LAYERS];
         for (int l = 0; l < L; ++l) {
             kx[l] = kslab(d, l);
-            XL[l] = take((S + 1) * rows * kx[l]);
+            XL[l] = pb.take((S + 1) * rows * kx[l]);
         }
         const long long kr = (long long)L * H + E;
-        float* XR = take(S * rows * kr);
-        if ((long long)(ws - fm_base) * 4 >= 0xfff00000ll) return 0;
-        float* const fm_end = ws;
-        for (int l = 0; l < L; ++l) hist_h[l] = take((S + 1) * BH);
-        for (int l = 0; l < L; ++l) hist_c[l] = take((S + 1) * BH);
-        float* b_hist = take((long long)S * B * d.A);
+        float* XR = pb.take(S * rows * kr);
+        pb.fm_end();
+        for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
+        for (int l = 0; l < L; ++l) hist_c[l] = pb.take((S + 1) * BH);
+        float* b_hist = pb.take((long long)S * B * d.A);
+        if (pb.failed) return 0;
 
-        auto boff = [&](const float* p) { return (unsigned)((p - fm_base) * 4); };
-        auto mkdst = [&](float* slab, long long step0, long long ks, int chunk) {
-            PmDst q;
-            q.off = boff(slab + step0 * rows * ks); q.st = (unsigned)(rows * ks * 4); q.nch = (int)(ks / 16); q.chunk = chunk;
-            return q;
-        };
-        auto rm = [](const float* p, long long st, int ld) { PmRM r; r.p = const_cast<float*>(p); r.st = st; r.ld = ld; r.pad = 0; return r; };
-        auto acc = [](int res, int dstep, int c0, int nch) { PmAccess a; a.res = res; a.dstep = dstep; a.c0 = c0; a.nch = nch; return a; };
-        auto gemm_unit = [&](int slot, float* slab, long long ks) {
-            PmReq q;
-            memset(&q, 0, sizeof(q));
-            q.u.kind = PM_GEMM; q.u.M = B; q.u.w_lds = -1;
-            q.u.a_off = boff(slab); q.u.a_st = (unsigned)(rows * ks * 4); q.u.a_nch = (int)(ks / 16); q.u.K = (int)ks;
-            q.slot = slot; q.crit = 1; q.krows = (int)ks;
-            return q;
-        };
-        std::vector<PmReq> reqs;
-        std::vector<PmMeta> metas;  // the symbolic replay's view: slabs by chunk, histories as one element per step
+        std::vector<PmMeta> metas;
         for (int l = 0; l < L; ++l) {
             const int nch = (int)(kx[l] / 16);
             PmMeta m;
             m.lag = 0; m.slot = slotL(l);
-            m.rd.push_back(acc(RES_XG + l, 0, 0, nch));
-            m.rd.push_back(acc(RES_C + l, 0, 0, 1));
-            m.wr.push_back(acc(RES_C + l, 1, 0, 1));
-            m.wr.push_back(acc(RES_H + l, 1, 0, 1));
-            m.wr.push_back(acc(RES_XG + l, 1, 0, hc));
-            for (int m2 = l + 1; m2 < L; ++m2) m.wr.push_back(acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
-            m.wr.push_back(acc(RES_XR, 0, l * hc, hc));
+            m.rd.push_back(pm_acc(RES_XG + l, 0, 0, nch));
+            m.rd.push_back(pm_acc(RES_C + l, 0, 0, 1));
+            m.wr.push_back(pm_acc(RES_C + l, 1, 0, 1));
+            m.wr.push_back(pm_acc(RES_H + l, 1, 0, 1));
+            m.wr.push_back(pm_acc(RES_XG + l, 1, 0, hc));
+            for (int m2 = l + 1; m2 < L; ++m2) m.wr.push_back(pm_acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
+            m.wr.push_back(pm_acc(RES_XR, 0, l * hc, hc));
             metas.push_back(m);
             for (int ct = 0; ct < H / 4; ++ct) {
-                PmReq q = gemm_unit(slotL(l), XL[l], kx[l]);
+                PmReq q = pb.gemm(slotL(l), XL[l], kx[l]);
                 PmUnit& u = q.u;
                 u.W = d.Wg_t[l] + (size_t)ct * nch * 256;
                 u.bias = d.bg[l] ? d.bg[l] + 4 * ct : nullptr;
-                if (d.seq_g[l]) u.add[0] = rm(d.seq_g[l] + 4 * ct, 0, 4 * H);
+                if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 4 * ct, 0, 4 * H));
                 u.epi = PM_EPI_LSTM; u.gstr = H; u.rtile = ct & 3;
-                u.e1 = rm(hist_c[l] + 4 * ct, BH, H);
-                u.o1 = rm(hist_c[l] + BH + 4 * ct, BH, H);
-                u.out = rm(hist_h[l] + BH + 4 * ct, BH, H);
-                u.dst[u.ndst++] = mkdst(XL[l], 1, kx[l], ct / 4);
-                for (int m2 = l + 1; m2 < L; ++m2) u.dst[u.ndst++] = mkdst(XL[m2], 0, kx[m2], hc + ec + l * hc + ct / 4);
-                u.dst[u.ndst++] = mkdst(XR, 0, kr, l * hc + ct / 4);
-                if (u.ndst > PM_MAXDST) return 0;
-                reqs.push_back(q);
+                u.e1 = pm_rm(hist_c[l] + 4 * ct, BH, H);
+                u.o1 = pm_rm(hist_c[l] + BH + 4 * ct, BH, H);
+                u.out = pm_rm(hist_h[l] + BH + 4 * ct, BH, H);
+                pb.add_dst(u, pb.dst(XL[l], 1, kx[l], ct / 4));
+                for (int m2 = l + 1; m2 < L; ++m2) pb.add_dst(u, pb.dst(XL[m2], 0, kx[m2], hc + ec + l * hc + ct / 4));
+                pb.add_dst(u, pb.dst(XR, 0, kr, l * hc + ct / 4));
+                pb.push(q);
             }
         }
         {
             PmMeta m;
             m.lag = 0; m.slot = sATT;
-            m.rd.push_back(acc(RES_H, 1, 0, 1));
-            m.rd.push_back(acc(RES_KAPPA, 0, 0, 1));
-            m.wr.push_back(acc(RES_KAPPA, 1, 0, 1));
-            m.wr.push_back(acc(RES_XG, 1, hc, ec));
-            for (int l = 1; l < L; ++l) m.wr.push_back(acc(RES_XG + l, 0, hc, ec));
-            m.wr.push_back(acc(RES_XR, 0, L * hc, ec));
+            m.rd.push_back(pm_acc(RES_H, 1, 0, 1));
+            m.rd.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
+            m.wr.push_back(pm_acc(RES_KAPPA, 1, 0, 1));
+            m.wr.push_back(pm_acc(RES_XG, 1, hc, ec));
+            for (int l = 1; l < L; ++l) m.wr.push_back(pm_acc(RES_XG + l, 0, hc, ec));
+            m.wr.push_back(pm_acc(RES_XR, 0, L * hc, ec));
             metas.push_back(m);
         }
-        for (int b = 0; b < B; ++b) {
-            PmReq q;
-            memset(&q, 0, sizeof(q));
-            q.u.kind = PM_ATT; q.u.row = b; q.u.w_lds = -1;
-            q.slot = sATT; q.crit = 1; q.krows = 0;
-            reqs.push_back(q);
-        }
+        pb.att_rows(sATT, 0);
         {
             PmMeta m;
             m.lag = 0; m.slot = sOUT;
-            m.rd.push_back(acc(RES_XR, 0, 0, (int)(kr / 16)));
-            m.wr.push_back(acc(RES_X, 1, 0, 1));
+            m.rd.push_back(pm_acc(RES_XR, 0, 0, (int)(kr / 16)));
+            m.wr.push_back(pm_acc(RES_X, 1, 0, 1));
             for (int l = 0; l < L; ++l)
-                if (fb_rows(d, l)) m.wr.push_back(acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
+                if (fb_rows(d, l)) m.wr.push_back(pm_acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
             metas.push_back(m);
         }
         for (int ct = 0; ct < 4; ++ct) {  // output frame x[t+1] (63 columns, padded to 64)
-            PmReq q = gemm_unit(sOUT, XR, kr);
+            PmReq q = pb.gemm(sOUT, XR, kr);
             PmUnit& u = q.u;
             u.W = d.Wro_t + (size_t)ct * (kr / 16) * 256;
-            u.add[0] = rm(d.ro_const + 16 * ct, 0, 64);
+            pb.add_operand(u, pm_rm(d.ro_const + 16 * ct, 0, 64));
             u.epi = PM_EPI_LINEAR;
-            u.out = rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
+            u.out = pm_rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
             for (int l = 0; l < L; ++l)
-                if (fb_rows(d, l)) u.dst[u.ndst++] = mkdst(XL[l], 1, kx[l], (int)(kx[l] / 16) - 4 + ct);
-            reqs.push_back(q);
+                if (fb_rows(d, l)) pb.add_dst(u, pb.dst(XL[l], 1, kx[l], (int)(kx[l] / 16) - 4 + ct));
+            pb.push(q);
         }
         std::vector<PmAccess> init;
         for (int l = 0; l < L; ++l) {
-            init.push_back(acc(RES_XG + l, 0, 0, hc));
-            init.push_back(acc(RES_H + l, 0, 0, 1));
-            init.push_back(acc(RES_C + l, 0, 0, 1));
-            if (fb_rows(d, l)) init.push_back(acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
+            init.push_back(pm_acc(RES_XG + l, 0, 0, hc));
+            init.push_back(pm_acc(RES_H + l, 0, 0, 1));
+            init.push_back(pm_acc(RES_C + l, 0, 0, 1));
+            if (fb_rows(d, l)) init.push_back(pm_acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
         }
-        init.push_back(acc(RES_XG, 0, hc, ec));
-        init.push_back(acc(RES_KAPPA, 0, 0, 1));
+        init.push_back(pm_acc(RES_XG, 0, hc, ec));
+        init.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
         const int chk = check_pieces(metas, init, n_slots, 4, 4);
-        memset(pieces_info, 0, sizeof(pieces_info));
-        pieces_info[0] = n_slots; pieces_info[2] = chk; pieces_info[3] = (int)reqs.size(); pieces_info[13] = maxu;
-        for (const PmReq& q : reqs) pieces_info[4 + q.slot] += 1;
-        if (chk != 0) return 0;
-        std::vector<PmUnit> table;
-        if (!pm_place(reqs, n_slots, maxu, nwg, table)) return 0;
-        for (const PmUnit& u : table)
-            if (u.kind == PM_GEMM && u.w_lds < 0) pieces_info[14] += 1;  // units that stream their weights
-        lstm_ok = true;
-        if (dry) return 0;
-        if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) return 0;
 
-        PmProgram& P = pm_prog;
-        memset(&P, 0, sizeof(P));
-        P.T = S; P.n_ticks = S; P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = n_slots; P.maxu = maxu;
-        P.units = units_dev; P.sync = sync; P.fm_base = fm_base;
-        PmAtt& a = P.att;
-        a.h1 = rm(hist_h[0], BH, H);
-        a.WattT = d.WattT; a.batt = d.batt; a.ctx = d.ctx;
-        a.kappa = d.kappa; a.a = d.a; a.b = b_hist; a.phi = d.phi; a.w = d.w; a.sup = nullptr;
-        a.B = B; a.H = H; a.A = d.A; a.U = d.U; a.E = E; a.att_type = d.att_type; a.dense = 0;
-        a.eps = d.eps; a.alignment = d.alignment; a.sharpening = d.sharpening; a.timing = d.timing;
-        a.wdst[a.nwdst++] = mkdst(XL[0], 1, kx[0], hc);
-        for (int l = 1; l < L; ++l) a.wdst[a.nwdst++] = mkdst(XL[l], 0, kx[l], hc);
-        a.wdst[a.nwdst++] = mkdst(XR, 0, kr, L * hc);
-        int ni = 0;
-        auto add_init = [&](const float* src, int ld, int K, float* slab, long long ks, int chunk) {
-            PmInit& in = P.init[ni++];
-            in.src = src; in.ld = ld; in.K = K; in.dst_off = boff(slab); in.nch = (int)(ks / 16); in.chunk = chunk; in.pad = 0;
-        };
-        for (int l = 0; l < L; ++l) add_init(d.h[l], H, H, XL[l], kx[l], 0);
-        add_init(d.w, E, E, XL[0], kx[0], hc);
+        pb.att_common(d, hist_h[0]);
+        pm_prog.att.b = b_hist;
+        pb.add_wdst(pb.dst(XL[0], 1, kx[0], hc));
+        for (int l = 1; l < L; ++l) pb.add_wdst(pb.dst(XL[l], 0, kx[l], hc));
+        pb.add_wdst(pb.dst(XR, 0, kr, L * hc));
+        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XL[l], kx[l], 0);
+        pb.add_init(d.w, E, E, XL[0], kx[0], hc);
         for (int l = 0; l < L; ++l)  // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states
-            if (fb_rows(d, l)) add_init(d.x, d.ldx, 64, XL[l], kx[l], (int)(kx[l] / 16) - 4);
-        P.ninit = ni;
-        P.lstm = 1;
+            if (fb_rows(d, l)) pb.add_init(d.x, d.ldx, 64, XL[l], kx[l], (int)(kx[l] / 16) - 4);
+        pm_prog.lstm = 1;
         // no grid barriers with one unit per workgroup and phase (34.9 against 38.7 us per step at 2 x 1024, B 16); with two
         // (H = 1536: 384 tiles on 256 workgroups, all weights streamed) the barriers measured faster: 114.8 against 124.9
-        P.dataflow = sw_pm_dataflow(maxu == 1 ? 1 : 0);
-        auto add_fill = [&](void* q, long long nfloats) {
-            if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
-        };
-        add_fill(fm_base, (long long)(fm_end - fm_base));
+        pm_prog.dataflow = sw_pm_dataflow(maxu == 1 ? 1 : 0);
+        pb.fill_fm();
         for (int l = 0; l < L; ++l) {
-            add_fill(hist_h[l] + BH, (long long)S * BH);
-            add_fill(hist_c[l] + BH, (long long)S * BH);
+            pb.add_fill(hist_h[l] + BH, (long long)S * BH);
+            pb.add_fill(hist_c[l] + BH, (long long)S * BH);
         }
-        persist_ok = true;
+        memset(pieces_info, 0, sizeof(pieces_info));
+        pieces_info[13] = maxu;
+        lstm_ok = pb.finish(S, S, chk, pieces_info);
+        persist_ok = lstm_ok && !dry;
         return 0;
     }
 
@@ -472,21 +440,6 @@ struct SamplePlan : PlanBase {
     // A tick has 2L + 2 phases; main units run step (tick - 1), pieces whose operand dates from the previous step may run
     // in the previous tick (lag 0), so the launch has S + 1 ticks.  check_pieces() replays the table symbolically (every
     // read satisfied by a write of a strictly earlier phase, every buffer element written once) before it is used.
-    struct PmPiece {
-        int c0, nch, gp;  // chunk range of the slab; position (phase index over two ticks) after which the operand exists
-        bool crit;
-        int lag, slot, pbuf;
-    };
-    struct PmGroup {
-        int kind, l, slot, N, res;  // kind 0 gates, 1 candidate, 2 output, 3 x_pre (fbc); res = checker resource id of the slab
-        int glag;                   // the group's critical unit runs `glag` ticks after the step's other main units
-        long long ks;
-        std::vector<PmPiece> pc;
-    };
-    struct PmAccess { int res, dstep, c0, nch; };
-    struct PmMeta { int lag, slot; std::vector<PmAccess> rd, wr; };
-    enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63, RES_C = 70,
-           RES_PART = 100 };
     // Round 5: the attention projection folded into layer 0's candidate units (PmUnit::pw / pp, persist.hip)
     static bool attfold_wanted(const ParrotSampleDesc& d) {
         return d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && env_int("PARROT_PM_ATTFOLD", 1) != 0;
@@ -656,57 +609,17 @@ struct SamplePlan : PlanBase {
             for (const PmPiece& p : g.pc)
                 if (!p.crit) n += (long long)(d.S + 1) * d.B * g.N + 16;
         if (fbc) {  // the longer layer-0 slabs, x_pre row-major, the zero rows behind x[0]
-            const long long rows = d.B <= 16 ? 16 : (d.B <= 32 ? 32 : 64);
+            const long long rows = pm_rows(d.B);
             n += 2 * (long long)(d.S + 1) * rows * d.H + (long long)(d.S + 2) * d.B * 64 + (long long)d.B * d.H + 64;
         }
         if (attfold_wanted(d)) n += (long long)d.S * (d.H / 16) * d.B * 32 + 64;  // the projection's partial sums
         return n;
     }
-    // symbolic replay over S steps: 0 = every read finds its value written in an earlier phase and nothing is written twice
-    static int check_pieces(const std::vector<PmMeta>& metas, const std::vector<PmAccess>& init, int n_slots, int S,
-                            int n_ticks) {
-        std::vector<std::array<int, 3>> written;  // (res, step, chunk), kept sorted
-        auto has = [&](int r, int t, int c) {
-            const std::array<int, 3> k = {r, t, c};
-            return std::binary_search(written.begin(), written.end(), k);
-        };
-        auto put = [&](int r, int t, int c) {
-            const std::array<int, 3> k = {r, t, c};
-            auto it = std::lower_bound(written.begin(), written.end(), k);
-            if (it != written.end() && *it == k) return false;
-            written.insert(it, k);
-            return true;
-        };
-        for (const PmAccess& a : init)
-            for (int c = a.c0; c < a.c0 + a.nch; ++c)
-                if (!put(a.res, a.dstep, c)) return 1;
-        for (int tick = 0; tick < n_ticks; ++tick)
-            for (int s = 0; s < n_slots; ++s) {
-                for (const PmMeta& m : metas) {
-                    const int t = tick - m.lag;
-                    if (m.slot != s || t < 0 || t >= S) continue;
-                    for (const PmAccess& a : m.rd)
-                        for (int c = a.c0; c < a.c0 + a.nch; ++c)
-                            if (!has(a.res, t + a.dstep, c)) return 2;
-                }
-                for (const PmMeta& m : metas) {
-                    const int t = tick - m.lag;
-                    if (m.slot != s || t < 0 || t >= S) continue;
-                    for (const PmAccess& a : m.wr)
-                        for (int c = a.c0; c < a.c0 + a.nch; ++c)
-                            if (!put(a.res, t + a.dstep, c)) return 3;
-                }
-            }
-        for (int t = 1; t <= S; ++t)
-            if (!has(RES_X, t, 0)) return 4;
-        return 0;
-    }
 
     // dry = true: plan, place and check only (no device memory is touched; nwg given by the caller) -- the CPU tests
     int build_persist_pieces(bool dry, int nwg_dry) {
         pieces_ok = false;
-        if (d.cell == 1) return build_persist_lstm(dry, nwg_dry);
-        if (!pieces_wanted(d) || !persist_eligible_shape(d)) return 0;
+        if (d.cell != 0 || !pieces_wanted(d) || !persist_eligible_shape(d)) return 0;
         const int nwg = dry ? nwg_dry : pm_max_workgroups();
         if (nwg < 64) return 0;
         if (!dry && (!d.persist_ws || d.persist_ws_floats < persist_floats(d, nwg))) return 0;
@@ -717,57 +630,43 @@ struct SamplePlan : PlanBase {
         while (!piece_slots(d, gs, nwg, fbc))   // more units than one per workgroup and phase: join two pieces and try again
             if (!join_closest_pieces(gs)) return 0;
         const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S;
-        const int MB = B <= 16 ? 1 : (B <= 32 ? 2 : 4);
-        const long long rows = (long long)MB * 16, BH = (long long)B * H;
+        const long long BH = (long long)B * H;
         const int n_slots = n_phases(d, fbc), sATT = 2, hc = H / 16, ec = E / 16;
         const int fbx = hc + ec, fbh = hc + ec + 4;  // (fbc) layer 0's x_pre chunks / the last layer's state chunks
-        float* ws = dry ? reinterpret_cast<float*>((uintptr_t)0x10000000) : d.persist_ws;
-        auto take = [&](long long n) { float* p = ws; ws += (n + 3) / 4 * 4; return p; };
-        unsigned* sync = reinterpret_cast<unsigned*>(take(PM_SYNC_WORDS + PM_DBG_WORDS));
-        const size_t unit_bytes = (size_t)n_slots * nwg * sizeof(PmUnit);
-        PmUnit* units_dev = reinterpret_cast<PmUnit*>(take((long long)(unit_bytes + 3) / 4 + 16));
-        float* fm_base = ws;
+        PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, 1);
+        const long long rows = pb.rows;
         float* XG[PARROT_MAX_LAYERS];
         float* XC[PARROT_MAX_LAYERS];
         long long kx[PARROT_MAX_LAYERS];
         for (int l = 0; l < L; ++l) {
             kx[l] = kslab_p(d, l, fbc);
-            XG[l] = take((S + 1) * rows * kx[l]);
-            XC[l] = take((S + 1) * rows * kx[l]);
+            XG[l] = pb.take((S + 1) * rows * kx[l]);
+            XC[l] = pb.take((S + 1) * rows * kx[l]);
         }
         const long long kr = (long long)L * H + E;
-        float* XR = take(S * rows * kr);
-        if ((long long)(ws - fm_base) * 4 >= 0xfff00000ll) return 0;
-        float* const fm_end = ws;
+        float* XR = pb.take(S * rows * kr);
+        pb.fm_end();
         float* zh[PARROT_MAX_LAYERS];
-        for (int l = 0; l < L; ++l) hist_h[l] = take((S + 1) * BH);
-        for (int l = 0; l < L; ++l) zh[l] = take(S * BH);
-        float* b_hist = take((long long)S * B * d.A);
-        const bool attfold = attfold_wanted(d) && MB == 1;
-        float* pp = attfold ? take((long long)S * hc * B * 32) : nullptr;  // [S][H / 16][B][32] partial projections
-        float* zero_rows = fbc ? take(BH) : nullptr;               // never written: the workspace arrives zero-filled
-        float* xpre_rm = fbc ? take((long long)(S + 1) * B * 64) : nullptr;  // x_pre of step t, row-major (the output unit adds it)
-        float* const part_base = ws;
+        for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
+        for (int l = 0; l < L; ++l) zh[l] = pb.take(S * BH);
+        float* b_hist = pb.take((long long)S * B * d.A);
+        const bool attfold = attfold_wanted(d) && pb.MB == 1;
+        float* pp = attfold ? pb.take((long long)S * hc * B * 32) : nullptr;  // [S][H / 16][B][32] partial projections
+        float* zero_rows = fbc ? pb.take(BH) : nullptr;            // never written: the workspace arrives zero-filled
+        float* xpre_rm = fbc ? pb.take((long long)(S + 1) * B * 64) : nullptr;  // x_pre of step t, row-major (the output unit adds it)
+        float* const part_base = pb.mark();
         int npart = 0;
         std::vector<float*> pbuf;
         for (PmGroup& g : gs)
             for (PmPiece& p : g.pc)
                 if (!p.crit) {
                     p.pbuf = npart++;
-                    pbuf.push_back(take((long long)(S + 1) * B * g.N + 16));
+                    pbuf.push_back(pb.take((long long)(S + 1) * B * g.N + 16));
                 }
-        float* const part_end = ws;
+        float* const part_end = pb.mark();
+        if (pb.failed) return 0;
 
-        auto boff = [&](const float* p) { return (unsigned)((p - fm_base) * 4); };
-        auto mkdst = [&](float* slab, long long step0, long long ks, int chunk) {
-            PmDst q;
-            q.off = boff(slab + step0 * rows * ks); q.st = (unsigned)(rows * ks * 4); q.nch = (int)(ks / 16); q.chunk = chunk;
-            return q;
-        };
-        auto rm = [](const float* p, long long st, int ld) { PmRM r; r.p = const_cast<float*>(p); r.st = st; r.ld = ld; r.pad = 0; return r; };
-        std::vector<PmReq> reqs;
         std::vector<PmMeta> metas;
-        auto acc = [](int res, int dstep, int c0, int nch) { PmAccess a; a.res = res; a.dstep = dstep; a.c0 = c0; a.nch = nch; return a; };
         for (const PmGroup& g : gs) {
             const int l = g.l, N = g.N, nch_all = (int)(g.ks / 16);
             float* slab = g.kind == 0 ? XG[l] : (g.kind == 1 ? XC[l] : XR);
@@ -776,160 +675,148 @@ struct SamplePlan : PlanBase {
             for (const PmPiece& p : g.pc) {
                 PmMeta m;
                 m.lag = p.lag; m.slot = p.slot;
-                m.rd.push_back(acc(g.res, 0, p.c0, p.nch));
+                m.rd.push_back(pm_acc(g.res, 0, p.c0, p.nch));
                 if (!p.crit) {
-                    m.wr.push_back(acc(RES_PART + p.pbuf, 0, 0, 1));
+                    m.wr.push_back(pm_acc(RES_PART + p.pbuf, 0, 0, 1));
                 } else {
                     for (const PmPiece& o : g.pc)
-                        if (!o.crit) m.rd.push_back(acc(RES_PART + o.pbuf, 0, 0, 1));
+                        if (!o.crit) m.rd.push_back(pm_acc(RES_PART + o.pbuf, 0, 0, 1));
                     if (g.kind == 0) {
-                        m.rd.push_back(acc(RES_H + l, 0, 0, 1));
-                        m.wr.push_back(acc(RES_Z + l, 0, 0, 1));
-                        m.wr.push_back(acc(RES_XC + l, 0, 0, hc));
+                        m.rd.push_back(pm_acc(RES_H + l, 0, 0, 1));
+                        m.wr.push_back(pm_acc(RES_Z + l, 0, 0, 1));
+                        m.wr.push_back(pm_acc(RES_XC + l, 0, 0, hc));
                     } else if (g.kind == 1) {
-                        m.rd.push_back(acc(RES_H + l, 0, 0, 1));
-                        m.rd.push_back(acc(RES_Z + l, 0, 0, 1));
-                        m.wr.push_back(acc(RES_H + l, 1, 0, 1));
-                        m.wr.push_back(acc(RES_XG + l, 1, 0, hc));
+                        m.rd.push_back(pm_acc(RES_H + l, 0, 0, 1));
+                        m.rd.push_back(pm_acc(RES_Z + l, 0, 0, 1));
+                        m.wr.push_back(pm_acc(RES_H + l, 1, 0, 1));
+                        m.wr.push_back(pm_acc(RES_XG + l, 1, 0, hc));
                         for (int m2 = l + 1; m2 < L; ++m2) {
-                            m.wr.push_back(acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
-                            m.wr.push_back(acc(RES_XC + m2, 0, hc + ec + l * hc, hc));
+                            m.wr.push_back(pm_acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
+                            m.wr.push_back(pm_acc(RES_XC + m2, 0, hc + ec + l * hc, hc));
                         }
-                        m.wr.push_back(acc(RES_XR, 0, l * hc, hc));
-                        if (attfold && l == 0) m.wr.push_back(acc(RES_PP, 0, 0, 1));
+                        m.wr.push_back(pm_acc(RES_XR, 0, l * hc, hc));
+                        if (attfold && l == 0) m.wr.push_back(pm_acc(RES_PP, 0, 0, 1));
                         if (fbc && l == L - 1) {
-                            m.wr.push_back(acc(RES_XG, 1, fbh, hc));
-                            m.wr.push_back(acc(RES_XC, 1, fbh, hc));
+                            m.wr.push_back(pm_acc(RES_XG, 1, fbh, hc));
+                            m.wr.push_back(pm_acc(RES_XC, 1, fbh, hc));
                         }
                     } else if (g.kind == 2) {
-                        m.wr.push_back(acc(RES_X, 1, 0, 1));
-                        if (fbc) m.rd.push_back(acc(RES_XPRE, 0, 0, 1));
+                        m.wr.push_back(pm_acc(RES_X, 1, 0, 1));
+                        if (fbc) m.rd.push_back(pm_acc(RES_XPRE, 0, 0, 1));
                         for (int q = 0; q < L && !fbc; ++q)
                             if (fb_rows(d, q)) {
-                                m.wr.push_back(acc(RES_XG + q, 1, (int)(kx[q] / 16) - 4, 4));
-                                m.wr.push_back(acc(RES_XC + q, 1, (int)(kx[q] / 16) - 4, 4));
+                                m.wr.push_back(pm_acc(RES_XG + q, 1, (int)(kx[q] / 16) - 4, 4));
+                                m.wr.push_back(pm_acc(RES_XC + q, 1, (int)(kx[q] / 16) - 4, 4));
                             }
                     } else {  // x_pre
-                        m.wr.push_back(acc(RES_XPRE, 0, 0, 1));
-                        m.wr.push_back(acc(RES_XG, 1, fbx, 4));
-                        m.wr.push_back(acc(RES_XC, 1, fbx, 4));
+                        m.wr.push_back(pm_acc(RES_XPRE, 0, 0, 1));
+                        m.wr.push_back(pm_acc(RES_XG, 1, fbx, 4));
+                        m.wr.push_back(pm_acc(RES_XC, 1, fbx, 4));
                     }
                 }
                 metas.push_back(m);
                 for (int ct = 0; ct < N / 16; ++ct) {
-                    PmReq q;
-                    memset(&q, 0, sizeof(q));
+                    PmReq q = pb.gemm(p.slot, slab, g.ks, p.c0, p.nch * 16, p.lag);
                     PmUnit& u = q.u;
-                    u.kind = PM_GEMM; u.M = B; u.w_lds = -1; u.lag = p.lag;
-                    u.a_off = boff(slab); u.a_st = (unsigned)(rows * g.ks * 4); u.a_nch = nch_all; u.a_c0 = p.c0; u.K = p.nch * 16;
                     u.W = Wt + ((size_t)ct * nch_all + p.c0) * 256;
-                    q.slot = p.slot; q.crit = p.crit ? 1 : 0; q.krows = p.nch * 16;
+                    q.crit = p.crit ? 1 : 0;
                     if (!p.crit) {
                         u.epi = PM_EPI_LINEAR;
-                        u.out = rm(pbuf[p.pbuf] + 16 * ct, (long long)B * N, N);
-                        reqs.push_back(q);
+                        u.out = pm_rm(pbuf[p.pbuf] + 16 * ct, (long long)B * N, N);
+                        pb.push(q);
                         continue;
                     }
-                    int na = 0;
                     for (const PmPiece& o : g.pc)
-                        if (!o.crit) u.add[na++] = rm(pbuf[o.pbuf] + 16 * ct, (long long)B * N, N);
+                        if (!o.crit) pb.add_operand(u, pm_rm(pbuf[o.pbuf] + 16 * ct, (long long)B * N, N));
                     if (g.kind == 0) {
                         u.bias = d.bg[l] ? d.bg[l] + 16 * ct : nullptr;
-                        if (d.seq_g[l]) u.add[na++] = rm(d.seq_g[l] + 16 * ct, 0, 2 * H);
+                        if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 16 * ct, 0, 2 * H));
                         u.epi = PM_EPI_GATES;
                         u.rtile = 16 * ct >= H;
                         if (!u.rtile) {
-                            u.o1 = rm(zh[l] + 16 * ct, BH, H);
+                            u.o1 = pm_rm(zh[l] + 16 * ct, BH, H);
                         } else {
                             const int j0 = 16 * ct - H;
-                            u.e0 = rm(hist_h[l] + j0, BH, H);
-                            u.dst[u.ndst++] = mkdst(XC[l], 0, kx[l], j0 / 16);
+                            u.e0 = pm_rm(hist_h[l] + j0, BH, H);
+                            pb.add_dst(u, pb.dst(XC[l], 0, kx[l], j0 / 16));
                         }
                     } else if (g.kind == 1) {
                         u.bias = d.bc[l] ? d.bc[l] + 16 * ct : nullptr;
-                        if (d.seq_c[l]) u.add[na++] = rm(d.seq_c[l] + 16 * ct, 0, H);
+                        if (d.seq_c[l]) pb.add_operand(u, pm_rm(d.seq_c[l] + 16 * ct, 0, H));
                         u.epi = PM_EPI_CAND;
-                        u.e0 = rm(hist_h[l] + 16 * ct, BH, H);
-                        u.e1 = rm(zh[l] + 16 * ct, BH, H);
-                        u.out = rm(hist_h[l] + BH + 16 * ct, BH, H);
-                        u.dst[u.ndst++] = mkdst(XG[l], 1, kx[l], ct);
+                        u.e0 = pm_rm(hist_h[l] + 16 * ct, BH, H);
+                        u.e1 = pm_rm(zh[l] + 16 * ct, BH, H);
+                        u.out = pm_rm(hist_h[l] + BH + 16 * ct, BH, H);
+                        pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ct));
                         for (int m2 = l + 1; m2 < L; ++m2) {
                             const int ch = hc + ec + l * hc + ct;
-                            u.dst[u.ndst++] = mkdst(XG[m2], 0, kx[m2], ch);
-                            u.dst[u.ndst++] = mkdst(XC[m2], 0, kx[m2], ch);
+                            pb.add_dst(u, pb.dst(XG[m2], 0, kx[m2], ch));
+                            pb.add_dst(u, pb.dst(XC[m2], 0, kx[m2], ch));
                         }
-                        u.dst[u.ndst++] = mkdst(XR, 0, kr, l * hc + ct);
+                        pb.add_dst(u, pb.dst(XR, 0, kr, l * hc + ct));
                         if (attfold && l == 0) {  // this tile's share of the attention projection h_1 . Watt
                             u.pw[0] = d.Watt_t + (size_t)ct * 256;
                             u.pw[1] = d.Watt_t + (size_t)(hc + ct) * 256;
-                            u.pp = rm(pp + (size_t)ct * B * 32, (long long)hc * B * 32, 32);
+                            u.pp = pm_rm(pp + (size_t)ct * B * 32, (long long)hc * B * 32, 32);
                         }
                         if (fbc && l == L - 1) {  // ... and the operand of layer 0's composed feedback rows, next step
-                            if (u.ndst + 2 > PM_MAXDST) return 0;
-                            u.dst[u.ndst++] = mkdst(XG[0], 1, kx[0], fbh + ct);
-                            u.dst[u.ndst++] = mkdst(XC[0], 1, kx[0], fbh + ct);
+                            pb.add_dst(u, pb.dst(XG[0], 1, kx[0], fbh + ct));
+                            pb.add_dst(u, pb.dst(XC[0], 1, kx[0], fbh + ct));
                         }
                     } else if (g.kind == 3) {  // x_pre = ro_const + the shares of every operand but the last layer's state
-                        u.add[na++] = rm(d.ro_const + 16 * ct, 0, 64);
+                        pb.add_operand(u, pm_rm(d.ro_const + 16 * ct, 0, 64));
                         u.epi = PM_EPI_LINEAR;
-                        u.out = rm(xpre_rm + 16 * ct, (long long)B * 64, 64);
-                        u.dst[u.ndst++] = mkdst(XG[0], 1, kx[0], fbx + ct);
-                        u.dst[u.ndst++] = mkdst(XC[0], 1, kx[0], fbx + ct);
+                        u.out = pm_rm(xpre_rm + 16 * ct, (long long)B * 64, 64);
+                        pb.add_dst(u, pb.dst(XG[0], 1, kx[0], fbx + ct));
+                        pb.add_dst(u, pb.dst(XC[0], 1, kx[0], fbx + ct));
                     } else {
-                        u.add[na++] = fbc ? rm(xpre_rm + 16 * ct, (long long)B * 64, 64) : rm(d.ro_const + 16 * ct, 0, 64);
+                        pb.add_operand(u, fbc ? pm_rm(xpre_rm + 16 * ct, (long long)B * 64, 64) : pm_rm(d.ro_const + 16 * ct, 0, 64));
                         u.epi = PM_EPI_LINEAR;
-                        u.out = rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
+                        u.out = pm_rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
                         for (int q2 = 0; q2 < L && !fbc; ++q2) {
                             if (!fb_rows(d, q2)) continue;
                             const int ch = (int)(kx[q2] / 16) - 4 + ct;
-                            u.dst[u.ndst++] = mkdst(XG[q2], 1, kx[q2], ch);
-                            u.dst[u.ndst++] = mkdst(XC[q2], 1, kx[q2], ch);
+                            pb.add_dst(u, pb.dst(XG[q2], 1, kx[q2], ch));
+                            pb.add_dst(u, pb.dst(XC[q2], 1, kx[q2], ch));
                         }
                     }
-                    if (na > 4 || u.ndst > PM_MAXDST) return 0;
-                    reqs.push_back(q);
+                    pb.push(q);
                 }
             }
         }
         {
             PmMeta m;
             m.lag = 1; m.slot = sATT;
-            m.rd.push_back(acc(RES_H, 1, 0, 1));
-            if (attfold) m.rd.push_back(acc(RES_PP, 0, 0, 1));
-            m.rd.push_back(acc(RES_KAPPA, 0, 0, 1));
-            m.wr.push_back(acc(RES_KAPPA, 1, 0, 1));
-            m.wr.push_back(acc(RES_XG, 1, hc, ec));
-            m.wr.push_back(acc(RES_XC, 1, hc, ec));
+            m.rd.push_back(pm_acc(RES_H, 1, 0, 1));
+            if (attfold) m.rd.push_back(pm_acc(RES_PP, 0, 0, 1));
+            m.rd.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
+            m.wr.push_back(pm_acc(RES_KAPPA, 1, 0, 1));
+            m.wr.push_back(pm_acc(RES_XG, 1, hc, ec));
+            m.wr.push_back(pm_acc(RES_XC, 1, hc, ec));
             for (int l = 1; l < L; ++l) {
-                m.wr.push_back(acc(RES_XG + l, 0, hc, ec));
-                m.wr.push_back(acc(RES_XC + l, 0, hc, ec));
+                m.wr.push_back(pm_acc(RES_XG + l, 0, hc, ec));
+                m.wr.push_back(pm_acc(RES_XC + l, 0, hc, ec));
             }
-            m.wr.push_back(acc(RES_XR, 0, L * hc, ec));
+            m.wr.push_back(pm_acc(RES_XR, 0, L * hc, ec));
             metas.push_back(m);
         }
-        for (int b = 0; b < B; ++b) {
-            PmReq q;
-            memset(&q, 0, sizeof(q));
-            q.u.kind = PM_ATT; q.u.row = b; q.u.w_lds = -1; q.u.lag = 1;
-            q.slot = sATT; q.crit = 1; q.krows = 0;
-            reqs.push_back(q);
-        }
+        pb.att_rows(sATT, 1);
         std::vector<PmAccess> init;
         for (int l = 0; l < L; ++l) {
-            init.push_back(acc(RES_XG + l, 0, 0, hc));
-            init.push_back(acc(RES_H + l, 0, 0, 1));
+            init.push_back(pm_acc(RES_XG + l, 0, 0, hc));
+            init.push_back(pm_acc(RES_H + l, 0, 0, 1));
             if (fb_rows(d, l) && !fbc) {
-                init.push_back(acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
-                init.push_back(acc(RES_XC + l, 0, (int)(kx[l] / 16) - 4, 4));
+                init.push_back(pm_acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
+                init.push_back(pm_acc(RES_XC + l, 0, (int)(kx[l] / 16) - 4, 4));
             }
         }
         if (fbc) {  // step 0: x[0] in the x_pre chunks, zero rows where the last layer's state would go
-            init.push_back(acc(RES_XG, 0, fbx, 4 + hc));
-            init.push_back(acc(RES_XC, 0, fbx, 4 + hc));
+            init.push_back(pm_acc(RES_XG, 0, fbx, 4 + hc));
+            init.push_back(pm_acc(RES_XC, 0, fbx, 4 + hc));
         }
-        init.push_back(acc(RES_XG, 0, hc, ec));
-        init.push_back(acc(RES_XC, 0, hc, ec));
-        init.push_back(acc(RES_KAPPA, 0, 0, 1));
+        init.push_back(pm_acc(RES_XG, 0, hc, ec));
+        init.push_back(pm_acc(RES_XC, 0, hc, ec));
+        init.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
         if (sw_pm_dump_plan())
             for (const PmGroup& g : gs)
                 for (const PmPiece& p : g.pc)
@@ -938,79 +825,48 @@ struct SamplePlan : PlanBase {
                             p.crit ? "CRITICAL" : "piece", p.slot, p.lag);
         const int n_extra = fbc ? 2 : 1;  // ticks beyond S: main units lag one tick, the output unit of the fbc plan two
         const int chk = check_pieces(metas, init, n_slots, 4, 4 + n_extra);
-        memset(pieces_info, 0, sizeof(pieces_info));
-        pieces_info[0] = n_slots; pieces_info[1] = npart; pieces_info[2] = chk; pieces_info[3] = (int)reqs.size();
-        pieces_info[15] = (fbc ? 1 : 0) + (attfold ? 2 : 0);
-        for (const PmReq& q : reqs) pieces_info[4 + q.slot] += 1;
-        if (chk != 0) return 0;
-        std::vector<PmUnit> table;
-        if (!pm_place(reqs, n_slots, 1, nwg, table)) return 0;
-        for (const PmUnit& u : table)
-            if (u.kind == PM_GEMM && u.w_lds < 0) pieces_info[14] += 1;  // units that stream their weights
-        pieces_ok = true;
-        fbc_on = fbc;
-        if (dry) return 0;
-        if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) { pieces_ok = false; return 0; }
 
-        PmProgram& P = pm_prog;
-        memset(&P, 0, sizeof(P));
-        P.T = S; P.n_ticks = S + n_extra; P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = n_slots; P.maxu = 1;
-        P.units = units_dev; P.sync = sync; P.fm_base = fm_base;
-        PmAtt& a = P.att;
-        a.h1 = rm(hist_h[0], BH, H);
-        a.WattT = d.WattT; a.batt = d.batt; a.ctx = d.ctx;
-        a.kappa = d.kappa; a.a = d.a; a.b = b_hist; a.phi = d.phi; a.w = d.w; a.sup = nullptr;
-        a.B = B; a.H = H; a.A = d.A; a.U = d.U; a.E = E; a.att_type = d.att_type; a.dense = 0;
-        a.eps = d.eps; a.alignment = d.alignment; a.sharpening = d.sharpening; a.timing = d.timing;
-        a.pp = pp; a.pp_st = (long long)hc * B * 32;
-        a.wdst[a.nwdst++] = mkdst(XG[0], 1, kx[0], hc);
-        a.wdst[a.nwdst++] = mkdst(XC[0], 1, kx[0], hc);
+        pb.att_common(d, hist_h[0]);
+        PmAtt& a = pm_prog.att;
+        a.b = b_hist; a.pp = pp; a.pp_st = (long long)hc * B * 32;
+        pb.add_wdst(pb.dst(XG[0], 1, kx[0], hc));
+        pb.add_wdst(pb.dst(XC[0], 1, kx[0], hc));
         for (int l = 1; l < L; ++l) {
-            a.wdst[a.nwdst++] = mkdst(XG[l], 0, kx[l], hc);
-            a.wdst[a.nwdst++] = mkdst(XC[l], 0, kx[l], hc);
+            pb.add_wdst(pb.dst(XG[l], 0, kx[l], hc));
+            pb.add_wdst(pb.dst(XC[l], 0, kx[l], hc));
         }
-        a.wdst[a.nwdst++] = mkdst(XR, 0, kr, L * hc);
-        if (a.nwdst > PM_MAXWDST) { pieces_ok = false; return 0; }
-        int ni = 0;
-        auto add_init = [&](const float* src, int ld, int K, float* slabp, long long ks, int chunk) {
-            PmInit& in = P.init[ni++];
-            in.src = src; in.ld = ld; in.K = K; in.dst_off = boff(slabp); in.nch = (int)(ks / 16); in.chunk = chunk; in.pad = 0;
-        };
-        for (int l = 0; l < L; ++l) add_init(d.h[l], H, H, XG[l], kx[l], 0);
-        add_init(d.w, E, E, XG[0], kx[0], hc);
-        add_init(d.w, E, E, XC[0], kx[0], hc);
+        pb.add_wdst(pb.dst(XR, 0, kr, L * hc));
+        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XG[l], kx[l], 0);
+        pb.add_init(d.w, E, E, XG[0], kx[0], hc);
+        pb.add_init(d.w, E, E, XC[0], kx[0], hc);
         for (int l = 0; l < L && !fbc; ++l) {
             if (!fb_rows(d, l)) continue;
-            if (ni + 2 > PM_MAXINIT) { pieces_ok = false; return 0; }
-            add_init(d.x, d.ldx, 64, XG[l], kx[l], (int)(kx[l] / 16) - 4);
-            add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)(kx[l] / 16) - 4);
+            pb.add_init(d.x, d.ldx, 64, XG[l], kx[l], (int)(kx[l] / 16) - 4);
+            pb.add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)(kx[l] / 16) - 4);
         }
         if (fbc) {
-            if (ni + 4 > PM_MAXINIT) { pieces_ok = false; return 0; }
-            add_init(d.x, d.ldx, 64, XG[0], kx[0], fbx);
-            add_init(d.x, d.ldx, 64, XC[0], kx[0], fbx);
-            add_init(zero_rows, H, H, XG[0], kx[0], fbh);
-            add_init(zero_rows, H, H, XC[0], kx[0], fbh);
+            pb.add_init(d.x, d.ldx, 64, XG[0], kx[0], fbx);
+            pb.add_init(d.x, d.ldx, 64, XC[0], kx[0], fbx);
+            pb.add_init(zero_rows, H, H, XG[0], kx[0], fbh);
+            pb.add_init(zero_rows, H, H, XC[0], kx[0], fbh);
         }
-        P.ninit = ni;
-        {
-            // no grid barriers by default: with the step cut into pieces a phase is ~3 us of fixed latency + a short K
-            // walk, and the barrier was a quarter of it (43.0 -> 36.1 us per step at configs[2]); the whole-K plan above
-            // measured no gain (57.6 either way).  Bit-identical to the barrier mode (tests/test_gpu_persist.py)
-            P.dataflow = sw_pm_dataflow(1);
-        }
-        auto add_fill = [&](void* q, long long nfloats) {
-            if (nfloats > 0) { P.fill[P.nfill].p = q; P.fill[P.nfill].bytes = nfloats * 4; ++P.nfill; }
-        };
-        add_fill(fm_base, (long long)(fm_end - fm_base));
+        // no grid barriers by default: with the step cut into pieces a phase is ~3 us of fixed latency + a short K
+        // walk, and the barrier was a quarter of it (43.0 -> 36.1 us per step at configs[2]); the whole-K plan above
+        // measured no gain (57.6 either way).  Bit-identical to the barrier mode (tests/test_gpu_persist.py)
+        pm_prog.dataflow = sw_pm_dataflow(1);
+        pb.fill_fm();
         for (int l = 0; l < L; ++l) {
-            add_fill(hist_h[l] + BH, (long long)S * BH);
-            add_fill(zh[l], (long long)S * BH);
+            pb.add_fill(hist_h[l] + BH, (long long)S * BH);
+            pb.add_fill(zh[l], (long long)S * BH);
         }
-        add_fill(part_base, (long long)(part_end - part_base));
-        if (fbc) add_fill(xpre_rm, (long long)(S + 1) * B * 64);
-        if (attfold) add_fill(pp, (long long)S * hc * B * 32);
-        persist_ok = true;
+        pb.add_fill(part_base, (long long)(part_end - part_base));
+        if (fbc) pb.add_fill(xpre_rm, (long long)(S + 1) * B * 64);
+        if (attfold) pb.add_fill(pp, (long long)S * hc * B * 32);
+        memset(pieces_info, 0, sizeof(pieces_info));
+        pieces_info[1] = npart; pieces_info[15] = (fbc ? 1 : 0) + (attfold ? 2 : 0);
+        pieces_ok = pb.finish(S, S + n_extra, chk, pieces_info);
+        fbc_on = pieces_ok && fbc;
+        persist_ok = pieces_ok && !dry;
         return 0;
     }
 
@@ -1273,7 +1129,7 @@ int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* in
     std::unique_ptr<SamplePlan> p(new (std::nothrow) SamplePlan());
     if (!p) return PARROT_ERR_BADARG;
     p->d = *desc;
-    p->build_persist_pieces(true, nwg);
+    p->plan_persist(true, nwg);
     for (int i = 0; i < 16; ++i) info16[i] = p->pieces_info[i];
     return (p->pieces_ok || p->lstm_ok) ? 0 : PARROT_ERR_UNSUPPORTED;
 }
