@@ -30,7 +30,6 @@
 #include <stdlib.h>
 
 #include <hip/hip_ext.h>
-#include <stdlib.h>
 #include <string.h>
 #include <type_traits>
 #include <vector>
@@ -80,26 +79,11 @@ __device__ __forceinline__ void sk_fetch(const SkSeg& sg, int kc, int m0, int M,
     }
 }
 
-// Activation operand of the fast path: 1 = quad-contiguous loads + ds_bpermute into the MFMA lanes (see
-// sk_fetch_fast / sk_a_unpermute), 0 = each lane loads its own row directly.
-#ifndef SK_A_PERMUTE
-#define SK_A_PERMUTE 1
-#endif
-
 // Register-buffer ring depth of the fast path (chunks in flight per wave).  Measured on MI355X, cfg2 training
 // step fwd/bwd ms: depth 2: 55.9/79.9, 4: 57.4/80.0, 6: 61.9/82.5, 8: 60.7/87.9 -- more loads in flight do
 // not help (the clamped tail refills add traffic), so the ping-pong pair stays.
-#ifndef SK_EARLY_DESC
-#define SK_EARLY_DESC 1
-#endif
 #ifndef SK_DEPTH
 #define SK_DEPTH 2
-#endif
-#ifndef SK_PIPE
-#define SK_PIPE 0
-#endif
-#ifndef SK_A_FRAG_PROBE
-#define SK_A_FRAG_PROBE 0
 #endif
 
 template <int MB>
@@ -121,18 +105,9 @@ __device__ __forceinline__ void sk_fetch_fast(const float* __restrict__ A, int l
     const int k = kc + 4 * kk;
 #pragma unroll
     for (int rb = 0; rb < MB; ++rb) {
-#if SK_A_FRAG_PROBE
-        // TIMING PROBE ONLY (values are wrong): the load pattern of a fragment-major activation copy -- one contiguous
-        // 1 KB block per (16-row block, 16-deep chunk), lanes in MFMA operand order, no lane permutation afterwards
-        a[rb] = *reinterpret_cast<const f32x4*>(A + ((size_t)((mrow[rb] >> 4) * (lda >> 4) + (kc >> 4)) << 8) +
-                                                ((threadIdx.x & 63) << 2));
-#elif SK_A_PERMUTE
         // quad-contiguous mapping: lane l reads 16 B of row (l >> 2) at k-offset 4 * (l & 3), so every quad of
         // lanes covers one contiguous 64-B segment; sk_a_unpermute moves the quads to the MFMA lanes later.
         a[rb] = *reinterpret_cast<const f32x4*>(A + (size_t)mrow[rb] * lda + kc + 4 * (threadIdx.x & 3));
-#else
-        a[rb] = *reinterpret_cast<const f32x4*>(A + (size_t)mrow[rb] * lda + k);
-#endif
     }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
@@ -153,7 +128,6 @@ __device__ __forceinline__ void sk_fetch_fast(const float* __restrict__ A, int l
 // MFMA lane (kk, i) = kk * 16 + i takes the quad that lane 4 * i + kk loaded (see sk_fetch_fast).
 template <int MB>
 __device__ __forceinline__ void sk_a_unpermute(f32x4 (&a)[MB]) {
-#if SK_A_PERMUTE && !SK_A_FRAG_PROBE
     const int lane = threadIdx.x & 63;
     const int src = (((lane & 15) << 2) | (lane >> 4)) << 2;  // byte address of the source lane
 #pragma unroll
@@ -161,7 +135,6 @@ __device__ __forceinline__ void sk_a_unpermute(f32x4 (&a)[MB]) {
 #pragma unroll
         for (int u = 0; u < 4; ++u)
             a[rb][u] = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(a[rb][u])));
-#endif
 }
 
 template <int MB, int NB>
@@ -267,16 +240,15 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
     const int m0 = blockIdx.y * (16 * MB);  // the launch picks MB / NB
     const int M = job.M, N = job.N;
     SK_STAMP(0);
-#if SK_EARLY_DESC  // (default 1: 20.2 -> 19.3 us per gate / candidate launch pair, tools/sktimers.hip)
     // The descriptor fields the prologue needs, pulled into scalar registers in one batch: read where the code first
     // needs them they arrive through five or six dependent s_load / s_waitcnt rounds (a cold kernel-argument line
     // each time) spread over the branches in front of the K loop.  (Invariant loads: the later reads reuse these.)
+    // Measured: 20.2 -> 19.3 us per gate / candidate launch pair (tools/sktimers.hip).
     asm volatile("" ::"s"(job.M), "s"(job.N), "s"(job.epi), "s"(job.H), "s"(job.nseg), "s"(job.accumulate), "s"(job.colmode),
                  "s"(job.bias), "s"(job.add), "s"(job.out), "s"(job.e0), "s"(job.e1), "s"(job.o1), "s"(job.ld_add),
                  "s"(job.ldo), "s"(job.lde0), "s"(job.lde1), "s"(job.ldo1), "s"(job.wait_flag), "s"(job.seg[0].A),
                  "s"(job.seg[0].B), "s"(job.seg[0].lda), "s"(job.seg[0].ldb), "s"(job.seg[0].K), "s"(job.seg[0].b_kcontig),
                  "s"(job.seg[1].A), "s"(job.seg[1].B), "s"(job.seg[1].lda), "s"(job.seg[1].ldb), "s"(job.seg[1].K));
-#endif
     if (m0 >= M) return;
 
     f32x4 acc[MB][NB];
@@ -362,25 +334,16 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
         }
         int mrow[MB], ncl[NB], btile[NB];
 #pragma unroll
-        for (int rb = 0; rb < MB; ++rb) mrow[rb] = min(m0 + rb * 16 + (SK_A_PERMUTE ? ((lane >> 2) & 15) : i), M - 1);
+        for (int rb = 0; rb < MB; ++rb) mrow[rb] = min(m0 + rb * 16 + ((lane >> 2) & 15), M - 1);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             ncl[nb] = min(sk_jcol(job, tile0 + nb, i), N - 1);
             btile[nb] = min(tile0 + nb, ((N + 15) >> 4) - 1);
         }
-#ifdef SK_BLOCKED
-        // contiguous range of chunks per wave: consecutive loads of a wave walk along the rows (whole 128-B lines)
-        const int base_n = total / SK_NW, extra = total % SK_NW;
-        const int mine = base_n + (wave < extra ? 1 : 0);
-        const int first = wave * base_n + min(wave, extra);
-        const int last = first + mine - 1;
-        constexpr int STR = 1;
-#else
         const int mine = (total - wave + SK_NW - 1) / SK_NW;  // chunks of this wave (dealt round-robin)
         const int first = wave;
         const int last = wave + (mine - 1) * SK_NW;
         constexpr int STR = SK_NW;
-#endif
         auto run = [&](auto kc_tag) {
             constexpr int BM = decltype(kc_tag)::value;
             auto fetch = [&](int g, f32x4 (&a)[MB], f32x4 (&b)[NB]) {
@@ -395,41 +358,6 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                 }
                 sk_fetch_fast<MB, NB, BM>(A, lda, B, ldb, (g - beg) << 4, mrow, ncl, btile, kk, a, b);
             };
-#if SK_PIPE
-            // Three-stage software pipeline, stages kept apart with scheduling barriers: [loads of chunk i+SK_DEPTH-1]
-            // [lane permutation of chunk i+1 (ds_bpermute into its own registers)] [MFMAs of chunk i].  Left to itself
-            // the scheduler parks every ds_bpermute right in front of the MFMA pair that consumes it, so each pair
-            // waits out an LDS round trip (s_waitcnt lgkmcnt(0) eight times per chunk) and the matrix pipe starves;
-            // it also hoists later chunks' permutations upwards, which drags their vmcnt waits along and collapses
-            // the load prefetch distance.  Here the permutation of the next chunk flies while this chunk multiplies.
-            {
-                f32x4 ra[SK_DEPTH][MB], rb_[SK_DEPTH][NB], pa[2][MB];
-#pragma unroll
-                for (int dd = 0; dd < SK_DEPTH; ++dd) fetch(min(first + dd * STR, last), ra[dd], rb_[dd]);
-#pragma unroll
-                for (int rb = 0; rb < MB; ++rb) pa[0][rb] = ra[0][rb];
-                sk_a_unpermute<MB>(pa[0]);
-                int g = first;
-                // one iteration = SK_DEPTH chunks (static slot indices); the tail runs with clamped fetches
-                const int ngroups = (mine + SK_DEPTH - 1) / SK_DEPTH;
-                for (int gr = 0; gr < ngroups; ++gr) {
-#pragma unroll
-                    for (int dd = 0; dd < SK_DEPTH; ++dd) {
-                        const int nx = (dd + 1) % SK_DEPTH;
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int rb = 0; rb < MB; ++rb) pa[(dd + 1) & 1][rb] = ra[nx][rb];
-                        sk_a_unpermute<MB>(pa[(dd + 1) & 1]);   // next chunk's lanes, consumed one stage later
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (g + dd * STR <= last) sk_mma2<MB, NB>(pa[dd & 1], rb_[dd], acc);
-                        __builtin_amdgcn_sched_barrier(0);
-                        fetch(min(g + (SK_DEPTH + dd) * STR, last), ra[dd], rb_[dd]);
-                    }
-                    g += SK_DEPTH * STR;
-                }
-                return;
-            }
-#endif
             // Ring of SK_DEPTH register buffers, SK_DEPTH chunks per iteration, each slot refilled right after
             // it has fed the MFMAs: no register copies, so nothing in the body waits for loads it has just
             // issued, and SK_DEPTH chunks stay in flight per wave.
@@ -487,9 +415,6 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                 if (dd < rem) sk_mma_bf16<MB, NB>(ra[dd], rb_[dd], acc);
         };
         SK_STAMP(1);
-#if SK_PRIO_YOUNG
-        if (wave >= SK_NW / 2) __builtin_amdgcn_s_setprio(1);  // the second-dispatched half loses every arbitration otherwise
-#endif
         if (mine > 0) {
             if (job.seg[0].b_kcontig == 3) run_bf16();
             else if (job.seg[0].b_kcontig == 2) run(std::integral_constant<int, 2>{});
@@ -555,9 +480,6 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
     }
 
     // Intra-workgroup split-K reduction through LDS.
-#if SK_PRIO_YOUNG
-    __builtin_amdgcn_s_setprio(0);
-#endif
     SK_STAMP(2);
 #pragma unroll
     for (int rb = 0; rb < MB; ++rb)
@@ -684,10 +606,9 @@ __global__ __launch_bounds__(SK_THREADS) void sk_kernel(const SkLaunch L) {
     // workgroups of the jobs are laid out back to back along x and the job is found in the prefix table
     // (a z-grid sized for the largest job was measured slower there: 59 -> 65 ms backward at cfg2).
     int j = blockIdx.z, bx = blockIdx.x;
-#if SK_EARLY_DESC  // the launch header in one batch of scalar loads (zmode, njobs and the prefix table sit in one line)
+    // the launch header in one batch of scalar loads (zmode, njobs and the prefix table sit in one line)
     asm volatile("" ::"s"(L.zmode), "s"(L.njobs), "s"(L.tile_end[0]), "s"(L.tile_end[1]), "s"(L.tile_end[2]), "s"(L.tile_end[3]),
                  "s"(L.tile_end[4]), "s"(L.tile_end[5]), "s"(L.tile_end[6]), "s"(L.tile_end[7]));
-#endif
     if (!L.zmode) {
         j = 0;
 #pragma unroll
@@ -799,7 +720,7 @@ void sk_finalize_job(SkJob& j) {
     if (j.ksplit > 1 && (j.seg[0].b_kcontig != 3 || j.nseg != 1)) j.aligned = -1;  // K parts: wide bf16 kernel only
     // a waiting job: fragment-major weights, f32 (sk_body's tail) or bf16 (wk_body's tail: sk_launch_att refuses the
     // launch if the wide kernel does not take it); anything else is rejected by sk_make_launch
-    if (j.wait_flag && (!al || (j.wait_all ? (j.nseg != 1 || j.seg[0].b_kcontig != 3) : j.nseg < 2) || j.seg[0].b_kcontig < 2 || !SK_A_PERMUTE))
+    if (j.wait_flag && (!al || (j.wait_all ? (j.nseg != 1 || j.seg[0].b_kcontig != 3) : j.nseg < 2) || j.seg[0].b_kcontig < 2))
         j.aligned = -1;
 }
 
@@ -813,7 +734,6 @@ int sk_make_launch(SkLaunch& L, const SkJob* jobs, int njobs) {
             return PH_ERR_BADARG;
     }
     memset(&L, 0, sizeof(L));
-    int t = 0;
     for (int q = 0; q < njobs; ++q) {
         L.job[q] = jobs[q];
         sk_finalize_job(L.job[q]);
@@ -828,7 +748,6 @@ int sk_make_launch(SkLaunch& L, const SkJob* jobs, int njobs) {
         } else {
             tiles = ceil_div(j.N, 16);
         }
-        (void)t;
         L.tile_end[q] = tiles;  // 16-column tiles of the job; sk_launch turns this into a prefix of workgroups
     }
     L.njobs = njobs;
@@ -948,6 +867,57 @@ void sk_account(const SkLaunch& L, double& flops, double& bytes) {
         }
         bytes += wb * ksum * j.N + 4.0 * ((double)j.M * ksum + epi * j.M * j.N);
     }
+}
+
+// The one way a kernel of the family is enqueued.  `acct`: the launch whose jobs are accounted when profiling is on;
+// hetero: the grid also carries attention / state row blocks; BIG_LDS: the kernel may ask for more than the default
+// 64 KiB of dynamic LDS (allowed once per kernel).
+template <auto KERNEL, bool BIG_LDS, typename... Args>
+void sk_enqueue(const SkLaunch& acct, int hetero, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+    if constexpr (BIG_LDS) {
+        static bool allowed = false;
+        if (!allowed) {
+            (void)hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            allowed = true;
+        }
+    }
+    if (g_prof.on) {
+        SkProfRec r;
+        (void)hipEventCreate(&r.e0);
+        (void)hipEventCreate(&r.e1);
+        sk_account(acct, r.flops, r.bytes);
+        hipExtLaunchKernelGGL(KERNEL, grid, block, lds, stream, r.e0, r.e1, 0, args...);
+        r.hetero = hetero;
+        g_prof.recs.push_back(r);
+    } else {
+        hipLaunchKernelGGL(KERNEL, grid, block, lds, stream, args...);
+    }
+}
+
+// Tile shape of a launch (sk_prepare's mbnb = 10 * MB + NB) as compile-time constants: f(MB, NB).
+template <typename F>
+void sk_with_tile(int mbnb, F&& f) {
+    using std::integral_constant;
+    switch (mbnb) {
+        case 11: f(integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
+        case 12: f(integral_constant<int, 1>{}, integral_constant<int, 2>{}); break;
+        case 21: f(integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
+        case 22: f(integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
+        case 31: f(integral_constant<int, 3>{}, integral_constant<int, 1>{}); break;
+        case 32: f(integral_constant<int, 3>{}, integral_constant<int, 2>{}); break;
+        case 41: f(integral_constant<int, 4>{}, integral_constant<int, 1>{}); break;
+        default: f(integral_constant<int, 4>{}, integral_constant<int, 2>{}); break;
+    }
+}
+
+// sk_prepare may have chosen the z-grid; the heterogeneous kernels always walk the prefix table.
+void sk_flatten_zgrid(SkLaunch& L, dim3& grid) {
+    if (!L.zmode) return;
+    const int per = (int)grid.x;
+    for (int q = 0; q < L.njobs; ++q) L.tile_end[q] = per * (q + 1);
+    grid.x = (unsigned)(per * L.njobs);
+    grid.z = 1;
+    L.zmode = 0;
 }
 }  // namespace
 
@@ -1281,16 +1251,22 @@ __device__ __forceinline__ void wk_body(const SkJob& job, int wg_in, int wgh, ch
     }
 }
 
-__global__ __launch_bounds__(SK_THREADS) void wk_kernel(const WkLaunch L) {
-    extern __shared__ __attribute__((aligned(16))) char wk_smem[];
-    int j = 0, bx = blockIdx.x;
+// Wide workgroup bx of the launch: its job from the workgroup prefix table, at the job's width.
+template <bool WAITALL>
+__device__ __forceinline__ void wk_tile(const WkLaunch& L, int bx, char* smem) {
+    int j = 0;
 #pragma unroll
     for (int q = 0; q < SK_MAXJOB - 1; ++q)
         if (q < L.njobs - 1 && bx >= L.wg_end[q]) j = q + 1;
     bx -= (j > 0 ? L.wg_end[j - 1] : 0);
     const SkJob& job = L.job[j];
-    if (L.ncw[j] == 8) wk_body<8>(job, bx, L.wgh[j], wk_smem);
-    else wk_body<4>(job, bx, L.wgh[j], wk_smem);
+    if (L.ncw[j] == 8) wk_body<8, WAITALL>(job, bx, L.wgh[j], smem);
+    else wk_body<4, WAITALL>(job, bx, L.wgh[j], smem);
+}
+
+__global__ __launch_bounds__(SK_THREADS) void wk_kernel(const WkLaunch L) {
+    extern __shared__ __attribute__((aligned(16))) char wk_smem[];
+    wk_tile<false>(L, blockIdx.x, wk_smem);
 }
 
 // Heterogeneous variant of wk_kernel: workgroups [0, natt) carry the attention forward step (one batch row each, all
@@ -1307,14 +1283,7 @@ __global__ __launch_bounds__(SK_THREADS) void wka_kernel(const WkLaunch L, const
         return;
     }
     bx -= natt;
-    int j = 0;
-#pragma unroll
-    for (int q = 0; q < SK_MAXJOB - 1; ++q)
-        if (q < L.njobs - 1 && bx >= L.wg_end[q]) j = q + 1;
-    bx -= (j > 0 ? L.wg_end[j - 1] : 0);
-    const SkJob& job = L.job[j];
-    if (L.ncw[j] == 8) wk_body<8>(job, bx, L.wgh[j], wk_smem);
-    else wk_body<4>(job, bx, L.wgh[j], wk_smem);
+    wk_tile<false>(L, bx, wk_smem);
 }
 
 // ---- fused backward tick (plans.hip schedule 7, LSTM layers, bf16 operands) ------------------------------------------
@@ -1362,14 +1331,7 @@ __global__ __launch_bounds__(ATTB_THREADS) void wkb_kernel(const WkLaunch L, con
     }
     if (threadIdx.x >= SK_THREADS) return;  // the wide workgroups run on eight waves
     bx -= P.nprod;
-    int j = 0;
-#pragma unroll
-    for (int q = 0; q < SK_MAXJOB - 1; ++q)
-        if (q < L.njobs - 1 && bx >= L.wg_end[q]) j = q + 1;
-    bx -= (j > 0 ? L.wg_end[j - 1] : 0);
-    const SkJob& job = L.job[j];
-    if (L.ncw[j] == 8) wk_body<8, true>(job, bx, L.wgh[j], wkb_smem);
-    else wk_body<4, true>(job, bx, L.wgh[j], wkb_smem);
+    wk_tile<true>(L, bx, wkb_smem);
 }
 
 // Would wk_try_launch take a bf16 launch whose jobs have M rows, ncols output columns in total and K segments of H and E
@@ -1380,11 +1342,10 @@ bool sk_wide_takes(int M, int ncols, int H, int E) {
     return ncols >= 4096 || enabled >= 2;
 }
 
-// Takes the launch when every job is a bf16-operand LSTM / LINEAR job over <= 64 rows with 64-deep K segments.
-// att != null: the attention step rides in the same launch (wka_kernel); `reserve` CUs are left to its blocks.
 // Legality + layout of a wide launch: W (jobs that wait go last), its workgroup count t, whether any job waits.
+// Legal when every job is a bf16-operand LSTM / LINEAR job over <= 64 rows with 64-deep K segments.
 // nlead = workgroups that lead the grid beside / before the wide ones (attention blocks, state-backward rows);
-// lead_waiters: some job waits for them (then the non-waiting jobs are sized to fit beside them).
+// has_lead: the launch carries such producers at all (only then may a job wait for them).
 static bool wk_build(const SkLaunch& Lin, int nlead, bool has_lead, WkLaunch& W, int& t, bool& any_flag) {
     const int enabled = sw_wk();  // 0: never; 1 (default): launches with >= 4096 output columns; 2: whenever legal
     if (!enabled) return false;
@@ -1468,29 +1429,9 @@ static bool wk_try_launch(const SkLaunch& Lin, hipStream_t stream, int* rc, cons
         const size_t alds = att_fwd_lds(att->U);
         if (alds > lds) lds = alds;
         const int att_last = any_flag ? 0 : 1;  // producers lead the grid when somebody waits for them
-        if (g_prof.on) {
-            SkProfRec r;
-            (void)hipEventCreate(&r.e0);
-            (void)hipEventCreate(&r.e1);
-            sk_account(Lin, r.flops, r.bytes);
-            hipExtLaunchKernelGGL(wka_kernel, dim3(t + natt), dim3(SK_THREADS), lds, stream, r.e0, r.e1, 0, W, *att, natt, att_last);
-            r.hetero = 1;
-        g_prof.recs.push_back(r);
-        } else {
-            hipLaunchKernelGGL(wka_kernel, dim3(t + natt), dim3(SK_THREADS), lds, stream, W, *att, natt, att_last);
-        }
-        *rc = (int)hipGetLastError();
-        return true;
-    }
-    if (g_prof.on) {
-        SkProfRec r;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        sk_account(Lin, r.flops, r.bytes);
-        hipExtLaunchKernelGGL(wk_kernel, dim3(t), dim3(SK_THREADS), lds, stream, r.e0, r.e1, 0, W);
-        g_prof.recs.push_back(r);
+        sk_enqueue<wka_kernel, false>(Lin, 1, dim3(t + natt), dim3(SK_THREADS), lds, stream, W, *att, natt, att_last);
     } else {
-        hipLaunchKernelGGL(wk_kernel, dim3(t), dim3(SK_THREADS), lds, stream, W);
+        sk_enqueue<wk_kernel, false>(Lin, 0, dim3(t), dim3(SK_THREADS), lds, stream, W);
     }
     *rc = (int)hipGetLastError();
     return true;
@@ -1534,38 +1475,8 @@ int sk_launch_bwd_fused(const SkLaunch& Lin, const AttBwdArgs* att, const LstmSt
     size_t lds = 2 * 64 * WK_PITCH;
     if (plds > lds) lds = plds;
     if (lds > 160 * 1024) return PH_ERR_UNSUPPORTED;
-    static bool allowed = false;
-    if (!allowed) {
-        (void)hipFuncSetAttribute((const void*)wkb_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        allowed = true;
-    }
-    if (g_prof.on) {
-        SkProfRec r;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        sk_account(Lin, r.flops, r.bytes);
-        hipExtLaunchKernelGGL(wkb_kernel, dim3(P.nprod + t), dim3(ATTB_THREADS), lds, stream, r.e0, r.e1, 0, W, P);
-        r.hetero = 1;
-        g_prof.recs.push_back(r);
-    } else {
-        hipLaunchKernelGGL(wkb_kernel, dim3(P.nprod + t), dim3(ATTB_THREADS), lds, stream, W, P);
-    }
+    sk_enqueue<wkb_kernel, true>(Lin, 1, dim3(P.nprod + t), dim3(ATTB_THREADS), lds, stream, W, P);
     return (int)hipGetLastError();
-}
-
-
-template <int MB, int NB>
-static void sk_dispatch(const SkLaunch& L, dim3 grid, size_t lds, hipStream_t stream) {
-    if (g_prof.on) {
-        SkProfRec r;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        sk_account(L, r.flops, r.bytes);
-        hipExtLaunchKernelGGL((sk_kernel<MB, NB>), grid, dim3(SK_THREADS), lds, stream, r.e0, r.e1, 0, L);
-        g_prof.recs.push_back(r);
-    } else {
-        hipLaunchKernelGGL((sk_kernel<MB, NB>), grid, dim3(SK_THREADS), lds, stream, L);
-    }
 }
 
 // Tile shape, grid and finished descriptor (workgroup prefix, z-mode) of a launch.
@@ -1644,49 +1555,10 @@ int sk_launch(const SkLaunch& Lin, hipStream_t stream) {
     size_t lds;
     int mbnb;
     sk_prepare(Lin, L, grid, lds, mbnb);
-    switch (mbnb) {
-        case 11: sk_dispatch<1, 1>(L, grid, lds, stream); break;
-        case 12: sk_dispatch<1, 2>(L, grid, lds, stream); break;
-        case 21: sk_dispatch<2, 1>(L, grid, lds, stream); break;
-        case 22: sk_dispatch<2, 2>(L, grid, lds, stream); break;
-        case 31: sk_dispatch<3, 1>(L, grid, lds, stream); break;
-        case 32: sk_dispatch<3, 2>(L, grid, lds, stream); break;
-        case 41: sk_dispatch<4, 1>(L, grid, lds, stream); break;
-        default: sk_dispatch<4, 2>(L, grid, lds, stream); break;
-    }
+    sk_with_tile(mbnb, [&](auto mb, auto nb) {
+        sk_enqueue<sk_kernel<decltype(mb)::value, decltype(nb)::value>, false>(L, 0, grid, dim3(SK_THREADS), lds, stream, L);
+    });
     return (int)hipGetLastError();
-}
-
-template <int MB, int NB>
-static void ska_allow_lds() {
-    static bool done = false;
-    if (!done) {
-        (void)hipFuncSetAttribute((const void*)ska_kernel<MB, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        done = true;
-    }
-}
-
-template <int MB, int NB>
-static void ska_dispatch(const SkLaunch& L, const AttFwdArgs& g, int natt_x, dim3 grid, size_t lds, hipStream_t stream) {
-    // Order of the two kinds of workgroups in the grid.  Without in-launch dependencies the GEMM workgroups (the long
-    // ones) go first and the attention fills in behind them (measured: forward scan 28.0 -> 25.3 ms at cfg2); a job that
-    // waits for the attention needs its producers dispatched first.
-    ska_allow_lds<MB, NB>();
-    int att_last = 1;
-    for (int q = 0; q < L.njobs; ++q)
-        if (L.job[q].wait_flag) att_last = 2;  // producers first, and all of them in grid row 0
-    if (g_prof.on) {
-        SkProfRec r;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        sk_account(L, r.flops, r.bytes);
-        hipExtLaunchKernelGGL((ska_kernel<MB, NB>), grid, dim3(SK_THREADS), lds, stream, r.e0, r.e1, 0, L, g, natt_x,
-                              att_last);
-        r.hetero = 1;
-        g_prof.recs.push_back(r);
-    } else {
-        hipLaunchKernelGGL((ska_kernel<MB, NB>), grid, dim3(SK_THREADS), lds, stream, L, g, natt_x, att_last);
-    }
 }
 
 // One launch for the attention step `att` and the step-GEMM jobs of L (njobs may be 0: attention alone).
@@ -1708,14 +1580,7 @@ int sk_launch_att(const SkLaunch& Lin, const AttFwdArgs& att, hipStream_t stream
     size_t lds;
     int mbnb;
     sk_prepare(Lin, L, grid, lds, mbnb);
-    // sk_prepare may have chosen the z-grid; this kernel always walks the prefix table
-    if (L.zmode) {
-        const int per = (int)grid.x;
-        for (int q = 0; q < L.njobs; ++q) L.tile_end[q] = per * (q + 1);
-        grid.x = (unsigned)(per * L.njobs);
-        grid.z = 1;
-        L.zmode = 0;
-    }
+    sk_flatten_zgrid(L, grid);
     const int natt = g.B * g.esplit;
     bool flagged = false;
     for (int q = 0; q < L.njobs; ++q)
@@ -1728,40 +1593,15 @@ int sk_launch_att(const SkLaunch& Lin, const AttFwdArgs& att, hipStream_t stream
     grid.x += (unsigned)natt_x;
     const size_t alds = att_fwd_lds(g.U);
     if (alds > lds) lds = alds;
-    switch (mbnb) {
-        case 11: ska_dispatch<1, 1>(L, g, natt_x, grid, lds, stream); break;
-        case 12: ska_dispatch<1, 2>(L, g, natt_x, grid, lds, stream); break;
-        case 21: ska_dispatch<2, 1>(L, g, natt_x, grid, lds, stream); break;
-        case 22: ska_dispatch<2, 2>(L, g, natt_x, grid, lds, stream); break;
-        case 31: ska_dispatch<3, 1>(L, g, natt_x, grid, lds, stream); break;
-        case 32: ska_dispatch<3, 2>(L, g, natt_x, grid, lds, stream); break;
-        case 41: ska_dispatch<4, 1>(L, g, natt_x, grid, lds, stream); break;
-        default: ska_dispatch<4, 2>(L, g, natt_x, grid, lds, stream); break;
-    }
+    // Order of the two kinds of workgroups in the grid.  Without in-launch dependencies the GEMM workgroups (the long
+    // ones) go first and the attention fills in behind them (measured: forward scan 28.0 -> 25.3 ms at cfg2); a job that
+    // waits for the attention needs its producers dispatched first, and all of them in grid row 0.
+    const int att_last = flagged ? 2 : 1;
+    sk_with_tile(mbnb, [&](auto mb, auto nb) {
+        sk_enqueue<ska_kernel<decltype(mb)::value, decltype(nb)::value>, true>(L, 1, grid, dim3(SK_THREADS), lds, stream, L, g,
+                                                                                natt_x, att_last);
+    });
     return (int)hipGetLastError();
-}
-
-template <int MB, int NB>
-static void skb_dispatch(const SkLaunch& L, const AttBwdArgs& g, const GruStateBwdArgs& sa, int att_rows, int l0_chain,
-                         int nlead, int nlead_x, int rpb, dim3 grid, size_t lds, hipStream_t stream) {
-    static bool allowed = false;
-    if (!allowed) {
-        (void)hipFuncSetAttribute((const void*)skb_kernel<MB, NB>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        allowed = true;
-    }
-    if (g_prof.on) {
-        SkProfRec r;
-        (void)hipEventCreate(&r.e0);
-        (void)hipEventCreate(&r.e1);
-        sk_account(L, r.flops, r.bytes);
-        hipExtLaunchKernelGGL((skb_kernel<MB, NB>), grid, dim3(ATTB_THREADS), lds, stream, r.e0, r.e1, 0, L, g, sa, att_rows,
-                              l0_chain, nlead, nlead_x, rpb);
-        r.hetero = 1;
-        g_prof.recs.push_back(r);
-    } else {
-        hipLaunchKernelGGL((skb_kernel<MB, NB>), grid, dim3(ATTB_THREADS), lds, stream, L, g, sa, att_rows, l0_chain, nlead,
-                           nlead_x, rpb);
-    }
 }
 
 // Attention backward (or null) + GRU state backward of all chains + the step-GEMM jobs of L in ONE launch (skb_kernel).
@@ -1792,26 +1632,14 @@ int sk_launch_bwd_hetero(const SkLaunch& Lin, const AttBwdArgs* att, const GruSt
     size_t lds;
     int mbnb;
     sk_prepare(Lin, L, grid, lds, mbnb);
-    if (L.zmode) {  // this kernel always walks the prefix table
-        const int per = (int)grid.x;
-        for (int q = 0; q < L.njobs; ++q) L.tile_end[q] = per * (q + 1);
-        grid.x = (unsigned)(per * L.njobs);
-        grid.z = 1;
-        L.zmode = 0;
-    }
+    sk_flatten_zgrid(L, grid);
     const int nlead_x = ceil_div(nlead, (int)grid.y);
     grid.x += (unsigned)nlead_x;
     if (alds > lds) lds = alds;
     if (lds > 160 * 1024) return PH_ERR_UNSUPPORTED;
-    switch (mbnb) {
-        case 11: skb_dispatch<1, 1>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        case 12: skb_dispatch<1, 2>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        case 21: skb_dispatch<2, 1>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        case 22: skb_dispatch<2, 2>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        case 31: skb_dispatch<3, 1>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        case 32: skb_dispatch<3, 2>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        case 41: skb_dispatch<4, 1>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-        default: skb_dispatch<4, 2>(L, g, sa, att_rows, l0_chain, nlead, nlead_x, rpb, grid, lds, stream); break;
-    }
+    sk_with_tile(mbnb, [&](auto mb, auto nb) {
+        sk_enqueue<skb_kernel<decltype(mb)::value, decltype(nb)::value>, true>(L, 1, grid, dim3(ATTB_THREADS), lds, stream, L, g,
+                                                                                sa, att_rows, l0_chain, nlead, nlead_x, rpb);
+    });
     return (int)hipGetLastError();
 }

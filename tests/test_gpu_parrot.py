@@ -498,3 +498,79 @@ def test_full_size_cfg2_properties(dev, monkeypatch):
     assert_close(g3, 2.0 * g1, 1e-6, "backward linearity")
 
 
+# ----------------------------------------------------------------------------- profiled launch path
+PROFILED_CASES = {
+    # name: (model kwargs, compute dtype, T, B, U, environment, schedule the plan picks, plain launches expected)
+    "gru_f32": (dict(num_layers=2, rnn_h_dim=64, readouts_dim=64, encoder_type='bidirectional', encoder_dim=32,
+                     cell_type='gru'), 'float32', 4, 5, 7, {}, 5, True),
+    "lstm_bf16_wide": (dict(num_layers=3, rnn_h_dim=128, readouts_dim=128, encoder_type='bidirectional', encoder_dim=64,
+                            cell_type='lstm'), 'bf16', 5, 5, 9, {"PARROT_WK": "2"}, 7, False),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PROFILED_CASES))
+def test_profiled_launches_count_and_compute_the_same(dev, monkeypatch, case):
+    """The per-dispatch timing of the step-kernel family (parrot_profile_begin / parrot_profile_end2: every launch goes out
+    through hipExtLaunchKernelGGL between two events of its own and is recorded with its flops and bytes) on eager
+    launches, as in bench.py's roofline leg: it counts launches, accounts work, and changes nothing that is computed --
+    cost and every gradient are bit-equal to the same step without profiling.
+
+    gru_f32: the plan picks schedule 5 (asserted) and, with all accumulators allocated, the K-balanced backward tick.  The
+    step reaches sk_kernel (the gate / candidate launches of every tick, the backward tick's X and Y launches: the plain
+    ones), ska_kernel (the attention beside the upper layer's input projections) and skb_kernel (the backward tick's row
+    blocks beside the deferred downward products).
+    lstm_bf16_wide: PARROT_WK=2 lets the wide kernel take these small launches, so the plan picks schedule 7 (asserted) with
+    the fused backward tick.  The step reaches wka_kernel (every forward tick that carries an attention step), wk_kernel
+    (the forward ticks without one: the first, and the two in which only upper layers are left) and wkb_kernel (every
+    backward tick); the f32 encoder's step launches stay on sk_kernel.  The plain count is only bounded by the launch
+    count here."""
+    import ctypes as C
+    from oracle import parrot_ref as R
+    from parrot_amd import _lib
+    from parrot_amd.model import Parrot
+    kw, dtype, T, B, U, env, schedule, plain_expected = PROFILED_CASES[case]
+    for name in ("PARROT_SCHEDULE", "PARROT_WK", "PARROT_BWD_HETERO", "PARROT_CHUNK", "PARROT_S5_WSTEP", "PARROT_GRU_ROWWISE"):
+        monkeypatch.delenv(name, raising=False)
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    cfg = R.default_config(**kw)
+    m = Parrot(device=dev, use_graph=False, compute_dtype=dtype, **kw).allocate()
+    m.set_parameter_values(R.init_params(cfg, seed=17, scale_by_fan_in=True))
+    feat, fm, lab, lm, _ = make_batch(cfg, T, B, U, seed=18, ragged=True)
+    batch = (feat.float().to(dev), fm.float().to(dev), lab.to(dev), lm.float().to(dev))
+    lib = _lib.load()
+
+    def step():
+        m.zero_grad()
+        cost = m.compute_cost(*batch, None, 1, B)[0]
+        cost.backward()
+        torch.cuda.synchronize()
+        return cost.detach().cpu().clone(), {k: v.detach().cpu().clone() for k, v in m.get_gradient_dict().items()}
+
+    def end():
+        us, fl, by, plain = C.c_double(), C.c_double(), C.c_double(), (C.c_double * 4)()
+        n = lib.parrot_profile_end2(C.byref(us), C.byref(fl), C.byref(by), plain)
+        return int(n), us.value, fl.value, by.value, [float(x) for x in plain]
+
+    cost0, grads0 = step()
+    lib.parrot_profile_begin()
+    try:
+        cost1, grads1 = step()
+    finally:  # profiling is process-wide: a failing step must not leave it on for the tests that follow
+        n, us, fl, by, plain = end()
+    assert int(lib.parrot_decoder_schedule(next(iter(m._train_ws.values()))['plan'])) == schedule
+    print(f"{case}: {n} launches ({plain[3]:.0f} plain), {us:.1f} us, {fl:.3e} flops, {by:.3e} bytes")
+    assert n > 0
+    assert 0 <= plain[3] <= n and plain[3] == int(plain[3])
+    assert plain[3] < n  # both cases carry heterogeneous launches (ska / skb, wka / wkb): those are not counted as plain
+    if plain_expected:
+        assert plain[3] > 0 and plain[1] > 0 and plain[2] > 0
+    assert fl > 0 and by > 0
+    assert plain[1] <= fl and plain[2] <= by
+    assert torch.equal(cost0, cost1)
+    assert len(grads0) >= 10 and grads0.keys() == grads1.keys()
+    for name, g0 in grads0.items():
+        assert torch.equal(g0, grads1[name]), name
+    lib.parrot_profile_begin()
+    assert end()[0] == 0
+    m.close()

@@ -1,6 +1,7 @@
 // The merged step launches of the cfg2 training scan (2 GRU layers, H=1024, E=256, B=64), timed in isolation with the
-// fragment-major weight copies the scan uses.  Development aid for the K-loop variants of sk_kernel (SK_DEPTH, SK_PIPE):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DSK_PIPE=1 -DSK_DEPTH=4] tools/skbench3.hip -o tools/probe_bin/skbench3_x
+// fragment-major weight copies the scan uses.  Development aid for the K loop of sk_kernel (ring depth SK_DEPTH; the
+// software-pipelined variant this probe once timed is recorded in profiles/r03_skbench3_kloop_variants.txt):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 [-DSK_DEPTH=4] tools/skbench3.hip parrot_amd/csrc/attention.hip -o tools/probe_bin/skbench3
 #include "../parrot_amd/csrc/skinny.hip"
 
 #include <stdio.h>
