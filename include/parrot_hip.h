@@ -450,12 +450,25 @@ typedef struct ParrotSampleDesc {
      * row adds H / 16 of them instead of reading its state row and the whole projection matrix (model.py:926-930 is the
      * same sum, associated tile by tile).  NULL or PARROT_PM_ATTFOLD=0: the row computes the projection itself. */
     const float* Watt_t;
+    /* bf16 = 1: decode with bf16 operands.  The one product per layer and step, [h_l[t] ; w ; h_0[t+1] .. h_{l-1}[t+1] ; x[t]]
+     * . Wg_t[l], rounds BOTH operands to bf16 (nearest even) where they enter the product and accumulates in f32; states,
+     * cells, biases, additive inputs, the attention and the composed output product stay f32.  LSTM stacks on the
+     * persistent machine only: cell = 1, MSE head, no layer_norm, B <= 64, H and E multiples of 32, workspace given, and
+     *   Wg_t16[l]: the matrix of Wg_t[l] (feedback rows appended, padded to 64) as parrot_tile_weights_bf16(.., mode 2,
+     *              lstm_H = H), rows*cols bf16; Wg_t[l] is then not read and may be NULL.
+     * Resident bf16 slabs take half the LDS, so more of them stay on chip, and the streamed ones move half the bytes.
+     * There is no f32 decode behind this switch: parrot_sample_create returns PARROT_ERR_UNSUPPORTED for every configuration
+     * the bf16 machine does not take (parrot_sample_persist_floats returns 0 for them). */
+    int bf16, reserved8;
+    const void* Wg_t16[PARROT_MAX_LAYERS];
 } ParrotSampleDesc;
 
 long long parrot_sample_persist_floats(const ParrotSampleDesc* desc);
 /* 0: per-step launches; 1: the machine with whole-K phases (GRU: 2L + 3; LSTM: L + 2); 2: the machine with the step cut
  * along K (GRU, Wro_t given); 3: the same with the fed-back frame out of the chain (Wgx_t / Wcx_t given, 2L + 1 phases) */
 int parrot_sample_is_persistent(void* plan);
+/* 1: the plan runs the machine with bf16 operands (ParrotSampleDesc::bf16); 0: every product has f32 operands */
+int parrot_sample_is_bf16(void* plan);
 /* Plans the decode machine for `desc` with `nwg` workgroups WITHOUT touching device memory (pointers are only used for
  * address arithmetic) and replays the unit table symbolically: every read must find its value written in an earlier
  * phase, every buffer element is written once.  info16: [0] phases per step, [1] partial-sum buffers, [2] checker
@@ -487,7 +500,11 @@ int parrot_sumsq(const float* x, size_t n, float* out, void* stream);
 int parrot_tile_weights(const float* W, int rows, int cols, int ld, float* out, int mode, int lstm_H, void* stream);
 /* The same copy rounded to bf16 (round to nearest even) for the bf16 operand mode of the decoder scan
  * (ParrotDecoderDesc::bf16): 1 KB blocks of 16 columns x 32 K-rows in v_mfma_f32_16x16x32_bf16 operand order.  The
- * K extent (rows in mode 0, cols in mode 1) must be a multiple of 32, the other one of 16.  out: rows*cols bf16. */
+ * K extent (rows in mode 0, cols in mode 1) must be a multiple of 32, the other one of 16.  out: rows*cols bf16.
+ * mode 2: for the bf16 decode machine (ParrotSampleDesc::bf16).  Tiles, chunks and columns as mode 0 (lstm_H applies), but
+ * the eight K rows of lane (kk, i) of chunk c are 32c + 4kk .. + 3 and 32c + 16 + 4kk .. + 3 -- the rows the same lane of
+ * two consecutive f32 fragment-major activation blocks holds, so the machine rounds its activations in place and moves
+ * nothing between lanes (an MFMA is indifferent to a permutation of K that both operands share). */
 int parrot_tile_weights_bf16(const float* W, int rows, int cols, int ld, void* out, int mode, int lstm_H, void* stream);
 
 /* _simple_norm / _apply_norm of the reference (model.py:24-34; used when layer_norm=True on the Fork outputs

@@ -114,6 +114,8 @@ class SampleDesc(C.Structure):
         ("Wro_t", C.c_void_p), ("ro_const", C.c_void_p),
         ("Wgx_t", C.c_void_p * MAX_LAYERS), ("Wcx_t", C.c_void_p * MAX_LAYERS),
         ("Watt_t", C.c_void_p),
+        ("bf16", C.c_int), ("reserved8", C.c_int),
+        ("Wg_t16", C.c_void_p * MAX_LAYERS),
     ]
 
 
@@ -180,6 +182,7 @@ SIGNATURES = {
     "parrot_sample_create": (_i, [C.POINTER(SampleDesc), C.POINTER(C.c_void_p)]),
     "parrot_sample_persist_floats": (C.c_longlong, [C.POINTER(SampleDesc)]),
     "parrot_sample_is_persistent": (_i, [_vp]),
+    "parrot_sample_is_bf16": (_i, [_vp]),
     "parrot_sample_plan_pieces_dry": (_i, [C.POINTER(SampleDesc), _i, C.POINTER(C.c_int)]),
     "parrot_sample_status": (_i, [_vp]),
     "parrot_decoder_status": (_i, [_vp]),

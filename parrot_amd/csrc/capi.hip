@@ -216,7 +216,7 @@ int parrot_tile_weights(const float* W, int rows, int cols, int ld, float* out, 
 }
 
 int parrot_tile_weights_bf16(const float* W, int rows, int cols, int ld, void* out, int mode, int lstm_H, void* stream) { PH_ENTRY();
-    if (mode != 0 && mode != 1) return PARROT_ERR_BADARG;
+    if (mode != 0 && mode != 1 && mode != 2) return PARROT_ERR_BADARG;
     return sk_tile_weights_bf16_launch(W, rows, cols, ld, out, mode, lstm_H, (hipStream_t)stream);
 }
 

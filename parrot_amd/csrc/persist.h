@@ -20,7 +20,8 @@
 
 enum { PM_MAXENT = 12,   // unit descriptors per workgroup: n_slots * maxu <= PM_MAXENT (training 3 x 3, decode 9 x 1)
        PM_MAXSLOTS = 9, PM_THREADS = 512, PM_MAXINIT = 12, PM_MAXDST = 6, PM_MAXWDST = 8, PM_MAXFILL = 16 };
-enum { PM_NONE = 0, PM_GEMM = 1, PM_ATT = 2 };
+// PM_GEMM16: a GEMM unit whose weight slab is a bf16 copy (decode with bf16 operands, below); every other field as PM_GEMM
+enum { PM_NONE = 0, PM_GEMM = 1, PM_ATT = 2, PM_GEMM16 = 3 };
 enum { PM_EPI_LINEAR = 0, PM_EPI_GATES = 1, PM_EPI_CAND = 2, PM_EPI_LSTM = 3 };
 
 // LDS map (floats): resident weights | scratch shared by the split-K reduction (8 partial 16x16 tiles, rows padded
@@ -56,7 +57,7 @@ struct PmUnit {
     int kind, lag, K, w_lds;     // w_lds >= 0: float offset of the resident weight slab in LDS; -1: stream from W
     unsigned a_off, a_st;        // the activation slab the unit reads
     int a_nch, a_c0;             // chunks per row block of that slab / the unit's first chunk in it (K/16 chunks are read)
-    const float* W;              // fragment-major weights of the unit: [K/16][256] floats
+    const float* W;              // fragment-major weights of the unit: [K/16][256] floats (PM_GEMM16: [K/32][512] bf16)
     int epi, M, rtile, row;      // rtile: GATES tile of the reset gate (LSTM: the tile's quarter of a block, below); row: batch row of an ATT unit
     const float* bias;           // 16 floats (the tile's columns) or null
     PmRM add[4];                 // additive pre-activation inputs (p == null: unused)
@@ -77,6 +78,13 @@ struct PmUnit {
     // instead of reading its state row and the 120 KB projection matrix.  pw[0] == null: no fold.
     const float* pw[2];
     PmRM pp;
+    // bf16 operands (decode, kind = PM_GEMM16; K a multiple of 32): the unit walks K in 32-deep steps.  Step s takes the two
+    // f32 activation blocks 2s and 2s + 1 of its slab -- lane (kk, r) holds X[r][32 s + 4 kk .. + 3] and
+    // X[r][32 s + 16 + 4 kk .. + 3] --, rounds them to bf16 (nearest even) where they enter the product and issues ONE
+    // v_mfma_f32_16x16x32_bf16 against the 1 KB block s of W, whose lane (kk, n) holds the same eight K rows of column n
+    // (parrot_tile_weights_bf16, mode 2): an MFMA does not care about a permutation of K both operands share, so no lane
+    // moves anything.  The slabs stay f32 (the dataflow hand-off polls f32 slots BEFORE they are rounded), accumulation,
+    // epilogue and outputs are those of the PM_GEMM unit.  A resident slab takes K * 8 floats of LDS instead of K * 16.
 };
 
 struct PmAtt {
@@ -115,7 +123,8 @@ struct PmFill {
 struct PmProgram {
     int T, n_ticks, nwg, MB, M, ninit, n_slots, maxu;  // a tick = n_slots phases of up to maxu units per workgroup
     int dataflow, nfill;
-    int lstm, pad;        // lstm: some units are PM_EPI_LSTM (selects the kernels compiled with that epilogue)
+    int lstm, w16;        // lstm: some units are PM_EPI_LSTM (selects the kernels compiled with that epilogue); w16: some
+                          // are PM_GEMM16 (the kernels that also carry the bf16 K loop; LSTM programs only)
     PmFill fill[PM_MAXFILL];
     const PmUnit* units;  // device: [n_slots][nwg][maxu]
     unsigned* sync;       // device: PM_SYNC_WORDS + PM_DBG_WORDS unsigned, zeroed before every launch

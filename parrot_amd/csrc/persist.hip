@@ -179,7 +179,9 @@ __device__ __forceinline__ f32x4 pm_sigmoid4(f32x4 x) {
 // LDS, shared by the MB waves of the same ks; or a global load when the slab is streamed) feed 4 MFMA 16x16x4.
 // LS: the program has LSTM units (PmProgram::lstm).  A template parameter, not a run-time branch: the kernels of the GRU
 // programs (LS = false) compile to what they were before the LSTM epilogue existed.
-template <int MB, bool DF, bool LS>
+// W16: the unit is a PM_GEMM16 (persist.h): bf16 weight slab, 32-deep steps, one v_mfma_f32_16x16x32_bf16 per step.  Also
+// a template parameter: only the kernels of the programs that have such units (PmProgram::w16) carry the second K loop.
+template <int MB, bool DF, bool LS, bool W16>
 __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds_w, float* lds_red,
                                         const __amdgpu_buffer_rsrc_t fm, unsigned long long* stage, unsigned* sync) {
     const unsigned long long ts0 = pm_clock();
@@ -188,7 +190,8 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rb = wave % MB, ks = wave / MB;
 
-    const int total = __builtin_amdgcn_readfirstlane(u.K >> 4);  // 16-deep chunks of the unit's slab
+    // 16-deep chunks of the unit's slab; W16: 32-deep steps (the waves' K ranges start on 32-deep boundaries, some may be empty)
+    const int total = __builtin_amdgcn_readfirstlane(u.K >> (W16 ? 5 : 4));
     const unsigned abase = __builtin_amdgcn_readfirstlane(u.a_off + (unsigned)t * u.a_st) +
                            ((unsigned)(rb * __builtin_amdgcn_readfirstlane(u.a_nch) + __builtin_amdgcn_readfirstlane(u.a_c0)) << 10);
     const int c0 = (ks * total) / KS, c1 = ((ks + 1) * total) / KS;
@@ -221,7 +224,7 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
 #pragma unroll
     for (int q = 0; q < 4; ++q) p_in[q] = (f32x4){0.f, 0.f, 0.f, 0.f};
     // (round 5) layer 0's candidate units of the decode machine: the two projection-matrix blocks of the fold, asked for now
-    const bool fold = MB == 1 && fin && __builtin_amdgcn_readfirstlane(u.pw[0] != nullptr);
+    const bool fold = !W16 && MB == 1 && fin && __builtin_amdgcn_readfirstlane(u.pw[0] != nullptr);  // (no bf16 unit carries it)
     f32x4 pwb0 = {0.f, 0.f, 0.f, 0.f}, pwb1 = {0.f, 0.f, 0.f, 0.f};
     if (fold) {
         pwb0 = *reinterpret_cast<const f32x4*>(u.pw[0] + (lane << 2));
@@ -319,9 +322,78 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
                 rbv[d % DB] = loadB(min(c + DB + d, last));
             }
     };
+    // W16: step s = A blocks 2s and 2s + 1 (f32: polled for EMPTY as they are, THEN rounded) against block s of the bf16 slab.
+    // The rings hold the same bytes of activations as above, half the bytes of weights.
+    auto run16 = [&](auto res_tag) {
+        constexpr bool RES = decltype(res_tag)::value;
+        auto loadB = [&](int s) -> f32x4 {  // 1 KB: 64 lanes x 8 bf16
+            if (RES) return *reinterpret_cast<const f32x4*>(wl + ((size_t)s << 8) + (lane << 2));
+            return __builtin_nontemporal_load(wg + ((size_t)s << 6) + lane);
+        };
+        auto mma16 = [&](const f32x4& lo, const f32x4& hi, const f32x4& b, f32x4& acc) {
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph_bf16x8(lo, hi), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+        };
+        constexpr int D = (RES ? PM_DEPTH : PM_SDEPTH) / 2, DB = RES ? PM_WDEPTH : D;  // (an LDS read outlasts several of these MFMAs)
+        static_assert(D % DB == 0, "");
+        f32x4 ra[D][2], rbv[DB];
+        const int last = c1 - 1;
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            ra[d][0] = loadA(2 * min(c0 + d, last));
+            ra[d][1] = loadA(2 * min(c0 + d, last) + 1);
+        }
+#pragma unroll
+        for (int d = 0; d < DB; ++d) rbv[d] = loadB(min(c0 + d, last));
+        if (DF) {  // (as above: wait for the first block, then ask for all the others again at once)
+            bool waited = false;
+            unsigned n = 0;
+            while (__builtin_amdgcn_ballot_w64(row_ok && pm_is_empty(ra[0][0])) != 0ull) {
+                waited = true;
+                if ((++n & 1023u) == 0u) {
+                    if (pm_ld(sync + PM_S_ABORT)) break;
+                    if (n > PM_POLL_LIMIT) { pm_give_up(sync); break; }
+                }
+                __builtin_amdgcn_s_sleep(1);
+                ra[0][0] = loadA(2 * c0);
+            }
+            if (waited) {
+                ra[0][1] = loadA(2 * c0 + 1);
+#pragma unroll
+                for (int d = 1; d < D; ++d) {
+                    ra[d][0] = loadA(2 * min(c0 + d, last));
+                    ra[d][1] = loadA(2 * min(c0 + d, last) + 1);
+                }
+            }
+        }
+        int c = c0;
+        for (; c + D <= c1; c += D) {
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                takeA(ra[d][0], 2 * (c + d));
+                takeA(ra[d][1], 2 * (c + d) + 1);
+                mma16(ra[d][0], ra[d][1], rbv[d % DB], (d & 1) ? acc1 : acc0);
+                ra[d][0] = loadA(2 * min(c + D + d, last));
+                ra[d][1] = loadA(2 * min(c + D + d, last) + 1);
+                rbv[d % DB] = loadB(min(c + DB + d, last));
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < D - 1; ++d)
+            if (c + d < c1) {
+                takeA(ra[d][0], 2 * (c + d));
+                takeA(ra[d][1], 2 * (c + d) + 1);
+                mma16(ra[d][0], ra[d][1], rbv[d % DB], (d & 1) ? acc1 : acc0);
+                rbv[d % DB] = loadB(min(c + DB + d, last));
+            }
+    };
     if (c1 > c0) {
-        if (resident) run(std::true_type{});
-        else run(std::false_type{});
+        if (W16) {
+            if (resident) run16(std::true_type{});
+            else run16(std::false_type{});
+        } else {
+            if (resident) run(std::true_type{});
+            else run(std::false_type{});
+        }
     }
     const f32x4 part = acc0 + acc1;
     if (DF && fin && row_ok) {  // whatever had not landed when it was first asked for: poll it now
@@ -695,7 +767,8 @@ __device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* 
 }
 
 // ------------------------------------------------------------------------------------------------ kernel
-template <int MB, bool DF, bool LS>
+// W16: the program has PM_GEMM16 units (PmProgram::w16); false: the kernel is what it was before they existed
+template <int MB, bool DF, bool LS, bool W16>
 __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lds_w = lds;
@@ -747,8 +820,9 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
     for (int s = 0; s < n_slots; ++s)
         for (int q = 0; q < maxu; ++q) {
             const PmUnit& u = lds_units[s * maxu + q];
-            if (u.kind != PM_GEMM || u.w_lds < 0) continue;
-            const int nch = u.K >> 4;
+            const bool w16 = W16 && u.kind == PM_GEMM16;
+            if ((u.kind != PM_GEMM && !w16) || u.w_lds < 0) continue;
+            const int nch = w16 ? u.K >> 5 : u.K >> 4;  // 1 KB blocks: 16 K-rows of floats or 32 of bf16
             const f32x4* src = reinterpret_cast<const f32x4*>(u.W);
             f32x4* dst = reinterpret_cast<f32x4*>(lds_w + u.w_lds);
             for (int i = tid; i < nch * 64; i += PM_THREADS) dst[i] = src[i];
@@ -793,7 +867,8 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
                 if (kind == PM_NONE) continue;
                 const int t = tick - __builtin_amdgcn_readfirstlane(u.lag);
                 if (t < 0 || t >= P.T) continue;
-                if (kind == PM_GEMM) pm_gemm<MB, DF, LS>(u, t, lds_w, lds_red, fmr, stage, sync);
+                if (kind == PM_GEMM) pm_gemm<MB, DF, LS, false>(u, t, lds_w, lds_red, fmr, stage, sync);
+                else if (W16 && kind == PM_GEMM16) pm_gemm<MB, DF, LS, true>(u, t, lds_w, lds_red, fmr, stage, sync);
                 else pm_att_row<DF>(P.att, u.row, t, lds_att, P.fm_base, sync);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -876,7 +951,7 @@ int pm_status(const PmProgram& P) {
 
 int pm_launch(const PmProgram& P, hipStream_t stream) {
     if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
-        P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL)
+        P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL || (P.w16 && !P.lstm))
         return PH_ERR_BADARG;
     if (P.att.U > PM_ATT_MAXU || P.att.A > PM_ATT_MAXA) return PH_ERR_UNSUPPORTED;
     // barrier / census / abort words and the timers are cleared; the sticky words at the end of the sync area are not
@@ -898,20 +973,23 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     static bool attr_done = false;
     if (!attr_done) {
         const int l = (int)lds;
-#define PM_ATTR(MB_, DF_, LS_) \
-    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
-        PM_ATTR(1, false, false); PM_ATTR(2, false, false); PM_ATTR(4, false, false);
-        PM_ATTR(1, true, false); PM_ATTR(2, true, false); PM_ATTR(4, true, false);
-        PM_ATTR(1, false, true); PM_ATTR(2, false, true); PM_ATTR(4, false, true);
-        PM_ATTR(1, true, true); PM_ATTR(2, true, true); PM_ATTR(4, true, true);
+#define PM_ATTR(MB_, DF_, LS_, W16_) \
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+        PM_ATTR(1, false, false, false); PM_ATTR(2, false, false, false); PM_ATTR(4, false, false, false);
+        PM_ATTR(1, true, false, false); PM_ATTR(2, true, false, false); PM_ATTR(4, true, false, false);
+        PM_ATTR(1, false, true, false); PM_ATTR(2, false, true, false); PM_ATTR(4, false, true, false);
+        PM_ATTR(1, true, true, false); PM_ATTR(2, true, true, false); PM_ATTR(4, true, true, false);
+        PM_ATTR(1, false, true, true); PM_ATTR(2, false, true, true); PM_ATTR(4, false, true, true);
+        PM_ATTR(1, true, true, true); PM_ATTR(2, true, true, true); PM_ATTR(4, true, true, true);
 #undef PM_ATTR
         attr_done = true;
     }
     const dim3 grid(P.nwg), block(PM_THREADS);
 #define PM_GO(MB_, DF_) \
     do { \
-        if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true>), grid, block, lds, stream, P); \
-        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false>), grid, block, lds, stream, P); \
+        if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true>), grid, block, lds, stream, P); \
+        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false>), grid, block, lds, stream, P); \
+        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false>), grid, block, lds, stream, P); \
     } while (0)
     switch (P.MB * 2 + (P.dataflow ? 1 : 0)) {
         case 2: PM_GO(1, false); break;

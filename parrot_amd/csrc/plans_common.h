@@ -253,10 +253,48 @@ int traced_bwd_fused_launch(const AttBwdArgs* g, const LstmStateBwdArgs& sa, int
 // ----------------------------------------------------------------------------- persistent machine: unit placement
 struct PmReq { PmUnit u; int slot, krows, crit; };
 
+// Programs with PM_GEMM16 units only (every other table stays as the greedy pass left it): with slabs of half the size a
+// workgroup's LDS can hold SEVERAL of its units' slabs, and longest-first is then not the best choice -- at 3 x 1536 one
+// layer-1 slab (3328 K-rows of bf16) shuts out the two layer-0 slabs (2 x 1856) that fit together in the 4608 a
+// workgroup holds.  Per workgroup, over the units the greedy pass gave it (at most PM_MAXENT): the subset that keeps the
+// most K rows on chip -- rows, not bytes: a phase waits for its slowest unit, and what a streamed unit loses is
+// proportional to the K it walks (an f32 output tile of the same K would otherwise push two bf16 layer slabs out); the
+// slabs are then laid out again from offset 0.
+void pm_repack_w16(std::vector<PmUnit>& table, int n_slots, int maxu, int nwg) {
+    bool any = false;
+    for (const PmUnit& u : table) any = any || u.kind == PM_GEMM16;
+    if (!any) return;
+    for (int w = 0; w < nwg; ++w) {
+        std::vector<PmUnit*> us;
+        for (int s = 0; s < n_slots; ++s)
+            for (int q = 0; q < maxu; ++q) {
+                PmUnit& u = table[((size_t)s * nwg + w) * maxu + q];
+                if (u.kind == PM_GEMM || u.kind == PM_GEMM16) us.push_back(&u);
+            }
+        auto need = [](const PmUnit& u) { return u.K * (u.kind == PM_GEMM16 ? 8 : 16); };
+        unsigned best = 0;
+        long long best_rows = -1;
+        for (unsigned set = 0; set < (1u << us.size()); ++set) {
+            long long floats = 0, rows = 0;
+            for (size_t i = 0; i < us.size(); ++i)
+                if (set >> i & 1) { floats += need(*us[i]); rows += us[i]->K; }
+            if (floats <= PM_LDS_W && rows > best_rows) { best = set; best_rows = rows; }
+        }
+        int off = 0;
+        for (size_t i = 0; i < us.size(); ++i) {
+            us[i]->w_lds = (best >> i & 1) ? off : -1;
+            if (best >> i & 1) off += need(*us[i]);
+        }
+    }
+}
+
 // Greedy placement of the units of one tick on the workgroups: per slot, critical and long units first; a unit goes
 // to the workgroup whose slot would end earliest (measured unit cost: ~3.5 us fixed + ~3.5 us per 1024 K-rows from
 // LDS, ~2x the K term when streamed; an attention row ~9 us), ties broken towards the least loaded workgroup.  A
-// unit's weight slab becomes LDS-resident when the workgroup still has room for it.
+// unit's weight slab becomes LDS-resident when the workgroup still has room for it.  A PM_GEMM16 unit is charged
+// krows * 8 floats of LDS instead of krows * 16 (bf16 slab) -- that is where residency is won; its cost keeps the f32
+// constants: the K term of a streamed bf16 slab (half the bytes) has not been measured.
+int pm_lds_need(const PmReq& q) { return q.krows * (q.u.kind == PM_GEMM16 ? 8 : 16); }
 bool pm_place(std::vector<PmReq>& reqs, int n_slots, int maxu, int nwg, std::vector<PmUnit>& table) {
     table.assign((size_t)n_slots * nwg * maxu, PmUnit());
     memset(table.data(), 0, table.size() * sizeof(PmUnit));
@@ -274,7 +312,7 @@ bool pm_place(std::vector<PmReq>& reqs, int n_slots, int maxu, int nwg, std::vec
     });
     for (int idx : order) {
         PmReq& q = reqs[idx];
-        const int need = q.krows * 16;
+        const int need = pm_lds_need(q);
         const bool is_att = q.u.kind == PM_ATT;
         int best = -1;
         double best_key = 0;
@@ -298,6 +336,7 @@ bool pm_place(std::vector<PmReq>& reqs, int n_slots, int maxu, int nwg, std::vec
         table[((size_t)q.slot * nwg + best) * maxu + c] = q.u;
         ++c;
     }
+    pm_repack_w16(table, n_slots, maxu, nwg);
     return true;
 }
 

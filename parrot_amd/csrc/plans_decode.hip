@@ -95,8 +95,17 @@ struct SamplePlan : PlanBase {
         if (d.layer_norm || d.gmm_K > 0 || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
             d.U > PM_ATT_MAXU || d.A > PM_ATT_MAXA || d.S < 1 || d.O > 64 || d.ldx < 64 || (d.ldx % 4))
             return false;
+        if (d.bf16) return bf16_eligible(d);
         for (int l = 0; l < d.L; ++l)
             if (!d.Wg_t[l] || (d.cell == 0 && !d.Wc_t[l])) return false;
+        return true;
+    }
+    // bf16 operands (ParrotSampleDesc::bf16): LSTM stacks only, 32-deep K steps, the bf16 copies in place of Wg_t.  A
+    // descriptor that asks for them and does not qualify gets NO machine plan -- parrot_sample_create then refuses it.
+    static bool bf16_eligible(const ParrotSampleDesc& d) {
+        if (d.cell != 1 || (d.H % 32) || (d.E % 32)) return false;
+        for (int l = 0; l < d.L; ++l)
+            if (!d.Wg_t16[l]) return false;
         return true;
     }
     // LSTM stacks (cell == 1): one phase per layer, readout and output composed (Wro_t / ro_const) -- build_persist_lstm
@@ -137,6 +146,7 @@ struct SamplePlan : PlanBase {
     // nwg_dry workgroups, no device memory is touched (parrot_sample_plan_pieces_dry: the CPU tests; the whole-K phases
     // have no dry mode).
     void plan_persist(bool dry, int nwg_dry) {
+        if (d.bf16 && !bf16_eligible(d)) return;  // (GRU programs have no bf16 units: no plan rather than an f32 one)
         if (d.cell == 1) {
             build_persist_lstm(dry, nwg_dry);
             return;
@@ -295,6 +305,9 @@ struct SamplePlan : PlanBase {
     // columns; each yields four state columns = a quarter of a fragment-major block (PmUnit::rtile), four neighbouring
     // units complete a block.  More tiles than workgroups (384 at H = 1536): two units per workgroup and phase (maxu 2).
     // The cell history [S + 1, B, H] is row-major and write-once like the state history (dataflow mode polls it).
+    // ParrotSampleDesc::bf16: the layer units become PM_GEMM16 (persist.h) on the bf16 copies Wg_t16 -- the same slabs,
+    // phases, epilogues and workspace; only the weight pointer, the unit kind and what pm_place charges for LDS differ.
+    // The output tiles stay f32 units of the same program.
     float* hist_c[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
     bool lstm_ok = false;  // (dry runs: planned and checked)
     static int slotL(int l) { return l == 0 ? 0 : l + 1; }
@@ -310,6 +323,7 @@ struct SamplePlan : PlanBase {
         const long long BH = (long long)B * H;
         const int n_slots = L + 2, sATT = 1, sOUT = L + 1, hc = H / 16, ec = E / 16;
         const int maxu = std::max(H / 4, B) <= nwg ? 1 : 2;
+        const bool w16 = d.bf16 != 0;  // (persist_eligible_shape: the widths and the copies qualify)
         if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT) return 0;
         PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, maxu);
         const long long rows = pb.rows;
@@ -343,7 +357,12 @@ struct SamplePlan : PlanBase {
             for (int ct = 0; ct < H / 4; ++ct) {
                 PmReq q = pb.gemm(slotL(l), XL[l], kx[l]);
                 PmUnit& u = q.u;
-                u.W = d.Wg_t[l] + (size_t)ct * nch * 256;
+                if (w16) {  // the tile's bf16 slab: kx / 32 blocks of 1 KB (parrot_tile_weights_bf16, mode 2)
+                    u.kind = PM_GEMM16;
+                    u.W = reinterpret_cast<const float*>(static_cast<const char*>(d.Wg_t16[l]) + (size_t)ct * (nch / 2) * 1024);
+                } else {
+                    u.W = d.Wg_t[l] + (size_t)ct * nch * 256;
+                }
                 u.bias = d.bg[l] ? d.bg[l] + 4 * ct : nullptr;
                 if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 4 * ct, 0, 4 * H));
                 u.epi = PM_EPI_LSTM; u.gstr = H; u.rtile = ct & 3;
@@ -409,6 +428,7 @@ struct SamplePlan : PlanBase {
         for (int l = 0; l < L; ++l)  // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states
             if (fb_rows(d, l)) pb.add_init(d.x, d.ldx, 64, XL[l], kx[l], (int)(kx[l] / 16) - 4);
         pm_prog.lstm = 1;
+        pm_prog.w16 = w16 ? 1 : 0;
         // no grid barriers with one unit per workgroup and phase (34.9 against 38.7 us per step at 2 x 1024, B 16); with two
         // (H = 1536: 384 tiles on 256 workgroups, all weights streamed) the barriers measured faster: 114.8 against 124.9
         pm_prog.dataflow = sw_pm_dataflow(maxu == 1 ? 1 : 0);
@@ -1102,6 +1122,10 @@ int parrot_sample_is_persistent(void* plan) {
     const SamplePlan* p = static_cast<SamplePlan*>(plan);
     return p->persist_ok ? (p->pieces_ok ? (p->fbc_on ? 3 : 2) : 1) : 0;
 }
+int parrot_sample_is_bf16(void* plan) {
+    const SamplePlan* p = static_cast<SamplePlan*>(plan);
+    return (p && p->persist_ok && p->pm_prog.w16) ? 1 : 0;
+}
 int parrot_sample_status(void* plan) { PH_ENTRY(); return plan ? static_cast<SamplePlan*>(plan)->persist_status() : PARROT_ERR_BADARG; }
 
 int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY();
@@ -1121,6 +1145,10 @@ int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY()
         }
     }
     p->build_persist();  // decode on the persistent phase machine when the configuration qualifies
+    if (desc->bf16 && !parrot_sample_is_bf16(p)) {  // no machine plan with bf16 operands: refused, never a silent f32 decode
+        delete p;
+        return PARROT_ERR_UNSUPPORTED;
+    }
     *plan = p;
     return 0;
 }

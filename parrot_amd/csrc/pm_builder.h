@@ -142,7 +142,7 @@ struct PmBuilder {
         if (!pm_place(reqs, n_slots, maxu, nwg, table)) return false;
         if (info16)
             for (const PmUnit& u : table)
-                if (u.kind == PM_GEMM && u.w_lds < 0) info16[14] += 1;
+                if ((u.kind == PM_GEMM || u.kind == PM_GEMM16) && u.w_lds < 0) info16[14] += 1;
         if (dry) return true;
         if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
         P.T = T; P.n_ticks = n_ticks; P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = n_slots; P.maxu = maxu;

@@ -789,10 +789,12 @@ __global__ __launch_bounds__(256) void sk_tile_weights_kernel(const float* __res
 // bf16 variant: block (column tile ct, 32-deep chunk c) holds, per lane (kk = lane >> 4, i = lane & 15), the 8
 // values k = 32c + 8kk .. +7 of column col(ct, i) (mode 0) / of W[16ct + i][k] (mode 1), rounded to nearest even;
 // 512 bf16 = 1 KB per block, blocks ordered [ct][c].
+// mode 2 (the decode machine's PM_GEMM16 units, persist.h): mode 0 with the K rows of a block in the order the lanes of
+// two f32 fragment-major activation blocks hold them: lane (kk, i) has k = 32c + 4kk .. +3 and 32c + 16 + 4kk .. +3.
 __global__ __launch_bounds__(256) void sk_tile_weights_bf16_kernel(const float* __restrict__ W, int rows, int cols, int ld,
                                                                    bf16x8* __restrict__ out, int mode, int lstm_H) {
-    const int nct = mode == 0 ? cols >> 4 : rows >> 4;
-    const int nch = mode == 0 ? rows >> 5 : cols >> 5;
+    const int nct = mode != 1 ? cols >> 4 : rows >> 4;
+    const int nch = mode != 1 ? rows >> 5 : cols >> 5;
     const size_t total = (size_t)nct * nch * 64;
     for (size_t it = (size_t)blockIdx.x * 256 + threadIdx.x; it < total; it += (size_t)gridDim.x * 256) {
         const int lane = (int)(it & 63);
@@ -800,11 +802,12 @@ __global__ __launch_bounds__(256) void sk_tile_weights_bf16_kernel(const float* 
         const int c = (int)(blk % nch), ct = (int)(blk / nch);
         const int i = lane & 15, kk = lane >> 4;
         f32x4 lo, hi;
-        if (mode == 0) {
+        if (mode != 1) {
             const int col = lstm_H > 0 ? (i >> 2) * lstm_H + ct * 4 + (i & 3) : ct * 16 + i;
-            const float* p = W + (size_t)(c * 32 + kk * 8) * ld + col;
+            const float* p = W + (size_t)(c * 32 + kk * (mode == 2 ? 4 : 8)) * ld + col;
+            const int hi0 = mode == 2 ? 16 : 4;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) { lo[u] = p[(size_t)u * ld]; hi[u] = p[(size_t)(u + 4) * ld]; }
+            for (int u = 0; u < 4; ++u) { lo[u] = p[(size_t)u * ld]; hi[u] = p[(size_t)(u + hi0) * ld]; }
         } else {
             const float* p = W + (size_t)(ct * 16 + i) * ld + c * 32 + kk * 8;
             lo = *reinterpret_cast<const f32x4*>(p);
@@ -817,9 +820,9 @@ __global__ __launch_bounds__(256) void sk_tile_weights_bf16_kernel(const float* 
 
 int sk_tile_weights_bf16_launch(const float* W, int rows, int cols, int ld, void* out, int mode, int lstm_H,
                                 hipStream_t stream) {
-    const int K = mode == 0 ? rows : cols, N = mode == 0 ? cols : rows;
+    const int K = mode != 1 ? rows : cols, N = mode != 1 ? cols : rows;
     if (!W || !out || K < 32 || N < 16 || (K & 31) || (N & 15) || (ld & 3) || ((uintptr_t)W & 15) ||
-        ((uintptr_t)out & 15) || (lstm_H > 0 && (mode != 0 || cols != 4 * lstm_H)))
+        ((uintptr_t)out & 15) || (lstm_H > 0 && (mode == 1 || cols != 4 * lstm_H)))
         return PH_ERR_BADARG;
     const size_t items = (size_t)rows * cols / 8;
     int blocks = (int)((items + 255) / 256);

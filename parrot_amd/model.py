@@ -114,7 +114,7 @@ class Parrot(Brick):
             raw_output=False,
             # --- extensions (not in the reference) ---
             num_layers=3, encoder_literal=True, use_graph=True, seed=1234,
-            cell_type='gru', lstm_forget_bias=3.0, compute_dtype='float32',
+            cell_type='gru', lstm_forget_bias=3.0, compute_dtype='float32', decode_dtype='float32',
             **kwargs):
         kwargs.setdefault('name', 'parrot')
         kwargs.setdefault('weights_init', IsotropicGaussian(0.01))  # train.py:30
@@ -130,6 +130,12 @@ class Parrot(Brick):
         # the decoder: scan steps, batched projections, readouts, deferred weight gradients), f32 accumulation, f32
         # master weights / states / gradients / optimiser.  Encoder, attention window and cost stay f32.
         self.compute_bf16 = compute_dtype != 'float32'
+        # decode_dtype='bf16': the recurrent-layer products of the decode loop (sample_model) round both operands to bf16
+        # and accumulate in f32 -- the arithmetic compute_dtype='bf16' trains in.  A switch of its own: the default decodes
+        # with f32 operands whatever compute_dtype says.  LSTM decoders on the persistent machine only; anything else is
+        # refused when the decode workspace is made (_sample_workspace), never decoded in f32 instead.
+        assert decode_dtype in ('float32', 'bf16', 'bfloat16')
+        self.decode_bf16 = decode_dtype != 'float32'
         self.input_dim, self.output_dim = input_dim, output_dim
         self.rnn_h_dim, self.readouts_dim = rnn_h_dim, readouts_dim
         self.layer_norm, self.which_cost, self.use_speaker = layer_norm, which_cost, use_speaker
@@ -1158,6 +1164,10 @@ class Parrot(Brick):
             return ws
         H, E, A, L, R, O = (self.rnn_h_dim, self.encoded_input_dim, self.attention_size, self.num_layers,
                             self.readouts_dim, self.output_dim)
+        if self.decode_bf16:
+            why = self._decode_bf16_refusal(N)
+            if why:
+                raise ValueError("decode_dtype='bf16' " + why)
         ldx = (O + 3) // 4 * 4
         f = dict(device=self._dev(), dtype=torch.float32)
         ws = dict(
@@ -1243,6 +1253,7 @@ class Parrot(Brick):
         # copies of the packed layer matrices with the fed-back-output rows appended (padded to 64 rows), of the
         # readout stack and of the output projection (63 -> 64 columns); sample_model_device refreshes them per call.
         # LSTM decoders: the one 4H-wide group, tiled in the gate-interleaved column order of the machine's LSTM units.
+        d.bf16 = 1 if self.decode_bf16 else 0  # (the library refuses what the bf16 machine does not take)
         if (not gmm and not self.layer_norm and N <= 64 and H % 16 == 0 and E % 16 == 0 and R % 16 == 0
                 and O <= 64 <= ldx and env_int('PARROT_SAMPLE_PERSIST', 1) != 0):
             pm = dict(cat={}, tiled={})
@@ -1251,6 +1262,10 @@ class Parrot(Brick):
                 for key, wd, suf, mat, rec in self._groups:
                     rows = H + E + l * H + fb
                     pm['cat'][(l, key)] = torch.zeros(rows, wd, **f)
+                    if self.decode_bf16:  # the bf16 copy in the machine's K order takes the place of the f32 one
+                        pm['tiled'][(l, key)] = torch.empty(rows, wd, device=self._dev(), dtype=torch.bfloat16)
+                        d.Wg_t16[l] = pm['tiled'][(l, key)].data_ptr()
+                        continue
                     pm['tiled'][(l, key)] = torch.empty(rows, wd, **f)
                     getattr(d, f'W{key}_t')[l] = pm['tiled'][(l, key)].data_ptr()
             pm['Wr_t'] = torch.empty(L * H + E, R, **f)
@@ -1284,10 +1299,37 @@ class Parrot(Brick):
                 d.persist_ws, d.persist_ws_floats = pm['ws'].data_ptr(), n
                 ws['pm'] = pm
         plan = C.c_void_p()
-        _lib.call('parrot_sample_create', C.byref(d), C.byref(plan))
+        try:
+            _lib.call('parrot_sample_create', C.byref(d), C.byref(plan))
+        except _lib.HipCallError as e:
+            if not self.decode_bf16:
+                raise
+            raise ValueError(f"decode_dtype='bf16': the library did not build the bf16 decode machine for S={S}, "
+                             f"N={N}, U={U} ({e}); there is no f32 decode behind this switch") from e
+        if self.decode_bf16 and _lib.load().parrot_sample_is_bf16(plan) != 1:
+            _lib.load().parrot_sample_destroy(plan)
+            raise ValueError("decode_dtype='bf16': the plan the library built does not run bf16 operands")
         ws['plan'], ws['desc'] = plan, d
         self._sample_ws[ws_key] = ws  # (`key` is the group key of the loops above)
         return ws
+
+    def _decode_bf16_refusal(self, N):
+        """Why this model / batch cannot decode with bf16 operands ('' when it can): what the bf16 machine does not take."""
+        H, E = self.rnn_h_dim, self.encoded_input_dim
+        if self.cell_type != 'lstm':
+            return "needs cell_type='lstm': GRU decoders have no bf16 decode path"
+        if self.which_cost != 'MSE':
+            return "needs which_cost='MSE': the GMM head does not decode on the persistent machine"
+        if self.layer_norm:
+            return "does not cover layer_norm=True (that decode runs as per-step launches)"
+        if H % 32 or E % 32:
+            return (f"needs rnn_h_dim and the encoder width to be multiples of 32 (v_mfma_f32_16x16x32_bf16 walks K in "
+                    f"steps of 32), got {H} and {E}")
+        if N > 64:
+            return f"covers at most 64 sequences per call, got {N}"
+        if env_int('PARROT_SAMPLE_PERSIST', 1) == 0:
+            return "runs on the persistent machine only, and PARROT_SAMPLE_PERSIST=0 turns that off"
+        return ''
 
     def sample_model_device(self, labels, labels_mask, speaker, num_samples, num_steps, unif=None, noise=None,
                             seed=None):
@@ -1355,6 +1397,10 @@ class Parrot(Brick):
         H, E, L, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.output_dim
 
         def tile(W, out, lstm_H=0):
+            if out.dtype == torch.bfloat16:  # decode_dtype='bf16': rounded to nearest even, the machine's K order (mode 2)
+                _lib.call('parrot_tile_weights_bf16', W.data_ptr(), W.shape[0], W.shape[1], W.shape[1], out.data_ptr(), 2,
+                          lstm_H, ops._stream())
+                return
             _lib.call('parrot_tile_weights', W.data_ptr(), W.shape[0], W.shape[1], W.shape[1], out.data_ptr(), 0, lstm_H,
                       ops._stream())
         lstm_H = H if self.cell_type == 'lstm' else 0

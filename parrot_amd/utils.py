@@ -4,7 +4,7 @@ which any non-empty string is truthy.  Plotting / animation helpers (utils.py:30
 and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
---device, --use_graph.
+--device, --use_graph; sample.py: --decode_dtype.
 """
 from __future__ import annotations
 
@@ -117,6 +117,10 @@ def sample_parse(argv=None):
     parser.add_argument('--random_speaker', type=bool, default=False)
     parser.add_argument('--plot_raw', type=bool, default=False)
     parser.add_argument('--device', type=str, default='cuda')
+    parser.add_argument('--decode_dtype', type=str, default='float32', choices=('float32', 'bf16'),
+                        help='bf16: the recurrent-layer products of the decode loop round both operands to bf16 '
+                             '(LSTM decoders on the persistent machine, DESIGN.md 3.6); float32: f32 operands, whatever '
+                             'the experiment was trained with')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:

@@ -57,8 +57,9 @@ def main(argv=None):
         encoder_type=saved_args.encoder_type, raw_output=raw_output, name='parrot',
         num_layers=getattr(saved_args, 'num_layers', 3), cell_type=getattr(saved_args, 'cell_type', 'gru'),
         encoder_literal=bool(getattr(saved_args, 'encoder_literal', 1)),
-        compute_dtype=getattr(saved_args, 'compute_dtype', 'float32'), device=device)
-    print("Operand precision of the decoder: %s" % getattr(saved_args, 'compute_dtype', 'float32'))
+        compute_dtype=getattr(saved_args, 'compute_dtype', 'float32'), decode_dtype=args.decode_dtype, device=device)
+    print("Operand precision of the decoder: trained with %s, decoding with %s"
+          % (getattr(saved_args, 'compute_dtype', 'float32'), args.decode_dtype))
     parrot.allocate()
     parrot.set_parameter_values(parameters)
     if raw_output:

@@ -1,6 +1,6 @@
 """Secondary measurements (BASELINE configs[2] decode latency, the same loop with LSTM decoders -- persistent machine
-against the per-step launches, alternating child processes --, configs[4] SampleRNN sample loop, mu-law quantiser
-bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
+with bf16 operands (decode_dtype='bf16') against the f32 machine against the per-step launches, alternating child
+processes --, configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
 
   bench_extra.py                         everything, one JSON line
   bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_lstm2_1024, decode_lstm3_1536, samplernn_cfg5, mulaw)
@@ -33,11 +33,12 @@ out = {}
 g = torch.Generator().manual_seed(0)
 
 
-def decode(kw, dump=None):
+def decode(kw, dump=None, decode_dtype='float32'):
     """Autoregressive decode, batch 16, 1000 frames, MSE head (greedy), hipGraph: three runs, the last one reported."""
     from parrot_amd import _lib
     from parrot_amd.model import Parrot
-    m = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, **kw).initialize()
+    m = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, decode_dtype=decode_dtype,
+               **kw).initialize()
     g = torch.Generator().manual_seed(0)
     N, U, S = 16, 100, 1000
     lab = torch.randint(0, 43, (N, U), generator=g)
@@ -50,37 +51,42 @@ def decode(kw, dump=None):
         np.save(dump, outs[0].cpu().numpy())
     ws = m._sample_ws[(S, N, U)]
     res = {"batch": N, "frames": S, "seconds": round(dt, 4), "us_per_step": round(1e6 * dt / S, 2),
-           "frames_per_s": round(N * S / dt, 1), "machine": int(_lib.load().parrot_sample_is_persistent(ws['plan']))}
+           "frames_per_s": round(N * S / dt, 1), "machine": int(_lib.load().parrot_sample_is_persistent(ws['plan'])),
+           "bf16": int(_lib.load().parrot_sample_is_bf16(ws['plan']))}
     m.close()
     return res
 
 
 if "--child" in sys.argv:  # one LSTM decode measurement under the caller's environment
-    print(json.dumps(decode(dict(LSTM_SHAPES[_arg("--child")], cell_type='lstm'))))
+    print(json.dumps(decode(dict(LSTM_SHAPES[_arg("--child")], cell_type='lstm'),
+                            decode_dtype=_arg("--decode-dtype", "float32"))))
     sys.exit(0)
 
 # ---- configs[2]: GRU decoder
 if "decode_cfg3" in only:
     out["decode_cfg3"] = decode(dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024), _arg("--dump-sample"))
 
-# ---- LSTM decoders: the persistent machine (PARROT_SAMPLE_PERSIST=1, the default) against the per-step launches
-# (PARROT_SAMPLE_PERSIST=0), each run in a child process of its own, on / off alternating so the spread is visible
+# ---- LSTM decoders: the persistent machine with bf16 operands and with f32 operands (PARROT_SAMPLE_PERSIST=1, the default)
+# against the per-step launches (PARROT_SAMPLE_PERSIST=0), each run in a child process of its own, alternating so the
+# spread is visible.  The bf16 machine's yardstick is the f32 machine of the SAME call.
 for name in LSTM_SHAPES:
     if name not in only:
         continue
-    runs = {"machine": [], "launches": []}
+    runs = {"machine_bf16": [], "machine": [], "launches": []}
     for rep in range(int(_arg("--reps", "3"))):
-        for key, val in (("machine", "1"), ("launches", "0")):
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name], capture_output=True, text=True,
-                               env=dict(os.environ, PARROT_SAMPLE_PERSIST=val), timeout=600)
+        for key, val, dt_ in (("machine_bf16", "1", "bf16"), ("machine", "1", "float32"), ("launches", "0", "float32")):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", name, "--decode-dtype", dt_],
+                               capture_output=True, text=True, env=dict(os.environ, PARROT_SAMPLE_PERSIST=val), timeout=600)
             if r.returncode != 0:  # (a fault in a child ends the measurement: nothing more is started on the device)
                 sys.stderr.write(r.stdout + r.stderr)
                 sys.exit(r.returncode)
             res = json.loads(r.stdout.strip().splitlines()[-1])
-            assert (res["machine"] != 0) == (key == "machine"), (key, res)
+            assert (res["machine"] != 0) == (key != "launches") and (res["bf16"] != 0) == (key == "machine_bf16"), (key, res)
             runs[key].append(res["us_per_step"])
-    out[name] = {"batch": 16, "frames": 1000, "us_per_step_machine": runs["machine"], "us_per_step_launches": runs["launches"],
-                 "machine_faster": max(runs["machine"]) < min(runs["launches"])}
+    out[name] = {"batch": 16, "frames": 1000, "us_per_step_machine_bf16": runs["machine_bf16"],
+                 "us_per_step_machine": runs["machine"], "us_per_step_launches": runs["launches"],
+                 "machine_faster": max(runs["machine"]) < min(runs["launches"]),
+                 "bf16_faster": max(runs["machine_bf16"]) < min(runs["machine"])}
 
 # ---- configs[4]: SampleRNN 3-tier GRU D=1024, batch 32, greedy, 16 kHz mu-law
 if "samplernn_cfg5" in only:
