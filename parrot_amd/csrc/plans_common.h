@@ -198,15 +198,21 @@ int launch_jobs_att(const SkJob* jobs, int n, const AttFwdArgs& att, hipStream_t
     return sk_launch_att(L, att, s);
 }
 
-// attention backward (or null) + the state backward of all chains in one launch; layer 0's chain is fused behind the
-// attention in the same workgroups (one job as far as ordering goes)
+// What every backward tick's first launch records: a new launch, the attention backward (or null) and the state backward
+// of all chains; layer 0's chain is fused behind the attention in the same workgroups (one job as far as ordering goes).
+template <class SA>
+void trace_bwd_head(const AttBwdArgs* g, const SA& sa, int l0_chain) {
+    g_tracer->begin();
+    if (g) g_tracer->att_bwd(*g, TRACE_JOB_ATT);
+    for (int q = 0; q < sa.nchain; ++q)
+        g_tracer->chain(sa.chain[q], sa.B, sa.H, (g && q == l0_chain) ? (int)TRACE_JOB_ATT : TRACE_JOB_CHAIN + q);
+}
+
+// attention backward (or null) + the state backward of all chains in one launch
 template <class SA>
 int traced_att_state_bwd_launch(const AttBwdArgs* g, const SA& sa, int l0_chain, hipStream_t s) {
     if (g_tracer) {
-        g_tracer->begin();
-        if (g) g_tracer->att_bwd(*g, TRACE_JOB_ATT);
-        for (int q = 0; q < sa.nchain; ++q)
-            g_tracer->chain(sa.chain[q], sa.B, sa.H, (g && q == l0_chain) ? (int)TRACE_JOB_ATT : TRACE_JOB_CHAIN + q);
+        trace_bwd_head(g, sa, l0_chain);
         return 0;
     }
     return att_state_bwd_launch(g, sa, l0_chain, s);
@@ -219,10 +225,7 @@ int traced_bwd_hetero_launch(const AttBwdArgs* g, const GruStateBwdArgs& sa, int
     SkLaunch L;
     PL_TRY(sk_make_launch(L, jobs, n));
     if (g_tracer) {
-        g_tracer->begin();
-        if (g) g_tracer->att_bwd(*g, TRACE_JOB_ATT);
-        for (int q = 0; q < sa.nchain; ++q)
-            g_tracer->chain(sa.chain[q], sa.B, sa.H, (g && q == l0_chain) ? (int)TRACE_JOB_ATT : TRACE_JOB_CHAIN + q);
+        trace_bwd_head(g, sa, l0_chain);
         for (int q = 0; q < n; ++q) g_tracer->sk_job(jobs[q], q);
         return 0;
     }
@@ -239,10 +242,7 @@ int traced_bwd_fused_launch(const AttBwdArgs* g, const LstmStateBwdArgs& sa, int
     PL_TRY(sk_make_launch(L, jobs, n));
     L.force_wide = 1;
     if (g_tracer) {
-        g_tracer->begin();
-        if (g) g_tracer->att_bwd(*g, TRACE_JOB_ATT);
-        for (int q = 0; q < sa.nchain; ++q)
-            g_tracer->chain(sa.chain[q], sa.B, sa.H, (g && q == l0_chain) ? (int)TRACE_JOB_ATT : TRACE_JOB_CHAIN + q);
+        trace_bwd_head(g, sa, l0_chain);
         for (int q = 0; q < n; ++q) g_tracer->sk_job(jobs[q], q);
         return 0;
     }

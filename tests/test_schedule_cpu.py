@@ -39,7 +39,13 @@ class _Arena:
         return lo
 
 
-def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, E=16, A=4, U=7, bf16=0, hetero=False):
+def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, E=16, A=4, U=7, bf16=0, hetero=False,
+               layer_norm=0, ln_buffers=True, accum=None, expect_rc=0):
+    """accum: None = the accumulators the descriptor's own backward tick wants (second for bf16 LSTM stacks, second and
+    third with `hetero`); 0 / 1 / 2 = none / second / second and third, whatever the descriptor.  expect_rc != 0: the
+    create call must refuse with that code (returns no plan)."""
+    if accum is None:
+        accum = 2 if hetero else (1 if (bf16 and cell == 1) else 0)
     if sched is None:
         monkeypatch.delenv("PARROT_SCHEDULE", raising=False)
     else:
@@ -48,7 +54,7 @@ def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, 
     ar = _Arena()
     d = L.DecoderDesc()
     d.T, d.B, d.H, d.E, d.A, d.U, d.L = T, B, H, E, A, U, nl
-    d.cell, d.use_graph, d.seq_init, d.bf16 = cell, 0, seq_init, bf16
+    d.cell, d.use_graph, d.seq_init, d.bf16, d.layer_norm = cell, 0, seq_init, bf16, layer_norm
     d.eps, d.alignment, d.sharpening, d.timing = 1e-5, 1.0, 1.0, 1.0
     f = 4
     gw = 4 * H if cell == 1 else 2 * H
@@ -65,11 +71,11 @@ def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, 
             d.dhup[l] = ar.take(f"dhup{l}", (T + 1) * B * H * f)
         if bf16 and cell == 1:  # bf16 copies of the pre-activation gradients, written by the fused backward tick (round 5)
             d.dG16[l] = ar.take(f"dG16_{l}", T * B * gw * 2)
-        if (bf16 and cell == 1) or hetero:  # second (and third) accumulators: the backward products run as K parts
+        if accum >= 1:  # second (and third) accumulators: the backward products run as K parts
             d.dh_b[l] = ar.take(f"dh_b{l}", (T + 1) * B * H * f)
             if l < nl - 1:
                 d.dhup_b[l] = ar.take(f"dhup_b{l}", (T + 1) * B * H * f)
-                if hetero:
+                if accum >= 2:
                     d.dhup_c[l] = ar.take(f"dhup_c{l}", (T + 1) * B * H * f)
         if l >= 1 or (seq_init >> l) & 1:
             d.seq_g[l] = ar.take(f"seq_g{l}", T * B * gw * f)
@@ -87,6 +93,12 @@ def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, 
             d.cst[l] = ar.take(f"cst{l}", (T + 1) * B * H * f)
             d.gate4[l] = ar.take(f"gate4{l}", T * B * 4 * H * f)
             d.dcell[l] = ar.take(f"dcell{l}", B * H * f)
+        for j in range(l if (layer_norm and ln_buffers) else 0):  # layer_norm: the normalised projection of h_j into layer l
+            pj = l * len(d.Wg) + j
+            for g, wd in (("g", gw),) + ((("c", H),) if cell == 0 else ()):
+                getattr(d, f"ln_y{g}")[pj] = ar.take(f"ln_y{g}{l}{j}", T * B * wd * f)
+                getattr(d, f"ln_s{g}")[pj] = ar.take(f"ln_s{g}{l}{j}", T * B * f)
+                getattr(d, f"ln_b{g}")[pj] = ar.take(f"ln_b{g}{l}{j}", wd * f)
     d.WattT = ar.take("WattT", 3 * A * H * f)
     d.batt = ar.take("batt", 3 * A * f)
     d.ctx = ar.take("ctx", B * U * E * f)
@@ -97,10 +109,10 @@ def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, 
     d.phi = ar.take("phi", T * B * U * f)
     d.dw = ar.take("dw", (T + 1) * B * E * f)
     d.dw0 = ar.take("dw0", (T + 1) * B * E * f)
-    if (bf16 and cell == 1) or hetero:
+    if accum >= 1:
         d.dw_b = ar.take("dw_b", (T + 1) * B * E * f)
         d.dw0_b = ar.take("dw0_b", (T + 1) * B * E * f)
-        if hetero:
+        if accum >= 2:
             d.dw_c = ar.take("dw_c", (T + 1) * B * E * f)
             d.dw0_c = ar.take("dw0_c", (T + 1) * B * E * f)
     d.dkappa = ar.take("dkappa", B * A * f)
@@ -108,8 +120,8 @@ def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, 
     d.att_sup = ar.take("att_sup", T * B * 2 * 4)
     plan = C.c_void_p()
     rc = lib.parrot_decoder_create(C.byref(d), C.byref(plan))
-    assert rc == 0, rc
-    return plan, ar, d
+    assert rc == expect_rc, rc
+    return (plan if rc == 0 else None), ar, d
 
 
 def _trace(lib, plan, which):
@@ -372,6 +384,33 @@ def test_k_balanced_backward_tick_keeps_the_scan_orderings(monkeypatch, sched, n
         buf = (C.c_longlong * (6 * n))()
         lib.parrot_decoder_trace_jobs(plan, 1, buf, n)
         assert max(buf[6 * i + 4] for i in range(n) if buf[6 * i + 5] >= 0) == 2 * H
+    finally:
+        lib.parrot_decoder_destroy(plan)
+
+
+@pytest.mark.parametrize("case,kw,want", [
+    # (PARROT_SCHEDULE, cell, layers), further descriptor fields -> schedule, or the refusal of the create call
+    ("layer_norm stack runs on the hoisted projections", dict(sched=None, cell=0, nl=2, layer_norm=1), 3),
+    ("layer_norm LSTM stack likewise", dict(sched=None, cell=1, nl=2, layer_norm=1), 3),
+    ("layer_norm without its buffers", dict(sched=None, cell=0, nl=2, layer_norm=1, ln_buffers=False), "refused"),
+    ("one launch per tick is for LSTM layers", dict(sched=7, cell=0, nl=2), 5),
+    ("the in-launch hand-off takes 64 rows", dict(sched=7, cell=1, nl=2, B=64), 7),
+    ("... and no more", dict(sched=7, cell=1, nl=2, B=80), 0),
+    ("bf16 operands come in 32-deep K chunks", dict(sched=None, cell=1, nl=2, bf16=1, H=48, E=32), "refused"),
+])
+def test_plan_resolution(monkeypatch, case, kw, want):
+    """Which schedule a descriptor resolves to (DecoderPlan::resolve), for the rows the tracing tests above do not visit."""
+    L, lib = _lib()
+    kw = dict(kw)
+    args = (kw.pop("sched"), kw.pop("cell"), kw.pop("nl"), 0, monkeypatch)
+    if want == "refused":
+        plan, _, _ = _make_plan(L, lib, *args, expect_rc=10001, **kw)  # PARROT_ERR_BADARG
+        assert plan is None
+        return
+    plan, _, _ = _make_plan(L, lib, *args, **kw)
+    try:
+        assert lib.parrot_decoder_schedule(plan) == want, case
+        assert lib.parrot_decoder_backward_tick(plan) == 0 and lib.parrot_decoder_is_persistent(plan) == 0
     finally:
         lib.parrot_decoder_destroy(plan)
 
