@@ -461,6 +461,20 @@ typedef struct ParrotSampleDesc {
      * the bf16 machine does not take (parrot_sample_persist_floats returns 0 for them). */
     int bf16, reserved8;
     const void* Wg_t16[PARROT_MAX_LAYERS];
+    /* eou_extra > 0: stop at the end of the utterance, inside the persistent machine.  Row b's predicate at step t (0-based)
+     * is  phi[t, b, eou_pos[b]] > phi[t, b, j] for all j < eou_ncmp[b]  on the f32 values stored to phi (strict; a NaN
+     * never holds; eou_ncmp[b] = 0 holds at once).  eou_first[b] (output, [B] ints) = the first step at which it held, or
+     * -1; the row's length is min(S, eou_first[b] + eou_extra), S for a row that never fires.  Once every row has fired the
+     * run ends after frame T_stop = the longest row: every output row below T_stop is bit-identical to a run without the
+     * stop, later rows are unspecified (parrot_sample_steps_run reports T_stop).  eou_pos, eou_ncmp, eou_first: device
+     * arrays of B ints, 0 <= eou_pos[b] < U, 0 <= eou_ncmp[b] <= U (clamped); eou_extra >= 8.  The stop exists on the
+     * persistent machine only: parrot_sample_create returns PARROT_ERR_UNSUPPORTED for a descriptor that asks for it and
+     * gets no machine plan (GMM head, layer_norm, B > 64, PARROT_SAMPLE_PERSIST=0, no workspace, eou_extra < 8, an array
+     * missing); the per-step launches are never substituted.  0: every run decodes all S steps. */
+    const int* eou_pos;
+    const int* eou_ncmp;
+    int* eou_first;
+    int eou_extra, reserved9;
 } ParrotSampleDesc;
 
 long long parrot_sample_persist_floats(const ParrotSampleDesc* desc);
@@ -478,6 +492,11 @@ int parrot_sample_is_bf16(void* plan);
 int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* info16);
 /* Like parrot_decoder_status, for a decode plan. */
 int parrot_sample_status(void* plan);
+/* 1: the plan stops at the end of the utterance (ParrotSampleDesc::eou_extra > 0 on the machine); 0: it runs all S steps */
+int parrot_sample_stops_early(void* plan);
+/* Frames the last parrot_sample_run completed (synchronises like parrot_sample_status): T_stop <= S for a plan that stops
+ * early, S for every other plan. */
+int parrot_sample_steps_run(void* plan, int* steps);
 
 int parrot_sample_create(const ParrotSampleDesc* desc, void** plan);
 int parrot_sample_run(void* plan, void* stream);

@@ -116,6 +116,8 @@ class SampleDesc(C.Structure):
         ("Watt_t", C.c_void_p),
         ("bf16", C.c_int), ("reserved8", C.c_int),
         ("Wg_t16", C.c_void_p * MAX_LAYERS),
+        ("eou_pos", C.c_void_p), ("eou_ncmp", C.c_void_p), ("eou_first", C.c_void_p),
+        ("eou_extra", C.c_int), ("reserved9", C.c_int),
     ]
 
 
@@ -185,6 +187,8 @@ SIGNATURES = {
     "parrot_sample_is_bf16": (_i, [_vp]),
     "parrot_sample_plan_pieces_dry": (_i, [C.POINTER(SampleDesc), _i, C.POINTER(C.c_int)]),
     "parrot_sample_status": (_i, [_vp]),
+    "parrot_sample_stops_early": (_i, [_vp]),
+    "parrot_sample_steps_run": (_i, [_vp, C.POINTER(C.c_int)]),
     "parrot_decoder_status": (_i, [_vp]),
     "parrot_sample_run": (_i, [_vp, _vp]),
     "parrot_sample_destroy": (_i, [_vp]),

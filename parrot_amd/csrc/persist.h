@@ -101,6 +101,13 @@ struct PmAtt {
     long long pp_st;              // floats per step
     int B, H, A, U, E, att_type, dense, pad;
     float eps, alignment, sharpening, timing;
+    // Optional end-of-utterance stop (decode, ParrotSampleDesc::eou_*; all null / 0: the launch runs every tick).  Row b's
+    // predicate at step t is phi[t, b, eou_pos[b]] > phi[t, b, j] for all j < eou_ncmp[b] (strict; NaN never holds; no j:
+    // holds), evaluated on the row's phi in LDS.  eou_first[b] = the first step it held, or -1 (reset by pm_launch).
+    // Once every row has fired, the launch ends after frame max_b min(T, eou_first[b] + eou_extra) -- see pm_kernel.
+    const int* eou_pos; const int* eou_ncmp;
+    int* eou_first;
+    int eou_extra, pad4;
 };
 
 struct PmInit {  // prologue: row-major [M,K] (ld) -> chunks [chunk, chunk + K/16) of a fragment-major slab
@@ -136,9 +143,22 @@ struct PmProgram {
 enum { PM_SYNC_WORDS = 1024, PM_DBG_WORDS = 256 * 24 * 2 };  // dbg: per workgroup 24 x u64: work[9], wait[9] per slot, 4 gemm stages (100 MHz ticks)
 // word offsets inside `sync` (128 B apart)
 enum { PM_S_XCNT = 0, PM_S_XGEN = 256, PM_S_TOP = 512, PM_S_CENSUS = 544, PM_S_TOTAL = 800, PM_S_ABORT = 832,
+       // end-of-utterance stop (PmAtt::eou_*): the tick at which every workgroup leaves (0: none yet; written once), the
+       // largest row length so far, the rows that have fired, the ticks the owner of attention row 0 executed
+       PM_S_STOP = 864, PM_S_EOUMAX = 896, PM_S_EOUCNT = 928, PM_S_TICKS = 960,
        PM_S_STICKY = 992 };  // words >= PM_S_STICKY survive pm_launch's clearing: [PM_S_STICKY] != 0 = some launch gave up
+// The smallest PmAtt::eou_extra a program may ask for.  The stop tick is published while some attention row works on step
+// t_p, and is >= t_p + eou_extra + D (D = n_ticks - T, the largest lag).  A unit of step t' reads values that depend on
+// every attention row of step t' - 3 or later (its newest operands are products of step t' - 1, theirs hold w[t' - 1] =
+// the attention of step t' - 2; one more for slack), so a workgroup that owns units has started no tick beyond
+// t_p + D + 3 when the word appears, its look at the word for the tick after that may already be under way (the look is
+// asked for one tick ahead), and the first tick certain to see the word is t_p + D + 5 <= the stop tick for
+// eou_extra >= 5.  8 leaves three ticks of margin.  With grid barriers every workgroup sees the word two ticks later.
+enum { PM_EOU_MIN_EXTRA = 8 };
 #define PM_EMPTY 0x7FC0DEADu
 
 int pm_launch(const PmProgram& prog, hipStream_t stream);
+// synchronises; frames the last launch completed: T, or fewer when the end-of-utterance stop ended it (PmAtt::eou_extra > 0)
+int pm_steps_run(const PmProgram& prog, int* steps);
 int pm_status(const PmProgram& prog);  // synchronises; 0, or non-zero when a launch on this program's workspace gave up
 int pm_max_workgroups();  // number of workgroups the machine runs with on this device (one per CU, <= 256)

@@ -524,9 +524,16 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
 // GMM-window attention of batch row b at step t (model.py:664-690) by the whole workgroup (512 threads):
 // projection h1 . Watt, window parameters, phi over the context, w = sum_u phi[u] ctx[b,u,:] over the support of the
 // window.  Same formulas as att_fwd_kernel (attention.hip); the summation order over u differs (two row groups).
-template <bool DF>
-__device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* sm, float* fm_base, unsigned* sync) {
+template <bool DF, bool EOU>
+__device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* sm, float* fm_base, unsigned* sync, int T,
+                                           int drain) {
     const int A = g.A, U = g.U, E = g.E, H = g.H;
+    // end-of-utterance stop: the row's two indices (wave-uniform), asked for now and used behind the w stores
+    int eou_pos = 0, eou_ncmp = 0;
+    if (EOU) {
+        eou_pos = g.eou_pos[b];
+        eou_ncmp = g.eou_ncmp[b];
+    }
     float* s_p = sm;                        // [3A]
     float* s_a = s_p + 3 * PM_ATT_MAXA;     // [A]
     float* s_b = s_a + PM_ATT_MAXA;
@@ -763,12 +770,40 @@ __device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* 
         }
         __syncthreads();
     }
+    // 5) end of the utterance (PmAtt::eou_*): decided on s_phi = the values stored to phi, behind the row's last store, so
+    // nothing of the step waits for it.  Wave 0 reads s_phi IN FRONT of the function's last barrier: behind it the other
+    // waves are free to start the workgroup's next unit, whose split-K partial tiles share this LDS (lds_red) -- without
+    // grid barriers nothing else would keep them off the row.  Only the atomics stay behind the barrier.
+    bool fires = false;
+    if (EOU && wave == 0) {
+        const int pos = min(max(eou_pos, 0), U - 1), ncmp = min(max(eou_ncmp, 0), U);
+        const float pv = s_phi[pos];
+        bool holds = true;
+        for (int j = lane; j < ncmp; j += 64) holds = holds && (pv > s_phi[j]);  // (a NaN on either side: false)
+        fires = __ballot(!holds) == 0ull;
+    }
     __syncthreads();
+    // The first time the predicate holds the row records the step and its length min(T, t + extra); the row that fires
+    // last publishes the tick at which every workgroup leaves = the tick count a launch of T_stop = max length steps
+    // would have had (written once: the count reaches B once).
+    if (EOU && wave == 0) {
+        if (fires && lane == 0) {
+            int expect = -1;
+            if (__hip_atomic_compare_exchange_strong(g.eou_first + b, &expect, t, PM_RLX, PM_RLX, PM_AGENT)) {
+                const unsigned len = (unsigned)min(T, t + g.eou_extra);
+                __hip_atomic_fetch_max(sync + PM_S_EOUMAX, len, PM_RLX, PM_AGENT);
+                const unsigned fired = __hip_atomic_fetch_add(sync + PM_S_EOUCNT, 1u, __ATOMIC_ACQ_REL, PM_AGENT);
+                if (fired + 1u == (unsigned)g.B)
+                    __hip_atomic_store(sync + PM_S_STOP, pm_ld(sync + PM_S_EOUMAX) + (unsigned)drain, __ATOMIC_RELEASE, PM_AGENT);
+            }
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ kernel
 // W16: the program has PM_GEMM16 units (PmProgram::w16); false: the kernel is what it was before they existed
-template <int MB, bool DF, bool LS, bool W16>
+// EOU: the program asks for the end-of-utterance stop (PmAtt::eou_extra > 0); false: the kernel is what it was before that
+template <int MB, bool DF, bool LS, bool W16, bool EOU>
 __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lds_w = lds;
@@ -816,6 +851,11 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
             }
     }
     __syncthreads();
+    // (stop) the workgroup that owns attention row 0 records the ticks it ran: it owns a unit in every tick, so it cannot
+    // run ahead of the stop the way a workgroup without units may
+    bool rec_ticks = false;
+    if (EOU)
+        for (int i = 0; i < n_slots * maxu; ++i) rec_ticks = rec_ticks || (lds_units[i].kind == PM_ATT && lds_units[i].row == 0);
     // resident weight slabs -> LDS (once per window)
     for (int s = 0; s < n_slots; ++s)
         for (int q = 0; q < maxu; ++q) {
@@ -858,7 +898,21 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
     unsigned long long stage[4] = {0, 0, 0, 0};
     if (tid < 2 * PM_MAXSLOTS) t_work[tid] = 0;
     __syncthreads();
-    for (int tick = 0; tick < P.n_ticks; ++tick) {
+    // End-of-utterance stop (EOU; else nothing of it is compiled in): the stop word is looked at only
+    // here, at the top of a tick.  Lane 0 asks for it one tick ahead of its use (an L1-bypassing load that returns beside
+    // the tick's other loads) and hands it to the workgroup through one of two LDS words; every workgroup leaves at the
+    // tick the word names, so the launch executes a prefix of its ticks (PM_EOU_MIN_EXTRA: why nobody overruns it).
+    unsigned* stop_sh = reinterpret_cast<unsigned*>(lds_red + PM_LDS_RED + PM_LDS_UNITS + 17);  // [2]
+    unsigned stop_next = 0;
+    int tick = 0;
+    for (; tick < P.n_ticks; ++tick) {
+        if (EOU) {
+            if (tid == 0) stop_sh[tick & 1] = stop_next;
+            __syncthreads();
+            const unsigned stop = stop_sh[tick & 1];
+            if (stop != 0u && (unsigned)tick >= stop) break;
+            if (tid == 0) stop_next = pm_ld(sync + PM_S_STOP);
+        }
         for (int s = 0; s < n_slots; ++s) {
             const unsigned long long ta = pm_clock();
             for (int q = 0; q < maxu; ++q) {
@@ -869,7 +923,7 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
                 if (t < 0 || t >= P.T) continue;
                 if (kind == PM_GEMM) pm_gemm<MB, DF, LS, false>(u, t, lds_w, lds_red, fmr, stage, sync);
                 else if (W16 && kind == PM_GEMM16) pm_gemm<MB, DF, LS, true>(u, t, lds_w, lds_red, fmr, stage, sync);
-                else pm_att_row<DF>(P.att, u.row, t, lds_att, P.fm_base, sync);
+                else pm_att_row<DF, EOU>(P.att, u.row, t, lds_att, P.fm_base, sync, P.T, P.n_ticks - P.T);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const unsigned long long tb = pm_clock();
@@ -893,6 +947,7 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
         unsigned long long* dbg = reinterpret_cast<unsigned long long*>(sync + PM_SYNC_WORDS) + (size_t)wg * 24;
         for (int s = 0; s < PM_MAXSLOTS; ++s) { dbg[s] = t_work[s]; dbg[PM_MAXSLOTS + s] = t_wait[s]; }
         for (int q = 0; q < 4; ++q) dbg[18 + q] = stage[q];
+        if (EOU && rec_ticks) pm_st(sync + PM_S_TICKS, (unsigned)tick);
     }
 }
 
@@ -915,6 +970,9 @@ __global__ __launch_bounds__(256) void pm_fill_kernel(unsigned* p, long long n, 
 __global__ __launch_bounds__(256) void pm_clear_kernel(unsigned* a, int na, unsigned* b, int nb) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < na; i += gridDim.x * 256) a[i] = 0u;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < nb; i += gridDim.x * 256) b[i] = 0u;
+}
+__global__ __launch_bounds__(64) void pm_eou_reset_kernel(int* first, int n) {
+    if ((int)threadIdx.x < n) first[threadIdx.x] = -1;
 }
 }  // namespace
 
@@ -949,11 +1007,27 @@ int pm_status(const PmProgram& P) {
     return w ? PH_ERR_UNSUPPORTED + 100 : 0;
 }
 
+int pm_steps_run(const PmProgram& P, int* steps) {
+    if (!steps) return PH_ERR_BADARG;
+    PH_CHECK(hipDeviceSynchronize());
+    *steps = P.T;
+    if (P.att.eou_extra > 0) {
+        unsigned ticks = 0;
+        PH_CHECK(hipMemcpy(&ticks, P.sync + PM_S_TICKS, sizeof(ticks), hipMemcpyDeviceToHost));
+        const int done = (int)ticks - (P.n_ticks - P.T);  // (a launch that gave up recorded nothing)
+        *steps = done < 0 ? 0 : (done > P.T ? P.T : done);
+    }
+    return 0;
+}
+
 int pm_launch(const PmProgram& P, hipStream_t stream) {
     if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
         P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL || (P.w16 && !P.lstm))
         return PH_ERR_BADARG;
     if (P.att.U > PM_ATT_MAXU || P.att.A > PM_ATT_MAXA) return PH_ERR_UNSUPPORTED;
+    if (P.att.eou_extra != 0 && (P.att.eou_extra < PM_EOU_MIN_EXTRA || !P.att.eou_pos || !P.att.eou_ncmp || !P.att.eou_first ||
+                                 P.att.B < 1 || P.att.B > 64))
+        return PH_ERR_BADARG;
     // barrier / census / abort words and the timers are cleared; the sticky words at the end of the sync area are not
     // (cleared by a kernel of our own, not by hipMemsetAsync: as graph memset nodes replayed on the default stream the
     // two memsets were seen to leave a non-zero pattern in the words when earlier work was still in flight -- every
@@ -961,6 +1035,10 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     hipLaunchKernelGGL(pm_clear_kernel, dim3(8), dim3(256), 0, stream, P.sync, (int)PM_S_STICKY, P.sync + PM_SYNC_WORDS,
                        (int)PM_DBG_WORDS);
     PH_CHECK(hipGetLastError());
+    if (P.att.eou_extra > 0) {  // (the stop word, the counts and the tick record are words of the area just cleared)
+        hipLaunchKernelGGL(pm_eou_reset_kernel, dim3(1), dim3(64), 0, stream, P.att.eou_first, P.att.B);
+        PH_CHECK(hipGetLastError());
+    }
     if (P.dataflow)
         for (int q = 0; q < P.nfill; ++q) {
             const long long n = P.fill[q].bytes / 4;
@@ -973,23 +1051,33 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     static bool attr_done = false;
     if (!attr_done) {
         const int l = (int)lds;
-#define PM_ATTR(MB_, DF_, LS_, W16_) \
-    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
-        PM_ATTR(1, false, false, false); PM_ATTR(2, false, false, false); PM_ATTR(4, false, false, false);
-        PM_ATTR(1, true, false, false); PM_ATTR(2, true, false, false); PM_ATTR(4, true, false, false);
-        PM_ATTR(1, false, true, false); PM_ATTR(2, false, true, false); PM_ATTR(4, false, true, false);
-        PM_ATTR(1, true, true, false); PM_ATTR(2, true, true, false); PM_ATTR(4, true, true, false);
-        PM_ATTR(1, false, true, true); PM_ATTR(2, false, true, true); PM_ATTR(4, false, true, true);
-        PM_ATTR(1, true, true, true); PM_ATTR(2, true, true, true); PM_ATTR(4, true, true, true);
+#define PM_ATTR1(MB_, DF_, LS_, W16_, EOU_) \
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_, EOU_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+#define PM_ATTR(EOU_) \
+    PM_ATTR1(1, false, false, false, EOU_); PM_ATTR1(2, false, false, false, EOU_); PM_ATTR1(4, false, false, false, EOU_); \
+    PM_ATTR1(1, true, false, false, EOU_); PM_ATTR1(2, true, false, false, EOU_); PM_ATTR1(4, true, false, false, EOU_); \
+    PM_ATTR1(1, false, true, false, EOU_); PM_ATTR1(2, false, true, false, EOU_); PM_ATTR1(4, false, true, false, EOU_); \
+    PM_ATTR1(1, true, true, false, EOU_); PM_ATTR1(2, true, true, false, EOU_); PM_ATTR1(4, true, true, false, EOU_); \
+    PM_ATTR1(1, false, true, true, EOU_); PM_ATTR1(2, false, true, true, EOU_); PM_ATTR1(4, false, true, true, EOU_); \
+    PM_ATTR1(1, true, true, true, EOU_); PM_ATTR1(2, true, true, true, EOU_); PM_ATTR1(4, true, true, true, EOU_)
+        // (the kernels without the stop first: they keep the order, and so the layout in the code object, they had)
+        PM_ATTR(false);
+        PM_ATTR(true);
 #undef PM_ATTR
+#undef PM_ATTR1
         attr_done = true;
     }
     const dim3 grid(P.nwg), block(PM_THREADS);
+#define PM_GO1(MB_, DF_, EOU_) \
+    do { \
+        if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_>), grid, block, lds, stream, P); \
+        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_>), grid, block, lds, stream, P); \
+        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_>), grid, block, lds, stream, P); \
+    } while (0)
 #define PM_GO(MB_, DF_) \
     do { \
-        if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true>), grid, block, lds, stream, P); \
-        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false>), grid, block, lds, stream, P); \
-        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false>), grid, block, lds, stream, P); \
+        if (P.att.eou_extra > 0) PM_GO1(MB_, DF_, true); \
+        else PM_GO1(MB_, DF_, false); \
     } while (0)
     switch (P.MB * 2 + (P.dataflow ? 1 : 0)) {
         case 2: PM_GO(1, false); break;
@@ -1001,5 +1089,6 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
         default: return PH_ERR_BADARG;
     }
 #undef PM_GO
+#undef PM_GO1
     return (int)hipGetLastError();
 }

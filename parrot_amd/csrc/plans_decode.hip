@@ -154,11 +154,23 @@ struct SamplePlan : PlanBase {
         if (pieces_wanted(d)) build_persist_pieces(dry, nwg_dry);  // the step cut along K by the age of its operands
         if (!persist_ok && !dry) build_persist_whole();            // else the 2L + 3 whole-K phases
     }
+    // End-of-utterance stop (ParrotSampleDesc::eou_extra > 0): a property of the launch, not of a program -- every program
+    // above gets it the same way, through PmAtt (persist.h).  A descriptor that asks for it and does not qualify gets NO
+    // machine plan, and parrot_sample_create then refuses it: the per-step launches cannot stop.
+    static bool stop_eligible(const ParrotSampleDesc& d) {
+        return d.eou_extra >= PM_EOU_MIN_EXTRA && d.eou_pos && d.eou_ncmp && d.eou_first;
+    }
+    bool stops_early() const { return persist_ok && pm_prog.att.eou_extra > 0; }
     int build_persist() {
         persist_ok = false;
         if (env_int("PARROT_SAMPLE_PERSIST", 1) == 0) return 0;
         if (!persist_eligible(d) || !d.persist_ws) return 0;
+        if (d.eou_extra > 0 && !stop_eligible(d)) return 0;
         plan_persist(false, 0);
+        if (persist_ok && d.eou_extra > 0) {
+            PmAtt& a = pm_prog.att;
+            a.eou_pos = d.eou_pos; a.eou_ncmp = d.eou_ncmp; a.eou_first = d.eou_first; a.eou_extra = d.eou_extra;
+        }
         return 0;
     }
 
@@ -287,6 +299,13 @@ struct SamplePlan : PlanBase {
         return 0;
     }
     int persist_status() const { return persist_ok ? pm_status(pm_prog) : 0; }
+    int steps_run(int* steps) const {
+        if (persist_ok) return pm_steps_run(pm_prog, steps);
+        if (!steps) return PH_ERR_BADARG;
+        PH_CHECK(hipDeviceSynchronize());
+        *steps = d.S;
+        return 0;
+    }
 
     int run_persist(hipStream_t st) {
         const size_t BH = (size_t)d.B * d.H;
@@ -1127,9 +1146,16 @@ int parrot_sample_is_bf16(void* plan) {
     return (p && p->persist_ok && p->pm_prog.w16) ? 1 : 0;
 }
 int parrot_sample_status(void* plan) { PH_ENTRY(); return plan ? static_cast<SamplePlan*>(plan)->persist_status() : PARROT_ERR_BADARG; }
+int parrot_sample_stops_early(void* plan) {
+    const SamplePlan* p = static_cast<SamplePlan*>(plan);
+    return (p && p->stops_early()) ? 1 : 0;
+}
+int parrot_sample_steps_run(void* plan, int* steps) { PH_ENTRY();
+    return plan ? static_cast<SamplePlan*>(plan)->steps_run(steps) : PARROT_ERR_BADARG;
+}
 
 int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY();
-    if (!desc || !plan || desc->S < 1 || desc->B < 1 || bad_dims(desc->L) || desc->ldx < desc->O)
+    if (!desc || !plan || desc->S < 1 || desc->B < 1 || bad_dims(desc->L) || desc->ldx < desc->O || desc->eou_extra < 0)
         return PARROT_ERR_BADARG;
     SamplePlan* p = new (std::nothrow) SamplePlan();
     if (!p) return PARROT_ERR_BADARG;
@@ -1146,6 +1172,10 @@ int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY()
     }
     p->build_persist();  // decode on the persistent phase machine when the configuration qualifies
     if (desc->bf16 && !parrot_sample_is_bf16(p)) {  // no machine plan with bf16 operands: refused, never a silent f32 decode
+        delete p;
+        return PARROT_ERR_UNSUPPORTED;
+    }
+    if (desc->eou_extra > 0 && !p->stops_early()) {  // the stop exists inside the machine only: refused, never all S steps
         delete p;
         return PARROT_ERR_UNSUPPORTED;
     }

@@ -1157,8 +1157,9 @@ class Parrot(Brick):
         self._weight_grad_rows(ws, save, T, B, 0, T)
 
     # ------------------------------------------------------------------ sampling
-    def _sample_workspace(self, S, N, U):
-        ws_key = (S, N, U)
+    def _sample_workspace(self, S, N, U, stop_extra=0):
+        # (a plan that stops at the end of the utterance is another plan: a workspace key of its own)
+        ws_key = ('stop', S, N, U, stop_extra) if stop_extra else (S, N, U)
         ws = self._sample_ws.get(ws_key)
         if ws is not None:
             return ws
@@ -1254,8 +1255,12 @@ class Parrot(Brick):
         # readout stack and of the output projection (63 -> 64 columns); sample_model_device refreshes them per call.
         # LSTM decoders: the one 4H-wide group, tiled in the gate-interleaved column order of the machine's LSTM units.
         d.bf16 = 1 if self.decode_bf16 else 0  # (the library refuses what the bf16 machine does not take)
-        if (not gmm and not self.layer_norm and N <= 64 and H % 16 == 0 and E % 16 == 0 and R % 16 == 0
-                and O <= 64 <= ldx and env_int('PARROT_SAMPLE_PERSIST', 1) != 0):
+        if stop_extra:  # ParrotSampleDesc::eou_*: the rule's two indices per row, filled per call; first firing step per row
+            i32 = dict(device=self._dev(), dtype=torch.int32)
+            ws.update(eou_pos=torch.zeros(N, **i32), eou_ncmp=torch.zeros(N, **i32), eou_first=torch.full((N,), -1, **i32))
+            d.eou_pos, d.eou_ncmp, d.eou_first = (ws[k].data_ptr() for k in ('eou_pos', 'eou_ncmp', 'eou_first'))
+            d.eou_extra = int(stop_extra)
+        if not self._decode_machine_refusal(N):
             pm = dict(cat={}, tiled={})
             for l in range(L):
                 fb = 64 if (l + 1) in self._fb_layers else 0
@@ -1302,6 +1307,9 @@ class Parrot(Brick):
         try:
             _lib.call('parrot_sample_create', C.byref(d), C.byref(plan))
         except _lib.HipCallError as e:
+            if stop_extra:
+                raise ValueError(f"sample_until_end: the library did not build a decode machine that stops early for S={S}, "
+                                 f"N={N}, U={U} ({e}); the per-step launches cannot stop") from e
             if not self.decode_bf16:
                 raise
             raise ValueError(f"decode_dtype='bf16': the library did not build the bf16 decode machine for S={S}, "
@@ -1309,27 +1317,84 @@ class Parrot(Brick):
         if self.decode_bf16 and _lib.load().parrot_sample_is_bf16(plan) != 1:
             _lib.load().parrot_sample_destroy(plan)
             raise ValueError("decode_dtype='bf16': the plan the library built does not run bf16 operands")
+        if stop_extra and _lib.load().parrot_sample_stops_early(plan) != 1:
+            _lib.load().parrot_sample_destroy(plan)
+            raise ValueError("sample_until_end: the plan the library built does not stop at the end of the utterance")
         ws['plan'], ws['desc'] = plan, d
         self._sample_ws[ws_key] = ws  # (`key` is the group key of the loops above)
         return ws
+
+    def _decode_machine_refusal(self, N):
+        """Why this model / batch does not decode on the persistent machine ('' when it does).  The one statement of the
+        machine's conditions on the Python side: _sample_workspace prepares the machine's operands when it is '', and the
+        switches that exist on the machine only (decode_dtype='bf16', sample_until_end) refuse with it."""
+        H, E, R, O = self.rnn_h_dim, self.encoded_input_dim, self.readouts_dim, self.output_dim
+        if self.which_cost != 'MSE':
+            return "needs which_cost='MSE': the GMM head does not decode on the persistent machine"
+        if self.layer_norm:
+            return "does not cover layer_norm=True (that decode runs as per-step launches)"
+        if N > 64:
+            return f"covers at most 64 sequences per call, got {N}"
+        if H % 16 or E % 16 or R % 16 or not 61 <= O <= 64:
+            return (f"needs rnn_h_dim, the encoder width and readouts_dim to be multiples of 16 and an output frame of 61 .. 64 "
+                    f"values (the persistent machine's tiles), got {H}, {E}, {R} and {O}")
+        if env_int('PARROT_SAMPLE_PERSIST', 1) == 0:
+            return "runs on the persistent machine only, and PARROT_SAMPLE_PERSIST=0 turns that off"
+        return ''
 
     def _decode_bf16_refusal(self, N):
         """Why this model / batch cannot decode with bf16 operands ('' when it can): what the bf16 machine does not take."""
         H, E = self.rnn_h_dim, self.encoded_input_dim
         if self.cell_type != 'lstm':
             return "needs cell_type='lstm': GRU decoders have no bf16 decode path"
-        if self.which_cost != 'MSE':
-            return "needs which_cost='MSE': the GMM head does not decode on the persistent machine"
-        if self.layer_norm:
-            return "does not cover layer_norm=True (that decode runs as per-step launches)"
-        if H % 32 or E % 32:
+        why = self._decode_machine_refusal(N)
+        if not why and (H % 32 or E % 32):
             return (f"needs rnn_h_dim and the encoder width to be multiples of 32 (v_mfma_f32_16x16x32_bf16 walks K in "
                     f"steps of 32), got {H} and {E}")
-        if N > 64:
-            return f"covers at most 64 sequences per call, got {N}"
-        if env_int('PARROT_SAMPLE_PERSIST', 1) == 0:
-            return "runs on the persistent machine only, and PARROT_SAMPLE_PERSIST=0 turns that off"
-        return ''
+        return why
+
+    def _decode_stop_refusal(self, N, extra):
+        """Why this model / batch cannot stop at the end of the utterance ('' when it can): the stop lives inside the
+        persistent machine, so whatever decodes as per-step launches cannot have it."""
+        if int(extra) < 8:
+            return (f"needs extra >= 8, got {extra}: the workgroups agree on the last tick from a word published when the "
+                    f"last row fires, and without grid barriers some are a few ticks ahead of it")
+        return self._decode_machine_refusal(N)
+
+    def sample_until_end_device(self, labels, labels_mask, speaker, num_samples, max_steps, extra=40, unif=None, noise=None,
+                                seed=None):
+        """sample_model_device that stops at the end of the utterance INSIDE the decode kernel instead of decoding
+        max_steps frames and cutting afterwards.  The rule is end_of_utterance's (reference sample.py:145-163): a row ends
+        `extra` frames after the first step whose window weight on the position just past its text beats the weight on every
+        real character.  Returns (outs, lengths): the six tensors of sample_model_device cut to steps_run = max(lengths)
+        along time -- bit-identical to the first steps_run steps of sample_model_device(.., max_steps) -- and lengths [N]
+        (int64, on the device) = what end_of_utterance gives for each row of the full-length phi."""
+        from .utils import end_of_utterance_args
+        why = self._decode_stop_refusal(num_samples, extra)  # (before anything is keyed on `extra` or allocated)
+        if why:
+            raise ValueError("sample_until_end " + why)
+        self.allocate()
+        lm = torch.as_tensor(labels_mask)
+        U = lm.shape[1]
+        ws = self._sample_workspace(max_steps, num_samples, U, stop_extra=int(extra))
+        pos, ncmp = end_of_utterance_args(lm.detach().cpu().numpy(), U)
+        ws['eou_pos'].copy_(torch.from_numpy(pos))
+        ws['eou_ncmp'].copy_(torch.from_numpy(ncmp))
+        outs = self._sample_device(ws, labels, labels_mask, speaker, num_samples, max_steps, unif, noise, seed)
+        steps = C.c_int(0)
+        _lib.call('parrot_sample_steps_run', ws['plan'], C.byref(steps))
+        first = ws['eou_first'].long()
+        lengths = torch.where(first >= 0, (first + int(extra)).clamp(max=max_steps), torch.full_like(first, max_steps))
+        steps_run = int(lengths.max().item())
+        if steps.value != steps_run:
+            raise RuntimeError(f"the decode machine completed {steps.value} frames, the rows' lengths ask for {steps_run}")
+        return [o[:steps_run] for o in outs], lengths
+
+    def sample_until_end(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, max_steps, extra=40):
+        """numpy twin of sample_until_end_device (as sample_model is of sample_model_device): (list of numpy arrays,
+        numpy lengths [N])."""
+        outs, lengths = self.sample_until_end_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, max_steps, extra)
+        return [o.detach().cpu().numpy().copy() for o in outs], lengths.cpu().numpy()
 
     def sample_model_device(self, labels, labels_mask, speaker, num_samples, num_steps, unif=None, noise=None,
                             seed=None):
@@ -1337,6 +1402,10 @@ class Parrot(Brick):
         [sample_x [S,N,O], k [S,N,A], w [S,N,E], pi, phi [S,N,U], pi_att [S,N,A]].
         GMM head: the component choice / Gaussian noise come from `unif` [S,N] and `noise` [S,N,O] if given,
         else from torch's generator (`seed`); Theano's MRG stream itself is not reproducible."""
+        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed)
+
+    def _sample_device(self, ws, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed):
+        """One decode call on the workspace `ws` (None: the plain workspace of the shape)."""
         self.allocate()
         dev = self._dev()
         labels = torch.as_tensor(labels).to(dev)
@@ -1344,7 +1413,8 @@ class Parrot(Brick):
         N, U = labels.shape[0], labels.shape[1]
         assert N == num_samples
         S, L, H, O = num_steps, self.num_layers, self.rnn_h_dim, self.output_dim
-        ws = self._sample_workspace(S, N, U)
+        if ws is None:
+            ws = self._sample_workspace(S, N, U)
         ws['ctx'].copy_(self._encoder_forward(labels, labels_mask, None))
         self._sum_layer_biases(ws, extra_fb=not self.layer_norm)
         for l in range(1, L + 1):

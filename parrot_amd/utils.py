@@ -4,7 +4,7 @@ which any non-empty string is truthy.  Plotting / animation helpers (utils.py:30
 and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
---device, --use_graph; sample.py: --decode_dtype.
+--device, --use_graph; sample.py: --decode_dtype, --stop_at_end.
 """
 from __future__ import annotations
 
@@ -121,6 +121,9 @@ def sample_parse(argv=None):
                         help='bf16: the recurrent-layer products of the decode loop round both operands to bf16 '
                              '(LSTM decoders on the persistent machine, DESIGN.md 3.6); float32: f32 operands, whatever '
                              'the experiment was trained with')
+    parser.add_argument('--stop_at_end', type=int, default=0,
+                        help='1: the decode kernel itself stops at the end of the utterance (the rule of sample.py:145-163) '
+                             'instead of decoding --num_steps frames and cutting afterwards; same frames, same lengths')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
@@ -137,3 +140,19 @@ def end_of_utterance(phi, labels_length, num_steps, extra=40):
         return int(numpy.minimum(num_steps, t + extra))
     except Exception:
         return int(num_steps)
+
+
+def end_of_utterance_args(labels_mask, U):
+    """The two indices per row that the decode kernel's end-of-utterance rule takes (Parrot.sample_until_end_device), built
+    from labels_mask exactly as sample.py and end_of_utterance do, Python slicing included: the rule compares
+    phi[:, pos] with phi[:, :pos - 1], and for pos = 0 the slice [:-1] is all but the LAST position.  Returns (pos, ncmp),
+    int32 arrays [N]: the row fires at the first step with phi[pos] > phi[j] for every j < ncmp."""
+    import numpy
+    mask = numpy.asarray(labels_mask)
+    pos = numpy.zeros(mask.shape[0], dtype=numpy.int32)
+    ncmp = numpy.zeros(mask.shape[0], dtype=numpy.int32)
+    for i in range(mask.shape[0]):
+        ll = int(mask[i].sum())
+        pos[i] = min(ll, U - 1)
+        ncmp[i] = pos[i] - 1 if pos[i] >= 1 else U - 1
+    return pos, ncmp

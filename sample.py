@@ -73,6 +73,9 @@ def main(argv=None):
 
     if args.sample_one_step:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_using_input(data_tr, args.num_samples)
+    elif args.stop_at_end:  # the kernel applies the end-of-utterance rule itself and decodes no frame beyond it
+        (gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att), stop_lengths = parrot.sample_until_end(
+            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps)
     else:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_model(
             labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps)
@@ -81,6 +84,9 @@ def main(argv=None):
     gen_x, gen_phi = gen_x.swapaxes(0, 1), gen_phi.swapaxes(0, 1)
     features_lengths = []
     for idx in range(args.num_samples):
+        if args.stop_at_end and not args.sample_one_step:
+            features_lengths.append(int(stop_lengths[idx]))
+            continue
         ll = int(labels_mask_tr[idx].sum())
         features_lengths.append(end_of_utterance(gen_phi[idx], min(ll, gen_phi.shape[2] - 1), args.num_steps))
     if raw_output:  # sample.py:165-173: SampleRNN vocoder on the generated frames

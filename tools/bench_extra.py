@@ -1,9 +1,13 @@
 """Secondary measurements (BASELINE configs[2] decode latency, the same loop with LSTM decoders -- persistent machine
 with bf16 operands (decode_dtype='bf16') against the f32 machine against the per-step launches, alternating child
-processes --, configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
+processes --, the configs[2] decode that stops at the end of the utterance against the one that runs all its steps,
+configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
 
   bench_extra.py                         everything, one JSON line
-  bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_lstm2_1024, decode_lstm3_1536, samplernn_cfg5, mulaw)
+  bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_stop, decode_lstm2_1024, decode_lstm3_1536,
+                                         samplernn_cfg5, mulaw)
+  bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
+                                         the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
   bench_extra.py --reps N                on / off alternations of the LSTM decode entries (default 3)"""
 import json
@@ -21,7 +25,7 @@ def _arg(name, dflt=None):
     return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else dflt
 
 
-ALL = ("decode_cfg3", "decode_lstm2_1024", "decode_lstm3_1536", "samplernn_cfg5", "mulaw")
+ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "samplernn_cfg5", "mulaw")
 only = tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -57,6 +61,62 @@ def decode(kw, dump=None, decode_dtype='float32'):
     return res
 
 
+def decode_stop(kappa_bias, reps):
+    """configs[2] decode shape, max_steps 2048: the plain plan (all steps), the stopping plan with a predicate that never
+    fires (all steps: what the stop costs per step) and the stopping plan with the rule of the text (leaves early),
+    alternating in one process; whole-call wall times, every call listed."""
+    from parrot_amd import _lib
+    from parrot_amd.model import Parrot
+    m = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, num_layers=2, rnn_h_dim=1024,
+               readouts_dim=1024).initialize()
+    m._p('/h1_to_att/fork_kappa.b').fill_(kappa_bias)
+    g = torch.Generator().manual_seed(0)
+    N, U, S, extra = 16, 100, 2048, 40
+    lab = torch.randint(0, 43, (N, U), generator=g)
+    lm = torch.ones(N, U)
+    for i in range(N):  # texts of 100, 97, .. 55 characters
+        lm[i, U - 3 * i:] = 0
+
+    def timed(fn):
+        torch.cuda.synchronize(); t0 = time.time()
+        r = fn()
+        torch.cuda.synchronize()
+        return time.time() - t0, r
+
+    def never():  # the stopping plan on the same inputs, its rows compare position 0 with itself: never true
+        ws = m._sample_workspace(S, N, U, stop_extra=extra)
+        ws['eou_pos'].zero_(); ws['eou_ncmp'].fill_(U - 1)
+        return m._sample_device(ws, lab, lm, None, N, S, None, None, None)
+
+    t = {"plain": [], "never": [], "stopped": []}
+    for rep in range(reps + 1):  # (the first round builds the plans and captures the graphs: not listed)
+        runs = (("plain", lambda: m.sample_model_device(lab, lm, None, N, S)), ("never", never),
+                ("stopped", lambda: m.sample_until_end_device(lab, lm, None, N, S, extra=extra)))
+        for key, fn in runs:
+            dt, r = timed(fn)
+            if rep:
+                t[key].append(dt)
+            if key == "plain":
+                full = r
+            if key == "never":
+                same_never = all(torch.equal(a, b) for a, b in zip(r, full))
+            if key == "stopped":
+                outs, lengths = r
+    steps = int(lengths.max())
+    ws = m._sample_ws[('stop', S, N, U, extra)]
+    us = lambda v: [round(1e6 * x / S, 2) for x in v]
+    res = {"batch": N, "max_steps": S, "extra": extra, "kappa_bias": kappa_bias,
+           "machine": int(_lib.load().parrot_sample_is_persistent(ws['plan'])),
+           "lengths": lengths.tolist(), "steps_run": steps,
+           "prefix_bit_identical": all(torch.equal(a, b[:steps]) for a, b in zip(outs, full)),
+           "never_firing_bit_identical": same_never,
+           "seconds_unstopped": [round(x, 4) for x in t["plain"]], "seconds_stopped": [round(x, 4) for x in t["stopped"]],
+           "us_per_step_plain": us(t["plain"]), "us_per_step_stop_plan_never_firing": us(t["never"]),
+           "us_per_step_stopped": [round(1e6 * x / steps, 2) for x in t["stopped"]]}
+    m.close()
+    return res
+
+
 if "--child" in sys.argv:  # one LSTM decode measurement under the caller's environment
     print(json.dumps(decode(dict(LSTM_SHAPES[_arg("--child")], cell_type='lstm'),
                             decode_dtype=_arg("--decode-dtype", "float32"))))
@@ -65,6 +125,10 @@ if "--child" in sys.argv:  # one LSTM decode measurement under the caller's envi
 # ---- configs[2]: GRU decoder
 if "decode_cfg3" in only:
     out["decode_cfg3"] = decode(dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024), _arg("--dump-sample"))
+
+# ---- configs[2] again: stop at the end of the utterance inside the machine
+if "decode_stop" in only:
+    out["decode_stop"] = decode_stop(float(_arg("--kappa-bias", "-1.0")), int(_arg("--reps", "3")))
 
 # ---- LSTM decoders: the persistent machine with bf16 operands and with f32 operands (PARROT_SAMPLE_PERSIST=1, the default)
 # against the per-step launches (PARROT_SAMPLE_PERSIST=0), each run in a child process of its own, alternating so the
