@@ -342,6 +342,52 @@ int parrot_decoder_writes_bf16_grads(void* plan);
 int parrot_decoder_seq_fwd(void* plan, void* stream);
 int parrot_decoder_seq_bwd(void* plan, void* stream);
 int parrot_decoder_destroy(void* plan);
+
+/* ------------------------------------------------------------------------------------------
+ * Training: readout stack and output layer composed (model.py:739-755 with the MSE head and no layer norm).
+ *   readouts = sum_s x_s . Wr_s + sum_i rb_i,   pred = readouts . Wo + bo
+ * has nothing non-linear in between, so pred = sum_s x_s . W'_s + b' with W' = Wr . Wo [sum K_s, O] and
+ * b' = (sum_i rb_i) . Wo + bo: products of width O <= 64 instead of R.  parrot_readout_composed_fwd composes W' and b'
+ * from the current weights (accumulated in double, rounded once) and writes pred; parrot_readout_composed_bwd takes
+ * dp = d cost / d pred and, by the chain rule through the same composition,
+ *   dx_s = dp . W'_s^T                                   stored below zero_rows zero-filled rows (slot 0 of a history),
+ *   gWr += dW' . Wo^T,  gWo += Wr^T . dW' + rbsum^T (x) sum_m dp,   with dW' = sum_m x[m,:]^T dp[m,:],
+ *   grb_i += (sum_m dp) . Wo^T,  gbo += sum_m dp.
+ * Segments: x_s [M, K_s] row-major, leading dimension ldx[s] (a multiple of 4, 16-byte aligned base), K_s a multiple
+ * of 16; Wr [sum K_s, R] holds the segments' rows in order.  The backward call reads the W' its forward call left in
+ * the workspace: call them in pairs, weights unchanged in between.  The reduction over M is cut into slices of
+ * slice_rows rows (0: chosen by the library) whose partial tiles are added in slice order: no float atomics, results
+ * are bit-reproducible.  The workspace is the caller's: parrot_readout_composed_ws_floats(desc) floats, 16-byte
+ * aligned, its size in ws_floats; the calls neither allocate nor synchronise.
+ * ------------------------------------------------------------------------------------------ */
+#define PARROT_READOUT_MAX_SEG 4
+typedef struct ParrotReadoutComposedDesc {
+    long long M;                  /* rows (T * B) */
+    long long ws_floats;          /* floats behind the workspace pointer handed to the calls */
+    int nseg, R, O, zero_rows;    /* segments, readout width, output width (<= 64), rows zero-filled on top of each dx_s */
+    int slice_rows, nbias;        /* rows of M per slice of the dW' reduction (0: automatic); readout bias vectors */
+    int K[PARROT_READOUT_MAX_SEG];
+    int ldx[PARROT_READOUT_MAX_SEG];
+    int lddx[PARROT_READOUT_MAX_SEG];
+    int ldwr, ldwo, ldp, lddp;    /* leading dimensions of Wr (>= R), Wo (>= O), pred (>= O), dp (>= O) */
+    int ldgwr, ldgwo;             /* leading dimensions of gWr (>= R) and gWo (>= O) */
+    const float* x[PARROT_READOUT_MAX_SEG];
+    const float* Wr; const float* Wo;
+    const float* rb[PARROT_READOUT_MAX_SEG];   /* [R] each: the *_to_readout biases */
+    const float* bo;              /* [O] */
+    float* pred;                  /* [M, O]  forward out */
+    const float* dp;              /* [M, O]  backward in */
+    float* dx[PARROT_READOUT_MAX_SEG];  /* [zero_rows + M, K_s], leading dimension lddx[s]: rows < zero_rows = 0, then dp . W'_s^T */
+    float* gWr; float* gWo;       /* [sum K_s, R], [R, O]   accumulated into */
+    float* grb[PARROT_READOUT_MAX_SEG]; /* [R] each           accumulated into */
+    float* gbo;                   /* [O]                    accumulated into */
+} ParrotReadoutComposedDesc;
+
+/* Floats of workspace the two calls need for this descriptor (sizes only are read), or -PARROT_ERR_BADARG. */
+long long parrot_readout_composed_ws_floats(const ParrotReadoutComposedDesc* desc);
+int parrot_readout_composed_fwd(const ParrotReadoutComposedDesc* desc, float* ws, void* stream);
+int parrot_readout_composed_bwd(const ParrotReadoutComposedDesc* desc, float* ws, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Autoregressive decode: the theano.scan over `sample_step` of Parrot.sample_model_fun
  * (model.py:882-1057) for the MSE ("greedy") head: x_t = readout_to_output(readouts_t).

@@ -78,6 +78,27 @@ class DecoderDesc(C.Structure):
     ]
 
 
+READOUT_MAX_SEG = 4
+
+
+class ReadoutComposedDesc(C.Structure):
+    _fields_ = [
+        ("M", C.c_longlong), ("ws_floats", C.c_longlong),
+        ("nseg", C.c_int), ("R", C.c_int), ("O", C.c_int), ("zero_rows", C.c_int),
+        ("slice_rows", C.c_int), ("nbias", C.c_int),
+        ("K", C.c_int * READOUT_MAX_SEG), ("ldx", C.c_int * READOUT_MAX_SEG), ("lddx", C.c_int * READOUT_MAX_SEG),
+        ("ldwr", C.c_int), ("ldwo", C.c_int), ("ldp", C.c_int), ("lddp", C.c_int),
+        ("ldgwr", C.c_int), ("ldgwo", C.c_int),
+        ("x", C.c_void_p * READOUT_MAX_SEG),
+        ("Wr", C.c_void_p), ("Wo", C.c_void_p),
+        ("rb", C.c_void_p * READOUT_MAX_SEG), ("bo", C.c_void_p),
+        ("pred", C.c_void_p), ("dp", C.c_void_p),
+        ("dx", C.c_void_p * READOUT_MAX_SEG),
+        ("gWr", C.c_void_p), ("gWo", C.c_void_p),
+        ("grb", C.c_void_p * READOUT_MAX_SEG), ("gbo", C.c_void_p),
+    ]
+
+
 class SampleDesc(C.Structure):
     _fields_ = [
         ("S", C.c_int), ("B", C.c_int), ("H", C.c_int), ("E", C.c_int), ("A", C.c_int),
@@ -181,6 +202,9 @@ SIGNATURES = {
     "parrot_decoder_seq_fwd": (_i, [_vp, _vp]),
     "parrot_decoder_seq_bwd": (_i, [_vp, _vp]),
     "parrot_decoder_destroy": (_i, [_vp]),
+    "parrot_readout_composed_ws_floats": (C.c_longlong, [C.POINTER(ReadoutComposedDesc)]),
+    "parrot_readout_composed_fwd": (_i, [C.POINTER(ReadoutComposedDesc), _vp, _vp]),
+    "parrot_readout_composed_bwd": (_i, [C.POINTER(ReadoutComposedDesc), _vp, _vp]),
     "parrot_sample_create": (_i, [C.POINTER(SampleDesc), C.POINTER(C.c_void_p)]),
     "parrot_sample_persist_floats": (C.c_longlong, [C.POINTER(SampleDesc)]),
     "parrot_sample_is_persistent": (_i, [_vp]),

@@ -520,8 +520,7 @@ class Parrot(Brick):
             dkappa=torch.zeros(B, A, **f),
             dp=torch.empty(T, B, 3 * A, **f),
             ctx=torch.zeros(B, U, E, **f),
-            readouts=torch.empty(T * B, R, **f),
-        )
+        )  # (`readouts` [T*B, R] comes from _readouts_buffer: the composed readout path never allocates it)
         lstm = self.cell_type == 'lstm'
         if lstm:
             ws.update(cst=[torch.zeros(T + 1, B, H, **f) for _ in range(L)],
@@ -794,46 +793,18 @@ class Parrot(Brick):
             _lib.call('parrot_decoder_status', ws['plan'])  # that gave up is consumed (synchronises)
 
         # --- readouts and output (model.py:739-755)
-        readouts = ws['readouts']
-        Wr = self.store.storage['dec.Wr']
-        rb = self._p('/att_to_readout.b').clone()
-        for l in range(1, L + 1):
-            rb.add_(self._p(f'/h{l}_to_readout.b'))
-        if self.layer_norm:
-            # model.py:739-753: each h{l}_to_readout output is normalised on its own, then summed
-            ops.gemm(ws['w'][1:].view(T * B, E), Wr[L * H:], bias=self._p('/att_to_readout.b'), out=readouts)
-            for l in range(L):
-                y, sig = ops.simple_norm_fwd(
-                    ops.gemm(ws['h'][l][1:].view(T * B, H), Wr[l * H:(l + 1) * H],
-                             bias=self._p(f'/h{l + 1}_to_readout.b')), add_into=readouts)
-                save[('ln_ro', l)] = (y, sig)
-        elif self._bf16_readouts(T, R):
-            # bf16-operand decoders (round 5): the readout products on bf16 COPIES of the state / context histories and of
-            # Wr (parrot_gemm_bf16in_ex, 256 x 256 tiles) instead of f32 operands rounded inside the product -- the same
-            # values rounded the same way (nearest even).  The copies are reused by the backward pass (dread . Wr^T, the
-            # readout and scan weight gradients).
-            cp = self._bf16_copies(ws, T, B, convert=('h', 'w'))
-            save['bf16_hw_done'] = True
-            Wr16 = save['Wr16'] = ops.to_bf16(Wr)
-            ops.gemm16(cp['h'][0][1:T + 1].view(T * B, H), Wr16[0:H], out=readouts, bias=rb)
-            for l in range(1, L):
-                ops.gemm16(cp['h'][l][1:T + 1].view(T * B, H), Wr16[l * H:(l + 1) * H], out=readouts, accumulate=True)
-            ops.gemm16(cp['w'][1:T + 1].view(T * B, E), Wr16[L * H:], out=readouts, accumulate=True)
+        composed = save['readout_composed'] = self._readout_composed()
+        self._readout_path = 'composed' if composed else 'factored'
+        if composed:
+            # nothing non-linear between the readout stack and the output layer: pred = [h_0 .. h_{L-1} | w] . (Wr . Wo) + b'
+            # in one launch of width 64 (csrc/readout.hip); no [T*B, R] readouts buffer
+            rd = self._readout_desc(ws, T, B)
+            pr = torch.empty(T * B, O, device=dev, dtype=torch.float32)
+            rd.pred = pr.data_ptr()
+            _lib.call('parrot_readout_composed_fwd', C.byref(rd), ws['ro_ws'].data_ptr(), ops._stream())
+            preds = [pr.view(T, B, O)]
         else:
-            ops.gemm(ws['h'][0][1:].view(T * B, H), Wr[0:H], bias=rb, out=readouts)
-            for l in range(1, L):
-                ops.gemm(ws['h'][l][1:].view(T * B, H), Wr[l * H:(l + 1) * H], out=readouts, accumulate=True)
-            ops.gemm(ws['w'][1:].view(T * B, E), Wr[L * H:], out=readouts, accumulate=True)
-        if self.use_speaker:
-            spr = ops.gemm(emb_spk, self._p('/speaker_to_readout.W'), bias=self._p('/speaker_to_readout.b'))
-            readouts.view(T, B, R).add_(spr.unsqueeze(0))
-        preds = []
-        for i, (wn, bn, dim) in enumerate(self._out_names):
-            pr = ops.gemm(readouts, self.store.param(wn), bias=self.store.param(bn)).view(T, B, dim)
-            if self.use_speaker:
-                swn, sbn, _ = self._spk_out_names[i]
-                pr.add_(ops.gemm(emb_spk, self.store.param(swn), bias=self.store.param(sbn)).unsqueeze(0))
-            preds.append(pr)
+            preds = self._readouts_factored(ws, save, T, B, emb_spk)
 
         # --- masked cost (model.py:757-784); small [T,B,O] elementwise math with local autograd
         leafs = [p.detach().requires_grad_(True) for p in preds]
@@ -882,6 +853,108 @@ class Parrot(Brick):
         cost = _CostFn.apply(anchor, self, self._token, cost_val.detach())
         return cost, updates, attention_vars, (cost_raw.detach() if cost_raw is not None else None)
 
+    def _readouts_factored(self, ws, save, T, B, emb_spk):
+        """The readout stack and the output layer as the reference writes them (model.py:739-755): readouts [T*B, R] =
+        sum of the `*_to_readout` bricks, then one product per output head.  Returns the heads' predictions."""
+        H, E, L, R, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.readouts_dim, self.output_dim
+        readouts = self._readouts_buffer(ws, T, B)
+        Wr = self.store.storage['dec.Wr']
+        rb = self._p('/att_to_readout.b').clone()
+        for l in range(1, L + 1):
+            rb.add_(self._p(f'/h{l}_to_readout.b'))
+        if self.layer_norm:
+            # model.py:739-753: each h{l}_to_readout output is normalised on its own, then summed
+            ops.gemm(ws['w'][1:].view(T * B, E), Wr[L * H:], bias=self._p('/att_to_readout.b'), out=readouts)
+            for l in range(L):
+                y, sig = ops.simple_norm_fwd(
+                    ops.gemm(ws['h'][l][1:].view(T * B, H), Wr[l * H:(l + 1) * H],
+                             bias=self._p(f'/h{l + 1}_to_readout.b')), add_into=readouts)
+                save[('ln_ro', l)] = (y, sig)
+        elif self._bf16_readouts(T, R):
+            # bf16-operand decoders (round 5): the readout products on bf16 COPIES of the state / context histories and of
+            # Wr (parrot_gemm_bf16in_ex, 256 x 256 tiles) instead of f32 operands rounded inside the product -- the same
+            # values rounded the same way (nearest even).  The copies are reused by the backward pass (dread . Wr^T, the
+            # readout and scan weight gradients).
+            cp = self._bf16_copies(ws, T, B, convert=('h', 'w'))
+            save['bf16_hw_done'] = True
+            Wr16 = save['Wr16'] = ops.to_bf16(Wr)
+            ops.gemm16(cp['h'][0][1:T + 1].view(T * B, H), Wr16[0:H], out=readouts, bias=rb)
+            for l in range(1, L):
+                ops.gemm16(cp['h'][l][1:T + 1].view(T * B, H), Wr16[l * H:(l + 1) * H], out=readouts, accumulate=True)
+            ops.gemm16(cp['w'][1:T + 1].view(T * B, E), Wr16[L * H:], out=readouts, accumulate=True)
+        else:
+            ops.gemm(ws['h'][0][1:].view(T * B, H), Wr[0:H], bias=rb, out=readouts)
+            for l in range(1, L):
+                ops.gemm(ws['h'][l][1:].view(T * B, H), Wr[l * H:(l + 1) * H], out=readouts, accumulate=True)
+            ops.gemm(ws['w'][1:].view(T * B, E), Wr[L * H:], out=readouts, accumulate=True)
+        if self.use_speaker:
+            spr = ops.gemm(emb_spk, self._p('/speaker_to_readout.W'), bias=self._p('/speaker_to_readout.b'))
+            readouts.view(T, B, R).add_(spr.unsqueeze(0))
+        preds = []
+        for i, (wn, bn, dim) in enumerate(self._out_names):
+            pr = ops.gemm(readouts, self.store.param(wn), bias=self.store.param(bn)).view(T, B, dim)
+            if self.use_speaker:
+                swn, sbn, _ = self._spk_out_names[i]
+                pr.add_(ops.gemm(emb_spk, self.store.param(swn), bias=self.store.param(sbn)).unsqueeze(0))
+            preds.append(pr)
+        return preds
+
+    # ------------------------------------------------------------------ composed readout -> output path
+    @property
+    def readout_path(self):
+        """'composed' or 'factored': how the last compute_cost() ran the readout stack and the output layer (None before
+        the first call)."""
+        return getattr(self, '_readout_path', None)
+
+    def _readout_composed(self):
+        """True when readouts -> output runs as one composed affine map (csrc/readout.hip): MSE head (one head, at most
+        64 wide), no layer norm between the bricks, no speaker terms, f32 operands, a readout wide enough for the
+        composition to pay.  PARROT_READOUT_COMPOSED=0 (read per step) keeps the factored products."""
+        H, E = self.rnn_h_dim, self.encoded_input_dim
+        return (not self.layer_norm and not self.use_speaker and not self.compute_bf16
+                and len(self._out_names) == 1 and sum(d for _, _, d in self._out_names) <= 64
+                and self.readouts_dim >= 256 and H % 16 == 0 and E % 16 == 0
+                and env_int('PARROT_READOUT_COMPOSED', 1) != 0)
+
+    def _readouts_buffer(self, ws, T, B):
+        if 'readouts' not in ws:
+            ws['readouts'] = torch.empty(T * B, self.readouts_dim, device=self._dev(), dtype=torch.float32)
+        return ws['readouts']
+
+    def _readout_desc(self, ws, T, B):
+        """ParrotReadoutComposedDesc over the window's histories and its workspace (made once per training workspace).
+        It holds raw pointers into the flat parameter / gradient buffers and into the workspace's histories: both are
+        allocated once (ParamStore.allocate, one workspace per (T, B, U)) and never reallocated; only `pred` and `dp`
+        change per step."""
+        if 'ro_desc' in ws:
+            return ws['ro_desc']
+        H, E, L, R, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.readouts_dim, self.output_dim
+        d = _lib.ReadoutComposedDesc()
+        d.M, d.nseg, d.R, d.O, d.zero_rows, d.slice_rows = T * B, L + 1, R, O, B, 0
+        for l in range(L):
+            d.K[l], d.ldx[l], d.lddx[l] = H, H, H
+            d.x[l], d.dx[l] = ws['h'][l][1:].data_ptr(), ws['dh'][l].data_ptr()
+        d.K[L], d.ldx[L], d.lddx[L] = E, E, E
+        d.x[L], d.dx[L] = ws['w'][1:].data_ptr(), ws['dw'].data_ptr()
+        Wr, gWr = self.store.storage['dec.Wr'], self.store.storage_grad['dec.Wr']
+        wn, bn, _ = self._out_names[0]
+        Wo, gWo = self.store.param(wn), self.store.grad(wn)
+        d.Wr, d.ldwr, d.gWr, d.ldgwr = Wr.data_ptr(), Wr.stride(0), gWr.data_ptr(), gWr.stride(0)
+        d.Wo, d.ldwo, d.gWo, d.ldgwo = Wo.data_ptr(), Wo.stride(0), gWo.data_ptr(), gWo.stride(0)
+        d.bo, d.gbo = self.store.param(bn).data_ptr(), self.store.grad(bn).data_ptr()
+        names = [f'/h{l}_to_readout.b' for l in range(1, L + 1)] + ['/att_to_readout.b']
+        d.nbias = len(names)
+        for i, n in enumerate(names):
+            d.rb[i], d.grb[i] = self._p(n).data_ptr(), self._g(n).data_ptr()
+        d.ldp, d.lddp = O, O
+        n = int(_lib.load().parrot_readout_composed_ws_floats(C.byref(d)))
+        if n <= 0:
+            raise _lib.HipCallError(f"parrot_readout_composed_ws_floats failed with code {-n}")
+        ws['ro_ws'] = torch.empty(n, device=self._dev(), dtype=torch.float32)
+        d.ws_floats = n
+        ws['ro_desc'] = d
+        return d
+
     # ------------------------------------------------------------------ backward
     def _backward_f(self, token, gscale):
         if self._saved is None or self._saved[0] != token:
@@ -891,7 +964,6 @@ class Parrot(Brick):
         ws, T, B, U = save['ws'], save['T'], save['B'], save['U']
         H, E, L, R, O, A = (self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.readouts_dim,
                             self.output_dim, self.attention_size)
-        readouts = ws['readouts']
         emb_spk = save.get('emb_spk')
         demb_spk = torch.zeros_like(emb_spk) if emb_spk is not None else None
 
@@ -905,65 +977,18 @@ class Parrot(Brick):
             save['dpreds'] = [(l.grad if l.grad is not None else torch.zeros_like(l)).reshape(T * B, -1).contiguous()
                               for l in leafs]
             gscale = torch.ones((), device=gscale.device)
-        # output layer
-        dread = torch.empty(T * B, R, device=readouts.device, dtype=torch.float32)  # (the first head's product stores: no fill)
-        for i, (wn, bn, dim) in enumerate(self._out_names):
-            dp = save['dpreds'][i] * gscale
-            ops.gemm(readouts.t(), dp, out=self.store.grad(wn), accumulate=True)
-            ops.colsum(dp, out=self.store.grad(bn), accumulate=True)
-            ops.gemm(dp, self.store.param(wn).t(), out=dread, accumulate=i > 0)
-            if self.use_speaker:
-                swn, sbn, _ = self._spk_out_names[i]
-                dsum = dp.view(T, B, dim).sum(0)
-                ops.gemm(emb_spk.t(), dsum, out=self.store.grad(swn), accumulate=True)
-                ops.colsum(dsum, out=self.store.grad(sbn), accumulate=True)
-                ops.gemm(dsum, self.store.param(swn).t(), out=demb_spk, accumulate=True)
-        # readouts
-        gWr = self.store.storage_grad['dec.Wr']
-        Wr = self.store.storage['dec.Wr']
-        db = ops.colsum(dread)
-        dro = [dread] * L  # gradient wrt each h{l}_to_readout output
-        if self.layer_norm:
-            dro = [ops.simple_norm_bwd(dread, *save[('ln_ro', l)]) for l in range(L)]
-        # weight gradients of the readout stack: nothing in the backward scan needs them, so they are handed to
-        # _scan_bwd_and_weight_grads, which may run them beside the scan
-        def readout_weight_grads():
-            if self._bf16_weight_grads(0, T, T) and R % 8 == 0 and not self.layer_norm:
-                # bf16-operand decoders: from the bf16 copies of the state / context histories (made here, reused by the
-                # scan's weight gradients below) and a bf16 copy of the readout gradient
-                cp = self._bf16_copies(ws, T, B, convert=() if save.get('bf16_hw_done') else ('h', 'w'))
-                ws['bf16_hw_fresh'] = True
-                d16 = save['d16'] if 'd16' in save else ops.to_bf16(dread)
-                for l in range(L):
-                    ops.gemm_bf16in(cp['h'][l][1:T + 1].view(T * B, H), d16, gWr[l * H:(l + 1) * H], accumulate=True)
-                ops.gemm_bf16in(cp['w'][1:T + 1].view(T * B, E), d16, gWr[L * H:], accumulate=True)
-                return
-            for l in range(L):
-                ops.gemm(ws['h'][l][1:].view(T * B, H).t(), dro[l], out=gWr[l * H:(l + 1) * H], accumulate=True)
-            ops.gemm(ws['w'][1:].view(T * B, E).t(), dread, out=gWr[L * H:], accumulate=True)
-        for l in range(L):
-            self._g(f'/h{l + 1}_to_readout.b').add_(ops.colsum(dro[l]) if self.layer_norm else db)
-        self._g('/att_to_readout.b').add_(db)
-        if self.use_speaker:
-            dsum = dread.view(T, B, R).sum(0)
-            ops.gemm(emb_spk.t(), dsum, out=self._g('/speaker_to_readout.W'), accumulate=True)
-            ops.colsum(dsum, out=self._g('/speaker_to_readout.b'), accumulate=True)
-            ops.gemm(dsum, self._p('/speaker_to_readout.W').t(), out=demb_spk, accumulate=True)
-        # gradients entering the scan through the readouts
-        if 'Wr16' in save:  # bf16-operand decoders: dread . Wr^T on the bf16 copies (one copy of dread, shared with gWr)
-            Wr16 = save['Wr16']
-            d16 = save['d16'] = ops.to_bf16(dread)
-            for l in range(L):
-                ws['dh'][l][0].zero_()
-                ops.gemm16(d16, Wr16[l * H:(l + 1) * H].t(), out=ws['dh'][l][1:].view(T * B, H))
-            ws['dw'][0].zero_()
-            ops.gemm16(d16, Wr16[L * H:].t(), out=ws['dw'][1:].view(T * B, E))
+        if save['readout_composed']:
+            # dh_l / dw (slot 0 zero-filled in the same launch) and every gradient of the readout stack and the output layer
+            # through the composed map, final before the backward scan starts (csrc/readout.hip)
+            # (the call reads the W' that this step's forward call left in ws['ro_ws']: _backward_f only accepts the token
+            # of the LAST compute_cost, so no other forward call on this workspace and no optimiser step lies in between)
+            rd = self._readout_desc(ws, T, B)
+            dp = (save['dpreds'][0] * gscale).contiguous()
+            rd.dp = dp.data_ptr()
+            _lib.call('parrot_readout_composed_bwd', C.byref(rd), ws['ro_ws'].data_ptr(), ops._stream())
+            readout_weight_grads = None
         else:
-            for l in range(L):
-                ws['dh'][l][0].zero_()
-                ops.gemm(dro[l], Wr[l * H:(l + 1) * H].t(), out=ws['dh'][l][1:].view(T * B, H))
-            ws['dw'][0].zero_()
-            ops.gemm(dread, Wr[L * H:].t(), out=ws['dw'][1:].view(T * B, E))
+            readout_weight_grads = self._readouts_factored_bwd(ws, save, T, B, gscale, emb_spk, demb_spk)
         ws['dkappa'].zero_()
         ws['dw0'].zero_()
         for t_ in (ws['dhup'] + ws.get('dcell', []) + ws.get('dhup_b', []) + ws.get('dhup_c', []) +
@@ -1026,7 +1051,7 @@ class Parrot(Brick):
         # encoder output: dctx[b] = phi[:, b, :]^T . dw_total[1:, b, :]   (batched over b).  (Round 4 ran this share -- the
         # d ctx product and the encoder's backward scan, two latency chains of 0.5 ms -- on a side stream BESIDE the weight-
         # gradient GEMMs: 76.5 vs 72.3 ms per cfg2 step, the chains and the MFMA-bound products slow each other down; removed.)
-        dctx = torch.empty(B, U, E, device=readouts.device, dtype=torch.float32)
+        dctx = torch.empty(B, U, E, device=ws['ctx'].device, dtype=torch.float32)
         with ops.gemm_precision(ops.PRECISION_F32):  # attention + encoder: f32 operands in every operand mode
             _lib.call('parrot_gemm', ws['phi'].data_ptr(), B * U, 1, ws['dw'][1:].data_ptr(), B * E, 0,
                       dctx.data_ptr(), E, U, E, T, None, 1.0, 0, 0, B, U, E, U * E, 1, ops._stream())
@@ -1034,6 +1059,72 @@ class Parrot(Brick):
                 self._scatter_rows_add(self._g('/lookuptable.W'), save['spk_idx'], demb_spk)
             self._encoder_backward(dctx, save)
         self._saved = None
+
+    def _readouts_factored_bwd(self, ws, save, T, B, gscale, emb_spk, demb_spk):
+        """Backward of _readouts_factored: output layer, readout biases, the gradients entering the scan (dh_l, dw).
+        Returns the closure that adds the readout weight gradients (run by _scan_bwd_and_weight_grads)."""
+        H, E, L, R = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.readouts_dim
+        readouts = ws['readouts']
+        # output layer
+        dread = torch.empty(T * B, R, device=readouts.device, dtype=torch.float32)  # (the first head's product stores: no fill)
+        for i, (wn, bn, dim) in enumerate(self._out_names):
+            dp = save['dpreds'][i] * gscale
+            ops.gemm(readouts.t(), dp, out=self.store.grad(wn), accumulate=True)
+            ops.colsum(dp, out=self.store.grad(bn), accumulate=True)
+            ops.gemm(dp, self.store.param(wn).t(), out=dread, accumulate=i > 0)
+            if self.use_speaker:
+                swn, sbn, _ = self._spk_out_names[i]
+                dsum = dp.view(T, B, dim).sum(0)
+                ops.gemm(emb_spk.t(), dsum, out=self.store.grad(swn), accumulate=True)
+                ops.colsum(dsum, out=self.store.grad(sbn), accumulate=True)
+                ops.gemm(dsum, self.store.param(swn).t(), out=demb_spk, accumulate=True)
+        # readouts
+        gWr = self.store.storage_grad['dec.Wr']
+        Wr = self.store.storage['dec.Wr']
+        db = ops.colsum(dread)
+        dro = [dread] * L  # gradient wrt each h{l}_to_readout output
+        if self.layer_norm:
+            dro = [ops.simple_norm_bwd(dread, *save[('ln_ro', l)]) for l in range(L)]
+        # weight gradients of the readout stack: nothing in the backward scan needs them, so they are handed to
+        # _scan_bwd_and_weight_grads, which may run them beside the scan
+        def readout_weight_grads():
+            if self._bf16_weight_grads(0, T, T) and R % 8 == 0 and not self.layer_norm:
+                # bf16-operand decoders: from the bf16 copies of the state / context histories (made here, reused by the
+                # scan's weight gradients below) and a bf16 copy of the readout gradient
+                cp = self._bf16_copies(ws, T, B, convert=() if save.get('bf16_hw_done') else ('h', 'w'))
+                ws['bf16_hw_fresh'] = True
+                d16 = save['d16'] if 'd16' in save else ops.to_bf16(dread)
+                for l in range(L):
+                    ops.gemm_bf16in(cp['h'][l][1:T + 1].view(T * B, H), d16, gWr[l * H:(l + 1) * H], accumulate=True)
+                ops.gemm_bf16in(cp['w'][1:T + 1].view(T * B, E), d16, gWr[L * H:], accumulate=True)
+                return
+            for l in range(L):
+                ops.gemm(ws['h'][l][1:].view(T * B, H).t(), dro[l], out=gWr[l * H:(l + 1) * H], accumulate=True)
+            ops.gemm(ws['w'][1:].view(T * B, E).t(), dread, out=gWr[L * H:], accumulate=True)
+        for l in range(L):
+            self._g(f'/h{l + 1}_to_readout.b').add_(ops.colsum(dro[l]) if self.layer_norm else db)
+        self._g('/att_to_readout.b').add_(db)
+        if self.use_speaker:
+            dsum = dread.view(T, B, R).sum(0)
+            ops.gemm(emb_spk.t(), dsum, out=self._g('/speaker_to_readout.W'), accumulate=True)
+            ops.colsum(dsum, out=self._g('/speaker_to_readout.b'), accumulate=True)
+            ops.gemm(dsum, self._p('/speaker_to_readout.W').t(), out=demb_spk, accumulate=True)
+        # gradients entering the scan through the readouts
+        if 'Wr16' in save:  # bf16-operand decoders: dread . Wr^T on the bf16 copies (one copy of dread, shared with gWr)
+            Wr16 = save['Wr16']
+            d16 = save['d16'] = ops.to_bf16(dread)
+            for l in range(L):
+                ws['dh'][l][0].zero_()
+                ops.gemm16(d16, Wr16[l * H:(l + 1) * H].t(), out=ws['dh'][l][1:].view(T * B, H))
+            ws['dw'][0].zero_()
+            ops.gemm16(d16, Wr16[L * H:].t(), out=ws['dw'][1:].view(T * B, E))
+        else:
+            for l in range(L):
+                ws['dh'][l][0].zero_()
+                ops.gemm(dro[l], Wr[l * H:(l + 1) * H].t(), out=ws['dh'][l][1:].view(T * B, H))
+            ws['dw'][0].zero_()
+            ops.gemm(dread, Wr[L * H:].t(), out=ws['dw'][1:].view(T * B, E))
+        return readout_weight_grads
 
     def _weight_grad_rows(self, ws, save, T, B, t0, t1):
         """Deferred weight gradients of the scan for the steps [t0, t1): dW += X[t0:t1]^T . dPre[t0:t1] over the
