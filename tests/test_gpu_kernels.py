@@ -288,38 +288,170 @@ def test_lstm_seq_fwd_bwd(dev, T, B, H):
         assert_close(t.grad, r.grad, 1e-4, n)
 
 
-@pytest.mark.parametrize("att_type", ["graves", "softmax"])
-@pytest.mark.parametrize("B,H,A,U,E", [(4, 64, 10, 23, 32), (64, 256, 10, 200, 256), (3, 40, 5, 17, 420)])
-def test_attention_fwd_bwd(dev, att_type, B, H, A, U, E):
-    from oracle import parrot_ref as R
-    from parrot_amd import ops
-    cfg = R.default_config(attention_type=att_type, attention_size=A, sharpening_coeff=1.3, timing_coeff=0.8,
-                           attention_alignment=0.7)
+# ---- GMM-window attention step (att_fwd_kernel / att_bwd_kernel through the C ABI) -----------------------------------
+ATT_EPS, ATT_ALIGN, ATT_SHARP, ATT_TIMING = 1e-5, 0.7, 1.3, 0.8
+ATT_TOL = dict(a=1e-5, kappa=1e-5, phi=2e-5, w=2e-5, dh1=1e-4, dkappa=1e-4, dp=1e-4)
+ATT_SHAPES = [  # (B, H, A, U, E)
+    (4, 64, 10, 23, 32), (64, 256, 10, 200, 256), (3, 40, 5, 17, 420),
+    (2, 1100, 5, 40, 64),    # pvec, H % 256 != 0 and H > 1024: second k0 pass + the H - 4 clamp; dh1 fallback loop
+    (2, 1536, 10, 40, 64),   # scalar projection at the shipped width; dh1 fallback loop
+    (3, 72, 11, 30, 48),     # 3A = 33: second jb pass forward, no wpre backward
+    (2, 64, 32, 20, 32),     # A = ATT_MAXA
+    (2, 64, 1, 20, 32),      # A = 1
+    (3, 30, 5, 128, 32),     # P = 2 (two threads per position); H % 4 != 0: pvec off by alignment
+    (3, 30, 5, 129, 32),     # P = 1
+    (2, 64, 10, 300, 40),    # two passes of the phi loop; backward without the context preload (U > 256)
+    (1, 64, 10, 1, 32),      # U = 1
+    (2, 64, 10, 23, 33),     # E odd, CW > EW
+    (2, 64, 10, 23, 1100),   # E > 1024: second pass of the dw staging loop; ragged column passes forward
+]
+
+
+def _att_inputs(dev, B, H, A, U, E):
     h1 = _rand((B, H), dev, 1)
     Watt = _rand((H, 3 * A), dev, 2, 0.5 / math.sqrt(H))
     batt = _rand((3 * A,), dev, 3, 0.1)
     kprev = _rand((B, A), dev, 4).abs() * 3
     ctx = _rand((B, U, E), dev, 5)
-    at = 1 if att_type == "softmax" else 0
-    WattT = Watt.t().contiguous()
-    a, b, k, phi, w = ops.gmm_attention_fwd(h1, WattT, batt, kprev, ctx, at, 1e-5, 0.7, 1.3, 0.8)
-    rh1, rW, rb, rk, rctx = (t.double().cpu().requires_grad_() for t in (h1, Watt, batt, kprev, ctx))
-    p = rh1 @ rW + rb
-    ra, rkk, rphi, rw = R.attention_step(cfg, p[:, :A], p[:, A:2 * A], p[:, 2 * A:], rk, rctx, sampling=True)
-    assert_close(a, ra, 1e-5, "a")
-    assert_close(k, rkk, 1e-5, "kappa")
-    assert_close(phi, rphi, 2e-5, "phi")
-    assert_close(w, rw, 2e-5, "w")
-    # backward: L = sum(w * gw) + sum(kappa * gk)
     gw = _rand((B, E), dev, 6)
     gk = _rand((B, A), dev, 7)
-    ((rw * gw.double().cpu()).sum() + (rkk * gk.double().cpu()).sum()).backward()
-    dkappa = gk.clone()
-    dh1 = torch.zeros(B, H, device=dev)
-    dp = ops.gmm_attention_bwd(gw, ctx, a, b, k, kprev, WattT, dkappa, dh1, at, 1e-5)
-    assert_close(dh1, rh1.grad, 1e-4, "dh1")
-    assert_close(dkappa, rk.grad, 1e-4, "dkappa_prev")
-    assert_close(dp.sum(0), rb.grad, 1e-4, "dp (bias grad)")
+    return dict(h1=h1, Watt=Watt, batt=batt, kprev=kprev, ctx=ctx, gw=gw, gk=gk)
+
+
+def _att_reference(att_type, x, dtype=torch.float64):
+    """The oracle's attention step + autograd on the CPU in `dtype`: outputs, and the gradients of
+    L = sum(w * gw) + sum(kappa * gk) with respect to h1, kappa_prev and the projection p itself."""
+    from oracle import parrot_ref as R
+    A = x['kprev'].shape[1]
+    cfg = R.default_config(attention_type=att_type, attention_size=A, sharpening_coeff=ATT_SHARP, timing_coeff=ATT_TIMING,
+                           attention_alignment=ATT_ALIGN, epsilon=ATT_EPS)
+    rh1, rW, rb, rk, rctx = (x[n].detach().to(dtype).cpu().requires_grad_() for n in ('h1', 'Watt', 'batt', 'kprev', 'ctx'))
+    p = rh1 @ rW + rb
+    p.retain_grad()
+    ra, rkk, rphi, rw = R.attention_step(cfg, p[:, :A], p[:, A:2 * A], p[:, 2 * A:], rk, rctx, sampling=True)
+    ((rw * x['gw'].to(dtype).cpu()).sum() + (rkk * x['gk'].to(dtype).cpu()).sum()).backward()
+    return dict(a=ra.detach(), kappa=rkk.detach(), phi=rphi.detach(), w=rw.detach(), dh1=rh1.grad, dkappa=rk.grad,
+                dp=p.grad, dbatt=rb.grad)
+
+
+def _att_kernels(att_type, x, monkeypatch=None, dense=None):
+    """Forward and backward step through the C ABI; `dense` sets PARROT_ATT_DENSE (read per launch)."""
+    from parrot_amd import ops
+    if dense is not None:
+        monkeypatch.setenv("PARROT_ATT_DENSE", "1" if dense else "0")
+    at = 1 if att_type == "softmax" else 0
+    WattT = x['Watt'].t().contiguous()
+    a, b, k, phi, w = ops.gmm_attention_fwd(x['h1'], WattT, x['batt'], x['kprev'], x['ctx'], at, ATT_EPS, ATT_ALIGN,
+                                            ATT_SHARP, ATT_TIMING)
+    dkappa = x['gk'].clone()  # the carry that comes in
+    dh1 = torch.zeros_like(x['h1'])
+    dp = ops.gmm_attention_bwd(x['gw'], x['ctx'], a, b, k, x['kprev'], WattT, dkappa, dh1, at, ATT_EPS)
+    return dict(a=a, b=b, kappa=k, phi=phi, w=w, dh1=dh1, dkappa=dkappa, dp=dp)
+
+
+def _att_parity(got, ref, what, tol=None):
+    tol = {**ATT_TOL, 'dbatt': ATT_TOL['dp'], **(tol or {})}
+    errs = {n: rel_err(got[n], ref[n]) for n in ATT_TOL}
+    errs['dbatt'] = rel_err(got['dp'].sum(0), ref['dbatt'])  # the check of earlier rounds: dp's column sums
+    print(f"attention {what}: " + " ".join(f"{n}={e:.2e}" for n, e in errs.items()))
+    for n, e in errs.items():
+        assert e <= tol[n], f"{what} {n}: relative error {e:.3e} > {tol[n]:.1e}"
+    return errs
+
+
+@pytest.mark.parametrize("att_type", ["graves", "softmax"])
+@pytest.mark.parametrize("B,H,A,U,E", ATT_SHAPES)
+def test_attention_fwd_bwd(dev, monkeypatch, att_type, B, H, A, U, E):
+    """One attention step, forward and backward, against the fp64 oracle (R.attention_step + autograd) at the shapes where
+    the kernels branch.  Thresholds (att_fwd_body.h at 256 threads, att_bwd_body.h) and the shape that crosses each:
+      * forward projection: `pvec` on for 3A <= 16, H % 4 == 0: (.., 1100, 5, ..) takes it with a second k0 pass and the
+        min(k, H - 4) clamp, H = 30 turns it off by alignment, A = 10 / 11 / 32 take the scalar path, 3A = 33 and
+        A = 32 its second `jb` pass;
+      * forward phi: two threads per position iff U <= 128 (U = 128 | 129), second `base` pass for U = 300, U = 1;
+      * forward w: E = 33 (CW = 64 > EW), E = 420 and E = 1100 (several column passes, the last one ragged);
+      * backward dphi: register preload for U <= 256 and E <= 256, off for U = 300, E = 420, E = 1100;
+      * backward dh1: column preload for H <= 1024 and 3A <= 32, fallback loop for H = 1100, 1536 and for 3A = 33;
+      * backward dw staging: second pass for E = 1100.
+    Every output is compared, `dp` row by row against the gradient of the projection (not only its column sums), and the
+    forward step reading only the window's support equals the one reading every context row bit for bit.
+    The window-placement cases (windows at the edges of the text and past it) are in test_attention_window_placements."""
+    x = _att_inputs(dev, B, H, A, U, E)
+    ref = _att_reference(att_type, x)
+    got = _att_kernels(att_type, x, monkeypatch, dense=False)
+    _att_parity(got, ref, f"{att_type} {(B, H, A, U, E)}")
+    dense = _att_kernels(att_type, x, monkeypatch, dense=True)
+    for n in ("phi", "w", "a", "b", "kappa"):
+        assert torch.equal(got[n], dense[n]), f"support vs dense: {n}"
+
+
+def _place_windows(att_type, x, U):
+    """kappa_prev per row for test_attention_window_placements.  Rows 3 and 4 need kappa itself (not kappa_prev) at a
+    distance from the edge that depends on each mixture's width: the step kappa - kappa_prev and b are taken from the
+    fp64 restatement of the projection (inputs only).  exp(-x) is exactly 0.0f for x > 104: the neighbour of the surviving
+    position is put at x = 110, which leaves the survivor at x = (sqrt(110) - sqrt(b'))^2 < 80 for every b' > 2.4."""
+    B, A = x['kprev'].shape
+    p = x['h1'].double().cpu() @ x['Watt'].double().cpu() + x['batt'].double().cpu()
+    step = ATT_ALIGN * torch.exp(p[:, 2 * A:]) / ATT_TIMING
+    beff = (torch.exp(p[:, A:2 * A]) * ATT_SHARP + ATT_EPS) * (0.5 if att_type == "softmax" else 1.0)
+    k = x['kprev'].double().cpu().clone()       # rows 6, 7: random as in test_attention_fwd_bwd
+    k[0] = U / 2.0 - step[0]                    # the middle of the text
+    k[1] = U + 15.0                             # past the text: empty support
+    k[2] = -15.0                                # empty on the left
+    k[3] = 1.0 - torch.sqrt(110.0 / beff[3]) - step[3]          # only u = 0 survives
+    k[4] = U - 2.0 + torch.sqrt(110.0 / beff[4]) - step[4]      # only u = U - 1 survives
+    k[5, :A // 2] = 2.0 - step[5, :A // 2]      # two groups of mixtures with exact zeros between them
+    k[5, A // 2:] = U - 3.0 - step[5, A // 2:]
+    return k.float()
+
+
+# Gradient bounds of the U = 200 placement batch: 4 x the error of the SAME formulas evaluated in float32 with torch on the
+# CPU against the fp64 reference (_att_reference(..., torch.float32); measured: graves dh1 1.514e-4, dkappa 3.878e-4,
+# dp 1.275e-4, dp's column sums 1.615e-4; softmax 1.288e-4, 2.198e-4, 1.689e-4, 1.937e-4 -- all of it from row 5, whose
+# narrow mixtures sit at kappa = 197: kappa - u loses 7 bits there and b (kappa - u)^2 amplifies that at the tails of the
+# window).  Float32 itself misses the 1e-4 of the other shapes here; the factor 4 is for the other summation order and an
+# expf that is not correctly rounded.  The forward outputs keep their bounds; so does everything at U = 23 (float32 there:
+# dh1 7.1e-6, dkappa 1.7e-5, dp 5.7e-6).
+PLACEMENT_TOL = {
+    ("graves", 200): dict(dh1=4 * 1.514e-4, dkappa=4 * 3.878e-4, dp=4 * 1.275e-4, dbatt=4 * 1.615e-4),
+    ("softmax", 200): dict(dh1=4 * 1.288e-4, dkappa=4 * 2.198e-4, dp=4 * 1.689e-4, dbatt=4 * 1.937e-4),
+}
+
+
+@pytest.mark.parametrize("att_type", ["graves", "softmax"])
+@pytest.mark.parametrize("B,H,A,U,E", [(8, 64, 10, 23, 32), (8, 64, 10, 200, 256)])
+def test_attention_window_placements(dev, monkeypatch, att_type, B, H, A, U, E):
+    """One batch whose rows put the window in the middle of the text, past its end, before its start, on its first and on
+    its last position alone, in two groups with exact zeros between them, and at random; narrow windows (beta_hat + 3).
+    Oracle parity on every output at the tolerances of test_attention_fwd_bwd (the gradients at U = 200: PLACEMENT_TOL,
+    from the float32 evaluation of the reference); a row whose fp64 phi stays below 1e-60 has
+    phi and w exactly 0.0 from the kernel, passes its kappa carry through unchanged and has exactly zero gradients for
+    alpha_hat and beta_hat; reading only the support equals reading every row bit for bit."""
+    x = _att_inputs(dev, B, H, A, U, E)
+    x['batt'] = x['batt'].clone()
+    x['batt'][A:2 * A] += 3.0
+    x['kprev'] = _place_windows(att_type, x, U).to(dev)
+    ref = _att_reference(att_type, x)
+    top = ref['phi'].amax(1)
+    dead = top < 1e-60
+    # premises, from the reference alone
+    assert int(dead.sum()) >= 2 and bool(dead[1]) and bool(dead[2]) and int((top > 1e-3).sum()) >= 1
+    assert float(ref['phi'][3, 0]) > 1e-40 and float(ref['phi'][3, 1:].max()) < 5e-46
+    assert float(ref['phi'][4, U - 1]) > 1e-40 and float(ref['phi'][4, :U - 1].max()) < 5e-46
+    assert float(ref['phi'][5, 9:U - 9].max()) < 1e-60 and float(ref['phi'][5, :9].max()) > 1e-3 \
+        and float(ref['phi'][5, U - 9:].max()) > 1e-3
+    got = _att_kernels(att_type, x, monkeypatch, dense=False)
+    _att_parity(got, ref, f"placements {att_type} {(B, H, A, U, E)}", PLACEMENT_TOL.get((att_type, U)))
+    for r in torch.nonzero(dead).flatten().tolist():
+        assert float(got['phi'][r].abs().max()) == 0.0 and float(got['w'][r].abs().max()) == 0.0, r
+        assert float(got['dp'][r, :2 * A].abs().max()) == 0.0, r
+        assert torch.equal(got['dkappa'][r], x['gk'][r]), r
+    # single survivors: the support is one position wide
+    assert float(got['phi'][3, 0]) > 0.0 and float(got['phi'][3, 1:].abs().max()) == 0.0
+    assert float(got['phi'][4, U - 1]) > 0.0 and float(got['phi'][4, :U - 1].abs().max()) == 0.0
+    assert float(got['phi'][5, 9:U - 9].abs().max()) == 0.0
+    dense = _att_kernels(att_type, x, monkeypatch, dense=True)
+    for n in ("phi", "w", "a", "b", "kappa"):
+        assert torch.equal(got[n], dense[n]), f"support vs dense: {n}"
 
 
 def test_quantize_bit_exact(dev):

@@ -13,22 +13,26 @@ pytestmark = pytest.mark.gpu
 SMALL = dict(rnn_h_dim=64, readouts_dim=48, encoder_dim=16, input_dim=24, speaker_dim=8, num_speakers=5)
 
 
-def _build(dev, use_graph=False, **kw):
+def _build(dev, use_graph=False, param_overrides=None, **kw):
+    """param_overrides: parameter name -> value the whole parameter is filled with (oracle and HIP model alike)."""
     from oracle import parrot_ref as R
     from parrot_amd.model import Parrot
     base = dict(SMALL)
     base.update(kw)
     cfg = R.default_config(**base)
     p = R.init_params(cfg, seed=7, scale_by_fan_in=True)
+    for name, value in (param_overrides or {}).items():
+        p[name].fill_(value)
     kw2 = {k: v for k, v in base.items()}
     m = Parrot(device=dev, use_graph=use_graph, **kw2).allocate()
     m.set_parameter_values(p)
     return cfg, p, m
 
 
-def _check_cost_and_grads(dev, T, B, U, ragged=False, tol_out=1e-4, tol_grad=1e-3, expect_schedule=None, **kw):
+def _check_cost_and_grads(dev, T, B, U, ragged=False, tol_out=1e-4, tol_grad=1e-3, expect_schedule=None,
+                          param_overrides=None, **kw):
     from oracle import parrot_ref as R
-    cfg, p, m = _build(dev, **kw)
+    cfg, p, m = _build(dev, param_overrides=param_overrides, **kw)
     feat, fm, lab, lm, spk = make_batch(cfg, T, B, U, seed=3, ragged=ragged, speaker=cfg['use_speaker'])
     for v in p.values():
         v.requires_grad_()
