@@ -623,6 +623,32 @@ int parrot_softmax_ce_bwd(const float* logits, int ld, const int* target, const 
                           long long rows, int Q, float* dlogits, int ldd, void* stream);
 int parrot_relu_gate(const float* dy, const float* gate, float* out, long long n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mixture-density head of the training step (parrot_amd/csrc/gmmcost.hip): the Gaussian-mixture negative log-likelihood
+ * (model.py:65-91) on the PRE-ACTIVATIONS of the three output heads (model.py:774-781) and its gradient, one pass over
+ * the rows each way.  Row m, column o*K + k of mu / sig_hat (the order of ParrotSampleDesc::Wmu):
+ *   sig_ok = exp(sig_hat_ok) + eps,   pi_k = softmax(co_hat)_k + eps,
+ *   a_k    = log pi_k - 1/2 sum_o [ (y_o - mu_ok)^2 / sig_ok^2 + 2 log sig_ok + log 2 pi ]
+ *   parrot_gmm_cost_fwd:  nll[m] = -logsumexp_k a_k (max-shifted, model.py:37-41),  pi_out[m,k] = pi_k (may be NULL),
+ *                         logr[m,k] = a_k + nll[m]  (log responsibility; [M, K] contiguous, saved for the backward call)
+ *   parrot_gmm_cost_bwd:  with r_k = exp(logr[m,k]), p = softmax(co_hat), q_k = -r_k / pi_k:
+ *                         dmu[m,ok]      = rowscale[m] * ( - r_k (y_o - mu_ok) / sig_ok^2 )
+ *                         dsig_hat[m,ok] = rowscale[m] * r_k (1 / sig_ok - (y_o - mu_ok)^2 / sig_ok^3) exp(sig_hat_ok)
+ *                         dco_hat[m,j]   = rowscale[m] * p_j (q_j - sum_k p_k q_k)
+ * rowscale is a device array [M] (mask, mask sum and upstream gradient folded in by the caller; no host read).  Leading
+ * dimensions in floats, at least the row's width; no alignment beyond 4 bytes.  The gradients' address ranges may overlap
+ * neither an input's nor each other's (PARROT_ERR_BADARG).  A row with rowscale[m] == 0 gets gradient rows of exactly 0.0
+ * whatever its operands hold.
+ * M, O, K >= 1; K > 64 is PARROT_ERR_UNSUPPORTED.  No allocation, no synchronisation, no atomics: the same bits every run.
+ * ------------------------------------------------------------------------------------------ */
+int parrot_gmm_cost_fwd(const float* y, int ldy, const float* mu, int ldmu, const float* sig_hat, int ldsig,
+                        const float* co_hat, int ldco, long long M, int O, int K, float eps, float* nll, float* pi_out,
+                        int ldpi, float* logr, void* stream);
+int parrot_gmm_cost_bwd(const float* y, int ldy, const float* mu, int ldmu, const float* sig_hat, int ldsig,
+                        const float* co_hat, int ldco, const float* logr, const float* rowscale, long long M, int O, int K,
+                        float eps, float* dmu, int lddmu, float* dsig_hat, int lddsig, float* dco_hat, int lddco,
+                        void* stream);
+
 /* Weight-norm fold of a SampleRNN Linear (sampleRNN/lib/ops.py:101-110: `W * (g / W.norm(2, axis=0))`), SURVEY 8b's K9:
  *   samplernn_weightnorm_fold:      W_eff[k][n] = W[k][n] * g[n] / ||W[:, n]||_2;  norm[n] = ||W[:, n]||_2 (may be NULL)
  *   samplernn_weightnorm_fold_bwd:  dg[n] (+)= sum_k dW_eff[k][n] W[k][n] / norm[n]

@@ -175,6 +175,8 @@ SIGNATURES = {
     "parrot_softmax_ce_fwd": (_i, [_vp, _i, _vp, _ll, _i, _vp, _vp, _vp]),
     "parrot_softmax_ce_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _ll, _i, _vp, _i, _vp]),
     "parrot_relu_gate": (_i, [_vp, _vp, _vp, _ll, _vp]),
+    "parrot_gmm_cost_fwd": (_i, [_vp, _i] * 4 + [_ll, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "parrot_gmm_cost_bwd": (_i, [_vp, _i] * 4 + [_vp, _vp, _ll, _i, _i, _f] + [_vp, _i] * 3 + [_vp]),
     "samplernn_weightnorm_ws_floats": (_ll, [_i]),
     "samplernn_weightnorm_fold": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "samplernn_weightnorm_fold_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -44,6 +44,8 @@
 // PARROT_WS_CACHE          6        alloc    workspace / plan cache entries per shape (at least 4)           development
 // PARROT_READOUT_COMPOSED  1        step     0: readouts and output layer as separate full-width products    tests, tools
 //                                            (the path of GMM / layer_norm / speaker / bf16 models anyway)
+// PARROT_GMM_COST_FUSED    1        step     0: GMM head cost and gradient as torch element-wise code         tests, tools
+//                                            (the path of raw_output and k_gmm > 64 models anyway)
 // PARROT_BF16_DW           1        step     0: bf16 decoders' weight gradients from f32 operands            tests
 // PARROT_BF16_READOUT      1        step     0: bf16 decoders' readout stack on f32 operands                 tests, tools
 // PARROT_BF16_DG16         1        alloc    0: LSTM backward scan leaves f32 pre-activation gradients       tools

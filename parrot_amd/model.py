@@ -807,9 +807,21 @@ class Parrot(Brick):
             preds = self._readouts_factored(ws, save, T, B, emb_spk)
 
         # --- masked cost (model.py:757-784); small [T,B,O] elementwise math with local autograd
-        leafs = [p.detach().requires_grad_(True) for p in preds]
+        gmm_fused = self._gmm_cost_fused()
+        self._gmm_cost_path = None if self.which_cost != 'GMM' else ('fused' if gmm_fused else 'torch')
+        leafs = [] if gmm_fused else [p.detach().requires_grad_(True) for p in preds]
         with torch.enable_grad():
-            if self.which_cost == 'MSE':
+            if gmm_fused:
+                # the mixture-density head in one HIP pass over the pre-activations (csrc/gmmcost.hip): no [T*B, O, K]
+                # temporaries; logr (the log responsibilities) is what the backward pass needs
+                M = T * B
+                tgt, heads = target.reshape(M, O), [p.view(M, -1) for p in preds]
+                nll, pi, logr = ops.gmm_cost_fwd(tgt, *heads, self.epsilon)
+                mrow, msum = mask.view(M), mask.sum() + 1e-5
+                cost_val = (nll * mrow).sum() / msum
+                save['gmm'] = (tgt, heads, logr, mrow / msum)
+                next_x, coeff = preds[0], pi.view(T, B, self.k_gmm)
+            elif self.which_cost == 'MSE':
                 cost_tb = ((leafs[0] - target) ** 2).sum(-1)
                 next_x, coeff = preds[0], preds[0]
             else:
@@ -817,7 +829,8 @@ class Parrot(Brick):
                 coeff_ = torch.softmax(leafs[2], -1) + self.epsilon
                 cost_tb = cost_gmm(target, leafs[0], sigma, coeff_)
                 next_x, coeff = preds[0], coeff_.detach()  # sampled next_x is stochastic in the reference
-            cost_val = (cost_tb * mask).sum() / (mask.sum() + 1e-5)
+            if not gmm_fused:
+                cost_val = (cost_tb * mask).sum() / (mask.sum() + 1e-5)
         cost_raw = None
         if self.raw_output:
             # model.py:793-820: the SampleRNN head is trained on the predicted frames; the reference sets
@@ -834,7 +847,7 @@ class Parrot(Brick):
             save['torch_cost'] = total
             save['leafs'] = leafs
             cost_val = total.detach()
-        else:
+        elif not gmm_fused:  # (the fused head's gradients are computed in the backward pass, already scaled)
             dpreds = torch.autograd.grad(cost_val, leafs)
             save['dpreds'] = [d.reshape(T * B, -1).contiguous() for d in dpreds]
 
@@ -916,6 +929,27 @@ class Parrot(Brick):
                 and self.readouts_dim >= 256 and H % 16 == 0 and E % 16 == 0
                 and env_int('PARROT_READOUT_COMPOSED', 1) != 0)
 
+    # ------------------------------------------------------------------ mixture-density head
+    @property
+    def gmm_cost_path(self):
+        """'fused' or 'torch': how the last compute_cost() ran the GMM head's cost and gradient (None before the first
+        call and for MSE models)."""
+        return getattr(self, '_gmm_cost_path', None)
+
+    def _gmm_cost_fused(self):
+        """True when the GMM head's cost and gradient run as the two HIP kernels of csrc/gmmcost.hip: a GMM model that
+        does not train a SampleRNN head on the predicted frames (raw_output keeps its torch graph through the leafs) with
+        at most 64 components.  PARROT_GMM_COST_FUSED=0 (read per step) keeps the torch element-wise path."""
+        return (self.which_cost == 'GMM' and not self.raw_output and self.k_gmm <= 64
+                and env_int('PARROT_GMM_COST_FUSED', 1) != 0)
+
+    def _gmm_grad_buffers(self, ws, T, B):
+        """(dmu, dsig_hat, dco_hat) of the fused head, made once per training workspace."""
+        if 'gmm_grads' not in ws:
+            ws['gmm_grads'] = tuple(torch.empty(T * B, d, device=self._dev(), dtype=torch.float32)
+                                    for _, _, d in self._out_names)
+        return ws['gmm_grads']
+
     def _readouts_buffer(self, ws, T, B):
         if 'readouts' not in ws:
             ws['readouts'] = torch.empty(T * B, self.readouts_dim, device=self._dev(), dtype=torch.float32)
@@ -977,6 +1011,13 @@ class Parrot(Brick):
             save['dpreds'] = [(l.grad if l.grad is not None else torch.zeros_like(l)).reshape(T * B, -1).contiguous()
                               for l in leafs]
             gscale = torch.ones((), device=gscale.device)
+        if 'gmm' in save:
+            # fused mixture-density head: mask / (sum mask + 1e-5) and the upstream gradient enter the kernel as one factor
+            # per row (a device array: gscale is never read on the host), so the three gradients arrive scaled
+            tgt, heads, logr, mrow = save['gmm']
+            save['dpreds'] = ops.gmm_cost_bwd(tgt, *heads, logr, (mrow * gscale.to(torch.float32)).contiguous(),
+                                              self.epsilon, out=self._gmm_grad_buffers(ws, T, B))
+            gscale = None  # (nothing left to scale in _readouts_factored_bwd)
         if save['readout_composed']:
             # dh_l / dw (slot 0 zero-filled in the same launch) and every gradient of the readout stack and the output layer
             # through the composed map, final before the backward scan starts (csrc/readout.hip)
@@ -1068,7 +1109,7 @@ class Parrot(Brick):
         # output layer
         dread = torch.empty(T * B, R, device=readouts.device, dtype=torch.float32)  # (the first head's product stores: no fill)
         for i, (wn, bn, dim) in enumerate(self._out_names):
-            dp = save['dpreds'][i] * gscale
+            dp = save['dpreds'][i] if gscale is None else save['dpreds'][i] * gscale
             ops.gemm(readouts.t(), dp, out=self.store.grad(wn), accumulate=True)
             ops.colsum(dp, out=self.store.grad(bn), accumulate=True)
             ops.gemm(dp, self.store.param(wn).t(), out=dread, accumulate=i > 0)

@@ -427,6 +427,90 @@ def softmax_ce(logits, target):
     return _SoftmaxCeFn.apply(logits, target)
 
 
+def _gmm_rows(y, mu, sig_hat, co_hat):
+    """Shape check of the mixture-density head's operands: y [M, O], mu / sig_hat [M, O*K], co_hat [M, K], f32 GPU tensors
+    with unit column stride (any row stride).  Returns (M, O, K)."""
+    for t, n in ((y, "y"), (mu, "mu"), (sig_hat, "sig_hat"), (co_hat, "co_hat")):
+        _chk(t, n)
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError(f"gmm_cost: {n} must be 2-D with unit column stride")
+    (M, O), K = y.shape, co_hat.shape[1]
+    if M < 1 or O < 1 or K < 1:
+        raise ValueError("gmm_cost: empty operand")
+    if mu.shape != (M, O * K) or sig_hat.shape != (M, O * K) or co_hat.shape[0] != M:
+        raise ValueError(f"gmm_cost: y [M, O], mu / sig_hat [M, O*K], co_hat [M, K] expected, got {tuple(y.shape)}, "
+                         f"{tuple(mu.shape)}, {tuple(sig_hat.shape)}, {tuple(co_hat.shape)}")
+    return M, O, K
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def gmm_cost_fwd(y, mu, sig_hat, co_hat, eps, pi_out=None):
+    """Gaussian-mixture negative log-likelihood per row (model.py:65-91 on the heads' pre-activations, :774-781), one HIP
+    pass.  Returns (nll [M], pi [M, K] = softmax(co_hat) + eps, logr [M, K]); logr goes to gmm_cost_bwd."""
+    M, O, K = _gmm_rows(y, mu, sig_hat, co_hat)
+    nll = torch.empty(M, device=y.device, dtype=torch.float32)
+    logr = torch.empty(M, K, device=y.device, dtype=torch.float32)
+    if pi_out is None:
+        pi_out = torch.empty(M, K, device=y.device, dtype=torch.float32)
+    _chk(pi_out, "pi_out")
+    if pi_out.shape != (M, K) or pi_out.stride(1) != 1:
+        raise ValueError("gmm_cost_fwd: pi_out must be [M, K] with unit column stride")
+    _lib.call("parrot_gmm_cost_fwd", y.data_ptr(), _ld(y), mu.data_ptr(), _ld(mu), sig_hat.data_ptr(), _ld(sig_hat),
+              co_hat.data_ptr(), _ld(co_hat), M, O, K, float(eps), nll.data_ptr(), pi_out.data_ptr(), _ld(pi_out),
+              logr.data_ptr(), _stream())
+    return nll, pi_out, logr
+
+
+def gmm_cost_bwd(y, mu, sig_hat, co_hat, logr, rowscale, eps, out=None):
+    """Gradient of gmm_cost_fwd's nll wrt mu, sig_hat and co_hat, every row times rowscale[m] (a device array), one HIP
+    pass.  out = (dmu, dsig_hat, dco_hat) to write into (unit column stride, not aliasing the inputs)."""
+    M, O, K = _gmm_rows(y, mu, sig_hat, co_hat)
+    _chk(logr, "logr"); _chk(rowscale, "rowscale")
+    if logr.shape != (M, K) or not logr.is_contiguous():
+        raise ValueError("gmm_cost_bwd: logr must be the contiguous [M, K] array of gmm_cost_fwd")
+    if rowscale.numel() != M or not rowscale.is_contiguous():
+        raise ValueError("gmm_cost_bwd: one rowscale per row expected")
+    if out is None:
+        out = (torch.empty(M, O * K, device=y.device, dtype=torch.float32),
+               torch.empty(M, O * K, device=y.device, dtype=torch.float32),
+               torch.empty(M, K, device=y.device, dtype=torch.float32))
+    dmu, dsig, dco = out
+    for t, n, w in ((dmu, "dmu", O * K), (dsig, "dsig_hat", O * K), (dco, "dco_hat", K)):
+        _chk(t, n)
+        if t.shape != (M, w) or t.stride(1) != 1:
+            raise ValueError(f"gmm_cost_bwd: {n} must be [M, {w}] with unit column stride")
+    _lib.call("parrot_gmm_cost_bwd", y.data_ptr(), _ld(y), mu.data_ptr(), _ld(mu), sig_hat.data_ptr(), _ld(sig_hat),
+              co_hat.data_ptr(), _ld(co_hat), logr.data_ptr(), rowscale.data_ptr(), M, O, K, float(eps),
+              dmu.data_ptr(), _ld(dmu), dsig.data_ptr(), _ld(dsig), dco.data_ptr(), _ld(dco), _stream())
+    return dmu, dsig, dco
+
+
+class _GmmNllFn(torch.autograd.Function):
+    """nll [M] of the mixture-density head; the incoming gradient is the kernel's rowscale.  y gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, y, mu, sig_hat, co_hat, eps):
+        nll, _, logr = gmm_cost_fwd(y, mu, sig_hat, co_hat, eps)
+        ctx.save_for_backward(y, mu, sig_hat, co_hat, logr)
+        ctx.eps = eps
+        return nll
+
+    @staticmethod
+    def backward(ctx, g):
+        y, mu, sig_hat, co_hat, logr = ctx.saved_tensors
+        g = g.reshape(-1).to(torch.float32).contiguous()
+        dmu, dsig, dco = gmm_cost_bwd(y, mu, sig_hat, co_hat, logr, g, ctx.eps)
+        return None, dmu, dsig, dco, None
+
+
+def gmm_nll(y, mu, sig_hat, co_hat, eps):
+    """Per-row Gaussian-mixture negative log-likelihood [M] with autograd through the two HIP kernels (csrc/gmmcost.hip)."""
+    return _GmmNllFn.apply(y, mu, sig_hat, co_hat, eps)
+
+
 class _WeightNormFn(torch.autograd.Function):
     """W_eff = W * (g / ||W||_2 per output column) (sampleRNN/lib/ops.py:101-110): one HIP pass each way."""
 

@@ -9,7 +9,10 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
-  bench_extra.py --reps N                on / off alternations of the LSTM decode entries (default 3)"""
+  bench_extra.py --reps N                on / off alternations of the LSTM decode entries (default 3)
+  bench_extra.py --gmm_head [--reps N]   this leg alone: the GMM head's cost and gradient, fused HIP kernels against the torch
+                                         path (head alone at M = 51 200, O = 63, K = 20 and the configs[1] training step with
+                                         that head; N >= 5 alternations, bytes moved, TB/s, peak memory)"""
 import json
 import os
 import subprocess
@@ -116,6 +119,116 @@ def decode_stop(kappa_bias, reps):
     m.close()
     return res
 
+
+def gmm_head(reps):
+    """The mixture-density head (which_cost='GMM', k_gmm=20) at the benchmark shape, the fused HIP kernels
+    (PARROT_GMM_COST_FUSED=1) against the torch element-wise path (=0), alternating in one process: the head alone
+    (forward + backward, device events) at M = 51 200, O = 63, K = 20, and the full training step of BASELINE configs[1]
+    with that head.  Every repetition is listed; the spread is max - min of a path's repetitions."""
+    from parrot_amd import ops
+    from parrot_amd.model import Parrot, cost_gmm
+    from parrot_amd.trainer import Trainer
+    T, B, U, O, K, eps = 800, 64, 200, 63, 20, 1e-5
+    M = T * B
+    gen = torch.Generator().manual_seed(0)
+    y, mu, co = (torch.randn(M, w, generator=gen).to(dev) for w in (O, O * K, K))
+    sh = (0.5 * torch.randn(M, O * K, generator=gen)).to(dev)
+    mask = torch.ones(M, device=dev)
+    gscale = torch.ones((), device=dev)
+    bufs = tuple(torch.empty(M, w, device=dev) for w in (O * K, O * K, K))
+
+    def head_fused():
+        nll, pi, logr = ops.gmm_cost_fwd(y, mu, sh, co, eps)
+        msum = mask.sum() + 1e-5
+        cost = (nll * mask).sum() / msum
+        return cost, ops.gmm_cost_bwd(y, mu, sh, co, logr, (mask / msum * gscale).contiguous(), eps, out=bufs)
+
+    def head_torch():  # Parrot.compute_cost's torch path and the copies of _readouts_factored_bwd
+        leafs = [t.detach().requires_grad_(True) for t in (mu, sh, co)]
+        with torch.enable_grad():
+            cost = (cost_gmm(y, leafs[0], torch.exp(leafs[1]) + eps, torch.softmax(leafs[2], -1) + eps) * mask).sum() \
+                / (mask.sum() + 1e-5)
+        return cost, [d * gscale for d in torch.autograd.grad(cost, leafs)]
+
+    def event_ms(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            r = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        del r
+        return e0.elapsed_time(e1) / n
+
+    res = {"shape": {"M": M, "O": O, "K": K}, "reps": reps}
+    head = {"fused": [], "torch": []}
+    peak = {}
+    for key, fn in (("fused", head_fused), ("torch", head_torch)):  # warm, and the peak memory of one pass on its own
+        fn(); torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        fn(); torch.cuda.synchronize()
+        peak[key] = torch.cuda.max_memory_allocated() - base
+    for rep in range(reps):
+        for key, fn in (("fused", head_fused), ("torch", head_torch)):
+            head[key].append(round(event_ms(fn, 5), 4))
+    # the bytes the kernels must move: both [M, O*K] pre-activation arrays, y and co_hat once per direction, the two big
+    # gradients once
+    fwd_b = 4 * (2 * M * O * K + M * O + M * K)
+    bwd_b = fwd_b + 4 * 2 * M * O * K
+    e0 = lambda f: event_ms(f, 10)
+    logr = ops.gmm_cost_fwd(y, mu, sh, co, eps)[2]
+    rs = torch.ones(M, device=dev)
+    fwd_all = [e0(lambda: ops.gmm_cost_fwd(y, mu, sh, co, eps)) for _ in range(3)]  # three means of 10 launches each;
+    bwd_all = [e0(lambda: ops.gmm_cost_bwd(y, mu, sh, co, logr, rs, eps, out=bufs)) for _ in range(3)]
+    t_fwd, t_bwd = min(fwd_all), min(bwd_all)  # the TB/s figures are of the best of the three
+    tbs = lambda b, ms: round(b / (ms * 1e-3) * 1e-12, 3)
+    res["head_ms"] = head
+    res["head_spread_ms"] = {k: round(max(v) - min(v), 4) for k, v in head.items()}
+    res["head_extra_bytes_peak"] = peak
+    res["kernels"] = {"fwd_bytes": fwd_b, "bwd_bytes": bwd_b, "fwd_ms_all": [round(t, 4) for t in fwd_all], "bwd_ms_all": [round(t, 4) for t in bwd_all],
+                      "fwd_ms": round(t_fwd, 4), "bwd_ms": round(t_bwd, 4), "TBps_of": "best of the three",
+                      "fwd_TBps": tbs(fwd_b, t_fwd), "bwd_TBps": tbs(bwd_b, t_bwd),
+                      "fwd_of_8TBps_peak": round(tbs(fwd_b, t_fwd) / 8.0, 3), "bwd_of_8TBps_peak": round(tbs(bwd_b, t_bwd) / 8.0, 3),
+                      "fwd_of_6.3TBps_achievable": round(tbs(fwd_b, t_fwd) / 6.3, 3),
+                      "bwd_of_6.3TBps_achievable": round(tbs(bwd_b, t_bwd) / 6.3, 3)}
+    del y, mu, sh, co, bufs, logr
+    torch.cuda.empty_cache()
+
+    # the full training step (forward, backward, clip + Adam) of BASELINE configs[1] with the GMM head
+    m = Parrot(device=dev, use_graph=True, seed=1234, num_layers=2, rnn_h_dim=1024, readouts_dim=1024,
+               encoder_type='bidirectional', which_cost='GMM', k_gmm=K).initialize()
+    with torch.no_grad():
+        m.get_parameter_dict()['/parrot/h1_to_att/fork_kappa.b'].fill_(-1.5)
+    tr = Trainer(m)
+    feat = torch.randn(T + 1, B, O, generator=gen).to(dev)
+    batch = (feat, torch.ones(T + 1, B, device=dev), torch.randint(0, 43, (B, U), generator=gen).to(dev),
+             torch.ones(B, U, device=dev))
+    step = {"fused": [], "torch": []}
+    speak = {"fused": 0, "torch": 0}
+    for rep in range(reps + 1):  # (the first round allocates the workspace and captures the graphs: not listed)
+        for key, val in (("fused", "1"), ("torch", "0")):
+            os.environ['PARROT_GMM_COST_FUSED'] = val
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            ms = event_ms(lambda: tr.step(*batch, None, 1), 3)
+            assert m.gmm_cost_path == key, (m.gmm_cost_path, key)
+            if rep:
+                step[key].append(round(ms, 3))
+                speak[key] = max(speak[key], torch.cuda.max_memory_allocated())
+    os.environ.pop('PARROT_GMM_COST_FUSED', None)
+    res["step_ms"] = step
+    res["step_spread_ms"] = {k: round(max(v) - min(v), 3) for k, v in step.items()}
+    res["step_max_memory_allocated"] = speak
+    res["fused_faster_head"] = max(head["fused"]) < min(head["torch"])
+    res["fused_faster_step"] = max(step["fused"]) < min(step["torch"])
+    m.close()
+    return res
+
+
+if "--gmm_head" in sys.argv:  # this leg alone, one JSON line
+    print(json.dumps({"gmm_head": gmm_head(max(5, int(_arg("--reps", "5"))))}))
+    sys.exit(0)
 
 if "--child" in sys.argv:  # one LSTM decode measurement under the caller's environment
     print(json.dumps(decode(dict(LSTM_SHAPES[_arg("--child")], cell_type='lstm'),
