@@ -55,16 +55,33 @@ long long parrot_profile_end2(double* total_us, double* flops, double* bytes, do
  *   batched with element strides; split_k > 1 splits K over workgroups, the partial products are summed in
  *   slice order by a second kernel (deterministic; inside a stream capture the product runs unsplit);
  *   split_k = 0 picks a split automatically (long reductions with few output tiles, e.g. deferred weight gradients).
- * M <= 64 with transA = 0 dispatches to the weight-streaming recurrent-step kernel.
+ *
+ * Small-M dispatch: a call with M <= 64, transA = 0, nbatch = 1, split_k <= 1, alpha = 1 and no gate runs on the
+ * weight-streaming recurrent-step kernel (f32 operands whatever the precision mode).  Any one of alpha != 1, a gate
+ * (parrot_gemm_gated), split_k > 1, transA = 1 or nbatch > 1 keeps a product of any M on the batched kernels below.
+ *
+ * accumulate together with an activation (act != 0) is rejected with PARROT_ERR_BADARG on every path: the step kernel
+ * would add C after the activation and the batched kernels before it, so the meaning would change between M = 64 and
+ * M = 65.  split_k > 1 with an activation is rejected too (the automatic rule never splits such a product).
  * ------------------------------------------------------------------------------------------ */
 #define PARROT_PRECISION_F32 0
 #define PARROT_PRECISION_BF16 1
 #define PARROT_PRECISION_BF16X3 2
-/* Operand precision of the batched path of parrot_gemm (M > 64, or transA / batched / split-K calls), process-wide:
- * PARROT_PRECISION_F32 (default; the reference computes in floatX = float32, model.py:21) or PARROT_PRECISION_BF16:
- * A and B are read as f32 and rounded to bf16 (nearest even) on their way into the matrix cores, products are
- * accumulated in f32, C / bias / activation stay f32 (BASELINE configs[3]).  Not a per-stream setting: change it only
- * between calls.  A decoder plan created with bf16 = 1 applies the mode to its own batched projections regardless. */
+/* Operand precision of the batched kernels of parrot_gemm / parrot_gemm_gated (every call the small-M rule above does
+ * not send to the step kernel), process-wide:
+ *   PARROT_PRECISION_BF16X3 (the default; PARROT_GEMM_PRECISION=f32 / bf16 in the environment picks another): f32
+ *     operands, each split into three bf16 terms inside the kernel, six bf16 matrix instructions per block, f32
+ *     accumulation: f32-grade results at 1.7-1.9 x the rate of the f32-input kernel.  It covers the products that are
+ *     eligible: no activation or relu, M >= 128, N >= 128, K >= 64, both operand pointers 16-byte aligned, lda, ldb and
+ *     both batch strides multiples of 4, and the contiguous extent of each operand (K, or M for transA; N, or K for
+ *     transB) a multiple of 4.  Every other product (tanh / sigmoid epilogues included) runs as under
+ *     PARROT_PRECISION_F32.
+ *   PARROT_PRECISION_F32: the f32-input matrix instructions for everything (the reference computes in floatX =
+ *     float32, model.py:21).
+ *   PARROT_PRECISION_BF16: A and B are read as f32 and rounded to bf16 (nearest even) on their way into the matrix
+ *     cores, products are accumulated in f32, C / bias / activation stay f32 (BASELINE configs[3]).
+ * Not a per-stream setting: change it only between calls.  A decoder plan created with bf16 = 1 applies the bf16 mode
+ * to its own batched projections regardless. */
 int parrot_set_gemm_precision(int mode);
 int parrot_get_gemm_precision(void);
 int parrot_gemm(const float* A, int lda, int transA, const float* B, int ldb, int transB, float* C, int ldc,
@@ -76,6 +93,20 @@ int parrot_gemm(const float* A, int lda, int transA, const float* B, int ldb, in
  * relu's output (three_tier.py:504-509: the two ReLU layers of sample_level_predictor).  Operand layouts as parrot_gemm. */
 int parrot_gemm_gated(const float* A, int lda, int transA, const float* B, int ldb, int transB, float* C, int ldc,
                       int M, int N, int K, const float* gate, int ldg, void* stream);
+
+/* Which kernel a parrot_gemm call with these arguments takes under the precision mode now in effect, and how many K
+ * slices it plans (has_gate != 0: a parrot_gemm_gated call; pass alpha = 1, act = 0, nbatch = 1, split_k = 0 as it
+ * does).  A and B are only inspected for their alignment, never dereferenced; no HIP call is made, so the query works
+ * without a device.  *slices is the planned count (split_k if > 0, else the automatic rule), before the fallback to
+ * one slice inside a stream capture or without a workspace; it is 1 for the step kernel.  Returns PARROT_ERR_BADARG for
+ * arguments parrot_gemm rejects (null pointers, extents < 1, a batched gate, an activation with more than one slice). */
+#define PARROT_GEMM_ROUTE_STEP 0   /* sk_kernel */
+#define PARROT_GEMM_ROUTE_F32 1    /* bg_kernel8 */
+#define PARROT_GEMM_ROUTE_BF16 2   /* bg_kernel_bf16 */
+#define PARROT_GEMM_ROUTE_BF16X3 3 /* bgs_kernel */
+int parrot_gemm_route(const float* A, int lda, int transA, const float* B, int ldb, int transB, int M, int N, int K,
+                      float alpha, int act, int nbatch, long long strideA, long long strideB, int split_k, int has_gate,
+                      int* kernel, int* slices);
 
 /* bf16-IN weight-gradient product (round 4): C[M,N] (+)= A^T . B with A [K, M] and B [K, N] ALREADY bf16 in device
  * memory (row-major, leading dimensions in elements, both multiples of 8; M, N multiples of 8; 16-byte aligned),

@@ -60,50 +60,55 @@ long long parrot_profile_end2(double* total_us, double* flops, double* bytes, do
 // model.py's _backward -- never share partial tiles).  Where there is none the product runs unsplit.
 static StreamScratch bg_workspace(0);
 
-// Auto split-K, the deterministic split-K workspace and the launch of one batched product (shared by parrot_gemm and
-// parrot_gemm_bf16in).
-static int bg_run(BgArgs a, int split_k, hipStream_t st) {
-    const int M = a.M, N = a.N, K = a.K, nbatch = a.nbatch, act = a.act;
-    const float* bias = a.bias;
-    int split = split_k;
-    if (split <= 0) {
-        // auto: few output tiles but a long reduction (deferred weight gradients: K = T*B rows)
-        // -> spread K over enough workgroups to fill 256 CUs.
-        int bm, bn;
-        bg_tile_shape(a.bf16, bm, bn);
-        const long long tiles = (long long)ceil_div(M, bm) * ceil_div(N, bn) * nbatch;
-        split = 1;
-        if (a.bf16 == 3) {
-            // 256 x 256 tiles, one workgroup per CU, slices dealt to XCDs: a multiple of 8 slices whose workgroups fill
-            // whole rounds of 256 best, at least 512 K rows per slice
-            if (act == 0 && tiles < 256 && K >= 4096) {
-                double best = -1.0;
-                for (int sp = 8; sp <= 64 && K / sp >= 512; sp += 8) {
-                    const long long wgs = tiles * sp;
-                    const double eff = (double)wgs / (double)((wgs + 255) / 256 * 256);
-                    const double score = eff - 0.001 * sp;
-                    if (score > best) { best = score; split = sp; }
-                }
-            }
-        } else if (a.bf16 == 2 && K >= 512 && tiles < 256) {
-            // (tiles >= 256: the output tiles fill the chip by themselves -- the M = T*B readout products -- and a split
-            // would only add a partial-sum pass larger than the operands: ADVICE r05)
-            // 256 x 256 tiles, one workgroup per CU: the slice count whose workgroups fill whole rounds of 256 best
-            // (at least two rounds, at most 16 slices, at least 1024 K rows per slice)
+// Automatic split-K: the slice count bg_run plans for a product on kernel `bf16` (BgArgs::bf16: 0 / 1 the 128 x 128
+// tile kernels, 2 bgh_kernel, 3 bgs_kernel) when the caller passes split_k <= 0.  One rule per tile family.  Pure host
+// arithmetic: parrot_gemm_route reports what it returns.
+static int bg_auto_split(int bf16, int M, int N, int K, int act, int nbatch) {
+    // few output tiles but a long reduction (deferred weight gradients: K = T*B rows)
+    // -> spread K over enough workgroups to fill 256 CUs.
+    int bm, bn;
+    bg_tile_shape(bf16, bm, bn);
+    const long long tiles = (long long)ceil_div(M, bm) * ceil_div(N, bn) * nbatch;
+    int split = 1;
+    if (bf16 == 3) {
+        // 256 x 256 tiles, one workgroup per CU, slices dealt to XCDs: a multiple of 8 slices whose workgroups fill
+        // whole rounds of 256 best, at least 512 K rows per slice
+        if (act == 0 && tiles < 256 && K >= 4096) {
             double best = -1.0;
-            for (int sp = 1; sp <= 16 && K / sp >= 1024; ++sp) {
+            for (int sp = 8; sp <= 64 && K / sp >= 512; sp += 8) {
                 const long long wgs = tiles * sp;
                 const double eff = (double)wgs / (double)((wgs + 255) / 256 * 256);
-                const double score = eff - (wgs < 512 ? 0.25 : 0.0) - 0.002 * sp;
+                const double score = eff - 0.001 * sp;
                 if (score > best) { best = score; split = sp; }
             }
-        } else if (act == 0 && tiles < 512 && K >= 512) {
-            split = (int)((gemm_target_wgs() + tiles - 1) / tiles);
-            const int maxs = K / 256 > 0 ? K / 256 : 1;
-            if (split > maxs) split = maxs;
-            if (split > 64) split = 64;
         }
+    } else if (bf16 == 2 && K >= 512 && tiles < 256) {
+        // (tiles >= 256: the output tiles fill the chip by themselves -- the M = T*B readout products -- and a split
+        // would only add a partial-sum pass larger than the operands: ADVICE r05)
+        // 256 x 256 tiles, one workgroup per CU: the slice count whose workgroups fill whole rounds of 256 best
+        // (at least two rounds, at most 16 slices, at least 1024 K rows per slice)
+        double best = -1.0;
+        for (int sp = 1; sp <= 16 && K / sp >= 1024; ++sp) {
+            const long long wgs = tiles * sp;
+            const double eff = (double)wgs / (double)((wgs + 255) / 256 * 256);
+            const double score = eff - (wgs < 512 ? 0.25 : 0.0) - 0.002 * sp;
+            if (score > best) { best = score; split = sp; }
+        }
+    } else if (act == 0 && tiles < 512 && K >= 512) {
+        split = (int)((gemm_target_wgs() + tiles - 1) / tiles);
+        const int maxs = K / 256 > 0 ? K / 256 : 1;
+        if (split > maxs) split = maxs;
+        if (split > 64) split = 64;
     }
+    return split;
+}
+
+// The deterministic split-K workspace and the launch of one batched product (shared by parrot_gemm and
+// parrot_gemm_bf16in).
+static int bg_run(BgArgs a, int split_k, hipStream_t st) {
+    const int M = a.M, N = a.N, nbatch = a.nbatch, act = a.act;
+    const float* bias = a.bias;
+    const int split = split_k > 0 ? split_k : bg_auto_split(a.bf16, M, N, a.K, act, nbatch);
     a.splitk = split;
     a.ws = nullptr;
     if (a.splitk > 1) {
@@ -126,14 +131,46 @@ static int bg_run(BgArgs a, int split_k, hipStream_t st) {
     return bg_launch(a, st);
 }
 
+// Which kernel a parrot_gemm / parrot_gemm_gated call takes (PARROT_GEMM_ROUTE_*) under precision `mode`.  The one copy
+// of the dispatch rule: gemm_impl launches what this returns and parrot_gemm_route reports it.  The pointers are only
+// looked at for their alignment.
+static int gemm_pick_kernel(const float* A, int lda, int transA, const float* B, int ldb, int transB, int M, int N, int K,
+                            float alpha, int act, int nbatch, long long strideA, long long strideB, int split_k,
+                            bool has_gate, int mode) {
+    // the weight-streaming step kernel: plain x . W (+ bias, activation, accumulate) on at most 64 rows
+    if (M <= 64 && !transA && nbatch == 1 && split_k <= 1 && alpha == 1.0f && !has_gate) return PARROT_GEMM_ROUTE_STEP;
+    if (mode == PARROT_PRECISION_BF16) return PARROT_GEMM_ROUTE_BF16;
+    if (mode == PARROT_PRECISION_BF16X3) {
+        // split-bf16 products (bgs_kernel): f32 operands and f32-grade results on the bf16 matrix pipe.  Taken where the
+        // 256 x 256 tile pays: both operands fetched as aligned 16-byte vectors, enough work; the rest stays on the
+        // f32-input MFMA kernel.
+        auto al = [](const float* p, long long ld) { return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0); };
+        const bool ok = act <= 1 && al(A, lda) && al(B, ldb) && (strideA % 4 == 0) && (strideB % 4 == 0) && M >= 128 && N >= 128 &&
+                        K >= 64 && (!transA || M % 4 == 0) && (transA || K % 4 == 0) && (transB || N % 4 == 0) && (!transB || K % 4 == 0);
+        if (ok) return PARROT_GEMM_ROUTE_BF16X3;
+    }
+    return PARROT_GEMM_ROUTE_F32;
+}
+
+static int gemm_mode_in_force() { return t_gemm_bf16 >= 0 ? t_gemm_bf16 : g_gemm_bf16.load(std::memory_order_relaxed); }
+
+// BgArgs::bf16 of a big-kernel route
+static int gemm_route_bf16(int route) {
+    return route == PARROT_GEMM_ROUTE_BF16X3 ? 3 : route == PARROT_GEMM_ROUTE_BF16 ? 1 : 0;
+}
+
 static int gemm_impl(const float* A, int lda, int transA, const float* B, int ldb, int transB, float* C, int ldc,
                      int M, int N, int K, const float* bias, float alpha, int accumulate, int act, int nbatch,
                      long long strideA, long long strideB, long long strideC, int split_k, const float* gate, int ldg,
                      void* stream) {
     if (!A || !B || !C || M < 1 || N < 1 || K < 1 || nbatch < 1) return PARROT_ERR_BADARG;
     if (gate && (nbatch != 1 || ldg < N)) return PARROT_ERR_BADARG;
+    // the step kernel adds C after the activation, the big kernels before it: the combination has no one meaning
+    if (act != 0 && accumulate) return PARROT_ERR_BADARG;
     hipStream_t st = (hipStream_t)stream;
-    if (M <= 64 && !transA && nbatch == 1 && split_k <= 1 && alpha == 1.0f && !gate) {
+    const int route = gemm_pick_kernel(A, lda, transA, B, ldb, transB, M, N, K, alpha, act, nbatch, strideA, strideB, split_k,
+                                       gate != nullptr, gemm_mode_in_force());
+    if (route == PARROT_GEMM_ROUTE_STEP) {
         SkJob j;
         sk_job_init(j);
         j.nseg = 1;
@@ -156,16 +193,7 @@ static int gemm_impl(const float* A, int lda, int transA, const float* B, int ld
     a.nbatch = nbatch;
     a.accumulate = accumulate; a.alpha = alpha; a.act = act;
     a.gate = gate; a.ldg = ldg;
-    a.bf16 = t_gemm_bf16 >= 0 ? t_gemm_bf16 : g_gemm_bf16.load(std::memory_order_relaxed);
-    if (a.bf16 == PARROT_PRECISION_BF16X3) {
-        // split-bf16 products (bgs_kernel): f32 operands and f32-grade results on the bf16 matrix pipe.  Taken where the
-        // 256 x 256 tile pays: both operands fetched as aligned 16-byte vectors, enough work; the rest stays on the
-        // f32-input MFMA kernel.
-        auto al = [](const float* p, long long ld) { return (((uintptr_t)p & 15) == 0) && (ld % 4 == 0); };
-        const bool ok = act <= 1 && al(A, lda) && al(B, ldb) && (strideA % 4 == 0) && (strideB % 4 == 0) && M >= 128 && N >= 128 &&
-                        K >= 64 && (!transA || M % 4 == 0) && (transA || K % 4 == 0) && (transB || N % 4 == 0) && (!transB || K % 4 == 0);
-        a.bf16 = ok ? 3 : 0;
-    }
+    a.bf16 = gemm_route_bf16(route);
     return bg_run(a, split_k, st);
 }
 
@@ -180,6 +208,24 @@ int parrot_gemm_gated(const float* A, int lda, int transA, const float* B, int l
                       int M, int N, int K, const float* gate, int ldg, void* stream) { PH_ENTRY();
     if (!gate) return PARROT_ERR_BADARG;
     return gemm_impl(A, lda, transA, B, ldb, transB, C, ldc, M, N, K, nullptr, 1.0f, 0, 0, 1, 0, 0, 0, 0, gate, ldg, stream);
+}
+
+int parrot_gemm_route(const float* A, int lda, int transA, const float* B, int ldb, int transB, int M, int N, int K,
+                      float alpha, int act, int nbatch, long long strideA, long long strideB, int split_k, int has_gate,
+                      int* kernel, int* slices) {
+    // (no HIP call here, not even PH_ENTRY's: the query works without a device)
+    if (!A || !B || !kernel || !slices || M < 1 || N < 1 || K < 1 || nbatch < 1) return PARROT_ERR_BADARG;
+    if (has_gate && nbatch != 1) return PARROT_ERR_BADARG;
+    const int route = gemm_pick_kernel(A, lda, transA, B, ldb, transB, M, N, K, alpha, act, nbatch, strideA, strideB, split_k,
+                                       has_gate != 0, gemm_mode_in_force());
+    int split = 1;
+    if (route != PARROT_GEMM_ROUTE_STEP) {
+        split = split_k > 0 ? split_k : bg_auto_split(gemm_route_bf16(route), M, N, K, act, nbatch);
+        if (split > 1 && act != 0) return PARROT_ERR_BADARG;  // as bg_run
+    }
+    *kernel = route;
+    *slices = split;
+    return 0;
 }
 
 int parrot_to_bf16(const float* x, void* y, long long n, void* stream) { PH_ENTRY();

@@ -52,7 +52,10 @@ def _mat(t: torch.Tensor, name: str):
 
 def gemm(a: torch.Tensor, b: torch.Tensor, bias=None, out=None, accumulate=False, act=ACT_NONE,
          alpha=1.0, split_k=0) -> torch.Tensor:
-    """out[M,N] (+)= alpha * a[M,K] @ b[K,N] + bias.  a / b may be transposed views (no copies)."""
+    """out[M,N] (+)= alpha * a[M,K] @ b[K,N] + bias.  a / b may be transposed views (no copies).  `accumulate` with an
+    activation is refused: the kernels disagree on whether `out` is added before or after it (parrot_hip.h)."""
+    if accumulate and int(act) != ACT_NONE:
+        raise ValueError("gemm: accumulate together with an activation is not defined")
     pa, M, K, lda, ta = _mat(a, "a")
     pb, K2, N, ldb, tb = _mat(b, "b")
     if K != K2:
@@ -75,6 +78,37 @@ def gemm(a: torch.Tensor, b: torch.Tensor, bias=None, out=None, accumulate=False
               ptr(bias, "bias"), float(alpha), int(bool(accumulate)), int(act), 1, 0, 0, 0, int(split_k),
               _stream())
     return out
+
+
+ROUTE_STEP, ROUTE_F32, ROUTE_BF16, ROUTE_BF16X3 = 0, 1, 2, 3
+
+
+def gemm_route(a: torch.Tensor, b: torch.Tensor, bias=None, out=None, accumulate=False, act=ACT_NONE, alpha=1.0,
+               split_k=0, gate=None, nbatch=None, transA=False, transB=False):
+    """(kernel, slices) the product would take under the precision mode now in effect (parrot_gemm_route): ROUTE_* and the
+    planned number of K slices.  Same tensors and keywords as `gemm`; with `gate` the call `gemm_gated(a, b, gate)`
+    makes; with `nbatch` the 3-d operands and transA / transB of `gemm_batched`.  Nothing is launched."""
+    import ctypes as C
+    if nbatch is not None:
+        _chk(a, "a"); _chk(b, "b")
+        if a.shape[0] != nbatch or b.shape[0] != nbatch:
+            raise ValueError("gemm_route: nbatch does not match the operands")
+        M, K = (a.shape[2], a.shape[1]) if transA else (a.shape[1], a.shape[2])
+        N = b.shape[1] if transB else b.shape[2]
+        args = (a.data_ptr(), a.stride(1), int(transA), b.data_ptr(), b.stride(1), int(transB), M, N, K, 1.0, 0,
+                int(nbatch), a.stride(0), b.stride(0), 1, 0)
+    else:
+        pa, M, K, lda, ta = _mat(a, "a")
+        pb, K2, N, ldb, tb = _mat(b, "b")
+        if K != K2:
+            raise ValueError(f"gemm_route: inner dimensions differ ({K} vs {K2})")
+        if gate is not None:
+            args = (pa, lda, ta, pb, ldb, tb, M, N, K, 1.0, 0, 1, 0, 0, 0, 1)
+        else:
+            args = (pa, lda, ta, pb, ldb, tb, M, N, K, float(alpha), int(act), 1, 0, 0, int(split_k), 0)
+    kernel, slices = C.c_int(-1), C.c_int(-1)
+    _lib.call("parrot_gemm_route", *args, C.byref(kernel), C.byref(slices))
+    return kernel.value, slices.value
 
 
 def to_bf16(x: torch.Tensor, out=None) -> torch.Tensor:

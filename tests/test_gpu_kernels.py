@@ -24,10 +24,11 @@ def test_skinny_gemm(dev, M, N, K, transB):
     b = _rand((N, K) if transB else (K, N), dev, 2)
     bias = _rand((N,), dev, 3)
     bb = b.t() if transB else b
+    assert ops.gemm_route(a, bb, bias=bias) == (ops.ROUTE_STEP, 1)
     out = ops.gemm(a, bb, bias=bias)
     ref = a.double().cpu() @ bb.double().cpu() + bias.double().cpu()
     assert_close(out, ref, 2e-6, "skinny gemm")
-    # accumulate + activation
+    # accumulate, then an activation
     out2 = ops.gemm(a, bb, out=out.clone(), accumulate=True)
     assert_close(out2, ref + ref - bias.double().cpu(), 2e-6, "skinny gemm accumulate")
     out3 = ops.gemm(a, bb, bias=bias, act=ops.ACT_TANH)
@@ -42,7 +43,9 @@ def test_big_gemm_layouts(dev, M, N, K, ta, tb):
     b = _rand((N, K) if tb else (K, N), dev, 5)
     aa = a.t() if ta else a
     bb = b.t() if tb else b
-    out = ops.gemm(aa, bb)
+    with ops.gemm_precision(ops.PRECISION_F32):   # the f32-input kernel whatever the library default is
+        assert ops.gemm_route(aa, bb)[0] == ops.ROUTE_F32
+        out = ops.gemm(aa, bb)
     ref = aa.double().cpu() @ bb.double().cpu()
     assert_close(out, ref, 3e-6, "big gemm")
 
@@ -51,21 +54,22 @@ def test_big_gemm_splitk_bias_batched(dev):
     from parrot_amd import ops
     a = _rand((5000, 96), dev, 6)
     b = _rand((5000, 200), dev, 7)
-    out = ops.gemm(a.t(), b, split_k=4)
-    assert_close(out, a.double().cpu().t() @ b.double().cpu(), 5e-6, "split-k")
     acc = _rand((96, 200), dev, 8)
-    out2 = ops.gemm(a.t(), b, out=acc.clone(), accumulate=True, split_k=2)
-    assert_close(out2, acc.double().cpu() + a.double().cpu().t() @ b.double().cpu(), 5e-6, "split-k accumulate")
     x = _rand((3, 70, 40), dev, 9)
     y = _rand((3, 40, 50), dev, 10)
     o = torch.empty(3, 70, 50, device=dev)
-    ops.gemm_batched(x, y, o)
-    assert_close(o, x.double().cpu() @ y.double().cpu(), 3e-6, "batched")
-    # strided operands: sub-blocks of larger matrices
     big = _rand((300, 400), dev, 11)
-    sub = big[10:210, 20:148]
+    sub = big[10:210, 20:148]  # strided operands: sub-blocks of larger matrices
     w = _rand((128, 64), dev, 12)
-    assert_close(ops.gemm(sub, w), sub.double().cpu() @ w.double().cpu(), 3e-6, "strided A")
+    with ops.gemm_precision(ops.PRECISION_F32):   # the f32-input kernel whatever the library default is
+        out = ops.gemm(a.t(), b, split_k=4)
+        out2 = ops.gemm(a.t(), b, out=acc.clone(), accumulate=True, split_k=2)
+        ops.gemm_batched(x, y, o)
+        osub = ops.gemm(sub, w)
+    assert_close(out, a.double().cpu().t() @ b.double().cpu(), 5e-6, "split-k")
+    assert_close(out2, acc.double().cpu() + a.double().cpu().t() @ b.double().cpu(), 5e-6, "split-k accumulate")
+    assert_close(o, x.double().cpu() @ y.double().cpu(), 3e-6, "batched")
+    assert_close(osub, sub.double().cpu() @ w.double().cpu(), 3e-6, "strided A")
     assert_close(ops.colsum(big), big.double().cpu().sum(0), 1e-5, "colsum")
     tall = _rand((40000, 70), dev, 13)
     assert_close(ops.colsum(tall), tall.double().cpu().sum(0), 2e-5, "colsum tall")
@@ -83,6 +87,7 @@ def test_split_gemm_layouts(dev, M, N, K, ta, tb):
     aa = a.t() if ta else a
     bb = b.t() if tb else b
     with ops.gemm_precision(ops.PRECISION_BF16X3):
+        assert ops.gemm_route(aa, bb)[0] == ops.ROUTE_BF16X3
         out = ops.gemm(aa, bb)
     ref = aa.double().cpu() @ bb.double().cpu()
     assert_close(out, ref, 3e-6, "split gemm")
