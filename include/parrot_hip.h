@@ -655,6 +655,34 @@ int parrot_softmax_ce_bwd(const float* logits, int ld, const int* target, const 
 int parrot_relu_gate(const float* dy, const float* gate, float* out, long long n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Label tables of the text encoder (parrot_amd/csrc/labeltables.hip).  The encoder's input rows are rows of the
+ * LookupTable (model.py:233-238): x = embed_label.W[labels], Q distinct rows.  So the Fork products x . W + b
+ * (model.py:226-231) are rows of P = embed_label.W . W + b [Q, cols], and their Theano gradient needs only
+ * S[q] = sum over the rows with label q of dY[row]:  dW = embed_label.W^T . S,  db = sum_q S[q],
+ * d embed_label.W = S . W^T.  Up to four matrices (candidate / gate inputs of both directions) per call.
+ *   parrot_label_gather:  rows[s][i,:] = tbl[s][labels[i],:]
+ *   parrot_label_segsum:  sums[s][q,:] = sum over the i with labels[i] == q of rows[s][i,:]  (overwritten; a label that
+ *                         never occurs gives a zero row).  Fixed summation order, no float atomics: same bits every
+ *                         run; accumulated in double and rounded once.
+ * labels [N] int32 in [0, Q) (values outside are clamped into the table, never read past it), D[s] % 4 == 0, 16-byte
+ * aligned matrices, Q <= 64 (parrot_label_tables_supported).  ws: parrot_label_segsum_ws_floats(N, Q, sum of D) floats, 8-byte aligned.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ParrotLabelTablesDesc {
+    long long N;              /* rows */
+    int Q, nseg;              /* table rows; matrices in this call (1..4) */
+    const int* labels;        /* [N] */
+    const float* tbl[4];      /* [Q, D[s]]  gather: in */
+    float* rows[4];           /* [N, D[s]]  gather: out, segsum: in */
+    float* sums[4];           /* [Q, D[s]]  segsum: out */
+    int D[4];
+} ParrotLabelTablesDesc;
+
+int parrot_label_tables_supported(long long N, int Q);
+int parrot_label_gather(const ParrotLabelTablesDesc* desc, void* stream);
+long long parrot_label_segsum_ws_floats(long long N, int Q, int Dtotal);
+int parrot_label_segsum(const ParrotLabelTablesDesc* desc, float* ws, long long ws_floats, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mixture-density head of the training step (parrot_amd/csrc/gmmcost.hip): the Gaussian-mixture negative log-likelihood
  * (model.py:65-91) on the PRE-ACTIVATIONS of the three output heads (model.py:774-781) and its gradient, one pass over
  * the rows each way.  Row m, column o*K + k of mu / sig_hat (the order of ParrotSampleDesc::Wmu):

@@ -40,6 +40,15 @@ class GruSeqDesc(C.Structure):
     ]
 
 
+class LabelTablesDesc(C.Structure):
+    _fields_ = [
+        ("N", C.c_longlong), ("Q", C.c_int), ("nseg", C.c_int),
+        ("labels", C.c_void_p),
+        ("tbl", C.c_void_p * 4), ("rows", C.c_void_p * 4), ("sums", C.c_void_p * 4),
+        ("D", C.c_int * 4),
+    ]
+
+
 class LstmSeqDesc(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("T", "B", "H", "use_graph")] + \
                [(n, C.c_void_p) for n in ("W", "pre_in", "s", "c", "gates", "dS", "dc", "dP")]
@@ -185,6 +194,10 @@ SIGNATURES = {
     "parrot_colsum": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp]),
     "parrot_gru_step_fwd": (_i, [_vp] * 11 + [_i, _i, _vp]),
     "parrot_gru_step_bwd": (_i, [_vp] * 11 + [_i, _i, _vp]),
+    "parrot_label_tables_supported": (_i, [_ll, _i]),
+    "parrot_label_gather": (_i, [C.POINTER(LabelTablesDesc), _vp]),
+    "parrot_label_segsum_ws_floats": (C.c_longlong, [_ll, _i, _i]),
+    "parrot_label_segsum": (_i, [C.POINTER(LabelTablesDesc), _vp, _ll, _vp]),
     "parrot_gru_seq_create": (_i, [C.POINTER(GruSeqDesc), C.POINTER(C.c_void_p)]),
     "parrot_gru_seq_fwd": (_i, [_vp, _vp]),
     "parrot_gru_seq_bwd": (_i, [_vp, _vp]),

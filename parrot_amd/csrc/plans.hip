@@ -15,6 +15,7 @@ struct GruSeqPlan : PlanBase {
     // kernels of rowgru.hip (PARROT_GRU_ROWWISE=0: the per-step launches below).  The plan owns the fragment-major
     // weight copies and refreshes them at the head of every forward scan (the weights change between steps).
     bool rowwise = false;
+    int waves = 4;           // PARROT_RG_WAVES, read with the plan
     float* tiled = nullptr;  // per chain: Wg_f, Wc_f, Wg_r, Wc_r
     ~GruSeqPlan() override {
         if (tiled) (void)hipFree(tiled);
@@ -24,6 +25,7 @@ struct GruSeqPlan : PlanBase {
         for (int ch = 0; ch < d.nchain && rowwise; ++ch)  // (the tiling kernel wants 16-byte aligned matrices)
             if (!d.Wg[ch] || !d.Wc[ch] || ((uintptr_t)d.Wg[ch] & 15) || ((uintptr_t)d.Wc[ch] & 15)) rowwise = false;
         if (!rowwise) return 0;
+        waves = rowgru_waves(sw_rg_waves());
         const size_t per = (size_t)6 * d.H * d.H;  // 2 x (H x 2H + H x H) floats
         if (hipMalloc(&tiled, sizeof(float) * per * d.nchain) != hipSuccess) {
             tiled = nullptr;
@@ -44,7 +46,7 @@ struct GruSeqPlan : PlanBase {
             c.dh = d.dh[ch]; c.dG = d.dG[ch]; c.dC = d.dC[ch];
             c.reverse = d.reverse[ch];
         }
-        g.mask = d.mask; g.T = d.T; g.B = d.B; g.H = d.H; g.nchain = d.nchain;
+        g.mask = d.mask; g.T = d.T; g.B = d.B; g.H = d.H; g.nchain = d.nchain; g.waves = waves;
         return g;
     }
     int fwd_rowwise(hipStream_t st) {

@@ -18,8 +18,10 @@ struct RowGruArgs {
     RowGruChain chain[4];
     const float* mask;  // [T,B] or null
     int T, B, H, nchain;
+    int waves;  // waves per 16-row block: 4 or 8 (rowgru_waves rounds anything else down; same results at every width)
 };
 
 bool rowgru_supported(int T, int B, int H, int nchain);
+int rowgru_waves(int requested);
 int rowgru_fwd_launch(const RowGruArgs& g, hipStream_t stream);
 int rowgru_bwd_launch(const RowGruArgs& g, hipStream_t stream);

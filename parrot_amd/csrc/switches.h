@@ -19,6 +19,8 @@
 // PARROT_BWD_HETERO        1        plan     0: no K-balanced backward tick (bwd8); Python then allocates    tests
 //                                            no second / third accumulators
 // PARROT_GRU_ROWWISE       1        plan     0: no row-wise GRU sequence kernel                              tests
+// PARROT_RG_WAVES          8        plan     waves per 16-row block of the row-wise GRU sequence kernels:    tests, tools
+//                                            4 or 8 (other values round down); same results, bit for bit
 // PARROT_WK                1        plan,    wide step kernel: 0 never, 1 launches of >= 4096 output          tests
 //                                   launch   columns, 2 whenever legal
 // PARROT_ATT_DENSE         0        plan,    1: the attention reads every context row instead of walking    bench.py, tests
@@ -44,6 +46,9 @@
 // PARROT_WS_CACHE          6        alloc    workspace / plan cache entries per shape (at least 4)           development
 // PARROT_READOUT_COMPOSED  1        step     0: readouts and output layer as separate full-width products    tests, tools
 //                                            (the path of GMM / layer_norm / speaker / bf16 models anyway)
+// PARROT_ENCODER_TABLES    1        step     0: the encoder's Fork products on the embedded text instead of   tests, tools
+//                                            lookups in projected label tables (the path of tables taller
+//                                            than 64 rows anyway)
 // PARROT_GMM_COST_FUSED    1        step     0: GMM head cost and gradient as torch element-wise code         tests, tools
 //                                            (the path of raw_output and k_gmm > 64 models anyway)
 // PARROT_BF16_DW           1        step     0: bf16 decoders' weight gradients from f32 operands            tests
@@ -69,5 +74,6 @@ static inline const char* env_str(const char* name) { return getenv(name); }
 // Switches read in more than one place.
 static inline int sw_att_dense() { return env_int("PARROT_ATT_DENSE", 0); }
 static inline int sw_pm_dataflow(int dflt) { return env_int("PARROT_PM_DATAFLOW", dflt); }
+static inline int sw_rg_waves() { return env_int("PARROT_RG_WAVES", 8); }
 static inline int sw_wk() { return env_int("PARROT_WK", 1); }
 static inline bool sw_pm_dump_plan() { return env_set("PARROT_PM_DUMP_PLAN"); }

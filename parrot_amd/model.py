@@ -436,6 +436,11 @@ class Parrot(Brick):
             ctx = labels.to(torch.float32) * labels_mask[..., None]
             return ctx.contiguous()
         B, U = labels.shape
+        # (sampling passes save=None and keeps the products: one pass per utterance, and decoded frames follow ctx to the bit)
+        tables = save is not None and self._encoder_tables(B, U)
+        self._encoder_path = 'tables' if tables else 'products'
+        if tables:
+            return self._encoder_forward_tables(labels, labels_mask, save)
         P = '/encoder/encoder'
         emb = self._p('/encoder/embed_label.W')[labels.long()]  # LookupTable gather [B,U,D]
         x = emb if self.encoder_literal else emb.transpose(0, 1)
@@ -466,6 +471,8 @@ class Parrot(Brick):
     def _encoder_backward(self, dctx, save):
         if self.encoder_type is None:
             return
+        if 'enc_lab32' in save:
+            return self._encoder_backward_tables(dctx, save)
         labels, mask, x2 = save['enc_labels'], save['enc_mask'], save['enc_x2']
         B, U = labels.shape
         P = '/encoder/encoder'
@@ -501,6 +508,97 @@ class Parrot(Brick):
             demb = demb.transpose(0, 1)
         self._scatter_rows_add(self._g('/encoder/embed_label.W'), labels.long().reshape(-1),
                                demb.reshape(-1, demb.shape[-1]))
+
+    # ------------------------------------------------------------------ encoder through label tables
+    @property
+    def encoder_path(self):
+        """'tables' or 'products': how the last encoder pass formed the products with the embedded text (None before the
+        first call and for models without an encoder)."""
+        return getattr(self, '_encoder_path', None)
+
+    def _encoder_tables(self, B, U):
+        """True when the Fork products of the encoder run as lookups in projected label tables (csrc/labeltables.hip):
+        every row of the embedded text is one of num_characters table rows, so x . W = (embed_label.W . W)[labels] and
+        x^T . dY = embed_label.W^T . S with S the per-label sums of dY.  A bidirectional encoder whose table fits the
+        segmented-sum kernel.  PARROT_ENCODER_TABLES=0 (read per step) keeps the products with the embedded text."""
+        return (self.encoder_type == 'bidirectional' and self.encoder_dim % 4 == 0
+                and ops.label_tables_supported(B * U, self._p('/encoder/embed_label.W').shape[0])
+                and env_int('PARROT_ENCODER_TABLES', 1) != 0)
+
+    def _enc_tables_ws(self, ws):
+        if 'P' not in ws:
+            Q, ED = self._p('/encoder/embed_label.W').shape[0], self.encoder_dim
+            f = dict(device=self._dev(), dtype=torch.float32)
+            ws['P'] = [torch.empty(Q, ED * (1 + k % 2), **f) for k in range(4)]  # per direction: inputs | gate inputs
+            ws['S'] = [torch.empty(Q, ED * (1 + k % 2), **f) for k in range(4)]
+            ws['seg_ws'] = None
+        return ws
+
+    def _encoder_forward_tables(self, labels, labels_mask, save):
+        B, U = labels.shape
+        P = '/encoder/encoder'
+        Te, Be = self._encoder_dims(B, U)
+        ws = self._enc_tables_ws(self._enc_runner(B, U))
+        run = ws['run']
+        emb_W = self._p('/encoder/embed_label.W')
+        lab = (labels if self.encoder_literal else labels.t()).to(torch.int32).contiguous().view(-1)  # scan order
+        Wg, Wc = [], []
+        with ops.gemm_precision(ops.PRECISION_F32):  # (tables of a few thousand entries: nothing to gain from bf16 operands)
+            for i, d in enumerate(('forward', 'backward')):
+                ops.gemm(emb_W, self._p(f'{P}/{d}/fork/fork_inputs.W'), bias=self._p(f'{P}/{d}/fork/fork_inputs.b'),
+                         out=ws['P'][2 * i])
+                ops.gemm(emb_W, self._p(f'{P}/{d}/fork/fork_gate_inputs.W'),
+                         bias=self._p(f'{P}/{d}/fork/fork_gate_inputs.b'), out=ws['P'][2 * i + 1])
+        ops.label_gather(lab, ws['P'], [b[i].view(Te * Be, -1) for i in range(2) for b in (run.inputs, run.gate_inputs)])
+        for i, d in enumerate(('forward', 'backward')):
+            run.h[i][0].copy_(self._p(f'{P}/{d}/gatedrecurrent.initial_state').unsqueeze(0).expand(Be, -1))
+            Wg.append(self._p(f'{P}/{d}/gatedrecurrent.state_to_gates'))
+            Wc.append(self._p(f'{P}/{d}/gatedrecurrent.state_to_state'))
+        run.bind(Wg, Wc)
+        run.forward()
+        out = torch.cat([run.h[0][1:], run.h[1][1:].flip(0)], dim=-1)  # [Te,Be,2*enc]
+        if not self.encoder_literal:
+            out = out.transpose(0, 1)
+        ctx = (out * labels_mask[..., None]).contiguous()
+        if save is not None:
+            save.update(enc_lab32=lab, enc_labels=labels, enc_mask=labels_mask)
+        return ctx
+
+    def _encoder_backward_tables(self, dctx, save):
+        labels, mask, lab = save['enc_labels'], save['enc_mask'], save['enc_lab32']
+        B, U = labels.shape
+        P = '/encoder/encoder'
+        ED = self.encoder_dim
+        ws = self._enc_tables_ws(self._enc_runner(B, U))
+        run = ws['run']
+        Te, Be = run.T, run.B
+        d_out = dctx * mask[..., None]
+        if not self.encoder_literal:
+            d_out = d_out.transpose(0, 1)
+        for i in range(2):
+            run.dh[i].zero_()
+        run.dh[0][1:].copy_(d_out[..., :ED])
+        run.dh[1][1:].copy_(d_out[..., ED:].flip(0))
+        run.backward()
+        # per-label sums of the gradients of the candidate / gate inputs: all the Fork and the LookupTable need
+        ws['seg_ws'] = ops.label_segsum(lab, [b[i].view(Te * Be, -1) for i in range(2) for b in (run.dC, run.dG)],
+                                        ws['S'], ws['seg_ws'])
+        emb_W, demb = self._p('/encoder/embed_label.W'), self._g('/encoder/embed_label.W')
+        with ops.gemm_precision(ops.PRECISION_F32):
+            for i, d in enumerate(('forward', 'backward')):
+                for S, name in ((ws['S'][2 * i], 'fork_inputs'), (ws['S'][2 * i + 1], 'fork_gate_inputs')):
+                    ops.gemm(emb_W.t(), S, out=self._g(f'{P}/{d}/fork/{name}.W'), accumulate=True)
+                    ops.colsum(S, out=self._g(f'{P}/{d}/fork/{name}.b'), accumulate=True)
+                    ops.gemm(S, self._p(f'{P}/{d}/fork/{name}.W').t(), out=demb, accumulate=True)
+        for i, d in enumerate(('forward', 'backward')):
+            dC = run.dC[i].view(Te * Be, ED)
+            dG = run.dG[i].view(Te * Be, 2 * ED)
+            hprev = run.h[i][:Te] if i == 0 else run.h[i][:Te].flip(0)
+            hprev = hprev.reshape(Te * Be, ED)
+            ops.gemm(run.rh[i].view(Te * Be, ED).t(), dC,
+                     out=self._g(f'{P}/{d}/gatedrecurrent.state_to_state'), accumulate=True)
+            ops.gemm(hprev.t(), dG, out=self._g(f'{P}/{d}/gatedrecurrent.state_to_gates'), accumulate=True)
+            ops.colsum(run.dh[i][0], out=self._g(f'{P}/{d}/gatedrecurrent.initial_state'), accumulate=True)
 
     # ------------------------------------------------------------------ training workspace
     def _train_workspace(self, T, B, U):

@@ -387,6 +387,42 @@ def embed_sum(E, W1, idx, add=None):
     return _EmbedSumFn.apply(E, W1, idx, add)
 
 
+def _label_desc(labels32, Q, mats, field):
+    import ctypes as C
+    d = _lib.LabelTablesDesc()
+    d.N, d.Q, d.nseg = labels32.numel(), int(Q), len(mats)
+    d.labels = ptr(labels32, "labels", torch.int32)
+    for s, (m, rows) in enumerate(mats):
+        if rows.shape != (labels32.numel(), m.shape[1]) or m.shape[0] != Q:
+            raise ValueError("label tables: expected [Q, D] tables / sums and [N, D] row matrices")
+        getattr(d, field)[s], d.rows[s], d.D[s] = ptr(m, field), ptr(rows, "rows"), m.shape[1]
+    return d, C.byref(d)
+
+
+def label_tables_supported(N, Q) -> bool:
+    """True when parrot_label_gather / parrot_label_segsum take a table of Q rows over N label positions."""
+    return bool(_lib.load().parrot_label_tables_supported(int(N), int(Q)))
+
+
+def label_gather(labels32, tables, rows):
+    """rows[s][i] = tables[s][labels32[i]] for up to four [Q, D_s] tables in one launch (labels32: int32 [N] in [0, Q);
+    the kernel clamps a value outside into the table)."""
+    d, ref = _label_desc(labels32, tables[0].shape[0], list(zip(tables, rows)), "tbl")
+    _lib.call("parrot_label_gather", ref, _stream())
+
+
+def label_segsum(labels32, rows, sums, ws=None):
+    """sums[s][q] = sum of the rows[s][i] with labels32[i] == q for up to four [N, D_s] matrices (overwrites sums; fixed
+    summation order: same bits every call).  `ws`: scratch from a previous call of the same shape, returned for reuse."""
+    Q = sums[0].shape[0]
+    d, ref = _label_desc(labels32, Q, list(zip(sums, rows)), "sums")
+    n_ws = int(_lib.load().parrot_label_segsum_ws_floats(d.N, Q, sum(m.shape[1] for m in sums)))
+    if ws is None or ws.numel() < n_ws:
+        ws = torch.empty(n_ws, device=labels32.device, dtype=torch.float32)
+    _lib.call("parrot_label_segsum", ref, ws.data_ptr(), ws.numel(), _stream())
+    return ws
+
+
 class _ReluMlpFn(torch.autograd.Function):
     """logits = relu(relu(x . W2 + b2) . W3 + b3) . W4 + b4 (three_tier.py:499-515) with bias + ReLU in the products'
     epilogues and, backward, the ReLU masks in the epilogues of the dx products (parrot_gemm_gated)."""
