@@ -150,29 +150,48 @@ int parrot_gru_step_bwd(const float* dh_out, const float* h, const float* mask, 
  * Plain GRU scans (Blocks GatedRecurrent.apply over a sequence -- the bidirectional encoder,
  * model.py:226-231, 245; lib.ops.LowMemGRU / stackedGRU, ops.py:395-440, 612-777).
  * Up to 4 independent chains (e.g. forward + backward direction) advance in the same launches.
+ *
+ * Indexing.  A chain's s-th processed step consumes time t = s (reverse: t = T-1-s).  The states h and their
+ * gradients dh are indexed by SLOT (slot s+1 = after step s); everything else -- inputs, gate_inputs, mask, the saved
+ * activations z / r / rh / c, and the gradients dG / dC -- is indexed by TIME t, also for a reversed chain.  (So the
+ * weight gradients dWc += rh^T dC pair equal indices, while dWg += h[slot s]^T dG[t(s)] needs the flip.)
+ * inputs[ch] / gate_inputs[ch] may be NULL: the chain then runs as if that operand were all zeros, and nothing is
+ * read through the pointer.  dC / dG are written either way.
  * ------------------------------------------------------------------------------------------ */
 typedef struct ParrotGruSeqDesc {
     int T, B, H, nchain, use_graph, reserved;
     int reverse[4];              /* chain consumes its inputs from t = T-1 down to 0 */
     const float* Wg[4];          /* [H,2H] */
     const float* Wc[4];          /* [H,H]  */
-    const float* inputs[4];      /* [T,B,H]  pre-projected candidate inputs (biases included) */
-    const float* gate_inputs[4]; /* [T,B,2H] */
+    const float* inputs[4];      /* [T,B,H]  pre-projected candidate inputs (biases included), or NULL = zeros */
+    const float* gate_inputs[4]; /* [T,B,2H] or NULL = zeros */
     const float* mask;           /* [T,B] or NULL (shared by all chains) */
     float* h[4];                 /* [T+1,B,H]; slot 0 = initial state (caller), slot s+1 = state after
                                     the chain's s-th processed step */
-    float* z[4]; float* r[4]; float* rh[4]; float* c[4]; /* [T,B,H] saved activations (per step s) */
+    float* z[4]; float* r[4]; float* rh[4]; float* c[4]; /* [T,B,H] saved activations (indexed by time t) */
     /* backward */
     float* dh[4];                /* [T+1,B,H] in: dL/dh[slot] from consumers (slots 1..T), slot 0 zero;
                                     out: total gradient per slot (slot 0 = grad of the initial state) */
-    float* dG[4];                /* [T,B,2H] out: gradient wrt gate_inputs (per step s) */
-    float* dC[4];                /* [T,B,H]  out: gradient wrt inputs      (per step s) */
+    float* dG[4];                /* [T,B,2H] out: gradient wrt gate_inputs (indexed by time t) */
+    float* dC[4];                /* [T,B,H]  out: gradient wrt inputs      (indexed by time t) */
 } ParrotGruSeqDesc;
 
 int parrot_gru_seq_create(const ParrotGruSeqDesc* desc, void** plan);
 int parrot_gru_seq_fwd(void* plan, void* stream);
 int parrot_gru_seq_bwd(void* plan, void* stream);
 int parrot_gru_seq_destroy(void* plan);
+
+/* Which path a plan's scans take (introspection, as parrot_gemm_route): info4 = {row-wise 0/1, waves per 16-row block
+ * (4 or 8; 0 on the launch path), H / 16 (0 on the launch path), reason}.  Row-wise = one launch per direction for the
+ * whole sequence (rowgru.hip); otherwise the per-step launches, for the reason given.  Decided once, at create. */
+#define PARROT_GRU_ROUTE_ROWWISE 0   /* reason: none, the plan is row-wise */
+#define PARROT_GRU_ROUTE_SHAPE 1     /* H > 128 or H % 16 != 0 (parrot_gru_seq_rowwise_supported) */
+#define PARROT_GRU_ROUTE_SWITCH 2    /* PARROT_GRU_ROWWISE=0 */
+#define PARROT_GRU_ROUTE_UNALIGNED 3 /* a Wg / Wc pointer that is not 16-byte aligned */
+#define PARROT_GRU_ROUTE_ALLOC 4     /* no memory for the fragment-major weight copies */
+int parrot_gru_seq_route(void* plan, int* info4);
+/* 1 if the row-wise kernels take the shape (T, B >= 1, H a multiple of 16 up to 128, 1..4 chains); needs no device. */
+int parrot_gru_seq_rowwise_supported(int T, int B, int H, int nchain);
 
 /* ------------------------------------------------------------------------------------------
  * LSTM scans (lib.ops.__LSTMStep / LowMemLSTM / stackedLSTM, sampleRNN/lib/ops.py:461-610, 823-989):

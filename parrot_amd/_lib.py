@@ -202,6 +202,8 @@ SIGNATURES = {
     "parrot_gru_seq_fwd": (_i, [_vp, _vp]),
     "parrot_gru_seq_bwd": (_i, [_vp, _vp]),
     "parrot_gru_seq_destroy": (_i, [_vp]),
+    "parrot_gru_seq_route": (_i, [_vp, C.POINTER(C.c_int)]),
+    "parrot_gru_seq_rowwise_supported": (_i, [_i, _i, _i, _i]),
     "parrot_lstm_seq_create": (_i, [C.POINTER(LstmSeqDesc), C.POINTER(C.c_void_p)]),
     "parrot_lstm_seq_fwd": (_i, [_vp, _vp]),
     "parrot_lstm_seq_bwd": (_i, [_vp, _vp]),

@@ -11,26 +11,35 @@ namespace {
 struct GruSeqPlan : PlanBase {
     ParrotGruSeqDesc d;
 
-    // Narrow layers (H <= 256: the encoder) run the whole sequence as ONE launch per direction on the row-owning
-    // kernels of rowgru.hip (PARROT_GRU_ROWWISE=0: the per-step launches below).  The plan owns the fragment-major
+    // Narrow layers (H <= 128, a multiple of 16: the encoder) run the whole sequence as ONE launch per direction on the
+    // row-owning kernels of rowgru.hip (PARROT_GRU_ROWWISE=0: the per-step launches below).  The plan owns the fragment-major
     // weight copies and refreshes them at the head of every forward scan (the weights change between steps).
     bool rowwise = false;
+    int reason = PARROT_GRU_ROUTE_SHAPE;  // why not row-wise (parrot_gru_seq_route); 0 when row-wise
     int waves = 4;           // PARROT_RG_WAVES, read with the plan
     float* tiled = nullptr;  // per chain: Wg_f, Wc_f, Wg_r, Wc_r
     ~GruSeqPlan() override {
         if (tiled) (void)hipFree(tiled);
     }
+    int launch_path(int why) {  // the per-step launches, for this reason
+        rowwise = false;
+        reason = why;
+        return 0;
+    }
     int setup_rowwise() {
-        rowwise = rowgru_supported(d.T, d.B, d.H, d.nchain) && env_int("PARROT_GRU_ROWWISE", 1) != 0;
-        for (int ch = 0; ch < d.nchain && rowwise; ++ch)  // (the tiling kernel wants 16-byte aligned matrices)
-            if (!d.Wg[ch] || !d.Wc[ch] || ((uintptr_t)d.Wg[ch] & 15) || ((uintptr_t)d.Wc[ch] & 15)) rowwise = false;
-        if (!rowwise) return 0;
+        if (!rowgru_supported(d.T, d.B, d.H, d.nchain)) return launch_path(PARROT_GRU_ROUTE_SHAPE);
+        if (env_int("PARROT_GRU_ROWWISE", 1) == 0) return launch_path(PARROT_GRU_ROUTE_SWITCH);
+        for (int ch = 0; ch < d.nchain; ++ch)  // (the tiling kernel wants 16-byte aligned matrices)
+            if (!d.Wg[ch] || !d.Wc[ch] || ((uintptr_t)d.Wg[ch] & 15) || ((uintptr_t)d.Wc[ch] & 15))
+                return launch_path(PARROT_GRU_ROUTE_UNALIGNED);
         waves = rowgru_waves(sw_rg_waves());
         const size_t per = (size_t)6 * d.H * d.H;  // 2 x (H x 2H + H x H) floats
         if (hipMalloc(&tiled, sizeof(float) * per * d.nchain) != hipSuccess) {
             tiled = nullptr;
-            rowwise = false;
+            return launch_path(PARROT_GRU_ROUTE_ALLOC);
         }
+        rowwise = true;
+        reason = PARROT_GRU_ROUTE_ROWWISE;
         return 0;
     }
     RowGruArgs row_args() const {
@@ -1336,6 +1345,16 @@ int parrot_gru_seq_destroy(void* plan) { PH_ENTRY();
     delete static_cast<PlanBase*>(plan);
     return 0;
 }
+int parrot_gru_seq_route(void* plan, int* info4) {  // (no HIP call: the plan's own record)
+    if (!plan || !info4) return PARROT_ERR_BADARG;
+    const GruSeqPlan* p = static_cast<GruSeqPlan*>(plan);
+    info4[0] = p->rowwise ? 1 : 0;
+    info4[1] = p->rowwise ? p->waves : 0;
+    info4[2] = p->rowwise ? p->d.H / 16 : 0;
+    info4[3] = p->reason;
+    return 0;
+}
+int parrot_gru_seq_rowwise_supported(int T, int B, int H, int nchain) { return rowgru_supported(T, B, H, nchain) ? 1 : 0; }
 
 int parrot_lstm_seq_create(const ParrotLstmSeqDesc* desc, void** plan) { PH_ENTRY();
     if (!desc || !plan || desc->T < 1 || desc->B < 1 || desc->H < 4 || (desc->H & 3)) return PARROT_ERR_BADARG;

@@ -665,6 +665,14 @@ def gru_step(inputs, gate_inputs, h, Wc, Wg, mask=None):
     return _GruStepFn.apply(inputs, gate_inputs, h, Wc, Wg, mask)
 
 
+GRU_ROUTE_REASONS = ("rowwise", "shape", "switch", "unaligned", "alloc")  # PARROT_GRU_ROUTE_* of parrot_hip.h
+
+
+def gru_rowwise_supported(T, B, H, nchain) -> bool:
+    """Whether the row-wise scan kernels take the shape (parrot_gru_seq_rowwise_supported; needs no device)."""
+    return bool(_lib.load().parrot_gru_seq_rowwise_supported(int(T), int(B), int(H), int(nchain)))
+
+
 class GruSeqRunner:
     """Owns the workspaces + plan of a GRU scan with up to 4 independent chains (include/parrot_hip.h,
     ParrotGruSeqDesc).  Buffers are allocated once, so the plan's hipGraph can be replayed."""
@@ -711,6 +719,16 @@ class GruSeqRunner:
         _lib.call("parrot_gru_seq_create", C.byref(d), C.byref(plan))
         self._plan, self._weights = plan, key
         self._keep = (list(Wg), list(Wc), mask)
+
+    def route(self):
+        """The path the bound plan's scans take (parrot_gru_seq_route): dict(rowwise, waves, nch, reason), reason one
+        of GRU_ROUTE_REASONS; waves and nch (= H / 16) are 0 on the launch path."""
+        import ctypes as C
+        if self._plan is None:
+            raise RuntimeError("GruSeqRunner.route: no plan bound")
+        info = (C.c_int * 4)()
+        _lib.call("parrot_gru_seq_route", self._plan, info)
+        return dict(rowwise=bool(info[0]), waves=info[1], nch=info[2], reason=GRU_ROUTE_REASONS[info[3]])
 
     def forward(self):
         _lib.call("parrot_gru_seq_fwd", self._plan, _stream())

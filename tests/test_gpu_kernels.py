@@ -229,12 +229,31 @@ def test_gru_seq_fwd_bwd(dev, reverse, use_mask):
         assert_close(t.grad, r.grad, 1e-4, n)
 
 
+def _gru_seq_and_route(monkeypatch, *args):
+    """ops.gru_seq(*args) and the route of the plan it ran on (GruSeqRunner.route() right after the plan is made)."""
+    from parrot_amd import ops
+    routes = []
+    bind = ops.GruSeqRunner.bind
+
+    def bind_and_ask(self, *a, **kw):
+        bind(self, *a, **kw)
+        routes.append(self.route())
+
+    with monkeypatch.context() as m:
+        m.setattr(ops.GruSeqRunner, "bind", bind_and_ask)
+        hs = ops.gru_seq(*args)
+    assert len(routes) == 1
+    return hs, routes[0]
+
+
 @pytest.mark.parametrize("T,B,H,reverse,use_mask", [(6, 37, 128, False, True), (5, 20, 256, True, False),
                                                    (64, 200, 128, True, True), (7, 16, 16, False, False)])
 def test_gru_seq_rowwise_vs_step_launches(dev, monkeypatch, T, B, H, reverse, use_mask):
-    """The row-owning scan kernels (rowgru.hip: one launch per direction for the whole sequence, H <= 256) against the
+    """The row-owning scan kernels (rowgru.hip: one launch per direction for the whole sequence, H <= 128) against the
     fp64 oracle and against the per-step launch path (PARROT_GRU_ROWWISE=0) -- the encoder's own shape (64 steps over
-    200 rows, H = 128), ragged row blocks, both directions, step masks, the widest and the narrowest layer it takes."""
+    200 rows, H = 128), ragged row blocks, both directions, step masks, the widest and the narrowest layer it takes.
+    H = 256 is the fallback: the row-wise kernels refuse the shape, the launch path runs in both modes, and the route
+    of every plan is asserted so that no mode is compared with itself unnoticed."""
     from oracle import parrot_ref as R
     from parrot_amd import ops
     inp = _rand((T, B, H), dev, 1)
@@ -248,7 +267,11 @@ def test_gru_seq_rowwise_vs_step_launches(dev, monkeypatch, T, B, H, reverse, us
     for mode in ("1", "0"):
         monkeypatch.setenv("PARROT_GRU_ROWWISE", mode)
         ts = [t.clone().requires_grad_() for t in (inp, gin, h0, Wc, Wg)]
-        hs = ops.gru_seq(*ts, mask, reverse)
+        hs, route = _gru_seq_and_route(monkeypatch, *ts, mask, reverse)
+        if mode == "1" and H <= 128:
+            assert route["rowwise"] and route["reason"] == "rowwise" and route["nch"] == H // 16 and route["waves"] in (4, 8)
+        else:
+            assert route == dict(rowwise=False, waves=0, nch=0, reason="shape" if H > 128 else "switch")
         (hs * gout).sum().backward()
         got[mode] = [hs.detach().clone()] + [t.grad.clone() for t in ts]
     rs = [t.detach().double().cpu().requires_grad_() for t in (inp, gin, h0, Wc, Wg)]

@@ -32,6 +32,8 @@ def _run(dev, monkeypatch, waves, T, B, H, reverse, mask, data):
         for buf in (run.z[i], run.r[i], run.rh[i], run.c[i], run.dC[i], run.dG[i]):
             buf.fill_(float("nan"))  # (every element must be written by the kernels)
     run.bind(data["Wg"][:n], data["Wc"][:n], mask)
+    # (a plan that fell back to the step launches would make the comparison of the two widths a tautology)
+    assert run.route() == dict(rowwise=True, waves=waves, nch=H // 16, reason="rowwise")
     run.forward()
     for i in range(n):
         run.dh[i].copy_(data["dh"][i])
