@@ -440,7 +440,8 @@ int parrot_readout_composed_bwd(const ParrotReadoutComposedDesc* desc, float* ws
 
 /* ------------------------------------------------------------------------------------------
  * Autoregressive decode: the theano.scan over `sample_step` of Parrot.sample_model_fun
- * (model.py:882-1057) for the MSE ("greedy") head: x_t = readout_to_output(readouts_t).
+ * (model.py:882-1057) for the MSE ("greedy") head: x_t = readout_to_output(readouts_t), or the GMM
+ * head (gmm_K > 0 below): x_t sampled from the mixture the readout parameterises.
  * Same packed weights as above plus, per layer, the fed-back-output rows (out_to_h*, present
  * when weak/full feedback is on; Wfg[l] [O,2H], Wfc[l] [O,H], NULL otherwise), and the readout
  * stack Wr = [h1_to_readout ; .. ; hL_to_readout ; att_to_readout] [L*H+E, R], br = summed bias,
@@ -502,8 +503,8 @@ typedef struct ParrotSampleDesc {
     float* ln_scratch;
     long long ln_scratch_floats;
     /* Optional: decode on the persistent phase machine (parrot_amd/csrc/persist.h) -- the whole S-step loop as one
-     * resident kernel, 2L + 3 barrier-separated phases per step instead of 2L + 3 launches.  MSE head, no
-     * layer_norm, B <= 64, O <= 64 <= ldx.  The caller provides fragment-major copies (parrot_tile_weights, mode 0) of
+     * resident kernel, 2L + 3 barrier-separated phases per step instead of 2L + 3 launches.  MSE head (a GMM head:
+     * Wrh_t / rh_const at the end of this struct), no layer_norm, B <= 64, O <= 64 <= ldx.  The caller provides fragment-major copies (parrot_tile_weights, mode 0) of
      *   Wg_t[l] / Wc_t[l]: [K_l + F_l, 2H] / [K_l + F_l, H] = the packed layer matrix with the feedback rows Wfg / Wfc
      *                      appended and zero-padded to F_l = 64 rows (F_l = 0 without feedback into the layer),
      *   Wr_t: [L*H + E, R],   Wo_t: [R, 64] (columns >= O zero),
@@ -549,7 +550,7 @@ typedef struct ParrotSampleDesc {
     /* bf16 = 1: decode with bf16 operands.  The one product per layer and step, [h_l[t] ; w ; h_0[t+1] .. h_{l-1}[t+1] ; x[t]]
      * . Wg_t[l], rounds BOTH operands to bf16 (nearest even) where they enter the product and accumulates in f32; states,
      * cells, biases, additive inputs, the attention and the composed output product stay f32.  LSTM stacks on the
-     * persistent machine only: cell = 1, MSE head, no layer_norm, B <= 64, H and E multiples of 32, workspace given, and
+     * persistent machine only: cell = 1, MSE head (never a GMM head), no layer_norm, B <= 64, H and E multiples of 32, workspace given, and
      *   Wg_t16[l]: the matrix of Wg_t[l] (feedback rows appended, padded to 64) as parrot_tile_weights_bf16(.., mode 2,
      *              lstm_H = H), rows*cols bf16; Wg_t[l] is then not read and may be NULL.
      * Resident bf16 slabs take half the LDS, so more of them stay on chip, and the streamed ones move half the bytes.
@@ -565,16 +566,34 @@ typedef struct ParrotSampleDesc {
      * stop, later rows are unspecified (parrot_sample_steps_run reports T_stop).  eou_pos, eou_ncmp, eou_first: device
      * arrays of B ints, 0 <= eou_pos[b] < U, 0 <= eou_ncmp[b] <= U (clamped); eou_extra >= 8.  The stop exists on the
      * persistent machine only: parrot_sample_create returns PARROT_ERR_UNSUPPORTED for a descriptor that asks for it and
-     * gets no machine plan (GMM head, layer_norm, B > 64, PARROT_SAMPLE_PERSIST=0, no workspace, eou_extra < 8, an array
+     * gets no machine plan (GMM head without PARROT_PM_GMM=1, layer_norm, B > 64, PARROT_SAMPLE_PERSIST=0, no workspace, eou_extra < 8, an array
      * missing); the per-step launches are never substituted.  0: every run decodes all S steps. */
     const int* eou_pos;
     const int* eou_ncmp;
     int* eou_first;
     int eou_extra, reserved9;
+    /* Optional, opt-in (PARROT_PM_GMM=1; unset or 0: a GMM head decodes as per-step launches whatever is given here): the GMM
+     * head on the persistent machine.  Without layer_norm nothing non-linear sits between the readout stack and the three
+     * head projections, so with Wh = [Wmu | Wsig | Wco] ([R, 2 O K + K] in that column order, zero-padded to rh_cols =
+     * a multiple of 16 columns) the caller hands over
+     *   Wrh_t:    fragment-major copy (parrot_tile_weights, mode 0) of Wr . Wh, [L*H + E, rh_cols], composed in double
+     *             precision and rounded once,
+     *   rh_const: [B, rh_cols] row-major = (br + radd) . Wh + [bmu | bsig | bco] + [add_mu | add_sig | add_co].
+     * A step then ends in a head phase (rh_cols / 16 column tiles of [h_0 .. h_{L-1} ; w] . Wrh_t + rh_const, kept as a
+     * write-once history [S, B, rh_cols] in the workspace) and a sampling phase (one unit per batch row: mixture weights,
+     * the pick against unif, x[t+1] = mu + (exp(sig_hat - sampling_bias) + eps) * noise, pi_out) in place of the readout
+     * and output phases: GRU stacks 2L + 3 whole-K phases, LSTM stacks L + 3; parrot_sample_is_persistent reports 1.
+     * Needs gmm_K <= 64, unif, noise and pi_out, f32 operands (bf16 = 0), rh_cols / 16 tiles within the machine's
+     * workgroups (x 2 where an LSTM layer has more tiles than workgroups), and everything the machine needs of an MSE
+     * head except Wr_t / Wo_t / bo_pad / oadd_pad / Wro_t / ro_const / Wgx_t / Wcx_t / Watt_t, which are not read.
+     * gmm_mu / gmm_sig / gmm_co stay untouched on the machine.  The end-of-utterance stop (eou_*) applies as it is. */
+    const float* Wrh_t;
+    const float* rh_const;
+    int rh_cols, reserved10;
 } ParrotSampleDesc;
 
 long long parrot_sample_persist_floats(const ParrotSampleDesc* desc);
-/* 0: per-step launches; 1: the machine with whole-K phases (GRU: 2L + 3; LSTM: L + 2); 2: the machine with the step cut
+/* 0: per-step launches; 1: the machine with whole-K phases (GRU: 2L + 3; LSTM: L + 2, L + 3 with a GMM head); 2: the machine with the step cut
  * along K (GRU, Wro_t given); 3: the same with the fed-back frame out of the chain (Wgx_t / Wcx_t given, 2L + 1 phases) */
 int parrot_sample_is_persistent(void* plan);
 /* 1: the plan runs the machine with bf16 operands (ParrotSampleDesc::bf16); 0: every product has f32 operands */

@@ -21,7 +21,9 @@
 enum { PM_MAXENT = 12,   // unit descriptors per workgroup: n_slots * maxu <= PM_MAXENT (training 3 x 3, decode 9 x 1)
        PM_MAXSLOTS = 9, PM_THREADS = 512, PM_MAXINIT = 12, PM_MAXDST = 6, PM_MAXWDST = 8, PM_MAXFILL = 16 };
 // PM_GEMM16: a GEMM unit whose weight slab is a bf16 copy (decode with bf16 operands, below); every other field as PM_GEMM
-enum { PM_NONE = 0, PM_GEMM = 1, PM_ATT = 2, PM_GEMM16 = 3 };
+// PM_SAMPLE: the GMM head's sampling of one batch row (decode, PmSamp below); row = the batch row, dst[] = the fed-back-frame
+// chunks of the layer slabs of the NEXT step (off already points at them, as PmAtt::wdst)
+enum { PM_NONE = 0, PM_GEMM = 1, PM_ATT = 2, PM_GEMM16 = 3, PM_SAMPLE = 4 };
 enum { PM_EPI_LINEAR = 0, PM_EPI_GATES = 1, PM_EPI_CAND = 2, PM_EPI_LSTM = 3 };
 
 // LDS map (floats): resident weights | scratch shared by the split-K reduction (8 partial 16x16 tiles, rows padded
@@ -110,6 +112,22 @@ struct PmAtt {
     int eou_extra, pad4;
 };
 
+// GMM head on the machine (decode, ParrotSampleDesc::gmm_K > 0; K == 0: the program has no sampling units).  The head
+// phase -- plain LINEAR units over the composed matrix Wr . [W_mu | W_sig | W_co] -- leaves the row-major, write-once head
+// history head[t] = [B, NH] (NH a multiple of 16: mu at column o K + k, sig_hat at O K + o K + k, the mixture logits at
+// 2 O K + k); the PM_SAMPLE unit of row b then does gmm_sample_kernel's arithmetic (elementwise.hip) with one wave: mixture
+// weights, the pick against unif[t, b], x[t + 1] = mu + (exp(sig_hat - bias) + eps) noise[t, b, :], stored row-major
+// (64 columns, zeros from O on) and as 16 fragment-major quads into every PmUnit::dst.
+struct PmSamp {
+    PmRM head;                    // p = step 0, st = B * NH, ld = NH
+    const float* unif;            // [T, B]
+    const float* noise;           // [T, B, O]
+    float* x;                     // row-major frame of step 0's OUTPUT (= slot 1 of ParrotSampleDesc::x), [.., B, ldx]
+    float* pi;                    // [T, B, K]
+    int B, O, K, ldx;
+    float bias, eps;
+};
+
 struct PmInit {  // prologue: row-major [M,K] (ld) -> chunks [chunk, chunk + K/16) of a fragment-major slab
     const float* src;
     unsigned dst_off;
@@ -138,6 +156,7 @@ struct PmProgram {
     float* fm_base;       // start of the fragment-major slab region (all PmDst / a_off offsets are relative to it)
     PmAtt att;
     PmInit init[PM_MAXINIT];
+    PmSamp samp;          // (last: the programs without a GMM head keep the argument layout they had)
 };
 
 enum { PM_SYNC_WORDS = 1024, PM_DBG_WORDS = 256 * 24 * 2 };  // dbg: per workgroup 24 x u64: work[9], wait[9] per slot, 4 gemm stages (100 MHz ticks)

@@ -800,10 +800,106 @@ __device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ GMM sampling row
+// The GMM head's sampling of batch row b at step t (PmSamp, persist.h): gmm_sample_kernel's arithmetic (elementwise.hip) by
+// ONE wave -- lane k < K owns mixture component k, lane o < O output column o; the other seven waves only meet it at the
+// barrier that protects lds_red.  Sums go through wave reductions, so pi may differ from the launches' sequential sums in the
+// last bits.  Every read of the head history is a whole aligned 16-byte slot (the heads' offsets are not: 2 O K = 378 at
+// K = 3), re-read in dataflow mode until its producer's store has landed; lanes beyond K / O read a clamped column, so no
+// load sits under a condition.
+__device__ __forceinline__ float pm_sel4(const f32x4& v, unsigned i) {  // (a run-time vector index would go through scratch)
+    return i == 0u ? v[0] : (i == 1u ? v[1] : (i == 2u ? v[2] : v[3]));
+}
+template <bool DF>
+__device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmUnit& u, int t, float* lds_red, float* fm_base,
+                                              unsigned* sync) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
+        const int b = __builtin_amdgcn_readfirstlane(u.row), K = g.K, O = g.O, OK = O * K;
+        const size_t tb = (size_t)t * g.B + b;
+        const __amdgpu_buffer_rsrc_t hr = pm_rsrc(g.head.p + (long long)t * g.head.st + (long long)b * g.head.ld);
+        // everything that does not depend on the pick is asked for now: the row's logits, its uniform number, its noise
+        const int kc = min(lane, K - 1), oc = min(lane, O - 1);
+        const unsigned col_c = (unsigned)(2 * OK + kc);
+        f32x4 vc = pm_ld16(hr, (col_c & ~3u) << 2);
+        const float uu = g.unif[tb];
+        const float nz = g.noise[tb * O + oc];
+        if (DF) {
+            unsigned n = 0;
+            while (__builtin_amdgcn_ballot_w64(pm_is_empty(vc)) != 0ull) {
+                if ((++n & 1023u) == 0u) {
+                    if (pm_ld(sync + PM_S_ABORT)) break;
+                    if (n > PM_POLL_LIMIT) { pm_give_up(sync); break; }
+                }
+                __builtin_amdgcn_s_sleep(1);
+                vc = pm_ld16(hr, (col_c & ~3u) << 2);
+            }
+        }
+        // pi = softmax(c_hat (1 + bias)) + eps; the pick = the first k with cumsum(pi)_k > u, else K - 1
+        const bool comp = lane < K;
+        const float v = comp ? pm_sel4(vc, col_c & 3u) * (1.f + g.bias) : -INFINITY;
+        float mx = v;
+#pragma unroll
+        for (int sh = 32; sh > 0; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
+        const float ex = comp ? expf(v - mx) : 0.f;
+        const float pk = ex / wave_sum(ex) + g.eps;
+        float cum = comp ? pk : 0.f;
+#pragma unroll
+        for (int sh = 1; sh < 64; sh <<= 1) {  // inclusive prefix sum in k order
+            const float below = __shfl_up(cum, sh, 64);
+            if (lane >= sh) cum += below;
+        }
+        const unsigned long long hit = __builtin_amdgcn_ballot_w64(comp && cum > uu);
+        const int pick = hit ? __ffsll((long long)hit) - 1 : K - 1;
+        if (comp) pm_stf(g.pi + tb * K + lane, pk);
+        // x[o] = mu[o, pick] + (exp(sig_hat[o, pick] - bias) + eps) noise[o]
+        const unsigned col_m = (unsigned)(oc * K + pick), col_s = (unsigned)OK + col_m;
+        f32x4 vm = pm_ld16(hr, (col_m & ~3u) << 2), vs = pm_ld16(hr, (col_s & ~3u) << 2);
+        if (DF) {
+            unsigned n = 0;
+            while (__builtin_amdgcn_ballot_w64(pm_is_empty(vm) || pm_is_empty(vs)) != 0ull) {
+                if ((++n & 1023u) == 0u) {
+                    if (pm_ld(sync + PM_S_ABORT)) break;
+                    if (n > PM_POLL_LIMIT) { pm_give_up(sync); break; }
+                }
+                __builtin_amdgcn_s_sleep(1);
+                vm = pm_ld16(hr, (col_m & ~3u) << 2);
+                vs = pm_ld16(hr, (col_s & ~3u) << 2);
+            }
+        }
+        const float xo = lane < O ? pm_sel4(vm, col_m & 3u) + (expf(pm_sel4(vs, col_s & 3u) - g.bias) + g.eps) * nz : 0.f;
+        // the frame (64 columns, zeros from O on) through LDS into 16 quads: one 16-byte write-through store per quad into
+        // row-major x[t + 1] and into every fragment-major destination (block (b / 16, chunk + e / 16), lane
+        // (e % 16) / 4 * 16 + b % 16 holds columns e .. e + 3, as the attention row's w); 16 lanes per destination
+        lds_red[lane] = xo;
+        __builtin_amdgcn_wave_barrier();
+        const int e4 = 4 * (lane & 15);
+        const f32x4 quad = *reinterpret_cast<const f32x4*>(lds_red + e4);
+        if (lane < 16) {
+            float* p = g.x + ((size_t)t * g.B + b) * g.ldx + e4;
+            asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(quad) : "memory");
+        }
+        const int ndst = __builtin_amdgcn_readfirstlane(u.ndst);
+        for (int q0 = 0; q0 < ndst && q0 < PM_MAXDST; q0 += 4) {
+            const int q = q0 + (lane >> 4);
+            if (q < ndst && q < PM_MAXDST) {
+                const PmDst ds = u.dst[q];
+                float* slab = fm_base + ((size_t)ds.off + (size_t)t * ds.st) / 4;
+                float* p = slab + (((size_t)((b >> 4) * ds.nch + ds.chunk + (e4 >> 4))) << 8) + ((((e4 & 15) >> 2) * 16 + (b & 15)) << 2);
+                asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(quad) : "memory");
+            }
+        }
+    }
+    // lds_red is the split-K scratch of the workgroup's next unit: nobody starts it before wave 0 has read its quads (without
+    // grid barriers nothing else would hold the other waves back -- the hazard of the attention row's last section)
+    __syncthreads();
+}
+
 // ------------------------------------------------------------------------------------------------ kernel
 // W16: the program has PM_GEMM16 units (PmProgram::w16); false: the kernel is what it was before they existed
 // EOU: the program asks for the end-of-utterance stop (PmAtt::eou_extra > 0); false: the kernel is what it was before that
-template <int MB, bool DF, bool LS, bool W16, bool EOU>
+// SMP: the program has PM_SAMPLE units (PmSamp::K > 0, a GMM head); false: the kernel is what it was before they existed
+template <int MB, bool DF, bool LS, bool W16, bool EOU, bool SMP>
 __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lds_w = lds;
@@ -923,6 +1019,7 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
                 if (t < 0 || t >= P.T) continue;
                 if (kind == PM_GEMM) pm_gemm<MB, DF, LS, false>(u, t, lds_w, lds_red, fmr, stage, sync);
                 else if (W16 && kind == PM_GEMM16) pm_gemm<MB, DF, LS, true>(u, t, lds_w, lds_red, fmr, stage, sync);
+                else if (SMP && kind == PM_SAMPLE) pm_sample_row<DF>(P.samp, u, t, lds_red, P.fm_base, sync);
                 else pm_att_row<DF, EOU>(P.att, u.row, t, lds_att, P.fm_base, sync, P.T, P.n_ticks - P.T);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1024,6 +1121,10 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
         P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL || (P.w16 && !P.lstm))
         return PH_ERR_BADARG;
+    if (P.samp.K != 0 && (P.w16 || P.samp.K < 1 || P.samp.K > 64 || P.samp.O < 1 || P.samp.O > 64 || P.samp.ldx < 64 || (P.samp.ldx % 4) ||
+                          (P.samp.head.ld % 4) || P.samp.head.ld < 2 * P.samp.O * P.samp.K + P.samp.K || !P.samp.head.p || !P.samp.unif ||
+                          !P.samp.noise || !P.samp.x || !P.samp.pi))
+        return PH_ERR_BADARG;
     if (P.att.U > PM_ATT_MAXU || P.att.A > PM_ATT_MAXA) return PH_ERR_UNSUPPORTED;
     if (P.att.eou_extra != 0 && (P.att.eou_extra < PM_EOU_MIN_EXTRA || !P.att.eou_pos || !P.att.eou_ncmp || !P.att.eou_first ||
                                  P.att.B < 1 || P.att.B > 64))
@@ -1052,7 +1153,7 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     if (!attr_done) {
         const int l = (int)lds;
 #define PM_ATTR1(MB_, DF_, LS_, W16_, EOU_) \
-    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_, EOU_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_, EOU_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
 #define PM_ATTR(EOU_) \
     PM_ATTR1(1, false, false, false, EOU_); PM_ATTR1(2, false, false, false, EOU_); PM_ATTR1(4, false, false, false, EOU_); \
     PM_ATTR1(1, true, false, false, EOU_); PM_ATTR1(2, true, false, false, EOU_); PM_ATTR1(4, true, false, false, EOU_); \
@@ -1065,14 +1166,26 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
         PM_ATTR(true);
 #undef PM_ATTR
 #undef PM_ATTR1
+        // behind them the kernels with the sampling row (GMM head: GRU and LSTM programs, f32 operands)
+#define PM_ATTRS(MB_, DF_, LS_, EOU_) \
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, false, EOU_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+#define PM_ATTRS6(LS_, EOU_) \
+    PM_ATTRS(1, false, LS_, EOU_); PM_ATTRS(2, false, LS_, EOU_); PM_ATTRS(4, false, LS_, EOU_); \
+    PM_ATTRS(1, true, LS_, EOU_); PM_ATTRS(2, true, LS_, EOU_); PM_ATTRS(4, true, LS_, EOU_)
+        PM_ATTRS6(false, false); PM_ATTRS6(true, false);
+        PM_ATTRS6(false, true); PM_ATTRS6(true, true);
+#undef PM_ATTRS6
+#undef PM_ATTRS
         attr_done = true;
     }
     const dim3 grid(P.nwg), block(PM_THREADS);
 #define PM_GO1(MB_, DF_, EOU_) \
     do { \
-        if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_>), grid, block, lds, stream, P); \
-        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_>), grid, block, lds, stream, P); \
-        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_>), grid, block, lds, stream, P); \
+        if (P.samp.K > 0 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, true>), grid, block, lds, stream, P); \
+        else if (P.samp.K > 0) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, true>), grid, block, lds, stream, P); \
+        else if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_, false>), grid, block, lds, stream, P); \
+        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, false>), grid, block, lds, stream, P); \
+        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, false>), grid, block, lds, stream, P); \
     } while (0)
 #define PM_GO(MB_, DF_) \
     do { \

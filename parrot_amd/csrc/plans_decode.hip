@@ -2,7 +2,8 @@
 // whole loop as ONE resident kernel on the persistent phase machine (persist.h) -- 2L + 3 whole-K phases (round 2,
 // build_persist_whole), 2L + 2 phases with every product cut along K by the age of its operands (round 4), 2L + 1 with
 // the fed-back frame out of the step's dependency chain (round 5; both build_persist_pieces); LSTM stacks: L + 2 whole-K
-// phases (build_persist_lstm).  SamplePlan::plan_persist picks the program; every planner emits its slabs, units and
+// phases (build_persist_lstm); with a GMM head (PARROT_PM_GMM=1) the two whole-K programs end in a composed head phase and a
+// sampling phase instead (gmm_eligible).  SamplePlan::plan_persist picks the program; every planner emits its slabs, units and
 // symbolic-replay metas through the shared builder (pm_builder.h), which carves the workspace within its bounds, checks
 // the table capacities, places and uploads.  Then the per-step launch path and the parrot_sample_* entry points.
 #include "pm_builder.h"
@@ -27,7 +28,7 @@ struct PmGroup {
 // element per step.
 struct PmAccess { int res, dstep, c0, nch; };
 struct PmMeta { int lag, slot; std::vector<PmAccess> rd, wr; };
-enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63, RES_C = 70,
+enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63, RES_HEAD = 64, RES_C = 70,
        RES_PART = 100 };
 PmAccess pm_acc(int res, int dstep, int c0, int nch) { PmAccess a; a.res = res; a.dstep = dstep; a.c0 = c0; a.nch = nch; return a; }
 
@@ -92,7 +93,7 @@ struct SamplePlan : PlanBase {
     float* hist_h[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
 
     static bool persist_eligible_shape(const ParrotSampleDesc& d) {  // (no device query: the CPU tests plan too)
-        if (d.layer_norm || d.gmm_K > 0 || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
+        if (d.layer_norm || (d.gmm_K > 0 && !gmm_eligible(d)) || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
             d.U > PM_ATT_MAXU || d.A > PM_ATT_MAXA || d.S < 1 || d.O > 64 || d.ldx < 64 || (d.ldx % 4))
             return false;
         if (d.bf16) return bf16_eligible(d);
@@ -100,6 +101,22 @@ struct SamplePlan : PlanBase {
             if (!d.Wg_t[l] || (d.cell == 0 && !d.Wc_t[l])) return false;
         return true;
     }
+    // GMM head (ParrotSampleDesc::gmm_K > 0), opt-in through PARROT_PM_GMM=1 -- read HERE and nowhere else in the library:
+    // the readout stack and the three head projections composed by the caller (Wrh_t / rh_const, rh_cols = NH16 columns) run
+    // as NH16 / 16 plain LINEAR units into a write-once head history [S, B, NH16]; one PM_SAMPLE unit per batch row (persist.h)
+    // then picks the component and writes x[t + 1].  The two whole-K programs take it (build_persist_whole,
+    // build_persist_lstm); the step cut along K does not (sampling is not linear in h: no Wgx_t / Wcx_t, no attention fold).
+    static bool gmm_eligible(const ParrotSampleDesc& d) {
+        if (env_int("PARROT_PM_GMM", 0) == 0) return false;
+        if (d.bf16 || d.gmm_K > 64 || !d.Wrh_t || !d.rh_const || (d.rh_cols % 16) || d.rh_cols < 2 * d.O * d.gmm_K + d.gmm_K) return false;
+        return d.unif && d.noise && d.pi_out;
+    }
+    static int lstm_maxu(const ParrotSampleDesc& d, int nwg) { return std::max(d.H / 4, d.B) <= nwg ? 1 : 2; }
+    // the head's column tiles need a place each in their phase (256 workgroups take K = 20: 159 tiles; 64 take K <= 8)
+    static bool head_fits(const ParrotSampleDesc& d, int nwg) {
+        return d.gmm_K <= 0 || d.rh_cols / 16 <= nwg * (d.cell == 1 ? lstm_maxu(d, nwg) : 1);
+    }
+    static long long head_floats(const ParrotSampleDesc& d) { return d.gmm_K > 0 ? (long long)d.S * d.B * d.rh_cols + 16 : 0; }
     // bf16 operands (ParrotSampleDesc::bf16): LSTM stacks only, 32-deep K steps, the bf16 copies in place of Wg_t.  A
     // descriptor that asks for them and does not qualify gets NO machine plan -- parrot_sample_create then refuses it.
     static bool bf16_eligible(const ParrotSampleDesc& d) {
@@ -110,34 +127,37 @@ struct SamplePlan : PlanBase {
     }
     // LSTM stacks (cell == 1): one phase per layer, readout and output composed (Wro_t / ro_const) -- build_persist_lstm
     static bool lstm_eligible(const ParrotSampleDesc& d) {
+        if (d.gmm_K > 0) return d.cell == 1 && d.L + 3 <= PM_MAXSLOTS;  // (persist_eligible_shape: Wrh_t / rh_const are there)
         return d.cell == 1 && d.Wro_t && d.ro_const && d.L + 2 <= PM_MAXSLOTS;
     }
     static bool legacy_eligible(const ParrotSampleDesc& d) {
+        if (d.gmm_K > 0) return 2 * d.L + 3 <= PM_MAXSLOTS;  // (head and sampling phases in place of readout and output)
         if (2 * d.L + 3 > PM_MAXSLOTS || !d.Wr_t || !d.Wo_t || !d.bo_pad) return false;
         return (d.oadd != nullptr) == (d.oadd_pad != nullptr);
     }
     static bool persist_eligible(const ParrotSampleDesc& d) {
         if (!persist_eligible_shape(d)) return false;
         if (d.cell == 1 ? !lstm_eligible(d) : !(legacy_eligible(d) || pieces_wanted(d))) return false;
-        return pm_max_workgroups() >= 64;
+        return pm_max_workgroups() >= 64 && head_fits(d, pm_max_workgroups());
     }
     static int fb_rows(const ParrotSampleDesc& d, int l) { return d.Wfg[l] ? 64 : 0; }
     static long long kslab(const ParrotSampleDesc& d, int l) { return d.H + d.E + (long long)l * d.H + fb_rows(d, l); }
     static long long persist_floats(const ParrotSampleDesc& d, int nwg) {
         const long long rows = pm_rows(d.B), S = d.S;
         if (d.cell == 1) {  // one slab per layer, the composed output's slab, h and c histories (build_persist_lstm)
-            long long n = pm_header_floats((long long)(d.L + 2) * nwg * 2);
+            long long n = pm_header_floats((long long)(d.L + 2 + (d.gmm_K > 0 ? 1 : 0)) * nwg * 2);
             for (int l = 0; l < d.L; ++l) n += (S + 1) * rows * kslab(d, l);
             n += S * rows * ((long long)d.L * d.H + d.E);
             n += 2 * (long long)d.L * (S + 1) * d.B * d.H + S * d.B * d.A;
-            return n + 4096;
+            return n + head_floats(d) + 4096;
         }
         long long n = pm_header_floats((long long)(2 * d.L + 3) * nwg);
         for (int l = 0; l < d.L; ++l) n += 2 * (S + 1) * rows * kslab(d, l);
-        n += S * rows * ((long long)d.L * d.H + d.E) + S * rows * d.R;
+        const long long ro = d.gmm_K > 0 ? 0 : d.R;  // (a GMM head has neither the readout's slab nor its history)
+        n += S * rows * ((long long)d.L * d.H + d.E) + S * rows * ro;
         n += (long long)d.L * (S + 1) * d.B * d.H + (long long)d.L * S * d.B * d.H;   // h and z histories (row-major)
-        n += S * d.B * d.R + S * d.B * d.A;
-        return n + piece_floats(d) + 4096;
+        n += S * d.B * ro + S * d.B * d.A;
+        return n + piece_floats(d) + head_floats(d) + 4096;
     }
     // the bound of a planner's carve-up: the caller's workspace; dry runs carve what the size query asks for
     long long ws_limit(bool dry, int nwg) const { return dry ? persist_floats(d, nwg) : d.persist_ws_floats; }
@@ -177,8 +197,10 @@ struct SamplePlan : PlanBase {
     int build_persist_whole() {
         if (!legacy_eligible(d)) return 0;
         const int nwg = pm_max_workgroups();
-        if (d.persist_ws_floats < persist_floats(d, nwg)) return 0;
+        if (d.persist_ws_floats < persist_floats(d, nwg) || !head_fits(d, nwg)) return 0;
         const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S, R = d.R;
+        const bool gmm = d.gmm_K > 0;  // readout and output phases -> composed head and sampling phases
+        const int NH = gmm ? d.rh_cols : 0;
         const long long BH = (long long)B * H;
         PmBuilder pb(pm_prog, false, d.persist_ws, d.persist_ws_floats, B, nwg, 2 * L + 3, 1);
         const long long rows = pb.rows;
@@ -192,13 +214,14 @@ struct SamplePlan : PlanBase {
         }
         const long long kr = (long long)L * H + E;
         float* XR = pb.take(S * rows * kr);
-        float* XO = pb.take(S * rows * R);
+        float* XO = gmm ? nullptr : pb.take(S * rows * R);
         pb.fm_end();
         float* zh[PARROT_MAX_LAYERS];
         for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
         for (int l = 0; l < L; ++l) zh[l] = pb.take(S * BH);
-        float* ro_hist = pb.take((long long)S * B * R);
+        float* ro_hist = gmm ? nullptr : pb.take((long long)S * B * R);
         float* b_hist = pb.take((long long)S * B * d.A);
+        float* head = gmm ? pb.take((long long)S * B * NH) : nullptr;
         if (pb.failed) return 0;
 
         for (int l = 0; l < L; ++l) {
@@ -242,7 +265,17 @@ struct SamplePlan : PlanBase {
             }
         }
         pb.att_rows(2, 0);
-        for (int ct = 0; ct < R / 16; ++ct) {             // readout
+        if (gmm) {
+            head_units(pb, 2 * L + 1, XR, kr, head);
+            std::vector<PmDst> fb;
+            for (int l = 0; l < L; ++l) {
+                if (!fb_rows(d, l)) continue;
+                fb.push_back(pb.dst(XG[l], 1, kx[l], (int)(kx[l] / 16) - 4));
+                fb.push_back(pb.dst(XC[l], 1, kx[l], (int)(kx[l] / 16) - 4));
+            }
+            pb.sample_rows(2 * L + 2, 0, fb);
+        }
+        for (int ct = 0; ct < R / 16 && !gmm; ++ct) {     // readout
             PmReq q = pb.gemm(2 * L + 1, XR, kr);
             PmUnit& u = q.u;
             u.W = d.Wr_t + (size_t)ct * (kr / 16) * 256;
@@ -253,7 +286,7 @@ struct SamplePlan : PlanBase {
             pb.add_dst(u, pb.dst(XO, 0, R, ct));
             pb.push(q);
         }
-        for (int ct = 0; ct < 4; ++ct) {                  // output frame x[t+1] (63 columns, padded to 64)
+        for (int ct = 0; ct < 4 && !gmm; ++ct) {          // output frame x[t+1] (63 columns, padded to 64)
             PmReq q = pb.gemm(2 * L + 2, XO, R);
             PmUnit& u = q.u;
             u.W = d.Wo_t + (size_t)ct * (R / 16) * 256;
@@ -272,6 +305,7 @@ struct SamplePlan : PlanBase {
 
         pb.att_common(d, hist_h[0]);
         pm_prog.att.b = b_hist;
+        if (gmm) samp_common(head);
         pb.add_wdst(pb.dst(XG[0], 1, kx[0], H / 16));
         pb.add_wdst(pb.dst(XC[0], 1, kx[0], H / 16));
         for (int l = 1; l < L; ++l) {
@@ -295,8 +329,31 @@ struct SamplePlan : PlanBase {
             pb.add_fill(hist_h[l] + BH, (long long)S * BH);
             pb.add_fill(zh[l], (long long)S * BH);
         }
+        if (gmm) pb.add_fill(head, (long long)S * B * NH);
         persist_ok = pb.finish(S, S);
         return 0;
+    }
+    // GMM head, both whole-K programs: the composed head's column tiles XR . Wrh_t + rh_const -> head history (row-major,
+    // write-once, no fragment-major copies), and what the sampling rows read (PmSamp)
+    void head_units(PmBuilder& pb, int slot, const float* XR, long long kr, float* head) const {
+        const int NH = d.rh_cols;
+        for (int ct = 0; ct < NH / 16; ++ct) {
+            PmReq q = pb.gemm(slot, XR, kr);
+            PmUnit& u = q.u;
+            u.W = d.Wrh_t + (size_t)ct * (kr / 16) * 256;
+            pb.add_operand(u, pm_rm(d.rh_const + 16 * ct, 0, NH));
+            u.epi = PM_EPI_LINEAR;
+            u.out = pm_rm(head + 16 * ct, (long long)d.B * NH, NH);
+            pb.push(q);
+        }
+    }
+    void samp_common(float* head) {
+        PmSamp& sp = pm_prog.samp;
+        sp.head = pm_rm(head, (long long)d.B * d.rh_cols, d.rh_cols);
+        sp.unif = d.unif; sp.noise = d.noise; sp.pi = d.pi_out;
+        sp.x = d.x + (size_t)d.B * d.ldx;
+        sp.B = d.B; sp.O = d.O; sp.K = d.gmm_K; sp.ldx = d.ldx;
+        sp.bias = d.sampling_bias; sp.eps = d.eps;
     }
     int persist_status() const { return persist_ok ? pm_status(pm_prog) : 0; }
     int steps_run(int* steps) const {
@@ -340,10 +397,12 @@ struct SamplePlan : PlanBase {
         for (int l = 0; l < L && !dry; ++l)
             if (!d.cwork[l]) return 0;
         const long long BH = (long long)B * H;
-        const int n_slots = L + 2, sATT = 1, sOUT = L + 1, hc = H / 16, ec = E / 16;
-        const int maxu = std::max(H / 4, B) <= nwg ? 1 : 2;
+        const bool gmm = d.gmm_K > 0;  // composed head phase + sampling phase in place of the composed output phase
+        const int NH = gmm ? d.rh_cols : 0;
+        const int n_slots = L + 2 + (gmm ? 1 : 0), sATT = 1, sOUT = L + 1, sSMP = L + 2, hc = H / 16, ec = E / 16;
+        const int maxu = lstm_maxu(d, nwg);
         const bool w16 = d.bf16 != 0;  // (persist_eligible_shape: the widths and the copies qualify)
-        if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT) return 0;
+        if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT || !head_fits(d, nwg)) return 0;
         PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, maxu);
         const long long rows = pb.rows;
         float* XL[PARROT_MAX_LAYERS];
@@ -358,6 +417,7 @@ struct SamplePlan : PlanBase {
         for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
         for (int l = 0; l < L; ++l) hist_c[l] = pb.take((S + 1) * BH);
         float* b_hist = pb.take((long long)S * B * d.A);
+        float* head = gmm ? pb.take((long long)S * B * NH) : nullptr;
         if (pb.failed) return 0;
 
         std::vector<PmMeta> metas;
@@ -406,7 +466,26 @@ struct SamplePlan : PlanBase {
             metas.push_back(m);
         }
         pb.att_rows(sATT, 0);
-        {
+        if (gmm) {  // head: XR -> head history; sampling rows: head history -> x[t+1] and the fed-back chunks
+            PmMeta mh;
+            mh.lag = 0; mh.slot = sOUT;
+            mh.rd.push_back(pm_acc(RES_XR, 0, 0, (int)(kr / 16)));
+            mh.wr.push_back(pm_acc(RES_HEAD, 0, 0, 1));
+            metas.push_back(mh);
+            PmMeta ms;
+            ms.lag = 0; ms.slot = sSMP;
+            ms.rd.push_back(pm_acc(RES_HEAD, 0, 0, 1));
+            ms.wr.push_back(pm_acc(RES_X, 1, 0, 1));
+            std::vector<PmDst> fb;
+            for (int l = 0; l < L; ++l)
+                if (fb_rows(d, l)) {
+                    ms.wr.push_back(pm_acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
+                    fb.push_back(pb.dst(XL[l], 1, kx[l], (int)(kx[l] / 16) - 4));
+                }
+            metas.push_back(ms);
+            head_units(pb, sOUT, XR, kr, head);
+            pb.sample_rows(sSMP, 0, fb);
+        } else {
             PmMeta m;
             m.lag = 0; m.slot = sOUT;
             m.rd.push_back(pm_acc(RES_XR, 0, 0, (int)(kr / 16)));
@@ -415,7 +494,7 @@ struct SamplePlan : PlanBase {
                 if (fb_rows(d, l)) m.wr.push_back(pm_acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
             metas.push_back(m);
         }
-        for (int ct = 0; ct < 4; ++ct) {  // output frame x[t+1] (63 columns, padded to 64)
+        for (int ct = 0; ct < 4 && !gmm; ++ct) {  // output frame x[t+1] (63 columns, padded to 64)
             PmReq q = pb.gemm(sOUT, XR, kr);
             PmUnit& u = q.u;
             u.W = d.Wro_t + (size_t)ct * (kr / 16) * 256;
@@ -439,6 +518,7 @@ struct SamplePlan : PlanBase {
 
         pb.att_common(d, hist_h[0]);
         pm_prog.att.b = b_hist;
+        if (gmm) samp_common(head);
         pb.add_wdst(pb.dst(XL[0], 1, kx[0], hc));
         for (int l = 1; l < L; ++l) pb.add_wdst(pb.dst(XL[l], 0, kx[l], hc));
         pb.add_wdst(pb.dst(XR, 0, kr, L * hc));
@@ -456,6 +536,7 @@ struct SamplePlan : PlanBase {
             pb.add_fill(hist_h[l] + BH, (long long)S * BH);
             pb.add_fill(hist_c[l] + BH, (long long)S * BH);
         }
+        if (gmm) pb.add_fill(head, (long long)S * B * NH);
         memset(pieces_info, 0, sizeof(pieces_info));
         pieces_info[13] = maxu;
         lstm_ok = pb.finish(S, S, chk, pieces_info);
@@ -505,7 +586,7 @@ struct SamplePlan : PlanBase {
     static int slotG(int l) { return l == 0 ? 0 : 2 * l + 1; }
     static int slotC(int l) { return slotG(l) + 1; }
     static bool pieces_wanted(const ParrotSampleDesc& d) {
-        return d.Wro_t && d.ro_const && env_int("PARROT_PM_PIECES", 1) != 0 && 2 * d.L + 2 <= PM_MAXSLOTS;
+        return d.gmm_K <= 0 && d.Wro_t && d.ro_const && env_int("PARROT_PM_PIECES", 1) != 0 && 2 * d.L + 2 <= PM_MAXSLOTS;
     }
     static bool piece_groups(const ParrotSampleDesc& d, std::vector<PmGroup>& gs, bool fbc) {
         const int H = d.H, E = d.E, L = d.L, n = n_phases(d, fbc), sATT = 2, sOUT = fbc ? 0 : 2 * L + 1;

@@ -90,6 +90,17 @@ struct PmBuilder {
         }
     }
 
+    void sample_rows(int slot, int lag, const std::vector<PmDst>& fb) {  // GMM sampling: one unit per batch row, placed alike;
+        for (int b = 0; b < B; ++b) {                                     // fb: the fed-back-frame chunks x[t + 1] goes to
+            PmReq q;
+            memset(&q, 0, sizeof(q));
+            q.u.kind = PM_SAMPLE; q.u.lag = lag; q.u.row = b; q.u.w_lds = -1;
+            for (const PmDst& f : fb) add_dst(q.u, f);
+            q.slot = slot; q.crit = 1; q.krows = 0;
+            reqs.push_back(q);
+        }
+    }
+
     // ---- bounded appends
     void add_dst(PmUnit& u, const PmDst& q) {
         if (u.ndst >= PM_MAXDST) { failed = true; return; }

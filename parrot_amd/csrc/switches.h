@@ -36,6 +36,9 @@
 //                                            (Python: no folded matrix)
 // PARROT_PM_FBC            1        plan     0: fed-back frame kept in the step's chain (Python: no          tests
 //                                            appended rows)
+// PARROT_PM_GMM            0        plan     1: GMM-head models decode on the sampling machine too (composed   tests, tools
+//                                            head phase + sampling phase; GRU whole-K and LSTM programs).
+//                                            Python prepares the composed head and lifts its refusals when 1
 // PARROT_PM_DUMP_PLAN      unset    plan,    set: print the sampling machine's pieces and the barrier words  development
 //                                   failure  of a persistent launch that gave up
 // PARROT_SR_PERSIST        1        plan     0: SampleRNN sampling without its persistent kernel             tests

@@ -1503,31 +1503,41 @@ class Parrot(Brick):
                         continue
                     pm['tiled'][(l, key)] = torch.empty(rows, wd, **f)
                     getattr(d, f'W{key}_t')[l] = pm['tiled'][(l, key)].data_ptr()
-            pm['Wr_t'] = torch.empty(L * H + E, R, **f)
-            pm['Wo_pad'], pm['Wo_t'] = torch.zeros(R, 64, **f), torch.empty(R, 64, **f)
-            pm['bo_pad'] = torch.zeros(64, **f)
-            d.Wr_t, d.Wo_t, d.bo_pad = pm['Wr_t'].data_ptr(), pm['Wo_t'].data_ptr(), pm['bo_pad'].data_ptr()
-            if ws['oadd'] is not None:
-                pm['oadd_pad'] = torch.zeros(N, 64, **f)
-                d.oadd_pad = pm['oadd_pad'].data_ptr()
-            # readout -> output is linear here (model.py:992-1013, MSE head, no layer norm): the machine takes the
-            # composed matrix Wr . Wo and the constant rows (br + radd) . Wo + bo + oadd, and x[t+1] costs ONE phase
-            pm['Wro'], pm['Wro_t'] = torch.empty(L * H + E, 64, **f), torch.empty(L * H + E, 64, **f)
-            pm['ro_const'] = torch.zeros(N, 64, **f)
-            d.Wro_t, d.ro_const = pm['Wro_t'].data_ptr(), pm['ro_const'].data_ptr()
-            if not lstm and N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
-                # round 5: the attention projection as an [H, 32] matrix (fragment-major): layer 0's candidate units fold
-                # their tile's share of h_1 . Watt into their epilogue (ParrotSampleDesc::Watt_t)
-                pm['Watt_pad'], pm['Watt_t'] = torch.zeros(H, 32, **f), torch.empty(H, 32, **f)
-                d.Watt_t = pm['Watt_t'].data_ptr()
-            # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
-            # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
-            if not lstm and L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
-                for key, wd, suf, mat, rec in self._groups:
-                    rows = H + E + 64 + H
-                    pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)
-                    pm['tiled'][('x', key)] = torch.empty(rows, wd, **f)
-                    getattr(d, f'W{key}x_t')[0] = pm['tiled'][('x', key)].data_ptr()
+            if gmm:  # (the refusal is '' for a GMM head only under PARROT_PM_GMM=1)
+                # readout stack -> three head projections is linear without layer norm (the reasoning of
+                # compose_readout_output): the machine takes Wr . [W_mu | W_sig | W_co], columns zero-padded to a multiple
+                # of 16, and the constant rows with the speaker terms (ParrotSampleDesc::Wrh_t / rh_const / rh_cols)
+                NH16 = (2 * O * K + K + 15) // 16 * 16
+                pm['Wh_pad'], pm['ch_pad'] = torch.zeros(R, NH16, **f), torch.zeros(N, NH16, **f)
+                pm['Wrh'], pm['Wrh_t'] = torch.empty(L * H + E, NH16, **f), torch.empty(L * H + E, NH16, **f)
+                pm['rh_const'] = torch.zeros(N, NH16, **f)
+                d.Wrh_t, d.rh_const, d.rh_cols = pm['Wrh_t'].data_ptr(), pm['rh_const'].data_ptr(), NH16
+            else:
+                pm['Wr_t'] = torch.empty(L * H + E, R, **f)
+                pm['Wo_pad'], pm['Wo_t'] = torch.zeros(R, 64, **f), torch.empty(R, 64, **f)
+                pm['bo_pad'] = torch.zeros(64, **f)
+                d.Wr_t, d.Wo_t, d.bo_pad = pm['Wr_t'].data_ptr(), pm['Wo_t'].data_ptr(), pm['bo_pad'].data_ptr()
+                if ws['oadd'] is not None:
+                    pm['oadd_pad'] = torch.zeros(N, 64, **f)
+                    d.oadd_pad = pm['oadd_pad'].data_ptr()
+                # readout -> output is linear here (model.py:992-1013, MSE head, no layer norm): the machine takes the
+                # composed matrix Wr . Wo and the constant rows (br + radd) . Wo + bo + oadd, and x[t+1] costs ONE phase
+                pm['Wro'], pm['Wro_t'] = torch.empty(L * H + E, 64, **f), torch.empty(L * H + E, 64, **f)
+                pm['ro_const'] = torch.zeros(N, 64, **f)
+                d.Wro_t, d.ro_const = pm['Wro_t'].data_ptr(), pm['ro_const'].data_ptr()
+                if not lstm and N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
+                    # round 5: the attention projection as an [H, 32] matrix (fragment-major): layer 0's candidate units fold
+                    # their tile's share of h_1 . Watt into their epilogue (ParrotSampleDesc::Watt_t)
+                    pm['Watt_pad'], pm['Watt_t'] = torch.zeros(H, 32, **f), torch.empty(H, 32, **f)
+                    d.Watt_t = pm['Watt_t'].data_ptr()
+                # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
+                # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
+                if not lstm and L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
+                    for key, wd, suf, mat, rec in self._groups:
+                        rows = H + E + 64 + H
+                        pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)
+                        pm['tiled'][('x', key)] = torch.empty(rows, wd, **f)
+                        getattr(d, f'W{key}x_t')[0] = pm['tiled'][('x', key)].data_ptr()
             n = int(_lib.load().parrot_sample_persist_floats(C.byref(d)))
             if n > 0:
                 pm['ws'] = torch.zeros(n, **f)
@@ -1560,7 +1570,11 @@ class Parrot(Brick):
         switches that exist on the machine only (decode_dtype='bf16', sample_until_end) refuse with it."""
         H, E, R, O = self.rnn_h_dim, self.encoded_input_dim, self.readouts_dim, self.output_dim
         if self.which_cost != 'MSE':
-            return "needs which_cost='MSE': the GMM head does not decode on the persistent machine"
+            # the one read of the switch on this side (csrc/switches.h): the GMM head on the machine is opt-in
+            if self.which_cost != 'GMM' or env_int('PARROT_PM_GMM', 0) == 0:
+                return "needs which_cost='MSE': the GMM head does not decode on the persistent machine"
+            if self.k_gmm > 64:
+                return f"covers at most 64 mixture components (one lane of the sampling wave each), got {self.k_gmm}"
         if self.layer_norm:
             return "does not cover layer_norm=True (that decode runs as per-step launches)"
         if N > 64:
@@ -1578,6 +1592,8 @@ class Parrot(Brick):
         if self.cell_type != 'lstm':
             return "needs cell_type='lstm': GRU decoders have no bf16 decode path"
         why = self._decode_machine_refusal(N)
+        if not why and self.which_cost != 'MSE':  # (PARROT_PM_GMM=1: the machine takes the head, with f32 operands only)
+            return "needs which_cost='MSE': the GMM head decodes on the persistent machine with f32 operands only"
         if not why and (H % 32 or E % 32):
             return (f"needs rnn_h_dim and the encoder width to be multiples of 32 (v_mfma_f32_16x16x32_bf16 walks K in "
                     f"steps of 32), got {H} and {E}")
@@ -1687,9 +1703,16 @@ class Parrot(Brick):
         _lib.call('parrot_sample_run', ws['plan'], ops._stream())
         if 'pm' in ws:  # persistent machine: a launch that gave up leaves invalid frames -- fail loudly (synchronises)
             _lib.call('parrot_sample_status', ws['plan'])
+        self._decode_path = 'machine' if _lib.load().parrot_sample_is_persistent(ws['plan']) else 'launches'
         sx = ws['x'][1:, :, :O]
         pi = ws['pi_out'] if self.which_cost == 'GMM' else sx
         return [sx, ws['kappa'][1:], ws['w'][1:], pi, ws['phi'], ws['a']]
+
+    @property
+    def decode_path(self):
+        """What the last decode call (sample_model*, sample_until_end*) ran on: 'machine' (the persistent phase machine), or
+        'launches' (per-step launches); None before the first."""
+        return getattr(self, '_decode_path', None)
 
     def _refresh_sample_machine_weights(self, ws):
         """Fragment-major weight copies of the decode machine from the current parameters."""
@@ -1713,30 +1736,52 @@ class Parrot(Brick):
                     if (l + 1) in self._fb_layers:
                         cat[kl:kl + O].copy_(self._p(f'/out_to_h{l + 1}/fork_rnn{l + 1}_{suf}.W'))
                     tile(cat, pm['tiled'][(l, key)], lstm_H)
-            tile(st['dec.Wr'], pm['Wr_t'])
-            pm['Wo_pad'][:, :O].copy_(self._p('/readout_to_output.W'))
-            tile(pm['Wo_pad'], pm['Wo_t'])
-            pm['bo_pad'][:O].copy_(self._p('/readout_to_output.b'))
-            if 'oadd_pad' in pm:
-                pm['oadd_pad'][:, :O].copy_(ws['oadd'])
-            Wro, c = compose_readout_output(st['dec.Wr'], pm['Wo_pad'], ws['br'], ws['radd'], pm['bo_pad'],
-                                            pm.get('oadd_pad'), pm['ro_const'].shape[0])
-            pm['Wro'].copy_(Wro)
-            tile(pm['Wro'], pm['Wro_t'])
-            pm['ro_const'].copy_(c)
-            if 'Watt_t' in pm:
-                A3 = 3 * self.attention_size
-                pm['Watt_pad'][:, :A3].copy_(st['dec.WattT'].t())
-                tile(pm['Watt_pad'], pm['Watt_t'])
-            for key, wd, suf, mat, rec in self._groups:
-                if ('x', key) not in pm['cat']:
-                    continue
-                # x . Wf = x_pre . Wf + h_{L-1} . (A . Wf) with A = Wro[(L-1)H : L H]: composed in double, rounded once
-                cat, base = pm['cat'][('x', key)], pm['cat'][(0, key)]
-                cat[:H + E + 64].copy_(base)
-                A_last = Wro[(L - 1) * H:L * H].double()
-                cat[H + E + 64:].copy_((A_last @ base[H + E:H + E + 64].double()).float())
-                tile(cat, pm['tiled'][('x', key)])
+            if 'Wrh_t' in pm:  # GMM head: Wr . [W_mu | W_sig | W_co] and its constant rows, composed in double, rounded once
+                col, Wh, ch = 0, pm['Wh_pad'], pm['ch_pad']
+                for nm, key in (('mu', 'gmm_mu'), ('sig', 'gmm_sigma'), ('co', 'gmm_coeff')):
+                    W = self._p(f'/readout_to_output/fork_{key}.W')
+                    n = W.shape[1]
+                    Wh[:, col:col + n].copy_(W)
+                    ch[:, col:col + n].copy_(self._p(f'/readout_to_output/fork_{key}.b').unsqueeze(0).expand(ch.shape[0], -1))
+                    if self.use_speaker:
+                        ch[:, col:col + n].add_(ws['add_' + nm])
+                    col += n
+                Wrh, c = compose_readout_output(st['dec.Wr'], Wh, ws['br'], ws['radd'], torch.zeros_like(ch[0]), ch, ch.shape[0])
+                pm['Wrh'].copy_(Wrh)
+                tile(pm['Wrh'], pm['Wrh_t'])
+                pm['rh_const'].copy_(c)
+            else:
+                self._refresh_mse_head_weights(ws, tile)
+
+    def _refresh_mse_head_weights(self, ws, tile):
+        """The MSE head's part of _refresh_sample_machine_weights: readout stack, output projection, their composition, the
+        folded attention projection and the composed feedback rows (called under no_grad)."""
+        pm, st = ws['pm'], self.store.storage
+        H, E, L, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.output_dim
+        tile(st['dec.Wr'], pm['Wr_t'])
+        pm['Wo_pad'][:, :O].copy_(self._p('/readout_to_output.W'))
+        tile(pm['Wo_pad'], pm['Wo_t'])
+        pm['bo_pad'][:O].copy_(self._p('/readout_to_output.b'))
+        if 'oadd_pad' in pm:
+            pm['oadd_pad'][:, :O].copy_(ws['oadd'])
+        Wro, c = compose_readout_output(st['dec.Wr'], pm['Wo_pad'], ws['br'], ws['radd'], pm['bo_pad'],
+                                        pm.get('oadd_pad'), pm['ro_const'].shape[0])
+        pm['Wro'].copy_(Wro)
+        tile(pm['Wro'], pm['Wro_t'])
+        pm['ro_const'].copy_(c)
+        if 'Watt_t' in pm:
+            A3 = 3 * self.attention_size
+            pm['Watt_pad'][:, :A3].copy_(st['dec.WattT'].t())
+            tile(pm['Watt_pad'], pm['Watt_t'])
+        for key, wd, suf, mat, rec in self._groups:
+            if ('x', key) not in pm['cat']:
+                continue
+            # x . Wf = x_pre . Wf + h_{L-1} . (A . Wf) with A = Wro[(L-1)H : L H]: composed in double, rounded once
+            cat, base = pm['cat'][('x', key)], pm['cat'][(0, key)]
+            cat[:H + E + 64].copy_(base)
+            A_last = Wro[(L - 1) * H:L * H].double()
+            cat[H + E + 64:].copy_((A_last @ base[H + E:H + E + 64].double()).float())
+            tile(cat, pm['tiled'][('x', key)])
 
     def sample_model(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, num_steps):
         """Parrot.sample_model (model.py:1061-1083): numpy in, list of numpy arrays out

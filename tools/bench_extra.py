@@ -1,15 +1,15 @@
 """Secondary measurements (BASELINE configs[2] decode latency, the same loop with LSTM decoders -- persistent machine
 with bf16 operands (decode_dtype='bf16') against the f32 machine against the per-step launches, alternating child
-processes --, the configs[2] decode that stops at the end of the utterance against the one that runs all its steps,
+processes --, both with a GMM head (k_gmm = 20) on the machine (PARROT_PM_GMM=1) against the launches, the configs[2] decode that stops at the end of the utterance against the one that runs all its steps,
 configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
 
   bench_extra.py                         everything, one JSON line
   bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_stop, decode_lstm2_1024, decode_lstm3_1536,
-                                         samplernn_cfg5, mulaw)
+                                         decode_gmm_gru2_1024, decode_gmm_lstm2_1024, samplernn_cfg5, mulaw)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
-  bench_extra.py --reps N                on / off alternations of the LSTM decode entries (default 3)
+  bench_extra.py --reps N                on / off alternations of the LSTM and GMM decode entries (default 3)
   bench_extra.py --gmm_head [--reps N]   this leg alone: the GMM head's cost and gradient, fused HIP kernels against the torch
                                          path (head alone at M = 51 200, O = 63, K = 20 and the configs[1] training step with
                                          that head; N >= 5 alternations, bytes moved, TB/s, peak memory)"""
@@ -28,12 +28,17 @@ def _arg(name, dflt=None):
     return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else dflt
 
 
-ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "samplernn_cfg5", "mulaw")
+ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
+       "samplernn_cfg5", "mulaw")
 only = tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
     "decode_lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024),
     "decode_lstm3_1536": dict(num_layers=3, rnn_h_dim=1536, readouts_dim=1536),
+}
+GMM_SHAPES = {  # the decode_cfg3 / decode_lstm2_1024 shapes with the mixture-density head (which_cost='GMM', k_gmm=20)
+    "decode_gmm_gru2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='gru', which_cost='GMM', k_gmm=20),
+    "decode_gmm_lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='lstm', which_cost='GMM', k_gmm=20),
 }
 dev = torch.device("cuda:0")
 out = {}
@@ -41,7 +46,8 @@ g = torch.Generator().manual_seed(0)
 
 
 def decode(kw, dump=None, decode_dtype='float32'):
-    """Autoregressive decode, batch 16, 1000 frames, MSE head (greedy), hipGraph: three runs, the last one reported."""
+    """Autoregressive decode, batch 16, 1000 frames, MSE head (greedy; a GMM head: fixed unif / noise), hipGraph: three
+    runs, the last one reported."""
     from parrot_amd import _lib
     from parrot_amd.model import Parrot
     m = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, decode_dtype=decode_dtype,
@@ -50,9 +56,12 @@ def decode(kw, dump=None, decode_dtype='float32'):
     N, U, S = 16, 100, 1000
     lab = torch.randint(0, 43, (N, U), generator=g)
     lm = torch.ones(N, U)
+    rnd = {}
+    if kw.get('which_cost') == 'GMM':
+        rnd = dict(unif=torch.rand(S, N, generator=g).to(dev), noise=torch.randn(S, N, 63, generator=g).to(dev))
     for rep in range(3):
         torch.cuda.synchronize(); t0 = time.time()
-        outs = m.sample_model_device(lab, lm, None, N, S)
+        outs = m.sample_model_device(lab, lm, None, N, S, **rnd)
         torch.cuda.synchronize(); dt = time.time() - t0
     if dump:
         np.save(dump, outs[0].cpu().numpy())
@@ -230,6 +239,10 @@ if "--gmm_head" in sys.argv:  # this leg alone, one JSON line
     print(json.dumps({"gmm_head": gmm_head(max(5, int(_arg("--reps", "5"))))}))
     sys.exit(0)
 
+if "--child-gmm" in sys.argv:  # one GMM-head decode measurement under the caller's environment
+    print(json.dumps(decode(GMM_SHAPES[_arg("--child-gmm")])))
+    sys.exit(0)
+
 if "--child" in sys.argv:  # one LSTM decode measurement under the caller's environment
     print(json.dumps(decode(dict(LSTM_SHAPES[_arg("--child")], cell_type='lstm'),
                             decode_dtype=_arg("--decode-dtype", "float32"))))
@@ -264,6 +277,28 @@ for name in LSTM_SHAPES:
                  "us_per_step_machine": runs["machine"], "us_per_step_launches": runs["launches"],
                  "machine_faster": max(runs["machine"]) < min(runs["launches"]),
                  "bf16_faster": max(runs["machine_bf16"]) < min(runs["machine"])}
+
+# ---- GMM head: the machine (PARROT_PM_GMM=1) against the per-step launches (the switch unset) of the same call, each run in a
+# child process of its own, alternating; the yardstick is the launch path, every repetition is listed
+for name in GMM_SHAPES:
+    if name not in only:
+        continue
+    runs = {"machine": [], "launches": []}
+    env_off = {k: v for k, v in os.environ.items() if k != "PARROT_PM_GMM"}
+    for rep in range(int(_arg("--reps", "3"))):
+        for key, env in (("machine", dict(env_off, PARROT_PM_GMM="1")), ("launches", env_off)):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child-gmm", name], capture_output=True, text=True,
+                               env=env, timeout=600)
+            if r.returncode != 0:  # (a fault in a child ends the measurement: nothing more is started on the device)
+                sys.stderr.write(r.stdout + r.stderr)
+                sys.exit(r.returncode)
+            res = json.loads(r.stdout.strip().splitlines()[-1])
+            assert (res["machine"] != 0) == (key == "machine"), (key, res)
+            runs[key].append(res["us_per_step"])
+    out[name] = {"batch": 16, "frames": 1000, "k_gmm": 20, "us_per_step_machine": runs["machine"],
+                 "us_per_step_launches": runs["launches"],
+                 "spread_us": {k: round(max(v) - min(v), 2) for k, v in runs.items()},
+                 "machine_faster": max(runs["machine"]) < min(runs["launches"])}
 
 # ---- configs[4]: SampleRNN 3-tier GRU D=1024, batch 32, greedy, 16 kHz mu-law
 if "samplernn_cfg5" in only:
