@@ -126,6 +126,14 @@ int parrot_gemm_bf16in_ex(const void* A, int lda, int transA, const void* B, int
 
 /* out[n] (+)= sum_m x[m, n]  -- bias gradients. */
 int parrot_colsum(const float* x, long long M, int N, int ld, float* out, int accumulate, void* stream);
+/* Which kernel a parrot_colsum call with these arguments takes and how many row slices it plans (introspection, as
+ * parrot_gemm_route): info2 = {0 colsum_kernel (one column per lane) / 1 colsum4_kernel (four columns per lane: N and ld
+ * multiples of 4, x and out 16-byte aligned, M >= 64), row slices}.  More than one slice: the kernel writes partial sums
+ * and colsum_finish_kernel adds them in slice order.  x and out are only inspected for their alignment, never
+ * dereferenced (out = NULL: an aligned result); no HIP call is made, so the query works without a device.  The plan is
+ * the one outside stream capture; inside a capture there is no partial buffer and the scalar kernel runs unsplit
+ * wherever more than one slice is planned.  Returns PARROT_ERR_BADARG for x or info2 NULL, M < 0 or N < 1. */
+int parrot_colsum_route(const float* x, long long M, int N, int ld, const float* out, int* info2);
 
 /* ------------------------------------------------------------------------------------------
  * One GatedRecurrent step (Blocks GatedRecurrent.apply(inputs, gate_inputs, states,

@@ -193,6 +193,7 @@ SIGNATURES = {
     "samplernn_weightnorm_fold": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _vp]),
     "samplernn_weightnorm_fold_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp]),
     "parrot_colsum": (_i, [_vp, _ll, _i, _i, _vp, _i, _vp]),
+    "parrot_colsum_route": (_i, [_vp, _ll, _i, _i, _vp, C.POINTER(C.c_int)]),
     "parrot_gru_step_fwd": (_i, [_vp] * 11 + [_i, _i, _vp]),
     "parrot_gru_step_bwd": (_i, [_vp] * 11 + [_i, _i, _vp]),
     "parrot_label_tables_supported": (_i, [_ll, _i]),

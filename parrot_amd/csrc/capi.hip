@@ -282,6 +282,15 @@ int parrot_colsum(const float* x, long long M, int N, int ld, float* out, int ac
     return colsum_launch(x, M, N, ld, out, accumulate, (hipStream_t)stream);
 }
 
+int parrot_colsum_route(const float* x, long long M, int N, int ld, const float* out, int* info2) {
+    // (no HIP call here, not even PH_ENTRY's: the query works without a device)
+    if (!x || !info2 || M < 0 || N < 1) return PARROT_ERR_BADARG;
+    const ColsumRoute r = colsum_route(x, M, N, ld, out);
+    info2[0] = r.vec4;
+    info2[1] = r.ysplit;
+    return 0;
+}
+
 int parrot_gru_step_fwd(const float* h, const float* inputs, const float* gate_inputs, const float* mask,
                         const float* Wg, const float* Wc, float* h_out, float* z, float* r, float* rh,
                         float* c, int B, int H, void* stream) { PH_ENTRY();

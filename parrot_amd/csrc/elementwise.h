@@ -145,6 +145,10 @@ __device__ __forceinline__ void gru_state_bwd_rows4(const GruStateBwdChain& c, i
 
 int gru_state_bwd_launch(const GruStateBwdArgs& g, hipStream_t stream);
 int colsum_launch(const float* x, long long M, int N, int ld, float* out, int accumulate, hipStream_t stream);
+// The plan of a colsum_launch call outside stream capture: vec4 = 1 colsum4_kernel (16-byte loads), 0 colsum_kernel;
+// ysplit row slices (> 1: partial sums and colsum_finish_kernel).  Host arithmetic, no HIP call.
+struct ColsumRoute { int vec4, ysplit; };
+ColsumRoute colsum_route(const float* x, long long M, int N, int ld, const float* out);
 int sumsq_launch(const float* x, size_t n, float* out, hipStream_t stream);
 int adam_clip_launch(float* p, const float* g, float* m, float* v, size_t n, const float* gnorm_sq,
                      float grad_scale, float threshold, float lr_t, float b1, float b2, float eps,

@@ -348,14 +348,38 @@ int gru_state_bwd_launch(const GruStateBwdArgs& g, hipStream_t stream) {
     return (int)hipGetLastError();
 }
 
-int colsum_launch(const float* x, long long M, int N, int ld, float* out, int accumulate, hipStream_t stream) {
-    if (M < 0 || N < 1) return PH_ERR_BADARG;
+// The scalar kernel's row slices: 64-column blocks, at least 256 rows per slice.
+static int colsum_scalar_ysplit(long long M, int N) {
+    int ysplit = 1;
+    const int bx = ceil_div(N, 64);
+    while (bx * ysplit < 512 && M / (ysplit * 2) >= 256) ysplit *= 2;
+    return ysplit;
+}
+
+// Which kernel a column sum takes and how many row slices it plans.  The one copy of the rule: colsum_launch launches
+// what this returns and parrot_colsum_route reports it.  The pointers are only looked at for their alignment.
+ColsumRoute colsum_route(const float* x, long long M, int N, int ld, const float* out) {
+    ColsumRoute r;
     if (!(N & 3) && !(ld & 3) && !((uintptr_t)x & 15) && !((uintptr_t)out & 15) && M >= 64) {
         const int bx = ceil_div(N, 256);
         int ysplit = 1;
         // one workgroup per CU: more row slices only lengthen the serial finish pass (8 column blocks x 128 slices
         // measured 19 us + 33 us of finish for [51200, 2048]; 32 slices: the finish reads a quarter)
         while (bx * ysplit < 256 && M / (ysplit * 2) >= 64) ysplit *= 2;
+        r.vec4 = 1;
+        r.ysplit = ysplit;
+        return r;
+    }
+    r.vec4 = 0;
+    r.ysplit = colsum_scalar_ysplit(M, N);
+    return r;
+}
+
+int colsum_launch(const float* x, long long M, int N, int ld, float* out, int accumulate, hipStream_t stream) {
+    if (M < 0 || N < 1) return PH_ERR_BADARG;
+    ColsumRoute r = colsum_route(x, M, N, ld, out);
+    if (r.vec4) {
+        const int bx = ceil_div(N, 256), ysplit = r.ysplit;
         float* part = ysplit > 1 ? ew_scratch.get(stream, (size_t)ysplit * N) : nullptr;
         if (ysplit == 1 || part) {
             hipLaunchKernelGGL(colsum4_kernel, dim3(bx, ysplit), dim3(256), 0, stream, x, M, N, ld, ysplit > 1 ? part : out,
@@ -365,10 +389,10 @@ int colsum_launch(const float* x, long long M, int N, int ld, float* out, int ac
                                    accumulate);
             return (int)hipGetLastError();
         }
+        r.ysplit = colsum_scalar_ysplit(M, N);  // no partial buffer (stream capture): the scalar kernel's plan
     }
-    int ysplit = 1;
+    int ysplit = r.ysplit;
     const int bx = ceil_div(N, 64);
-    while (bx * ysplit < 512 && M / (ysplit * 2) >= 256) ysplit *= 2;
     if (ysplit > 1) {  // row slices -> partial sums -> fixed-order finish (deterministic, no float atomics)
         float* part = ew_scratch.get(stream, (size_t)ysplit * N);
         if (!part) ysplit = 1;

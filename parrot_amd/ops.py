@@ -244,6 +244,24 @@ def colsum(x: torch.Tensor, out=None, accumulate=False) -> torch.Tensor:
     return out
 
 
+def colsum_route(x: torch.Tensor, out=None):
+    """(vec4, ysplit) of the call `colsum(x, out)` makes (parrot_colsum_route): whether the 16-byte kernel takes it and
+    the planned number of row slices.  Nothing is launched."""
+    import ctypes as C
+    _chk(x, "x")
+    N = x.shape[-1]
+    M = x.numel() // N if N else 0
+    if x.dim() == 2 and x.stride(1) == 1:
+        px, ld = x.data_ptr(), x.stride(0)
+    elif x.is_contiguous():
+        px, ld = x.data_ptr(), N
+    else:
+        px, ld = 4096, N  # colsum sums a fresh contiguous copy: an aligned allocation
+    info = (C.c_int * 2)(-1, -1)
+    _lib.call("parrot_colsum_route", px, M, N, ld, None if out is None else out.data_ptr(), info)
+    return info[0], info[1]
+
+
 class _LinearFn(torch.autograd.Function):
     """y = x . W + b with x [..., in], W [in, out] (Blocks Linear.apply / lib.ops.Linear)."""
 

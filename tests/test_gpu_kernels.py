@@ -70,9 +70,6 @@ def test_big_gemm_splitk_bias_batched(dev):
     assert_close(out2, acc.double().cpu() + a.double().cpu().t() @ b.double().cpu(), 5e-6, "split-k accumulate")
     assert_close(o, x.double().cpu() @ y.double().cpu(), 3e-6, "batched")
     assert_close(osub, sub.double().cpu() @ w.double().cpu(), 3e-6, "strided A")
-    assert_close(ops.colsum(big), big.double().cpu().sum(0), 1e-5, "colsum")
-    tall = _rand((40000, 70), dev, 13)
-    assert_close(ops.colsum(tall), tall.double().cpu().sum(0), 2e-5, "colsum tall")
 
 
 # ---- split-bf16 products (PARROT_PRECISION_BF16X3, bgs_kernel): f32 operands, six bf16 MFMAs per block ---------------
