@@ -108,6 +108,17 @@ int parrot_gemm_route(const float* A, int lda, int transA, const float* B, int l
                       float alpha, int act, int nbatch, long long strideA, long long strideB, int split_k, int has_gate,
                       int* kernel, int* slices);
 
+/* How the host lays out one step-kernel launch of njobs (1..9) jobs (introspection, as parrot_gemm_route; no HIP call is
+ * made, so the query works without a device).  Job q has M[q] rows, N[q] output columns and one K[q]-deep operand
+ * segment (K % 16 != 0 puts the job on the generic path, which keeps the whole launch on one column tile per
+ * workgroup); lstm_H (or NULL) > 0 marks an LSTM-cell job with N = 4 * lstm_H gate-interleaved columns.  info gets
+ * 5 + njobs values: {z-mode 0/1, 10 * MB + NB (row and column blocks of 16 per workgroup), grid.x, grid.y, grid.z,
+ * then per job the number of workgroups along x up to and including that job}.  z-mode = every job has the same number
+ * of workgroups: grid.z enumerates the jobs and the kernel instantiation that never reads the launch header runs;
+ * otherwise the jobs lie back to back along x and the kernel finds its job in that prefix table.  The wide bf16 kernel,
+ * which takes some bf16-operand launches instead, is not part of the query. */
+int parrot_step_launch_mode(int njobs, const int* M, const int* N, const int* K, const int* lstm_H, int* info);
+
 /* bf16-IN weight-gradient product (round 4): C[M,N] (+)= A^T . B with A [K, M] and B [K, N] ALREADY bf16 in device
  * memory (row-major, leading dimensions in elements, both multiples of 8; M, N multiples of 8; 16-byte aligned),
  * f32 accumulation, f32 C; deterministic split-K as parrot_gemm (split_k = 0: automatic).  parrot_to_bf16 makes the

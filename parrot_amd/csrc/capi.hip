@@ -228,6 +228,33 @@ int parrot_gemm_route(const float* A, int lda, int transA, const float* B, int l
     return 0;
 }
 
+int parrot_step_launch_mode(int njobs, const int* M, const int* N, const int* K, const int* lstm_H, int* info) {
+    // (no HIP call here: the query works without a device)
+    if (!M || !N || !K || !info || njobs < 1 || njobs > SK_MAXJOB) return PARROT_ERR_BADARG;
+    SkJob jobs[SK_MAXJOB];
+    for (int q = 0; q < njobs; ++q) {
+        if (M[q] < 1 || N[q] < 1 || K[q] < 1) return PARROT_ERR_BADARG;
+        SkJob& j = jobs[q];
+        sk_job_init(j);
+        const float* aligned_base = reinterpret_cast<const float*>(uintptr_t(4096));  // (inspected for alignment only)
+        j.nseg = 1;
+        j.seg[0] = sk_seg(aligned_base, (K[q] + 3) & ~3, aligned_base, (N[q] + 3) & ~3, K[q], 0);
+        j.M = M[q]; j.N = N[q];
+        j.H = lstm_H && lstm_H[q] > 0 ? lstm_H[q] : N[q];
+        j.epi = lstm_H && lstm_H[q] > 0 ? SK_EPI_LSTM : SK_EPI_LINEAR;
+    }
+    SkLaunch Lin, L;
+    const int rc = sk_make_launch(Lin, jobs, njobs);
+    if (rc) return rc;
+    dim3 grid;
+    size_t lds;
+    int mbnb;
+    sk_prepare(Lin, L, grid, lds, mbnb);
+    info[0] = L.zmode; info[1] = mbnb; info[2] = (int)grid.x; info[3] = (int)grid.y; info[4] = (int)grid.z;
+    for (int q = 0; q < njobs; ++q) info[5 + q] = L.tile_end[q];
+    return 0;
+}
+
 int parrot_to_bf16(const float* x, void* y, long long n, void* stream) { PH_ENTRY();
     if (!x || !y || n < 0) return PARROT_ERR_BADARG;
     return bg_to_bf16_launch(x, y, n, (hipStream_t)stream);

@@ -485,6 +485,12 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
     for (int rb = 0; rb < MB; ++rb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) red[((wave * MB + rb) * NB + nb) * 64 + lane] = acc[rb][nb];
+    // The descriptor fields the epilogue reads, requested in one batch BEFORE the meeting point: the entry batch's registers
+    // do not survive the K loop, and read where the epilogue first needs them they came back one conditional block at a
+    // time -- four dependent s_load / s_waitcnt rounds between the barrier and the first store.  Here their latency lies
+    // under the barrier wait and they are live behind it.  (Still no local copy of the descriptor: DESIGN 3.1 item 2.)
+    asm volatile("" ::"s"(job.epi), "s"(job.act), "s"(job.accumulate), "s"(job.H), "s"(job.colmode), "s"(job.bias), "s"(job.out),
+                 "s"(job.o1), "s"(job.o2), "s"(job.mask), "s"(job.ldo), "s"(job.ldo1), "s"(job.ldo2), "s"(job.N), "s"(job.M));
     __syncthreads();
     SK_STAMP(3);
     if (wave >= EWAVES) return;
@@ -597,25 +603,36 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
 #endif
 }
 
-template <int MB, int NB>
+// Job of workgroup bx in a launch whose jobs lie back to back along x (the prefix table of sk_prepare); bx becomes the
+// workgroup's index inside its job.  The launch header (njobs and the table: one line of the argument block) comes in ONE
+// batch of scalar loads (the heterogeneous kernels request it at their entry already, with the scalars that decide a
+// workgroup's role: the batch here then finds the registers filled), and the start of the job is picked from the registers
+// that batch filled: written as `tile_end[j - 1]` it was one more dependent s_load behind the search.
+__device__ __forceinline__ int sk_find_job(const SkLaunch& L, int& bx) {
+    asm volatile("" ::"s"(L.njobs), "s"(L.tile_end[0]), "s"(L.tile_end[1]), "s"(L.tile_end[2]), "s"(L.tile_end[3]),
+                 "s"(L.tile_end[4]), "s"(L.tile_end[5]), "s"(L.tile_end[6]), "s"(L.tile_end[7]));
+    int j = 0, beg = 0;
+#pragma unroll
+    for (int q = 0; q < SK_MAXJOB - 1; ++q) {
+        const bool nx = q < L.njobs - 1 && bx >= L.tile_end[q];
+        j = nx ? q + 1 : j;
+        beg = nx ? L.tile_end[q] : beg;
+    }
+    bx -= beg;
+    return j;
+}
+
+// ZMODE (the host's choice, sk_prepare): launches whose jobs all have the same number of workgroups use grid.z = job.  The
+// descriptor address then follows from the block id alone: the wave's FIRST scalar loads fetch the job itself and the launch
+// header is never read (as a run-time flag in that header, z-mode cost every wave one cold round trip to learn that it
+// did not need the header).  Otherwise the workgroups of the jobs are laid out back to back along x and the job is found
+// in the prefix table (a z-grid sized for the largest job was measured slower there: 59 -> 65 ms backward at cfg2).
+template <int MB, int NB, bool ZMODE>
 __global__ __launch_bounds__(SK_THREADS) void sk_kernel(const SkLaunch L) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];
     f32x4* red = reinterpret_cast<f32x4*>(sk_smem);
-    // Launches whose jobs all have the same number of workgroups use grid.z = job: the descriptor address then
-    // follows from the block id alone and the wave's first scalar loads fetch the job itself.  Otherwise the
-    // workgroups of the jobs are laid out back to back along x and the job is found in the prefix table
-    // (a z-grid sized for the largest job was measured slower there: 59 -> 65 ms backward at cfg2).
     int j = blockIdx.z, bx = blockIdx.x;
-    // the launch header in one batch of scalar loads (zmode, njobs and the prefix table sit in one line)
-    asm volatile("" ::"s"(L.zmode), "s"(L.njobs), "s"(L.tile_end[0]), "s"(L.tile_end[1]), "s"(L.tile_end[2]), "s"(L.tile_end[3]),
-                 "s"(L.tile_end[4]), "s"(L.tile_end[5]), "s"(L.tile_end[6]), "s"(L.tile_end[7]));
-    if (!L.zmode) {
-        j = 0;
-#pragma unroll
-        for (int q = 0; q < SK_MAXJOB - 1; ++q)
-            if (q < L.njobs - 1 && bx >= L.tile_end[q]) j = q + 1;
-        bx -= (j > 0 ? L.tile_end[j - 1] : 0);
-    }
+    if (!ZMODE) j = sk_find_job(L, bx);
     const SkJob& job = L.job[j];
     const int tile0 = bx * NB;  // first 16-column tile of this workgroup
     if (NB > 1 || job.aligned) sk_body<MB, NB, true>(job, tile0, red);  // fast path: branch-free operand fetch
@@ -635,6 +652,12 @@ __global__ __launch_bounds__(SK_THREADS, 4) void ska_kernel(const SkLaunch L, co
                                                          const int att_last) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];
     int bx = blockIdx.x;
+    // What decides the workgroup's role and what a GEMM workgroup needs to find its job, in one batch of scalar loads: the
+    // trailing arguments, the grid width and the launch header were three to four dependent rounds in front of the
+    // job-descriptor batch (role -> grid width -> header -> start of the job).
+    asm volatile("" ::"s"(natt_x), "s"(att_last), "s"((int)gridDim.x), "s"(L.njobs), "s"(L.tile_end[0]), "s"(L.tile_end[1]),
+                 "s"(L.tile_end[2]), "s"(L.tile_end[3]), "s"(L.tile_end[4]), "s"(L.tile_end[5]), "s"(L.tile_end[6]),
+                 "s"(L.tile_end[7]));
     if (att_last == 1) {  // GEMM workgroups (the long ones) are dispatched first, the attention fills in behind them
         const int ngemm = (int)gridDim.x - natt_x;
         bx = bx >= ngemm ? bx - ngemm : bx + natt_x;
@@ -649,11 +672,7 @@ __global__ __launch_bounds__(SK_THREADS, 4) void ska_kernel(const SkLaunch L, co
     }
     bx -= natt_x;
     f32x4* red = reinterpret_cast<f32x4*>(sk_smem);
-    int j = 0;
-#pragma unroll
-    for (int q = 0; q < SK_MAXJOB - 1; ++q)
-        if (q < L.njobs - 1 && bx >= L.tile_end[q]) j = q + 1;
-    bx -= (j > 0 ? L.tile_end[j - 1] : 0);
+    const int j = sk_find_job(L, bx);
     const SkJob& job = L.job[j];
     const int tile0 = bx * NB;
     if (NB > 1 || job.aligned) sk_body<MB, NB, true>(job, tile0, red);
@@ -671,6 +690,10 @@ __global__ __launch_bounds__(ATTB_THREADS) void skb_kernel(const SkLaunch L, con
                                                            const int nlead_x, const int rpb) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];
     int bx = blockIdx.x;
+    // the trailing arguments and the launch header in one batch of scalar loads (as in ska_kernel)
+    asm volatile("" ::"s"(att_rows), "s"(l0_chain), "s"(nlead), "s"(nlead_x), "s"(rpb), "s"(L.njobs), "s"(L.tile_end[0]),
+                 "s"(L.tile_end[1]), "s"(L.tile_end[2]), "s"(L.tile_end[3]), "s"(L.tile_end[4]), "s"(L.tile_end[5]),
+                 "s"(L.tile_end[6]), "s"(L.tile_end[7]));
     if (bx < nlead_x) {
         const int id = blockIdx.y * nlead_x + bx;
         if (id >= nlead) return;
@@ -680,11 +703,7 @@ __global__ __launch_bounds__(ATTB_THREADS) void skb_kernel(const SkLaunch L, con
     if (threadIdx.x >= SK_THREADS) return;
     bx -= nlead_x;
     f32x4* red = reinterpret_cast<f32x4*>(sk_smem);
-    int j = 0;
-#pragma unroll
-    for (int q = 0; q < SK_MAXJOB - 1; ++q)
-        if (q < L.njobs - 1 && bx >= L.tile_end[q]) j = q + 1;
-    bx -= (j > 0 ? L.tile_end[j - 1] : 0);
+    const int j = sk_find_job(L, bx);
     const SkJob& job = L.job[j];
     const int tile0 = bx * NB;
     if (NB > 1 || job.aligned) sk_body<MB, NB, true>(job, tile0, red);
@@ -1559,7 +1578,9 @@ int sk_launch(const SkLaunch& Lin, hipStream_t stream) {
     int mbnb;
     sk_prepare(Lin, L, grid, lds, mbnb);
     sk_with_tile(mbnb, [&](auto mb, auto nb) {
-        sk_enqueue<sk_kernel<decltype(mb)::value, decltype(nb)::value>, false>(L, 0, grid, dim3(SK_THREADS), lds, stream, L);
+        constexpr int MB = decltype(mb)::value, NB = decltype(nb)::value;
+        if (L.zmode) sk_enqueue<sk_kernel<MB, NB, true>, false>(L, 0, grid, dim3(SK_THREADS), lds, stream, L);
+        else sk_enqueue<sk_kernel<MB, NB, false>, false>(L, 0, grid, dim3(SK_THREADS), lds, stream, L);
     });
     return (int)hipGetLastError();
 }

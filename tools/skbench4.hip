@@ -59,8 +59,10 @@ int main(int argc, char** argv) {
     g_ptr = getenv("SKB_PTR") ? atoi(getenv("SKB_PTR")) : 0;
     {
         const int big = 160 * 1024;
-        (void)hipFuncSetAttribute((const void*)sk_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
-        (void)hipFuncSetAttribute((const void*)sk_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)sk_kernel<2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)sk_kernel<2, 2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)sk_kernel<2, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
+        (void)hipFuncSetAttribute((const void*)sk_kernel<2, 1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         (void)hipFuncSetAttribute((const void*)sk_kernel_p<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
         (void)hipFuncSetAttribute((const void*)sk_kernel_p<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, big);
     }
