@@ -624,6 +624,11 @@ int parrot_sample_is_bf16(void* plan);
  * fed-back frame is out of the chain (Wgx_t / Wcx_t), bit 1: the attention projection is folded into the candidate units (Watt_t).
  * 0, or PARROT_ERR_UNSUPPORTED when the configuration does not take this plan.  Used by the CPU tests. */
 int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* info16);
+/* The same dry run, reduced to one number: the FNV-1a 64-bit hash of the placed unit table, of the program's attention,
+ * sampling, init and fill records, and of T, ticks, phases, units per workgroup and workgroups.  The dry run carves a
+ * workspace at a fixed fake address, so equal descriptors (pointers included) and switches give equal digests, in any
+ * process.  Same return codes; *digest = 0 when there is no plan.  Used by the CPU tests to hold the planners still. */
+int parrot_sample_plan_digest_dry(const ParrotSampleDesc* desc, int nwg, unsigned long long* digest);
 /* Like parrot_decoder_status, for a decode plan. */
 int parrot_sample_status(void* plan);
 /* 1: the plan stops at the end of the utterance (ParrotSampleDesc::eou_extra > 0 on the machine); 0: it runs all S steps */

@@ -232,6 +232,7 @@ SIGNATURES = {
     "parrot_sample_is_persistent": (_i, [_vp]),
     "parrot_sample_is_bf16": (_i, [_vp]),
     "parrot_sample_plan_pieces_dry": (_i, [C.POINTER(SampleDesc), _i, C.POINTER(C.c_int)]),
+    "parrot_sample_plan_digest_dry": (_i, [C.POINTER(SampleDesc), _i, C.POINTER(C.c_ulonglong)]),
     "parrot_sample_status": (_i, [_vp]),
     "parrot_sample_stops_early": (_i, [_vp]),
     "parrot_sample_steps_run": (_i, [_vp, C.POINTER(C.c_int)]),

@@ -1,11 +1,15 @@
 // The decode loop of Parrot.sample_model_fun (model.py:882-1057) as a plan: per-step launches in one hipGraph, or the
-// whole loop as ONE resident kernel on the persistent phase machine (persist.h) -- 2L + 3 whole-K phases (round 2,
-// build_persist_whole), 2L + 2 phases with every product cut along K by the age of its operands (round 4), 2L + 1 with
-// the fed-back frame out of the step's dependency chain (round 5; both build_persist_pieces); LSTM stacks: L + 2 whole-K
-// phases (build_persist_lstm); with a GMM head (PARROT_PM_GMM=1) the two whole-K programs end in a composed head phase and a
-// sampling phase instead (gmm_eligible).  SamplePlan::plan_persist picks the program; every planner emits its slabs, units and
-// symbolic-replay metas through the shared builder (pm_builder.h), which carves the workspace within its bounds, checks
-// the table capacities, places and uploads.  Then the per-step launch path and the parrot_sample_* entry points.
+// whole loop as ONE resident kernel on the persistent phase machine (persist.h) -- 2L + 3 whole-K phases
+// (build_persist_whole), 2L + 2 phases with every product cut along K by the age of its operands, 2L + 1 with the fed-back
+// frame out of the step's dependency chain (both build_persist_pieces); LSTM stacks: L + 2 whole-K phases
+// (build_persist_lstm); with a GMM head (PARROT_PM_GMM=1) the two whole-K programs end in a composed head phase and a
+// sampling phase instead (gmm_eligible).  SamplePlan::plan_persist picks the program (SamplePlan::Program), for real and
+// for dry runs alike.  The three planners speak one vocabulary: the slabs of a program and who writes into them (PmSlabs,
+// SamplePlan::carve), one emitter per unit kind that pushes the units AND the kind's symbolic-replay meta from the same
+// operands (gate_tiles, cand_tiles, linear_tiles, att_rows, head_phases), one tail; a planner itself only says which
+// kinds run in which phase on which chunks.  Underneath, the shared builder (pm_builder.h) carves the workspace within
+// its bounds, checks the table capacities, places, digests and uploads.  Then the per-step launch path and the
+// parrot_sample_* entry points.
 #include "pm_builder.h"
 #include "switches.h"
 
@@ -28,9 +32,67 @@ struct PmGroup {
 // element per step.
 struct PmAccess { int res, dstep, c0, nch; };
 struct PmMeta { int lag, slot; std::vector<PmAccess> rd, wr; };
-enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63, RES_HEAD = 64, RES_C = 70,
-       RES_PART = 100 };
+enum { RES_XG = 10, RES_XC = 20, RES_XR = 30, RES_XO = 31, RES_RO = 32, RES_H = 40, RES_Z = 50, RES_X = 60, RES_KAPPA = 61, RES_XPRE = 62, RES_PP = 63,
+       RES_HEAD = 64, RES_C = 70, RES_PART = 100 };
 PmAccess pm_acc(int res, int dstep, int c0, int nch) { PmAccess a; a.res = res; a.dstep = dstep; a.c0 = c0; a.nch = nch; return a; }
+
+// What the units of one kind read: chunks [c0, c0 + nch) of one slab (K = ks per step, `res` in the replay), in phase
+// `slot`, `lag` ticks behind.
+struct PmIn { int slot, lag; const float* slab; long long ks; int res, c0, nch; };
+// One place the result of a unit kind goes: column tile ct -> chunk c0 + ct of the slab of step t + dstep.  A unit's
+// destination list and its meta's write list are both made from these (add_tos / wr_tos), so they cannot drift apart.
+struct PmTo { const float* slab; long long ks; int res, dstep, c0; };
+// A row-major [B, N] buffer that a unit adds in its epilogue and the replay must find written: a partial sum, x_pre.
+struct PmPart { float* buf; int res; };
+
+// The slabs and histories of a decode program, in workspace order (SamplePlan::carve), and who writes what into them.
+struct PmSlabs {
+    int L = 0, hc = 0, ec = 0;                        // layers; chunks of a state / of the attention's w
+    float* XG[PARROT_MAX_LAYERS] = {};                // gate slab of layer l (LSTM: the layer's only slab)
+    float* XC[PARROT_MAX_LAYERS] = {};                // candidate slab (GRU)
+    long long kx[PARROT_MAX_LAYERS] = {};
+    int fbch[PARROT_MAX_LAYERS] = {};                 // first of the four chunks of the fed-back frame in layer l's slabs; -1: none
+    float* XR = nullptr;                              // [h_0[t+1] .. h_{L-1}[t+1] ; w[t+1]]
+    long long kr = 0;
+    float* XO = nullptr;                              // readout[t] (whole-K GRU with an MSE head)
+    float* h[PARROT_MAX_LAYERS] = {};                 // row-major histories: states [S + 1],
+    float* z[PARROT_MAX_LAYERS] = {};                 // update gates [S] (GRU),
+    float* c[PARROT_MAX_LAYERS] = {};                 // cells [S + 1] (LSTM),
+    float *ro_hist = nullptr, *b_hist = nullptr, *head = nullptr;  // readout, attention b, GMM head [S]
+
+    template <class F>
+    void each_slab(int l, F f) const {  // every slab of layer l
+        f(XG[l], RES_XG + l);
+        if (XC[l]) f(XC[l], RES_XC + l);
+    }
+    // h_l[t+1]: the layer's own gate slab of the next step, every later layer's slabs, the readout's slab
+    std::vector<PmTo> state_tos(int l) const {
+        std::vector<PmTo> v = {{XG[l], kx[l], RES_XG + l, 1, 0}};
+        for (int m = l + 1; m < L; ++m) each_slab(m, [&](const float* s, int res) { v.push_back({s, kx[m], res, 0, hc + ec + l * hc}); });
+        v.push_back({XR, kr, RES_XR, 0, l * hc});
+        return v;
+    }
+    // w[t+1] (attention): layer 0 reads it in the next step, the later layers and the readout in this one
+    std::vector<PmTo> w_tos() const {
+        std::vector<PmTo> v;
+        for (int l = 0; l < L; ++l) each_slab(l, [&](const float* s, int res) { v.push_back({s, kx[l], res, l == 0 ? 1 : 0, hc}); });
+        v.push_back({XR, kr, RES_XR, 0, L * hc});
+        return v;
+    }
+    // x[t+1] (63 columns, padded to 64): the fed-back chunks of the next step
+    std::vector<PmTo> frame_tos() const {
+        std::vector<PmTo> v;
+        for (int l = 0; l < L; ++l)
+            if (fbch[l] >= 0) each_slab(l, [&](const float* s, int res) { v.push_back({s, kx[l], res, 1, fbch[l]}); });
+        return v;
+    }
+};
+void add_tos(PmBuilder& pb, PmUnit& u, const std::vector<PmTo>& tos, int ct) {
+    for (const PmTo& t : tos) pb.add_dst(u, pb.dst(t.slab, t.dstep, t.ks, t.c0 + ct));
+}
+void wr_tos(PmMeta& m, const std::vector<PmTo>& tos, int ntiles) {
+    for (const PmTo& t : tos) m.wr.push_back(pm_acc(t.res, t.dstep, t.c0, ntiles));
+}
 
 // symbolic replay over S steps: 0 = every read finds its value written in an earlier phase and nothing is written twice
 int check_pieces(const std::vector<PmMeta>& metas, const std::vector<PmAccess>& init, int n_slots, int S,
@@ -77,7 +139,7 @@ struct SamplePlan : PlanBase {
     ParrotSampleDesc d;
     int esplit = 1;
 
-    int enqueue(int, hipStream_t s) override { return persist_ok ? run_persist(s) : run_all(s); }
+    int enqueue(int, hipStream_t s) override { return live ? run_persist(s) : run_all(s); }
 
     // ---- persistent phase machine for the decode loop (persist.h) ------------------------------------------------
     // One resident kernel runs all S steps; a step = 2L + 3 phases: G_0, C_0, ATT, (G_l, C_l for l >= 1), readout,
@@ -88,9 +150,13 @@ struct SamplePlan : PlanBase {
     //   XR[t] = [h_0[t+1] .. h_{L-1}[t+1] ; w[t+1]]      XO[t] = readout[t]
     // Weights: fragment-major copies prepared by the caller (Wg_t / Wc_t: packed layer matrix with the feedback rows
     // appended and padded to 64; Wr_t; Wo_t with the columns padded to 64).
-    bool persist_ok = false;
+    enum Program { NONE, WHOLE, PIECES, PIECES_FBC, LSTM };
+    Program program = NONE;  // what pm_prog holds: planned, replayed and placed (dry runs stop there)
+    bool live = false;       // ... and uploaded: the launches go to the machine
     PmProgram pm_prog;
-    float* hist_h[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
+    PmSlabs sl;
+    int pieces_info[16] = {0};
+    unsigned long long plan_digest = 0;  // PmBuilder::digest of the program; 0: none
 
     static bool persist_eligible_shape(const ParrotSampleDesc& d) {  // (no device query: the CPU tests plan too)
         if (d.layer_norm || (d.gmm_K > 0 && !gmm_eligible(d)) || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
@@ -130,14 +196,14 @@ struct SamplePlan : PlanBase {
         if (d.gmm_K > 0) return d.cell == 1 && d.L + 3 <= PM_MAXSLOTS;  // (persist_eligible_shape: Wrh_t / rh_const are there)
         return d.cell == 1 && d.Wro_t && d.ro_const && d.L + 2 <= PM_MAXSLOTS;
     }
-    static bool legacy_eligible(const ParrotSampleDesc& d) {
+    static bool whole_eligible(const ParrotSampleDesc& d) {  // GRU, whole-K phases -- build_persist_whole
         if (d.gmm_K > 0) return 2 * d.L + 3 <= PM_MAXSLOTS;  // (head and sampling phases in place of readout and output)
         if (2 * d.L + 3 > PM_MAXSLOTS || !d.Wr_t || !d.Wo_t || !d.bo_pad) return false;
         return (d.oadd != nullptr) == (d.oadd_pad != nullptr);
     }
     static bool persist_eligible(const ParrotSampleDesc& d) {
         if (!persist_eligible_shape(d)) return false;
-        if (d.cell == 1 ? !lstm_eligible(d) : !(legacy_eligible(d) || pieces_wanted(d))) return false;
+        if (d.cell == 1 ? !lstm_eligible(d) : !(whole_eligible(d) || pieces_wanted(d))) return false;
         return pm_max_workgroups() >= 64 && head_fits(d, pm_max_workgroups());
     }
     static int fb_rows(const ParrotSampleDesc& d, int l) { return d.Wfg[l] ? 64 : 0; }
@@ -162,17 +228,30 @@ struct SamplePlan : PlanBase {
     // the bound of a planner's carve-up: the caller's workspace; dry runs carve what the size query asks for
     long long ws_limit(bool dry, int nwg) const { return dry ? persist_floats(d, nwg) : d.persist_ws_floats; }
 
-    // The one planning entry: the program the descriptor and the switches ask for.  dry: plan, place and check only, on
-    // nwg_dry workgroups, no device memory is touched (parrot_sample_plan_pieces_dry: the CPU tests; the whole-K phases
-    // have no dry mode).
+    // The one planning entry: the program the descriptor and the switches ask for.  dry: plan, replay and place only, on
+    // nwg_dry workgroups, no device memory is touched (parrot_sample_plan_pieces_dry / _digest_dry: the CPU tests plan every
+    // program this way).
     void plan_persist(bool dry, int nwg_dry) {
-        if (d.bf16 && !bf16_eligible(d)) return;  // (GRU programs have no bf16 units: no plan rather than an f32 one)
+        program = NONE;
+        live = false;
+        plan_digest = 0;
+        if (!persist_eligible_shape(d)) return;  // (bf16 on a GRU stack too: no plan rather than an f32 one)
+        const int nwg = dry ? nwg_dry : pm_max_workgroups();
+        if (nwg < 64 || !head_fits(d, nwg)) return;
+        if (!dry && (!d.persist_ws || d.persist_ws_floats < persist_floats(d, nwg))) return;
         if (d.cell == 1) {
-            build_persist_lstm(dry, nwg_dry);
+            if (lstm_eligible(d)) build_persist_lstm(dry, nwg);
             return;
         }
-        if (pieces_wanted(d)) build_persist_pieces(dry, nwg_dry);  // the step cut along K by the age of its operands
-        if (!persist_ok && !dry) build_persist_whole();            // else the 2L + 3 whole-K phases
+        if (pieces_wanted(d)) build_persist_pieces(dry, nwg);                     // the step cut along K by the age of its operands
+        if (program == NONE && whole_eligible(d)) build_persist_whole(dry, nwg);  // else the 2L + 3 whole-K phases
+    }
+    // How every planner ends: replay verdict in, placement, upload unless dry; which program the plan now holds.
+    void finish(PmBuilder& pb, Program p, int n_ticks, int chk) {
+        const bool ok = pb.finish(d.S, n_ticks, chk, pieces_info);
+        plan_digest = pb.digest;
+        program = ok ? p : NONE;
+        live = ok && !pb.dry;
     }
     // End-of-utterance stop (ParrotSampleDesc::eou_extra > 0): a property of the launch, not of a program -- every program
     // above gets it the same way, through PmAtt (persist.h).  A descriptor that asks for it and does not qualify gets NO
@@ -180,172 +259,171 @@ struct SamplePlan : PlanBase {
     static bool stop_eligible(const ParrotSampleDesc& d) {
         return d.eou_extra >= PM_EOU_MIN_EXTRA && d.eou_pos && d.eou_ncmp && d.eou_first;
     }
-    bool stops_early() const { return persist_ok && pm_prog.att.eou_extra > 0; }
+    bool stops_early() const { return live && pm_prog.att.eou_extra > 0; }
     int build_persist() {
-        persist_ok = false;
         if (env_int("PARROT_SAMPLE_PERSIST", 1) == 0) return 0;
         if (!persist_eligible(d) || !d.persist_ws) return 0;
         if (d.eou_extra > 0 && !stop_eligible(d)) return 0;
         plan_persist(false, 0);
-        if (persist_ok && d.eou_extra > 0) {
+        if (live && d.eou_extra > 0) {
             PmAtt& a = pm_prog.att;
             a.eou_pos = d.eou_pos; a.eou_ncmp = d.eou_ncmp; a.eou_first = d.eou_first; a.eou_extra = d.eou_extra;
         }
         return 0;
     }
 
-    int build_persist_whole() {
-        if (!legacy_eligible(d)) return 0;
-        const int nwg = pm_max_workgroups();
-        if (d.persist_ws_floats < persist_floats(d, nwg) || !head_fits(d, nwg)) return 0;
-        const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S, R = d.R;
-        const bool gmm = d.gmm_K > 0;  // readout and output phases -> composed head and sampling phases
-        const int NH = gmm ? d.rh_cols : 0;
-        const long long BH = (long long)B * H;
-        PmBuilder pb(pm_prog, false, d.persist_ws, d.persist_ws_floats, B, nwg, 2 * L + 3, 1);
-        const long long rows = pb.rows;
-        float* XG[PARROT_MAX_LAYERS];
-        float* XC[PARROT_MAX_LAYERS];
-        long long kx[PARROT_MAX_LAYERS];
+    // ---- what the three decode programs share: the carve-up, one emitter per unit kind, the tail -------------------------
+    // The workspace in the order every program holds it (take() order = addresses): per layer the gate slab and, for a GRU,
+    // the candidate slab; XR; with R_out the readout's slab; then the row-major histories.  extra0: K rows appended to
+    // layer 0's slabs, behind the fed-back frame (the fbc program keeps the last layer's state there).
+    void carve(PmBuilder& pb, long long extra0, int R_out) {
+        const int L = d.L, S = d.S, B = d.B;
+        const long long rows = pb.rows, BH = (long long)B * d.H;
+        sl = PmSlabs();
+        sl.L = L; sl.hc = d.H / 16; sl.ec = d.E / 16;
         for (int l = 0; l < L; ++l) {
-            kx[l] = kslab(d, l);
-            XG[l] = pb.take((S + 1) * rows * kx[l]);
-            XC[l] = pb.take((S + 1) * rows * kx[l]);
+            sl.kx[l] = kslab(d, l) + (l == 0 ? extra0 : 0);
+            sl.fbch[l] = fb_rows(d, l) ? (int)(kslab(d, l) / 16) - 4 : -1;
+            sl.XG[l] = pb.take((S + 1) * rows * sl.kx[l]);
+            if (d.cell == 0) sl.XC[l] = pb.take((S + 1) * rows * sl.kx[l]);
         }
-        const long long kr = (long long)L * H + E;
-        float* XR = pb.take(S * rows * kr);
-        float* XO = gmm ? nullptr : pb.take(S * rows * R);
+        sl.kr = (long long)L * d.H + d.E;
+        sl.XR = pb.take(S * rows * sl.kr);
+        if (R_out) sl.XO = pb.take(S * rows * R_out);
         pb.fm_end();
-        float* zh[PARROT_MAX_LAYERS];
-        for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
-        for (int l = 0; l < L; ++l) zh[l] = pb.take(S * BH);
-        float* ro_hist = gmm ? nullptr : pb.take((long long)S * B * R);
-        float* b_hist = pb.take((long long)S * B * d.A);
-        float* head = gmm ? pb.take((long long)S * B * NH) : nullptr;
-        if (pb.failed) return 0;
-
+        for (int l = 0; l < L; ++l) sl.h[l] = pb.take((S + 1) * BH);
         for (int l = 0; l < L; ++l) {
-            const int sg = slotG(l), sc = slotC(l);
-            const int nch = (int)(kx[l] / 16);
-            for (int ct = 0; ct < 2 * H / 16; ++ct) {     // gates
-                PmReq q = pb.gemm(sg, XG[l], kx[l]);
-                PmUnit& u = q.u;
-                u.W = d.Wg_t[l] + (size_t)ct * nch * 256;
-                u.bias = d.bg[l] ? d.bg[l] + 16 * ct : nullptr;
-                if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 16 * ct, 0, 2 * H));
-                u.epi = PM_EPI_GATES;
-                u.rtile = 16 * ct >= H;
-                if (!u.rtile) {
-                    u.o1 = pm_rm(zh[l] + 16 * ct, BH, H);
-                } else {
-                    const int j0 = 16 * ct - H;
-                    u.e0 = pm_rm(hist_h[l] + j0, BH, H);
-                    pb.add_dst(u, pb.dst(XC[l], 0, kx[l], j0 / 16));
-                }
-                pb.push(q);
-            }
-            for (int ct = 0; ct < H / 16; ++ct) {         // candidate -> h_l[t+1]
-                PmReq q = pb.gemm(sc, XC[l], kx[l]);
-                PmUnit& u = q.u;
-                u.W = d.Wc_t[l] + (size_t)ct * nch * 256;
-                u.bias = d.bc[l] ? d.bc[l] + 16 * ct : nullptr;
-                if (d.seq_c[l]) pb.add_operand(u, pm_rm(d.seq_c[l] + 16 * ct, 0, H));
-                u.epi = PM_EPI_CAND;
-                u.e0 = pm_rm(hist_h[l] + 16 * ct, BH, H);
-                u.e1 = pm_rm(zh[l] + 16 * ct, BH, H);
-                u.out = pm_rm(hist_h[l] + BH + 16 * ct, BH, H);
-                pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ct));
-                for (int m2 = l + 1; m2 < L; ++m2) {
-                    const int ch = (H + E) / 16 + l * (H / 16) + ct;
-                    pb.add_dst(u, pb.dst(XG[m2], 0, kx[m2], ch));
-                    pb.add_dst(u, pb.dst(XC[m2], 0, kx[m2], ch));
-                }
-                pb.add_dst(u, pb.dst(XR, 0, kr, l * (H / 16) + ct));
-                pb.push(q);
-            }
+            if (d.cell == 0) sl.z[l] = pb.take(S * BH);
+            else sl.c[l] = pb.take((S + 1) * BH);
         }
-        pb.att_rows(2, 0);
-        if (gmm) {
-            head_units(pb, 2 * L + 1, XR, kr, head);
-            std::vector<PmDst> fb;
-            for (int l = 0; l < L; ++l) {
-                if (!fb_rows(d, l)) continue;
-                fb.push_back(pb.dst(XG[l], 1, kx[l], (int)(kx[l] / 16) - 4));
-                fb.push_back(pb.dst(XC[l], 1, kx[l], (int)(kx[l] / 16) - 4));
-            }
-            pb.sample_rows(2 * L + 2, 0, fb);
-        }
-        for (int ct = 0; ct < R / 16 && !gmm; ++ct) {     // readout
-            PmReq q = pb.gemm(2 * L + 1, XR, kr);
+        if (R_out) sl.ro_hist = pb.take((long long)S * B * R_out);
+        sl.b_hist = pb.take((long long)S * B * d.A);
+        if (d.gmm_K > 0) sl.head = pb.take((long long)S * B * d.rh_cols);
+    }
+
+    // Column tile ct of a product over `in`, W = its fragment-major weights ([N / 16][ks / 16] blocks of 16 x 16); `parts`
+    // are added in the epilogue.  The meta of the kind starts the same way: what every tile of it reads.
+    PmReq tile(PmBuilder& pb, const PmIn& in, const float* W, int ct, const std::vector<PmPart>& parts, int N) const {
+        PmReq q = pb.gemm(in.slot, in.slab, in.ks, in.c0, in.nch * 16, in.lag);
+        q.u.W = W + ((size_t)ct * (in.ks / 16) + in.c0) * 256;
+        for (const PmPart& p : parts) pb.add_operand(q.u, pm_rm(p.buf + 16 * ct, (long long)d.B * N, N));
+        return q;
+    }
+    static PmMeta meta(const PmIn& in, const std::vector<PmPart>& parts) {
+        PmMeta m;
+        m.lag = in.lag; m.slot = in.slot;
+        m.rd.push_back(pm_acc(in.res, 0, in.c0, in.nch));
+        for (const PmPart& p : parts) m.rd.push_back(pm_acc(p.res, 0, 0, 1));
+        return m;
+    }
+    // G_l: z -> its history, r * h_l[t] -> the head of the candidate slab
+    void gate_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, const float* W, int l, const std::vector<PmPart>& parts) {
+        const int H = d.H;
+        const long long BH = (long long)d.B * H;
+        for (int ct = 0; ct < 2 * H / 16; ++ct) {
+            PmReq q = tile(pb, in, W, ct, parts, 2 * H);
             PmUnit& u = q.u;
-            u.W = d.Wr_t + (size_t)ct * (kr / 16) * 256;
-            u.bias = d.br ? d.br + 16 * ct : nullptr;
-            if (d.radd) pb.add_operand(u, pm_rm(d.radd + 16 * ct, 0, R));
-            u.epi = PM_EPI_LINEAR;
-            u.out = pm_rm(ro_hist + 16 * ct, (long long)B * R, R);
-            pb.add_dst(u, pb.dst(XO, 0, R, ct));
-            pb.push(q);
-        }
-        for (int ct = 0; ct < 4 && !gmm; ++ct) {          // output frame x[t+1] (63 columns, padded to 64)
-            PmReq q = pb.gemm(2 * L + 2, XO, R);
-            PmUnit& u = q.u;
-            u.W = d.Wo_t + (size_t)ct * (R / 16) * 256;
-            u.bias = d.bo_pad + 16 * ct;
-            if (d.oadd_pad) pb.add_operand(u, pm_rm(d.oadd_pad + 16 * ct, 0, 64));
-            u.epi = PM_EPI_LINEAR;
-            u.out = pm_rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
-            for (int l = 0; l < L; ++l) {
-                if (!fb_rows(d, l)) continue;
-                const int ch = (int)((kx[l] - 64) / 16) + ct;
-                pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ch));
-                pb.add_dst(u, pb.dst(XC[l], 1, kx[l], ch));
+            u.bias = d.bg[l] ? d.bg[l] + 16 * ct : nullptr;
+            if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 16 * ct, 0, 2 * H));
+            u.epi = PM_EPI_GATES;
+            u.rtile = 16 * ct >= H;
+            if (!u.rtile) {
+                u.o1 = pm_rm(sl.z[l] + 16 * ct, BH, H);
+            } else {
+                const int j0 = 16 * ct - H;
+                u.e0 = pm_rm(sl.h[l] + j0, BH, H);
+                pb.add_dst(u, pb.dst(sl.XC[l], 0, sl.kx[l], j0 / 16));
             }
             pb.push(q);
         }
-
-        pb.att_common(d, hist_h[0]);
-        pm_prog.att.b = b_hist;
-        if (gmm) samp_common(head);
-        pb.add_wdst(pb.dst(XG[0], 1, kx[0], H / 16));
-        pb.add_wdst(pb.dst(XC[0], 1, kx[0], H / 16));
-        for (int l = 1; l < L; ++l) {
-            pb.add_wdst(pb.dst(XG[l], 0, kx[l], H / 16));
-            pb.add_wdst(pb.dst(XC[l], 0, kx[l], H / 16));
+        PmMeta m = meta(in, parts);
+        m.rd.push_back(pm_acc(RES_H + l, 0, 0, 1));
+        m.wr.push_back(pm_acc(RES_Z + l, 0, 0, 1));
+        m.wr.push_back(pm_acc(RES_XC + l, 0, 0, sl.hc));
+        metas.push_back(m);
+    }
+    // C_l -> h_l[t+1], into `tos`.  pp: this tile's share of the attention projection h_1 . Watt goes there (layer 0's
+    // tiles of a program that folds it, PmUnit::pw / pp), else null.
+    void cand_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, const float* W, int l, const std::vector<PmPart>& parts,
+                    const std::vector<PmTo>& tos, float* pp) {
+        const int H = d.H, B = d.B, hc = sl.hc;
+        const long long BH = (long long)B * H;
+        for (int ct = 0; ct < hc; ++ct) {
+            PmReq q = tile(pb, in, W, ct, parts, H);
+            PmUnit& u = q.u;
+            u.bias = d.bc[l] ? d.bc[l] + 16 * ct : nullptr;
+            if (d.seq_c[l]) pb.add_operand(u, pm_rm(d.seq_c[l] + 16 * ct, 0, H));
+            u.epi = PM_EPI_CAND;
+            u.e0 = pm_rm(sl.h[l] + 16 * ct, BH, H);
+            u.e1 = pm_rm(sl.z[l] + 16 * ct, BH, H);
+            u.out = pm_rm(sl.h[l] + BH + 16 * ct, BH, H);
+            add_tos(pb, u, tos, ct);
+            if (pp) {
+                u.pw[0] = d.Watt_t + (size_t)ct * 256;
+                u.pw[1] = d.Watt_t + (size_t)(hc + ct) * 256;
+                u.pp = pm_rm(pp + (size_t)ct * B * 32, (long long)hc * B * 32, 32);
+            }
+            pb.push(q);
         }
-        pb.add_wdst(pb.dst(XR, 0, kr, L * (H / 16)));
-        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XG[l], kx[l], 0);   // initial states (slot 0 of the ping-pong)
-        pb.add_init(d.w, E, E, XG[0], kx[0], H / 16);
-        pb.add_init(d.w, E, E, XC[0], kx[0], H / 16);
-        // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states (the slabs start EMPTY in
-        // dataflow mode, so "stays at the zero fill" is not enough)
-        for (int l = 0; l < L; ++l) {
-            if (!fb_rows(d, l)) continue;
-            pb.add_init(d.x, d.ldx, 64, XG[l], kx[l], (int)((kx[l] - 64) / 16));
-            pb.add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)((kx[l] - 64) / 16));
+        PmMeta m = meta(in, parts);
+        m.rd.push_back(pm_acc(RES_H + l, 0, 0, 1));
+        m.rd.push_back(pm_acc(RES_Z + l, 0, 0, 1));
+        m.wr.push_back(pm_acc(RES_H + l, 1, 0, 1));
+        wr_tos(m, tos, hc);
+        if (pp) m.wr.push_back(pm_acc(RES_PP, 0, 0, 1));
+        metas.push_back(m);
+    }
+    // Every plain product -- a piece's partial sums, readout, output frame, x_pre, GMM head: the N / 16 column tiles of
+    // in . W + bias + parts + add ([B, N] row-major, the same for every step) -> out (row-major, `wr` in the replay) and `tos`.
+    // crit: on the step's dependency chain (pm_place serves those first).
+    void linear_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, const float* W, int N, const std::vector<PmPart>& parts,
+                      const float* bias, const float* add, PmRM out, PmAccess wr, const std::vector<PmTo>& tos, bool crit = true) {
+        for (int ct = 0; ct < N / 16; ++ct) {
+            PmReq q = tile(pb, in, W, ct, parts, N);
+            PmUnit& u = q.u;
+            q.crit = crit ? 1 : 0;
+            u.bias = bias ? bias + 16 * ct : nullptr;
+            if (add) pb.add_operand(u, pm_rm(add + 16 * ct, 0, N));
+            u.epi = PM_EPI_LINEAR;
+            u.out = pm_rm(out.p + 16 * ct, out.st, out.ld);
+            add_tos(pb, u, tos, ct);
+            pb.push(q);
         }
-        pm_prog.dataflow = sw_pm_dataflow(0);  // (measured no gain without barriers: 57.6 us per step either way at configs[2])
-        pb.fill_fm();
-        for (int l = 0; l < L; ++l) {
-            pb.add_fill(hist_h[l] + BH, (long long)S * BH);
-            pb.add_fill(zh[l], (long long)S * BH);
-        }
-        if (gmm) pb.add_fill(head, (long long)S * B * NH);
-        persist_ok = pb.finish(S, S);
-        return 0;
+        PmMeta m = meta(in, parts);
+        m.wr.push_back(wr);
+        wr_tos(m, tos, N / 16);
+        metas.push_back(m);
+    }
+    PmRM x_next() const { return pm_rm(d.x + (size_t)d.B * d.ldx, (long long)d.B * d.ldx, d.ldx); }  // x[t+1] (63 columns, padded to 64)
+    // The attention: one unit per batch row; with_pp: it reads the projection's partial sums of cand_tiles
+    void att_rows(PmBuilder& pb, std::vector<PmMeta>& metas, int slot, int lag, bool with_pp) {
+        pb.att_rows(slot, lag);
+        PmMeta m;
+        m.lag = lag; m.slot = slot;
+        m.rd.push_back(pm_acc(RES_H, 1, 0, 1));
+        if (with_pp) m.rd.push_back(pm_acc(RES_PP, 0, 0, 1));
+        m.rd.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
+        m.wr.push_back(pm_acc(RES_KAPPA, 1, 0, 1));
+        wr_tos(m, sl.w_tos(), sl.ec);
+        metas.push_back(m);
     }
     // GMM head, both whole-K programs: the composed head's column tiles XR . Wrh_t + rh_const -> head history (row-major,
-    // write-once, no fragment-major copies), and what the sampling rows read (PmSamp)
-    void head_units(PmBuilder& pb, int slot, const float* XR, long long kr, float* head) const {
+    // write-once, no fragment-major copies) in phase `slot`, then one sampling unit per batch row: head history -> x[t+1]
+    // and the fed-back chunks; and what the sampling rows read (PmSamp)
+    void head_phases(PmBuilder& pb, std::vector<PmMeta>& metas, int slot) {
         const int NH = d.rh_cols;
-        for (int ct = 0; ct < NH / 16; ++ct) {
-            PmReq q = pb.gemm(slot, XR, kr);
-            PmUnit& u = q.u;
-            u.W = d.Wrh_t + (size_t)ct * (kr / 16) * 256;
-            pb.add_operand(u, pm_rm(d.rh_const + 16 * ct, 0, NH));
-            u.epi = PM_EPI_LINEAR;
-            u.out = pm_rm(head + 16 * ct, (long long)d.B * NH, NH);
-            pb.push(q);
-        }
+        linear_tiles(pb, metas, {slot, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, d.Wrh_t, NH, {}, nullptr, d.rh_const,
+                     pm_rm(sl.head, (long long)d.B * NH, NH), pm_acc(RES_HEAD, 0, 0, 1), {});
+        const std::vector<PmTo> tos = sl.frame_tos();
+        std::vector<PmDst> fb;
+        for (const PmTo& t : tos) fb.push_back(pb.dst(t.slab, t.dstep, t.ks, t.c0));
+        pb.sample_rows(slot + 1, 0, fb);
+        PmMeta m;
+        m.lag = 0; m.slot = slot + 1;
+        m.rd.push_back(pm_acc(RES_HEAD, 0, 0, 1));
+        m.wr.push_back(pm_acc(RES_X, 1, 0, 1));
+        wr_tos(m, tos, 4);
+        metas.push_back(m);
     }
     void samp_common(float* head) {
         PmSamp& sp = pm_prog.samp;
@@ -355,9 +433,77 @@ struct SamplePlan : PlanBase {
         sp.B = d.B; sp.O = d.O; sp.K = d.gmm_K; sp.ldx = d.ldx;
         sp.bias = d.sampling_bias; sp.eps = d.eps;
     }
-    int persist_status() const { return persist_ok ? pm_status(pm_prog) : 0; }
+    // What every program ends with: the attention's and the sampling's records, the entering states converted into slot 0
+    // of the slabs, the buffers that start EMPTY in dataflow mode.  Returns the same entering states for the replay.
+    std::vector<PmAccess> tail(PmBuilder& pb) {
+        const int H = d.H, E = d.E, L = d.L, hc = sl.hc;
+        const long long SBH = (long long)d.S * d.B * H, BH = (long long)d.B * H;
+        std::vector<PmAccess> init;
+        pb.att_common(d, sl.h[0]);
+        pm_prog.att.b = sl.b_hist;
+        if (sl.head) samp_common(sl.head);
+        for (const PmTo& t : sl.w_tos()) pb.add_wdst(pb.dst(t.slab, t.dstep, t.ks, t.c0));
+        for (int l = 0; l < L; ++l) {  // initial states (slot 0 of the ping-pong)
+            pb.add_init(d.h[l], H, H, sl.XG[l], sl.kx[l], 0);
+            init.push_back(pm_acc(RES_XG + l, 0, 0, hc));
+            init.push_back(pm_acc(RES_H + l, 0, 0, 1));
+            if (sl.c[l]) init.push_back(pm_acc(RES_C + l, 0, 0, 1));
+        }
+        sl.each_slab(0, [&](const float* s, int res) {
+            pb.add_init(d.w, E, E, s, sl.kx[0], hc);
+            init.push_back(pm_acc(res, 0, hc, sl.ec));
+        });
+        init.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
+        // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states (the slabs start EMPTY in
+        // dataflow mode, so "stays at the zero fill" is not enough)
+        for (int l = 0; l < L; ++l)
+            if (sl.fbch[l] >= 0)
+                sl.each_slab(l, [&](const float* s, int res) {
+                    pb.add_init(d.x, d.ldx, 64, s, sl.kx[l], sl.fbch[l]);
+                    init.push_back(pm_acc(res, 0, sl.fbch[l], 4));
+                });
+        pb.fill_fm();
+        for (int l = 0; l < L; ++l) {
+            pb.add_fill(sl.h[l] + BH, SBH);
+            if (sl.z[l]) pb.add_fill(sl.z[l], SBH);
+            if (sl.c[l]) pb.add_fill(sl.c[l] + BH, SBH);
+        }
+        if (sl.head) pb.add_fill(sl.head, (long long)d.S * d.B * d.rh_cols);
+        return init;
+    }
+
+    // ---- GRU, whole-K phases: every product walks its whole slab, nothing lags ------------------------------------------
+    static int slotG(int l) { return l == 0 ? 0 : 2 * l + 1; }
+    static int slotC(int l) { return slotG(l) + 1; }
+    void build_persist_whole(bool dry, int nwg) {
+        const int B = d.B, L = d.L, R = d.R, n_slots = 2 * L + 3;
+        const bool gmm = d.gmm_K > 0;  // readout and output phases -> composed head and sampling phases
+        PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, 1);
+        carve(pb, 0, gmm ? 0 : R);
+        if (pb.failed) return;
+        std::vector<PmMeta> metas;
+        for (int l = 0; l < L; ++l) {
+            const int nch = (int)(sl.kx[l] / 16);
+            gate_tiles(pb, metas, {slotG(l), 0, sl.XG[l], sl.kx[l], RES_XG + l, 0, nch}, d.Wg_t[l], l, {});
+            cand_tiles(pb, metas, {slotC(l), 0, sl.XC[l], sl.kx[l], RES_XC + l, 0, nch}, d.Wc_t[l], l, {}, sl.state_tos(l), nullptr);
+        }
+        att_rows(pb, metas, 2, 0, false);
+        if (gmm) {
+            head_phases(pb, metas, 2 * L + 1);
+        } else {
+            linear_tiles(pb, metas, {2 * L + 1, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, d.Wr_t, R, {}, d.br, d.radd,
+                         pm_rm(sl.ro_hist, (long long)B * R, R), pm_acc(RES_RO, 0, 0, 1), {{sl.XO, R, RES_XO, 0, 0}});
+            linear_tiles(pb, metas, {2 * L + 2, 0, sl.XO, R, RES_XO, 0, R / 16}, d.Wo_t, 64, {}, d.bo_pad, d.oadd_pad, x_next(),
+                         pm_acc(RES_X, 1, 0, 1), sl.frame_tos());
+        }
+        const std::vector<PmAccess> init = tail(pb);
+        pm_prog.dataflow = sw_pm_dataflow(0);  // (measured no gain without barriers: 57.6 us per step either way at configs[2])
+        memset(pieces_info, 0, sizeof(pieces_info));
+        finish(pb, WHOLE, d.S, check_pieces(metas, init, n_slots, 4, 4));
+    }
+    int persist_status() const { return live ? pm_status(pm_prog) : 0; }
     int steps_run(int* steps) const {
-        if (persist_ok) return pm_steps_run(pm_prog, steps);
+        if (live) return pm_steps_run(pm_prog, steps);
         if (!steps) return PH_ERR_BADARG;
         PH_CHECK(hipDeviceSynchronize());
         *steps = d.S;
@@ -367,8 +513,8 @@ struct SamplePlan : PlanBase {
     int run_persist(hipStream_t st) {
         const size_t BH = (size_t)d.B * d.H;
         for (int l = 0; l < d.L; ++l) {  // row-major initial state for the epilogues (r * h_prev, state blend; LSTM: cells)
-            PL_TRY((int)hipMemcpyAsync(hist_h[l], d.h[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if (hist_c[l]) PL_TRY((int)hipMemcpyAsync(hist_c[l], d.cwork[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
+            PL_TRY((int)hipMemcpyAsync(sl.h[l], d.h[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if (sl.c[l]) PL_TRY((int)hipMemcpyAsync(sl.c[l], d.cwork[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
         return pm_launch(pm_prog, st);
     }
@@ -384,57 +530,35 @@ struct SamplePlan : PlanBase {
     // ParrotSampleDesc::bf16: the layer units become PM_GEMM16 (persist.h) on the bf16 copies Wg_t16 -- the same slabs,
     // phases, epilogues and workspace; only the weight pointer, the unit kind and what pm_place charges for LDS differ.
     // The output tiles stay f32 units of the same program.
-    float* hist_c[PARROT_MAX_LAYERS] = {nullptr, nullptr, nullptr};
-    bool lstm_ok = false;  // (dry runs: planned and checked)
     static int slotL(int l) { return l == 0 ? 0 : l + 1; }
-    int build_persist_lstm(bool dry, int nwg_dry) {
-        lstm_ok = false;
-        if (!persist_eligible_shape(d) || !lstm_eligible(d)) return 0;
-        const int nwg = dry ? nwg_dry : pm_max_workgroups();
-        if (nwg < 64) return 0;
-        if (!dry && (!d.persist_ws || d.persist_ws_floats < persist_floats(d, nwg))) return 0;
-        const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S;
+    void build_persist_lstm(bool dry, int nwg) {
+        const int H = d.H, B = d.B, L = d.L, hc = H / 16;
         for (int l = 0; l < L && !dry; ++l)
-            if (!d.cwork[l]) return 0;
+            if (!d.cwork[l]) return;
         const long long BH = (long long)B * H;
         const bool gmm = d.gmm_K > 0;  // composed head phase + sampling phase in place of the composed output phase
-        const int NH = gmm ? d.rh_cols : 0;
-        const int n_slots = L + 2 + (gmm ? 1 : 0), sATT = 1, sOUT = L + 1, sSMP = L + 2, hc = H / 16, ec = E / 16;
+        const int n_slots = L + 2 + (gmm ? 1 : 0), sATT = 1, sOUT = L + 1;
         const int maxu = lstm_maxu(d, nwg);
         const bool w16 = d.bf16 != 0;  // (persist_eligible_shape: the widths and the copies qualify)
-        if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT || !head_fits(d, nwg)) return 0;
+        if (std::max(H / 4, B) > nwg * maxu || n_slots * maxu > PM_MAXENT) return;
         PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, maxu);
-        const long long rows = pb.rows;
-        float* XL[PARROT_MAX_LAYERS];
-        long long kx[PARROT_MAX_LAYERS];
-        for (int l = 0; l < L; ++l) {
-            kx[l] = kslab(d, l);
-            XL[l] = pb.take((S + 1) * rows * kx[l]);
-        }
-        const long long kr = (long long)L * H + E;
-        float* XR = pb.take(S * rows * kr);
-        pb.fm_end();
-        for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
-        for (int l = 0; l < L; ++l) hist_c[l] = pb.take((S + 1) * BH);
-        float* b_hist = pb.take((long long)S * B * d.A);
-        float* head = gmm ? pb.take((long long)S * B * NH) : nullptr;
-        if (pb.failed) return 0;
+        carve(pb, 0, 0);
+        if (pb.failed) return;
 
         std::vector<PmMeta> metas;
         for (int l = 0; l < L; ++l) {
-            const int nch = (int)(kx[l] / 16);
+            const int nch = (int)(sl.kx[l] / 16);
+            const std::vector<PmTo> tos = sl.state_tos(l);
             PmMeta m;
             m.lag = 0; m.slot = slotL(l);
             m.rd.push_back(pm_acc(RES_XG + l, 0, 0, nch));
             m.rd.push_back(pm_acc(RES_C + l, 0, 0, 1));
             m.wr.push_back(pm_acc(RES_C + l, 1, 0, 1));
             m.wr.push_back(pm_acc(RES_H + l, 1, 0, 1));
-            m.wr.push_back(pm_acc(RES_XG + l, 1, 0, hc));
-            for (int m2 = l + 1; m2 < L; ++m2) m.wr.push_back(pm_acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
-            m.wr.push_back(pm_acc(RES_XR, 0, l * hc, hc));
+            wr_tos(m, tos, hc);
             metas.push_back(m);
             for (int ct = 0; ct < H / 4; ++ct) {
-                PmReq q = pb.gemm(slotL(l), XL[l], kx[l]);
+                PmReq q = pb.gemm(slotL(l), sl.XG[l], sl.kx[l]);
                 PmUnit& u = q.u;
                 if (w16) {  // the tile's bf16 slab: kx / 32 blocks of 1 KB (parrot_tile_weights_bf16, mode 2)
                     u.kind = PM_GEMM16;
@@ -445,103 +569,28 @@ struct SamplePlan : PlanBase {
                 u.bias = d.bg[l] ? d.bg[l] + 4 * ct : nullptr;
                 if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 4 * ct, 0, 4 * H));
                 u.epi = PM_EPI_LSTM; u.gstr = H; u.rtile = ct & 3;
-                u.e1 = pm_rm(hist_c[l] + 4 * ct, BH, H);
-                u.o1 = pm_rm(hist_c[l] + BH + 4 * ct, BH, H);
-                u.out = pm_rm(hist_h[l] + BH + 4 * ct, BH, H);
-                pb.add_dst(u, pb.dst(XL[l], 1, kx[l], ct / 4));
-                for (int m2 = l + 1; m2 < L; ++m2) pb.add_dst(u, pb.dst(XL[m2], 0, kx[m2], hc + ec + l * hc + ct / 4));
-                pb.add_dst(u, pb.dst(XR, 0, kr, l * hc + ct / 4));
+                u.e1 = pm_rm(sl.c[l] + 4 * ct, BH, H);
+                u.o1 = pm_rm(sl.c[l] + BH + 4 * ct, BH, H);
+                u.out = pm_rm(sl.h[l] + BH + 4 * ct, BH, H);
+                add_tos(pb, u, tos, ct / 4);
                 pb.push(q);
             }
         }
-        {
-            PmMeta m;
-            m.lag = 0; m.slot = sATT;
-            m.rd.push_back(pm_acc(RES_H, 1, 0, 1));
-            m.rd.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
-            m.wr.push_back(pm_acc(RES_KAPPA, 1, 0, 1));
-            m.wr.push_back(pm_acc(RES_XG, 1, hc, ec));
-            for (int l = 1; l < L; ++l) m.wr.push_back(pm_acc(RES_XG + l, 0, hc, ec));
-            m.wr.push_back(pm_acc(RES_XR, 0, L * hc, ec));
-            metas.push_back(m);
-        }
-        pb.att_rows(sATT, 0);
-        if (gmm) {  // head: XR -> head history; sampling rows: head history -> x[t+1] and the fed-back chunks
-            PmMeta mh;
-            mh.lag = 0; mh.slot = sOUT;
-            mh.rd.push_back(pm_acc(RES_XR, 0, 0, (int)(kr / 16)));
-            mh.wr.push_back(pm_acc(RES_HEAD, 0, 0, 1));
-            metas.push_back(mh);
-            PmMeta ms;
-            ms.lag = 0; ms.slot = sSMP;
-            ms.rd.push_back(pm_acc(RES_HEAD, 0, 0, 1));
-            ms.wr.push_back(pm_acc(RES_X, 1, 0, 1));
-            std::vector<PmDst> fb;
-            for (int l = 0; l < L; ++l)
-                if (fb_rows(d, l)) {
-                    ms.wr.push_back(pm_acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
-                    fb.push_back(pb.dst(XL[l], 1, kx[l], (int)(kx[l] / 16) - 4));
-                }
-            metas.push_back(ms);
-            head_units(pb, sOUT, XR, kr, head);
-            pb.sample_rows(sSMP, 0, fb);
-        } else {
-            PmMeta m;
-            m.lag = 0; m.slot = sOUT;
-            m.rd.push_back(pm_acc(RES_XR, 0, 0, (int)(kr / 16)));
-            m.wr.push_back(pm_acc(RES_X, 1, 0, 1));
-            for (int l = 0; l < L; ++l)
-                if (fb_rows(d, l)) m.wr.push_back(pm_acc(RES_XG + l, 1, (int)(kx[l] / 16) - 4, 4));
-            metas.push_back(m);
-        }
-        for (int ct = 0; ct < 4 && !gmm; ++ct) {  // output frame x[t+1] (63 columns, padded to 64)
-            PmReq q = pb.gemm(sOUT, XR, kr);
-            PmUnit& u = q.u;
-            u.W = d.Wro_t + (size_t)ct * (kr / 16) * 256;
-            pb.add_operand(u, pm_rm(d.ro_const + 16 * ct, 0, 64));
-            u.epi = PM_EPI_LINEAR;
-            u.out = pm_rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
-            for (int l = 0; l < L; ++l)
-                if (fb_rows(d, l)) pb.add_dst(u, pb.dst(XL[l], 1, kx[l], (int)(kx[l] / 16) - 4 + ct));
-            pb.push(q);
-        }
-        std::vector<PmAccess> init;
-        for (int l = 0; l < L; ++l) {
-            init.push_back(pm_acc(RES_XG + l, 0, 0, hc));
-            init.push_back(pm_acc(RES_H + l, 0, 0, 1));
-            init.push_back(pm_acc(RES_C + l, 0, 0, 1));
-            if (fb_rows(d, l)) init.push_back(pm_acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
-        }
-        init.push_back(pm_acc(RES_XG, 0, hc, ec));
-        init.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
-        const int chk = check_pieces(metas, init, n_slots, 4, 4);
-
-        pb.att_common(d, hist_h[0]);
-        pm_prog.att.b = b_hist;
-        if (gmm) samp_common(head);
-        pb.add_wdst(pb.dst(XL[0], 1, kx[0], hc));
-        for (int l = 1; l < L; ++l) pb.add_wdst(pb.dst(XL[l], 0, kx[l], hc));
-        pb.add_wdst(pb.dst(XR, 0, kr, L * hc));
-        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XL[l], kx[l], 0);
-        pb.add_init(d.w, E, E, XL[0], kx[0], hc);
-        for (int l = 0; l < L; ++l)  // x[0] = 0 (model.py:834-835): slot 0 of d.x, converted like the other entering states
-            if (fb_rows(d, l)) pb.add_init(d.x, d.ldx, 64, XL[l], kx[l], (int)(kx[l] / 16) - 4);
+        att_rows(pb, metas, sATT, 0, false);
+        if (gmm)
+            head_phases(pb, metas, sOUT);
+        else
+            linear_tiles(pb, metas, {sOUT, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, d.Wro_t, 64, {}, nullptr, d.ro_const, x_next(),
+                         pm_acc(RES_X, 1, 0, 1), sl.frame_tos());
+        const std::vector<PmAccess> init = tail(pb);
         pm_prog.lstm = 1;
         pm_prog.w16 = w16 ? 1 : 0;
         // no grid barriers with one unit per workgroup and phase (34.9 against 38.7 us per step at 2 x 1024, B 16); with two
         // (H = 1536: 384 tiles on 256 workgroups, all weights streamed) the barriers measured faster: 114.8 against 124.9
         pm_prog.dataflow = sw_pm_dataflow(maxu == 1 ? 1 : 0);
-        pb.fill_fm();
-        for (int l = 0; l < L; ++l) {
-            pb.add_fill(hist_h[l] + BH, (long long)S * BH);
-            pb.add_fill(hist_c[l] + BH, (long long)S * BH);
-        }
-        if (gmm) pb.add_fill(head, (long long)S * B * NH);
         memset(pieces_info, 0, sizeof(pieces_info));
         pieces_info[13] = maxu;
-        lstm_ok = pb.finish(S, S, chk, pieces_info);
-        persist_ok = lstm_ok && !dry;
-        return 0;
+        finish(pb, LSTM, d.S, check_pieces(metas, init, n_slots, 4, 4));
     }
 
     // ---- round 4: the decode step cut along K by the AGE of its operands ------------------------------------------
@@ -564,8 +613,6 @@ struct SamplePlan : PlanBase {
     static bool attfold_wanted(const ParrotSampleDesc& d) {
         return d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && env_int("PARROT_PM_ATTFOLD", 1) != 0;
     }
-    bool pieces_ok = false;
-    bool fbc_on = false;
     // Round 5 ("fbc"): the fed-back frame out of the chain.  x[t+1] = x_pre + h_{L-1}[t+1] . A (A = the last layer's rows of
     // Wr . Wo), so layer 0's next gates need  x_pre . Wfg  (x_pre is complete two phases before h_{L-1}) and
     // h_{L-1} . (A . Wfg)  -- the caller composes A . Wfg / A . Wfc and appends them to layer 0's matrices (Wgx_t / Wcx_t).
@@ -581,10 +628,6 @@ struct SamplePlan : PlanBase {
     static long long kslab_p(const ParrotSampleDesc& d, int l, bool fbc) { return kslab(d, l) + ((fbc && l == 0) ? d.H : 0); }
     static int n_phases(const ParrotSampleDesc& d, bool fbc) { return fbc ? 2 * d.L + 1 : 2 * d.L + 2; }
     static int slot_pre(const ParrotSampleDesc& d) { return std::max(slotC(d.L - 2), 2) + 1; }  // (fbc) after x_pre's last operand
-    int pieces_info[16] = {0};
-
-    static int slotG(int l) { return l == 0 ? 0 : 2 * l + 1; }
-    static int slotC(int l) { return slotG(l) + 1; }
     static bool pieces_wanted(const ParrotSampleDesc& d) {
         return d.gmm_K <= 0 && d.Wro_t && d.ro_const && env_int("PARROT_PM_PIECES", 1) != 0 && 2 * d.L + 2 <= PM_MAXSLOTS;
     }
@@ -736,43 +779,20 @@ struct SamplePlan : PlanBase {
         return n;
     }
 
-    // dry = true: plan, place and check only (no device memory is touched; nwg given by the caller) -- the CPU tests
-    int build_persist_pieces(bool dry, int nwg_dry) {
-        pieces_ok = false;
-        if (d.cell != 0 || !pieces_wanted(d) || !persist_eligible_shape(d)) return 0;
-        const int nwg = dry ? nwg_dry : pm_max_workgroups();
-        if (nwg < 64) return 0;
-        if (!dry && (!d.persist_ws || d.persist_ws_floats < persist_floats(d, nwg))) return 0;
+    void build_persist_pieces(bool dry, int nwg) {
         std::vector<PmGroup> gs;
         const bool fbc = fbc_wanted(d);
-        fbc_on = false;
-        if (!piece_groups(d, gs, fbc)) return 0;
+        if (!piece_groups(d, gs, fbc)) return;
         while (!piece_slots(d, gs, nwg, fbc))   // more units than one per workgroup and phase: join two pieces and try again
-            if (!join_closest_pieces(gs)) return 0;
-        const int H = d.H, E = d.E, B = d.B, L = d.L, S = d.S;
-        const long long BH = (long long)B * H;
-        const int n_slots = n_phases(d, fbc), sATT = 2, hc = H / 16, ec = E / 16;
-        const int fbx = hc + ec, fbh = hc + ec + 4;  // (fbc) layer 0's x_pre chunks / the last layer's state chunks
+            if (!join_closest_pieces(gs)) return;
+        const int H = d.H, B = d.B, L = d.L, S = d.S;
+        const int n_slots = n_phases(d, fbc), hc = H / 16;
         PmBuilder pb(pm_prog, dry, d.persist_ws, ws_limit(dry, nwg), B, nwg, n_slots, 1);
-        const long long rows = pb.rows;
-        float* XG[PARROT_MAX_LAYERS];
-        float* XC[PARROT_MAX_LAYERS];
-        long long kx[PARROT_MAX_LAYERS];
-        for (int l = 0; l < L; ++l) {
-            kx[l] = kslab_p(d, l, fbc);
-            XG[l] = pb.take((S + 1) * rows * kx[l]);
-            XC[l] = pb.take((S + 1) * rows * kx[l]);
-        }
-        const long long kr = (long long)L * H + E;
-        float* XR = pb.take(S * rows * kr);
-        pb.fm_end();
-        float* zh[PARROT_MAX_LAYERS];
-        for (int l = 0; l < L; ++l) hist_h[l] = pb.take((S + 1) * BH);
-        for (int l = 0; l < L; ++l) zh[l] = pb.take(S * BH);
-        float* b_hist = pb.take((long long)S * B * d.A);
+        carve(pb, fbc ? H : 0, 0);  // (fbc) layer 0's slabs: x_pre in the frame's chunks, then the last layer's state
+        const int fbh = sl.fbch[0] + 4;
         const bool attfold = attfold_wanted(d) && pb.MB == 1;
         float* pp = attfold ? pb.take((long long)S * hc * B * 32) : nullptr;  // [S][H / 16][B][32] partial projections
-        float* zero_rows = fbc ? pb.take(BH) : nullptr;            // never written: the workspace arrives zero-filled
+        float* zero_rows = fbc ? pb.take((long long)B * H) : nullptr;            // never written: the workspace arrives zero-filled
         float* xpre_rm = fbc ? pb.take((long long)(S + 1) * B * 64) : nullptr;  // x_pre of step t, row-major (the output unit adds it)
         float* const part_base = pb.mark();
         int npart = 0;
@@ -784,159 +804,49 @@ struct SamplePlan : PlanBase {
                     pbuf.push_back(pb.take((long long)(S + 1) * B * g.N + 16));
                 }
         float* const part_end = pb.mark();
-        if (pb.failed) return 0;
+        if (pb.failed) return;
 
         std::vector<PmMeta> metas;
         for (const PmGroup& g : gs) {
-            const int l = g.l, N = g.N, nch_all = (int)(g.ks / 16);
-            float* slab = g.kind == 0 ? XG[l] : (g.kind == 1 ? XC[l] : XR);
+            const int l = g.l, N = g.N;
+            const float* slab = g.kind == 0 ? sl.XG[l] : (g.kind == 1 ? sl.XC[l] : sl.XR);
             const float* Wt = g.kind == 0 ? ((fbc && l == 0) ? d.Wgx_t[0] : d.Wg_t[l])
                                           : (g.kind == 1 ? ((fbc && l == 0) ? d.Wcx_t[0] : d.Wc_t[l]) : d.Wro_t);
+            std::vector<PmPart> parts;  // what the critical unit adds: the other pieces' sums
+            for (const PmPiece& o : g.pc)
+                if (!o.crit) parts.push_back({pbuf[o.pbuf], RES_PART + o.pbuf});
             for (const PmPiece& p : g.pc) {
-                PmMeta m;
-                m.lag = p.lag; m.slot = p.slot;
-                m.rd.push_back(pm_acc(g.res, 0, p.c0, p.nch));
+                const PmIn in = {p.slot, p.lag, slab, g.ks, g.res, p.c0, p.nch};
                 if (!p.crit) {
-                    m.wr.push_back(pm_acc(RES_PART + p.pbuf, 0, 0, 1));
+                    linear_tiles(pb, metas, in, Wt, N, {}, nullptr, nullptr, pm_rm(pbuf[p.pbuf], (long long)B * N, N),
+                                 pm_acc(RES_PART + p.pbuf, 0, 0, 1), {}, false);
+                } else if (g.kind == 0) {
+                    gate_tiles(pb, metas, in, Wt, l, parts);
+                } else if (g.kind == 1) {
+                    std::vector<PmTo> tos = sl.state_tos(l);
+                    if (fbc && l == L - 1)  // ... and the operand of layer 0's composed feedback rows, next step
+                        sl.each_slab(0, [&](const float* s, int res) { tos.push_back({s, sl.kx[0], res, 1, fbh}); });
+                    cand_tiles(pb, metas, in, Wt, l, parts, tos, l == 0 ? pp : nullptr);
+                } else if (g.kind == 3) {  // x_pre = ro_const + the shares of every operand but the last layer's state
+                    linear_tiles(pb, metas, in, Wt, 64, parts, nullptr, d.ro_const, pm_rm(xpre_rm, (long long)B * 64, 64),
+                                 pm_acc(RES_XPRE, 0, 0, 1), sl.frame_tos());
+                } else if (fbc) {          // x[t+1] = x_pre + the last layer's share; feeds nothing inside the loop
+                    parts.push_back({xpre_rm, RES_XPRE});
+                    linear_tiles(pb, metas, in, Wt, 64, parts, nullptr, nullptr, x_next(), pm_acc(RES_X, 1, 0, 1), {});
                 } else {
-                    for (const PmPiece& o : g.pc)
-                        if (!o.crit) m.rd.push_back(pm_acc(RES_PART + o.pbuf, 0, 0, 1));
-                    if (g.kind == 0) {
-                        m.rd.push_back(pm_acc(RES_H + l, 0, 0, 1));
-                        m.wr.push_back(pm_acc(RES_Z + l, 0, 0, 1));
-                        m.wr.push_back(pm_acc(RES_XC + l, 0, 0, hc));
-                    } else if (g.kind == 1) {
-                        m.rd.push_back(pm_acc(RES_H + l, 0, 0, 1));
-                        m.rd.push_back(pm_acc(RES_Z + l, 0, 0, 1));
-                        m.wr.push_back(pm_acc(RES_H + l, 1, 0, 1));
-                        m.wr.push_back(pm_acc(RES_XG + l, 1, 0, hc));
-                        for (int m2 = l + 1; m2 < L; ++m2) {
-                            m.wr.push_back(pm_acc(RES_XG + m2, 0, hc + ec + l * hc, hc));
-                            m.wr.push_back(pm_acc(RES_XC + m2, 0, hc + ec + l * hc, hc));
-                        }
-                        m.wr.push_back(pm_acc(RES_XR, 0, l * hc, hc));
-                        if (attfold && l == 0) m.wr.push_back(pm_acc(RES_PP, 0, 0, 1));
-                        if (fbc && l == L - 1) {
-                            m.wr.push_back(pm_acc(RES_XG, 1, fbh, hc));
-                            m.wr.push_back(pm_acc(RES_XC, 1, fbh, hc));
-                        }
-                    } else if (g.kind == 2) {
-                        m.wr.push_back(pm_acc(RES_X, 1, 0, 1));
-                        if (fbc) m.rd.push_back(pm_acc(RES_XPRE, 0, 0, 1));
-                        for (int q = 0; q < L && !fbc; ++q)
-                            if (fb_rows(d, q)) {
-                                m.wr.push_back(pm_acc(RES_XG + q, 1, (int)(kx[q] / 16) - 4, 4));
-                                m.wr.push_back(pm_acc(RES_XC + q, 1, (int)(kx[q] / 16) - 4, 4));
-                            }
-                    } else {  // x_pre
-                        m.wr.push_back(pm_acc(RES_XPRE, 0, 0, 1));
-                        m.wr.push_back(pm_acc(RES_XG, 1, fbx, 4));
-                        m.wr.push_back(pm_acc(RES_XC, 1, fbx, 4));
-                    }
-                }
-                metas.push_back(m);
-                for (int ct = 0; ct < N / 16; ++ct) {
-                    PmReq q = pb.gemm(p.slot, slab, g.ks, p.c0, p.nch * 16, p.lag);
-                    PmUnit& u = q.u;
-                    u.W = Wt + ((size_t)ct * nch_all + p.c0) * 256;
-                    q.crit = p.crit ? 1 : 0;
-                    if (!p.crit) {
-                        u.epi = PM_EPI_LINEAR;
-                        u.out = pm_rm(pbuf[p.pbuf] + 16 * ct, (long long)B * N, N);
-                        pb.push(q);
-                        continue;
-                    }
-                    for (const PmPiece& o : g.pc)
-                        if (!o.crit) pb.add_operand(u, pm_rm(pbuf[o.pbuf] + 16 * ct, (long long)B * N, N));
-                    if (g.kind == 0) {
-                        u.bias = d.bg[l] ? d.bg[l] + 16 * ct : nullptr;
-                        if (d.seq_g[l]) pb.add_operand(u, pm_rm(d.seq_g[l] + 16 * ct, 0, 2 * H));
-                        u.epi = PM_EPI_GATES;
-                        u.rtile = 16 * ct >= H;
-                        if (!u.rtile) {
-                            u.o1 = pm_rm(zh[l] + 16 * ct, BH, H);
-                        } else {
-                            const int j0 = 16 * ct - H;
-                            u.e0 = pm_rm(hist_h[l] + j0, BH, H);
-                            pb.add_dst(u, pb.dst(XC[l], 0, kx[l], j0 / 16));
-                        }
-                    } else if (g.kind == 1) {
-                        u.bias = d.bc[l] ? d.bc[l] + 16 * ct : nullptr;
-                        if (d.seq_c[l]) pb.add_operand(u, pm_rm(d.seq_c[l] + 16 * ct, 0, H));
-                        u.epi = PM_EPI_CAND;
-                        u.e0 = pm_rm(hist_h[l] + 16 * ct, BH, H);
-                        u.e1 = pm_rm(zh[l] + 16 * ct, BH, H);
-                        u.out = pm_rm(hist_h[l] + BH + 16 * ct, BH, H);
-                        pb.add_dst(u, pb.dst(XG[l], 1, kx[l], ct));
-                        for (int m2 = l + 1; m2 < L; ++m2) {
-                            const int ch = hc + ec + l * hc + ct;
-                            pb.add_dst(u, pb.dst(XG[m2], 0, kx[m2], ch));
-                            pb.add_dst(u, pb.dst(XC[m2], 0, kx[m2], ch));
-                        }
-                        pb.add_dst(u, pb.dst(XR, 0, kr, l * hc + ct));
-                        if (attfold && l == 0) {  // this tile's share of the attention projection h_1 . Watt
-                            u.pw[0] = d.Watt_t + (size_t)ct * 256;
-                            u.pw[1] = d.Watt_t + (size_t)(hc + ct) * 256;
-                            u.pp = pm_rm(pp + (size_t)ct * B * 32, (long long)hc * B * 32, 32);
-                        }
-                        if (fbc && l == L - 1) {  // ... and the operand of layer 0's composed feedback rows, next step
-                            pb.add_dst(u, pb.dst(XG[0], 1, kx[0], fbh + ct));
-                            pb.add_dst(u, pb.dst(XC[0], 1, kx[0], fbh + ct));
-                        }
-                    } else if (g.kind == 3) {  // x_pre = ro_const + the shares of every operand but the last layer's state
-                        pb.add_operand(u, pm_rm(d.ro_const + 16 * ct, 0, 64));
-                        u.epi = PM_EPI_LINEAR;
-                        u.out = pm_rm(xpre_rm + 16 * ct, (long long)B * 64, 64);
-                        pb.add_dst(u, pb.dst(XG[0], 1, kx[0], fbx + ct));
-                        pb.add_dst(u, pb.dst(XC[0], 1, kx[0], fbx + ct));
-                    } else {
-                        pb.add_operand(u, fbc ? pm_rm(xpre_rm + 16 * ct, (long long)B * 64, 64) : pm_rm(d.ro_const + 16 * ct, 0, 64));
-                        u.epi = PM_EPI_LINEAR;
-                        u.out = pm_rm(d.x + (size_t)B * d.ldx + 16 * ct, (long long)B * d.ldx, d.ldx);
-                        for (int q2 = 0; q2 < L && !fbc; ++q2) {
-                            if (!fb_rows(d, q2)) continue;
-                            const int ch = (int)(kx[q2] / 16) - 4 + ct;
-                            pb.add_dst(u, pb.dst(XG[q2], 1, kx[q2], ch));
-                            pb.add_dst(u, pb.dst(XC[q2], 1, kx[q2], ch));
-                        }
-                    }
-                    pb.push(q);
+                    linear_tiles(pb, metas, in, Wt, 64, parts, nullptr, d.ro_const, x_next(), pm_acc(RES_X, 1, 0, 1), sl.frame_tos());
                 }
             }
         }
-        {
-            PmMeta m;
-            m.lag = 1; m.slot = sATT;
-            m.rd.push_back(pm_acc(RES_H, 1, 0, 1));
-            if (attfold) m.rd.push_back(pm_acc(RES_PP, 0, 0, 1));
-            m.rd.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
-            m.wr.push_back(pm_acc(RES_KAPPA, 1, 0, 1));
-            m.wr.push_back(pm_acc(RES_XG, 1, hc, ec));
-            m.wr.push_back(pm_acc(RES_XC, 1, hc, ec));
-            for (int l = 1; l < L; ++l) {
-                m.wr.push_back(pm_acc(RES_XG + l, 0, hc, ec));
-                m.wr.push_back(pm_acc(RES_XC + l, 0, hc, ec));
-            }
-            m.wr.push_back(pm_acc(RES_XR, 0, L * hc, ec));
-            metas.push_back(m);
-        }
-        pb.att_rows(sATT, 1);
-        std::vector<PmAccess> init;
-        for (int l = 0; l < L; ++l) {
-            init.push_back(pm_acc(RES_XG + l, 0, 0, hc));
-            init.push_back(pm_acc(RES_H + l, 0, 0, 1));
-            if (fb_rows(d, l) && !fbc) {
-                init.push_back(pm_acc(RES_XG + l, 0, (int)(kx[l] / 16) - 4, 4));
-                init.push_back(pm_acc(RES_XC + l, 0, (int)(kx[l] / 16) - 4, 4));
-            }
-        }
-        if (fbc) {  // step 0: x[0] in the x_pre chunks, zero rows where the last layer's state would go
-            init.push_back(pm_acc(RES_XG, 0, fbx, 4 + hc));
-            init.push_back(pm_acc(RES_XC, 0, fbx, 4 + hc));
-        }
-        init.push_back(pm_acc(RES_XG, 0, hc, ec));
-        init.push_back(pm_acc(RES_XC, 0, hc, ec));
-        init.push_back(pm_acc(RES_KAPPA, 0, 0, 1));
+        att_rows(pb, metas, 2, 1, attfold);
+        std::vector<PmAccess> init = tail(pb);
+        pm_prog.att.pp = pp;
+        pm_prog.att.pp_st = (long long)hc * B * 32;
+        if (fbc)  // step 0: zero rows where the last layer's state would go
+            sl.each_slab(0, [&](const float* s, int res) {
+                pb.add_init(zero_rows, H, H, s, sl.kx[0], fbh);
+                init.push_back(pm_acc(res, 0, fbh, hc));
+            });
         if (sw_pm_dump_plan())
             for (const PmGroup& g : gs)
                 for (const PmPiece& p : g.pc)
@@ -944,50 +854,16 @@ struct SamplePlan : PlanBase {
                             g.kind == 0 ? "G" : (g.kind == 1 ? "C" : (g.kind == 2 ? "OUT" : "XPRE")), g.l, g.slot, p.c0, p.c0 + p.nch, p.nch * 16,
                             p.crit ? "CRITICAL" : "piece", p.slot, p.lag);
         const int n_extra = fbc ? 2 : 1;  // ticks beyond S: main units lag one tick, the output unit of the fbc plan two
-        const int chk = check_pieces(metas, init, n_slots, 4, 4 + n_extra);
-
-        pb.att_common(d, hist_h[0]);
-        PmAtt& a = pm_prog.att;
-        a.b = b_hist; a.pp = pp; a.pp_st = (long long)hc * B * 32;
-        pb.add_wdst(pb.dst(XG[0], 1, kx[0], hc));
-        pb.add_wdst(pb.dst(XC[0], 1, kx[0], hc));
-        for (int l = 1; l < L; ++l) {
-            pb.add_wdst(pb.dst(XG[l], 0, kx[l], hc));
-            pb.add_wdst(pb.dst(XC[l], 0, kx[l], hc));
-        }
-        pb.add_wdst(pb.dst(XR, 0, kr, L * hc));
-        for (int l = 0; l < L; ++l) pb.add_init(d.h[l], H, H, XG[l], kx[l], 0);
-        pb.add_init(d.w, E, E, XG[0], kx[0], hc);
-        pb.add_init(d.w, E, E, XC[0], kx[0], hc);
-        for (int l = 0; l < L && !fbc; ++l) {
-            if (!fb_rows(d, l)) continue;
-            pb.add_init(d.x, d.ldx, 64, XG[l], kx[l], (int)(kx[l] / 16) - 4);
-            pb.add_init(d.x, d.ldx, 64, XC[l], kx[l], (int)(kx[l] / 16) - 4);
-        }
-        if (fbc) {
-            pb.add_init(d.x, d.ldx, 64, XG[0], kx[0], fbx);
-            pb.add_init(d.x, d.ldx, 64, XC[0], kx[0], fbx);
-            pb.add_init(zero_rows, H, H, XG[0], kx[0], fbh);
-            pb.add_init(zero_rows, H, H, XC[0], kx[0], fbh);
-        }
         // no grid barriers by default: with the step cut into pieces a phase is ~3 us of fixed latency + a short K
         // walk, and the barrier was a quarter of it (43.0 -> 36.1 us per step at configs[2]); the whole-K plan above
         // measured no gain (57.6 either way).  Bit-identical to the barrier mode (tests/test_gpu_persist.py)
         pm_prog.dataflow = sw_pm_dataflow(1);
-        pb.fill_fm();
-        for (int l = 0; l < L; ++l) {
-            pb.add_fill(hist_h[l] + BH, (long long)S * BH);
-            pb.add_fill(zh[l], (long long)S * BH);
-        }
         pb.add_fill(part_base, (long long)(part_end - part_base));
         if (fbc) pb.add_fill(xpre_rm, (long long)(S + 1) * B * 64);
         if (attfold) pb.add_fill(pp, (long long)S * hc * B * 32);
         memset(pieces_info, 0, sizeof(pieces_info));
         pieces_info[1] = npart; pieces_info[15] = (fbc ? 1 : 0) + (attfold ? 2 : 0);
-        pieces_ok = pb.finish(S, S + n_extra, chk, pieces_info);
-        fbc_on = pieces_ok && fbc;
-        persist_ok = pieces_ok && !dry;
-        return 0;
+        finish(pb, fbc ? PIECES_FBC : PIECES, S + n_extra, check_pieces(metas, init, n_slots, 4, 4 + n_extra));
     }
 
 
@@ -1220,11 +1096,12 @@ long long parrot_sample_persist_floats(const ParrotSampleDesc* desc) { PH_ENTRY(
 }
 int parrot_sample_is_persistent(void* plan) {
     const SamplePlan* p = static_cast<SamplePlan*>(plan);
-    return p->persist_ok ? (p->pieces_ok ? (p->fbc_on ? 3 : 2) : 1) : 0;
+    static const int code[] = {0, 1, 2, 3, 1};  // SamplePlan::Program: NONE, WHOLE, PIECES, PIECES_FBC, LSTM
+    return p->live ? code[p->program] : 0;
 }
 int parrot_sample_is_bf16(void* plan) {
     const SamplePlan* p = static_cast<SamplePlan*>(plan);
-    return (p && p->persist_ok && p->pm_prog.w16) ? 1 : 0;
+    return (p && p->live && p->pm_prog.w16) ? 1 : 0;
 }
 int parrot_sample_status(void* plan) { PH_ENTRY(); return plan ? static_cast<SamplePlan*>(plan)->persist_status() : PARROT_ERR_BADARG; }
 int parrot_sample_stops_early(void* plan) {
@@ -1270,7 +1147,16 @@ int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* in
     p->d = *desc;
     p->plan_persist(true, nwg);
     for (int i = 0; i < 16; ++i) info16[i] = p->pieces_info[i];
-    return (p->pieces_ok || p->lstm_ok) ? 0 : PARROT_ERR_UNSUPPORTED;
+    return p->program != SamplePlan::NONE ? 0 : PARROT_ERR_UNSUPPORTED;
+}
+int parrot_sample_plan_digest_dry(const ParrotSampleDesc* desc, int nwg, unsigned long long* digest) { PH_ENTRY();
+    if (!desc || !digest || nwg < 1 || desc->S < 1 || desc->B < 1 || bad_dims(desc->L)) return PARROT_ERR_BADARG;
+    std::unique_ptr<SamplePlan> p(new (std::nothrow) SamplePlan());
+    if (!p) return PARROT_ERR_BADARG;
+    p->d = *desc;
+    p->plan_persist(true, nwg);
+    *digest = p->plan_digest;
+    return p->program != SamplePlan::NONE ? 0 : PARROT_ERR_UNSUPPORTED;
 }
 int parrot_sample_run(void* plan, void* stream) { PH_ENTRY(); return static_cast<PlanBase*>(plan)->run(0, (hipStream_t)stream); }
 int parrot_sample_destroy(void* plan) { PH_ENTRY();

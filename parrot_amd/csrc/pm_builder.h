@@ -3,8 +3,9 @@
 // LSTM stacks).  It owns what every program has in common -- the workspace carve-up with its bounds, the descriptor
 // constructors, the capacity checks of the fixed-size tables, placement and upload -- so that a planner only says which
 // slabs exist and which units run with which operands.  Any take() past the workspace and any append past a table's
-// capacity marks the build as failed; finish() then refuses the program and the caller falls back.  Nothing here is
-// device code; everything has internal linkage like the rest of plans_common.h.
+// capacity marks the build as failed; finish() then refuses the program and the caller falls back.  A program that
+// finish() places also gets a digest of its table and records, which the CPU tests hold the decode planners to.  Nothing
+// here is device code; everything has internal linkage like the rest of plans_common.h.
 #pragma once
 #include "plans_common.h"
 
@@ -32,6 +33,7 @@ struct PmBuilder {
     PmProgram& P;    // att, init[] and fill[] are filled through the builder, the header by finish()
     std::vector<PmReq> reqs;
     bool failed = false;
+    unsigned long long digest = 0;  // of the placed program (finish); 0 while there is none
 
     // ws / limit_floats: the caller's workspace; dry runs carve a fake one of the size the size query returns
     PmBuilder(PmProgram& prog, bool dry_, float* ws, long long limit_floats, int B_, int nwg_, int n_slots_, int maxu_)
@@ -142,7 +144,9 @@ struct PmBuilder {
     // Places the requests and, unless dry, uploads the unit table and completes the program header.  True: the program may
     // run (dry: would).  chk: the verdict of the planner's symbolic replay (0 = legal).  info16 (or null) receives what
     // parrot_sample_plan_pieces_dry reports of every plan: [0] phases, [2] chk, [3] units, [4 + phase] units of the phase,
-    // [14] units that stream their weights.
+    // [14] units that stream their weights.  `digest` then covers the bytes of the placed table and of P as the planner
+    // left it (both zero-filled before they were written; the header is not yet set), and T, n_ticks, n_slots, maxu, nwg:
+    // with the dry run's fixed workspace address it names the program a descriptor gets (parrot_sample_plan_digest_dry).
     bool finish(int T, int n_ticks, int chk = 0, int* info16 = nullptr) {
         if (info16 && !failed) {
             info16[0] = n_slots; info16[2] = chk; info16[3] = (int)reqs.size();
@@ -154,6 +158,13 @@ struct PmBuilder {
         if (info16)
             for (const PmUnit& u : table)
                 if ((u.kind == PM_GEMM || u.kind == PM_GEMM16) && u.w_lds < 0) info16[14] += 1;
+        digest = 14695981039346656037ull;  // FNV-1a, 64 bit
+        auto eat = [&](const void* p, size_t n) {
+            for (size_t i = 0; i < n; ++i) digest = (digest ^ static_cast<const unsigned char*>(p)[i]) * 1099511628211ull;
+        };
+        eat(table.data(), table.size() * sizeof(PmUnit));
+        eat(&P, sizeof(P));
+        for (int v : {T, n_ticks, n_slots, maxu, nwg}) eat(&v, sizeof(v));
         if (dry) return true;
         if (hipMemcpy(units_dev, table.data(), unit_bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
         P.T = T; P.n_ticks = n_ticks; P.nwg = nwg; P.MB = MB; P.M = B; P.n_slots = n_slots; P.maxu = maxu;

@@ -1,5 +1,6 @@
-"""The decode machine's step cut along K by the age of its operands (plans_decode.hip, build_persist_pieces): planned and
-replayed symbolically on the CPU -- no device memory is touched (parrot_sample_plan_pieces_dry)."""
+"""The GRU programs of the decode machine -- the step cut along K by the age of its operands (plans_decode.hip,
+build_persist_pieces) and the whole-K phases (build_persist_whole): planned and replayed symbolically on the CPU -- no
+device memory is touched (parrot_sample_plan_pieces_dry)."""
 import ctypes as C
 
 import pytest
@@ -93,6 +94,43 @@ def test_env_switch_keeps_the_whole_k_phases(monkeypatch):
     monkeypatch.setenv("PARROT_PM_PIECES", "0")
     rc, info = _plan(_desc())
     assert rc != 0
+
+
+@pytest.mark.parametrize("K", [0, 1, 3, 20])
+@pytest.mark.parametrize("B", [5, 37])
+@pytest.mark.parametrize("L,fb,speaker", [(1, (0,), False), (2, (), True), (2, (0, 1), False), (3, (0,), True), (3, (0, 1, 2), False)])
+def test_whole_k_program_is_planned_dry_and_replays(monkeypatch, L, fb, speaker, B, K):
+    """The 2L + 3 whole-K phases (build_persist_whole) -- what PARROT_PM_PIECES=0, a descriptor without the composed output
+    matrix and every GMM-head GRU model (PARROT_PM_GMM=1, K > 0 here) run: G_0, C_0, attention, (G_l, C_l), then readout
+    and output, or the composed head and the sampling rows.  The symbolic replay passes and every phase holds the units of
+    its kind."""
+    from tests.decode_plan_cases import desc
+    H, R = 256, 256
+    monkeypatch.setenv("PARROT_PM_PIECES", "0")
+    monkeypatch.setenv("PARROT_PM_GMM", "1")
+    d = desc(L=L, H=H, B=B, R=R, fb=fb, speaker=speaker, whole=K == 0, composed=K == 0, gmm_K=K)
+    rc, info = _plan(d)
+    assert rc == 0 and info[2] == 0, (rc, info)
+    n = 2 * L + 3
+    assert info[0] == n and info[1] == 0 and info[15] == 0
+    layers = [2 * H // 16, H // 16]
+    last = [d.rh_cols // 16, B] if K else [R // 16, 4]
+    assert info[4:4 + n] == layers + [B] + layers * (L - 1) + last
+    assert sum(info[4:4 + n]) == info[3]
+    if K:                                     # without the switch a GMM head has no machine plan
+        monkeypatch.delenv("PARROT_PM_GMM")
+        rc, info = _plan(d)
+        assert rc != 0 and info[2] == 0
+
+
+def test_whole_k_program_is_what_a_descriptor_without_the_composed_matrix_gets():
+    from tests.decode_plan_cases import desc
+    rc, info = _plan(desc(whole=True, composed=False))
+    assert rc == 0 and info[2] == 0 and info[0] == 7
+    rc, info = _plan(desc(whole=True, composed=True))      # both given: the step cut along K
+    assert rc == 0 and info[2] == 0 and info[0] == 6
+    rc, info = _plan(desc(whole=True, composed=False, unset=("bo_pad",)))
+    assert rc != 0 and info[2] == 0
 
 
 def test_composed_readout_output_is_the_same_affine_map():
