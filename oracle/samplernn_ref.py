@@ -262,10 +262,40 @@ def compute_cost(p, c, sequences, features, h0, big_h0, reset, mask, relu_ties=N
     return cost, ip_cost, new_h0, new_big_h0
 
 
-def generate(p, c, features, return_logits=False):
+_M64 = (1 << 64) - 1
+
+
+def draw_u01(seed, t, b):
+    """The uniform of the device generator's seeded draw at sample index t, stream b (sr_pick_kernel in samplernn.hip,
+    the pick of srp_kernel in sr_persist.hip), written from the formula, in Python integers masked to 64 bits: a counter
+    hash, x = seed ^ K1 (t + 1) ^ K2 (b + 1) through the splitmix64 finaliser; the top 24 bits plus one half, ROUNDED to
+    float32 (25 significant bits do not fit: the result can be exactly 1.0), times 2^-24."""
+    x = (int(seed) & _M64) ^ ((0x9E3779B97F4A7C15 * (t + 1)) & _M64) ^ ((0xBF58476D1CE4E5B9 * (b + 1)) & _M64)
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _M64
+    x ^= x >> 31
+    return float(torch.tensor(float(x >> 40) + 0.5, dtype=torch.float64).to(torch.float32)) / 2.0 ** 24
+
+
+def draw_cdf(logits, temperature):
+    """c_q = sum_{j <= q} softmax(logits / temperature)_j in float64 (last axis)."""
+    return torch.cumsum(torch.softmax(logits.to(torch.float64) / temperature, -1), -1)
+
+
+def draw_pick(logits, temperature, u01):
+    """Inverse-CDF draw: the first q with u01 < c_q, the last code when there is none."""
+    c = draw_cdf(logits, temperature)
+    below = torch.nonzero(u01 < c)
+    return int(below[0]) if below.numel() else c.numel() - 1
+
+
+def generate(p, c, features, return_logits=False, temperature=0.0, seed=234):
     """generate_and_save_samples loop (three_tier.py:794-832) with the temperature-0 sampler
-    (softmax_and_argmax, ops.py:296-297; argmax ties -> lowest index).  features [T,B,63] time-major.
-    Returns samples [B, 80*T] int32 (first 80 = Q_ZERO)."""
+    (softmax_and_argmax, ops.py:296-297; argmax ties -> lowest index), or, for temperature > 0, the device generator's
+    seeded multinomial draw (draw_u01 / draw_pick; Theano's MRG stream is not reproducible).  features [T,B,63]
+    time-major.  Returns samples [B, 80*T] int32 (first 80 = Q_ZERO)."""
     BFS, FS, D = c['BIG_FRAME_SIZE'], c['FRAME_SIZE'], c['DIM']
     feats = features.transpose(0, 1)
     B, LENGTH = feats.shape[0], feats.shape[1] * BFS
@@ -286,7 +316,10 @@ def generate(p, c, features, return_logits=False):
         logits = sample_level_predictor(p, c, frame_out[:, t % FS], samples[:, t - FS:t])
         if return_logits:
             all_logits.append(logits)
-        samples[:, t] = torch.argmax(torch.softmax(logits, -1), -1)
+        if temperature > 0:
+            samples[:, t] = torch.tensor([draw_pick(logits[b], temperature, draw_u01(seed, t, b)) for b in range(B)])
+        else:
+            samples[:, t] = torch.argmax(torch.softmax(logits, -1), -1)
     if return_logits:
         return samples.to(torch.int32), torch.stack(all_logits, 1)
     return samples.to(torch.int32)
