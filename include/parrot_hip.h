@@ -574,7 +574,17 @@ typedef struct ParrotSampleDesc {
      *              lstm_H = H), rows*cols bf16; Wg_t[l] is then not read and may be NULL.
      * Resident bf16 slabs take half the LDS, so more of them stay on chip, and the streamed ones move half the bytes.
      * There is no f32 decode behind this switch: parrot_sample_create returns PARROT_ERR_UNSUPPORTED for every configuration
-     * the bf16 machine does not take (parrot_sample_persist_floats returns 0 for them). */
+     * the bf16 machine does not take (parrot_sample_persist_floats returns 0 for them).
+     * GRU stacks (cell = 0), opt-in (PARROT_PM_GRU_BF16=1; unset or 0: refused as before): the two products per layer and step,
+     * gates [h_l[t] ; ..] . Wg_t[l] and candidate [r * h_l[t] ; ..] . Wc_t[l], round both operands the same way (r * h_l[t] is
+     * rounded where it enters the candidate product); gate activations, the state blend, the attention and the readout /
+     * output tiles stay f32.  Same conditions (MSE head, no layer_norm, B <= 64, H and E multiples of 32), and
+     *   Wg_t16[l] / Wc_t16[l] (the last field of this struct): the matrices of Wg_t[l] (2H columns) / Wc_t[l] (H columns),
+     *              feedback rows appended and padded to 64, as parrot_tile_weights_bf16(.., mode 2, lstm_H = 0); Wg_t[l] and
+     *              Wc_t[l] are then not read and may be NULL.
+     * Both GRU programs take them (the step cut along K, or the whole-K phases under PARROT_PM_PIECES=0 / without Wro_t);
+     * Wgx_t / Wcx_t / Watt_t are NOT taken under bf16: the composed rows A . Wf and the folded projection would round at other
+     * points than x . Wf and h . Watt do.  The output tiles (Wro_t, or Wr_t / Wo_t) are f32 units of the same program. */
     int bf16, reserved8;
     const void* Wg_t16[PARROT_MAX_LAYERS];
     /* eou_extra > 0: stop at the end of the utterance, inside the persistent machine.  Row b's predicate at step t (0-based)
@@ -609,6 +619,9 @@ typedef struct ParrotSampleDesc {
     const float* Wrh_t;
     const float* rh_const;
     int rh_cols, reserved10;
+    /* bf16 = 1, GRU stacks (PARROT_PM_GRU_BF16=1): the bf16 copies of the candidate matrices, see Wg_t16 above.  Appended
+     * here: the fields above keep their offsets. */
+    const void* Wc_t16[PARROT_MAX_LAYERS];
 } ParrotSampleDesc;
 
 long long parrot_sample_persist_floats(const ParrotSampleDesc* desc);

@@ -149,6 +149,7 @@ class SampleDesc(C.Structure):
         ("eou_pos", C.c_void_p), ("eou_ncmp", C.c_void_p), ("eou_first", C.c_void_p),
         ("eou_extra", C.c_int), ("reserved9", C.c_int),
         ("Wrh_t", C.c_void_p), ("rh_const", C.c_void_p), ("rh_cols", C.c_int), ("reserved10", C.c_int),
+        ("Wc_t16", C.c_void_p * MAX_LAYERS),
     ]
 
 

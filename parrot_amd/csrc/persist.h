@@ -149,7 +149,7 @@ struct PmProgram {
     int T, n_ticks, nwg, MB, M, ninit, n_slots, maxu;  // a tick = n_slots phases of up to maxu units per workgroup
     int dataflow, nfill;
     int lstm, w16;        // lstm: some units are PM_EPI_LSTM (selects the kernels compiled with that epilogue); w16: some
-                          // are PM_GEMM16 (the kernels that also carry the bf16 K loop; LSTM programs only)
+                          // are PM_GEMM16 (the kernels that also carry the bf16 K loop; decode programs, LSTM or GRU)
     PmFill fill[PM_MAXFILL];
     const PmUnit* units;  // device: [n_slots][nwg][maxu]
     unsigned* sync;       // device: PM_SYNC_WORDS + PM_DBG_WORDS unsigned, zeroed before every launch

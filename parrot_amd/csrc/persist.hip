@@ -1119,7 +1119,7 @@ int pm_steps_run(const PmProgram& P, int* steps) {
 
 int pm_launch(const PmProgram& P, hipStream_t stream) {
     if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
-        P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL || (P.w16 && !P.lstm))
+        P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL)
         return PH_ERR_BADARG;
     if (P.samp.K != 0 && (P.w16 || P.samp.K < 1 || P.samp.K > 64 || P.samp.O < 1 || P.samp.O > 64 || P.samp.ldx < 64 || (P.samp.ldx % 4) ||
                           (P.samp.head.ld % 4) || P.samp.head.ld < 2 * P.samp.O * P.samp.K + P.samp.K || !P.samp.head.p || !P.samp.unif ||
@@ -1176,6 +1176,15 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
         PM_ATTRS6(false, true); PM_ATTRS6(true, true);
 #undef PM_ATTRS6
 #undef PM_ATTRS
+        // behind them the kernels of the GRU programs with bf16 layer units (no LSTM epilogue, the bf16 K loop)
+#define PM_ATTRG(MB_, DF_, EOU_) \
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, false, true, EOU_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+#define PM_ATTRG6(EOU_) \
+    PM_ATTRG(1, false, EOU_); PM_ATTRG(2, false, EOU_); PM_ATTRG(4, false, EOU_); \
+    PM_ATTRG(1, true, EOU_); PM_ATTRG(2, true, EOU_); PM_ATTRG(4, true, EOU_)
+        PM_ATTRG6(false); PM_ATTRG6(true);
+#undef PM_ATTRG6
+#undef PM_ATTRG
         attr_done = true;
     }
     const dim3 grid(P.nwg), block(PM_THREADS);
@@ -1183,7 +1192,8 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     do { \
         if (P.samp.K > 0 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, true>), grid, block, lds, stream, P); \
         else if (P.samp.K > 0) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, true>), grid, block, lds, stream, P); \
-        else if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_, false>), grid, block, lds, stream, P); \
+        else if (P.w16 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_, false>), grid, block, lds, stream, P); \
+        else if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, true, EOU_, false>), grid, block, lds, stream, P); \
         else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, false>), grid, block, lds, stream, P); \
         else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, false>), grid, block, lds, stream, P); \
     } while (0)

@@ -183,13 +183,24 @@ struct SamplePlan : PlanBase {
         return d.gmm_K <= 0 || d.rh_cols / 16 <= nwg * (d.cell == 1 ? lstm_maxu(d, nwg) : 1);
     }
     static long long head_floats(const ParrotSampleDesc& d) { return d.gmm_K > 0 ? (long long)d.S * d.B * d.rh_cols + 16 : 0; }
-    // bf16 operands (ParrotSampleDesc::bf16): LSTM stacks only, 32-deep K steps, the bf16 copies in place of Wg_t.  A
-    // descriptor that asks for them and does not qualify gets NO machine plan -- parrot_sample_create then refuses it.
+    // bf16 operands (ParrotSampleDesc::bf16): 32-deep K steps, the bf16 copies in place of Wg_t (GRU: and Wc_t).  LSTM
+    // stacks; GRU stacks are opt-in through PARROT_PM_GRU_BF16=1 -- read HERE and nowhere else in the library -- with an MSE
+    // head (a GMM head never qualifies under bf16: gmm_eligible; layer_norm never reaches this).  A descriptor that asks for
+    // bf16 operands and does not qualify gets NO machine plan -- parrot_sample_create then refuses it.
     static bool bf16_eligible(const ParrotSampleDesc& d) {
-        if (d.cell != 1 || (d.H % 32) || (d.E % 32)) return false;
+        if ((d.cell != 0 && d.cell != 1) || (d.H % 32) || (d.E % 32)) return false;
+        if (d.cell == 0 && (env_int("PARROT_PM_GRU_BF16", 0) == 0 || d.gmm_K > 0 || d.layer_norm)) return false;
         for (int l = 0; l < d.L; ++l)
-            if (!d.Wg_t16[l]) return false;
+            if (!d.Wg_t16[l] || (d.cell == 0 && !d.Wc_t16[l])) return false;
         return true;
+    }
+    // The weights of a product: fragment-major f32 blocks, or (w16) the bf16 copy in the machine's K order -- tile() below.
+    struct PmW { const void* p; bool w16; };
+    static PmW w32(const float* W) { return {W, false}; }
+    // layer l's gate (kind 0) / candidate (kind 1) matrix of a GRU program
+    PmW layer_w(int kind, int l) const {
+        if (d.bf16) return {kind == 0 ? d.Wg_t16[l] : d.Wc_t16[l], true};
+        return w32(kind == 0 ? d.Wg_t[l] : d.Wc_t[l]);
     }
     // LSTM stacks (cell == 1): one phase per layer, readout and output composed (Wro_t / ro_const) -- build_persist_lstm
     static bool lstm_eligible(const ParrotSampleDesc& d) {
@@ -235,7 +246,7 @@ struct SamplePlan : PlanBase {
         program = NONE;
         live = false;
         plan_digest = 0;
-        if (!persist_eligible_shape(d)) return;  // (bf16 on a GRU stack too: no plan rather than an f32 one)
+        if (!persist_eligible_shape(d)) return;  // (bf16 that does not qualify: no plan rather than an f32 one)
         const int nwg = dry ? nwg_dry : pm_max_workgroups();
         if (nwg < 64 || !head_fits(d, nwg)) return;
         if (!dry && (!d.persist_ws || d.persist_ws_floats < persist_floats(d, nwg))) return;
@@ -303,9 +314,18 @@ struct SamplePlan : PlanBase {
 
     // Column tile ct of a product over `in`, W = its fragment-major weights ([N / 16][ks / 16] blocks of 16 x 16); `parts`
     // are added in the epilogue.  The meta of the kind starts the same way: what every tile of it reads.
-    PmReq tile(PmBuilder& pb, const PmIn& in, const float* W, int ct, const std::vector<PmPart>& parts, int N) const {
+    // W.w16: a PM_GEMM16 unit on the tile's bf16 slab, [N / 16][ks / 32] blocks of 1 KB (32 K-rows each), so the chunk range
+    // must start and end on a 32-row boundary: every piece boundary does when H and E are multiples of 32 (the fed-back
+    // rows are 64); a range that does not fails the build.
+    PmReq tile(PmBuilder& pb, const PmIn& in, PmW W, int ct, const std::vector<PmPart>& parts, int N) const {
         PmReq q = pb.gemm(in.slot, in.slab, in.ks, in.c0, in.nch * 16, in.lag);
-        q.u.W = W + ((size_t)ct * (in.ks / 16) + in.c0) * 256;
+        if (W.w16) {
+            if ((in.c0 & 1) || (in.nch & 1) || (in.ks % 32)) pb.failed = true;
+            q.u.kind = PM_GEMM16;
+            q.u.W = reinterpret_cast<const float*>(static_cast<const char*>(W.p) + ((size_t)ct * (in.ks / 32) + in.c0 / 2) * 1024);
+        } else {
+            q.u.W = static_cast<const float*>(W.p) + ((size_t)ct * (in.ks / 16) + in.c0) * 256;
+        }
         for (const PmPart& p : parts) pb.add_operand(q.u, pm_rm(p.buf + 16 * ct, (long long)d.B * N, N));
         return q;
     }
@@ -317,7 +337,7 @@ struct SamplePlan : PlanBase {
         return m;
     }
     // G_l: z -> its history, r * h_l[t] -> the head of the candidate slab
-    void gate_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, const float* W, int l, const std::vector<PmPart>& parts) {
+    void gate_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, PmW W, int l, const std::vector<PmPart>& parts) {
         const int H = d.H;
         const long long BH = (long long)d.B * H;
         for (int ct = 0; ct < 2 * H / 16; ++ct) {
@@ -344,7 +364,7 @@ struct SamplePlan : PlanBase {
     }
     // C_l -> h_l[t+1], into `tos`.  pp: this tile's share of the attention projection h_1 . Watt goes there (layer 0's
     // tiles of a program that folds it, PmUnit::pw / pp), else null.
-    void cand_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, const float* W, int l, const std::vector<PmPart>& parts,
+    void cand_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, PmW W, int l, const std::vector<PmPart>& parts,
                     const std::vector<PmTo>& tos, float* pp) {
         const int H = d.H, B = d.B, hc = sl.hc;
         const long long BH = (long long)B * H;
@@ -376,7 +396,7 @@ struct SamplePlan : PlanBase {
     // Every plain product -- a piece's partial sums, readout, output frame, x_pre, GMM head: the N / 16 column tiles of
     // in . W + bias + parts + add ([B, N] row-major, the same for every step) -> out (row-major, `wr` in the replay) and `tos`.
     // crit: on the step's dependency chain (pm_place serves those first).
-    void linear_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, const float* W, int N, const std::vector<PmPart>& parts,
+    void linear_tiles(PmBuilder& pb, std::vector<PmMeta>& metas, const PmIn& in, PmW W, int N, const std::vector<PmPart>& parts,
                       const float* bias, const float* add, PmRM out, PmAccess wr, const std::vector<PmTo>& tos, bool crit = true) {
         for (int ct = 0; ct < N / 16; ++ct) {
             PmReq q = tile(pb, in, W, ct, parts, N);
@@ -412,7 +432,7 @@ struct SamplePlan : PlanBase {
     // and the fed-back chunks; and what the sampling rows read (PmSamp)
     void head_phases(PmBuilder& pb, std::vector<PmMeta>& metas, int slot) {
         const int NH = d.rh_cols;
-        linear_tiles(pb, metas, {slot, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, d.Wrh_t, NH, {}, nullptr, d.rh_const,
+        linear_tiles(pb, metas, {slot, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, w32(d.Wrh_t), NH, {}, nullptr, d.rh_const,
                      pm_rm(sl.head, (long long)d.B * NH, NH), pm_acc(RES_HEAD, 0, 0, 1), {});
         const std::vector<PmTo> tos = sl.frame_tos();
         std::vector<PmDst> fb;
@@ -484,19 +504,20 @@ struct SamplePlan : PlanBase {
         std::vector<PmMeta> metas;
         for (int l = 0; l < L; ++l) {
             const int nch = (int)(sl.kx[l] / 16);
-            gate_tiles(pb, metas, {slotG(l), 0, sl.XG[l], sl.kx[l], RES_XG + l, 0, nch}, d.Wg_t[l], l, {});
-            cand_tiles(pb, metas, {slotC(l), 0, sl.XC[l], sl.kx[l], RES_XC + l, 0, nch}, d.Wc_t[l], l, {}, sl.state_tos(l), nullptr);
+            gate_tiles(pb, metas, {slotG(l), 0, sl.XG[l], sl.kx[l], RES_XG + l, 0, nch}, layer_w(0, l), l, {});
+            cand_tiles(pb, metas, {slotC(l), 0, sl.XC[l], sl.kx[l], RES_XC + l, 0, nch}, layer_w(1, l), l, {}, sl.state_tos(l), nullptr);
         }
         att_rows(pb, metas, 2, 0, false);
         if (gmm) {
             head_phases(pb, metas, 2 * L + 1);
         } else {
-            linear_tiles(pb, metas, {2 * L + 1, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, d.Wr_t, R, {}, d.br, d.radd,
+            linear_tiles(pb, metas, {2 * L + 1, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, w32(d.Wr_t), R, {}, d.br, d.radd,
                          pm_rm(sl.ro_hist, (long long)B * R, R), pm_acc(RES_RO, 0, 0, 1), {{sl.XO, R, RES_XO, 0, 0}});
-            linear_tiles(pb, metas, {2 * L + 2, 0, sl.XO, R, RES_XO, 0, R / 16}, d.Wo_t, 64, {}, d.bo_pad, d.oadd_pad, x_next(),
+            linear_tiles(pb, metas, {2 * L + 2, 0, sl.XO, R, RES_XO, 0, R / 16}, w32(d.Wo_t), 64, {}, d.bo_pad, d.oadd_pad, x_next(),
                          pm_acc(RES_X, 1, 0, 1), sl.frame_tos());
         }
         const std::vector<PmAccess> init = tail(pb);
+        pm_prog.w16 = d.bf16 ? 1 : 0;  // (the layer units are PM_GEMM16; readout and output tiles stay f32 units)
         pm_prog.dataflow = sw_pm_dataflow(0);  // (measured no gain without barriers: 57.6 us per step either way at configs[2])
         memset(pieces_info, 0, sizeof(pieces_info));
         finish(pb, WHOLE, d.S, check_pieces(metas, init, n_slots, 4, 4));
@@ -580,7 +601,7 @@ struct SamplePlan : PlanBase {
         if (gmm)
             head_phases(pb, metas, sOUT);
         else
-            linear_tiles(pb, metas, {sOUT, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, d.Wro_t, 64, {}, nullptr, d.ro_const, x_next(),
+            linear_tiles(pb, metas, {sOUT, 0, sl.XR, sl.kr, RES_XR, 0, (int)(sl.kr / 16)}, w32(d.Wro_t), 64, {}, nullptr, d.ro_const, x_next(),
                          pm_acc(RES_X, 1, 0, 1), sl.frame_tos());
         const std::vector<PmAccess> init = tail(pb);
         pm_prog.lstm = 1;
@@ -611,7 +632,9 @@ struct SamplePlan : PlanBase {
     // read satisfied by a write of a strictly earlier phase, every buffer element written once) before it is used.
     // Round 5: the attention projection folded into layer 0's candidate units (PmUnit::pw / pp, persist.hip)
     static bool attfold_wanted(const ParrotSampleDesc& d) {
-        return d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && env_int("PARROT_PM_ATTFOLD", 1) != 0;
+        // (bf16 operands: not taken -- the oracle's projection is an exact product of h_1, and the f32-only fold of
+        // pm_gemm is not part of a PM_GEMM16 unit)
+        return !d.bf16 && d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && env_int("PARROT_PM_ATTFOLD", 1) != 0;
     }
     // Round 5 ("fbc"): the fed-back frame out of the chain.  x[t+1] = x_pre + h_{L-1}[t+1] . A (A = the last layer's rows of
     // Wr . Wo), so layer 0's next gates need  x_pre . Wfg  (x_pre is complete two phases before h_{L-1}) and
@@ -620,6 +643,7 @@ struct SamplePlan : PlanBase {
     // 2L + 1 dependent phases (G_0 with K = H critical instead of K = 64, but one phase of ~5 us less).
     static bool fbc_wanted(const ParrotSampleDesc& d) {
         if (env_int("PARROT_PM_FBC", 1) == 0) return false;
+        if (d.bf16) return false;  // composed rows A . Wf would round at other points than the oracle's x . Wf
         if (d.L < 2 || !d.Wgx_t[0] || !d.Wcx_t[0] || !fb_rows(d, 0)) return false;
         for (int l = 1; l < d.L; ++l)
             if (fb_rows(d, l)) return false;
@@ -810,8 +834,9 @@ struct SamplePlan : PlanBase {
         for (const PmGroup& g : gs) {
             const int l = g.l, N = g.N;
             const float* slab = g.kind == 0 ? sl.XG[l] : (g.kind == 1 ? sl.XC[l] : sl.XR);
-            const float* Wt = g.kind == 0 ? ((fbc && l == 0) ? d.Wgx_t[0] : d.Wg_t[l])
-                                          : (g.kind == 1 ? ((fbc && l == 0) ? d.Wcx_t[0] : d.Wc_t[l]) : d.Wro_t);
+            // (bf16 operands: the layer products on the bf16 copies, never composed -- fbc_wanted; the output tiles stay f32)
+            const PmW Wt = g.kind >= 2 ? w32(d.Wro_t)
+                                       : ((fbc && l == 0) ? w32(g.kind == 0 ? d.Wgx_t[0] : d.Wcx_t[0]) : layer_w(g.kind, l));
             std::vector<PmPart> parts;  // what the critical unit adds: the other pieces' sums
             for (const PmPiece& o : g.pc)
                 if (!o.crit) parts.push_back({pbuf[o.pbuf], RES_PART + o.pbuf});
@@ -842,6 +867,7 @@ struct SamplePlan : PlanBase {
         std::vector<PmAccess> init = tail(pb);
         pm_prog.att.pp = pp;
         pm_prog.att.pp_st = (long long)hc * B * 32;
+        pm_prog.w16 = d.bf16 ? 1 : 0;  // (every piece of a layer product is a PM_GEMM16 unit; the output tiles stay f32)
         if (fbc)  // step 0: zero rows where the last layer's state would go
             sl.each_slab(0, [&](const float* s, int res) {
                 pb.add_init(zero_rows, H, H, s, sl.kx[0], fbh);

@@ -39,6 +39,9 @@
 // PARROT_PM_GMM            0        plan     1: GMM-head models decode on the sampling machine too (composed   tests, tools
 //                                            head phase + sampling phase; GRU whole-K and LSTM programs).
 //                                            Python prepares the composed head and lifts its refusals when 1
+// PARROT_PM_GRU_BF16       0        plan     1: decode_dtype='bf16' / ParrotSampleDesc::bf16 also decodes GRU   tests, tools
+//                                            stacks (bf16 layer units in both GRU programs; no attention fold,
+//                                            no composed feedback rows).  Python lifts its GRU refusal when 1
 // PARROT_PM_DUMP_PLAN      unset    plan,    set: print the sampling machine's pieces and the barrier words  development
 //                                   failure  of a persistent launch that gave up
 // PARROT_SR_PERSIST        1        plan     0: SampleRNN sampling without its persistent kernel             tests

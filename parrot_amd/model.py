@@ -1499,7 +1499,7 @@ class Parrot(Brick):
                     pm['cat'][(l, key)] = torch.zeros(rows, wd, **f)
                     if self.decode_bf16:  # the bf16 copy in the machine's K order takes the place of the f32 one
                         pm['tiled'][(l, key)] = torch.empty(rows, wd, device=self._dev(), dtype=torch.bfloat16)
-                        d.Wg_t16[l] = pm['tiled'][(l, key)].data_ptr()
+                        getattr(d, f'W{key}_t16')[l] = pm['tiled'][(l, key)].data_ptr()  # (GRU: 'g' and 'c', a copy each)
                         continue
                     pm['tiled'][(l, key)] = torch.empty(rows, wd, **f)
                     getattr(d, f'W{key}_t')[l] = pm['tiled'][(l, key)].data_ptr()
@@ -1525,14 +1525,17 @@ class Parrot(Brick):
                 pm['Wro'], pm['Wro_t'] = torch.empty(L * H + E, 64, **f), torch.empty(L * H + E, 64, **f)
                 pm['ro_const'] = torch.zeros(N, 64, **f)
                 d.Wro_t, d.ro_const = pm['Wro_t'].data_ptr(), pm['ro_const'].data_ptr()
-                if not lstm and N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
+                # (bf16 operands: neither the fold nor the composed feedback rows below -- both would round at other points
+                # than the products they replace, and the bf16 plan does not take them)
+                if not lstm and not self.decode_bf16 and N <= 16 and 3 * A <= 32 and env_int('PARROT_PM_ATTFOLD', 1) != 0:
                     # round 5: the attention projection as an [H, 32] matrix (fragment-major): layer 0's candidate units fold
                     # their tile's share of h_1 . Watt into their epilogue (ParrotSampleDesc::Watt_t)
                     pm['Watt_pad'], pm['Watt_t'] = torch.zeros(H, 32, **f), torch.empty(H, 32, **f)
                     d.Watt_t = pm['Watt_t'].data_ptr()
                 # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
                 # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
-                if not lstm and L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
+                if (not lstm and not self.decode_bf16 and L >= 2 and self._fb_layers == [1]
+                        and env_int('PARROT_PM_FBC', 1) != 0):
                     for key, wd, suf, mat, rec in self._groups:
                         rows = H + E + 64 + H
                         pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)
@@ -1589,8 +1592,10 @@ class Parrot(Brick):
     def _decode_bf16_refusal(self, N):
         """Why this model / batch cannot decode with bf16 operands ('' when it can): what the bf16 machine does not take."""
         H, E = self.rnn_h_dim, self.encoded_input_dim
-        if self.cell_type != 'lstm':
-            return "needs cell_type='lstm': GRU decoders have no bf16 decode path"
+        # the one read of the switch on this side (csrc/switches.h): bf16 operands for GRU decoders are opt-in
+        if self.cell_type != 'lstm' and env_int('PARROT_PM_GRU_BF16', 0) == 0:
+            return ("needs cell_type='lstm': GRU decoders have no bf16 decode path "
+                    "(unless PARROT_PM_GRU_BF16=1 opts in to the bf16 GRU programs)")
         why = self._decode_machine_refusal(N)
         if not why and self.which_cost != 'MSE':  # (PARROT_PM_GMM=1: the machine takes the head, with f32 operands only)
             return "needs which_cost='MSE': the GMM head decodes on the persistent machine with f32 operands only"

@@ -1,11 +1,14 @@
 """Secondary measurements (BASELINE configs[2] decode latency, the same loop with LSTM decoders -- persistent machine
 with bf16 operands (decode_dtype='bf16') against the f32 machine against the per-step launches, alternating child
-processes --, both with a GMM head (k_gmm = 20) on the machine (PARROT_PM_GMM=1) against the launches, the configs[2] decode that stops at the end of the utterance against the one that runs all its steps,
+processes --, GRU decoders with bf16 operands (PARROT_PM_GRU_BF16=1) against the f32 machine from 2 x 1024 to 3 x 1536, alternating in one
+process; the LSTM and GRU shapes with a GMM head (k_gmm = 20) on the machine (PARROT_PM_GMM=1) against the launches, the configs[2] decode that stops at the end of the utterance against the one that runs all its steps,
 configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / documentation aid; the driver's headline bench is bench.py.
 
   bench_extra.py                         everything, one JSON line
   bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_stop, decode_lstm2_1024, decode_lstm3_1536,
-                                         decode_gmm_gru2_1024, decode_gmm_lstm2_1024, samplernn_cfg5, mulaw)
+                                         decode_gmm_gru2_1024, decode_gmm_lstm2_1024, decode_bf16_gru2_1024,
+                                         decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
+                                         samplernn_cfg5, mulaw)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -29,12 +32,19 @@ def _arg(name, dflt=None):
 
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
-       "samplernn_cfg5", "mulaw")
+       "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "mulaw")
 only = tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
     "decode_lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024),
     "decode_lstm3_1536": dict(num_layers=3, rnn_h_dim=1536, readouts_dim=1536),
+}
+GRU_BF16_SHAPES = {  # configs[2] (2 x GRU-1024), a 3 x GRU-1536 stack whose f32 layer matrices no longer fit in LDS, and two
+    # shapes between them (where bf16 operands start to pay)
+    "decode_bf16_gru2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024),
+    "decode_bf16_gru3_1024": dict(num_layers=3, rnn_h_dim=1024, readouts_dim=1024),
+    "decode_bf16_gru2_1536": dict(num_layers=2, rnn_h_dim=1536, readouts_dim=1536),
+    "decode_bf16_gru3_1536": dict(num_layers=3, rnn_h_dim=1536, readouts_dim=1536),
 }
 GMM_SHAPES = {  # the decode_cfg3 / decode_lstm2_1024 shapes with the mixture-density head (which_cost='GMM', k_gmm=20)
     "decode_gmm_gru2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='gru', which_cost='GMM', k_gmm=20),
@@ -126,6 +136,55 @@ def decode_stop(kappa_bias, reps):
            "us_per_step_plain": us(t["plain"]), "us_per_step_stop_plan_never_firing": us(t["never"]),
            "us_per_step_stopped": [round(1e6 * x / steps, 2) for x in t["stopped"]]}
     m.close()
+    return res
+
+
+def decode_gru_bf16(kw, reps, whole_too):
+    """GRU decode with bf16 operands (PARROT_PM_GRU_BF16=1, decode_dtype='bf16') against the f32 machine of the same model,
+    batch 16, 1000 frames, alternating within one process; whole_too: also the bf16 whole-K phases (PARROT_PM_PIECES=0) beside
+    the bf16 step cut along K.  The switches are read when a model's plan is built (its first call), so every model makes its
+    first call under its own environment and keeps that plan.  Whole-call wall times around a device synchronise, every call
+    listed; the first round (plans, graph capture) is not."""
+    from parrot_amd import _lib
+    from parrot_amd.model import Parrot
+    g = torch.Generator().manual_seed(0)
+    N, U, S = 16, 100, 1000
+    lab = torch.randint(0, 43, (N, U), generator=g)
+    lm = torch.ones(N, U)
+    legs = [("bf16", "bf16", {}), ("f32", "float32", {})] + ([("bf16_whole_k", "bf16", {"PARROT_PM_PIECES": "0"})] if whole_too else [])
+    saved = {k: os.environ.get(k) for k in ("PARROT_PM_GRU_BF16", "PARROT_PM_PIECES")}
+    os.environ["PARROT_PM_GRU_BF16"] = "1"
+    models, t, info = {}, {}, {}
+    try:
+        for key, dtype, env in legs:
+            os.environ.update(env)
+            m = models[key] = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, cell_type='gru',
+                                     decode_dtype=dtype, **kw).initialize()
+            m.sample_model_device(lab, lm, None, N, S)
+            torch.cuda.synchronize()
+            for k in env:
+                os.environ.pop(k)
+            ws = m._sample_ws[(S, N, U)]
+            lib = _lib.load()
+            info[key] = {"machine": int(lib.parrot_sample_is_persistent(ws['plan'])), "bf16": int(lib.parrot_sample_is_bf16(ws['plan']))}
+            assert info[key]["machine"] != 0 and (info[key]["bf16"] != 0) == (dtype == "bf16"), (key, info[key])
+            t[key] = []
+        for rep in range(reps):
+            for key, _, _ in legs:
+                torch.cuda.synchronize(); t0 = time.time()
+                models[key].sample_model_device(lab, lm, None, N, S)
+                torch.cuda.synchronize()
+                t[key].append(round(1e6 * (time.time() - t0) / S, 2))
+    finally:
+        for k, v in saved.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+        for m in models.values():
+            m.close()
+    res = {"batch": N, "frames": S, "plans": info, "us_per_step": t,
+           "spread_us": {k: round(max(v) - min(v), 2) for k, v in t.items()},
+           "bf16_faster": max(t["bf16"]) < min(t["f32"]), "f32_faster": max(t["f32"]) < min(t["bf16"])}
+    if whole_too:
+        res["bf16_pieces_faster_than_whole_k"] = max(t["bf16"]) < min(t["bf16_whole_k"])
     return res
 
 
@@ -299,6 +358,12 @@ for name in GMM_SHAPES:
                  "us_per_step_launches": runs["launches"],
                  "spread_us": {k: round(max(v) - min(v), 2) for k, v in runs.items()},
                  "machine_faster": max(runs["machine"]) < min(runs["launches"])}
+
+# ---- GRU decoders with bf16 operands (PARROT_PM_GRU_BF16=1) against the f32 machine, alternating in one process; at the
+# configs[2] shape also the bf16 whole-K phases against the bf16 step cut along K
+for name in GRU_BF16_SHAPES:
+    if name in only:
+        out[name] = decode_gru_bf16(GRU_BF16_SHAPES[name], int(_arg("--reps", "3")), whole_too=name == "decode_bf16_gru2_1024")
 
 # ---- configs[4]: SampleRNN 3-tier GRU D=1024, batch 32, greedy, 16 kHz mu-law
 if "samplernn_cfg5" in only:
