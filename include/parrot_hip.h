@@ -848,13 +848,24 @@ typedef struct SampleRnnGenDesc {
      * samplernn_persist_floats(desc) floats (create initialises it; it belongs to ONE plan).  With it (B <= 32, D in {256, 512, 1024},
      * Q = 256, a 256-CU device) the FS sample steps between two frame-tier steps run as ONE launch: each XCD takes four
      * streams through the whole sample-level MLP with its weights held in LDS / registers and hand-offs that stay inside
-     * the XCD's L2.  NULL or a non-qualifying configuration: five launches per sample as before. */
+     * the XCD's L2.  NULL or a non-qualifying configuration: five launches per sample as before.
+     * PARROT_SR_PERSIST_GROUPS = G (1 .. 8, default 1; read by samplernn_persist_floats and create) lifts the batch limit to
+     * B <= 32 G: one launch then takes the batch in ceil(B / 32) row groups of 32 streams, one after the other, with the
+     * weights loaded once; the workspace grows with the group count. */
     float* persist_ws;
     long long persist_ws_floats;
 } SampleRnnGenDesc;
 
-/* Floats of persist_ws a plan for this descriptor needs; 0 when the configuration does not qualify. */
+/* Floats of persist_ws a plan for this descriptor needs (it grows with the row groups the batch takes); 0 when the
+ * configuration does not qualify. */
 long long samplernn_persist_floats(const SampleRnnGenDesc* desc);
+/* Row groups of 32 streams per launch of the plan's persistent sample kernel: ceil(B / 32); 0 when the plan is not
+ * persistent. */
+int samplernn_generate_persist_groups(void* plan);
+/* The same arithmetic without a device or a plan: the row groups a batch of B streams would take when at most max_groups
+ * are allowed (PARROT_SR_PERSIST_GROUPS; values outside 1 .. 8 are clamped to that range), or 0 when B < 1 or
+ * B > 32 * max_groups -- such a batch runs on launches. */
+int samplernn_persist_groups_dry(int B, int max_groups);
 int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan);
 int samplernn_generate_run(void* plan, void* stream);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */

@@ -258,6 +258,8 @@ SIGNATURES = {
     "samplernn_generate_run": (_i, [_vp, _vp]),
     "samplernn_persist_floats": (C.c_longlong, [C.POINTER(SampleRnnGenDesc)]),
     "samplernn_generate_is_persistent": (_i, [_vp]),
+    "samplernn_generate_persist_groups": (_i, [_vp]),
+    "samplernn_persist_groups_dry": (_i, [_i, _i]),
     "samplernn_generate_status": (_i, [_vp]),
     "samplernn_generate_destroy": (_i, [_vp]),
 }

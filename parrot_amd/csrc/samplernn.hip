@@ -150,6 +150,7 @@ __global__ void sr_tick_kernel(int* tbase, int inc, int set) {
 struct SrPlan {
     SampleRnnGenDesc d;
     bool persist = false;  // sample steps on the persistent-thread kernel (sr_persist.hip)
+    int groups = 0;        // ... in this many row groups of 32 streams per launch (0: not persistent)
     // Fragment-major copies (sk_tile_weights, mode 0) of the single-GRU tiers' matrices, owned by the plan and made once
     // at create time: the step kernel then reads its weights as contiguous 1 KB wave loads instead of 64-byte row pieces.
     struct Tiled { float* U = nullptr; float* Wg = nullptr; float* Wc = nullptr; float* Wout = nullptr; };
@@ -450,7 +451,7 @@ struct SrPlan {
                 // ---- all FS sample steps of this frame in one launch: XCD-local persistent-thread kernel
                 SrpArgs sa{};
                 sa.tbase = d.tbase; sa.toff = toff; sa.samples = d.samples; sa.len = len;
-                sa.B = B; sa.D = D; sa.Q = d.Q; sa.FS = FS; sa.nsteps = FS;
+                sa.B = B; sa.D = D; sa.Q = d.Q; sa.FS = FS; sa.nsteps = FS; sa.ngroups = groups;
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
@@ -554,9 +555,11 @@ int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan) { PH_EN
     SrPlan* p = new (std::nothrow) SrPlan();
     if (!p) return PARROT_ERR_BADARG;
     p->d = *desc;
-    p->persist = desc->persist_ws && srp_eligible(desc->B, desc->D, desc->Q, desc->FS) &&
-                 desc->persist_ws_floats >= srp_ws_floats(desc->D, desc->Q) && srp_prepare(desc->D) == 0 &&
-                 srp_init_ws(desc->persist_ws, desc->D, desc->Q) == 0 && p->make_composed() == 0;
+    const int max_groups = srp_max_groups(), groups = srp_groups_for(desc->B, max_groups);
+    p->persist = desc->persist_ws && srp_eligible(desc->B, desc->D, desc->Q, desc->FS, max_groups) &&
+                 desc->persist_ws_floats >= srp_ws_floats(desc->D, desc->Q, groups) && srp_prepare(desc->D) == 0 &&
+                 srp_init_ws(desc->persist_ws, desc->D, desc->Q, groups) == 0 && p->make_composed() == 0;
+    p->groups = p->persist ? groups : 0;
     p->make_tiled();  // (after the decision: the persistent path tiles the composed projection)
     p->make_winu();
     *plan = p;
@@ -564,13 +567,21 @@ int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan) { PH_EN
 }
 
 long long samplernn_persist_floats(const SampleRnnGenDesc* desc) { PH_ENTRY();
-    if (!desc || !srp_eligible(desc->B, desc->D, desc->Q, desc->FS)) return 0;
-    return srp_ws_floats(desc->D, desc->Q);
+    const int max_groups = srp_max_groups();
+    if (!desc || !srp_eligible(desc->B, desc->D, desc->Q, desc->FS, max_groups)) return 0;
+    return srp_ws_floats(desc->D, desc->Q, srp_groups_for(desc->B, max_groups));
 }
 
 int samplernn_generate_is_persistent(void* plan) { PH_ENTRY();
     return plan && static_cast<SrPlan*>(plan)->persist ? 1 : 0;
 }
+
+int samplernn_generate_persist_groups(void* plan) { PH_ENTRY();
+    return plan ? static_cast<SrPlan*>(plan)->groups : 0;
+}
+
+// (no HIP call, not even PH_ENTRY's: the group arithmetic is testable on a machine without a device)
+int samplernn_persist_groups_dry(int B, int max_groups) { return srp_groups_for(B, max_groups); }
 
 int samplernn_generate_status(void* plan) { PH_ENTRY();
     SrPlan* p = static_cast<SrPlan*>(plan);

@@ -10,14 +10,16 @@ constexpr int SRP_SYNC_WORDS = 1024;  // [256 + 32 team] arrivals per team (coun
                                       // [600 ..) phase stamps of a timed launch (PARROT_SR_TIMING)
 constexpr int SRP_MAXHIST = 64;       // FS + nsteps
 constexpr int SRP_GMAX = 12;          // table rows of the gather requested in one batch (FS - 1 <= SRP_GMAX; else a loop)
-// f32x4 hand-off slots per team in the workspace: x1, x2 [D] and the logits [Q]
+constexpr int SRP_MAXGROUPS = 8;      // row groups of SRP_ROWS * SRP_NTEAMS streams one launch may take (PARROT_SR_PERSIST_GROUPS)
+// f32x4 hand-off slots per (row group, team) in the workspace: x1, x2 [D] and the logits [Q]
 __host__ __device__ constexpr int srp_team_vecs(int D, int Q) { return 2 * D + Q; }
-// Carry between consecutive launches, per team, behind the hand-off slots: [0] the sample index it is for (-1: none),
-// [16 ..) the team's last FS samples [4][SRP_CARRY_HIST], then per CU the table part of the next first gather [32][4][DC <= 32]
+// Carry between consecutive launches, per (row group, team), behind the hand-off slots of all groups: [0] the sample index
+// it is for (-1: none), [16 ..) the team's last FS samples [4][SRP_CARRY_HIST], then per CU the table part of the next first
+// gather [32][4][DC <= 32].  Blocks of both kinds are numbered group * SRP_NTEAMS + team.
 constexpr int SRP_CARRY_HIST = 32;
 constexpr int SRP_CARRY_WORDS = 16 + SRP_ROWS * SRP_CARRY_HIST + SRP_TEAM * SRP_ROWS * 32;
-__host__ __device__ constexpr long long srp_carry_base(int D, int Q) {
-    return SRP_SYNC_WORDS + (long long)SRP_NTEAMS * srp_team_vecs(D, Q) * 4;
+__host__ __device__ constexpr long long srp_carry_base(int D, int Q, int groups) {
+    return SRP_SYNC_WORDS + (long long)groups * SRP_NTEAMS * srp_team_vecs(D, Q) * 4;
 }
 
 __device__ __forceinline__ int srp_xcc() {

@@ -27,11 +27,19 @@ struct SrpArgs {
     float* ws;                         // srp_ws_floats() floats, prepared once by srp_init_ws
     float temperature; int pad;
     unsigned long long seed;
+    int ngroups;                       // row groups of 32 streams this launch takes one after the other: ceil(B / 32), the
+                                       // count ws was sized and initialised for (1: the kernel without the group loop)
 };
 
-bool srp_eligible(int B, int D, int Q, int FS);
-long long srp_ws_floats(int D, int Q);
-int srp_init_ws(float* ws, int D, int Q);  // once per plan: sync words zero, hand-off slots EMPTY
+// PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8
+int srp_max_groups();
+// Row groups a batch of B streams takes, ceil(B / 32), or 0 when that is more than max_groups (clamped to 1 .. 8) or
+// B < 1.  No device needed.
+int srp_groups_for(int B, int max_groups);
+bool srp_eligible(int B, int D, int Q, int FS, int max_groups);
+// sync words + groups * 8 exchange blocks + groups * 8 carries; with one group every offset is the one-group kernel's
+long long srp_ws_floats(int D, int Q, int groups);
+int srp_init_ws(float* ws, int D, int Q, int groups);  // once per plan: sync words zero, hand-off slots EMPTY
 int srp_prepare(int D);  // once per process and width, outside stream capture (raises the kernel's LDS limit)
 int srp_launch(const SrpArgs& a, hipStream_t stream);
 // 0 when no launch on this workspace has timed out / mis-teamed so far

@@ -42,7 +42,14 @@ namespace {
 #define SRP_FINE(slot) nullptr
 #endif
 
-template <int D>
+// MG = true (SrpArgs::ngroups > 1): the launch takes the batch in ngroups row groups of SRP_ROWS * SRP_NTEAMS = 32 streams,
+// one after the other; group grp's team `team` runs streams (grp * SRP_NTEAMS + team) * SRP_ROWS + 0 .. 3.  What a launch
+// pays for once does not depend on the streams and is loaded in front of the group loop -- the census atomic, the table
+// slice in LDS, the W3 / W4 slices in registers, the biases --; what does (carry, history, gather, the sample steps, the
+// tail) is the body of the loop, with exchange slots and a carry of its own per (group, team), so the slot life cycle
+// below holds per group.  MG = false is the one-group kernel, instruction for instruction what it was before the loop
+// existed (srp_launch takes it whenever ngroups == 1); profiles/samplernn_groups_kernel_resources.txt has both sets.
+template <int D, bool MG>
 __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     constexpr int Q = SRP_Q;
     constexpr int DC = D / 32, G = DC / 4, S = SRP_THREADS / G, KP = D / S;
@@ -71,7 +78,8 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     // class over XCDs leaves a team incomplete: its polls time out and raise abort (the caller falls back to launches).
     const int team = srp_xcc();
     const int cu = (int)(blockIdx.x / SRP_NTEAMS);
-    const bool timing = a.pad && blockIdx.x == 0 && tid == 0;
+    const int ngroups = MG ? a.ngroups : 1;
+    bool timing = a.pad && blockIdx.x == 0 && tid == 0;  // (the stamps of a timed launch are group 0's)
     if (timing) stamps[80] = srp_clock();
     if (tid == 0) __hip_atomic_fetch_add(sync + 256 + team * 32, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 
@@ -88,18 +96,23 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     // return in order -- the weight requests need not wait for them)
     typedef const int __attribute__((address_space(4))) * srp_cint;
     const int t0 = *(srp_cint)(unsigned long long)a.tbase + a.toff;
-    int* carry = reinterpret_cast<int*>(a.ws + srp_carry_base(D, Q)) + (size_t)team * SRP_CARRY_WORDS;
+    // Row groups (MG): everything from here to the exchange buffers below that depends on the streams is set for group 0
+    // and moved on at the end of the group loop -- srow = the first stream of this team in the current group, its carry
+    // block, gb --; the four values requested here (carry_t, hc, cs, f0: what a group starts from) are used up at the top
+    // of the loop and asked for again, for the next group, behind the current group's sample steps.
+    int* carry = reinterpret_cast<int*>(a.ws + srp_carry_base(D, Q, ngroups)) + (size_t)team * SRP_CARRY_WORDS;
     float* carry_sum = reinterpret_cast<float*>(carry + 16 + SRP_ROWS * SRP_CARRY_HIST) + (size_t)cu * SRP_ROWS * DC;
-    const int carry_t = *(srp_cint)(unsigned long long)carry;
+    int carry_t = *(srp_cint)(unsigned long long)carry;
     // (threads past SRP_ROWS * FS repeat the last slot: same address, same value, same LDS word -- no divergent block the
     // compiler could sink the request into)
     const int hu = min(tid, SRP_ROWS * a.FS - 1), hr = hu / a.FS, hpos = hu % a.FS;
-    const int hc = carry[16 + hr * SRP_CARRY_HIST + min(hpos, SRP_CARRY_HIST - 1)];
+    int hc = carry[16 + hr * SRP_CARRY_HIST + min(hpos, SRP_CARRY_HIST - 1)];
     constexpr int GU = SRP_ROWS * DC, GW0 = (SRP_THREADS - GU) / 64;  // first gathering wave (GU <= 128: waves 6-7 at D = 1024)
     const int gu = min(max(tid - GW0 * 64, 0), GU - 1), gr = gu / DC, gc = gu % DC;
-    const int gb = min(team * SRP_ROWS + gr, a.B - 1);
-    const float cs = carry_sum[gu];
-    const float f0 = a.frame_out[(size_t)gb * a.ldf + cu * DC + gc];
+    int srow = team * SRP_ROWS;
+    int gb = min(srow + gr, a.B - 1);
+    float cs = carry_sum[gu];
+    float f0 = a.frame_out[(size_t)gb * a.ldf + cu * DC + gc];
     const int g = (tid >> 3) % G, s = 8 * (tid / (8 * G)) + (tid & 7);
     const int gq = (tid >> 3) % GQ, sq = 8 * (tid / (8 * GQ)) + (tid & 7);
     constexpr int T2V = Q * (DC / 4) / SRP_THREADS;  // f32x4 of the table slice per thread
@@ -124,9 +137,10 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     for (int kk = 0; kk < KQ; ++kk)
         w4[kk] = *reinterpret_cast<const f32x4*>(a.W4 + (size_t)(kk * SQ + sq) * Q + cu * QC + 4 * gq);
     __builtin_amdgcn_sched_barrier(0);
-    // team exchange buffers ([D] f32x4 each, 4 streams per vector): x1, x2, and the logits ([Q] f32x4)
+    // team exchange buffers ([D] f32x4 each, 4 streams per vector): x1, x2, and the logits ([Q] f32x4); one set per
+    // (row group, team), numbered like the carry blocks
     float* xbase = a.ws + SRP_SYNC_WORDS + (size_t)team * srp_team_vecs(D, Q) * 4;
-    const __amdgpu_buffer_rsrc_t xr = srp_rsrc(xbase);
+    __amdgpu_buffer_rsrc_t xr = srp_rsrc(xbase);
     f32x4* x1 = reinterpret_cast<f32x4*>(xbase);
     f32x4* x2 = x1 + D;
     f32x4* lb = x2 + D;
@@ -134,6 +148,7 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     // Slot life cycle.  All slots are EMPTY when a plan is created (srp_init_ws) and every launch leaves them EMPTY again,
     // except the logits of its last step: their owners empty them once they hold the complete x1 of the NEXT launch's
     // first step (every CU that published into it has left the previous launch), like the logits of any other step.
+    // (With row groups: per group -- a group's last logits are emptied by the same group of the next launch.)
     // A buffer is emptied by its owner as soon as the owner has taken the NEXT buffer of the chain from all 32 CUs (which
     // proves that all of them are done with this one), always by threads that later publish, behind an
     // s_waitcnt vmcnt(0), something the readers take before they look at the emptied buffer again.  No counted barrier.
@@ -187,195 +202,229 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     if (tid == 0) sh->ok = 1;
 #pragma unroll
     for (int j = 0; j < T2V; ++j) reinterpret_cast<f32x4*>(t2l)[tid + j * SRP_THREADS] = tv[j];
-    if (carry_t == t0) {
-        sh->hist[hr][hpos] = hc;
-        if (glane) tmp[gc * SRP_ROWS + gr] = f0 + cs;
-    } else {
-        const int hv = a.samples[(size_t)min(team * SRP_ROWS + hr, a.B - 1) * a.len + t0 - a.FS + hpos];
-        sh->hist[hr][hpos] = hv;
-        __syncthreads();
-        if (gwave) {
-            gather_request(0);
-            gather_sum(0);
-        }
-    }
-    __syncthreads();
-    take_part();
-    if (timing) stamps[81] = srp_clock();
-
-    auto stamp = [&](int i, int q) { if (timing && i < 10) stamps[i * 8 + q] = srp_clock(); };
-    for (int i = 0; i < a.nsteps; ++i) {
-        const bool more = i + 1 < a.nsteps;
-        stamp(i, 0);
-        // ---- x1 = relu(part_i + the newest sample's row): no product, the owner publishes its columns right away
-        if (tid < DC) {
-            const int c = fin_h - cu * DC;
-            f32x4 v = part;
-#pragma unroll
-            for (int r = 0; r < SRP_ROWS; ++r) v[r] += t2l[sh->hist[r][i + a.FS - 1] * DC + c];
-            // (behind the stores that emptied x2: none in front of step 0, whose wait would be for the weight slices)
-            if (i > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            x1[fin_h] = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-        }
-        stamp(i, 1);
-        {
-            for (int k = tid; k < D; k += SRP_THREADS) act[k] = srp_take(xr, (unsigned)(k * 16), abort_, sh);
+    int grp = 0;
+    do {
+        // ---- one row group: streams srow .. srow + 3 of this team (the last group is usually partial: a stream b >= a.B loads
+        // stream a.B - 1's operands and stores nothing; a team without a live stream still runs every hand-off)
+        if (carry_t == t0) {
+            sh->hist[hr][hpos] = hc;
+            if (glane) tmp[gc * SRP_ROWS + gr] = f0 + cs;
+        } else {
+            const int hv = a.samples[(size_t)min(srow + hr, a.B - 1) * a.len + t0 - a.FS + hpos];
+            sh->hist[hr][hpos] = hv;
             __syncthreads();
-            if (!sh->ok) return;
-            stamp(i, 2);
-            // x1(i) complete => every CU is done with the logits of step i-1 (i = 0: of the previous launch's last step)
-            if (tid < QC) lb[fin_q] = srp_empty();
-            if (more && gwave) gather_request(i + 1);
-            f32x4 v;
-            srp_layer<KP, G>(act, w3, red, v, tid, SRP_FINE(84));
+            if (gwave) {
+                gather_request(0);
+                gather_sum(0);
+            }
+        }
+        __syncthreads();
+        take_part();
+        if (timing) stamps[81] = srp_clock();
+
+        auto stamp = [&](int i, int q) { if (timing && i < 10) stamps[i * 8 + q] = srp_clock(); };
+        for (int i = 0; i < a.nsteps; ++i) {
+            const bool more = i + 1 < a.nsteps;
+            stamp(i, 0);
+            // ---- x1 = relu(part_i + the newest sample's row): no product, the owner publishes its columns right away
             if (tid < DC) {
-                v += bias3;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                x2[fin_h] = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                const int c = fin_h - cu * DC;
+                f32x4 v = part;
+#pragma unroll
+                for (int r = 0; r < SRP_ROWS; ++r) v[r] += t2l[sh->hist[r][i + a.FS - 1] * DC + c];
+                // (behind the stores that emptied x2: none in front of step 0, whose wait would be for the weight slices)
+                if (i > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                x1[fin_h] = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
             }
-            stamp(i, 3);
-            if (more && gwave) gather_sum(i + 1);
-            stamp(i, 4);
-        }
-        {
-            for (int k = tid; k < D; k += SRP_THREADS) act[k] = srp_take(xr, (unsigned)((D + k) * 16), abort_, sh);
+            stamp(i, 1);
+            {
+                for (int k = tid; k < D; k += SRP_THREADS) act[k] = srp_take(xr, (unsigned)(k * 16), abort_, sh);
+                __syncthreads();
+                if (!sh->ok) return;
+                stamp(i, 2);
+                // x1(i) complete => every CU is done with the logits of step i-1 (i = 0: of the previous launch's last step)
+                if (tid < QC) lb[fin_q] = srp_empty();
+                if (more && gwave) gather_request(i + 1);
+                f32x4 v;
+                srp_layer<KP, G>(act, w3, red, v, tid, SRP_FINE(84));
+                if (tid < DC) {
+                    v += bias3;
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    x2[fin_h] = (f32x4){fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+                }
+                stamp(i, 3);
+                if (more && gwave) gather_sum(i + 1);
+                stamp(i, 4);
+            }
+            {
+                for (int k = tid; k < D; k += SRP_THREADS) act[k] = srp_take(xr, (unsigned)((D + k) * 16), abort_, sh);
+                __syncthreads();
+                if (!sh->ok) return;
+                if (more) take_part();
+                stamp(i, 5);
+                if (tid < QC) {  // x2(i) complete => every CU is done with x1(i); emptied by the threads that publish lb
+#pragma unroll
+                    for (int q = 0; q < DC / QC; ++q) x1[cu * DC + tid * (DC / QC) + q] = srp_empty();
+                }
+                f32x4 v;
+                srp_layer<KQ, GQ>(act, w4, red, v, tid, SRP_FINE(88));
+                if (tid < QC) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    lb[fin_q] = v + bias4;
+                }
+#ifdef SRP_FINE_TIMERS
+                if (timing && i == 5) stamps[92] = srp_clock();
+#endif
+            }
+
+            // ---- pick (every CU of the team, identical result): argmax with lowest-index ties, or the seeded draw
+            if (tid < Q) lg[tid] = srp_take(xr, (unsigned)((2 * D + tid) * 16), abort_, sh);
             __syncthreads();
             if (!sh->ok) return;
-            if (more) take_part();
-            stamp(i, 5);
-            if (tid < QC) {  // x2(i) complete => every CU is done with x1(i); emptied by the threads that publish lb
+            stamp(i, 6);
+            if (tid < DC) x2[fin_h] = srp_empty();  // logits(i) complete => every CU is done with x2(i)
+            const int t = t0 + i;
+            if (wave < SRP_ROWS) {
+                const int r = wave;
+                float best;
+                const int bi = srp_argmax_row<Q>(lg, r, lane, best);
+                int pick = bi;
+                if (a.temperature > 0.f) {
 #pragma unroll
-                for (int q = 0; q < DC / QC; ++q) x1[cu * DC + tid * (DC / QC) + q] = srp_empty();
-            }
-            f32x4 v;
-            srp_layer<KQ, GQ>(act, w4, red, v, tid, SRP_FINE(88));
-            if (tid < QC) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                lb[fin_q] = v + bias4;
-            }
-#ifdef SRP_FINE_TIMERS
-            if (timing && i == 5) stamps[92] = srp_clock();
-#endif
-        }
-
-        // ---- pick (every CU of the team, identical result): argmax with lowest-index ties, or the seeded draw
-        if (tid < Q) lg[tid] = srp_take(xr, (unsigned)((2 * D + tid) * 16), abort_, sh);
-        __syncthreads();
-        if (!sh->ok) return;
-        stamp(i, 6);
-        if (tid < DC) x2[fin_h] = srp_empty();  // logits(i) complete => every CU is done with x2(i)
-        const int t = t0 + i;
-        if (wave < SRP_ROWS) {
-            const int r = wave;
-            float best;
-            const int bi = srp_argmax_row<Q>(lg, r, lane, best);
-            int pick = bi;
-            if (a.temperature > 0.f) {
-#pragma unroll
-                for (int m = 0; m < Q / 64; ++m) ev[r * Q + lane + 64 * m] = expf((lg[lane + 64 * m][r] - best) / a.temperature);
-                __builtin_amdgcn_wave_barrier();
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (lane == 0) {
-                    const int b = team * SRP_ROWS + r;
-                    float tot = 0.f;
-                    for (int q = 0; q < Q; ++q) tot += ev[r * Q + q];
-                    unsigned long long x = a.seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(t + 1)) ^
-                                           (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
-                    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-                    const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
-                    float c = 0.f;
-                    pick = Q - 1;
-                    for (int q = 0; q < Q; ++q) {
-                        c += ev[r * Q + q];
-                        if (u < c) { pick = q; break; }
+                    for (int m = 0; m < Q / 64; ++m) ev[r * Q + lane + 64 * m] = expf((lg[lane + 64 * m][r] - best) / a.temperature);
+                    __builtin_amdgcn_wave_barrier();
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (lane == 0) {
+                        const int b = srow + r;
+                        float tot = 0.f;
+                        for (int q = 0; q < Q; ++q) tot += ev[r * Q + q];
+                        unsigned long long x = a.seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(t + 1)) ^
+                                               (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
+                        x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+                        const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
+                        float c = 0.f;
+                        pick = Q - 1;
+                        for (int q = 0; q < Q; ++q) {
+                            c += ev[r * Q + q];
+                            if (u < c) { pick = q; break; }
+                        }
                     }
                 }
-            }
-            if (lane == 0) {
-                sh->hist[r][a.FS + i] = pick;
-                const int b = team * SRP_ROWS + r;
-                if (cu == 0 && b < a.B) a.samples[(size_t)b * a.len + t] = pick;
-            }
-        }
-        if (a.logits && i == a.nsteps - 1 && cu == 0 && tid < Q) {
-#pragma unroll
-            for (int r = 0; r < SRP_ROWS; ++r) {
-                const int b = team * SRP_ROWS + r;
-                if (b < a.B) a.logits[(size_t)b * Q + tid] = lg[tid][r];
-            }
-        }
-        __syncthreads();
-        stamp(i, 7);
-    }
-    // ---- the carry for the next launch (see the prologue): this team's last FS samples and, per CU, the table part of
-    // the next launch's first gather -- requested here, stored at the very end
-    const bool leave = gfast && a.FS <= SRP_CARRY_HIST;
-    if (leave && gwave) gather_rows(a.nsteps);
-    if (leave && cu == 0) {
-        carry[16 + hr * SRP_CARRY_HIST + min(hpos, SRP_CARRY_HIST - 1)] = sh->hist[hr][a.nsteps + hpos];
-        if (tid == 0) carry[0] = t0 + a.nsteps;
-    }
-    if (!leave && cu == 0 && tid == 0) carry[0] = -1;
-    // ---- the next frame's frame-tier input for this team's streams (saves the launch that would compute it).  All
-    // operands of an item are requested in one batch (unconditional loads, dummy addresses where an operand is absent).
-    if (timing) stamps[82] = srp_clock();
-    if (a.next_in) {
-        constexpr int TW = SRP_GMAX + 1;
-        const float half_q = (float)(Q / 2);
-        const int NN = a.next_n > 0 ? a.next_n : D, NC = NN / 32;  // this CU's share: NC of the NN columns
-        const bool gates = a.next_gpre != nullptr, wfast = a.FS <= TW;
-        const float* bias_p = a.next_bias ? a.next_bias : a.next_Win;
-        const float* gpre_p = gates ? a.next_gpre : a.next_Win;
-        const float* h_p = gates ? a.next_h : a.next_Win;
-        for (int idx0 = 0; idx0 < SRP_ROWS * NC; idx0 += SRP_THREADS) {
-            const int idx = min(idx0 + tid, SRP_ROWS * NC - 1);
-            const int r = idx / NC, col = cu * NC + idx % NC;
-            const int b = team * SRP_ROWS + r, bb = min(b, a.B - 1);
-            const bool live = idx0 + tid < SRP_ROWS * NC && b < a.B;
-            const bool gcol = gates && col < 2 * D;
-            const int hc = col < D ? col : min(col - D, D - 1);
-            float wv[TW];
-#pragma unroll
-            for (int p = 0; p < TW; ++p) wv[p] = a.next_Win[(size_t)min(p, a.FS - 1) * NN + col];
-            const float bv = bias_p[col];
-            const float av = a.next_add[(size_t)bb * a.next_ld_add + col];
-            const float gp = gpre_p[gcol ? (size_t)bb * 2 * D + col : 0];
-            const float hv2 = h_p[gcol ? (size_t)bb * D + hc : 0];
-            float acc = 0.f;
-            if (wfast) {
-                int hq[TW];
-#pragma unroll
-                for (int p = 0; p < TW; ++p) hq[p] = sh->hist[r][a.nsteps + min(p, a.FS - 1)];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int p = 0; p < TW; ++p) {
-                    const float xf = ((float)hq[p] / half_q - 1.0f) * 2.0f;
-                    acc = p < a.FS ? fmaf(xf, wv[p], acc) : acc;
-                }
-            } else {
-                for (int p = 0; p < a.FS; ++p) {
-                    const float xf = ((float)sh->hist[r][a.nsteps + p] / half_q - 1.0f) * 2.0f;
-                    acc = fmaf(xf, a.next_Win[(size_t)p * NN + col], acc);
+                if (lane == 0) {
+                    sh->hist[r][a.FS + i] = pick;
+                    const int b = srow + r;
+                    if (cu == 0 && b < a.B) a.samples[(size_t)b * a.len + t] = pick;
                 }
             }
-            acc += (a.next_bias ? bv : 0.f) + av;
-            if (!live) continue;
-            if (gcol) {
-                // the recurrent product h . Wg of the NEXT frame's gates is already there (it does not depend on the new
-                // samples: the projection launch made it): finish the gates here -- one launch fewer per frame
-                const float gt = ph_sigmoid(gp + acc);
-                if (col < D) a.next_z[(size_t)b * D + col] = gt;          // update gate
-                else a.next_rh[(size_t)b * D + col - D] = gt * hv2;       // reset gate * h
-            } else {
-                a.next_in[(size_t)b * NN + col] = acc;
+            if (a.logits && i == a.nsteps - 1 && cu == 0 && tid < Q) {
+#pragma unroll
+                for (int r = 0; r < SRP_ROWS; ++r) {
+                    const int b = srow + r;
+                    if (b < a.B) a.logits[(size_t)b * Q + tid] = lg[tid][r];
+                }
+            }
+            __syncthreads();
+            stamp(i, 7);
+        }
+        // ---- the carry for the next launch (see the prologue): this team's last FS samples and, per CU, the table part of
+        // the next launch's first gather -- requested here, stored at the very end
+        const bool leave = gfast && a.FS <= SRP_CARRY_HIST;
+        // (row groups: what the NEXT group starts from, requested here -- one round trip in the shadow of this group's tail;
+        // unconditional: the last group asks for its own values again and nobody uses them)
+        const int ngt = MG ? min(grp + 1, ngroups - 1) * SRP_NTEAMS + team : team;
+        int* ncarry = reinterpret_cast<int*>(a.ws + srp_carry_base(D, Q, ngroups)) + (size_t)ngt * SRP_CARRY_WORDS;
+        float* ncarry_sum = reinterpret_cast<float*>(ncarry + 16 + SRP_ROWS * SRP_CARRY_HIST) + (size_t)cu * SRP_ROWS * DC;
+        const int ngb = min(ngt * SRP_ROWS + gr, a.B - 1);
+        if (MG) {
+            carry_t = *(srp_cint)(unsigned long long)ncarry;
+            hc = ncarry[16 + hr * SRP_CARRY_HIST + min(hpos, SRP_CARRY_HIST - 1)];
+            cs = ncarry_sum[gu];
+            f0 = a.frame_out[(size_t)ngb * a.ldf + cu * DC + gc];
+        }
+        if (leave && gwave) gather_rows(a.nsteps);
+        if (leave && cu == 0) {
+            carry[16 + hr * SRP_CARRY_HIST + min(hpos, SRP_CARRY_HIST - 1)] = sh->hist[hr][a.nsteps + hpos];
+            if (tid == 0) carry[0] = t0 + a.nsteps;
+        }
+        if (!leave && cu == 0 && tid == 0) carry[0] = -1;
+        // ---- the next frame's frame-tier input for this team's streams (saves the launch that would compute it).  All
+        // operands of an item are requested in one batch (unconditional loads, dummy addresses where an operand is absent).
+        if (timing) stamps[82] = srp_clock();
+        if (a.next_in) {
+            constexpr int TW = SRP_GMAX + 1;
+            const float half_q = (float)(Q / 2);
+            const int NN = a.next_n > 0 ? a.next_n : D, NC = NN / 32;  // this CU's share: NC of the NN columns
+            const bool gates = a.next_gpre != nullptr, wfast = a.FS <= TW;
+            const float* bias_p = a.next_bias ? a.next_bias : a.next_Win;
+            const float* gpre_p = gates ? a.next_gpre : a.next_Win;
+            const float* h_p = gates ? a.next_h : a.next_Win;
+            for (int idx0 = 0; idx0 < SRP_ROWS * NC; idx0 += SRP_THREADS) {
+                const int idx = min(idx0 + tid, SRP_ROWS * NC - 1);
+                const int r = idx / NC, col = cu * NC + idx % NC;
+                const int b = srow + r, bb = min(b, a.B - 1);
+                const bool live = idx0 + tid < SRP_ROWS * NC && b < a.B;
+                const bool gcol = gates && col < 2 * D;
+                const int hc = col < D ? col : min(col - D, D - 1);
+                float wv[TW];
+#pragma unroll
+                for (int p = 0; p < TW; ++p) wv[p] = a.next_Win[(size_t)min(p, a.FS - 1) * NN + col];
+                const float bv = bias_p[col];
+                const float av = a.next_add[(size_t)bb * a.next_ld_add + col];
+                const float gp = gpre_p[gcol ? (size_t)bb * 2 * D + col : 0];
+                const float hv2 = h_p[gcol ? (size_t)bb * D + hc : 0];
+                float acc = 0.f;
+                if (wfast) {
+                    int hq[TW];
+#pragma unroll
+                    for (int p = 0; p < TW; ++p) hq[p] = sh->hist[r][a.nsteps + min(p, a.FS - 1)];
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int p = 0; p < TW; ++p) {
+                        const float xf = ((float)hq[p] / half_q - 1.0f) * 2.0f;
+                        acc = p < a.FS ? fmaf(xf, wv[p], acc) : acc;
+                    }
+                } else {
+                    for (int p = 0; p < a.FS; ++p) {
+                        const float xf = ((float)sh->hist[r][a.nsteps + p] / half_q - 1.0f) * 2.0f;
+                        acc = fmaf(xf, a.next_Win[(size_t)p * NN + col], acc);
+                    }
+                }
+                acc += (a.next_bias ? bv : 0.f) + av;
+                if (!live) continue;
+                if (gcol) {
+                    // the recurrent product h . Wg of the NEXT frame's gates is already there (it does not depend on the new
+                    // samples: the projection launch made it): finish the gates here -- one launch fewer per frame
+                    const float gt = ph_sigmoid(gp + acc);
+                    if (col < D) a.next_z[(size_t)b * D + col] = gt;          // update gate
+                    else a.next_rh[(size_t)b * D + col - D] = gt * hv2;       // reset gate * h
+                } else {
+                    a.next_in[(size_t)b * NN + col] = acc;
+                }
             }
         }
-    }
-    if (leave && gwave) {
-        const float acc = rows_sum(a.nsteps, 0.f);
-        if (glane) carry_sum[gu] = acc;
-    }
-    if (timing) stamps[83] = srp_clock();
+        if (leave && gwave) {
+            const float acc = rows_sum(a.nsteps, 0.f);
+            if (glane) carry_sum[gu] = acc;
+        }
+        if (timing) stamps[83] = srp_clock();
+        // The LDS arrays are the next group's as well.  The step loop's last barrier lies in front of the tail, so without this
+        // one a wave with no share in the tail (or done with it) would run ahead and overwrite sh->hist / tmp under the tail's
+        // reads of sh->hist (next_in items, the slow rows_sum) -- the hazard DESIGN 3.6 describes for the decode machine.
+        // This barrier closes it: nobody writes the next group's history before every wave is past the tail and the carry sum.
+        if (MG) {
+            __syncthreads();
+            timing = false;
+            srow = ngt * SRP_ROWS;
+            carry = ncarry;
+            carry_sum = ncarry_sum;
+            gb = ngb;
+            xbase = a.ws + SRP_SYNC_WORDS + (size_t)ngt * srp_team_vecs(D, Q) * 4;
+            xr = srp_rsrc(xbase);
+            x1 = reinterpret_cast<f32x4*>(xbase);
+            x2 = x1 + D;
+            lb = x2 + D;
+        }
+    } while (MG && ++grp < ngroups);  // row groups (MG = false: no loop at all -- the one-group kernel as it was)
 }
 
 size_t srp_lds_bytes(int D) {
@@ -384,7 +433,18 @@ size_t srp_lds_bytes(int D) {
 
 }  // namespace
 
-bool srp_eligible(int B, int D, int Q, int FS) {
+int srp_max_groups() {
+    const int g = env_int("PARROT_SR_PERSIST_GROUPS", 1);
+    return g < 1 ? 1 : g > SRP_MAXGROUPS ? SRP_MAXGROUPS : g;
+}
+
+int srp_groups_for(int B, int max_groups) {
+    const int mg = max_groups < 1 ? 1 : max_groups > SRP_MAXGROUPS ? SRP_MAXGROUPS : max_groups;
+    constexpr int per = SRP_ROWS * SRP_NTEAMS;
+    return B >= 1 && B <= per * mg ? (B + per - 1) / per : 0;
+}
+
+bool srp_eligible(int B, int D, int Q, int FS, int max_groups) {
     static int cus = -1;
     const int enabled = env_int("PARROT_SR_PERSIST", 1);
     if (cus < 0) {
@@ -393,19 +453,22 @@ bool srp_eligible(int B, int D, int Q, int FS) {
         cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) ? prop.multiProcessorCount : 0;
     }
     if (!enabled || cus != SRP_TEAM * SRP_NTEAMS) return false;
-    if (B < 1 || B > SRP_ROWS * SRP_NTEAMS || Q != SRP_Q || FS < 1 || 2 * FS > SRP_MAXHIST) return false;
+    if (srp_groups_for(B, max_groups) == 0 || Q != SRP_Q || FS < 1 || 2 * FS > SRP_MAXHIST) return false;
     return D == 256 || D == 512 || D == 1024;
 }
 
-long long srp_ws_floats(int D, int Q) { return srp_carry_base(D, Q) + (long long)SRP_NTEAMS * SRP_CARRY_WORDS; }
+long long srp_ws_floats(int D, int Q, int groups) {
+    return srp_carry_base(D, Q, groups) + (long long)groups * SRP_NTEAMS * SRP_CARRY_WORDS;
+}
 
-int srp_init_ws(float* ws, int D, int Q) {
+int srp_init_ws(float* ws, int D, int Q, int groups) {
     // barrier / census / abort words zero, every hand-off slot EMPTY
     PH_CHECK(hipMemset(ws, 0, SRP_SYNC_WORDS * sizeof(float)));
     PH_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(ws + SRP_SYNC_WORDS), (int)SRP_EMPTY,
-                          (size_t)SRP_NTEAMS * srp_team_vecs(D, Q) * 4));
+                          (size_t)groups * SRP_NTEAMS * srp_team_vecs(D, Q) * 4));
     // no carry yet: the sample index it is for can never match
-    PH_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(ws + srp_carry_base(D, Q)), -1, (size_t)SRP_NTEAMS * SRP_CARRY_WORDS));
+    PH_CHECK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(ws + srp_carry_base(D, Q, groups)), -1,
+                          (size_t)groups * SRP_NTEAMS * SRP_CARRY_WORDS));
     return (int)hipDeviceSynchronize();
 }
 
@@ -415,25 +478,43 @@ int srp_status(const float* ws) {
     return w[0] ? (int)(w[1] ? w[1] : 1) : 0;
 }
 
+namespace {
+
+template <int D>
+int srp_prepare_width(int lds) {
+    PH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(srp_kernel<D, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    PH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(srp_kernel<D, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    return 0;
+}
+
+// one group: the kernel without the group loop, whatever the switch says
+template <int D>
+void srp_launch_width(const SrpArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
+    if (a.ngroups > 1) hipLaunchKernelGGL((srp_kernel<D, true>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((srp_kernel<D, false>), grid, block, lds, stream, a);
+}
+
+}  // namespace
+
 int srp_prepare(int D) {
     const int lds = (int)srp_lds_bytes(D);
     switch (D) {
-        case 256: PH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(srp_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); break;
-        case 512: PH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(srp_kernel<512>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); break;
-        case 1024: PH_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(srp_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); break;
+        case 256: return srp_prepare_width<256>(lds);
+        case 512: return srp_prepare_width<512>(lds);
+        case 1024: return srp_prepare_width<1024>(lds);
         default: return PH_ERR_UNSUPPORTED;
     }
-    return 0;
 }
 
 int srp_launch(const SrpArgs& a, hipStream_t stream) {
     if (!a.ws || a.nsteps < 1 || a.FS + a.nsteps > SRP_MAXHIST) return PH_ERR_BADARG;
+    if (a.ngroups < 1 || a.ngroups > SRP_MAXGROUPS || a.B < 1 || a.B > SRP_ROWS * SRP_NTEAMS * a.ngroups) return PH_ERR_BADARG;
     const size_t lds = srp_lds_bytes(a.D);
     const dim3 grid(SRP_TEAM * SRP_NTEAMS), block(SRP_THREADS);
     switch (a.D) {
-        case 256: hipLaunchKernelGGL(srp_kernel<256>, grid, block, lds, stream, a); break;
-        case 512: hipLaunchKernelGGL(srp_kernel<512>, grid, block, lds, stream, a); break;
-        case 1024: hipLaunchKernelGGL(srp_kernel<1024>, grid, block, lds, stream, a); break;
+        case 256: srp_launch_width<256>(a, grid, block, lds, stream); break;
+        case 512: srp_launch_width<512>(a, grid, block, lds, stream); break;
+        case 1024: srp_launch_width<1024>(a, grid, block, lds, stream); break;
         default: return PH_ERR_UNSUPPORTED;
     }
     return (int)hipGetLastError();

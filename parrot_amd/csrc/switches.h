@@ -45,6 +45,10 @@
 // PARROT_PM_DUMP_PLAN      unset    plan,    set: print the sampling machine's pieces and the barrier words  development
 //                                   failure  of a persistent launch that gave up
 // PARROT_SR_PERSIST        1        plan     0: SampleRNN sampling without its persistent kernel             tests
+// PARROT_SR_PERSIST_GROUPS 1        plan     largest number of 32-stream row groups one launch of SampleRNN's  tests, tools
+//                                            persistent kernel may take (1 .. 8, clamped): batches up to 32 x
+//                                            this many streams leave the launch path.  Python sizes the
+//                                            workspace through the library (samplernn_persist_floats)
 // PARROT_SR_TIMING         0        load     SampleRNN persistent kernel's in-kernel timers                  tools
 // PARROT_TRACE_ONLY        unset    plan     set: plans build on a machine without a GPU (schedule tracing)  tests, tools
 //

@@ -285,6 +285,8 @@ class DeviceGenerator:
         self.plan = C.c_void_p()
         _lib.call('samplernn_generate_create', C.byref(d), C.byref(self.plan))
         self.persistent = bool(_lib.load().samplernn_generate_is_persistent(self.plan))
+        # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
+        self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
 
     def generate(self, features):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32."""

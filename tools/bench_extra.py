@@ -8,7 +8,12 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
   bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_stop, decode_lstm2_1024, decode_lstm3_1536,
                                          decode_gmm_gru2_1024, decode_gmm_lstm2_1024, decode_bf16_gru2_1024,
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
-                                         samplernn_cfg5, mulaw)
+                                         samplernn_cfg5, samplernn_groups, mulaw)
+  bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
+                                         SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
+                                         kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
+                                         alternations in one process; us per sample step, x real time per stream; the
+                                         result also goes to FILE (default profiles/samplernn_groups.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -32,8 +37,9 @@ def _arg(name, dflt=None):
 
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
-       "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "mulaw")
-only = tuple(_arg("--only", ",".join(ALL)).split(","))
+       "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
+       "mulaw")
+only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
     "decode_lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024),
@@ -388,6 +394,71 @@ if "samplernn_cfg5" in only:
                              "samples_per_s": round(B * nsamp / dt, 1),
                              "x_realtime_per_stream": round(nsamp / dt / 16000.0, 3)}
     gen.close()
+
+# ---- SampleRNN D=1024 above 32 streams: the persistent sample kernel in row groups (PARROT_SR_PERSIST_GROUPS) against the
+# launch path, plans of both kinds alive in one process and run alternately; B = 32 is the anchor (one group: the same
+# kernel instantiation with the switch set and unset)
+if "samplernn_groups" in only:
+    from parrot_amd.sampleRNN import lib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    lib.delete_all_params(); lib.set_device(dev)
+    tt.configure(DIM=1024, EMB_SIZE=256)
+    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+    with torch.no_grad():  # registers all parameters with the reference initialisation
+        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
+                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    T, reps = 26, int(_arg("--reps", "5"))
+    nsamp = (T - 1) * 80
+    saved = {k: os.environ.get(k) for k in ("PARROT_SR_PERSIST", "PARROT_SR_PERSIST_GROUPS")}
+
+    def plan(B, persist, groups):
+        os.environ["PARROT_SR_PERSIST"] = str(persist)
+        if groups is None:
+            os.environ.pop("PARROT_SR_PERSIST_GROUPS", None)
+        else:
+            os.environ["PARROT_SR_PERSIST_GROUPS"] = str(groups)
+        return tt.DeviceGenerator(B, T, temperature=0.0)
+
+    def run(gen, feats):
+        torch.cuda.synchronize(); t0 = time.time()
+        s = gen.generate(feats)
+        torch.cuda.synchronize()
+        return time.time() - t0, s.cpu().numpy().copy()
+
+    res = {"dim": 1024, "samples_per_stream": nsamp, "alternations": reps, "batches": {}}
+    for B in (32, 64, 128, 200):
+        feats = torch.randn(T, B, 63, generator=g).numpy()
+        gens = {"groups": plan(B, 1, 8), "launches": plan(B, 0, None)}
+        if B == 32:
+            gens["switch_unset"] = plan(B, 1, None)
+        assert gens["groups"].persist_groups == -(-B // 32) and not gens["launches"].persistent
+        times, samples = {k: [] for k in gens}, {}
+        keys = list(gens)
+        for rep in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+            for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:  # (no plan always runs behind the same other one)
+                dt, samples[k] = run(gens[k], feats)
+                if rep:
+                    times[k].append(dt)
+        entry = {"row_groups": gens["groups"].persist_groups,
+                 "rows_equal_to_launches": int((samples["groups"] == samples["launches"]).all(axis=1).sum())}
+        for k, v in times.items():
+            us = sorted(1e6 * dt / nsamp for dt in v)
+            entry[k] = {"us_per_sample_step": round(us[len(us) // 2], 2), "spread_us": round(us[-1] - us[0], 2),
+                        "x_realtime_per_stream": round(nsamp / sorted(v)[len(v) // 2] / 16000.0, 3)}
+        entry["groups_faster"] = max(times["groups"]) < min(times["launches"])
+        if B == 32:
+            entry["bit_identical_to_switch_unset"] = bool((samples["groups"] == samples["switch_unset"]).all())
+        res["batches"][str(B)] = entry
+        for gen in gens.values():
+            gen.close()
+    for k, v in saved.items():
+        os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    out["samplernn_groups"] = res
+    path = _arg("--groups-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                              "samplernn_groups.json"))
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
