@@ -854,6 +854,19 @@ typedef struct SampleRnnGenDesc {
      * weights loaded once; the workspace grows with the group count. */
     float* persist_ws;
     long long persist_ws_floats;
+    /* Optional: several utterances one after the other in each stream (three_tier.generate_packed).  starts [T][B],
+     * device memory, read inside the loop: starts[f][b] != 0 means that stream b begins a new utterance at big frame f and
+     * that slot f - 1 is that utterance's Q/2 prefix.  The first launch of such a period then rewrites, for the flagged
+     * streams only, samples[b][BFS (f-1) .. BFS f) = Q/2, every state of row b that outlives a period (big_h / frm_h, or
+     * big_hs / frm_hs and big_cs / frm_cs of every layer) from the learned initial states below, the row's share of the
+     * next frame's gate product and, on the persistent path, the launch-to-launch carry of the row's team (invalidated:
+     * that period's first sample launch reads its history from `samples`).  From there on the stream computes what a run
+     * of its own computes.  starts[0] is never read.  NULL: nothing of this is launched.
+     * big_h0 / frm_h0: [max(n_rnn, 1)][H0_MULT * D] learned initial states (BigFrameLevel.h0 / FrameLevel.h0), H0_MULT = 2
+     * for LSTM tiers whose rows are [s | c], else 1.  Both are required when starts is set (PARROT_ERR_BADARG otherwise);
+     * the caller still fills big_h / frm_h (...) with them for the first utterance of every stream. */
+    const int* starts;
+    const float* big_h0; const float* frm_h0;
 } SampleRnnGenDesc;
 
 /* Floats of persist_ws a plan for this descriptor needs (it grows with the row groups the batch takes); 0 when the

@@ -167,7 +167,8 @@ class SampleRnnGenDesc(C.Structure):
                  ("big_hs", C.c_void_p * 5), ("big_cs", C.c_void_p * 5),
                  ("frm_hs", C.c_void_p * 5), ("frm_cs", C.c_void_p * 5),
                  ("gate_ws", C.c_void_p), ("layer_tmp", C.c_void_p),
-                 ("persist_ws", C.c_void_p), ("persist_ws_floats", C.c_longlong)])
+                 ("persist_ws", C.c_void_p), ("persist_ws_floats", C.c_longlong),
+                 ("starts", C.c_void_p), ("big_h0", C.c_void_p), ("frm_h0", C.c_void_p)])
 
 
 # name -> (restype, argtypes); every symbol include/parrot_hip.h declares must be listed here

@@ -141,6 +141,33 @@ __global__ void sr_tick_kernel(int* tbase, int inc, int set) {
     if (threadIdx.x == 0 && blockIdx.x == 0) tbase[0] = set ? inc : tbase[0] + inc;
 }
 
+// Utterance starts inside a packed run (SampleRnnGenDesc::starts): the first launch of a period.  Block b looks at
+// starts[f][b], f = the big frame this period generates; a flagged stream gets what the first period of a run of its own
+// finds -- slot f - 1 = Q/2 (all three levels read their history from `samples`), every state that outlives a period =
+// the learned h0, its row of the next frame's gate product = h0 . Wg (the copy run() kept), and the carry of its team
+// invalidated (the other rows of the team then read their true history from `samples` too).  Rows without a flag are
+// not touched.
+struct SrStartArgs {
+    const int* starts; const int* tbase;
+    int* samples;
+    int B, D, T, BFS, len, q0;
+    int nstate;                  // row states [B][D] to reset: state[i][b][:] = h0[i][:]
+    float* state[20]; const float* h0[20];
+    float* gpre; const float* gpre0;  // [B][2D] both (null: no such product on this path)
+    SrpCarryKeys carry;
+};
+
+__global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
+    const int f = a.tbase[0] / a.BFS, b = blockIdx.x, tid = threadIdx.x;
+    if (f < 1 || f >= a.T || b >= a.B || a.starts[(size_t)f * a.B + b] == 0) return;
+    for (int i = tid; i < a.BFS; i += 256) a.samples[(size_t)b * a.len + (size_t)(f - 1) * a.BFS + i] = a.q0;
+    for (int s = 0; s < a.nstate; ++s)
+        for (int i = tid; i < a.D; i += 256) a.state[s][(size_t)b * a.D + i] = a.h0[s][i];
+    if (a.gpre)
+        for (int i = tid; i < 2 * a.D; i += 256) a.gpre[(size_t)b * 2 * a.D + i] = a.gpre0[(size_t)b * 2 * a.D + i];
+    if (a.carry.key0 && tid == 0) srp_carry_invalidate(a.carry, b);
+}
+
 #define SR_TRY(x)                 \
     do {                          \
         const int rc__ = (x);     \
@@ -170,10 +197,14 @@ struct SrPlan {
     // period, by sr_frame_in_kernel at width 3D.
     float* winu = nullptr; float* pbias = nullptr; float* pbig = nullptr; float* pin = nullptr;
     float* gpre = nullptr;  // [B, 2D] h . Wg of the next frame, made beside the projection (persistent path)
+    // Packed runs (d.starts): what run() leaves in gpre in front of the first period, h0 . Wg of every row, kept outside the
+    // period graph.  sr_start_kernel copies row b of it when stream b begins an utterance: the bits a run of that utterance
+    // in the same stream starts from, whatever tile of that launch the row was in.
+    float* gpre0 = nullptr;
     int make_winu() {
         const size_t D = d.D, nfr = d.BFS / d.FS;
         if (d.n_rnn != 0) return 0;
-        if (hipMalloc(&winu, ((size_t)d.FS * 3 * D + 3 * D + (size_t)d.B * nfr * 3 * D + (size_t)d.B * 3 * D + (size_t)d.B * 2 * D) * sizeof(float)) != hipSuccess) {
+        if (hipMalloc(&winu, ((size_t)d.FS * 3 * D + 3 * D + (size_t)d.B * nfr * 3 * D + (size_t)d.B * 3 * D + (size_t)d.B * 2 * D + (d.starts ? (size_t)d.B * 2 * D : 0)) * sizeof(float)) != hipSuccess) {
             winu = nullptr;
             return 0;
         }
@@ -181,6 +212,7 @@ struct SrPlan {
         pbig = pbias + 3 * D;
         pin = pbig + (size_t)d.B * nfr * 3 * D;
         gpre = pin + (size_t)d.B * 3 * D;
+        if (d.starts) gpre0 = gpre + (size_t)d.B * 2 * D;
         BgPrecisionScope f32_only(0);
         int rc = parrot_gemm(d.frm_Win, (int)D, 0, d.frm_U, 3 * (int)D, 0, winu, 3 * (int)D, d.FS, 3 * (int)D, (int)D, nullptr, 1.f, 0, 0,
                              1, 0, 0, 0, 1, nullptr);
@@ -188,7 +220,7 @@ struct SrPlan {
             rc = parrot_gemm(d.frm_bin, (int)D, 0, d.frm_U, 3 * (int)D, 0, pbias, 3 * (int)D, 1, 3 * (int)D, (int)D, d.frm_bU, 1.f, 0, 0,
                              1, 0, 0, 0, 1, nullptr);
         if (rc == 0) rc = (int)hipDeviceSynchronize();
-        if (rc != 0) { (void)hipFree(winu); winu = nullptr; }
+        if (rc != 0) { (void)hipFree(winu); winu = nullptr; gpre0 = nullptr; }
         return 0;
     }
     int make_composed() {
@@ -356,10 +388,39 @@ struct SrPlan {
         return 0;
     }
 
+    // Packed runs: the streams that begin an utterance in this period (sr_start_kernel).  Everything a period reads that an
+    // earlier period wrote is in this list: the sample history, the tiers' states, gpre and the sample kernel's carry; the
+    // rest of the scratch (xf_big .. logits, pbig, pin, z, rh, P, gate_ws, layer_tmp) is written before it is read in
+    // every period, and tbase belongs to the run, not to a stream.
+    int start_rows(hipStream_t st) {
+        SrStartArgs a{};
+        a.starts = d.starts; a.tbase = d.tbase; a.samples = d.samples;
+        a.B = d.B; a.D = d.D; a.T = d.T; a.BFS = d.BFS; a.len = d.BFS * d.T; a.q0 = d.Q / 2;
+        const size_t D = d.D, row = (d.lstm ? 2 : 1) * D;
+        auto add = [&](float* state, const float* h0) { a.state[a.nstate] = state; a.h0[a.nstate] = h0; ++a.nstate; };
+        if (d.n_rnn == 0) {
+            add(d.big_h, d.big_h0);
+            add(d.frm_h, d.frm_h0);
+        }
+        for (int k = 0; k < d.n_rnn; ++k) {
+            add(d.big_hs[k], d.big_h0 + k * row);
+            add(d.frm_hs[k], d.frm_h0 + k * row);
+            if (d.lstm) {  // h0 rows are [s | c]
+                add(d.big_cs[k], d.big_h0 + k * row + D);
+                add(d.frm_cs[k], d.frm_h0 + k * row + D);
+            }
+        }
+        if (persist && winu) { a.gpre = gpre; a.gpre0 = gpre0; }
+        if (persist) a.carry = srp_carry_keys(d.persist_ws, d.D, d.Q, groups);
+        hipLaunchKernelGGL(sr_start_kernel, dim3(d.B), dim3(256), 0, st, a);
+        return (int)hipGetLastError();
+    }
+
     int period(hipStream_t st) {
         const int B = d.B, D = d.D, FS = d.FS, BFS = d.BFS, len = BFS * d.T;
         const float half_q = (float)(d.Q / 2);
         const int nfr = BFS / FS;
+        if (d.starts) SR_TRY(start_rows(st));
         // ---- big-frame tier (three_tier.py:291-380), consumes samples[t-80:t] and features[t/80]
         {
             const int n = B * (BFS > d.feat_dim ? BFS : d.feat_dim);
@@ -495,6 +556,8 @@ struct SrPlan {
         if (persist && winu)  // h0 . Wg: the gates' recurrent product of the very first frame (see period())
             SR_TRY(linear(d.frm_h, d.D, d.frm_Wg, 2 * d.D, d.D, 2 * d.D, nullptr, nullptr, 0, gpre, 2 * d.D, 0, st, nullptr, 0,
                           nullptr, 0, t_frm.Wg));
+        if (persist && winu && d.starts)
+            SR_TRY((int)hipMemcpyAsync(gpre0, gpre, (size_t)d.B * 2 * d.D * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (!d.use_graph) {
             for (int p = 0; p < periods; ++p) SR_TRY(period(st));
             return 0;
@@ -543,6 +606,7 @@ int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan) { PH_EN
     if (!desc || !plan || desc->B < 1 || desc->T < 2 || desc->D < 4 || (desc->D & 3) || desc->FS < 1 ||
         desc->BFS % desc->FS != 0 || desc->Q < 2 || desc->n_rnn < 0 || desc->n_rnn > 5)
         return PARROT_ERR_BADARG;
+    if (desc->starts && (!desc->big_h0 || !desc->frm_h0)) return PARROT_ERR_BADARG;
     if (desc->n_rnn > 0) {
         if (desc->lstm && (!desc->gate_ws || !desc->layer_tmp)) return PARROT_ERR_BADARG;
         for (int k = 0; k < desc->n_rnn; ++k) {

@@ -44,3 +44,16 @@ int srp_prepare(int D);  // once per process and width, outside stream capture (
 int srp_launch(const SrpArgs& a, hipStream_t stream);
 // 0 when no launch on this workspace has timed out / mis-teamed so far
 int srp_status(const float* ws);
+
+// The launch-to-launch carry (sr_persist.hip, prologue) as seen from outside the kernel: the word that holds the sample
+// index a carry block is for, per block, and the streams a block serves.  A kernel that rewrites the sample history of
+// stream b behind the sample kernel's back (an utterance start inside a packed run, samplernn.hip) invalidates the
+// carry of b's team -- the state srp_init_ws leaves -- and the next sample launch walks the chain from `samples` for all
+// rows of that team, as the first launch of any utterance does.
+struct SrpCarryKeys {
+    int* key0;   // key word of block 0 (null: no persistent kernel)
+    int stride;  // words from one block's key to the next one's
+    int rows;    // stream b belongs to block b / rows (blocks are numbered group * teams + team)
+};
+SrpCarryKeys srp_carry_keys(float* ws, int D, int Q, int groups);
+__device__ inline void srp_carry_invalidate(const SrpCarryKeys& k, int b) { k.key0[(size_t)(b / k.rows) * k.stride] = -1; }

@@ -472,6 +472,14 @@ int srp_init_ws(float* ws, int D, int Q, int groups) {
     return (int)hipDeviceSynchronize();
 }
 
+SrpCarryKeys srp_carry_keys(float* ws, int D, int Q, int groups) {
+    SrpCarryKeys k;
+    k.key0 = ws ? reinterpret_cast<int*>(ws + srp_carry_base(D, Q, groups)) : nullptr;
+    k.stride = SRP_CARRY_WORDS;
+    k.rows = SRP_ROWS;
+    return k;
+}
+
 int srp_status(const float* ws) {
     unsigned w[2] = {0, 0};
     if (hipMemcpy(w, reinterpret_cast<const unsigned*>(ws) + 512, sizeof(w), hipMemcpyDeviceToHost) != hipSuccess) return -1;

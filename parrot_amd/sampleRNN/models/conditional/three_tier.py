@@ -197,12 +197,16 @@ def getting_generation_functions(sequences=None, h0=None, big_h0=None, reset=Non
 class DeviceGenerator:
     """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
 
-    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True):
+    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
-        three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically)."""
+        three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
+
+        packed=True: the plan takes per-stream utterance starts (SampleRnnGenDesc::starts): generate(features, starts)
+        then begins a new utterance in stream b at big frame f wherever starts[f][b] != 0 (see generate_packed)."""
         if SKIP_CONN:
             raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
         self.B, self.T = batch, n_frames
+        self.packed = bool(packed)
         dev = lib.device()
         f = dict(device=dev, dtype=torch.float32)
         D, FS, BFS, Q = DIM, FRAME_SIZE, BIG_FRAME_SIZE, Q_LEVELS
@@ -255,6 +259,11 @@ class DeviceGenerator:
             frame_out=torch.zeros(batch, FS * D, **f), o1=torch.zeros(batch, D, **f), o2=torch.zeros(batch, D, **f),
             o3=torch.zeros(batch, D, **f), logits=torch.zeros(batch, Q, **f),
             tbase=torch.zeros(1, device=dev, dtype=torch.int32))
+        if self.packed:
+            self.ws['starts'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int32)
+            # the learned initial states, [N_RNN, H0_MULT * D]: what a stream restarts from inside the loop
+            w['big_h0'] = lib.param('BigFrameLevel.h0').detach().to(**f).contiguous()
+            w['frm_h0'] = lib.param('FrameLevel.h0').detach().to(**f).contiguous()
         d = _lib.SampleRnnGenDesc()
         d.B, d.D, d.T, d.Q, d.FS, d.BFS, d.feat_dim, d.use_graph = batch, D, n_frames, Q, FS, BFS, FEAT_DIM, int(use_graph)
         d.temperature, d.seed = float(temperature), int(seed)
@@ -288,9 +297,18 @@ class DeviceGenerator:
         # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
         self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
 
-    def generate(self, features):
-        """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32."""
+    def generate(self, features, starts=None):
+        """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
+        starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
+        frame f, whose Q/2 prefix is slot f - 1."""
+        if (starts is not None) != self.packed:
+            raise ValueError("starts must be given exactly when the plan was built with packed=True")
         ws = self.ws
+        if self.packed:
+            st = torch.as_tensor(numpy.asarray(starts))
+            if tuple(st.shape) != (self.T, self.B):
+                raise ValueError("starts must be [T, B] = [%d, %d], got %s" % (self.T, self.B, tuple(st.shape)))
+            ws['starts'].copy_((st != 0).to(ws['starts'].device, torch.int32))
         ws['features'].copy_(torch.as_tensor(features).to(ws['features'].device, torch.float32))
         ws['samples'].zero_()
         ws['samples'][:, :BIG_FRAME_SIZE] = int(Q_ZERO)  # three_tier.py:795
@@ -316,6 +334,79 @@ class DeviceGenerator:
             self.plan = None
 
 
+def pack_utterances(lengths, n_streams):
+    """Places utterances of `lengths[i]` big frames one after the other into `n_streams` streams: longest first onto the
+    least-loaded stream (ties: the lower utterance index first, the lower stream index).  Returns (stream, first_slot, T):
+    utterance i occupies slots first_slot[i] .. first_slot[i] + lengths[i] - 1 of stream[i]; T = max(2, the longest
+    stream) is the frame count of the plan that runs them.  Pure Python and deterministic."""
+    lengths = [int(n) for n in lengths]
+    n_streams = int(n_streams)
+    if n_streams < 1:
+        raise ValueError("n_streams must be at least 1")
+    if any(n < 1 for n in lengths):
+        raise ValueError("every utterance needs at least one frame (its prefix slot)")
+    load = [0] * n_streams
+    stream, first_slot = [0] * len(lengths), [0] * len(lengths)
+    for i in sorted(range(len(lengths)), key=lambda i: (-lengths[i], i)):
+        b = min(range(n_streams), key=lambda b: (load[b], b))
+        stream[i], first_slot[i] = b, load[b]
+        load[b] += lengths[i]
+    return stream, first_slot, max(2, max(load))
+
+
+def build_packed_inputs(utterances, stream, first_slot, T, n_streams):
+    """(features [T, n_streams, 63] float32, starts [T, n_streams] int32) of a packing: utterance i's frame j at slot
+    first_slot[i] + j of stream[i], zeros elsewhere; starts[first_slot[i] + 1][stream[i]] = 1 wherever that slot is
+    below T (the generator overwrites slot first_slot[i] with the Q/2 prefix there and restarts the stream's state)."""
+    feat_dim = numpy.asarray(utterances[0]).shape[1] if len(utterances) else FEAT_DIM
+    features = numpy.zeros((T, n_streams, feat_dim), dtype='float32')
+    starts = numpy.zeros((T, n_streams), dtype='int32')
+    for u, b, s in zip(utterances, stream, first_slot):
+        u = numpy.asarray(u, dtype='float32')
+        if not (0 <= b < n_streams and 0 <= s and s + u.shape[0] <= T):
+            raise ValueError("utterance of %d frames does not fit at slot %d of stream %d" % (u.shape[0], s, b))
+        features[s:s + u.shape[0], b] = u
+        if s + 1 < T:
+            starts[s + 1, b] = 1
+    return features, starts
+
+
+def generate_packed(utterances, n_streams=32, temperature=TEMPERATURE, seed=234, use_graph=True):
+    """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
+    utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
+    n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
+
+    At temperature = 0 element i equals what DeviceGenerator returns for that utterance generated on its own.  At
+    temperature > 0 the draws are seeded and repeatable, but they are keyed by the packed (sample index, stream) of the
+    run, so they are NOT the draws of the utterance's standalone run."""
+    if SKIP_CONN:
+        raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
+    utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
+    if not utterances:
+        return []
+    stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
+    features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
+    gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True)
+    try:
+        samples = gen.generate(features, starts).cpu().numpy()
+    finally:
+        gen.close()
+    return unpack_samples(samples, [u.shape[0] for u in utterances], stream, first_slot)
+
+
+def unpack_samples(samples, lengths, stream, first_slot):
+    """The utterances' pieces of a packed run's samples [B, 80 T].  (The prefix of a one-frame utterance in the last slot
+    of the plan has no period behind it that would write it: it is Q/2 by definition.)"""
+    T = samples.shape[1] // BIG_FRAME_SIZE
+    out = []
+    for n, b, s in zip(lengths, stream, first_slot):
+        piece = numpy.array(samples[b, BIG_FRAME_SIZE * s:BIG_FRAME_SIZE * (s + n)], dtype='int32')
+        if s + 1 >= T:
+            piece[:BIG_FRAME_SIZE] = Q_ZERO
+        out.append(piece)
+    return out
+
+
 def write_audio_file(name, data, path_to_save):
     """three_tier.py:739-748."""
     import scipy.io.wavfile
@@ -330,9 +421,13 @@ def write_audio_file(name, data, path_to_save):
 def generate_and_save_samples(tag, path_to_save=None, features=None, features_length=None, noise_level=0.,
                               big_frame_level_generate_fn=None, frame_level_generate_fn=None,
                               sample_level_generate_fn=None, npy_address=None, temperature=TEMPERATURE,
-                              use_device_loop=True):
+                              use_device_loop=True, pack_streams=0):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
-    (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally."""
+    (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.
+
+    pack_streams = N > 0 with features_length given: row i's first features_length[i] frames form utterance i, the
+    utterances run through generate_packed on N streams and the wav files are written from the returned pieces (the
+    return value is then that list of [80 * features_length[i]] arrays).  0: the rectangle above, as before."""
     total_time = time()
     if npy_address is not None:
         test_feats = numpy.load(npy_address).astype('float32')  # [T,B,63]
@@ -341,6 +436,20 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         test_feats = numpy.asarray(features, dtype='float32')
     n_seqs, n_frames = test_feats.shape[1], test_feats.shape[0]
     LENGTH = n_frames * BIG_FRAME_SIZE
+    if pack_streams > 0 and features_length is not None:
+        lens = [min(max(int(n), 1), n_frames) for n in features_length]
+        pieces = generate_packed([test_feats[:lens[i], i] for i in range(n_seqs)], n_streams=int(pack_streams),
+                                 temperature=temperature)
+        total_time = time() - total_time
+        print("{} samples of {} seconds in all generated in {} seconds ({} packed streams).".format(
+            n_seqs, sum(lens) * BIG_FRAME_SIZE / float(BITRATE), total_time, int(pack_streams)))
+        if path_to_save is not None:
+            os.makedirs(path_to_save, exist_ok=True)
+            for i, samp in enumerate(pieces):
+                if Q_TYPE == 'mu-law':
+                    samp = hip.mu2linear(torch.from_numpy(samp.astype('int32')).to(lib.device())).cpu().numpy()
+                write_audio_file("sample_{}_{}".format(tag, i), samp, path_to_save)
+        return pieces
     if use_device_loop and not SKIP_CONN:  # (the device loop does not take the skip-connection stacks: literal loop)
         gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature)
         samples = gen.generate(test_feats).cpu().numpy()

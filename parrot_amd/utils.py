@@ -4,7 +4,7 @@ which any non-empty string is truthy.  Plotting / animation helpers (utils.py:30
 and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
---device, --use_graph; sample.py: --decode_dtype, --stop_at_end.
+--device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams.
 """
 from __future__ import annotations
 
@@ -124,6 +124,10 @@ def sample_parse(argv=None):
     parser.add_argument('--stop_at_end', type=int, default=0,
                         help='1: the decode kernel itself stops at the end of the utterance (the rule of sample.py:145-163) '
                              'instead of decoding --num_steps frames and cutting afterwards; same frames, same lengths')
+    parser.add_argument('--pack_streams', type=int, default=0,
+                        help='N > 0 (with --raw_output): the SampleRNN vocoder packs the utterances, each cut at its own '
+                             'length, one after the other into N streams of one generation plan instead of running '
+                             '--num_steps frames for every row (DESIGN.md 3.6); 0: the rectangle')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:

@@ -93,7 +93,8 @@ def main(argv=None):
         print("Sampling and saving raw audio...")
         to_save_path = os.path.join(args.save_dir, 'samples', 'new_raw')
         os.makedirs(to_save_path, exist_ok=True)
-        parrot.sampleRnn.sample_raw(gen_x.swapaxes(0, 1).copy(), features_lengths, args.samples_name, to_save_path)
+        parrot.sampleRnn.sample_raw(gen_x.swapaxes(0, 1).copy(), features_lengths, args.samples_name, to_save_path,
+                                   pack_streams=args.pack_streams)
         print("Successfully sampled raw audio...")
     out_dir = os.path.join(args.save_dir, 'samples')
     for idx, this_sample in enumerate(gen_x):

@@ -8,12 +8,19 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
   bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_stop, decode_lstm2_1024, decode_lstm3_1536,
                                          decode_gmm_gru2_1024, decode_gmm_lstm2_1024, decode_bf16_gru2_1024,
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
-                                         samplernn_cfg5, samplernn_groups, mulaw)
+                                         samplernn_cfg5, samplernn_groups, samplernn_packed, mulaw)
   bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
                                          SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
                                          kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
                                          alternations in one process; us per sample step, x real time per stream; the
                                          result also goes to FILE (default profiles/samplernn_groups.json)
+  bench_extra.py --only samplernn_packed [--reps N] [--packed-json FILE]
+                                         SampleRNN at D = 1024, 64 utterances of unequal length (fixed seed) on 32 streams:
+                                         two rectangles of 32 at their own max(length) against ONE packed run
+                                         (three_tier.pack_utterances, SampleRnnGenDesc::starts), and a packed plan whose
+                                         starts are all zero against the plain plan (the cost of the extra launch per
+                                         period); N alternations in one process; the result also goes to FILE (default
+                                         profiles/samplernn_packed.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -38,7 +45,7 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "mulaw")
+       "samplernn_packed", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -456,6 +463,73 @@ if "samplernn_groups" in only:
     out["samplernn_groups"] = res
     path = _arg("--groups-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                               "samplernn_groups.json"))
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+# ---- SampleRNN D=1024, 64 utterances of unequal length on 32 streams: (a) two rectangles of 32 in arrival order, each at
+# its own max(length); (b) one packed run (longest first onto the least-loaded stream, utterance starts inside the loop);
+# (c) the first rectangle on a packed plan whose starts are all zero against the plain plan of (a) -- what the extra launch
+# per period costs.  All plans alive in one process and run alternately.
+if "samplernn_packed" in only:
+    from parrot_amd.sampleRNN import lib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    lib.delete_all_params(); lib.set_device(dev)
+    tt.configure(DIM=1024, EMB_SIZE=256)
+    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+    with torch.no_grad():  # registers all parameters with the reference initialisation
+        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
+                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    B, N, LEN_SEED, reps = 32, 64, 1234, int(_arg("--reps", "5"))
+    rs = np.random.RandomState(LEN_SEED)
+    lengths = [int(n) for n in rs.randint(20, 201, size=N)]  # big frames of 5 ms: 0.1 .. 1 s of audio
+    utts = [rs.randn(n, 63).astype(np.float32) for n in lengths]
+    rect = []
+    for k in range(N // B):
+        Tk = max(lengths[k * B:(k + 1) * B])
+        f = np.zeros((Tk, B, 63), dtype=np.float32)
+        for b in range(B):
+            f[:lengths[k * B + b], b] = utts[k * B + b]
+        rect.append(f)
+    stream, first, Tp = tt.pack_utterances(lengths, B)
+    pf, ps = tt.build_packed_inputs(utts, stream, first, Tp, B)
+    gens = {"rect0": tt.DeviceGenerator(B, rect[0].shape[0], temperature=0.0),
+            "rect1": tt.DeviceGenerator(B, rect[1].shape[0], temperature=0.0),
+            "packed": tt.DeviceGenerator(B, Tp, temperature=0.0, packed=True),
+            "rect0_on_packed_plan": tt.DeviceGenerator(B, rect[0].shape[0], temperature=0.0, packed=True)}
+    args = {"rect0": (rect[0],), "rect1": (rect[1],), "packed": (pf, ps),
+            "rect0_on_packed_plan": (rect[0], np.zeros((rect[0].shape[0], B), dtype=np.int32))}
+    assert all(gen.persistent for gen in gens.values())
+    times, samples = {k: [] for k in gens}, {}
+    keys = list(gens)
+    for rep in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+        for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:  # (no plan always runs behind the same other one)
+            torch.cuda.synchronize(); t0 = time.time()
+            s = gens[k].generate(*args[k])
+            torch.cuda.synchronize(); dt = time.time() - t0
+            samples[k] = s.cpu().numpy().copy()
+            if rep:
+                times[k].append(dt)
+    for gen in gens.values():
+        gen.close()
+    pieces = tt.unpack_samples(samples["packed"], lengths, stream, first)
+    same = sum(int(np.array_equal(pieces[i], samples["rect%d" % (i // B)][i % B, :80 * lengths[i]])) for i in range(N))
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    periods = {k: gens[k].T - 1 for k in gens}
+    res = {"dim": 1024, "streams": B, "utterances": N, "length_seed": LEN_SEED, "lengths": lengths, "alternations": reps,
+           "periods": {"rectangles": periods["rect0"] + periods["rect1"], "packed": periods["packed"],
+                       "ratio": round((periods["rect0"] + periods["rect1"]) / periods["packed"], 3)},
+           "ms": {k: {"median": round(1e3 * med[k], 2), "spread": round(1e3 * (max(v) - min(v)), 2),
+                      "us_per_period": round(1e6 * med[k] / periods[k], 2)} for k, v in times.items()},
+           "ms_rectangles": round(1e3 * (med["rect0"] + med["rect1"]), 2),
+           "ms_packed": round(1e3 * med["packed"], 2),
+           "measured_ratio": round((med["rect0"] + med["rect1"]) / med["packed"], 3),
+           "start_launch_us_per_period": round(1e6 * (med["rect0_on_packed_plan"] - med["rect0"]) / periods["rect0"], 2),
+           "utterances_equal_to_rectangles": same,
+           "zero_starts_bit_identical": bool((samples["rect0_on_packed_plan"] == samples["rect0"]).all())}
+    out["samplernn_packed"] = res
+    path = _arg("--packed-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                              "samplernn_packed.json"))
     with open(path, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
