@@ -810,6 +810,8 @@ int samplernn_weightnorm_fold_bwd(const float* W, int ld, const float* g, const 
  * plan's life: create makes fragment-major copies of the tiers' matrices for the step kernel (single-GRU tiers) and, on the
  * persistent path, composes everything in front of L2's ReLU through W2 once (emb_tbl[pos] . W2, frm_Wout_i . W2,
  * frm_bout_i . W2 + b2; round 5) -- the sample kernel then has no L2 product.
+ * A run need not be one rectangle of T frames: samplernn_generate_run_segment (below) runs any number of periods up to
+ * T-1 and resumes from where the last call ended, with the buffers of this descriptor used as a ring.
  * ------------------------------------------------------------------------------------------ */
 typedef struct SampleRnnGenDesc {
     int B, D, T, Q, FS, BFS, feat_dim, use_graph;
@@ -881,6 +883,22 @@ int samplernn_generate_persist_groups(void* plan);
 int samplernn_persist_groups_dry(int B, int max_groups);
 int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan);
 int samplernn_generate_run(void* plan, void* stream);
+/* A run in segments: the plan's buffers as a ring of T slots.  n_periods in 1 .. T-1, else PARROT_ERR_BADARG.
+ *   resume = 0: what samplernn_generate_run does, for n_periods periods instead of T-1 -- the caller has set the prefix slot
+ *     and the initial states; slots 1 .. n_periods are generated from features[1 .. n_periods] (and starts[1 .. n_periods]).
+ *     samplernn_generate_run(plan, stream) is samplernn_generate_run_segment(plan, T-1, 0, stream).
+ *   resume = 1: continues the run the plan executed last (PARROT_ERR_BADARG on a plan that has not run).  A small launch in
+ *     front of the first period reads on the device where that run ended (tbase / BFS - 1, whatever its n_periods was),
+ *     copies that slot of every stream to slot 0, sets tbase back to BFS, re-keys the persistent kernel's carry and adds the
+ *     samples moved past to the plan's draw origin; then slots 1 .. n_periods are generated from features[1 .. n_periods]
+ *     and, on packed plans, starts[1 .. n_periods] (a start at frame 1 overwrites the moved slot with the Q/2 prefix).
+ *     Nothing else is reset: the tier states, the next frame's gate product and, on packed plans, the h0 . Wg rows of the
+ *     first run stay.  The caller reads slots 1 .. n_periods of `samples` (after samplernn_generate_status, which
+ *     synchronises) and writes the next segment's frames before it calls again.
+ * The segments of a run compute, bit for bit, the samples of the same run in one piece: seeded draws (temperature > 0) are
+ * keyed by (draw origin + index in the buffer, stream), and resume = 0 sets the origin to 0.  Every segment replays the
+ * plan's two captured graphs (eight periods, one period); nothing is captured per segment. */
+int samplernn_generate_run_segment(void* plan, int n_periods, int resume, void* stream);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

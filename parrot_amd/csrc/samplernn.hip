@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 // temperature-scaled multinomial draw from a counter-based generator when temperature > 0.
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
-                                                      unsigned long long seed) {
+                                                      unsigned long long seed, const unsigned long long* __restrict__ origin) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int t = tbase[0] + toff;
@@ -93,7 +93,8 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
         const float mx = sv[0];
         float tot = 0.f;
         for (int q = 0; q < Q; ++q) tot += expf((lg[q] - mx) / temperature);
-        unsigned long long x = seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(t + 1)) ^
+        // (keyed by the sample's index in the whole run: the draw origin counts what resumed segments have moved past)
+        unsigned long long x = seed ^ (0x9E3779B97F4A7C15ull * (origin[0] + (unsigned long long)(t + 1))) ^
                                (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
         x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;  // splitmix64
         const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
@@ -137,8 +138,45 @@ __global__ __launch_bounds__(256) void sr_frame_in_kernel(const int* __restrict_
     out[(size_t)b * D + dd] = acc;
 }
 
-__global__ void sr_tick_kernel(int* tbase, int inc, int set) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) tbase[0] = set ? inc : tbase[0] + inc;
+// (origin: the draw origin, set to 0 with tbase in front of a run that does not resume; null inside a period)
+__global__ void sr_tick_kernel(int* tbase, int inc, int set, unsigned long long* origin) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        tbase[0] = set ? inc : tbase[0] + inc;
+        if (set && origin) origin[0] = 0;
+    }
+}
+
+// Segment boundary of a resumed run (samplernn_generate_run_segment, resume = 1): the first launch of the segment, outside
+// the period graphs.  The plan's buffer is a ring of T slots: the last slot the previous run wrote, tbase / BFS - 1 whatever
+// its length was, becomes slot 0 of every stream (the only history a period reads), tbase goes back to BFS, and the draw
+// origin moves on by the samples the ring has turned past, so that a seeded draw stays keyed by the sample's index in the
+// whole run.  The sample kernel's carry holds that slot's last samples and their table sums, keyed by the sample index
+// they were left for: the blocks with the key of the old tbase are re-keyed to BFS (the next launch takes them as it
+// does inside a run), any other block is invalidated.  One workgroup: every thread has read tbase before it is rewritten.
+struct SrResumeArgs {
+    int* tbase; int* samples; unsigned long long* origin;
+    int B, T, BFS, len;
+    SrpCarryKeys carry;  // (key0 null: no persistent kernel)
+};
+
+__global__ __launch_bounds__(256) void sr_resume_kernel(const SrResumeArgs a) {
+    const int tid = threadIdx.x;
+    const int tb = a.tbase[0], last = tb / a.BFS - 1;
+    __syncthreads();
+    if (last < 1 || last >= a.T) return;  // (nothing has run: the host refuses that before it gets here)
+    for (int idx = tid; idx < a.B * a.BFS; idx += 256) {
+        const int b = idx / a.BFS, i = idx % a.BFS;
+        a.samples[(size_t)b * a.len + i] = a.samples[(size_t)b * a.len + (size_t)last * a.BFS + i];
+    }
+    if (a.carry.key0)
+        for (int k = tid; k < a.carry.blocks; k += 256) {
+            int* key = a.carry.key0 + (size_t)k * a.carry.stride;
+            key[0] = key[0] == tb ? a.BFS : -1;
+        }
+    if (tid == 0) {
+        a.tbase[0] = a.BFS;
+        a.origin[0] += (unsigned long long)last * (unsigned long long)a.BFS;
+    }
 }
 
 // Utterance starts inside a packed run (SampleRnnGenDesc::starts): the first launch of a period.  Block b looks at
@@ -201,6 +239,14 @@ struct SrPlan {
     // period graph.  sr_start_kernel copies row b of it when stream b begins an utterance: the bits a run of that utterance
     // in the same stream starts from, whatever tile of that launch the row was in.
     float* gpre0 = nullptr;
+    // Draw origin (one device word, owned by the plan): samples the resumed segments of the current run have moved past;
+    // the seeded draw of buffer index t is keyed by origin + t.  A device word because the periods replay from graphs.
+    unsigned long long* origin = nullptr;
+    bool has_run = false;  // a run has been issued: resume = 1 has something to continue
+    int make_origin() {
+        if (hipMalloc(&origin, sizeof(unsigned long long)) != hipSuccess) { origin = nullptr; return 1; }
+        return (int)hipMemset(origin, 0, sizeof(unsigned long long));
+    }
     int make_winu() {
         const size_t D = d.D, nfr = d.BFS / d.FS;
         if (d.n_rnn != 0) return 0;
@@ -278,6 +324,7 @@ struct SrPlan {
         if (tiled_slab) (void)hipFree(tiled_slab);
         if (t2tbl) (void)hipFree(t2tbl);
         if (winu) (void)hipFree(winu);
+        if (origin) (void)hipFree(origin);
     }
 
     int linear(const float* A, int lda, const float* W, int ldw, int K, int N, const float* bias, const float* add,
@@ -516,6 +563,7 @@ struct SrPlan {
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
+                sa.origin = origin;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -540,24 +588,40 @@ struct SrPlan {
                 SR_TRY(linear(d.o2, D, d.W3, D, D, D, d.b3, nullptr, 0, d.o3, D, SK_ACT_RELU, st));
                 SR_TRY(linear(d.o3, D, d.W4, d.Q, D, d.Q, d.b4, nullptr, 0, d.logits, d.Q, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
-                                   d.temperature, d.seed);
+                                   d.temperature, d.seed, (const unsigned long long*)origin);
             }
         }
-        hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0);
+        hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
         return (int)hipGetLastError();
     }
 
-    int run(hipStream_t st) {
-        // tbase starts at BFS (first 80 samples are Q_ZERO, set by the caller); T-1 periods follow.
-        hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, d.BFS, 1);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-        const int periods = d.T - 1;
-        if (persist && winu)  // h0 . Wg: the gates' recurrent product of the very first frame (see period())
-            SR_TRY(linear(d.frm_h, d.D, d.frm_Wg, 2 * d.D, d.D, 2 * d.D, nullptr, nullptr, 0, gpre, 2 * d.D, 0, st, nullptr, 0,
-                          nullptr, 0, t_frm.Wg));
-        if (persist && winu && d.starts)
-            SR_TRY((int)hipMemcpyAsync(gpre0, gpre, (size_t)d.B * 2 * d.D * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // The ring turns (sr_resume_kernel): everything else a period reads from the one before it -- the tiers' states, gpre,
+    // and gpre0 of a packed plan -- stays where the last period left it.
+    int resume_rows(hipStream_t st) {
+        SrResumeArgs a{};
+        a.tbase = d.tbase; a.samples = d.samples; a.origin = origin;
+        a.B = d.B; a.T = d.T; a.BFS = d.BFS; a.len = d.BFS * d.T;
+        if (persist) a.carry = srp_carry_keys(d.persist_ws, d.D, d.Q, groups);
+        hipLaunchKernelGGL(sr_resume_kernel, dim3(1), dim3(256), 0, st, a);
+        return (int)hipGetLastError();
+    }
+
+    int run(int periods, bool resume, hipStream_t st) {
+        hipError_t e;
+        if (resume) {
+            SR_TRY(resume_rows(st));
+        } else {
+            // tbase starts at BFS (first 80 samples are Q_ZERO, set by the caller); `periods` periods follow (T-1: a whole run).
+            hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, d.BFS, 1, origin);
+            e = hipGetLastError();
+            if (e != hipSuccess) return (int)e;
+            if (persist && winu)  // h0 . Wg: the gates' recurrent product of the very first frame (see period())
+                SR_TRY(linear(d.frm_h, d.D, d.frm_Wg, 2 * d.D, d.D, 2 * d.D, nullptr, nullptr, 0, gpre, 2 * d.D, 0, st, nullptr, 0,
+                              nullptr, 0, t_frm.Wg));
+            if (persist && winu && d.starts)
+                SR_TRY((int)hipMemcpyAsync(gpre0, gpre, (size_t)d.B * 2 * d.D * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+        has_run = true;
         if (!d.use_graph) {
             for (int p = 0; p < periods; ++p) SR_TRY(period(st));
             return 0;
@@ -626,6 +690,7 @@ int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan) { PH_EN
     p->groups = p->persist ? groups : 0;
     p->make_tiled();  // (after the decision: the persistent path tiles the composed projection)
     p->make_winu();
+    if (p->make_origin() != 0) { delete p; return PARROT_ERR_BADARG; }
     *plan = p;
     return 0;
 }
@@ -656,11 +721,17 @@ int samplernn_generate_status(void* plan) { PH_ENTRY();
     return p->persist ? srp_status(p->d.persist_ws) : 0;
 }
 
-int samplernn_generate_run(void* plan, void* stream) { PH_ENTRY();
+int samplernn_generate_run_segment(void* plan, int n_periods, int resume, void* stream) { PH_ENTRY();
     SrPlan* p = static_cast<SrPlan*>(plan);
-    const int rc = p->run((hipStream_t)stream);
+    if (!p || n_periods < 1 || n_periods > p->d.T - 1 || (resume && !p->has_run)) return PARROT_ERR_BADARG;
+    const int rc = p->run(n_periods, resume != 0, (hipStream_t)stream);
     if (rc != 0 && p->last_error == 0) p->last_error = rc;
     return rc;
+}
+
+int samplernn_generate_run(void* plan, void* stream) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    return samplernn_generate_run_segment(plan, p ? p->d.T - 1 : 0, 0, stream);
 }
 
 int samplernn_generate_destroy(void* plan) { PH_ENTRY();

@@ -29,6 +29,9 @@ struct SrpArgs {
     unsigned long long seed;
     int ngroups;                       // row groups of 32 streams this launch takes one after the other: ceil(B / 32), the
                                        // count ws was sized and initialised for (1: the kernel without the group loop)
+    // Draw origin (device word, required): the seeded draw of sample index t is keyed by origin[0] + t -- 0 in a run of one
+    // piece; a resumed segment (samplernn.hip, sr_resume_kernel) counts the samples the ring has turned past in it.
+    const unsigned long long* origin;
 };
 
 // PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8
@@ -54,6 +57,7 @@ struct SrpCarryKeys {
     int* key0;   // key word of block 0 (null: no persistent kernel)
     int stride;  // words from one block's key to the next one's
     int rows;    // stream b belongs to block b / rows (blocks are numbered group * teams + team)
+    int blocks;  // blocks in all (groups * teams)
 };
 SrpCarryKeys srp_carry_keys(float* ws, int D, int Q, int groups);
 __device__ inline void srp_carry_invalidate(const SrpCarryKeys& k, int b) { k.key0[(size_t)(b / k.rows) * k.stride] = -1; }

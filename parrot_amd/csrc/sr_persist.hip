@@ -96,6 +96,9 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
     // return in order -- the weight requests need not wait for them)
     typedef const int __attribute__((address_space(4))) * srp_cint;
     const int t0 = *(srp_cint)(unsigned long long)a.tbase + a.toff;
+    // (the draw origin beside it, once per launch: a seeded draw is keyed by the sample's index in the whole run)
+    typedef const unsigned long long __attribute__((address_space(4))) * srp_cull;
+    const unsigned long long draw0 = *(srp_cull)(unsigned long long)a.origin;
     // Row groups (MG): everything from here to the exchange buffers below that depends on the streams is set for group 0
     // and moved on at the end of the group loop -- srow = the first stream of this team in the current group, its carry
     // block, gb --; the four values requested here (carry_t, hc, cs, f0: what a group starts from) are used up at the top
@@ -298,7 +301,7 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                         const int b = srow + r;
                         float tot = 0.f;
                         for (int q = 0; q < Q; ++q) tot += ev[r * Q + q];
-                        unsigned long long x = a.seed ^ (0x9E3779B97F4A7C15ull * (unsigned long long)(t + 1)) ^
+                        unsigned long long x = a.seed ^ (0x9E3779B97F4A7C15ull * (draw0 + (unsigned long long)(t + 1))) ^
                                                (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
                         x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
                         const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
@@ -477,6 +480,7 @@ SrpCarryKeys srp_carry_keys(float* ws, int D, int Q, int groups) {
     k.key0 = ws ? reinterpret_cast<int*>(ws + srp_carry_base(D, Q, groups)) : nullptr;
     k.stride = SRP_CARRY_WORDS;
     k.rows = SRP_ROWS;
+    k.blocks = groups * SRP_NTEAMS;
     return k;
 }
 
@@ -515,7 +519,7 @@ int srp_prepare(int D) {
 }
 
 int srp_launch(const SrpArgs& a, hipStream_t stream) {
-    if (!a.ws || a.nsteps < 1 || a.FS + a.nsteps > SRP_MAXHIST) return PH_ERR_BADARG;
+    if (!a.ws || !a.origin || a.nsteps < 1 || a.FS + a.nsteps > SRP_MAXHIST) return PH_ERR_BADARG;
     if (a.ngroups < 1 || a.ngroups > SRP_MAXGROUPS || a.B < 1 || a.B > SRP_ROWS * SRP_NTEAMS * a.ngroups) return PH_ERR_BADARG;
     const size_t lds = srp_lds_bytes(a.D);
     const dim3 grid(SRP_TEAM * SRP_NTEAMS), block(SRP_THREADS);

@@ -296,20 +296,60 @@ class DeviceGenerator:
         self.persistent = bool(_lib.load().samplernn_generate_is_persistent(self.plan))
         # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
         self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
+        self._has_run = False
 
-    def generate(self, features, starts=None):
+    def generate(self, features, starts=None, resume=False, n_frames=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
-        frame f, whose Q/2 prefix is slot f - 1."""
+        frame f, whose Q/2 prefix is slot f - 1.
+
+        A run in segments (samplernn_generate_run_segment): n_frames = k in 1 .. T-1 generates k frames in this call.
+        resume=False starts a run: features (and starts) hold k + 1 rows, slot 0 = the prefix, and the [B, 80 (k + 1)]
+        samples come back, prefix included.  resume=True continues the run of the last call from the states where they
+        stand: features (and starts) hold k rows, for slots 1 .. k of the ring -- slot 0 is the last slot of the call
+        before --, nothing is re-initialised and the [B, 80 k] samples of this segment come back (a copy: the next
+        segment overwrites the ring).  The segments of a run equal the run in one piece, seeded draws included."""
         if (starts is not None) != self.packed:
             raise ValueError("starts must be given exactly when the plan was built with packed=True")
+        resume = bool(resume)
+        if resume and not self._has_run:
+            raise ValueError("resume=True needs a run to continue: call generate(..., resume=False) first")
+        segment = resume or n_frames is not None
+        k = self.T - 1 if n_frames is None else int(n_frames)
+        if not 1 <= k <= self.T - 1:
+            raise ValueError("n_frames must be in 1 .. T-1 = %d, got %d" % (self.T - 1, k))
+        rows = k if resume else (k + 1 if n_frames is not None else self.T)
+        first = 1 if resume else 0
         ws = self.ws
+        feats = torch.as_tensor(features)
+        if segment and (feats.dim() != 3 or tuple(feats.shape[:2]) != (rows, self.B)):
+            raise ValueError("features must be [%d, %d, %d], got %s" % (rows, self.B, FEAT_DIM, tuple(feats.shape)))
         if self.packed:
             st = torch.as_tensor(numpy.asarray(starts))
-            if tuple(st.shape) != (self.T, self.B):
-                raise ValueError("starts must be [T, B] = [%d, %d], got %s" % (self.T, self.B, tuple(st.shape)))
-            ws['starts'].copy_((st != 0).to(ws['starts'].device, torch.int32))
-        ws['features'].copy_(torch.as_tensor(features).to(ws['features'].device, torch.float32))
+            if tuple(st.shape) != (rows, self.B):
+                raise ValueError("starts must be [%s, B] = [%d, %d], got %s" % ("T" if not segment else "rows", rows, self.B,
+                                                                                 tuple(st.shape)))
+            ws['starts'][first:first + rows].copy_((st != 0).to(ws['starts'].device, torch.int32))
+        if not segment:
+            ws['features'].copy_(feats.to(ws['features'].device, torch.float32))
+        else:
+            ws['features'][first:first + rows].copy_(feats.to(ws['features'].device, torch.float32))
+        if not resume:
+            self._init_run()
+        if not segment:
+            _lib.call('samplernn_generate_run', self.plan, hip._stream())
+        else:
+            _lib.call('samplernn_generate_run_segment', self.plan, k, int(resume), hip._stream())
+        self._has_run = True
+        if self.persistent or segment:  # a team of the persistent kernel that gave up leaves invalid samples: fail loudly
+            _lib.call('samplernn_generate_status', self.plan)
+        if not segment:
+            return ws['samples']
+        return ws['samples'][:, BIG_FRAME_SIZE * first:BIG_FRAME_SIZE * (k + 1)].clone()
+
+    def _init_run(self):
+        """The prefix slot and the learned initial states: what a run that does not resume starts from."""
+        ws = self.ws
         ws['samples'].zero_()
         ws['samples'][:, :BIG_FRAME_SIZE] = int(Q_ZERO)  # three_tier.py:795
         # reset = (t == BIG_FRAME_SIZE): the first step of both tiers starts from the learned h0 (:334-342, 411-419)
@@ -323,10 +363,6 @@ class DeviceGenerator:
                     self.states[(tag, 'h', k)].copy_(h0[k, :DIM].unsqueeze(0).expand(self.B, -1))
                     if RNN_TYPE == 'LSTM':
                         self.states[(tag, 'c', k)].copy_(h0[k, DIM:].unsqueeze(0).expand(self.B, -1))
-        _lib.call('samplernn_generate_run', self.plan, hip._stream())
-        if self.persistent:  # a team of the persistent kernel that gave up leaves invalid samples: fail loudly
-            _lib.call('samplernn_generate_status', self.plan)
-        return ws['samples']
 
     def close(self):
         if self.plan:
@@ -407,6 +443,191 @@ def unpack_samples(samples, lengths, stream, first_slot):
     return out
 
 
+def generate_stream(features, segment_frames, temperature=TEMPERATURE, seed=234, use_graph=True, gen=None):
+    """Generator over a rectangle features [N, B, 63] on a plan of segment_frames + 1 slots used as a ring: yields int32
+    arrays [B, 80 n] -- the first one holds the Q/2 prefix and up to segment_frames frames, every later one up to
+    segment_frames frames -- whose concatenation is the [B, 80 N] result of DeviceGenerator(B, N).generate(features), bit
+    for bit, seeded draws included.  The plan does not grow with N, and the first samples are out after segment_frames
+    periods.  gen: a plain DeviceGenerator(B, segment_frames + 1) of the caller's to run on (it is left open; temperature,
+    seed and use_graph are then the plan's); default: a plan of its own for this call."""
+    if SKIP_CONN:
+        raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
+    features = numpy.asarray(features, dtype='float32')
+    S = int(segment_frames)
+    if S < 1:
+        raise ValueError("segment_frames must be at least 1")
+    if features.ndim != 3 or features.shape[0] < 2:
+        raise ValueError("features must be [N, B, %d] with N >= 2 (the prefix slot and one frame)" % FEAT_DIM)
+    N, B = features.shape[0], features.shape[1]
+    own = gen is None
+    if own:
+        gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph)
+    elif gen.packed or (gen.B, gen.T) != (B, S + 1):
+        raise ValueError("gen must be a plain plan of %d streams and %d slots" % (B, S + 1))
+    try:
+        k = min(S, N - 1)
+        yield gen.generate(features[:k + 1], n_frames=k).cpu().numpy()
+        done = k + 1
+        while done < N:
+            k = min(S, N - done)
+            yield gen.generate(features[done:done + k], resume=True, n_frames=k).cpu().numpy()
+            done += k
+    finally:
+        if own:
+            gen.close()
+
+
+def schedule_segment(running, queue, n_streams, segment_frames):
+    """One segment of continuous admission (StreamingGenerator): which utterance takes which slots 1 .. segment_frames of
+    which stream.  Pure Python and deterministic; the arguments are not changed.
+
+    running[b] = None or (ticket, placed, length): stream b's utterance and how many of its `length` frames earlier
+    segments have placed (>= 1; its last one is the ring's slot 0).  queue = [(ticket, length), ...], oldest first.
+    The rules: a stream goes on with its utterance from slot 1; when that ends at slot k < segment_frames (k = 0: the
+    stream was idle) a queued utterance may begin at slot k + 1 of the same stream -- that slot is its Q/2 prefix, its
+    start flag is on the slot of its frame 1, in this segment or at slot 1 of the next.  The queue is FIFO: its oldest
+    utterance takes the earliest free slot of any stream (the lower stream index among equals), until no stream has a
+    free slot or the queue is empty.
+
+    Returns (placements, starts, n_slots, running', queue'): placements = [(ticket, stream, slot, frame, count)] --
+    frames frame .. frame + count - 1 of the utterance at slots slot .. slot + count - 1 --, starts = [(slot, stream)],
+    n_slots = the busiest stream's last slot (the periods the segment runs: no period with every stream idle; 0 = nothing to
+    run).  Whenever an utterance is left unfinished it has reached slot segment_frames = n_slots, so its next frame is
+    slot 1 of the next segment."""
+    B, S = int(n_streams), int(segment_frames)
+    if B < 1:
+        raise ValueError("n_streams must be at least 1")
+    if S < 1:
+        raise ValueError("segment_frames must be at least 1")
+    running = list(running)
+    if len(running) != B:
+        raise ValueError("running must hold one entry per stream")
+    queue = [(t, int(n)) for t, n in queue]
+    placements = []
+    free = [1] * B  # the stream's first slot nobody has taken yet
+
+    def place(b, ticket, placed, length):
+        count = min(length - placed, S - free[b] + 1)
+        placements.append((ticket, b, free[b], placed, count))
+        free[b] += count
+        running[b] = (ticket, placed + count, length) if placed + count < length else None
+
+    for b in range(B):
+        if running[b] is not None:
+            place(b, *running[b])
+    while queue:
+        b = min(range(B), key=lambda b: (free[b], b))
+        if free[b] > S or running[b] is not None:  # (a stream whose utterance goes on is full: free = S + 1)
+            break
+        ticket, length = queue.pop(0)
+        if length < 1:
+            raise ValueError("every utterance needs at least one frame (its prefix slot)")
+        place(b, ticket, 0, length)
+    placements.sort(key=lambda x: (x[1], x[2]))
+    starts = [(slot + 1 - frame, b) for _, b, slot, frame, count in placements if frame <= 1 < frame + count]
+    n_slots = max(free) - 1
+    return placements, starts, n_slots, running, queue
+
+
+class StreamingGenerator:
+    """Continuous admission on ONE packed plan of segment_frames + 1 slots that never ends: utterances are submitted at any
+    time, every step() runs one segment of the ring (schedule_segment decides who takes which slots) and hands out the
+    samples of every utterance that had slots in it.
+
+    The first 80 samples of an utterance's first chunk are its Q/2 prefix.  At temperature = 0 the concatenated chunks of
+    an utterance equal what a plain plan of n_streams returns for it carried in the same stream (record[ticket] =
+    (stream, absolute slot of its prefix)); at temperature > 0 the draws are repeatable for the same sequence of
+    submit / step calls, but they are not the draws of the utterance's standalone run.
+
+    run_segment(features [n, B, 63], starts [n, B], resume) -> samples [B, 80 n] of slots 1 .. n is the callable that
+    runs a segment; the default runs it on the device."""
+
+    def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None):
+        if SKIP_CONN:
+            raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
+        self.B, self.S = int(n_streams), int(segment_frames)
+        if self.B < 1:
+            raise ValueError("n_streams must be at least 1")
+        if self.S < 1:
+            raise ValueError("segment_frames must be at least 1")
+        self.gen = None
+        if run_segment is None:
+            self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
+                                       packed=True)
+            run_segment = self._run_on_device
+        self._run = run_segment
+        self._resume = False
+        self._next_ticket = 0
+        self._slots_run = 0            # periods run so far: slot s of this segment is absolute slot _slots_run + s
+        self.running = [None] * self.B
+        self.queue = []
+        self._features = {}
+        self.record = {}
+
+    def _run_on_device(self, features, starts, resume):
+        if resume:
+            return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0]).cpu().numpy()
+        n = features.shape[0]  # the first segment: slot 0 is the run's prefix slot, no stream uses it
+        features = numpy.concatenate([numpy.zeros_like(features[:1]), features])
+        starts = numpy.concatenate([numpy.zeros_like(starts[:1]), starts])
+        return self.gen.generate(features, starts, n_frames=n).cpu().numpy()[:, BIG_FRAME_SIZE:]
+
+    def submit(self, features):
+        """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order."""
+        features = numpy.asarray(features, dtype='float32')
+        if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != FEAT_DIM:
+            raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (FEAT_DIM, features.shape))
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        self._features[ticket] = features
+        self.queue.append((ticket, features.shape[0]))
+        return ticket
+
+    def idle(self):
+        return not self.queue and all(r is None for r in self.running)
+
+    def step(self):
+        """Runs one segment; returns [(ticket, chunk int32 [80 k], done)] for every utterance that had slots in it."""
+        placements, starts, n, self.running, self.queue = schedule_segment(self.running, self.queue, self.B, self.S)
+        if n == 0:
+            return []
+        feats = numpy.zeros((n, self.B, FEAT_DIM), dtype='float32')
+        flags = numpy.zeros((n, self.B), dtype='int32')
+        for ticket, b, slot, frame, count in placements:
+            feats[slot - 1:slot - 1 + count, b] = self._features[ticket][frame:frame + count]
+            if frame == 0:
+                self.record[ticket] = (b, self._slots_run + slot)
+        for slot, b in starts:
+            flags[slot - 1, b] = 1
+        samples = numpy.asarray(self._run(feats, flags, self._resume))
+        if samples.shape != (self.B, BIG_FRAME_SIZE * n):
+            raise ValueError("the segment runner returned %s, not %s" % (samples.shape, (self.B, BIG_FRAME_SIZE * n)))
+        self._resume = True
+        self._slots_run += n
+        out = []
+        for ticket, b, slot, frame, count in placements:
+            chunk = numpy.array(samples[b, BIG_FRAME_SIZE * (slot - 1):BIG_FRAME_SIZE * (slot - 1 + count)], dtype='int32')
+            if frame == 0:
+                chunk[:BIG_FRAME_SIZE] = Q_ZERO  # (the period that would write it may lie in the next segment)
+            done = frame + count == self._features[ticket].shape[0]
+            if done:
+                del self._features[ticket]
+            out.append((ticket, chunk, done))
+        return out
+
+    def drain(self):
+        """Steps until nothing is queued or running; returns the chunks of all those steps in order."""
+        out = []
+        while not self.idle():
+            out += self.step()
+        return out
+
+    def close(self):
+        if self.gen is not None:
+            self.gen.close()
+            self.gen = None
+
+
 def write_audio_file(name, data, path_to_save):
     """three_tier.py:739-748."""
     import scipy.io.wavfile
@@ -421,13 +642,17 @@ def write_audio_file(name, data, path_to_save):
 def generate_and_save_samples(tag, path_to_save=None, features=None, features_length=None, noise_level=0.,
                               big_frame_level_generate_fn=None, frame_level_generate_fn=None,
                               sample_level_generate_fn=None, npy_address=None, temperature=TEMPERATURE,
-                              use_device_loop=True, pack_streams=0):
+                              use_device_loop=True, pack_streams=0, stream_frames=0):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
     (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.
 
     pack_streams = N > 0 with features_length given: row i's first features_length[i] frames form utterance i, the
     utterances run through generate_packed on N streams and the wav files are written from the returned pieces (the
-    return value is then that list of [80 * features_length[i]] arrays).  0: the rectangle above, as before."""
+    return value is then that list of [80 * features_length[i]] arrays).  0: the rectangle above, as before.
+
+    stream_frames = S > 0 with features_length given: the utterances go through a StreamingGenerator of
+    pack_streams or 32 streams in segments of S frames; each wav is written as soon as its utterance has finished, and
+    the return value is the list of pieces as above."""
     total_time = time()
     if npy_address is not None:
         test_feats = numpy.load(npy_address).astype('float32')  # [T,B,63]
@@ -436,6 +661,34 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         test_feats = numpy.asarray(features, dtype='float32')
     n_seqs, n_frames = test_feats.shape[1], test_feats.shape[0]
     LENGTH = n_frames * BIG_FRAME_SIZE
+    if stream_frames > 0 and features_length is not None:
+        lens = [min(max(int(n), 1), n_frames) for n in features_length]
+        n_streams = int(pack_streams) if pack_streams > 0 else 32
+        if path_to_save is not None:
+            os.makedirs(path_to_save, exist_ok=True)
+        sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature)
+        chunks = [[] for _ in range(n_seqs)]
+        pieces = [None] * n_seqs
+        try:
+            for i in range(n_seqs):
+                assert sg.submit(test_feats[:lens[i], i]) == i
+            while not sg.idle():
+                for i, chunk, done in sg.step():
+                    chunks[i].append(chunk)
+                    if not done:
+                        continue
+                    pieces[i] = samp = numpy.concatenate(chunks[i])
+                    chunks[i] = None
+                    if path_to_save is not None:
+                        if Q_TYPE == 'mu-law':
+                            samp = hip.mu2linear(torch.from_numpy(samp.astype('int32')).to(lib.device())).cpu().numpy()
+                        write_audio_file("sample_{}_{}".format(tag, i), samp, path_to_save)
+        finally:
+            sg.close()
+        total_time = time() - total_time
+        print("{} samples of {} seconds in all generated in {} seconds ({} streams, segments of {} frames).".format(
+            n_seqs, sum(lens) * BIG_FRAME_SIZE / float(BITRATE), total_time, n_streams, int(stream_frames)))
+        return pieces
     if pack_streams > 0 and features_length is not None:
         lens = [min(max(int(n), 1), n_frames) for n in features_length]
         pieces = generate_packed([test_feats[:lens[i], i] for i in range(n_seqs)], n_streams=int(pack_streams),

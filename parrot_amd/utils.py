@@ -4,7 +4,7 @@ which any non-empty string is truthy.  Plotting / animation helpers (utils.py:30
 and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
---device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams.
+--device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames.
 """
 from __future__ import annotations
 
@@ -128,6 +128,10 @@ def sample_parse(argv=None):
                         help='N > 0 (with --raw_output): the SampleRNN vocoder packs the utterances, each cut at its own '
                              'length, one after the other into N streams of one generation plan instead of running '
                              '--num_steps frames for every row (DESIGN.md 3.6); 0: the rectangle')
+    parser.add_argument('--stream_frames', type=int, default=0,
+                        help='S > 0 (with --raw_output): the SampleRNN vocoder runs the utterances through one plan of S + 1 '
+                             'slots used as a ring, in segments of S frames on --pack_streams (or 32) streams, and writes '
+                             'each wav as its utterance finishes (DESIGN.md 3.6); 0: one closed run')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
