@@ -896,9 +896,26 @@ int samplernn_generate_run(void* plan, void* stream);
  *     first run stay.  The caller reads slots 1 .. n_periods of `samples` (after samplernn_generate_status, which
  *     synchronises) and writes the next segment's frames before it calls again.
  * The segments of a run compute, bit for bit, the samples of the same run in one piece: seeded draws (temperature > 0) are
- * keyed by (draw origin + index in the buffer, stream), and resume = 0 sets the origin to 0.  Every segment replays the
- * plan's two captured graphs (eight periods, one period); nothing is captured per segment. */
+ * keyed by the sample's run index = draw origin + index in the buffer, and resume = 0 sets the origin to 0 -- together
+ * with the stream and the plan's seed by default, or, after samplernn_generate_set_utterance_draws (below), counted from
+ * the utterance's own prefix slot and hashed with the utterance's own seed.  Every segment replays the plan's two
+ * captured graphs (eight periods, one period); nothing is captured per segment. */
 int samplernn_generate_run_segment(void* plan, int n_periods, int resume, void* stream);
+/* Per-utterance seeds and temperatures.  utt_seed [T][B] (unsigned long long), utt_temp [T][B] (float): device memory,
+ * indexed like `starts` (ring rows), owned by the caller for the plan's life.  Row f holds what an utterance that begins at
+ * big frame f draws with.  The plan keeps one entry {seed, off, temperature} per stream: a run with resume = 0 sets every
+ * entry from row 1 with off = 0 (the stream's first utterance has its prefix in slot 0); a start flagged at (f, b) sets
+ * entry b from row f with off = the run index (draw origin + index in the buffer) of the first sample of slot f - 1; a
+ * resumed segment leaves the entries alone.  The draw of buffer index t in stream b then hashes
+ * seed_b ^ K1 (origin + t - off_b + 1) -- the counter is the sample's index in the utterance's own buffer, prefix included,
+ * and there is no stream term -- through the same finaliser and the same float32 inverse-CDF arithmetic as the default
+ * key, with temperature_b (<= 0: argmax, lowest index on ties) in place of the descriptor's.  With off = 0 and
+ * seed_b = s ^ K2 (b + 1) that is the default draw of plan seed s, bit for bit (K1 = 0x9E3779B97F4A7C15,
+ * K2 = 0xBF58476D1CE4E5B9).  An utterance's samples then depend on the model, the plan's shape, the carrying stream and
+ * the utterance's features, seed and temperature -- not on its slot, the segment boundaries or its neighbours.
+ * PARROT_ERR_BADARG for a null plan or pointer (checked before any device call) and for a plan that has run: the period
+ * graphs hold the pointers by value. */
+int samplernn_generate_set_utterance_draws(void* plan, const unsigned long long* utt_seed, const float* utt_temp);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

@@ -258,6 +258,7 @@ SIGNATURES = {
     "samplernn_generate_create": (_i, [C.POINTER(SampleRnnGenDesc), C.POINTER(C.c_void_p)]),
     "samplernn_generate_run": (_i, [_vp, _vp]),
     "samplernn_generate_run_segment": (_i, [_vp, _i, _i, _vp]),
+    "samplernn_generate_set_utterance_draws": (_i, [_vp, _vp, _vp]),
     "samplernn_persist_floats": (C.c_longlong, [C.POINTER(SampleRnnGenDesc)]),
     "samplernn_generate_is_persistent": (_i, [_vp]),
     "samplernn_generate_persist_groups": (_i, [_vp]),

@@ -62,12 +62,17 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 // temperature-scaled multinomial draw from a counter-based generator when temperature > 0.
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
-                                                      unsigned long long seed, const unsigned long long* __restrict__ origin) {
+                                                      unsigned long long seed, const unsigned long long* __restrict__ origin,
+                                                      const SrUttDraw* __restrict__ utt) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int t = tbase[0] + toff;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* lg = logits + (size_t)b * Q;
+    // key = what the draw's counter is hashed with: the plan's seed and the stream, or (per-utterance entries, a uniform
+    // branch) the utterance's seed alone, with its own temperature and its counter taken back by the run index of its prefix
+    unsigned long long key = seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1)), off = 0;
+    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; }
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int q = tid; q < Q; q += 256) {
@@ -94,8 +99,7 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
         float tot = 0.f;
         for (int q = 0; q < Q; ++q) tot += expf((lg[q] - mx) / temperature);
         // (keyed by the sample's index in the whole run: the draw origin counts what resumed segments have moved past)
-        unsigned long long x = seed ^ (0x9E3779B97F4A7C15ull * (origin[0] + (unsigned long long)(t + 1))) ^
-                               (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
+        unsigned long long x = key ^ (0x9E3779B97F4A7C15ull * (origin[0] + (unsigned long long)(t + 1) - off));
         x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;  // splitmix64
         const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
         float c = 0.f;
@@ -146,13 +150,27 @@ __global__ void sr_tick_kernel(int* tbase, int inc, int set, unsigned long long*
     }
 }
 
+// Per-utterance draws at the start of a run that does not resume: every stream's first utterance has its prefix in slot 0,
+// so entry b = (row 1 of the caller's arrays, off 0).  Outside the period graphs, beside the sr_tick_kernel call that sets
+// tbase; a start flagged at frame 1 then rewrites the same values.
+__global__ __launch_bounds__(256) void sr_utt_init_kernel(SrUttDraw* __restrict__ utt, const unsigned long long* __restrict__ seed1,
+                                                          const float* __restrict__ temp1, int B) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    utt[b].seed = seed1[b];
+    utt[b].off = 0;
+    utt[b].temperature = temp1[b];
+    utt[b].pad = 0;
+}
+
 // Segment boundary of a resumed run (samplernn_generate_run_segment, resume = 1): the first launch of the segment, outside
 // the period graphs.  The plan's buffer is a ring of T slots: the last slot the previous run wrote, tbase / BFS - 1 whatever
 // its length was, becomes slot 0 of every stream (the only history a period reads), tbase goes back to BFS, and the draw
 // origin moves on by the samples the ring has turned past, so that a seeded draw stays keyed by the sample's index in the
 // whole run.  The sample kernel's carry holds that slot's last samples and their table sums, keyed by the sample index
 // they were left for: the blocks with the key of the old tbase are re-keyed to BFS (the next launch takes them as it
-// does inside a run), any other block is invalidated.  One workgroup: every thread has read tbase before it is rewritten.
+// does inside a run), any other block is invalidated.  The per-utterance draw entries stay as they are: their `off` is a
+// run index, and origin + t does not change when the ring turns.  One workgroup: every thread has read tbase before it is rewritten.
 struct SrResumeArgs {
     int* tbase; int* samples; unsigned long long* origin;
     int B, T, BFS, len;
@@ -183,8 +201,9 @@ __global__ __launch_bounds__(256) void sr_resume_kernel(const SrResumeArgs a) {
 // starts[f][b], f = the big frame this period generates; a flagged stream gets what the first period of a run of its own
 // finds -- slot f - 1 = Q/2 (all three levels read their history from `samples`), every state that outlives a period =
 // the learned h0, its row of the next frame's gate product = h0 . Wg (the copy run() kept), and the carry of its team
-// invalidated (the other rows of the team then read their true history from `samples` too).  Rows without a flag are
-// not touched.
+// invalidated (the other rows of the team then read their true history from `samples` too).  With per-utterance draws
+// the stream's entry becomes (utt_seed[f][b], run index of the prefix slot = origin + (f - 1) BFS, utt_temp[f][b]).  Rows
+// without a flag are not touched.
 struct SrStartArgs {
     const int* starts; const int* tbase;
     int* samples;
@@ -193,6 +212,9 @@ struct SrStartArgs {
     float* state[20]; const float* h0[20];
     float* gpre; const float* gpre0;  // [B][2D] both (null: no such product on this path)
     SrpCarryKeys carry;
+    SrUttDraw* utt;                   // [B] per-utterance draw entries (null: none)
+    const unsigned long long* utt_seed; const float* utt_temp;  // [T][B] both, indexed like starts
+    const unsigned long long* origin;
 };
 
 __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
@@ -204,6 +226,11 @@ __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
     if (a.gpre)
         for (int i = tid; i < 2 * a.D; i += 256) a.gpre[(size_t)b * 2 * a.D + i] = a.gpre0[(size_t)b * 2 * a.D + i];
     if (a.carry.key0 && tid == 0) srp_carry_invalidate(a.carry, b);
+    if (a.utt && tid == 0) {
+        a.utt[b].seed = a.utt_seed[(size_t)f * a.B + b];
+        a.utt[b].off = a.origin[0] + (unsigned long long)(f - 1) * (unsigned long long)a.BFS;
+        a.utt[b].temperature = a.utt_temp[(size_t)f * a.B + b];
+    }
 }
 
 #define SR_TRY(x)                 \
@@ -243,6 +270,19 @@ struct SrPlan {
     // the seeded draw of buffer index t is keyed by origin + t.  A device word because the periods replay from graphs.
     unsigned long long* origin = nullptr;
     bool has_run = false;  // a run has been issued: resume = 1 has something to continue
+    // Per-utterance draws (samplernn_generate_set_utterance_draws): [B] entries owned by the plan, allocated by the setter
+    // (outside stream capture, like origin), and the caller's [T][B] arrays.  Null: the plan's key and temperature.
+    SrUttDraw* utt = nullptr;
+    const unsigned long long* utt_seed = nullptr;
+    const float* utt_temp = nullptr;
+    int set_utt(const unsigned long long* seed, const float* temp) {
+        if (!utt) {
+            if (hipMalloc(&utt, (size_t)d.B * sizeof(SrUttDraw)) != hipSuccess) { utt = nullptr; return (int)hipErrorOutOfMemory; }
+            PH_CHECK(hipMemset(utt, 0, (size_t)d.B * sizeof(SrUttDraw)));
+        }
+        utt_seed = seed; utt_temp = temp;
+        return 0;
+    }
     int make_origin() {
         if (hipMalloc(&origin, sizeof(unsigned long long)) != hipSuccess) { origin = nullptr; return 1; }
         return (int)hipMemset(origin, 0, sizeof(unsigned long long));
@@ -325,6 +365,7 @@ struct SrPlan {
         if (t2tbl) (void)hipFree(t2tbl);
         if (winu) (void)hipFree(winu);
         if (origin) (void)hipFree(origin);
+        if (utt) (void)hipFree(utt);
     }
 
     int linear(const float* A, int lda, const float* W, int ldw, int K, int N, const float* bias, const float* add,
@@ -459,6 +500,7 @@ struct SrPlan {
         }
         if (persist && winu) { a.gpre = gpre; a.gpre0 = gpre0; }
         if (persist) a.carry = srp_carry_keys(d.persist_ws, d.D, d.Q, groups);
+        a.utt = utt; a.utt_seed = utt_seed; a.utt_temp = utt_temp; a.origin = origin;
         hipLaunchKernelGGL(sr_start_kernel, dim3(d.B), dim3(256), 0, st, a);
         return (int)hipGetLastError();
     }
@@ -563,7 +605,7 @@ struct SrPlan {
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
-                sa.origin = origin;
+                sa.origin = origin; sa.utt = utt;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -588,7 +630,7 @@ struct SrPlan {
                 SR_TRY(linear(d.o2, D, d.W3, D, D, D, d.b3, nullptr, 0, d.o3, D, SK_ACT_RELU, st));
                 SR_TRY(linear(d.o3, D, d.W4, d.Q, D, d.Q, d.b4, nullptr, 0, d.logits, d.Q, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
-                                   d.temperature, d.seed, (const unsigned long long*)origin);
+                                   d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt);
             }
         }
         hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
@@ -615,6 +657,12 @@ struct SrPlan {
             hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, d.BFS, 1, origin);
             e = hipGetLastError();
             if (e != hipSuccess) return (int)e;
+            if (utt) {  // every stream's first utterance: row 1 of the caller's arrays, prefix in slot 0
+                hipLaunchKernelGGL(sr_utt_init_kernel, dim3(ceil_div(d.B, 256)), dim3(256), 0, st, utt, utt_seed + d.B,
+                                   utt_temp + d.B, d.B);
+                e = hipGetLastError();
+                if (e != hipSuccess) return (int)e;
+            }
             if (persist && winu)  // h0 . Wg: the gates' recurrent product of the very first frame (see period())
                 SR_TRY(linear(d.frm_h, d.D, d.frm_Wg, 2 * d.D, d.D, 2 * d.D, nullptr, nullptr, 0, gpre, 2 * d.D, 0, st, nullptr, 0,
                               nullptr, 0, t_frm.Wg));
@@ -727,6 +775,15 @@ int samplernn_generate_run_segment(void* plan, int n_periods, int resume, void* 
     const int rc = p->run(n_periods, resume != 0, (hipStream_t)stream);
     if (rc != 0 && p->last_error == 0) p->last_error = rc;
     return rc;
+}
+
+// (the argument checks in front of any HIP call, PH_ENTRY's included: they are testable on a machine without a device)
+int samplernn_generate_set_utterance_draws(void* plan, const unsigned long long* utt_seed, const float* utt_temp) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !utt_seed || !utt_temp) return PARROT_ERR_BADARG;
+    if (p->has_run) return PARROT_ERR_BADARG;  // the period graphs hold the pointers by value
+    PH_ENTRY();
+    return p->set_utt(utt_seed, utt_temp);
 }
 
 int samplernn_generate_run(void* plan, void* stream) {

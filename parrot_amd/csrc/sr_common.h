@@ -63,7 +63,12 @@ struct SrpShared {
     int ok;
     int hist[SRP_ROWS][SRP_MAXHIST];
     float mx[SRP_ROWS];
+    // per-utterance draw entries of the group's rows (SrpArgs::utt; unused without): parked here, not in registers
+    float utemp[SRP_ROWS];
+    int upad;
+    unsigned long long useed[SRP_ROWS], uoff[SRP_ROWS];
 };
+static_assert(sizeof(SrpShared) % 8 == 0, "SrpShared holds 64-bit words");
 
 // Load a hand-off slot, re-reading until it is full (bounded: ~1 s, then the abort word is raised).
 __device__ __forceinline__ f32x4 srp_take(__amdgpu_buffer_rsrc_t r, unsigned byte_off, unsigned* abort_, SrpShared* sh) {

@@ -3,6 +3,15 @@
 #pragma once
 #include "common.h"
 
+// Per-utterance draws (samplernn_generate_set_utterance_draws): one entry per stream, owned by the plan.  With the
+// entries in force the seeded draw of buffer index t in stream b hashes seed ^ K1 (origin + t - off + 1) -- no stream
+// term --, where off is the run index (origin + buffer index) of the first sample of the utterance's Q/2 prefix slot: the
+// counter is the sample's index in the utterance's own buffer, wherever the utterance sits.  temperature <= 0: argmax.
+struct SrUttDraw {
+    unsigned long long seed, off;
+    float temperature; int pad;
+};
+
 struct SrpArgs {
     const int* tbase; int toff;        // first sample index of this launch: tbase[0] + toff
     int* samples; int len;             // [B][len] sample history (read: the FS samples before t0; written: t0 .. t0+nsteps-1)
@@ -32,6 +41,9 @@ struct SrpArgs {
     // Draw origin (device word, required): the seeded draw of sample index t is keyed by origin[0] + t -- 0 in a run of one
     // piece; a resumed segment (samplernn.hip, sr_resume_kernel) counts the samples the ring has turned past in it.
     const unsigned long long* origin;
+    // Per-utterance draws: [B] entries, or null = the plan's key (seed, stream) and temperature above.  Wave r picks for
+    // row srow + r, so its entry is wave-uniform: fetched once per launch and row group into the shared block.
+    const SrUttDraw* utt;
 };
 
 // PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8

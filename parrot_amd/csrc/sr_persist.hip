@@ -221,6 +221,17 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                 gather_sum(0);
             }
         }
+        // Per-utterance draws: wave r picks for row srow + r, so it parks that row's entry in the shared block (rows past B:
+        // the entry of row B - 1, like every other per-row load here), once per launch and row group -- through the scalar
+        // cache like tbase and the draw origin, beside the vector queue.  The branch is uniform; without entries, no code runs.
+        if (a.utt && wave < SRP_ROWS) {
+            const int rw = __builtin_amdgcn_readfirstlane(wave);
+            const unsigned long long ea = (unsigned long long)(a.utt + min(srow + rw, a.B - 1));
+            typedef const float __attribute__((address_space(4))) * srp_cfloat;
+            const unsigned long long es = *(srp_cull)ea, eo = *(srp_cull)(ea + 8);
+            const float et = *(srp_cfloat)(ea + 16);
+            if (lane == 0) { sh->useed[rw] = es; sh->uoff[rw] = eo; sh->utemp[rw] = et; }
+        }
         __syncthreads();
         take_part();
         if (timing) stamps[81] = srp_clock();
@@ -292,17 +303,23 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                 float best;
                 const int bi = srp_argmax_row<Q>(lg, r, lane, best);
                 int pick = bi;
-                if (a.temperature > 0.f) {
+                // (the row's own temperature with per-utterance entries: rows of one team may mix argmax and draws)
+                const float temperature = a.utt ? sh->utemp[r] : a.temperature;
+                if (temperature > 0.f) {
 #pragma unroll
-                    for (int m = 0; m < Q / 64; ++m) ev[r * Q + lane + 64 * m] = expf((lg[lane + 64 * m][r] - best) / a.temperature);
+                    for (int m = 0; m < Q / 64; ++m) ev[r * Q + lane + 64 * m] = expf((lg[lane + 64 * m][r] - best) / temperature);
                     __builtin_amdgcn_wave_barrier();
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                     if (lane == 0) {
                         const int b = srow + r;
                         float tot = 0.f;
                         for (int q = 0; q < Q; ++q) tot += ev[r * Q + q];
-                        unsigned long long x = a.seed ^ (0x9E3779B97F4A7C15ull * (draw0 + (unsigned long long)(t + 1))) ^
-                                               (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
+                        // key = what the counter is hashed with: the plan's seed and the stream, or the utterance's seed alone,
+                        // its counter taken back by the run index of the utterance's prefix slot
+                        unsigned long long key = a.seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
+                        unsigned long long ctr = draw0 + (unsigned long long)(t + 1);
+                        if (a.utt) { key = sh->useed[r]; ctr -= sh->uoff[r]; }
+                        unsigned long long x = key ^ (0x9E3779B97F4A7C15ull * ctr);
                         x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
                         const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
                         float c = 0.f;

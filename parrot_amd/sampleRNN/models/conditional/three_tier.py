@@ -194,19 +194,63 @@ def getting_generation_functions(sequences=None, h0=None, big_h0=None, reset=Non
     return big_fn, frame_fn, sample_fn
 
 
+_M64 = (1 << 64) - 1
+DRAW_K1, DRAW_K2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9
+
+
+def _splitmix64(x):
+    """The splitmix64 finaliser, in Python integers masked to 64 bits."""
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def utterance_draw_u01(seed, n):
+    """The uniform an utterance with seed `seed` draws at counter n = the sample's index in the utterance's own buffer,
+    prefix included (the first generated sample has n = BIG_FRAME_SIZE): seed ^ K1 (n + 1) through the splitmix64
+    finaliser; the top 24 bits plus one half, rounded to float32, times 2^-24.  What sr_pick_kernel and the pick of
+    srp_kernel compute with per-utterance draws (samplernn_generate_set_utterance_draws); no stream term."""
+    x = _splitmix64((int(seed) & _M64) ^ ((DRAW_K1 * (int(n) + 1)) & _M64))
+    return float(numpy.float32(float(x >> 40) + 0.5)) / 2.0 ** 24
+
+
+def utterance_seed(seed, index):
+    """One 64-bit seed per utterance from a base seed: seed + K1 (index + 1) through the splitmix64 finaliser."""
+    return _splitmix64(((int(seed) & _M64) + DRAW_K1 * (int(index) + 1)) & _M64)
+
+
+_derive_seed = utterance_seed  # (generate_and_save_samples has an argument of that name)
+
+
+def _seed_image(seeds):
+    """Unsigned 64-bit seeds (Python integers or any integer array) as their two's-complement int64 image."""
+    flat = [int(s) & _M64 for s in numpy.asarray(seeds, dtype=object).reshape(-1)]
+    return numpy.array(flat, dtype=numpy.uint64).reshape(numpy.shape(seeds)).view(numpy.int64)
+
+
 class DeviceGenerator:
     """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
 
-    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False):
+    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
         three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
 
         packed=True: the plan takes per-stream utterance starts (SampleRnnGenDesc::starts): generate(features, starts)
-        then begins a new utterance in stream b at big frame f wherever starts[f][b] != 0 (see generate_packed)."""
+        then begins a new utterance in stream b at big frame f wherever starts[f][b] != 0 (see generate_packed).
+
+        utterance_draws=True: every utterance draws with a seed and a temperature of its own
+        (samplernn_generate_set_utterance_draws): generate(..., seeds=, temperatures=) takes them, aligned with starts on a
+        packed plan, one per stream on a plain one; the plan's temperature and seed are then not used.  An utterance's
+        samples are then a function of the model, the plan's shape, the carrying stream, and the utterance's features,
+        seed and temperature (utterance_draw_u01 is the uniform of its n-th sample): they do not depend on its slot, the
+        segment boundaries or its neighbours."""
         if SKIP_CONN:
             raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
         self.B, self.T = batch, n_frames
         self.packed = bool(packed)
+        self.utterance_draws = bool(utterance_draws)
         dev = lib.device()
         f = dict(device=dev, dtype=torch.float32)
         D, FS, BFS, Q = DIM, FRAME_SIZE, BIG_FRAME_SIZE, Q_LEVELS
@@ -297,8 +341,19 @@ class DeviceGenerator:
         # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
         self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
         self._has_run = False
+        if self.utterance_draws:
+            # [T, B] like starts (ring rows): row f = what an utterance that begins at big frame f draws with; utt_seed is the
+            # two's-complement image of the unsigned 64-bit seed
+            self.ws['utt_seed'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int64)
+            self.ws['utt_temp'] = torch.zeros(n_frames, batch, **f)
+            self.set_utterance_draws()
 
-    def generate(self, features, starts=None, resume=False, n_frames=None):
+    def set_utterance_draws(self):
+        """Hands the plan its per-utterance seed and temperature arrays; refused (HipCallError) once the plan has run."""
+        _lib.call('samplernn_generate_set_utterance_draws', self.plan, self.ws['utt_seed'].data_ptr(),
+                  self.ws['utt_temp'].data_ptr())
+
+    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
         frame f, whose Q/2 prefix is slot f - 1.
@@ -308,10 +363,20 @@ class DeviceGenerator:
         samples come back, prefix included.  resume=True continues the run of the last call from the states where they
         stand: features (and starts) hold k rows, for slots 1 .. k of the ring -- slot 0 is the last slot of the call
         before --, nothing is re-initialised and the [B, 80 k] samples of this segment come back (a copy: the next
-        segment overwrites the ring).  The segments of a run equal the run in one piece, seeded draws included."""
+        segment overwrites the ring).  The segments of a run equal the run in one piece, seeded draws included.
+
+        seeds / temperatures (plans built with utterance_draws=True only, and both required there): on a packed plan
+        [rows, B] aligned with starts -- row f, stream b holds what the utterance that starts[f][b] flags draws with, and the
+        row of slot 1 of a run that does not resume what every stream's first utterance draws with --; on a plain plan [B],
+        one utterance per stream, with resume=False only (the segments that resume go on with them).  Seeds are unsigned
+        64-bit integers (Python integers or an integer array)."""
         if (starts is not None) != self.packed:
             raise ValueError("starts must be given exactly when the plan was built with packed=True")
         resume = bool(resume)
+        takes_draws = self.utterance_draws and (self.packed or not resume)
+        if (seeds is not None) != takes_draws or (temperatures is not None) != takes_draws:
+            raise ValueError("seeds and temperatures must both be given exactly when the plan was built with "
+                             "utterance_draws=True (a plain plan takes them with resume=False only)")
         if resume and not self._has_run:
             raise ValueError("resume=True needs a run to continue: call generate(..., resume=False) first")
         segment = resume or n_frames is not None
@@ -330,6 +395,17 @@ class DeviceGenerator:
                 raise ValueError("starts must be [%s, B] = [%d, %d], got %s" % ("T" if not segment else "rows", rows, self.B,
                                                                                  tuple(st.shape)))
             ws['starts'][first:first + rows].copy_((st != 0).to(ws['starts'].device, torch.int32))
+        if takes_draws:
+            want = (rows, self.B) if self.packed else (self.B,)
+            sd = _seed_image(seeds)
+            tp = numpy.broadcast_to(numpy.asarray(temperatures, dtype='float32'), want) if numpy.ndim(temperatures) == 0 \
+                else numpy.asarray(temperatures, dtype='float32')
+            if sd.shape != want or tp.shape != want:
+                raise ValueError("seeds and temperatures must be %s, got %s and %s" % (list(want), sd.shape, tp.shape))
+            # (a plain plan: one utterance per stream, prefix in slot 0 -- the row of slot 1, like a start flagged there)
+            lo, hi = (first, first + rows) if self.packed else (1, 2)
+            ws['utt_seed'][lo:hi].copy_(torch.from_numpy(sd.reshape(hi - lo, self.B)).to(ws['utt_seed'].device))
+            ws['utt_temp'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tp).reshape(hi - lo, self.B)).to(ws['utt_temp'].device))
         if not segment:
             ws['features'].copy_(feats.to(ws['features'].device, torch.float32))
         else:
@@ -407,24 +483,67 @@ def build_packed_inputs(utterances, stream, first_slot, T, n_streams):
     return features, starts
 
 
-def generate_packed(utterances, n_streams=32, temperature=TEMPERATURE, seed=234, use_graph=True):
+def build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams):
+    """(utt_seed [T, n_streams] uint64, utt_temp [T, n_streams] float32) of a packing, the sibling of build_packed_inputs:
+    utterance i's seed and temperature on the row of its start flag, first_slot[i] + 1 of stream[i], wherever that row is
+    below T (an utterance that is its prefix alone in the last slot draws nothing); zeros elsewhere."""
+    utt_seed = numpy.zeros((T, n_streams), dtype=numpy.uint64)
+    utt_temp = numpy.zeros((T, n_streams), dtype='float32')
+    for sd, tp, b, s in zip(seeds, temperatures, stream, first_slot):
+        if not (0 <= b < n_streams and 0 <= s < T):
+            raise ValueError("no slot %d in stream %d" % (s, b))
+        if s + 1 < T:
+            utt_seed[s + 1, b] = int(sd) & _M64
+            utt_temp[s + 1, b] = tp
+    return utt_seed, utt_temp
+
+
+def _per_utterance(seeds, temperatures, n, default_temperature):
+    """seeds: one per utterance; temperatures: one per utterance, a scalar, or None = default_temperature."""
+    seeds = [int(s) & _M64 for s in seeds]
+    if temperatures is None:
+        temperatures = default_temperature
+    temperatures = [float(temperatures)] * n if numpy.ndim(temperatures) == 0 else [float(t) for t in temperatures]
+    if len(seeds) != n or len(temperatures) != n:
+        raise ValueError("%d utterances, but %d seeds and %d temperatures" % (n, len(seeds), len(temperatures)))
+    return seeds, temperatures
+
+
+def generate_packed(utterances, n_streams=32, temperature=TEMPERATURE, seed=234, use_graph=True, seeds=None,
+                    temperatures=None):
     """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
     utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
     n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
 
     At temperature = 0 element i equals what DeviceGenerator returns for that utterance generated on its own.  At
-    temperature > 0 the draws are seeded and repeatable, but they are keyed by the packed (sample index, stream) of the
-    run, so they are NOT the draws of the utterance's standalone run."""
+    temperature > 0 without `seeds` the draws are seeded and repeatable, but they are keyed by the packed (sample index,
+    stream) of the run, so they are NOT the draws of the utterance's standalone run.
+
+    seeds = one unsigned 64-bit seed per utterance (temperatures = one temperature per utterance or a scalar; default:
+    `temperature` for all): the plan runs with per-utterance draws (DeviceGenerator(utterance_draws=True)).  Element i is
+    then a function of the model, the plan's shape (n_streams), the carrying stream, and the utterance's features, seed
+    and temperature: it equals, bit for bit, what a plain plan of n_streams streams in that mode returns for the utterance
+    carried alone in the same stream with the same seed and temperature, and does not depend on its slot, the order of
+    the list or its neighbours.  (The carrying stream is pack_utterances' choice, which does depend on the list.)"""
     if SKIP_CONN:
         raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
     utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
+    if seeds is None and temperatures is not None:
+        raise ValueError("temperatures per utterance need seeds per utterance")
+    if seeds is not None:  # (before a plan is created)
+        seeds, temperatures = _per_utterance(seeds, temperatures, len(utterances), temperature)
     if not utterances:
         return []
     stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
     features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
-    gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True)
+    gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
+                          utterance_draws=seeds is not None)
     try:
-        samples = gen.generate(features, starts).cpu().numpy()
+        if seeds is not None:
+            utt_seed, utt_temp = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
+            samples = gen.generate(features, starts, seeds=utt_seed, temperatures=utt_temp).cpu().numpy()
+        else:
+            samples = gen.generate(features, starts).cpu().numpy()
     finally:
         gen.close()
     return unpack_samples(samples, [u.shape[0] for u in utterances], stream, first_slot)
@@ -536,13 +655,22 @@ class StreamingGenerator:
 
     The first 80 samples of an utterance's first chunk are its Q/2 prefix.  At temperature = 0 the concatenated chunks of
     an utterance equal what a plain plan of n_streams returns for it carried in the same stream (record[ticket] =
-    (stream, absolute slot of its prefix)); at temperature > 0 the draws are repeatable for the same sequence of
-    submit / step calls, but they are not the draws of the utterance's standalone run.
+    (stream, absolute slot of its prefix)); at temperature > 0 without utterance_draws the draws are repeatable for the
+    same sequence of submit / step calls, but they are not the draws of the utterance's standalone run.
+
+    utterance_draws=True: submit takes the utterance's seed (required) and temperature (default: the generator's).  The
+    concatenated chunks of an utterance are then a function of the model, the plan's shape (n_streams; segment_frames does
+    not enter), the carrying stream, and the utterance's features, seed and temperature: they equal, bit for bit, what a
+    plain plan of n_streams streams in that mode returns for the utterance carried alone in stream record[ticket][0] with
+    the same seed and temperature, and do not depend on its slot, the segment boundaries, the submission order or its
+    neighbours.  (Which stream carries it is schedule_segment's choice, and that does depend on the traffic.)
 
     run_segment(features [n, B, 63], starts [n, B], resume) -> samples [B, 80 n] of slots 1 .. n is the callable that
-    runs a segment; the default runs it on the device."""
+    runs a segment; the default runs it on the device.  With utterance_draws it is called with two more keyword arguments,
+    seeds [n, B] uint64 and temperatures [n, B] float32: what the utterance whose start flag is on that row draws with."""
 
-    def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None):
+    def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
+                 utterance_draws=False):
         if SKIP_CONN:
             raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
         self.B, self.S = int(n_streams), int(segment_frames)
@@ -551,9 +679,11 @@ class StreamingGenerator:
         if self.S < 1:
             raise ValueError("segment_frames must be at least 1")
         self.gen = None
+        self.utterance_draws = bool(utterance_draws)
+        self.temperature = float(temperature)
         if run_segment is None:
             self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
-                                       packed=True)
+                                       packed=True, utterance_draws=self.utterance_draws)
             run_segment = self._run_on_device
         self._run = run_segment
         self._resume = False
@@ -562,23 +692,33 @@ class StreamingGenerator:
         self.running = [None] * self.B
         self.queue = []
         self._features = {}
+        self._draws = {}               # ticket -> (seed, temperature), until the utterance's start flag has been placed
         self.record = {}
 
-    def _run_on_device(self, features, starts, resume):
+    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None):
+        draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
         if resume:
-            return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0]).cpu().numpy()
+            return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0], **draws).cpu().numpy()
         n = features.shape[0]  # the first segment: slot 0 is the run's prefix slot, no stream uses it
         features = numpy.concatenate([numpy.zeros_like(features[:1]), features])
         starts = numpy.concatenate([numpy.zeros_like(starts[:1]), starts])
-        return self.gen.generate(features, starts, n_frames=n).cpu().numpy()[:, BIG_FRAME_SIZE:]
+        draws = {k: numpy.concatenate([numpy.zeros_like(v[:1]), v]) for k, v in draws.items()}
+        return self.gen.generate(features, starts, n_frames=n, **draws).cpu().numpy()[:, BIG_FRAME_SIZE:]
 
-    def submit(self, features):
-        """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order."""
+    def submit(self, features, seed=None, temperature=None):
+        """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
+        seed (an unsigned 64-bit integer) and temperature (default: the generator's): with utterance_draws=True only, where
+        the seed is required."""
+        if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
+            raise ValueError("a seed (and a temperature) per utterance is given exactly when the generator was built with "
+                             "utterance_draws=True")
         features = numpy.asarray(features, dtype='float32')
         if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != FEAT_DIM:
             raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (FEAT_DIM, features.shape))
         ticket = self._next_ticket
         self._next_ticket += 1
+        if self.utterance_draws:
+            self._draws[ticket] = (int(seed) & _M64, self.temperature if temperature is None else float(temperature))
         self._features[ticket] = features
         self.queue.append((ticket, features.shape[0]))
         return ticket
@@ -599,7 +739,18 @@ class StreamingGenerator:
                 self.record[ticket] = (b, self._slots_run + slot)
         for slot, b in starts:
             flags[slot - 1, b] = 1
-        samples = numpy.asarray(self._run(feats, flags, self._resume))
+        draws = {}
+        if self.utterance_draws:
+            # on the row of the utterance's start flag: the slot of its frame 1, in the segment that holds that frame even
+            # when its prefix was the last slot of the segment before
+            draws = dict(seeds=numpy.zeros((n, self.B), dtype=numpy.uint64),
+                         temperatures=numpy.zeros((n, self.B), dtype='float32'))
+            for ticket, b, slot, frame, count in placements:
+                if frame <= 1 < frame + count:
+                    row = slot - frame  # = (slot + 1 - frame) - 1
+                    assert flags[row, b] == 1
+                    draws['seeds'][row, b], draws['temperatures'][row, b] = self._draws[ticket]
+        samples = numpy.asarray(self._run(feats, flags, self._resume, **draws))
         if samples.shape != (self.B, BIG_FRAME_SIZE * n):
             raise ValueError("the segment runner returned %s, not %s" % (samples.shape, (self.B, BIG_FRAME_SIZE * n)))
         self._resume = True
@@ -612,6 +763,7 @@ class StreamingGenerator:
             done = frame + count == self._features[ticket].shape[0]
             if done:
                 del self._features[ticket]
+                self._draws.pop(ticket, None)
             out.append((ticket, chunk, done))
         return out
 
@@ -642,7 +794,7 @@ def write_audio_file(name, data, path_to_save):
 def generate_and_save_samples(tag, path_to_save=None, features=None, features_length=None, noise_level=0.,
                               big_frame_level_generate_fn=None, frame_level_generate_fn=None,
                               sample_level_generate_fn=None, npy_address=None, temperature=TEMPERATURE,
-                              use_device_loop=True, pack_streams=0, stream_frames=0):
+                              use_device_loop=True, pack_streams=0, stream_frames=0, utterance_seed=None):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
     (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.
 
@@ -652,8 +804,15 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
 
     stream_frames = S > 0 with features_length given: the utterances go through a StreamingGenerator of
     pack_streams or 32 streams in segments of S frames; each wav is written as soon as its utterance has finished, and
-    the return value is the list of pieces as above."""
+    the return value is the list of pieces as above.
+
+    utterance_seed = S (an integer; None: off): utterance i draws with the seed utterance_seed(S, i) of its own at
+    `temperature`, in the rectangle, packed and streamed modes alike (DeviceGenerator(utterance_draws=True)): its samples
+    no longer depend on where it was placed.  Device loop only."""
     total_time = time()
+    per_utt = utterance_seed is not None
+    if per_utt and not (use_device_loop and not SKIP_CONN):
+        raise ValueError("utterance_seed needs the device-resident generator")
     if npy_address is not None:
         test_feats = numpy.load(npy_address).astype('float32')  # [T,B,63]
     else:
@@ -666,12 +825,13 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         n_streams = int(pack_streams) if pack_streams > 0 else 32
         if path_to_save is not None:
             os.makedirs(path_to_save, exist_ok=True)
-        sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature)
+        sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature, utterance_draws=per_utt)
         chunks = [[] for _ in range(n_seqs)]
         pieces = [None] * n_seqs
         try:
             for i in range(n_seqs):
-                assert sg.submit(test_feats[:lens[i], i]) == i
+                draws = dict(seed=_derive_seed(utterance_seed, i)) if per_utt else {}
+                assert sg.submit(test_feats[:lens[i], i], **draws) == i
             while not sg.idle():
                 for i, chunk, done in sg.step():
                     chunks[i].append(chunk)
@@ -691,8 +851,9 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         return pieces
     if pack_streams > 0 and features_length is not None:
         lens = [min(max(int(n), 1), n_frames) for n in features_length]
+        seeds = [_derive_seed(utterance_seed, i) for i in range(n_seqs)] if per_utt else None
         pieces = generate_packed([test_feats[:lens[i], i] for i in range(n_seqs)], n_streams=int(pack_streams),
-                                 temperature=temperature)
+                                 temperature=temperature, seeds=seeds)
         total_time = time() - total_time
         print("{} samples of {} seconds in all generated in {} seconds ({} packed streams).".format(
             n_seqs, sum(lens) * BIG_FRAME_SIZE / float(BITRATE), total_time, int(pack_streams)))
@@ -704,8 +865,10 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
                 write_audio_file("sample_{}_{}".format(tag, i), samp, path_to_save)
         return pieces
     if use_device_loop and not SKIP_CONN:  # (the device loop does not take the skip-connection stacks: literal loop)
-        gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature)
-        samples = gen.generate(test_feats).cpu().numpy()
+        gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature, utterance_draws=per_utt)
+        draws = dict(seeds=[_derive_seed(utterance_seed, i) for i in range(n_seqs)],
+                     temperatures=float(temperature)) if per_utt else {}
+        samples = gen.generate(test_feats, **draws).cpu().numpy()
         gen.close()
     else:
         feats_bt = test_feats.transpose(1, 0, 2)

@@ -4,7 +4,8 @@ which any non-empty string is truthy.  Plotting / animation helpers (utils.py:30
 and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
---device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames.
+--device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames,
+--utterance_seed.
 """
 from __future__ import annotations
 
@@ -132,6 +133,11 @@ def sample_parse(argv=None):
                         help='S > 0 (with --raw_output): the SampleRNN vocoder runs the utterances through one plan of S + 1 '
                              'slots used as a ring, in segments of S frames on --pack_streams (or 32) streams, and writes '
                              'each wav as its utterance finishes (DESIGN.md 3.6); 0: one closed run')
+    parser.add_argument('--utterance_seed', type=int, default=-1,
+                        help='S >= 0 (with --raw_output): utterance i of the SampleRNN vocoder draws with a seed of its own, '
+                             'derived from S and i, in the rectangle, with --pack_streams and with --stream_frames alike: its '
+                             'samples do not depend on where it was placed (DESIGN.md 3.6); -1: the plan\'s seed and the '
+                             'stream key the draws')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:

@@ -8,7 +8,8 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
   bench_extra.py --only NAME[,NAME]      a subset (decode_cfg3, decode_stop, decode_lstm2_1024, decode_lstm3_1536,
                                          decode_gmm_gru2_1024, decode_gmm_lstm2_1024, decode_bf16_gru2_1024,
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
-                                         samplernn_cfg5, samplernn_groups, samplernn_packed, samplernn_stream, mulaw)
+                                         samplernn_cfg5, samplernn_groups, samplernn_packed, samplernn_stream,
+                                         samplernn_utt_draws, mulaw)
   bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
                                          SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
                                          kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
@@ -28,6 +29,14 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          copy of the samples and the synchronisation per segment; total time, us per sample
                                          step, the difference to the run in one piece per segment boundary, the time to the
                                          first chunk; the result also goes to FILE (default profiles/samplernn_stream.json)
+  bench_extra.py --only samplernn_utt_draws [--reps N] [--utt-draws-json FILE]
+                                         SampleRNN at D = 1024 and B = 32, 2000 samples per stream at temperature 1: the
+                                         plan's key against per-utterance entries (DeviceGenerator(utterance_draws=True),
+                                         with the seeds that reproduce the plan's key: bit identity is checked), and
+                                         temperature 0 beside them; then the 64 utterances of samplernn_packed on one packed
+                                         plan with temperatures 0 / 0.5 / 1 / 2 mixed inside every team against the same
+                                         packing at temperature 0 and at 1 with the plan's key; N alternations in one
+                                         process; the result also goes to FILE (default profiles/samplernn_utt_draws.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -52,7 +61,7 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "samplernn_packed", "samplernn_stream", "mulaw")
+       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -601,6 +610,75 @@ if "samplernn_stream" in only:
     out["samplernn_stream"] = res
     path = _arg("--stream-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                               "samplernn_stream.json"))
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+# ---- SampleRNN D=1024, B=32: per-utterance seeds and temperatures (samplernn_generate_set_utterance_draws) against the plan's
+# key at temperature 1 -- the same draws, bit for bit, with seeds[b] = seed ^ K2 (b + 1) --, and a packed run whose teams mix
+# arg-max rows with draws at 0.5 / 1 / 2.  All plans alive in one process and run alternately.
+if "samplernn_utt_draws" in only:
+    from parrot_amd.sampleRNN import lib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    lib.delete_all_params(); lib.set_device(dev)
+    tt.configure(DIM=1024, EMB_SIZE=256)
+    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+    with torch.no_grad():  # registers all parameters with the reference initialisation
+        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
+                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    B, T, SEED, reps = 32, 26, 234, int(_arg("--reps", "3"))
+    nsamp = (T - 1) * 80
+    feats = torch.randn(T, B, 63, generator=g).numpy()
+    key_seeds = [(SEED ^ (tt.DRAW_K2 * (b + 1))) & (2 ** 64 - 1) for b in range(B)]
+    N, LEN_SEED = 64, 1234  # the utterances of samplernn_packed
+    rs = np.random.RandomState(LEN_SEED)
+    lengths = [int(n) for n in rs.randint(20, 201, size=N)]
+    utts = [rs.randn(n, 63).astype(np.float32) for n in lengths]
+    stream, first, Tp = tt.pack_utterances(lengths, B)
+    pf, ps = tt.build_packed_inputs(utts, stream, first, Tp, B)
+    # utterance i draws at MIX[stream % 4]: the four rows of every team of the persistent kernel differ
+    MIX = (0.0, 0.5, 1.0, 2.0)
+    mixed = [MIX[stream[i] % 4] for i in range(N)]
+    useed, utemp = tt.build_packed_draws([tt.utterance_seed(SEED, i) for i in range(N)], mixed, stream, first, Tp, B)
+    gens = {"plan_key_t1": tt.DeviceGenerator(B, T, temperature=1.0, seed=SEED),
+            "utterance_draws_t1": tt.DeviceGenerator(B, T, utterance_draws=True),
+            "plan_key_t0": tt.DeviceGenerator(B, T, temperature=0.0),
+            "packed_t0": tt.DeviceGenerator(B, Tp, temperature=0.0, packed=True),
+            "packed_plan_key_t1": tt.DeviceGenerator(B, Tp, temperature=1.0, seed=SEED, packed=True),
+            "packed_mixed_temperatures": tt.DeviceGenerator(B, Tp, packed=True, utterance_draws=True)}
+    args = {"plan_key_t1": ((feats,), {}), "plan_key_t0": ((feats,), {}),
+            "utterance_draws_t1": ((feats,), dict(seeds=key_seeds, temperatures=1.0)),
+            "packed_t0": ((pf, ps), {}), "packed_plan_key_t1": ((pf, ps), {}),
+            "packed_mixed_temperatures": ((pf, ps), dict(seeds=useed, temperatures=utemp))}
+    assert all(gen.persistent for gen in gens.values())
+    times, samples = {k: [] for k in gens}, {}
+    keys = list(gens)
+    for rep in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+        for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:  # (no plan always runs behind the same other one)
+            torch.cuda.synchronize(); t0 = time.time()
+            s = gens[k].generate(*args[k][0], **args[k][1])
+            torch.cuda.synchronize(); dt = time.time() - t0
+            samples[k] = s.cpu().numpy().copy()
+            if rep:
+                times[k].append(dt)
+    steps = {k: (gens[k].T - 1) * 80 for k in gens}
+    for gen in gens.values():
+        gen.close()
+    pieces = {k: tt.unpack_samples(samples[k], lengths, stream, first) for k in ("packed_t0", "packed_mixed_temperatures")}
+    argmax_rows = [i for i in range(N) if mixed[i] == 0.0]
+    res = {"dim": 1024, "streams": B, "alternations": reps, "timed": "call to device idle (host-side input copies included)",
+           "runs": {k: {"sample_steps": steps[k], "ms": [round(1e3 * dt, 2) for dt in v],
+                        "us_per_sample_step": [round(1e6 * dt / steps[k], 3) for dt in v],
+                        "us_per_sample_step_median": round(1e6 * sorted(v)[len(v) // 2] / steps[k], 3)}
+                    for k, v in times.items()},
+           "utterance_draws_bit_identical_to_plan_key": bool(np.array_equal(samples["utterance_draws_t1"], samples["plan_key_t1"])),
+           "packed": {"utterances": N, "length_seed": LEN_SEED, "periods": Tp - 1, "temperatures_by_stream_mod_4": list(MIX),
+                      "argmax_utterances": len(argmax_rows),
+                      "argmax_utterances_equal_to_packed_t0": sum(int(np.array_equal(pieces["packed_mixed_temperatures"][i],
+                                                                                     pieces["packed_t0"][i])) for i in argmax_rows)}}
+    out["samplernn_utt_draws"] = res
+    path = _arg("--utt-draws-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                 "samplernn_utt_draws.json"))
     with open(path, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
