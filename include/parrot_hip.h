@@ -805,6 +805,23 @@ int samplernn_weightnorm_fold_bwd(const float* W, int ld, const float* g, const 
  * SampleLevel.L1_PrevSamples: emb_tbl[pos][q][:] = Embedding[q] . W1[pos*EMB:(pos+1)*EMB, :].
  * temperature = 0 -> argmax (softmax_and_argmax, ops.py:296-297; lowest index on ties);
  * temperature > 0 -> multinomial draw from a seeded counter-based generator (not Theano's MRG stream).
+ * draw_mode: how such a draw finds its code among the terms e_q = expf((logit_q - max) / temperature), on every path
+ * (launches, the persistent sample kernel, row groups, starts, resumed segments, per-utterance draws); both modes see the
+ * same uniforms u01, and argmax (temperature <= 0) is the same in both.
+ *   0 (sequential, the default; a zeroed field): one lane adds the Q terms one after the other in float32 -- once for the
+ *     total, once to find the first code with u01 * total < running sum.  The samples every earlier version drew.
+ *   1 (scan): one 64-lane wave; Q must be a multiple of 64 (PARROT_ERR_BADARG otherwise).  Lane l owns the n = Q / 64
+ *     contiguous codes n l + j and adds them left to right (p_l); an inclusive Hillis-Steele scan with offsets 1, 2, 4, 8
+ *     inside each row of 16 lanes gives w_l (a lane without a source adds nothing); the row totals T_k = w_{16k+15} are
+ *     chained R_0 = T_0, R_1 = R_0 + T_1, R_2 = R_1 + T_2 and s_l = w_l in row 0, R_{k-1} + w_l in row k; total = s_63,
+ *     u = u01 * total; l* = the lowest lane with u < s_l (none: the pick is Q - 1); inside l* the terms are added one at a
+ *     time to s_{l*-1} (0 for lane 0) and the first code with u < c is the pick (none: the lane's last code).  Every add
+ *     is one float32 addition in exactly this order, so the pick is a function of the logits, the temperature and u01
+ *     alone, the same on both kernel paths.  About 20 dependent operations instead of 2 Q; a sum has at most 14 roundings
+ *     behind it instead of Q, so the pick agrees with the exact CDF wherever u01 is further than 2^-17 from a boundary
+ *     (sequential: 2^-14), and terms below 2^-24 of the total are not lost.  A few draws per ten thousand differ from
+ *     mode 0's by one code.
+ *   Any other value: PARROT_ERR_BADARG.
  * samples: [B, BFS*T] int32, first BFS entries = Q/2 set by the caller; big_h / frm_h hold the
  * initial states (learned h0) on entry and the final states on return.  The weight buffers must not change during a
  * plan's life: create makes fragment-major copies of the tiers' matrices for the step kernel (single-GRU tiers) and, on the
@@ -815,7 +832,7 @@ int samplernn_weightnorm_fold_bwd(const float* W, int ld, const float* g, const 
  * ------------------------------------------------------------------------------------------ */
 typedef struct SampleRnnGenDesc {
     int B, D, T, Q, FS, BFS, feat_dim, use_graph;
-    float temperature; int reserved;
+    float temperature; int draw_mode;
     unsigned long long seed;
     const float* big_Win_frames; const float* big_Win_feats; const float* big_bin; /* [BFS,D],[feat,D],[D] */
     const float* big_U; const float* big_bU; const float* big_Wg; const float* big_Wc; /* [D,3D],[3D],[D,2D],[D,D] */

@@ -155,7 +155,7 @@ class SampleDesc(C.Structure):
 
 class SampleRnnGenDesc(C.Structure):
     _fields_ = ([(n, C.c_int) for n in ("B", "D", "T", "Q", "FS", "BFS", "feat_dim", "use_graph")] +
-                [("temperature", C.c_float), ("reserved", C.c_int), ("seed", C.c_ulonglong)] +
+                [("temperature", C.c_float), ("draw_mode", C.c_int), ("seed", C.c_ulonglong)] +
                 [(n, C.c_void_p) for n in (
                     "big_Win_frames", "big_Win_feats", "big_bin", "big_U", "big_bU", "big_Wg", "big_Wc",
                     "big_Wout", "big_bout", "frm_Win", "frm_bin", "frm_U", "frm_bU", "frm_Wg", "frm_Wc",

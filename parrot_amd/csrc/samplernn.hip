@@ -17,6 +17,7 @@
 #include "../../include/parrot_hip.h"
 #include "biggemm.h"
 #include "skinny.h"
+#include "sr_common.h"
 #include "sr_persist.h"
 #include "switches.h"
 
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
                                                       unsigned long long seed, const unsigned long long* __restrict__ origin,
-                                                      const SrUttDraw* __restrict__ utt) {
+                                                      const SrUttDraw* __restrict__ utt, int draw_mode) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int t = tbase[0] + toff;
@@ -91,6 +92,18 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
     }
     if (temperature <= 0.f) {
         if (tid == 0) samples[(size_t)b * len + t] = si[0];
+        return;
+    }
+    if (draw_mode == 1) {
+        // wave-parallel draw (a uniform branch; create has checked that Q is a multiple of 64): wave 0, lane l owns the
+        // Q / 64 contiguous codes from l Q / 64 on; same terms, key, counter and uniform as the walk below
+        if (tid < 64) {
+            const float mx = sv[0];
+            const int n = Q / 64;
+            const float u01 = srp_u01(key, origin[0] + (unsigned long long)(t + 1) - off);
+            const int pick = srp_scan_draw([&](int j) { return expf((lg[n * tid + j] - mx) / temperature); }, n, tid, u01);
+            if (tid == 0) samples[(size_t)b * len + t] = pick;
+        }
         return;
     }
     // inverse-CDF sampling of softmax(logits / temperature) by one thread (Q = 256)
@@ -605,7 +618,7 @@ struct SrPlan {
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
-                sa.origin = origin; sa.utt = utt;
+                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -630,7 +643,7 @@ struct SrPlan {
                 SR_TRY(linear(d.o2, D, d.W3, D, D, D, d.b3, nullptr, 0, d.o3, D, SK_ACT_RELU, st));
                 SR_TRY(linear(d.o3, D, d.W4, d.Q, D, d.Q, d.b4, nullptr, 0, d.logits, d.Q, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
-                                   d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt);
+                                   d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode);
             }
         }
         hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
@@ -719,6 +732,8 @@ int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan) { PH_EN
         desc->BFS % desc->FS != 0 || desc->Q < 2 || desc->n_rnn < 0 || desc->n_rnn > 5)
         return PARROT_ERR_BADARG;
     if (desc->starts && (!desc->big_h0 || !desc->frm_h0)) return PARROT_ERR_BADARG;
+    // (draw_mode 1: every lane of the drawing wave owns Q / 64 codes)
+    if (desc->draw_mode < 0 || desc->draw_mode > 1 || (desc->draw_mode == 1 && desc->Q % 64 != 0)) return PARROT_ERR_BADARG;
     if (desc->n_rnn > 0) {
         if (desc->lstm && (!desc->gate_ws || !desc->layer_tmp)) return PARROT_ERR_BADARG;
         for (int k = 0; k < desc->n_rnn; ++k) {

@@ -148,6 +148,55 @@ __device__ __forceinline__ int srp_argmax_row(const f32x4* __restrict__ lg, int 
     return srp_wave_min(bv == best ? bi : 0x7fffffff);
 }
 
+// 24-bit uniform of a seeded draw: splitmix64 finaliser of key ^ K1 * counter, the middle of one of 2^24 cells of (0, 1)
+__device__ __forceinline__ float srp_u01(unsigned long long key, unsigned long long ctr) {
+    unsigned long long x = key ^ (0x9E3779B97F4A7C15ull * ctr);
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f);
+}
+
+// Wave-parallel seeded draw (SampleRnnGenDesc::draw_mode = 1) by one whole wave: inverse-CDF pick among Q = 64 n codes
+// whose terms e_q >= 0 lane `lane` delivers for its n contiguous codes, term(j) = e_{n lane + j} (called twice with the
+// same bits).  The CDF is a fixed tree of plain float32 adds (__fadd_rn: never contracted, never reassociated):
+//   p_l = ((e_{nl} + e_{nl+1}) + ...)                      the lane's partial, left to right
+//   w_l = inclusive Hillis-Steele scan of p inside each row of 16 lanes, offsets 1, 2, 4, 8 (DPP row_shr with bound_ctrl:
+//         a lane without a source adds the 0 it is handed, exact for terms >= 0)
+//   s_l = w_l (row 0), R_{k-1} + w_l (row k) with the row totals chained R_0 = T_0, R_1 = R_0 + T_1, R_2 = R_1 + T_2
+// tot = s_63, u = u01 * tot, l* = the lowest lane with u < s_l (none: the pick is Q - 1), and inside l* the terms are added
+// one at a time to s_{l*-1} (0 for lane 0): the first code with u < c, or the lane's last code.  Every lane returns the pick.
+template <class F>
+__device__ __forceinline__ int srp_scan_draw(F term, int n, int lane, float u01) {
+    float p = term(0);
+    for (int j = 1; j < n; ++j) p = __fadd_rn(p, term(j));
+    float w = p;
+    w = __fadd_rn(w, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(w), 0x111, 0xf, 0xf, true)));  // row_shr:1
+    w = __fadd_rn(w, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(w), 0x112, 0xf, 0xf, true)));  // row_shr:2
+    w = __fadd_rn(w, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(w), 0x114, 0xf, 0xf, true)));  // row_shr:4
+    w = __fadd_rn(w, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(w), 0x118, 0xf, 0xf, true)));  // row_shr:8
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), 15));
+    const float r1 = __fadd_rn(r0, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), 31)));
+    const float r2 = __fadd_rn(r1, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), 47)));
+    // (the row number is made opaque here: as a loop invariant of the caller its three compare masks would be kept in
+    // six scalar registers across the persistent kernel's whole step loop, which has none to spare)
+    int row = lane >> 4;
+    asm volatile("" : "+v"(row));
+    const float s =row == 0 ? w : __fadd_rn(row == 1 ? r0 : row == 2 ? r1 : r2, w);
+    const float u = u01 * __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 63));
+    const unsigned long long hit = __ballot(u < s);
+    if (hit == 0) return 64 * n - 1;
+    const int ls = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(hit));
+    const float below = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), max(ls - 1, 0)));
+    int pick = n * ls + n - 1;
+    if (lane == ls) {
+        float c = ls == 0 ? 0.f : below;
+        for (int j = 0; j < n; ++j) {
+            c = __fadd_rn(c, term(j));
+            if (u < c) { pick = n * ls + j; break; }
+        }
+    }
+    return __builtin_amdgcn_readlane(pick, ls);
+}
+
 // v + the same vector of the lane 16 (ROWS = 16: neighbouring row) or 32 (other half of the wave) lanes away
 template <int ROWS>
 __device__ __forceinline__ f32x4 srp_swap_add(const f32x4& v) {

@@ -44,6 +44,9 @@ struct SrpArgs {
     // Per-utterance draws: [B] entries, or null = the plan's key (seed, stream) and temperature above.  Wave r picks for
     // row srow + r, so its entry is wave-uniform: fetched once per launch and row group into the shared block.
     const SrUttDraw* utt;
+    // SampleRnnGenDesc::draw_mode: 0 = one lane walks the codes (the default's bits), 1 = the wave-parallel draw
+    // (sr_common.h, srp_scan_draw).  A uniform branch of the pick, like utt.
+    int draw_mode;
 };
 
 // PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8

@@ -305,7 +305,18 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                 int pick = bi;
                 // (the row's own temperature with per-utterance entries: rows of one team may mix argmax and draws)
                 const float temperature = a.utt ? sh->utemp[r] : a.temperature;
-                if (temperature > 0.f) {
+                if (temperature > 0.f && a.draw_mode == 1) {
+                    // wave-parallel draw: lane l owns codes 4 l .. 4 l + 3, terms in registers, no LDS; the key, the counter
+                    // and the uniform are the ones of the walk below
+                    static_assert(Q == 256, "four codes per lane");
+                    const int b = srow + r;
+                    const float e0 = expf((lg[4 * lane][r] - best) / temperature), e1 = expf((lg[4 * lane + 1][r] - best) / temperature);
+                    const float e2 = expf((lg[4 * lane + 2][r] - best) / temperature), e3 = expf((lg[4 * lane + 3][r] - best) / temperature);
+                    unsigned long long key = a.seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
+                    unsigned long long ctr = draw0 + (unsigned long long)(t + 1);
+                    if (a.utt) { key = sh->useed[r]; ctr -= sh->uoff[r]; }
+                    pick = srp_scan_draw([&](int j) { return j == 0 ? e0 : j == 1 ? e1 : j == 2 ? e2 : e3; }, 4, lane, srp_u01(key, ctr));
+                } else if (temperature > 0.f) {
 #pragma unroll
                     for (int m = 0; m < Q / 64; ++m) ev[r * Q + lane + 64 * m] = expf((lg[lane + 64 * m][r] - best) / temperature);
                     __builtin_amdgcn_wave_barrier();

@@ -230,10 +230,21 @@ def _seed_image(seeds):
     return numpy.array(flat, dtype=numpy.uint64).reshape(numpy.shape(seeds)).view(numpy.int64)
 
 
+DRAW_MODES = {'sequential': 0, 'scan': 1}
+
+
+def draw_mode_code(draw_mode):
+    """SampleRnnGenDesc::draw_mode of a mode's name; ValueError on any other name (no device call)."""
+    if draw_mode not in DRAW_MODES:
+        raise ValueError("draw_mode must be one of %s, got %r" % (sorted(DRAW_MODES), draw_mode))
+    return DRAW_MODES[draw_mode]
+
+
 class DeviceGenerator:
     """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
 
-    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False):
+    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
+                 draw_mode='sequential'):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
         three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
 
@@ -245,7 +256,14 @@ class DeviceGenerator:
         packed plan, one per stream on a plain one; the plan's temperature and seed are then not used.  An utterance's
         samples are then a function of the model, the plan's shape, the carrying stream, and the utterance's features,
         seed and temperature (utterance_draw_u01 is the uniform of its n-th sample): they do not depend on its slot, the
-        segment boundaries or its neighbours."""
+        segment boundaries or its neighbours.
+
+        draw_mode: how a draw at temperature > 0 finds its code.  'sequential' (default): one lane walks the 256 codes, the
+        samples every earlier version drew.  'scan': the wave-parallel draw (SampleRnnGenDesc::draw_mode = 1) -- the same
+        terms and uniforms, the CDF as a fixed tree of float32 sums; faster, and a different (equally valid) rounding of the
+        CDF, so a few draws per ten thousand land on the neighbouring code.  Argmax (temperature <= 0) is the same in both."""
+        self.draw_mode = draw_mode
+        mode = draw_mode_code(draw_mode)
         if SKIP_CONN:
             raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
         self.B, self.T = batch, n_frames
@@ -310,7 +328,7 @@ class DeviceGenerator:
             w['frm_h0'] = lib.param('FrameLevel.h0').detach().to(**f).contiguous()
         d = _lib.SampleRnnGenDesc()
         d.B, d.D, d.T, d.Q, d.FS, d.BFS, d.feat_dim, d.use_graph = batch, D, n_frames, Q, FS, BFS, FEAT_DIM, int(use_graph)
-        d.temperature, d.seed = float(temperature), int(seed)
+        d.temperature, d.seed, d.draw_mode = float(temperature), int(seed), mode
         for k, v in list(w.items()) + list(self.ws.items()):
             setattr(d, k, v.data_ptr())
         if not self.single:
@@ -510,7 +528,7 @@ def _per_utterance(seeds, temperatures, n, default_temperature):
 
 
 def generate_packed(utterances, n_streams=32, temperature=TEMPERATURE, seed=234, use_graph=True, seeds=None,
-                    temperatures=None):
+                    temperatures=None, draw_mode='sequential'):
     """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
     utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
     n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
@@ -524,7 +542,10 @@ def generate_packed(utterances, n_streams=32, temperature=TEMPERATURE, seed=234,
     then a function of the model, the plan's shape (n_streams), the carrying stream, and the utterance's features, seed
     and temperature: it equals, bit for bit, what a plain plan of n_streams streams in that mode returns for the utterance
     carried alone in the same stream with the same seed and temperature, and does not depend on its slot, the order of
-    the list or its neighbours.  (The carrying stream is pack_utterances' choice, which does depend on the list.)"""
+    the list or its neighbours.  (The carrying stream is pack_utterances' choice, which does depend on the list.)
+
+    draw_mode: 'sequential' or 'scan', see DeviceGenerator."""
+    draw_mode_code(draw_mode)
     if SKIP_CONN:
         raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
     utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
@@ -537,7 +558,7 @@ def generate_packed(utterances, n_streams=32, temperature=TEMPERATURE, seed=234,
     stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
     features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
     gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
-                          utterance_draws=seeds is not None)
+                          utterance_draws=seeds is not None, draw_mode=draw_mode)
     try:
         if seeds is not None:
             utt_seed, utt_temp = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
@@ -562,13 +583,16 @@ def unpack_samples(samples, lengths, stream, first_slot):
     return out
 
 
-def generate_stream(features, segment_frames, temperature=TEMPERATURE, seed=234, use_graph=True, gen=None):
+def generate_stream(features, segment_frames, temperature=TEMPERATURE, seed=234, use_graph=True, gen=None,
+                    draw_mode='sequential'):
     """Generator over a rectangle features [N, B, 63] on a plan of segment_frames + 1 slots used as a ring: yields int32
     arrays [B, 80 n] -- the first one holds the Q/2 prefix and up to segment_frames frames, every later one up to
     segment_frames frames -- whose concatenation is the [B, 80 N] result of DeviceGenerator(B, N).generate(features), bit
     for bit, seeded draws included.  The plan does not grow with N, and the first samples are out after segment_frames
     periods.  gen: a plain DeviceGenerator(B, segment_frames + 1) of the caller's to run on (it is left open; temperature,
-    seed and use_graph are then the plan's); default: a plan of its own for this call."""
+    seed, use_graph and draw_mode are then the plan's); default: a plan of its own for this call, with draw_mode
+    'sequential' or 'scan' (see DeviceGenerator)."""
+    draw_mode_code(draw_mode)
     if SKIP_CONN:
         raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
     features = numpy.asarray(features, dtype='float32')
@@ -580,7 +604,7 @@ def generate_stream(features, segment_frames, temperature=TEMPERATURE, seed=234,
     N, B = features.shape[0], features.shape[1]
     own = gen is None
     if own:
-        gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph)
+        gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph, draw_mode=draw_mode)
     elif gen.packed or (gen.B, gen.T) != (B, S + 1):
         raise ValueError("gen must be a plain plan of %d streams and %d slots" % (B, S + 1))
     try:
@@ -667,10 +691,13 @@ class StreamingGenerator:
 
     run_segment(features [n, B, 63], starts [n, B], resume) -> samples [B, 80 n] of slots 1 .. n is the callable that
     runs a segment; the default runs it on the device.  With utterance_draws it is called with two more keyword arguments,
-    seeds [n, B] uint64 and temperatures [n, B] float32: what the utterance whose start flag is on that row draws with."""
+    seeds [n, B] uint64 and temperatures [n, B] float32: what the utterance whose start flag is on that row draws with.
+
+    draw_mode: 'sequential' or 'scan', the plan's (see DeviceGenerator); a run_segment of the caller's does not see it."""
 
     def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
-                 utterance_draws=False):
+                 utterance_draws=False, draw_mode='sequential'):
+        draw_mode_code(draw_mode)
         if SKIP_CONN:
             raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
         self.B, self.S = int(n_streams), int(segment_frames)
@@ -683,7 +710,7 @@ class StreamingGenerator:
         self.temperature = float(temperature)
         if run_segment is None:
             self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
-                                       packed=True, utterance_draws=self.utterance_draws)
+                                       packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode)
             run_segment = self._run_on_device
         self._run = run_segment
         self._resume = False
@@ -794,7 +821,8 @@ def write_audio_file(name, data, path_to_save):
 def generate_and_save_samples(tag, path_to_save=None, features=None, features_length=None, noise_level=0.,
                               big_frame_level_generate_fn=None, frame_level_generate_fn=None,
                               sample_level_generate_fn=None, npy_address=None, temperature=TEMPERATURE,
-                              use_device_loop=True, pack_streams=0, stream_frames=0, utterance_seed=None):
+                              use_device_loop=True, pack_streams=0, stream_frames=0, utterance_seed=None,
+                              draw_mode='sequential'):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
     (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.
 
@@ -808,8 +836,13 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
 
     utterance_seed = S (an integer; None: off): utterance i draws with the seed utterance_seed(S, i) of its own at
     `temperature`, in the rectangle, packed and streamed modes alike (DeviceGenerator(utterance_draws=True)): its samples
-    no longer depend on where it was placed.  Device loop only."""
+    no longer depend on where it was placed.  Device loop only.
+
+    draw_mode = 'sequential' (default) or 'scan': how the device loop's draws at temperature > 0 find their code
+    (DeviceGenerator), in the rectangle, packed and streamed modes alike.  'scan' needs the device loop."""
     total_time = time()
+    if draw_mode_code(draw_mode) != 0 and not (use_device_loop and not SKIP_CONN):
+        raise ValueError("draw_mode='scan' needs the device-resident generator")
     per_utt = utterance_seed is not None
     if per_utt and not (use_device_loop and not SKIP_CONN):
         raise ValueError("utterance_seed needs the device-resident generator")
@@ -825,7 +858,8 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         n_streams = int(pack_streams) if pack_streams > 0 else 32
         if path_to_save is not None:
             os.makedirs(path_to_save, exist_ok=True)
-        sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature, utterance_draws=per_utt)
+        sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature, utterance_draws=per_utt,
+                                draw_mode=draw_mode)
         chunks = [[] for _ in range(n_seqs)]
         pieces = [None] * n_seqs
         try:
@@ -853,7 +887,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         lens = [min(max(int(n), 1), n_frames) for n in features_length]
         seeds = [_derive_seed(utterance_seed, i) for i in range(n_seqs)] if per_utt else None
         pieces = generate_packed([test_feats[:lens[i], i] for i in range(n_seqs)], n_streams=int(pack_streams),
-                                 temperature=temperature, seeds=seeds)
+                                 temperature=temperature, seeds=seeds, draw_mode=draw_mode)
         total_time = time() - total_time
         print("{} samples of {} seconds in all generated in {} seconds ({} packed streams).".format(
             n_seqs, sum(lens) * BIG_FRAME_SIZE / float(BITRATE), total_time, int(pack_streams)))
@@ -865,7 +899,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
                 write_audio_file("sample_{}_{}".format(tag, i), samp, path_to_save)
         return pieces
     if use_device_loop and not SKIP_CONN:  # (the device loop does not take the skip-connection stacks: literal loop)
-        gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature, utterance_draws=per_utt)
+        gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature, utterance_draws=per_utt, draw_mode=draw_mode)
         draws = dict(seeds=[_derive_seed(utterance_seed, i) for i in range(n_seqs)],
                      temperatures=float(temperature)) if per_utt else {}
         samples = gen.generate(test_feats, **draws).cpu().numpy()

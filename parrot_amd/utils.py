@@ -5,7 +5,7 @@ and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
 --device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames,
---utterance_seed.
+--utterance_seed, --draw_mode.
 """
 from __future__ import annotations
 
@@ -138,6 +138,11 @@ def sample_parse(argv=None):
                              'derived from S and i, in the rectangle, with --pack_streams and with --stream_frames alike: its '
                              'samples do not depend on where it was placed (DESIGN.md 3.6); -1: the plan\'s seed and the '
                              'stream key the draws')
+    parser.add_argument('--draw_mode', type=str, default='sequential', choices=('sequential', 'scan'),
+                        help="(with --raw_output) how the SampleRNN vocoder's draws at temperature > 0 find their code: "
+                             "'sequential' walks the 256 codes in one lane (the samples of every earlier version); 'scan' is "
+                             "the wave-parallel draw -- same uniforms, the CDF summed as a fixed tree: faster, and a few "
+                             "draws per ten thousand land on the neighbouring code (DESIGN.md 3.6)")
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:

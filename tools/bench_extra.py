@@ -9,7 +9,7 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          decode_gmm_gru2_1024, decode_gmm_lstm2_1024, decode_bf16_gru2_1024,
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
                                          samplernn_cfg5, samplernn_groups, samplernn_packed, samplernn_stream,
-                                         samplernn_utt_draws, mulaw)
+                                         samplernn_utt_draws, samplernn_draw_scan, mulaw)
   bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
                                          SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
                                          kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
@@ -37,6 +37,15 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          plan with temperatures 0 / 0.5 / 1 / 2 mixed inside every team against the same
                                          packing at temperature 0 and at 1 with the plan's key; N alternations in one
                                          process; the result also goes to FILE (default profiles/samplernn_utt_draws.json)
+  bench_extra.py --only samplernn_draw_scan [--reps N] [--draw-scan-json FILE] [--parent-lib FILE]
+                                         SampleRNN at D = 1024 and B = 32, 8000 samples per stream: argmax, the sequential
+                                         draw at temperature 1 and the wave-parallel draw (draw_mode='scan') at temperature 1,
+                                         N alternations in one process, each with its spread (max - min); the same three with
+                                         per-utterance draws on; the two draws on the launch path at B = 33 and in two row
+                                         groups (B = 64, PARROT_SR_PERSIST_GROUPS=8); with --parent-lib (the parent commit's
+                                         libparrot_hip.so) the default path of both libraries at temperature 0 and 1 in the
+                                         same alternation, bit identity included; the two bars of the mode are evaluated;
+                                         the result also goes to FILE (default profiles/samplernn_draw_scan.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -61,7 +70,7 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "mulaw")
+       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -679,6 +688,143 @@ if "samplernn_utt_draws" in only:
     out["samplernn_utt_draws"] = res
     path = _arg("--utt-draws-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
                                                  "samplernn_utt_draws.json"))
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+# ---- SampleRNN D=1024, B=32: the wave-parallel seeded draw (SampleRnnGenDesc::draw_mode = 1, DeviceGenerator(draw_mode='scan'))
+# against the sequential draw and argmax; the same with per-utterance draws; the launch path at B = 33; two row groups at
+# B = 64; and, with --parent-lib, the default path against the parent commit's library.  All plans alive in one process and
+# run alternately.
+if "samplernn_draw_scan" in only:
+    import contextlib
+    import ctypes
+    from parrot_amd import _lib as plib
+    from parrot_amd.sampleRNN import lib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    lib.delete_all_params(); lib.set_device(dev)
+    tt.configure(DIM=1024, EMB_SIZE=256)
+    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+    with torch.no_grad():  # registers all parameters with the reference initialisation
+        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
+                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    T, SEED, reps = 101, 234, int(_arg("--reps", "5"))
+    nsamp = (T - 1) * 80
+    feats = {B: torch.randn(T, B, 63, generator=g).numpy() for B in (32, 33, 64)}
+    key_seeds = [(SEED ^ (tt.DRAW_K2 * (b + 1))) & (2 ** 64 - 1) for b in range(32)]
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            fn = getattr(parent_lib, name)
+            fn.restype = res_
+            fn.argtypes = args_
+
+    @contextlib.contextmanager
+    def under(which):  # every call of a plan goes to the library that made it
+        plib._lib = which
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+
+    saved = {k: os.environ.get(k) for k in ("PARROT_SR_PERSIST", "PARROT_SR_PERSIST_GROUPS")}
+
+    def plan(B, groups=None, which=this_lib, **kw):
+        if groups is None:
+            os.environ.pop("PARROT_SR_PERSIST_GROUPS", None)
+        else:
+            os.environ["PARROT_SR_PERSIST_GROUPS"] = str(groups)
+        with under(which):
+            return tt.DeviceGenerator(B, T, seed=SEED, **kw)
+
+    draws = dict(seeds=key_seeds, temperatures=1.0)
+    # name: (plan, its library, generate's keywords)
+    plans = {"argmax": (plan(32, temperature=0.0), this_lib, {}),
+             "sequential_t1": (plan(32, temperature=1.0), this_lib, {}),
+             "scan_t1": (plan(32, temperature=1.0, draw_mode='scan'), this_lib, {}),
+             "utt_argmax": (plan(32, utterance_draws=True), this_lib, dict(seeds=key_seeds, temperatures=0.0)),
+             "utt_sequential_t1": (plan(32, utterance_draws=True), this_lib, draws),
+             "utt_scan_t1": (plan(32, utterance_draws=True, draw_mode='scan'), this_lib, draws),
+             "launch_B33_sequential_t1": (plan(33, temperature=1.0), this_lib, {}),
+             "launch_B33_scan_t1": (plan(33, temperature=1.0, draw_mode='scan'), this_lib, {}),
+             "groups2_B64_sequential_t1": (plan(64, groups=8, temperature=1.0), this_lib, {}),
+             "groups2_B64_scan_t1": (plan(64, groups=8, temperature=1.0, draw_mode='scan'), this_lib, {})}
+    if parent_lib is not None:
+        plans["parent_argmax"] = (plan(32, which=parent_lib, temperature=0.0), parent_lib, {})
+        plans["parent_sequential_t1"] = (plan(32, which=parent_lib, temperature=1.0), parent_lib, {})
+        # a second plan of each kind, created in the other order: what differs between two plans of ONE library (where their
+        # buffers landed) is the floor under any difference between the libraries
+        plans["argmax_again"] = (plan(32, temperature=0.0), this_lib, {})
+        plans["sequential_t1_again"] = (plan(32, temperature=1.0), this_lib, {})
+        plans["parent_sequential_t1_again"] = (plan(32, which=parent_lib, temperature=1.0), parent_lib, {})
+        plans["parent_argmax_again"] = (plan(32, which=parent_lib, temperature=0.0), parent_lib, {})
+    for k, v in saved.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+    for k, (gen, _, _) in plans.items():
+        want = 0 if k.startswith("launch") else 2 if k.startswith("groups2") else 1
+        assert gen.persist_groups == want, (k, gen.persist_groups)
+    times, samples = {k: [] for k in plans}, {}
+    keys = list(plans)
+    for rep_ in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+        for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:  # (no plan always runs behind the same other one)
+            gen, which, kw = plans[k]
+            with under(which):
+                torch.cuda.synchronize(); t0 = time.time()
+                s = gen.generate(feats[gen.B], **kw)
+                torch.cuda.synchronize(); dt = time.time() - t0
+                samples[k] = s.cpu().numpy().copy()
+            if rep_:
+                times[k].append(dt)
+    for gen, which, _ in plans.values():
+        with under(which):
+            gen.close()
+    us = {k: [1e6 * dt / nsamp for dt in v] for k, v in times.items()}
+    med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+    spread = {k: max(v) - min(v) for k, v in us.items()}
+
+    def faster(a, b):  # a faster than b by more than the sum of the two spreads
+        return bool(med[b] - med[a] > spread[a] + spread[b])
+
+    differ = int((samples["scan_t1"] != samples["sequential_t1"]).sum())
+    res = {"dim": 1024, "alternations": reps, "samples_per_stream": nsamp,
+           "timed": "call to device idle (host-side input copies included)",
+           "runs": {k: {"streams": plans[k][0].B, "us_per_sample_step": [round(x, 3) for x in us[k]],
+                        "us_per_sample_step_median": round(med[k], 3), "spread_max_minus_min": round(spread[k], 3)}
+                    for k in plans},
+           "scan_samples_that_differ_from_sequential": {"differ": differ, "of": int(samples["scan_t1"].size - 32 * 80)},
+           "utt_scan_bit_identical_to_scan": bool(np.array_equal(samples["utt_scan_t1"], samples["scan_t1"])),
+           "utt_sequential_bit_identical_to_sequential": bool(np.array_equal(samples["utt_sequential_t1"], samples["sequential_t1"])),
+           "bar_scan_faster_than_sequential_by_more_than_both_spreads": {
+               "persistent_B32": faster("scan_t1", "sequential_t1"),
+               "persistent_B32_utterance_draws": faster("utt_scan_t1", "utt_sequential_t1"),
+               "launch_B33": faster("launch_B33_scan_t1", "launch_B33_sequential_t1"),
+               "groups2_B64": faster("groups2_B64_scan_t1", "groups2_B64_sequential_t1")},
+           "not_measured": ["eight row groups", "the streaming generator's end-to-end time", "D = 256 and D = 512"]}
+    if parent_lib is not None:
+        def pair(t):  # medians of the two plans of each library, the gap between the libraries and inside each
+            a, b = (med[t], med[t + "_again"]), (med["parent_" + t], med["parent_" + t + "_again"])
+            four = sorted(spread[k] for k in (t, t + "_again", "parent_" + t, "parent_" + t + "_again"))
+            inside = max(abs(a[0] - a[1]), abs(b[0] - b[1]), (four[1] + four[2]) / 2)  # (the median: one outlier is no spread)
+            gap = sum(a) / 2 - sum(b) / 2
+            return {"this_us": [round(x, 3) for x in a], "parent_us": [round(x, 3) for x in b],
+                    "this_minus_parent_us": round(gap, 3), "largest_difference_inside_one_library_us": round(inside, 3),
+                    "bar_default_within_its_spread_of_parent": bool(abs(gap) <= inside)}
+        res["default_path_against_parent_commit"] = {
+            "how": "this build and the parent commit's library loaded in one process, two plans of each per temperature (the "
+                   "second pair created in the other order), all in the same alternation; the spread of the default path is "
+                   "the larger of the four plans' median max - min and the difference between two plans of one library",
+            "bit_identical_t0": bool(np.array_equal(samples["argmax"], samples["parent_argmax"])),
+            "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
+            "t0": pair("argmax"), "t1": pair("sequential_t1")}
+    out["samplernn_draw_scan"] = res
+    path = _arg("--draw-scan-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                                                 "samplernn_draw_scan.json"))
     with open(path, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
