@@ -112,9 +112,7 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
         float tot = 0.f;
         for (int q = 0; q < Q; ++q) tot += expf((lg[q] - mx) / temperature);
         // (keyed by the sample's index in the whole run: the draw origin counts what resumed segments have moved past)
-        unsigned long long x = key ^ (0x9E3779B97F4A7C15ull * (origin[0] + (unsigned long long)(t + 1) - off));
-        x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;  // splitmix64
-        const float u = (float)((x >> 40) + 0.5) * (1.0f / 16777216.0f) * tot;
+        const float u = srp_u01(key, origin[0] + (unsigned long long)(t + 1) - off) * tot;
         float c = 0.f;
         int pick = Q - 1;
         for (int q = 0; q < Q; ++q) {

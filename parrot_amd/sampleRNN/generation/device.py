@@ -1,0 +1,254 @@
+"""The plan of the device-resident generation loop: folded weights, workspace, runs in one piece or in resumable segments."""
+import ctypes as C
+
+import numpy
+import torch
+
+from ... import _lib
+from ... import ops as hip
+from .. import lib
+from ..lib import ops as lops
+from .inputs import _seed_image, config, draw_mode_code
+
+
+def device_loop_guard(draw_mode):
+    """What every entry to the device-resident loop checks before any device call: draw_mode's code (ValueError on an
+    unknown name), and that the model has no skip-connection stacks, which the loop does not take."""
+    mode = draw_mode_code(draw_mode)
+    if config().SKIP_CONN:
+        raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
+    return mode
+
+
+class DeviceGenerator:
+    """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
+
+    def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
+                 draw_mode='sequential'):
+        """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
+        three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
+
+        packed=True: the plan takes per-stream utterance starts (SampleRnnGenDesc::starts): generate(features, starts)
+        then begins a new utterance in stream b at big frame f wherever starts[f][b] != 0 (see generate_packed).
+
+        utterance_draws=True: every utterance draws with a seed and a temperature of its own
+        (samplernn_generate_set_utterance_draws): generate(..., seeds=, temperatures=) takes them, aligned with starts on a
+        packed plan, one per stream on a plain one; the plan's temperature and seed are then not used.  An utterance's
+        samples are then a function of the model, the plan's shape, the carrying stream, and the utterance's features,
+        seed and temperature (utterance_draw_u01 is the uniform of its n-th sample): they do not depend on its slot, the
+        segment boundaries or its neighbours.
+
+        draw_mode: how a draw at temperature > 0 finds its code.  'sequential' (default): one lane walks the 256 codes, the
+        samples every earlier version drew.  'scan': the wave-parallel draw (SampleRnnGenDesc::draw_mode = 1) -- the same
+        terms and uniforms, the CDF as a fixed tree of float32 sums; faster, and a different (equally valid) rounding of the
+        CDF, so a few draws per ten thousand land on the neighbouring code.  Argmax (temperature <= 0) is the same in both."""
+        self.draw_mode = draw_mode
+        mode = device_loop_guard(draw_mode)
+        self.B, self.T = batch, n_frames
+        self.packed = bool(packed)
+        self.utterance_draws = bool(utterance_draws)
+        dev = lib.device()
+        f = dict(device=dev, dtype=torch.float32)
+        tt = config()
+        D, FS, BFS, Q, N_RNN, RNN_TYPE = tt.DIM, tt.FRAME_SIZE, tt.BIG_FRAME_SIZE, tt.Q_LEVELS, tt.N_RNN, tt.RNN_TYPE
+        nfr = BFS // FS
+        ew = lambda n, i=0: lops.effective_weight(n, i, tt.WEIGHT_NORM).detach().contiguous()
+        pb = lambda n: lib.param(n + '.b').detach().contiguous()
+        with torch.no_grad():
+            single = RNN_TYPE == 'GRU' and N_RNN == 1
+            w = dict(
+                big_Win_frames=ew('BigFrameLevel.rnn_inp_fusion', 0), big_Win_feats=ew('BigFrameLevel.rnn_inp_fusion', 1),
+                big_bin=pb('BigFrameLevel.rnn_inp_fusion'),
+                big_Wout=ew('BigFrameLevel.Output'), big_bout=pb('BigFrameLevel.Output'),
+                frm_Win=ew('FrameLevel.InputExpand'), frm_bin=pb('FrameLevel.InputExpand'),
+                frm_Wout=ew('FrameLevel.Output'), frm_bout=pb('FrameLevel.Output'),
+                W2=ew('SampleLevel.L2'), b2=pb('SampleLevel.L2'), W3=ew('SampleLevel.L3'), b3=pb('SampleLevel.L3'),
+                W4=ew('SampleLevel.Output'), b4=pb('SampleLevel.Output'))
+            # fold Embedding . L1_PrevSamples into a [FS, Q, D] table (one GEMM per previous-sample position)
+            emb = lib.param('SampleLevel.Embedding').detach().contiguous()
+            W1 = ew('SampleLevel.L1_PrevSamples')
+            tbl = torch.empty(FS, Q, D, **f)
+            for pos in range(FS):
+                hip.gemm(emb, W1[pos * tt.EMB_SIZE:(pos + 1) * tt.EMB_SIZE], out=tbl[pos])
+            w['emb_tbl'] = tbl
+            # the RNN stacks of the two tiers: per layer (Input.W, Input.b | b, Recurrent_Gates, Recurrent_Candidate | -)
+            self.layers = {}
+            for tier, tag in (('BigFrameLevel', 'big'), ('FrameLevel', 'frm')):
+                for k in range(1, N_RNN + 1):
+                    if RNN_TYPE == 'GRU':
+                        pre = f'{tier}.GRU{k}.Step'
+                        self.layers[(tag, k - 1)] = [ew(pre + '.Input'), pb(pre + '.Input'), ew(pre + '.Recurrent_Gates'),
+                                                     ew(pre + '.Recurrent_Candidate')]
+                    else:
+                        pre = f'{tier}.LSTM{k}.Step'
+                        self.layers[(tag, k - 1)] = [ew(pre + '.Input'), lib.param(pre + '.b').detach().contiguous(),
+                                                     ew(pre + '.Recurrent_Gates')]
+            if single:
+                for tag in ('big', 'frm'):
+                    U_, bU_, Wg_, Wc_ = self.layers[(tag, 0)]
+                    w.update({f'{tag}_U': U_, f'{tag}_bU': bU_, f'{tag}_Wg': Wg_, f'{tag}_Wc': Wc_})
+        self.w = w
+        self.single = single
+        self.ws = dict(
+            samples=torch.zeros(batch, BFS * n_frames, device=dev, dtype=torch.int32),
+            features=torch.zeros(n_frames, batch, tt.FEAT_DIM, **f),
+            big_h=torch.zeros(batch, D, **f), frm_h=torch.zeros(batch, D, **f),
+            xf_big=torch.zeros(batch, BFS, **f), xf_frm=torch.zeros(batch, FS, **f),
+            feat_cur=torch.zeros(batch, tt.FEAT_DIM, **f), gru_in=torch.zeros(batch, D, **f),
+            P=torch.zeros(batch, 4 * D, **f), z=torch.zeros(batch, D, **f), r=torch.zeros(batch, D, **f),
+            rh=torch.zeros(batch, D, **f), big_out=torch.zeros(batch, nfr * D, **f),
+            frame_out=torch.zeros(batch, FS * D, **f), o1=torch.zeros(batch, D, **f), o2=torch.zeros(batch, D, **f),
+            o3=torch.zeros(batch, D, **f), logits=torch.zeros(batch, Q, **f),
+            tbase=torch.zeros(1, device=dev, dtype=torch.int32))
+        if self.packed:
+            self.ws['starts'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int32)
+            # the learned initial states, [N_RNN, H0_MULT * D]: what a stream restarts from inside the loop
+            w['big_h0'] = lib.param('BigFrameLevel.h0').detach().to(**f).contiguous()
+            w['frm_h0'] = lib.param('FrameLevel.h0').detach().to(**f).contiguous()
+        d = _lib.SampleRnnGenDesc()
+        d.B, d.D, d.T, d.Q, d.FS, d.BFS, d.feat_dim, d.use_graph = batch, D, n_frames, Q, FS, BFS, tt.FEAT_DIM, int(use_graph)
+        d.temperature, d.seed, d.draw_mode = float(temperature), int(seed), mode
+        for k, v in list(w.items()) + list(self.ws.items()):
+            setattr(d, k, v.data_ptr())
+        if not self.single:
+            lstm = RNN_TYPE == 'LSTM'
+            d.n_rnn, d.lstm = N_RNN, int(lstm)
+            self.states = {}
+            for tag in ('big', 'frm'):
+                for k in range(N_RNN):
+                    for q, t in enumerate(self.layers[(tag, k)]):
+                        getattr(d, tag + '_L')[k][q] = t.data_ptr()
+                    self.states[(tag, 'h', k)] = torch.zeros(batch, D, **f)
+                    getattr(d, tag + '_hs')[k] = self.states[(tag, 'h', k)].data_ptr()
+                    if lstm:
+                        self.states[(tag, 'c', k)] = torch.zeros(batch, D, **f)
+                        getattr(d, tag + '_cs')[k] = self.states[(tag, 'c', k)].data_ptr()
+            self.ws['gate_ws'] = torch.zeros(batch, 4 * D, **f)
+            self.ws['layer_tmp'] = torch.zeros(batch, D, **f)
+            d.gate_ws, d.layer_tmp = self.ws['gate_ws'].data_ptr(), self.ws['layer_tmp'].data_ptr()
+        # persistent-thread sample kernel (sr_persist.hip): zero-filled exchange / barrier workspace when the shape qualifies
+        n = int(_lib.load().samplernn_persist_floats(C.byref(d)))
+        if n > 0:
+            self.ws['persist_ws'] = torch.zeros(n, **f)
+            d.persist_ws, d.persist_ws_floats = self.ws['persist_ws'].data_ptr(), n
+        self.desc = d
+        self.plan = C.c_void_p()
+        _lib.call('samplernn_generate_create', C.byref(d), C.byref(self.plan))
+        self.persistent = bool(_lib.load().samplernn_generate_is_persistent(self.plan))
+        # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
+        self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
+        self._has_run = False
+        if self.utterance_draws:
+            # [T, B] like starts (ring rows): row f = what an utterance that begins at big frame f draws with; utt_seed is the
+            # two's-complement image of the unsigned 64-bit seed
+            self.ws['utt_seed'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int64)
+            self.ws['utt_temp'] = torch.zeros(n_frames, batch, **f)
+            self.set_utterance_draws()
+
+    def set_utterance_draws(self):
+        """Hands the plan its per-utterance seed and temperature arrays; refused (HipCallError) once the plan has run."""
+        _lib.call('samplernn_generate_set_utterance_draws', self.plan, self.ws['utt_seed'].data_ptr(),
+                  self.ws['utt_temp'].data_ptr())
+
+    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None):
+        """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
+        starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
+        frame f, whose Q/2 prefix is slot f - 1.
+
+        A run in segments (samplernn_generate_run_segment): n_frames = k in 1 .. T-1 generates k frames in this call.
+        resume=False starts a run: features (and starts) hold k + 1 rows, slot 0 = the prefix, and the [B, 80 (k + 1)]
+        samples come back, prefix included.  resume=True continues the run of the last call from the states where they
+        stand: features (and starts) hold k rows, for slots 1 .. k of the ring -- slot 0 is the last slot of the call
+        before --, nothing is re-initialised and the [B, 80 k] samples of this segment come back (a copy: the next
+        segment overwrites the ring).  The segments of a run equal the run in one piece, seeded draws included.
+
+        seeds / temperatures (plans built with utterance_draws=True only, and both required there): on a packed plan
+        [rows, B] aligned with starts -- row f, stream b holds what the utterance that starts[f][b] flags draws with, and the
+        row of slot 1 of a run that does not resume what every stream's first utterance draws with --; on a plain plan [B],
+        one utterance per stream, with resume=False only (the segments that resume go on with them).  Seeds are unsigned
+        64-bit integers (Python integers or an integer array)."""
+        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures)
+        self._stage(features, starts, seeds, temperatures, segment, rows, first)
+        self._launch(segment, resume, k)
+        if not segment:
+            return self.ws['samples']
+        BFS = config().BIG_FRAME_SIZE
+        return self.ws['samples'][:, BFS * first:BFS * (k + 1)].clone()
+
+    def _resolve(self, starts, resume, n_frames, seeds, temperatures):
+        """Which arguments this plan takes in which kind of run -> (segment, resume, k, rows, first): a run in segments or
+        in one piece, k frames to generate, `rows` rows of input for the ring's slots from `first` on."""
+        if (starts is not None) != self.packed:
+            raise ValueError("starts must be given exactly when the plan was built with packed=True")
+        resume = bool(resume)
+        takes_draws = self.utterance_draws and (self.packed or not resume)
+        if (seeds is not None) != takes_draws or (temperatures is not None) != takes_draws:
+            raise ValueError("seeds and temperatures must both be given exactly when the plan was built with "
+                             "utterance_draws=True (a plain plan takes them with resume=False only)")
+        if resume and not self._has_run:
+            raise ValueError("resume=True needs a run to continue: call generate(..., resume=False) first")
+        k = self.T - 1 if n_frames is None else int(n_frames)
+        if not 1 <= k <= self.T - 1:
+            raise ValueError("n_frames must be in 1 .. T-1 = %d, got %d" % (self.T - 1, k))
+        rows = k if resume else (k + 1 if n_frames is not None else self.T)
+        return resume or n_frames is not None, resume, k, rows, 1 if resume else 0
+
+    def _stage(self, features, starts, seeds, temperatures, segment, rows, first):
+        """Checks the arrays' shapes and copies them into rows first .. first + rows - 1 of the workspace."""
+        ws = self.ws
+        feats = torch.as_tensor(features)
+        if segment and (feats.dim() != 3 or tuple(feats.shape[:2]) != (rows, self.B)):
+            raise ValueError("features must be [%d, %d, %d], got %s" % (rows, self.B, config().FEAT_DIM, tuple(feats.shape)))
+        if self.packed:
+            st = torch.as_tensor(numpy.asarray(starts))
+            if tuple(st.shape) != (rows, self.B):
+                raise ValueError("starts must be [%s, B] = [%d, %d], got %s" % ("T" if not segment else "rows", rows, self.B,
+                                                                                 tuple(st.shape)))
+            ws['starts'][first:first + rows].copy_((st != 0).to(ws['starts'].device, torch.int32))
+        if seeds is not None:
+            want = (rows, self.B) if self.packed else (self.B,)
+            sd = _seed_image(seeds)
+            tp = numpy.broadcast_to(numpy.asarray(temperatures, dtype='float32'), want) if numpy.ndim(temperatures) == 0 \
+                else numpy.asarray(temperatures, dtype='float32')
+            if sd.shape != want or tp.shape != want:
+                raise ValueError("seeds and temperatures must be %s, got %s and %s" % (list(want), sd.shape, tp.shape))
+            # (a plain plan: one utterance per stream, prefix in slot 0 -- the row of slot 1, like a start flagged there)
+            lo, hi = (first, first + rows) if self.packed else (1, 2)
+            ws['utt_seed'][lo:hi].copy_(torch.from_numpy(sd.reshape(hi - lo, self.B)).to(ws['utt_seed'].device))
+            ws['utt_temp'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tp).reshape(hi - lo, self.B)).to(ws['utt_temp'].device))
+        ws['features'][first:first + rows].copy_(feats.to(ws['features'].device, torch.float32))
+
+    def _launch(self, segment, resume, k):
+        """Initialises a run that does not resume, launches it and asks for its status."""
+        if not resume:
+            self._init_run()
+        if not segment:
+            _lib.call('samplernn_generate_run', self.plan, hip._stream())
+        else:
+            _lib.call('samplernn_generate_run_segment', self.plan, k, int(resume), hip._stream())
+        self._has_run = True
+        if self.persistent or segment:  # a team of the persistent kernel that gave up leaves invalid samples: fail loudly
+            _lib.call('samplernn_generate_status', self.plan)
+
+    def _init_run(self):
+        """The prefix slot and the learned initial states: what a run that does not resume starts from."""
+        tt = config()
+        ws = self.ws
+        ws['samples'].zero_()
+        ws['samples'][:, :tt.BIG_FRAME_SIZE] = int(tt.Q_ZERO)  # three_tier.py:795
+        # reset = (t == BIG_FRAME_SIZE): the first step of both tiers starts from the learned h0 (:334-342, 411-419)
+        if self.single:
+            ws['big_h'].copy_(lib.param('BigFrameLevel.h0').detach()[0].unsqueeze(0).expand(self.B, -1))
+            ws['frm_h'].copy_(lib.param('FrameLevel.h0').detach()[0].unsqueeze(0).expand(self.B, -1))
+        else:  # h0 [N_RNN, H0_MULT * D]: LSTM layers carry [s | c] (ops.py:552)
+            for tier, tag in (('BigFrameLevel', 'big'), ('FrameLevel', 'frm')):
+                h0 = lib.param(tier + '.h0').detach()
+                for k in range(tt.N_RNN):
+                    self.states[(tag, 'h', k)].copy_(h0[k, :tt.DIM].unsqueeze(0).expand(self.B, -1))
+                    if tt.RNN_TYPE == 'LSTM':
+                        self.states[(tag, 'c', k)].copy_(h0[k, tt.DIM:].unsqueeze(0).expand(self.B, -1))
+
+    def close(self):
+        if self.plan:
+            _lib.load().samplernn_generate_destroy(self.plan)
+            self.plan = None

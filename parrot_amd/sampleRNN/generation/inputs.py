@@ -1,0 +1,195 @@
+"""What a generation plan is fed, computed on the host with numpy alone (no torch, no device): the seeded draw in Python
+integers -- the hash sr_pick_kernel and srp_kernel key their uniforms with, a seed per utterance, the draw modes' names --
+and where utterances go: into the streams of one packed plan (pack_utterances and the arrays of such a packing) and into
+the segments of a plan that never ends (schedule_segment)."""
+import numpy
+
+
+def config():
+    """The three_tier module, whose globals are the run configuration.  Looked up when called: configure() rebinds those
+    globals between plans, and three_tier imports this package, so no module of it imports three_tier while loading."""
+    from ..models.conditional import three_tier
+    return three_tier
+
+
+_M64 = (1 << 64) - 1
+DRAW_K1, DRAW_K2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9
+DRAW_MODES = {'sequential': 0, 'scan': 1}
+
+
+def u64(seed):
+    """A seed as the unsigned 64-bit integer the kernels see."""
+    return int(seed) & _M64
+
+
+def _splitmix64(x):
+    """The splitmix64 finaliser, in Python integers masked to 64 bits."""
+    x ^= x >> 30
+    x = (x * 0xBF58476D1CE4E5B9) & _M64
+    x ^= x >> 27
+    x = (x * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def utterance_draw_u01(seed, n):
+    """The uniform an utterance with seed `seed` draws at counter n = the sample's index in the utterance's own buffer,
+    prefix included (the first generated sample has n = BIG_FRAME_SIZE): seed ^ K1 (n + 1) through the splitmix64
+    finaliser; the top 24 bits plus one half, rounded to float32, times 2^-24.  What sr_pick_kernel and the pick of
+    srp_kernel compute with per-utterance draws (samplernn_generate_set_utterance_draws); no stream term."""
+    x = _splitmix64(u64(seed) ^ u64(DRAW_K1 * (int(n) + 1)))
+    return float(numpy.float32(float(x >> 40) + 0.5)) / 2.0 ** 24
+
+
+def utterance_seed(seed, index):
+    """One 64-bit seed per utterance from a base seed: seed + K1 (index + 1) through the splitmix64 finaliser."""
+    return _splitmix64(u64(u64(seed) + DRAW_K1 * (int(index) + 1)))
+
+
+def _seed_image(seeds):
+    """Unsigned 64-bit seeds (Python integers or any integer array) as their two's-complement int64 image."""
+    flat = [u64(s) for s in numpy.asarray(seeds, dtype=object).reshape(-1)]
+    return numpy.array(flat, dtype=numpy.uint64).reshape(numpy.shape(seeds)).view(numpy.int64)
+
+
+def draw_mode_code(draw_mode):
+    """SampleRnnGenDesc::draw_mode of a mode's name; ValueError on any other name (no device call)."""
+    if draw_mode not in DRAW_MODES:
+        raise ValueError("draw_mode must be one of %s, got %r" % (sorted(DRAW_MODES), draw_mode))
+    return DRAW_MODES[draw_mode]
+
+
+def _per_utterance(seeds, temperatures, n, default_temperature):
+    """seeds: one per utterance; temperatures: one per utterance, a scalar, or None = default_temperature."""
+    seeds = [u64(s) for s in seeds]
+    if temperatures is None:
+        temperatures = default_temperature
+    temperatures = [float(temperatures)] * n if numpy.ndim(temperatures) == 0 else [float(t) for t in temperatures]
+    if len(seeds) != n or len(temperatures) != n:
+        raise ValueError("%d utterances, but %d seeds and %d temperatures" % (n, len(seeds), len(temperatures)))
+    return seeds, temperatures
+
+
+
+def pack_utterances(lengths, n_streams):
+    """Places utterances of `lengths[i]` big frames one after the other into `n_streams` streams: longest first onto the
+    least-loaded stream (ties: the lower utterance index first, the lower stream index).  Returns (stream, first_slot, T):
+    utterance i occupies slots first_slot[i] .. first_slot[i] + lengths[i] - 1 of stream[i]; T = max(2, the longest
+    stream) is the frame count of the plan that runs them.  Pure Python and deterministic."""
+    lengths = [int(n) for n in lengths]
+    n_streams = int(n_streams)
+    if n_streams < 1:
+        raise ValueError("n_streams must be at least 1")
+    if any(n < 1 for n in lengths):
+        raise ValueError("every utterance needs at least one frame (its prefix slot)")
+    load = [0] * n_streams
+    stream, first_slot = [0] * len(lengths), [0] * len(lengths)
+    for i in sorted(range(len(lengths)), key=lambda i: (-lengths[i], i)):
+        b = min(range(n_streams), key=lambda b: (load[b], b))
+        stream[i], first_slot[i] = b, load[b]
+        load[b] += lengths[i]
+    return stream, first_slot, max(2, max(load))
+
+
+def start_row(first_slot, T):
+    """The row of a plan of T slots that holds the start flag, the seed and the temperature of the utterance whose Q/2
+    prefix is slot first_slot: the slot of its frame 1, where the generator overwrites the slot before with the prefix and
+    restarts the stream's state.  None when that row is not below T: the prefix alone in the last slot draws nothing."""
+    return first_slot + 1 if first_slot + 1 < T else None
+
+
+def build_packed_inputs(utterances, stream, first_slot, T, n_streams):
+    """(features [T, n_streams, 63] float32, starts [T, n_streams] int32) of a packing: utterance i's frame j at slot
+    first_slot[i] + j of stream[i], zeros elsewhere; starts = 1 on every utterance's start_row."""
+    feat_dim = numpy.asarray(utterances[0]).shape[1] if len(utterances) else config().FEAT_DIM
+    features = numpy.zeros((T, n_streams, feat_dim), dtype='float32')
+    starts = numpy.zeros((T, n_streams), dtype='int32')
+    for u, b, s in zip(utterances, stream, first_slot):
+        u = numpy.asarray(u, dtype='float32')
+        if not (0 <= b < n_streams and 0 <= s and s + u.shape[0] <= T):
+            raise ValueError("utterance of %d frames does not fit at slot %d of stream %d" % (u.shape[0], s, b))
+        features[s:s + u.shape[0], b] = u
+        row = start_row(s, T)
+        if row is not None:
+            starts[row, b] = 1
+    return features, starts
+
+
+def build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams):
+    """(utt_seed [T, n_streams] uint64, utt_temp [T, n_streams] float32) of a packing, the sibling of build_packed_inputs:
+    utterance i's seed and temperature on its start_row; zeros elsewhere."""
+    utt_seed = numpy.zeros((T, n_streams), dtype=numpy.uint64)
+    utt_temp = numpy.zeros((T, n_streams), dtype='float32')
+    for sd, tp, b, s in zip(seeds, temperatures, stream, first_slot):
+        if not (0 <= b < n_streams and 0 <= s < T):
+            raise ValueError("no slot %d in stream %d" % (s, b))
+        row = start_row(s, T)
+        if row is not None:
+            utt_seed[row, b], utt_temp[row, b] = u64(sd), tp
+    return utt_seed, utt_temp
+
+
+def unpack_samples(samples, lengths, stream, first_slot):
+    """The utterances' pieces of a packed run's samples [B, 80 T].  (The prefix of a one-frame utterance in the last slot
+    of the plan has no period behind it that would write it: it is Q/2 by definition.)"""
+    tt = config()
+    BFS = tt.BIG_FRAME_SIZE
+    T = samples.shape[1] // BFS
+    out = []
+    for n, b, s in zip(lengths, stream, first_slot):
+        piece = numpy.array(samples[b, BFS * s:BFS * (s + n)], dtype='int32')
+        if start_row(s, T) is None:
+            piece[:BFS] = tt.Q_ZERO
+        out.append(piece)
+    return out
+
+
+def schedule_segment(running, queue, n_streams, segment_frames):
+    """One segment of continuous admission (StreamingGenerator): which utterance takes which slots 1 .. segment_frames of
+    which stream.  Pure Python and deterministic; the arguments are not changed.
+
+    running[b] = None or (ticket, placed, length): stream b's utterance and how many of its `length` frames earlier
+    segments have placed (>= 1; its last one is the ring's slot 0).  queue = [(ticket, length), ...], oldest first.
+    The rules: a stream goes on with its utterance from slot 1; when that ends at slot k < segment_frames (k = 0: the
+    stream was idle) a queued utterance may begin at slot k + 1 of the same stream -- that slot is its Q/2 prefix, its
+    start flag is on the slot of its frame 1, in this segment or at slot 1 of the next.  The queue is FIFO: its oldest
+    utterance takes the earliest free slot of any stream (the lower stream index among equals), until no stream has a
+    free slot or the queue is empty.
+
+    Returns (placements, starts, n_slots, running', queue'): placements = [(ticket, stream, slot, frame, count)] --
+    frames frame .. frame + count - 1 of the utterance at slots slot .. slot + count - 1 --, starts = [(slot, stream)],
+    n_slots = the busiest stream's last slot (the periods the segment runs: no period with every stream idle; 0 = nothing to
+    run).  Whenever an utterance is left unfinished it has reached slot segment_frames = n_slots, so its next frame is
+    slot 1 of the next segment."""
+    B, S = int(n_streams), int(segment_frames)
+    if B < 1:
+        raise ValueError("n_streams must be at least 1")
+    if S < 1:
+        raise ValueError("segment_frames must be at least 1")
+    running = list(running)
+    if len(running) != B:
+        raise ValueError("running must hold one entry per stream")
+    queue = [(t, int(n)) for t, n in queue]
+    placements = []
+    free = [1] * B  # the stream's first slot nobody has taken yet
+
+    def place(b, ticket, placed, length):
+        count = min(length - placed, S - free[b] + 1)
+        placements.append((ticket, b, free[b], placed, count))
+        free[b] += count
+        running[b] = (ticket, placed + count, length) if placed + count < length else None
+
+    for b in range(B):
+        if running[b] is not None:
+            place(b, *running[b])
+    while queue:
+        b = min(range(B), key=lambda b: (free[b], b))
+        if free[b] > S or running[b] is not None:  # (a stream whose utterance goes on is full: free = S + 1)
+            break
+        ticket, length = queue.pop(0)
+        if length < 1:
+            raise ValueError("every utterance needs at least one frame (its prefix slot)")
+        place(b, ticket, 0, length)
+    placements.sort(key=lambda x: (x[1], x[2]))
+    starts = [(slot + 1 - frame, b) for _, b, slot, frame, count in placements if frame <= 1 < frame + count]
+    n_slots = max(free) - 1
+    return placements, starts, n_slots, running, queue

@@ -1,0 +1,216 @@
+"""Entry points on top of the device plan: a list of utterances packed into one run (generate_packed), a rectangle in
+segments on a ring (generate_stream) and continuous admission on a plan that never ends (StreamingGenerator)."""
+import numpy
+
+from .device import DeviceGenerator, device_loop_guard
+from .inputs import (_per_utterance, build_packed_draws, build_packed_inputs, config, pack_utterances, schedule_segment,
+                     start_row, u64, unpack_samples)
+
+
+def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_graph=True, seeds=None,
+                    temperatures=None, draw_mode='sequential'):
+    """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
+    utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
+    n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
+
+    At temperature = 0 element i equals what DeviceGenerator returns for that utterance generated on its own.  At
+    temperature > 0 without `seeds` the draws are seeded and repeatable, but they are keyed by the packed (sample index,
+    stream) of the run, so they are NOT the draws of the utterance's standalone run.
+
+    seeds = one unsigned 64-bit seed per utterance (temperatures = one temperature per utterance or a scalar; default:
+    `temperature` for all): the plan runs with per-utterance draws (DeviceGenerator(utterance_draws=True)).  Element i is
+    then a function of the model, the plan's shape (n_streams), the carrying stream, and the utterance's features, seed
+    and temperature: it equals, bit for bit, what a plain plan of n_streams streams in that mode returns for the utterance
+    carried alone in the same stream with the same seed and temperature, and does not depend on its slot, the order of
+    the list or its neighbours.  (The carrying stream is pack_utterances' choice, which does depend on the list.)
+
+    draw_mode: 'sequential' or 'scan', see DeviceGenerator.  (temperature's default: three_tier.TEMPERATURE as imported.)"""
+    device_loop_guard(draw_mode)
+    utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
+    if seeds is None and temperatures is not None:
+        raise ValueError("temperatures per utterance need seeds per utterance")
+    if seeds is not None:  # (before a plan is created)
+        seeds, temperatures = _per_utterance(seeds, temperatures, len(utterances), temperature)
+    if not utterances:
+        return []
+    stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
+    features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
+    gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
+                          utterance_draws=seeds is not None, draw_mode=draw_mode)
+    try:
+        draws = {}
+        if seeds is not None:
+            draws['seeds'], draws['temperatures'] = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
+        samples = gen.generate(features, starts, **draws).cpu().numpy()
+    finally:
+        gen.close()
+    return unpack_samples(samples, [u.shape[0] for u in utterances], stream, first_slot)
+
+
+def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_graph=True, gen=None, draw_mode='sequential'):
+    """Generator over a rectangle features [N, B, 63] on a plan of segment_frames + 1 slots used as a ring: yields int32
+    arrays [B, 80 n] -- the first one holds the Q/2 prefix and up to segment_frames frames, every later one up to
+    segment_frames frames -- whose concatenation is the [B, 80 N] result of DeviceGenerator(B, N).generate(features), bit
+    for bit, seeded draws included.  The plan does not grow with N, and the first samples are out after segment_frames
+    periods.  gen: a plain DeviceGenerator(B, segment_frames + 1) of the caller's to run on (it is left open; temperature,
+    seed, use_graph and draw_mode are then the plan's); default: a plan of its own for this call, with draw_mode
+    'sequential' or 'scan' (see DeviceGenerator) and temperature's default as in generate_packed."""
+    device_loop_guard(draw_mode)
+    features = numpy.asarray(features, dtype='float32')
+    S = int(segment_frames)
+    if S < 1:
+        raise ValueError("segment_frames must be at least 1")
+    if features.ndim != 3 or features.shape[0] < 2:
+        raise ValueError("features must be [N, B, %d] with N >= 2 (the prefix slot and one frame)" % config().FEAT_DIM)
+    N, B = features.shape[0], features.shape[1]
+    own = gen is None
+    if own:
+        gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph, draw_mode=draw_mode)
+    elif gen.packed or (gen.B, gen.T) != (B, S + 1):
+        raise ValueError("gen must be a plain plan of %d streams and %d slots" % (B, S + 1))
+    try:
+        k = min(S, N - 1)
+        yield gen.generate(features[:k + 1], n_frames=k).cpu().numpy()
+        done = k + 1
+        while done < N:
+            k = min(S, N - done)
+            yield gen.generate(features[done:done + k], resume=True, n_frames=k).cpu().numpy()
+            done += k
+    finally:
+        if own:
+            gen.close()
+
+
+class StreamingGenerator:
+    """Continuous admission on ONE packed plan of segment_frames + 1 slots that never ends: utterances are submitted at any
+    time, every step() runs one segment of the ring (schedule_segment decides who takes which slots) and hands out the
+    samples of every utterance that had slots in it.
+
+    The first 80 samples of an utterance's first chunk are its Q/2 prefix.  At temperature = 0 the concatenated chunks of
+    an utterance equal what a plain plan of n_streams returns for it carried in the same stream (record[ticket] =
+    (stream, absolute slot of its prefix)); at temperature > 0 without utterance_draws the draws are repeatable for the
+    same sequence of submit / step calls, but they are not the draws of the utterance's standalone run.
+
+    utterance_draws=True: submit takes the utterance's seed (required) and temperature (default: the generator's).  The
+    concatenated chunks of an utterance are then a function of the model, the plan's shape (n_streams; segment_frames does
+    not enter), the carrying stream, and the utterance's features, seed and temperature: they equal, bit for bit, what a
+    plain plan of n_streams streams in that mode returns for the utterance carried alone in stream record[ticket][0] with
+    the same seed and temperature, and do not depend on its slot, the segment boundaries, the submission order or its
+    neighbours.  (Which stream carries it is schedule_segment's choice, and that does depend on the traffic.)
+
+    run_segment(features [n, B, 63], starts [n, B], resume) -> samples [B, 80 n] of slots 1 .. n is the callable that
+    runs a segment; the default runs it on the device.  With utterance_draws it is called with two more keyword arguments,
+    seeds [n, B] uint64 and temperatures [n, B] float32: what the utterance whose start flag is on that row draws with.
+
+    draw_mode: 'sequential' or 'scan', the plan's (see DeviceGenerator); a run_segment of the caller's does not see it."""
+
+    def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
+                 utterance_draws=False, draw_mode='sequential'):
+        device_loop_guard(draw_mode)
+        self.B, self.S = int(n_streams), int(segment_frames)
+        if self.B < 1:
+            raise ValueError("n_streams must be at least 1")
+        if self.S < 1:
+            raise ValueError("segment_frames must be at least 1")
+        self.gen = None
+        self.utterance_draws = bool(utterance_draws)
+        self.temperature = float(temperature)
+        if run_segment is None:
+            self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
+                                       packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode)
+            run_segment = self._run_on_device
+        self._run = run_segment
+        self._resume = False
+        self._next_ticket = 0
+        self._slots_run = 0            # periods run so far: slot s of this segment is absolute slot _slots_run + s
+        self.running = [None] * self.B
+        self.queue = []
+        self._features = {}
+        self._draws = {}               # ticket -> (seed, temperature), until the utterance's start flag has been placed
+        self.record = {}
+
+    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None):
+        draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
+        if resume:
+            return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0], **draws).cpu().numpy()
+        n = features.shape[0]  # the first segment: slot 0 is the run's prefix slot, no stream uses it
+        features = numpy.concatenate([numpy.zeros_like(features[:1]), features])
+        starts = numpy.concatenate([numpy.zeros_like(starts[:1]), starts])
+        draws = {k: numpy.concatenate([numpy.zeros_like(v[:1]), v]) for k, v in draws.items()}
+        return self.gen.generate(features, starts, n_frames=n, **draws).cpu().numpy()[:, config().BIG_FRAME_SIZE:]
+
+    def submit(self, features, seed=None, temperature=None):
+        """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
+        seed (an unsigned 64-bit integer) and temperature (default: the generator's): with utterance_draws=True only, where
+        the seed is required."""
+        if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
+            raise ValueError("a seed (and a temperature) per utterance is given exactly when the generator was built with "
+                             "utterance_draws=True")
+        features = numpy.asarray(features, dtype='float32')
+        if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
+            raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
+        ticket = self._next_ticket
+        self._next_ticket += 1
+        if self.utterance_draws:
+            self._draws[ticket] = (u64(seed), self.temperature if temperature is None else float(temperature))
+        self._features[ticket] = features
+        self.queue.append((ticket, features.shape[0]))
+        return ticket
+
+    def idle(self):
+        return not self.queue and all(r is None for r in self.running)
+
+    def step(self):
+        """Runs one segment; returns [(ticket, chunk int32 [80 k], done)] for every utterance that had slots in it."""
+        placements, starts, n, self.running, self.queue = schedule_segment(self.running, self.queue, self.B, self.S)
+        if n == 0:
+            return []
+        tt = config()
+        BFS = tt.BIG_FRAME_SIZE
+        feats = numpy.zeros((n, self.B, tt.FEAT_DIM), dtype='float32')
+        flags = numpy.zeros((n, self.B), dtype='int32')
+        for ticket, b, slot, frame, count in placements:
+            feats[slot - 1:slot - 1 + count, b] = self._features[ticket][frame:frame + count]
+            if frame == 0:
+                self.record[ticket] = (b, self._slots_run + slot)
+        for slot, b in starts:
+            flags[slot - 1, b] = 1
+        draws = {}
+        if self.utterance_draws:
+            draws = dict(seeds=numpy.zeros((n, self.B), dtype=numpy.uint64),
+                         temperatures=numpy.zeros((n, self.B), dtype='float32'))
+            for ticket, b, slot, frame, count in placements:
+                if frame <= 1 < frame + count:
+                    # the utterance's start_row in the ring of this segment, whose slot 0 is the last slot of the segment
+                    # before (where its prefix may lie); the arrays hold the ring's rows 1 .. n
+                    row = start_row(slot - frame, n + 1) - 1
+                    assert flags[row, b] == 1
+                    draws['seeds'][row, b], draws['temperatures'][row, b] = self._draws[ticket]
+        samples = numpy.asarray(self._run(feats, flags, self._resume, **draws))
+        if samples.shape != (self.B, BFS * n):
+            raise ValueError("the segment runner returned %s, not %s" % (samples.shape, (self.B, BFS * n)))
+        self._resume = True
+        self._slots_run += n
+        out = []
+        for ticket, b, slot, frame, count in placements:
+            chunk = numpy.array(samples[b, BFS * (slot - 1):BFS * (slot - 1 + count)], dtype='int32')
+            if frame == 0:
+                chunk[:BFS] = tt.Q_ZERO  # (the period that would write it may lie in the next segment)
+            done = frame + count == self._features[ticket].shape[0]
+            if done:
+                del self._features[ticket]
+                self._draws.pop(ticket, None)
+            out.append((ticket, chunk, done))
+        return out
+
+    def drain(self):
+        """Steps until nothing is queued or running; returns the chunks of all those steps in order."""
+        out = []
+        while not self.idle():
+            out += self.step()
+        return out
+
+    def close(self):
+        if self.gen is not None:
+            self.gen.close()
+            self.gen = None

@@ -332,6 +332,46 @@ def gmm_head(reps):
     return res
 
 
+def samplernn_d1024():
+    """The three_tier module with the BASELINE configs[4] model in it: parameters deleted, D = 1024, and one dummy
+    compute_cost that registers all parameters with the reference initialisation."""
+    from parrot_amd.sampleRNN import lib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    lib.delete_all_params(); lib.set_device(dev)
+    tt.configure(DIM=1024, EMB_SIZE=256)
+    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+    with torch.no_grad():
+        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
+                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    return tt
+
+
+def alternate(gens, args, kw, reps):
+    """Every plan's generate(*args[k], **kw.get(k, {})) reps + 1 times in turn, each round starting one plan further on (no
+    plan always runs behind the same other one); the first round captures the graphs and is not counted.  Returns (call to
+    device idle in seconds per plan and counted round, every plan's last samples)."""
+    times, samples = {k: [] for k in gens}, {}
+    keys = list(gens)
+    for rep in range(reps + 1):
+        for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:
+            torch.cuda.synchronize(); t0 = time.time()
+            s = gens[k].generate(*args[k], **kw.get(k, {}))
+            torch.cuda.synchronize(); dt = time.time() - t0
+            samples[k] = s.cpu().numpy().copy()
+            if rep:
+                times[k].append(dt)
+    return times, samples
+
+
+def record(name, flag, res):
+    """A SampleRNN section's result: into the JSON line, and into the file `flag` names (default profiles/<name>.json)."""
+    out[name] = res
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(_arg(flag, os.path.join(root, "profiles", name + ".json")), "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+
+
 if "--gmm_head" in sys.argv:  # this leg alone, one JSON line
     print(json.dumps({"gmm_head": gmm_head(max(5, int(_arg("--reps", "5"))))}))
     sys.exit(0)
@@ -405,15 +445,8 @@ for name in GRU_BF16_SHAPES:
 
 # ---- configs[4]: SampleRNN 3-tier GRU D=1024, batch 32, greedy, 16 kHz mu-law
 if "samplernn_cfg5" in only:
-    from parrot_amd.sampleRNN import lib
-    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-    lib.delete_all_params(); lib.set_device(dev)
-    tt.configure(DIM=1024, EMB_SIZE=256)
+    tt = samplernn_d1024()
     B, T = 32, 26  # 25 generated big frames = 2000 samples per stream
-    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-    with torch.no_grad():  # registers all parameters with the reference initialisation
-        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
     gen = tt.DeviceGenerator(B, T, temperature=0.0)
     feats = torch.randn(T, B, 63, generator=g).numpy()
     for rep in range(2):
@@ -431,14 +464,7 @@ if "samplernn_cfg5" in only:
 # launch path, plans of both kinds alive in one process and run alternately; B = 32 is the anchor (one group: the same
 # kernel instantiation with the switch set and unset)
 if "samplernn_groups" in only:
-    from parrot_amd.sampleRNN import lib
-    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-    lib.delete_all_params(); lib.set_device(dev)
-    tt.configure(DIM=1024, EMB_SIZE=256)
-    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-    with torch.no_grad():  # registers all parameters with the reference initialisation
-        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    tt = samplernn_d1024()
     T, reps = 26, int(_arg("--reps", "5"))
     nsamp = (T - 1) * 80
     saved = {k: os.environ.get(k) for k in ("PARROT_SR_PERSIST", "PARROT_SR_PERSIST_GROUPS")}
@@ -451,12 +477,6 @@ if "samplernn_groups" in only:
             os.environ["PARROT_SR_PERSIST_GROUPS"] = str(groups)
         return tt.DeviceGenerator(B, T, temperature=0.0)
 
-    def run(gen, feats):
-        torch.cuda.synchronize(); t0 = time.time()
-        s = gen.generate(feats)
-        torch.cuda.synchronize()
-        return time.time() - t0, s.cpu().numpy().copy()
-
     res = {"dim": 1024, "samples_per_stream": nsamp, "alternations": reps, "batches": {}}
     for B in (32, 64, 128, 200):
         feats = torch.randn(T, B, 63, generator=g).numpy()
@@ -464,13 +484,7 @@ if "samplernn_groups" in only:
         if B == 32:
             gens["switch_unset"] = plan(B, 1, None)
         assert gens["groups"].persist_groups == -(-B // 32) and not gens["launches"].persistent
-        times, samples = {k: [] for k in gens}, {}
-        keys = list(gens)
-        for rep in range(reps + 1):  # (the first alternation captures the graphs: not counted)
-            for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:  # (no plan always runs behind the same other one)
-                dt, samples[k] = run(gens[k], feats)
-                if rep:
-                    times[k].append(dt)
+        times, samples = alternate(gens, {k: (feats,) for k in gens}, {}, reps)
         entry = {"row_groups": gens["groups"].persist_groups,
                  "rows_equal_to_launches": int((samples["groups"] == samples["launches"]).all(axis=1).sum())}
         for k, v in times.items():
@@ -485,26 +499,14 @@ if "samplernn_groups" in only:
             gen.close()
     for k, v in saved.items():
         os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
-    out["samplernn_groups"] = res
-    path = _arg("--groups-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                              "samplernn_groups.json"))
-    with open(path, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    record("samplernn_groups", "--groups-json", res)
 
 # ---- SampleRNN D=1024, 64 utterances of unequal length on 32 streams: (a) two rectangles of 32 in arrival order, each at
 # its own max(length); (b) one packed run (longest first onto the least-loaded stream, utterance starts inside the loop);
 # (c) the first rectangle on a packed plan whose starts are all zero against the plain plan of (a) -- what the extra launch
 # per period costs.  All plans alive in one process and run alternately.
 if "samplernn_packed" in only:
-    from parrot_amd.sampleRNN import lib
-    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-    lib.delete_all_params(); lib.set_device(dev)
-    tt.configure(DIM=1024, EMB_SIZE=256)
-    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-    with torch.no_grad():  # registers all parameters with the reference initialisation
-        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    tt = samplernn_d1024()
     B, N, LEN_SEED, reps = 32, 64, 1234, int(_arg("--reps", "5"))
     rs = np.random.RandomState(LEN_SEED)
     lengths = [int(n) for n in rs.randint(20, 201, size=N)]  # big frames of 5 ms: 0.1 .. 1 s of audio
@@ -525,16 +527,7 @@ if "samplernn_packed" in only:
     args = {"rect0": (rect[0],), "rect1": (rect[1],), "packed": (pf, ps),
             "rect0_on_packed_plan": (rect[0], np.zeros((rect[0].shape[0], B), dtype=np.int32))}
     assert all(gen.persistent for gen in gens.values())
-    times, samples = {k: [] for k in gens}, {}
-    keys = list(gens)
-    for rep in range(reps + 1):  # (the first alternation captures the graphs: not counted)
-        for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:  # (no plan always runs behind the same other one)
-            torch.cuda.synchronize(); t0 = time.time()
-            s = gens[k].generate(*args[k])
-            torch.cuda.synchronize(); dt = time.time() - t0
-            samples[k] = s.cpu().numpy().copy()
-            if rep:
-                times[k].append(dt)
+    times, samples = alternate(gens, args, {}, reps)
     for gen in gens.values():
         gen.close()
     pieces = tt.unpack_samples(samples["packed"], lengths, stream, first)
@@ -552,26 +545,14 @@ if "samplernn_packed" in only:
            "start_launch_us_per_period": round(1e6 * (med["rect0_on_packed_plan"] - med["rect0"]) / periods["rect0"], 2),
            "utterances_equal_to_rectangles": same,
            "zero_starts_bit_identical": bool((samples["rect0_on_packed_plan"] == samples["rect0"]).all())}
-    out["samplernn_packed"] = res
-    path = _arg("--packed-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                              "samplernn_packed.json"))
-    with open(path, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    record("samplernn_packed", "--packed-json", res)
 
 # ---- SampleRNN D=1024, B=32, 201 frames: the run in one piece against the same run in segments of 8 and of 40 frames on a
 # plan of S + 1 slots used as a ring (three_tier.generate_stream, samplernn_generate_run_segment).  All plans alive in one
 # process and run alternately; every time includes the samples' way to the host (one copy for the run in one piece, one
 # per segment -- behind samplernn_generate_status, which synchronises -- for the segmented runs).
 if "samplernn_stream" in only:
-    from parrot_amd.sampleRNN import lib
-    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-    lib.delete_all_params(); lib.set_device(dev)
-    tt.configure(DIM=1024, EMB_SIZE=256)
-    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-    with torch.no_grad():  # registers all parameters with the reference initialisation
-        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    tt = samplernn_d1024()
     B, N, SEGS, reps = 32, 201, (8, 40), int(_arg("--reps", "5"))
     feats = torch.randn(N, B, 63, generator=g).numpy()
     gens = {"one_shot": tt.DeviceGenerator(B, N, temperature=0.0)}
@@ -616,25 +597,13 @@ if "samplernn_stream" in only:
             e["us_per_boundary_over_one_shot"] = round(1e6 * (med[k] - med["one_shot"]) / bounds, 2)
             e["bit_identical_to_one_shot"] = bool(np.array_equal(samples[k], samples["one_shot"]))
         res["runs"][k] = e
-    out["samplernn_stream"] = res
-    path = _arg("--stream-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                              "samplernn_stream.json"))
-    with open(path, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    record("samplernn_stream", "--stream-json", res)
 
 # ---- SampleRNN D=1024, B=32: per-utterance seeds and temperatures (samplernn_generate_set_utterance_draws) against the plan's
 # key at temperature 1 -- the same draws, bit for bit, with seeds[b] = seed ^ K2 (b + 1) --, and a packed run whose teams mix
 # arg-max rows with draws at 0.5 / 1 / 2.  All plans alive in one process and run alternately.
 if "samplernn_utt_draws" in only:
-    from parrot_amd.sampleRNN import lib
-    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-    lib.delete_all_params(); lib.set_device(dev)
-    tt.configure(DIM=1024, EMB_SIZE=256)
-    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-    with torch.no_grad():  # registers all parameters with the reference initialisation
-        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    tt = samplernn_d1024()
     B, T, SEED, reps = 32, 26, 234, int(_arg("--reps", "3"))
     nsamp = (T - 1) * 80
     feats = torch.randn(T, B, 63, generator=g).numpy()
@@ -655,21 +624,11 @@ if "samplernn_utt_draws" in only:
             "packed_t0": tt.DeviceGenerator(B, Tp, temperature=0.0, packed=True),
             "packed_plan_key_t1": tt.DeviceGenerator(B, Tp, temperature=1.0, seed=SEED, packed=True),
             "packed_mixed_temperatures": tt.DeviceGenerator(B, Tp, packed=True, utterance_draws=True)}
-    args = {"plan_key_t1": ((feats,), {}), "plan_key_t0": ((feats,), {}),
-            "utterance_draws_t1": ((feats,), dict(seeds=key_seeds, temperatures=1.0)),
-            "packed_t0": ((pf, ps), {}), "packed_plan_key_t1": ((pf, ps), {}),
-            "packed_mixed_temperatures": ((pf, ps), dict(seeds=useed, temperatures=utemp))}
+    args = {k: (pf, ps) if k.startswith("packed") else (feats,) for k in gens}
+    kw = {"utterance_draws_t1": dict(seeds=key_seeds, temperatures=1.0),
+          "packed_mixed_temperatures": dict(seeds=useed, temperatures=utemp)}
     assert all(gen.persistent for gen in gens.values())
-    times, samples = {k: [] for k in gens}, {}
-    keys = list(gens)
-    for rep in range(reps + 1):  # (the first alternation captures the graphs: not counted)
-        for k in keys[rep % len(keys):] + keys[:rep % len(keys)]:  # (no plan always runs behind the same other one)
-            torch.cuda.synchronize(); t0 = time.time()
-            s = gens[k].generate(*args[k][0], **args[k][1])
-            torch.cuda.synchronize(); dt = time.time() - t0
-            samples[k] = s.cpu().numpy().copy()
-            if rep:
-                times[k].append(dt)
+    times, samples = alternate(gens, args, kw, reps)
     steps = {k: (gens[k].T - 1) * 80 for k in gens}
     for gen in gens.values():
         gen.close()
@@ -685,12 +644,7 @@ if "samplernn_utt_draws" in only:
                       "argmax_utterances": len(argmax_rows),
                       "argmax_utterances_equal_to_packed_t0": sum(int(np.array_equal(pieces["packed_mixed_temperatures"][i],
                                                                                      pieces["packed_t0"][i])) for i in argmax_rows)}}
-    out["samplernn_utt_draws"] = res
-    path = _arg("--utt-draws-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "samplernn_utt_draws.json"))
-    with open(path, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    record("samplernn_utt_draws", "--utt-draws-json", res)
 
 # ---- SampleRNN D=1024, B=32: the wave-parallel seeded draw (SampleRnnGenDesc::draw_mode = 1, DeviceGenerator(draw_mode='scan'))
 # against the sequential draw and argmax; the same with per-utterance draws; the launch path at B = 33; two row groups at
@@ -700,14 +654,7 @@ if "samplernn_draw_scan" in only:
     import contextlib
     import ctypes
     from parrot_amd import _lib as plib
-    from parrot_amd.sampleRNN import lib
-    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
-    lib.delete_all_params(); lib.set_device(dev)
-    tt.configure(DIM=1024, EMB_SIZE=256)
-    seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
-    with torch.no_grad():  # registers all parameters with the reference initialisation
-        tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, 1, 1024, device=dev),
-                        torch.zeros(2, 1, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+    tt = samplernn_d1024()
     T, SEED, reps = 101, 234, int(_arg("--reps", "5"))
     nsamp = (T - 1) * 80
     feats = {B: torch.randn(T, B, 63, generator=g).numpy() for B in (32, 33, 64)}
@@ -822,12 +769,7 @@ if "samplernn_draw_scan" in only:
             "bit_identical_t0": bool(np.array_equal(samples["argmax"], samples["parent_argmax"])),
             "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
             "t0": pair("argmax"), "t1": pair("sequential_t1")}
-    out["samplernn_draw_scan"] = res
-    path = _arg("--draw-scan-json", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                                                 "samplernn_draw_scan.json"))
-    with open(path, "w") as f:
-        json.dump(res, f, indent=1)
-        f.write("\n")
+    record("samplernn_draw_scan", "--draw-scan-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
