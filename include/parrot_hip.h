@@ -822,6 +822,16 @@ int samplernn_weightnorm_fold_bwd(const float* W, int ld, const float* g, const 
  *     (sequential: 2^-14), and terms below 2^-24 of the total are not lost.  A few draws per ten thousand differ from
  *     mode 0's by one code.
  *   Any other value: PARROT_ERR_BADARG.
+ * top_k: a draw at temperature > 0 is taken among the k most likely codes, in both modes and on every path.
+ *   The kept set is the k codes that come first when the codes are ordered by logit descending, then by code index
+ *   ascending: a tie at the cut-off goes to the lower index, the argmax's rule.  A kept code's term is e_q as above, every
+ *   other code's is 0.0f; the max, the key, the counter, the uniform, the comparison u01 * total < running sum and the order
+ *   of the float32 additions (the walk over all Q codes; the tree of mode 1) are unchanged -- adding 0.0f is exact.  Where no
+ *   code satisfies the comparison (u01 can be exactly 1.0) the pick is the highest kept code: in mode 0 the highest of all, in
+ *   mode 1 the highest kept code not above the code that falls through without truncation (Q - 1; the last code of lane l*).
+ *   top_k = 1 at any temperature > 0 therefore picks the argmax code.  0 (a zeroed field) or >= Q: no truncation, the samples
+ *   and the executed instructions of the pick are those of a build without the field.  < 0: PARROT_ERR_BADARG.  1 .. Q-1
+ *   with Q > 256: PARROT_ERR_UNSUPPORTED.  At temperature <= 0 the pick is the argmax and top_k is ignored.
  * samples: [B, BFS*T] int32, first BFS entries = Q/2 set by the caller; big_h / frm_h hold the
  * initial states (learned h0) on entry and the final states on return.  The weight buffers must not change during a
  * plan's life: create makes fragment-major copies of the tiers' matrices for the step kernel (single-GRU tiers) and, on the
@@ -831,7 +841,11 @@ int samplernn_weightnorm_fold_bwd(const float* W, int ld, const float* g, const 
  * T-1 and resumes from where the last call ended, with the buffers of this descriptor used as a ring.
  * ------------------------------------------------------------------------------------------ */
 typedef struct SampleRnnGenDesc {
-    int B, D, T, Q, FS, BFS, feat_dim, use_graph;
+    int B, D, T, Q, FS, BFS, feat_dim;
+    /* The descriptor has no spare word and its size and offsets are part of the ABI, so top_k shares the four bytes that
+     * were `int use_graph` (a flag: 0 or 1).  On the little-endian hosts this library runs on, a caller compiled against
+     * the earlier header still sets use_graph and leaves top_k = 0. */
+    short use_graph, top_k;
     float temperature; int draw_mode;
     unsigned long long seed;
     const float* big_Win_frames; const float* big_Win_feats; const float* big_bin; /* [BFS,D],[feat,D],[D] */
@@ -933,6 +947,14 @@ int samplernn_generate_run_segment(void* plan, int n_periods, int resume, void* 
  * PARROT_ERR_BADARG for a null plan or pointer (checked before any device call) and for a plan that has run: the period
  * graphs hold the pointers by value. */
 int samplernn_generate_set_utterance_draws(void* plan, const unsigned long long* utt_seed, const float* utt_temp);
+/* Per-utterance top-k.  utt_top_k [T][B] (int): device memory, indexed and owned like utt_temp; row f holds the top_k of an
+ * utterance that begins at big frame f, with the meaning of SampleRnnGenDesc::top_k (<= 0 or >= Q: no truncation).  The
+ * entry of a stream takes it wherever it takes the seed and the temperature, so the streams of one plan -- and the four
+ * rows of one team of the persistent kernel -- may mix truncations as they mix temperatures.  Valid only after
+ * samplernn_generate_set_utterance_draws, and refused once the plan has run (PARROT_ERR_BADARG for either, and for a null
+ * plan or pointer; no device call); PARROT_ERR_UNSUPPORTED when Q > 256.  Without it every utterance takes the descriptor's
+ * top_k. */
+int samplernn_generate_set_utterance_top_k(void* plan, const int* utt_top_k);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

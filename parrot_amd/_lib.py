@@ -154,7 +154,9 @@ class SampleDesc(C.Structure):
 
 
 class SampleRnnGenDesc(C.Structure):
-    _fields_ = ([(n, C.c_int) for n in ("B", "D", "T", "Q", "FS", "BFS", "feat_dim", "use_graph")] +
+    # (top_k shares the four bytes that were `int use_graph`: the descriptor has no spare word, see the header)
+    _fields_ = ([(n, C.c_int) for n in ("B", "D", "T", "Q", "FS", "BFS", "feat_dim")] +
+                [("use_graph", C.c_short), ("top_k", C.c_short)] +
                 [("temperature", C.c_float), ("draw_mode", C.c_int), ("seed", C.c_ulonglong)] +
                 [(n, C.c_void_p) for n in (
                     "big_Win_frames", "big_Win_feats", "big_bin", "big_U", "big_bU", "big_Wg", "big_Wc",
@@ -259,6 +261,7 @@ SIGNATURES = {
     "samplernn_generate_run": (_i, [_vp, _vp]),
     "samplernn_generate_run_segment": (_i, [_vp, _i, _i, _vp]),
     "samplernn_generate_set_utterance_draws": (_i, [_vp, _vp, _vp]),
+    "samplernn_generate_set_utterance_top_k": (_i, [_vp, _vp]),
     "samplernn_persist_floats": (C.c_longlong, [C.POINTER(SampleRnnGenDesc)]),
     "samplernn_generate_is_persistent": (_i, [_vp]),
     "samplernn_generate_persist_groups": (_i, [_vp]),

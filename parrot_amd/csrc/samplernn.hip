@@ -60,11 +60,12 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 }
 
 // samples[b][t] = argmax_q logits[b][q] (lowest index on ties, like numpy / Theano argmax), or a
-// temperature-scaled multinomial draw from a counter-based generator when temperature > 0.
+// temperature-scaled multinomial draw from a counter-based generator when temperature > 0 -- among all Q codes, or among
+// the top_k most likely ones (SampleRnnGenDesc::top_k: terms 0.0f outside the kept set, same sums, same uniform).
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
                                                       unsigned long long seed, const unsigned long long* __restrict__ origin,
-                                                      const SrUttDraw* __restrict__ utt, int draw_mode) {
+                                                      const SrUttDraw* __restrict__ utt, int draw_mode, int top_k) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int t = tbase[0] + toff;
@@ -73,7 +74,11 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
     // key = what the draw's counter is hashed with: the plan's seed and the stream, or (per-utterance entries, a uniform
     // branch) the utterance's seed alone, with its own temperature and its counter taken back by the run index of its prefix
     unsigned long long key = seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1)), off = 0;
-    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; }
+    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; top_k = utt[b].top_k; }
+    // top-k truncation (a uniform branch of both draws; create admits it for Q <= 256 only): wave 0 selects the kept set with
+    // the persistent kernel's helper, four codes per lane at most; off, a draw runs the instructions it always ran
+    top_k = __builtin_amdgcn_readfirstlane(top_k);
+    const bool trunc = top_k > 0 && top_k < Q && Q <= 256;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int q = tid; q < Q; q += 256) {
@@ -101,8 +106,50 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
             const float mx = sv[0];
             const int n = Q / 64;
             const float u01 = srp_u01(key, origin[0] + (unsigned long long)(t + 1) - off);
-            const int pick = srp_scan_draw([&](int j) { return expf((lg[n * tid + j] - mx) / temperature); }, n, tid, u01);
+            int pick;
+            if (trunc) {  // (n <= 4) the terms outside the kept set are 0.0f, the fall-through picks the highest kept code
+                unsigned f[4];
+                int idx[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { idx[j] = n * tid + j; f[j] = j < n ? srp_order_image(lg[min(idx[j], Q - 1)]) : 0u; }
+                const unsigned keep = srp_topk_keep<4>(f, idx, top_k);
+                const int lk = keep ? n * tid + 31 - __clz((int)keep) : -1;
+                pick = srp_scan_draw<true>([&](int j) { return (keep >> j) & 1u ? expf((lg[n * tid + j] - mx) / temperature) : 0.f; },
+                                           n, tid, u01, lk);
+            } else {
+                pick = srp_scan_draw([&](int j) { return expf((lg[n * tid + j] - mx) / temperature); }, n, tid, u01);
+            }
             if (tid == 0) samples[(size_t)b * len + t] = pick;
+        }
+        return;
+    }
+    if (trunc) {
+        // the sequential walk among the kept codes: wave 0 selects (lane l holds codes l + 64 m) and leaves the kept flags
+        // in si; thread 0 walks all Q codes in today's order with 0.0f for the others (adding it is exact)
+        if (tid < 64) {
+            unsigned f[4];
+            int idx[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) { idx[m] = tid + 64 * m; f[m] = idx[m] < Q ? srp_order_image(lg[idx[m]]) : 0u; }
+            const unsigned keep = srp_topk_keep<4>(f, idx, top_k);
+            const int last = srp_topk_last<4>(keep, idx);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) si[idx[m]] = (int)((keep >> m) & 1u);
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            if (tid == 0) {
+                const float mx = sv[0];
+                float tot = 0.f;
+                for (int q = 0; q < Q; ++q) tot += si[q] ? expf((lg[q] - mx) / temperature) : 0.f;
+                const float u = srp_u01(key, origin[0] + (unsigned long long)(t + 1) - off) * tot;
+                float c = 0.f;
+                int pick = last;
+                for (int q = 0; q < Q; ++q) {
+                    c += si[q] ? expf((lg[q] - mx) / temperature) : 0.f;
+                    if (u < c) { pick = q; break; }
+                }
+                samples[(size_t)b * len + t] = pick;
+            }
         }
         return;
     }
@@ -165,13 +212,14 @@ __global__ void sr_tick_kernel(int* tbase, int inc, int set, unsigned long long*
 // so entry b = (row 1 of the caller's arrays, off 0).  Outside the period graphs, beside the sr_tick_kernel call that sets
 // tbase; a start flagged at frame 1 then rewrites the same values.
 __global__ __launch_bounds__(256) void sr_utt_init_kernel(SrUttDraw* __restrict__ utt, const unsigned long long* __restrict__ seed1,
-                                                          const float* __restrict__ temp1, int B) {
+                                                          const float* __restrict__ temp1, const int* __restrict__ top_k1,
+                                                          int top_k, int B) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     utt[b].seed = seed1[b];
     utt[b].off = 0;
     utt[b].temperature = temp1[b];
-    utt[b].pad = 0;
+    utt[b].top_k = top_k1 ? top_k1[b] : top_k;  // (no array of the caller's: the plan's)
 }
 
 // Segment boundary of a resumed run (samplernn_generate_run_segment, resume = 1): the first launch of the segment, outside
@@ -213,8 +261,8 @@ __global__ __launch_bounds__(256) void sr_resume_kernel(const SrResumeArgs a) {
 // finds -- slot f - 1 = Q/2 (all three levels read their history from `samples`), every state that outlives a period =
 // the learned h0, its row of the next frame's gate product = h0 . Wg (the copy run() kept), and the carry of its team
 // invalidated (the other rows of the team then read their true history from `samples` too).  With per-utterance draws
-// the stream's entry becomes (utt_seed[f][b], run index of the prefix slot = origin + (f - 1) BFS, utt_temp[f][b]).  Rows
-// without a flag are not touched.
+// the stream's entry becomes (utt_seed[f][b], run index of the prefix slot = origin + (f - 1) BFS, utt_temp[f][b],
+// utt_top_k[f][b] or the plan's top_k).  Rows without a flag are not touched.
 struct SrStartArgs {
     const int* starts; const int* tbase;
     int* samples;
@@ -226,6 +274,7 @@ struct SrStartArgs {
     SrUttDraw* utt;                   // [B] per-utterance draw entries (null: none)
     const unsigned long long* utt_seed; const float* utt_temp;  // [T][B] both, indexed like starts
     const unsigned long long* origin;
+    const int* utt_top_k; int top_k;  // [T][B] like utt_temp, or null: every utterance takes the plan's top_k
 };
 
 __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
@@ -241,6 +290,7 @@ __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
         a.utt[b].seed = a.utt_seed[(size_t)f * a.B + b];
         a.utt[b].off = a.origin[0] + (unsigned long long)(f - 1) * (unsigned long long)a.BFS;
         a.utt[b].temperature = a.utt_temp[(size_t)f * a.B + b];
+        a.utt[b].top_k = a.utt_top_k ? a.utt_top_k[(size_t)f * a.B + b] : a.top_k;
     }
 }
 
@@ -294,6 +344,8 @@ struct SrPlan {
         utt_seed = seed; utt_temp = temp;
         return 0;
     }
+    // samplernn_generate_set_utterance_top_k: the caller's [T][B] truncations beside them (null: the plan's top_k for all)
+    const int* utt_top_k = nullptr;
     int make_origin() {
         if (hipMalloc(&origin, sizeof(unsigned long long)) != hipSuccess) { origin = nullptr; return 1; }
         return (int)hipMemset(origin, 0, sizeof(unsigned long long));
@@ -512,6 +564,7 @@ struct SrPlan {
         if (persist && winu) { a.gpre = gpre; a.gpre0 = gpre0; }
         if (persist) a.carry = srp_carry_keys(d.persist_ws, d.D, d.Q, groups);
         a.utt = utt; a.utt_seed = utt_seed; a.utt_temp = utt_temp; a.origin = origin;
+        a.utt_top_k = utt_top_k; a.top_k = d.top_k;
         hipLaunchKernelGGL(sr_start_kernel, dim3(d.B), dim3(256), 0, st, a);
         return (int)hipGetLastError();
     }
@@ -616,7 +669,7 @@ struct SrPlan {
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
-                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode;
+                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode; sa.top_k = d.top_k;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -641,7 +694,8 @@ struct SrPlan {
                 SR_TRY(linear(d.o2, D, d.W3, D, D, D, d.b3, nullptr, 0, d.o3, D, SK_ACT_RELU, st));
                 SR_TRY(linear(d.o3, D, d.W4, d.Q, D, d.Q, d.b4, nullptr, 0, d.logits, d.Q, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
-                                   d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode);
+                                   d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode,
+                                   d.top_k);
             }
         }
         hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
@@ -670,7 +724,7 @@ struct SrPlan {
             if (e != hipSuccess) return (int)e;
             if (utt) {  // every stream's first utterance: row 1 of the caller's arrays, prefix in slot 0
                 hipLaunchKernelGGL(sr_utt_init_kernel, dim3(ceil_div(d.B, 256)), dim3(256), 0, st, utt, utt_seed + d.B,
-                                   utt_temp + d.B, d.B);
+                                   utt_temp + d.B, utt_top_k ? utt_top_k + d.B : (const int*)nullptr, d.top_k, d.B);
                 e = hipGetLastError();
                 if (e != hipSuccess) return (int)e;
             }
@@ -732,6 +786,9 @@ int samplernn_generate_create(const SampleRnnGenDesc* desc, void** plan) { PH_EN
     if (desc->starts && (!desc->big_h0 || !desc->frm_h0)) return PARROT_ERR_BADARG;
     // (draw_mode 1: every lane of the drawing wave owns Q / 64 codes)
     if (desc->draw_mode < 0 || desc->draw_mode > 1 || (desc->draw_mode == 1 && desc->Q % 64 != 0)) return PARROT_ERR_BADARG;
+    // (top_k = 0 or >= Q: no truncation; the selection holds at most four codes per lane of one wave)
+    if (desc->top_k < 0) return PARROT_ERR_BADARG;
+    if (desc->top_k >= 1 && desc->top_k < desc->Q && desc->Q > 256) return PARROT_ERR_UNSUPPORTED;
     if (desc->n_rnn > 0) {
         if (desc->lstm && (!desc->gate_ws || !desc->layer_tmp)) return PARROT_ERR_BADARG;
         for (int k = 0; k < desc->n_rnn; ++k) {
@@ -797,6 +854,16 @@ int samplernn_generate_set_utterance_draws(void* plan, const unsigned long long*
     if (p->has_run) return PARROT_ERR_BADARG;  // the period graphs hold the pointers by value
     PH_ENTRY();
     return p->set_utt(utt_seed, utt_temp);
+}
+
+// (no HIP call at all: the pointer is handed to the kernels that fill the entries)
+int samplernn_generate_set_utterance_top_k(void* plan, const int* utt_top_k) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !utt_top_k || !p->utt) return PARROT_ERR_BADARG;  // only after samplernn_generate_set_utterance_draws
+    if (p->has_run) return PARROT_ERR_BADARG;                    // the period graphs hold the pointers by value
+    if (p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
+    p->utt_top_k = utt_top_k;
+    return 0;
 }
 
 int samplernn_generate_run(void* plan, void* stream) {

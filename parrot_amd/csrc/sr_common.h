@@ -65,6 +65,8 @@ struct SrpShared {
     float mx[SRP_ROWS];
     // per-utterance draw entries of the group's rows (SrpArgs::utt; unused without): parked here, not in registers
     float utemp[SRP_ROWS];
+    int utopk[SRP_ROWS];
+    int ulast[SRP_ROWS];  // the highest kept code of a truncated sequential draw (srp_kernel's pick)
     int upad;
     unsigned long long useed[SRP_ROWS], uoff[SRP_ROWS];
 };
@@ -148,6 +150,59 @@ __device__ __forceinline__ int srp_argmax_row(const f32x4* __restrict__ lg, int 
     return srp_wave_min(bv == best ? bi : 0x7fffffff);
 }
 
+// Top-k truncation of a draw (SampleRnnGenDesc::top_k): the kept set is the k codes that come first when the codes are
+// ordered by logit descending, then by code index ascending (a tie at the cut-off goes to the lower index, the argmax's rule).
+// srp_order_image: the order-preserving unsigned image of a float32 logit, a > b <=> image(a) > image(b); -0.0 and +0.0, equal
+// as logits, share one image.  Image 0 belongs to a NaN pattern no logit holds: it marks "no code" (a lane's padding).
+__device__ __forceinline__ unsigned srp_order_image(float v) {
+    unsigned u = __float_as_uint(v);
+    u = u == 0x80000000u ? 0u : u;
+    return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+}
+// Selection by one whole wave, whatever codes a lane holds: f[j] = the image of the lane's j-th logit (0: no code),
+// idx[j] = its code index in 0 .. 255, 1 <= k < the number of codes, k wave-uniform.  Returns the lane's kept codes, bit j.
+// A binary search over the 40-bit key (image, 255 - index), most significant bit first.  32 rounds find V = the largest
+// image that at least k codes reach.  Then every code gets its rank in the cut-off's tie, t = 511 above V, 256 - index at V,
+// 0 below, and 8 rounds find Y = the largest bound in 0 .. 255 that at least k codes exceed: the kept codes are those with
+// t > Y -- all above V and the lowest indices of the tie.  A round is N compares, N ballots and their popcounts; the state
+// (V, Y) is scalar and no lane mask outlives its round; the control flow is uniform; no LDS.
+template <int N>
+__device__ __forceinline__ unsigned srp_topk_keep(const unsigned (&f)[N], const int (&idx)[N], int k) {
+    unsigned v = 0;
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned x = v | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) cnt += (int)__popcll(__ballot(f[j] >= x));
+        v = cnt >= k ? x : v;
+    }
+    unsigned t[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) t[j] = f[j] > v ? 511u : f[j] == v ? (unsigned)(256 - idx[j]) : 0u;
+    unsigned y = 0;
+#pragma unroll 1
+    for (int bit = 7; bit >= 0; --bit) {
+        const unsigned x = y | (1u << bit);
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < N; ++j) cnt += (int)__popcll(__ballot(t[j] > x));
+        y = cnt >= k ? x : y;
+    }
+    unsigned keep = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) keep |= t[j] > y ? 1u << j : 0u;
+    return keep;
+}
+// The highest kept code of the wave (every lane receives it): what a sequential walk falls through to
+template <int N>
+__device__ __forceinline__ int srp_topk_last(unsigned keep, const int (&idx)[N]) {
+    int hi = -1;
+#pragma unroll
+    for (int j = 0; j < N; ++j) hi = (keep >> j) & 1u ? max(hi, idx[j]) : hi;
+    return -srp_wave_min(-hi);
+}
+
 // 24-bit uniform of a seeded draw: splitmix64 finaliser of key ^ K1 * counter, the middle of one of 2^24 cells of (0, 1)
 __device__ __forceinline__ float srp_u01(unsigned long long key, unsigned long long ctr) {
     unsigned long long x = key ^ (0x9E3779B97F4A7C15ull * ctr);
@@ -164,8 +219,12 @@ __device__ __forceinline__ float srp_u01(unsigned long long key, unsigned long l
 //   s_l = w_l (row 0), R_{k-1} + w_l (row k) with the row totals chained R_0 = T_0, R_1 = R_0 + T_1, R_2 = R_1 + T_2
 // tot = s_63, u = u01 * tot, l* = the lowest lane with u < s_l (none: the pick is Q - 1), and inside l* the terms are added
 // one at a time to s_{l*-1} (0 for lane 0): the first code with u < c, or the lane's last code.  Every lane returns the pick.
-template <class F>
-__device__ __forceinline__ int srp_scan_draw(F term, int n, int lane, float u01) {
+// TK (a truncated draw: the terms of the codes outside the kept set are 0.0f, lk = the lane's highest kept code, -1 for
+// none): both fall-through picks become the highest kept code not above the one they name without truncation -- the
+// highest kept code of all for Q - 1, the highest kept code of lanes 0 .. l* for the lane's last code (there is one: u < s_l*
+// needs s_l* > 0, and a sum of masked terms alone is exactly 0).  TK = false: the code as it was.
+template <bool TK = false, class F>
+__device__ __forceinline__ int srp_scan_draw(F term, int n, int lane, float u01, int lk = -1) {
     float p = term(0);
     for (int j = 1; j < n; ++j) p = __fadd_rn(p, term(j));
     float w = p;
@@ -183,10 +242,17 @@ __device__ __forceinline__ int srp_scan_draw(F term, int n, int lane, float u01)
     const float s =row == 0 ? w : __fadd_rn(row == 1 ? r0 : row == 2 ? r1 : r2, w);
     const float u = u01 * __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 63));
     const unsigned long long hit = __ballot(u < s);
-    if (hit == 0) return 64 * n - 1;
+    const unsigned long long has = TK ? __ballot(lk >= 0) : 0ull;  // lanes that hold a kept code
+    // the highest kept code of lanes 0 .. l (no such lane, which cannot happen: the lowest kept code)
+    auto kept_up_to = [&](int l) {
+        const unsigned long long m = has & (~0ull >> (63 - l));
+        const int src = m ? 63 - (int)__builtin_clzll(m) : (int)__builtin_ctzll(has | (1ull << 63));
+        return __builtin_amdgcn_readlane(lk, __builtin_amdgcn_readfirstlane(src));
+    };
+    if (hit == 0) return TK ? kept_up_to(63) : 64 * n - 1;
     const int ls = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(hit));
     const float below = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), max(ls - 1, 0)));
-    int pick = n * ls + n - 1;
+    int pick = TK ? kept_up_to(ls) : n * ls + n - 1;
     if (lane == ls) {
         float c = ls == 0 ? 0.f : below;
         for (int j = 0; j < n; ++j) {

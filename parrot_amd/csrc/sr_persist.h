@@ -7,9 +7,10 @@
 // entries in force the seeded draw of buffer index t in stream b hashes seed ^ K1 (origin + t - off + 1) -- no stream
 // term --, where off is the run index (origin + buffer index) of the first sample of the utterance's Q/2 prefix slot: the
 // counter is the sample's index in the utterance's own buffer, wherever the utterance sits.  temperature <= 0: argmax.
+// top_k: the utterance's truncation (samplernn_generate_set_utterance_top_k; the plan's without); outside 1 .. Q-1: none.
 struct SrUttDraw {
     unsigned long long seed, off;
-    float temperature; int pad;
+    float temperature; int top_k;
 };
 
 struct SrpArgs {
@@ -47,6 +48,9 @@ struct SrpArgs {
     // SampleRnnGenDesc::draw_mode: 0 = one lane walks the codes (the default's bits), 1 = the wave-parallel draw
     // (sr_common.h, srp_scan_draw).  A uniform branch of the pick, like utt.
     int draw_mode;
+    // SampleRnnGenDesc::top_k: a draw at temperature > 0 is taken among the k most likely codes (sr_common.h, srp_topk_keep);
+    // outside 1 .. Q-1: among all of them, by the instructions of the pick without this field.  With utt: the entry's top_k.
+    int top_k;
 };
 
 // PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8

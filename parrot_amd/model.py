@@ -1869,19 +1869,22 @@ class SampleRnn(Brick):
         return self.three_tier.compute_cost(sequences, features, h0, big_h0, reset, mask)
 
     def sample_raw(self, test_feats, features_length, tag, path_to_save, pack_streams=0, stream_frames=0, utterance_seed=None,
-                   draw_mode='sequential'):
+                   draw_mode='sequential', top_k=0):
         """pack_streams = N > 0: the utterances (row i cut at features_length[i]) are packed one after the other into N
         streams of one generation plan (three_tier.generate_packed) instead of one rectangle of num_steps frames.
         stream_frames = S > 0: they run through a three_tier.StreamingGenerator (pack_streams or 32 streams) in segments of
         S frames, and each wav is written as its utterance finishes.
         utterance_seed = S (None: off): utterance i draws with three_tier.utterance_seed(S, i), whichever of the three ways
         it runs: its samples do not depend on where it was placed.
-        draw_mode = 'sequential' or 'scan' (three_tier.DeviceGenerator): ValueError on any other name, before any device call."""
+        draw_mode = 'sequential' or 'scan' (three_tier.DeviceGenerator): ValueError on any other name, before any device call.
+        top_k = k > 0: the draws at temperature > 0 are taken among the k most likely codes (three_tier.DeviceGenerator); 0:
+        among all; ValueError on a negative one, before any device call."""
         tt = self.three_tier
         tt.draw_mode_code(draw_mode)
+        tt.top_k_code(top_k)
         fns = tt.getting_generation_functions(None, None, None, None, None)
         return tt.generate_and_save_samples(
             tag, path_to_save=path_to_save, features=test_feats, features_length=features_length,
             noise_level=0., big_frame_level_generate_fn=fns[0], frame_level_generate_fn=fns[1],
             sample_level_generate_fn=fns[2], npy_address=None, pack_streams=pack_streams, stream_frames=stream_frames,
-            utterance_seed=utterance_seed, draw_mode=draw_mode)
+            utterance_seed=utterance_seed, draw_mode=draw_mode, top_k=top_k)

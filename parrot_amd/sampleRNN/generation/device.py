@@ -8,13 +8,15 @@ from ... import _lib
 from ... import ops as hip
 from .. import lib
 from ..lib import ops as lops
-from .inputs import _seed_image, config, draw_mode_code
+from .inputs import _seed_image, config, draw_mode_code, top_k_array, top_k_code
 
 
-def device_loop_guard(draw_mode):
+def device_loop_guard(draw_mode, top_k=0):
     """What every entry to the device-resident loop checks before any device call: draw_mode's code (ValueError on an
-    unknown name), and that the model has no skip-connection stacks, which the loop does not take."""
+    unknown name), top_k (ValueError on a negative one), and that the model has no skip-connection stacks, which the loop
+    does not take."""
     mode = draw_mode_code(draw_mode)
+    top_k_code(top_k)
     if config().SKIP_CONN:
         raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
     return mode
@@ -24,7 +26,7 @@ class DeviceGenerator:
     """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
 
     def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
-                 draw_mode='sequential'):
+                 draw_mode='sequential', top_k=0):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
         three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
 
@@ -41,9 +43,16 @@ class DeviceGenerator:
         draw_mode: how a draw at temperature > 0 finds its code.  'sequential' (default): one lane walks the 256 codes, the
         samples every earlier version drew.  'scan': the wave-parallel draw (SampleRnnGenDesc::draw_mode = 1) -- the same
         terms and uniforms, the CDF as a fixed tree of float32 sums; faster, and a different (equally valid) rounding of the
-        CDF, so a few draws per ten thousand land on the neighbouring code.  Argmax (temperature <= 0) is the same in both."""
+        CDF, so a few draws per ten thousand land on the neighbouring code.  Argmax (temperature <= 0) is the same in both.
+
+        top_k = k > 0: a draw at temperature > 0 is taken among the k most likely codes (SampleRnnGenDesc::top_k) -- the k
+        first codes by logit descending, then by index ascending; every other code's term is 0 in the same sums, with the
+        same uniforms, in both draw modes.  0 (default) or k >= Q_LEVELS: among all codes, the samples of every earlier
+        version.  k = 1 picks the argmax.  With utterance_draws=True it is what an utterance draws with unless
+        generate(..., top_ks=) names its own.  Negative: ValueError."""
         self.draw_mode = draw_mode
-        mode = device_loop_guard(draw_mode)
+        mode = device_loop_guard(draw_mode, top_k)
+        self.top_k = top_k_code(top_k)
         self.B, self.T = batch, n_frames
         self.packed = bool(packed)
         self.utterance_draws = bool(utterance_draws)
@@ -108,6 +117,7 @@ class DeviceGenerator:
         d = _lib.SampleRnnGenDesc()
         d.B, d.D, d.T, d.Q, d.FS, d.BFS, d.feat_dim, d.use_graph = batch, D, n_frames, Q, FS, BFS, tt.FEAT_DIM, int(use_graph)
         d.temperature, d.seed, d.draw_mode = float(temperature), int(seed), mode
+        d.top_k = self.top_k if self.top_k < Q else 0  # (k >= Q: no truncation)
         for k, v in list(w.items()) + list(self.ws.items()):
             setattr(d, k, v.data_ptr())
         if not self.single:
@@ -143,14 +153,16 @@ class DeviceGenerator:
             # two's-complement image of the unsigned 64-bit seed
             self.ws['utt_seed'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int64)
             self.ws['utt_temp'] = torch.zeros(n_frames, batch, **f)
+            self.ws['utt_top_k'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int32)
             self.set_utterance_draws()
 
     def set_utterance_draws(self):
-        """Hands the plan its per-utterance seed and temperature arrays; refused (HipCallError) once the plan has run."""
+        """Hands the plan its per-utterance seed, temperature and top_k arrays; refused (HipCallError) once the plan has run."""
         _lib.call('samplernn_generate_set_utterance_draws', self.plan, self.ws['utt_seed'].data_ptr(),
                   self.ws['utt_temp'].data_ptr())
+        _lib.call('samplernn_generate_set_utterance_top_k', self.plan, self.ws['utt_top_k'].data_ptr())
 
-    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None):
+    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
         frame f, whose Q/2 prefix is slot f - 1.
@@ -166,16 +178,20 @@ class DeviceGenerator:
         [rows, B] aligned with starts -- row f, stream b holds what the utterance that starts[f][b] flags draws with, and the
         row of slot 1 of a run that does not resume what every stream's first utterance draws with --; on a plain plan [B],
         one utterance per stream, with resume=False only (the segments that resume go on with them).  Seeds are unsigned
-        64-bit integers (Python integers or an integer array)."""
-        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures)
-        self._stage(features, starts, seeds, temperatures, segment, rows, first)
+        64-bit integers (Python integers or an integer array).
+
+        top_ks (optional, accepted exactly where seeds is): integers of the same shape as seeds, or one integer for all --
+        the top_k each utterance draws with (0 or >= Q_LEVELS: no truncation); omitted, every utterance takes the plan's
+        top_k.  A negative value or another shape: ValueError."""
+        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures, top_ks)
+        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks)
         self._launch(segment, resume, k)
         if not segment:
             return self.ws['samples']
         BFS = config().BIG_FRAME_SIZE
         return self.ws['samples'][:, BFS * first:BFS * (k + 1)].clone()
 
-    def _resolve(self, starts, resume, n_frames, seeds, temperatures):
+    def _resolve(self, starts, resume, n_frames, seeds, temperatures, top_ks=None):
         """Which arguments this plan takes in which kind of run -> (segment, resume, k, rows, first): a run in segments or
         in one piece, k frames to generate, `rows` rows of input for the ring's slots from `first` on."""
         if (starts is not None) != self.packed:
@@ -185,15 +201,20 @@ class DeviceGenerator:
         if (seeds is not None) != takes_draws or (temperatures is not None) != takes_draws:
             raise ValueError("seeds and temperatures must both be given exactly when the plan was built with "
                              "utterance_draws=True (a plain plan takes them with resume=False only)")
+        if top_ks is not None and not takes_draws:
+            raise ValueError("top_ks is accepted only where seeds is: on a plan built with utterance_draws=True (a plain "
+                             "plan takes them with resume=False only)")
         if resume and not self._has_run:
             raise ValueError("resume=True needs a run to continue: call generate(..., resume=False) first")
         k = self.T - 1 if n_frames is None else int(n_frames)
         if not 1 <= k <= self.T - 1:
             raise ValueError("n_frames must be in 1 .. T-1 = %d, got %d" % (self.T - 1, k))
         rows = k if resume else (k + 1 if n_frames is not None else self.T)
+        if top_ks is not None:  # (its values and shape before anything is staged on the device)
+            top_k_code(top_ks) if numpy.ndim(top_ks) == 0 else top_k_array(top_ks, (rows, self.B) if self.packed else (self.B,))
         return resume or n_frames is not None, resume, k, rows, 1 if resume else 0
 
-    def _stage(self, features, starts, seeds, temperatures, segment, rows, first):
+    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None):
         """Checks the arrays' shapes and copies them into rows first .. first + rows - 1 of the workspace."""
         ws = self.ws
         feats = torch.as_tensor(features)
@@ -212,8 +233,13 @@ class DeviceGenerator:
                 else numpy.asarray(temperatures, dtype='float32')
             if sd.shape != want or tp.shape != want:
                 raise ValueError("seeds and temperatures must be %s, got %s and %s" % (list(want), sd.shape, tp.shape))
+            if top_ks is None or numpy.ndim(top_ks) == 0:
+                tk = numpy.full(want, top_k_code(self.top_k if top_ks is None else top_ks), dtype=numpy.int32)
+            else:
+                tk = top_k_array(top_ks, want)
             # (a plain plan: one utterance per stream, prefix in slot 0 -- the row of slot 1, like a start flagged there)
             lo, hi = (first, first + rows) if self.packed else (1, 2)
+            ws['utt_top_k'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tk).reshape(hi - lo, self.B)).to(ws['utt_top_k'].device))
             ws['utt_seed'][lo:hi].copy_(torch.from_numpy(sd.reshape(hi - lo, self.B)).to(ws['utt_seed'].device))
             ws['utt_temp'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tp).reshape(hi - lo, self.B)).to(ws['utt_temp'].device))
         ws['features'][first:first + rows].copy_(feats.to(ws['features'].device, torch.float32))

@@ -1,5 +1,6 @@
 """What a generation plan is fed, computed on the host with numpy alone (no torch, no device): the seeded draw in Python
-integers -- the hash sr_pick_kernel and srp_kernel key their uniforms with, a seed per utterance, the draw modes' names --
+integers -- the hash sr_pick_kernel and srp_kernel key their uniforms with, a seed per utterance, the draw modes' names,
+the checks of a top_k --
 and where utterances go: into the streams of one packed plan (pack_utterances and the arrays of such a packing) and into
 the segments of a plan that never ends (schedule_segment)."""
 import numpy
@@ -56,6 +57,37 @@ def draw_mode_code(draw_mode):
     if draw_mode not in DRAW_MODES:
         raise ValueError("draw_mode must be one of %s, got %r" % (sorted(DRAW_MODES), draw_mode))
     return DRAW_MODES[draw_mode]
+
+
+def top_k_code(top_k):
+    """SampleRnnGenDesc::top_k of a plan's or an utterance's top_k: the int itself, 0 = no truncation; ValueError on a
+    negative value or on anything that is not an integer (no device call)."""
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, numpy.integer)):
+        raise ValueError("top_k must be an integer >= 0 (0: no truncation), got %r" % (top_k,))
+    if top_k < 0:
+        raise ValueError("top_k must be >= 0 (0: no truncation), got %d" % top_k)
+    return min(int(top_k), 2 ** 31 - 1)
+
+
+def top_k_array(top_ks, shape):
+    """Per-utterance top_k values as the int32 array of `shape` a plan is fed: ValueError on another shape, a negative
+    value or a non-integer array (no device call).  Values >= Q_LEVELS mean no truncation, like 0."""
+    a = numpy.asarray(top_ks)
+    if a.dtype.kind not in 'iu' or a.shape != tuple(shape):
+        raise ValueError("top_ks must be integers of shape %s, got %s of %s" % (list(shape), a.dtype, list(a.shape)))
+    if a.size and a.min() < 0:
+        raise ValueError("top_ks must be >= 0 (0: no truncation)")
+    return numpy.minimum(a, 2 ** 31 - 1).astype(numpy.int32)
+
+
+def _per_utterance_top_k(top_ks, n, default_top_k):
+    """top_ks: one per utterance or a scalar; None = default_top_k for all."""
+    if top_ks is None:
+        top_ks = default_top_k
+    top_ks = [top_ks] * n if numpy.ndim(top_ks) == 0 else list(top_ks)
+    if len(top_ks) != n:
+        raise ValueError("%d utterances, but %d top_ks" % (n, len(top_ks)))
+    return [top_k_code(k) for k in top_ks]
 
 
 def _per_utterance(seeds, temperatures, n, default_temperature):
@@ -126,6 +158,19 @@ def build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams):
         if row is not None:
             utt_seed[row, b], utt_temp[row, b] = u64(sd), tp
     return utt_seed, utt_temp
+
+
+def build_packed_top_k(top_ks, stream, first_slot, T, n_streams):
+    """utt_top_k [T, n_streams] int32 of a packing, the sibling of build_packed_draws: utterance i's top_k on its
+    start_row; zeros (no truncation) elsewhere."""
+    utt_top_k = numpy.zeros((T, n_streams), dtype=numpy.int32)
+    for k, b, s in zip(top_ks, stream, first_slot):
+        if not (0 <= b < n_streams and 0 <= s < T):
+            raise ValueError("no slot %d in stream %d" % (s, b))
+        row = start_row(s, T)
+        if row is not None:
+            utt_top_k[row, b] = top_k_code(k)
+    return utt_top_k
 
 
 def unpack_samples(samples, lengths, stream, first_slot):

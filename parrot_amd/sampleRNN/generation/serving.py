@@ -3,12 +3,12 @@ segments on a ring (generate_stream) and continuous admission on a plan that nev
 import numpy
 
 from .device import DeviceGenerator, device_loop_guard
-from .inputs import (_per_utterance, build_packed_draws, build_packed_inputs, config, pack_utterances, schedule_segment,
-                     start_row, u64, unpack_samples)
+from .inputs import (_per_utterance, _per_utterance_top_k, build_packed_draws, build_packed_inputs, build_packed_top_k,
+                     config, pack_utterances, schedule_segment, start_row, top_k_code, u64, unpack_samples)
 
 
 def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_graph=True, seeds=None,
-                    temperatures=None, draw_mode='sequential'):
+                    temperatures=None, draw_mode='sequential', top_k=0, top_ks=None):
     """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
     utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
     n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
@@ -24,38 +24,46 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
     carried alone in the same stream with the same seed and temperature, and does not depend on its slot, the order of
     the list or its neighbours.  (The carrying stream is pack_utterances' choice, which does depend on the list.)
 
-    draw_mode: 'sequential' or 'scan', see DeviceGenerator.  (temperature's default: three_tier.TEMPERATURE as imported.)"""
-    device_loop_guard(draw_mode)
+    draw_mode: 'sequential' or 'scan', see DeviceGenerator.  (temperature's default: three_tier.TEMPERATURE as imported.)
+
+    top_k: the draws at temperature > 0 are taken among the k most likely codes (0: among all; see DeviceGenerator).
+    top_ks = one top_k per utterance (needs `seeds`; default: `top_k` for all)."""
+    device_loop_guard(draw_mode, top_k)
     utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
     if seeds is None and temperatures is not None:
         raise ValueError("temperatures per utterance need seeds per utterance")
+    if seeds is None and top_ks is not None:
+        raise ValueError("top_ks per utterance need seeds per utterance")
     if seeds is not None:  # (before a plan is created)
         seeds, temperatures = _per_utterance(seeds, temperatures, len(utterances), temperature)
+        top_ks = _per_utterance_top_k(top_ks, len(utterances), top_k)
     if not utterances:
         return []
     stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
     features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
     gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
-                          utterance_draws=seeds is not None, draw_mode=draw_mode)
+                          utterance_draws=seeds is not None, draw_mode=draw_mode, top_k=top_k)
     try:
         draws = {}
         if seeds is not None:
             draws['seeds'], draws['temperatures'] = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
+            draws['top_ks'] = build_packed_top_k(top_ks, stream, first_slot, T, n_streams)
         samples = gen.generate(features, starts, **draws).cpu().numpy()
     finally:
         gen.close()
     return unpack_samples(samples, [u.shape[0] for u in utterances], stream, first_slot)
 
 
-def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_graph=True, gen=None, draw_mode='sequential'):
+def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_graph=True, gen=None, draw_mode='sequential',
+                    top_k=0):
     """Generator over a rectangle features [N, B, 63] on a plan of segment_frames + 1 slots used as a ring: yields int32
     arrays [B, 80 n] -- the first one holds the Q/2 prefix and up to segment_frames frames, every later one up to
     segment_frames frames -- whose concatenation is the [B, 80 N] result of DeviceGenerator(B, N).generate(features), bit
     for bit, seeded draws included.  The plan does not grow with N, and the first samples are out after segment_frames
     periods.  gen: a plain DeviceGenerator(B, segment_frames + 1) of the caller's to run on (it is left open; temperature,
-    seed, use_graph and draw_mode are then the plan's); default: a plan of its own for this call, with draw_mode
-    'sequential' or 'scan' (see DeviceGenerator) and temperature's default as in generate_packed."""
-    device_loop_guard(draw_mode)
+    seed, use_graph, draw_mode and top_k are then the plan's); default: a plan of its own for this call, with draw_mode
+    'sequential' or 'scan' and top_k (see DeviceGenerator) and temperature's default as in generate_packed."""
+    device_loop_guard(draw_mode, top_k)
     features = numpy.asarray(features, dtype='float32')
     S = int(segment_frames)
     if S < 1:
@@ -65,7 +73,8 @@ def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_gra
     N, B = features.shape[0], features.shape[1]
     own = gen is None
     if own:
-        gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph, draw_mode=draw_mode)
+        gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph, draw_mode=draw_mode,
+                              top_k=top_k)
     elif gen.packed or (gen.B, gen.T) != (B, S + 1):
         raise ValueError("gen must be a plain plan of %d streams and %d slots" % (B, S + 1))
     try:
@@ -102,11 +111,18 @@ class StreamingGenerator:
     runs a segment; the default runs it on the device.  With utterance_draws it is called with two more keyword arguments,
     seeds [n, B] uint64 and temperatures [n, B] float32: what the utterance whose start flag is on that row draws with.
 
-    draw_mode: 'sequential' or 'scan', the plan's (see DeviceGenerator); a run_segment of the caller's does not see it."""
+    draw_mode: 'sequential' or 'scan', the plan's (see DeviceGenerator); a run_segment of the caller's does not see it.
+
+    top_k: the plan's truncation (see DeviceGenerator), what every utterance draws with unless submit(..., top_k=) names
+    its own (utterance_draws=True only).  A generator that truncates -- its top_k is non-zero, or some utterance was
+    submitted with one -- calls run_segment with one more keyword argument, top_ks [n, B] int32: the top_k of the utterance
+    whose start flag is on that row, zeros elsewhere.  A generator that does not calls it exactly as before."""
 
     def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
-                 utterance_draws=False, draw_mode='sequential'):
-        device_loop_guard(draw_mode)
+                 utterance_draws=False, draw_mode='sequential', top_k=0):
+        device_loop_guard(draw_mode, top_k)
+        self.top_k = top_k_code(top_k)
+        self._truncates = self.top_k != 0
         self.B, self.S = int(n_streams), int(segment_frames)
         if self.B < 1:
             raise ValueError("n_streams must be at least 1")
@@ -117,7 +133,8 @@ class StreamingGenerator:
         self.temperature = float(temperature)
         if run_segment is None:
             self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
-                                       packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode)
+                                       packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode,
+                                       top_k=self.top_k)
             run_segment = self._run_on_device
         self._run = run_segment
         self._resume = False
@@ -127,10 +144,14 @@ class StreamingGenerator:
         self.queue = []
         self._features = {}
         self._draws = {}               # ticket -> (seed, temperature), until the utterance's start flag has been placed
+        self._top_ks = {}              # ticket -> top_k, likewise (utterance_draws only)
         self.record = {}
 
-    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None):
+    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None):
+        # (without utterance_draws the plan has no entries: every utterance draws with the plan's top_k)
         draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
+        if seeds is not None and top_ks is not None:
+            draws['top_ks'] = top_ks
         if resume:
             return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0], **draws).cpu().numpy()
         n = features.shape[0]  # the first segment: slot 0 is the run's prefix slot, no stream uses it
@@ -139,13 +160,17 @@ class StreamingGenerator:
         draws = {k: numpy.concatenate([numpy.zeros_like(v[:1]), v]) for k, v in draws.items()}
         return self.gen.generate(features, starts, n_frames=n, **draws).cpu().numpy()[:, config().BIG_FRAME_SIZE:]
 
-    def submit(self, features, seed=None, temperature=None):
+    def submit(self, features, seed=None, temperature=None, top_k=None):
         """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
-        seed (an unsigned 64-bit integer) and temperature (default: the generator's): with utterance_draws=True only, where
-        the seed is required."""
+        seed (an unsigned 64-bit integer), temperature and top_k (defaults: the generator's): with utterance_draws=True
+        only, where the seed is required."""
         if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
             raise ValueError("a seed (and a temperature) per utterance is given exactly when the generator was built with "
                              "utterance_draws=True")
+        if top_k is not None and not self.utterance_draws:
+            raise ValueError("a top_k per utterance needs a generator built with utterance_draws=True")
+        if top_k is not None:
+            top_k = top_k_code(top_k)
         features = numpy.asarray(features, dtype='float32')
         if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
             raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
@@ -153,6 +178,8 @@ class StreamingGenerator:
         self._next_ticket += 1
         if self.utterance_draws:
             self._draws[ticket] = (u64(seed), self.temperature if temperature is None else float(temperature))
+            self._top_ks[ticket] = self.top_k if top_k is None else top_k
+            self._truncates = self._truncates or top_k is not None
         self._features[ticket] = features
         self.queue.append((ticket, features.shape[0]))
         return ticket
@@ -186,6 +213,11 @@ class StreamingGenerator:
                     row = start_row(slot - frame, n + 1) - 1
                     assert flags[row, b] == 1
                     draws['seeds'][row, b], draws['temperatures'][row, b] = self._draws[ticket]
+        if self._truncates:  # (like the seeds: on the row of the utterance's start flag)
+            draws['top_ks'] = numpy.zeros((n, self.B), dtype=numpy.int32)
+            for ticket, b, slot, frame, count in placements:
+                if frame <= 1 < frame + count:
+                    draws['top_ks'][start_row(slot - frame, n + 1) - 1, b] = self._top_ks.get(ticket, self.top_k)
         samples = numpy.asarray(self._run(feats, flags, self._resume, **draws))
         if samples.shape != (self.B, BFS * n):
             raise ValueError("the segment runner returned %s, not %s" % (samples.shape, (self.B, BFS * n)))
@@ -200,6 +232,7 @@ class StreamingGenerator:
             if done:
                 del self._features[ticket]
                 self._draws.pop(ticket, None)
+                self._top_ks.pop(ticket, None)
             out.append((ticket, chunk, done))
         return out
 

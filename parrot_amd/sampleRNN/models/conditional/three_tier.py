@@ -196,8 +196,9 @@ def getting_generation_functions(sequences=None, h0=None, big_h0=None, reset=Non
 # the generation package's names, as they always were here (it reads the configuration above from this module when called)
 from ...generation import inputs as _inputs  # noqa: E402
 from ...generation.inputs import (DRAW_K1, DRAW_K2, DRAW_MODES, _M64, _per_utterance, _seed_image,  # noqa: E402,F401
-                                  _splitmix64, build_packed_draws, build_packed_inputs, draw_mode_code, pack_utterances,
-                                  schedule_segment, unpack_samples, utterance_draw_u01, utterance_seed)
+                                  _per_utterance_top_k, _splitmix64, build_packed_draws, build_packed_inputs,
+                                  build_packed_top_k, draw_mode_code, pack_utterances, schedule_segment, top_k_array,
+                                  top_k_code, unpack_samples, utterance_draw_u01, utterance_seed)
 from ...generation.device import DeviceGenerator  # noqa: E402
 from ...generation.serving import StreamingGenerator, generate_packed, generate_stream  # noqa: E402,F401
 
@@ -227,7 +228,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
                               big_frame_level_generate_fn=None, frame_level_generate_fn=None,
                               sample_level_generate_fn=None, npy_address=None, temperature=TEMPERATURE,
                               use_device_loop=True, pack_streams=0, stream_frames=0, utterance_seed=None,
-                              draw_mode='sequential'):
+                              draw_mode='sequential', top_k=0):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
     (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.
 
@@ -244,11 +245,16 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
     no longer depend on where it was placed.  Device loop only.
 
     draw_mode = 'sequential' (default) or 'scan': how the device loop's draws at temperature > 0 find their code
-    (DeviceGenerator), in the rectangle, packed and streamed modes alike.  'scan' needs the device loop."""
+    (DeviceGenerator), in the rectangle, packed and streamed modes alike.  'scan' needs the device loop.
+
+    top_k = k > 0: those draws are taken among the k most likely codes (DeviceGenerator), in all three modes; 0
+    (default): among all codes.  A non-zero top_k needs the device loop; a negative one is a ValueError."""
     total_time = time()
     device_loop = use_device_loop and not SKIP_CONN  # (the device loop does not take the skip-connection stacks)
     if draw_mode_code(draw_mode) != 0 and not device_loop:
         raise ValueError("draw_mode='scan' needs the device-resident generator")
+    if top_k_code(top_k) != 0 and not device_loop:
+        raise ValueError("top_k needs the device-resident generator")
     per_utt = utterance_seed is not None
     if per_utt and not device_loop:
         raise ValueError("utterance_seed needs the device-resident generator")
@@ -268,7 +274,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
     if placed and stream_frames > 0:
         n_streams = int(pack_streams) if pack_streams > 0 else 32
         sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature, utterance_draws=per_utt,
-                                draw_mode=draw_mode)
+                                draw_mode=draw_mode, top_k=top_k)
         chunks = [[] for _ in range(n_seqs)]
         pieces = [None] * n_seqs
         try:
@@ -289,7 +295,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         return pieces
     if placed:
         pieces = generate_packed(utts, n_streams=int(pack_streams), temperature=temperature, seeds=seeds,
-                                 draw_mode=draw_mode)
+                                 draw_mode=draw_mode, top_k=top_k)
         total_time = time() - total_time
         print("{} samples of {} seconds in all generated in {} seconds ({} packed streams).".format(
             n_seqs, seconds, total_time, int(pack_streams)))
@@ -297,7 +303,8 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
             _write_piece(tag, i, samp, path_to_save)
         return pieces
     if device_loop:
-        gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature, utterance_draws=per_utt, draw_mode=draw_mode)
+        gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature, utterance_draws=per_utt, draw_mode=draw_mode,
+                              top_k=top_k)
         draws = dict(seeds=seeds, temperatures=float(temperature)) if per_utt else {}
         samples = gen.generate(test_feats, **draws).cpu().numpy()
         gen.close()

@@ -5,7 +5,7 @@ and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
 --device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames,
---utterance_seed, --draw_mode.
+--utterance_seed, --draw_mode, --top_k.
 """
 from __future__ import annotations
 
@@ -143,6 +143,10 @@ def sample_parse(argv=None):
                              "'sequential' walks the 256 codes in one lane (the samples of every earlier version); 'scan' is "
                              "the wave-parallel draw -- same uniforms, the CDF summed as a fixed tree: faster, and a few "
                              "draws per ten thousand land on the neighbouring code (DESIGN.md 3.6)")
+    parser.add_argument('--top_k', type=int, default=0,
+                        help="K > 0 (with --raw_output): the SampleRNN vocoder's draws at temperature > 0 are taken among the "
+                             "K most likely of the 256 codes (ties at the cut-off go to the lower code), in both draw modes; "
+                             "0: among all of them (DESIGN.md 3.6)")
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
