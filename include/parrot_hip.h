@@ -832,6 +832,29 @@ int samplernn_weightnorm_fold_bwd(const float* W, int ld, const float* g, const 
  *   top_k = 1 at any temperature > 0 therefore picks the argmax code.  0 (a zeroed field) or >= Q: no truncation, the samples
  *   and the executed instructions of the pick are those of a build without the field.  < 0: PARROT_ERR_BADARG.  1 .. Q-1
  *   with Q > 256: PARROT_ERR_UNSUPPORTED.  At temperature <= 0 the pick is the argmax and top_k is ignored.
+ * top_p (nucleus; no field of the descriptor, which has no spare word: samplernn_generate_set_top_p below): for one draw with
+ *   logits lg[0..Q-1] and temperature > 0,
+ *   1. the terms are e_q as above; if top_k is active its kept set K is taken first, exactly as above, otherwise K is all codes;
+ *   2. the codes of K are ordered by logit descending, then by code index ascending (top_k's order, the argmax's tie rule),
+ *      tot_K is the mass of K, and the nucleus is the shortest prefix q_1 .. q_m of that order whose mass is >= p * tot_K;
+ *      m >= 1 always, and a tie at the cut-off goes to the lower indices;
+ *   3. every code outside the nucleus gets the term 0.0f;
+ *   4. everything else is what a top_k draw with k = m does: the same max, key, counter and 24-bit u01, the same comparison
+ *      u01 * tot < c, the same order of float32 additions (the walk over all Q codes in mode 0, the tree of mode 1) and the
+ *      same fall-through picks (the highest kept code; in mode 1 the highest kept code not above the code the scan falls
+ *      through to);
+ *   5. so a draw with top_p = p is indistinguishable from a draw with top_k = m.
+ *   The masses that find m are float32 sums of the non-negative terms in an order fixed per draw mode: a lane of the selecting
+ *   wave adds its codes left to right (codes l, l + 64, l + 128, l + 192 in mode 0; 4 l .. 4 l + 3, or l Q/64 .. with Q < 256,
+ *   in mode 1), and the 64 lane sums are added as a fixed tree -- lanes l and l^1, then l^2, then the mirror inside each
+ *   half-row of 8, then inside each row of 16, then rows (0 + 1) + (2 + 3).  The bar is the float32 product p * tot_K.  A tree
+ *   of round-to-nearest adds is monotone in every input, so the mass above a threshold is monotone in the threshold and the
+ *   cut is found by binary search.  m equals the exact (real-number) m whenever every prefix mass of the exact order lies
+ *   farther than 2^-14 from p, as a fraction of tot_K; for the same logits and draw mode the launch path and the persistent
+ *   kernel keep the same set.  Not promised: the same m in both draw modes inside that margin.
+ *   0.0 or >= 1.0: off, and the pick runs the instructions of a build without it.  < 0 or NaN: PARROT_ERR_BADARG.  Strictly
+ *   between 0 and 1 with Q > 256: PARROT_ERR_UNSUPPORTED.  At temperature <= 0 the pick is the argmax and top_p is ignored; a
+ *   very small p gives m = 1, the argmax.
  * samples: [B, BFS*T] int32, first BFS entries = Q/2 set by the caller; big_h / frm_h hold the
  * initial states (learned h0) on entry and the final states on return.  The weight buffers must not change during a
  * plan's life: create makes fragment-major copies of the tiers' matrices for the step kernel (single-GRU tiers) and, on the
@@ -955,6 +978,17 @@ int samplernn_generate_set_utterance_draws(void* plan, const unsigned long long*
  * plan or pointer; no device call); PARROT_ERR_UNSUPPORTED when Q > 256.  Without it every utterance takes the descriptor's
  * top_k. */
 int samplernn_generate_set_utterance_top_k(void* plan, const int* utt_top_k);
+/* The plan's top_p (see top_p above; a new plan's is 0.0 = off).  PARROT_ERR_BADARG for a null plan, for top_p < 0 or NaN
+ * and for a plan that has run (the period graphs hold the value); PARROT_ERR_UNSUPPORTED for 0 < top_p < 1 with Q > 256.
+ * No device call. */
+int samplernn_generate_set_top_p(void* plan, float top_p);
+/* Per-utterance top_p.  utt_top_p [T][B] (float): device memory, indexed and owned like utt_temp; row f holds the top_p of an
+ * utterance that begins at big frame f (not strictly between 0 and 1: no nucleus).  The entry of a stream takes it wherever
+ * it takes the seed, the temperature and top_k, so the streams of one plan -- and the four rows of one team of the
+ * persistent kernel -- may mix nuclei as they mix truncations and temperatures.  Valid only after
+ * samplernn_generate_set_utterance_draws, and refused once the plan has run (PARROT_ERR_BADARG for either, and for a null
+ * plan or pointer; no device call); PARROT_ERR_UNSUPPORTED when Q > 256.  Without it every utterance takes the plan's top_p. */
+int samplernn_generate_set_utterance_top_p(void* plan, const float* utt_top_p);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

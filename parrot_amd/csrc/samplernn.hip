@@ -61,11 +61,13 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 
 // samples[b][t] = argmax_q logits[b][q] (lowest index on ties, like numpy / Theano argmax), or a
 // temperature-scaled multinomial draw from a counter-based generator when temperature > 0 -- among all Q codes, or among
-// the top_k most likely ones (SampleRnnGenDesc::top_k: terms 0.0f outside the kept set, same sums, same uniform).
+// the top_k most likely ones (SampleRnnGenDesc::top_k: terms 0.0f outside the kept set, same sums, same uniform), or among
+// the nucleus of those (samplernn_generate_set_top_p: the shortest prefix of the same order with top_p of their mass).
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
                                                       unsigned long long seed, const unsigned long long* __restrict__ origin,
-                                                      const SrUttDraw* __restrict__ utt, int draw_mode, int top_k) {
+                                                      const SrUttDraw* __restrict__ utt, int draw_mode, int top_k,
+                                                      float top_p) {
     __shared__ float sv[256];
     __shared__ int si[256];
     const int t = tbase[0] + toff;
@@ -74,11 +76,15 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
     // key = what the draw's counter is hashed with: the plan's seed and the stream, or (per-utterance entries, a uniform
     // branch) the utterance's seed alone, with its own temperature and its counter taken back by the run index of its prefix
     unsigned long long key = seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1)), off = 0;
-    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; top_k = utt[b].top_k; }
+    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; top_k = utt[b].top_k; top_p = utt[b].top_p; }
     // top-k truncation (a uniform branch of both draws; create admits it for Q <= 256 only): wave 0 selects the kept set with
     // the persistent kernel's helper, four codes per lane at most; off, a draw runs the instructions it always ran
     top_k = __builtin_amdgcn_readfirstlane(top_k);
-    const bool trunc = top_k > 0 && top_k < Q && Q <= 256;
+    const bool use_k = top_k > 0 && top_k < Q && Q <= 256;
+    // the nucleus, behind top-k when both are active (the setters admit it for Q <= 256 only): srp_topp_keep, same lanes
+    top_p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(top_p)));
+    const bool use_p = top_p > 0.f && top_p < 1.f && Q <= 256;
+    const bool trunc = use_k || use_p;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int q = tid; q < Q; q += 256) {
@@ -112,7 +118,13 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
                 int idx[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) { idx[j] = n * tid + j; f[j] = j < n ? srp_order_image(lg[min(idx[j], Q - 1)]) : 0u; }
-                const unsigned keep = srp_topk_keep<4>(f, idx, top_k);
+                unsigned keep = use_k ? srp_topk_keep<4>(f, idx, top_k) : (1u << n) - 1u;
+                if (use_p) {
+                    float ek[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ek[j] = (keep >> j) & 1u ? expf((lg[min(idx[j], Q - 1)] - mx) / temperature) : 0.f;
+                    keep &= srp_topp_keep<4>(f, idx, ek, top_p);
+                }
                 const int lk = keep ? n * tid + 31 - __clz((int)keep) : -1;
                 pick = srp_scan_draw<true>([&](int j) { return (keep >> j) & 1u ? expf((lg[n * tid + j] - mx) / temperature) : 0.f; },
                                            n, tid, u01, lk);
@@ -131,7 +143,16 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
             int idx[4];
 #pragma unroll
             for (int m = 0; m < 4; ++m) { idx[m] = tid + 64 * m; f[m] = idx[m] < Q ? srp_order_image(lg[idx[m]]) : 0u; }
-            const unsigned keep = srp_topk_keep<4>(f, idx, top_k);
+            unsigned keep = 0;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) keep |= idx[m] < Q ? 1u << m : 0u;
+            if (use_k) keep = srp_topk_keep<4>(f, idx, top_k);
+            if (use_p) {
+                float ek[4];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) ek[m] = (keep >> m) & 1u ? expf((lg[min(idx[m], Q - 1)] - sv[0]) / temperature) : 0.f;
+                keep &= srp_topp_keep<4>(f, idx, ek, top_p);
+            }
             const int last = srp_topk_last<4>(keep, idx);
 #pragma unroll
             for (int m = 0; m < 4; ++m) si[idx[m]] = (int)((keep >> m) & 1u);
@@ -213,13 +234,15 @@ __global__ void sr_tick_kernel(int* tbase, int inc, int set, unsigned long long*
 // tbase; a start flagged at frame 1 then rewrites the same values.
 __global__ __launch_bounds__(256) void sr_utt_init_kernel(SrUttDraw* __restrict__ utt, const unsigned long long* __restrict__ seed1,
                                                           const float* __restrict__ temp1, const int* __restrict__ top_k1,
-                                                          int top_k, int B) {
+                                                          int top_k, const float* __restrict__ top_p1, float top_p, int B) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     utt[b].seed = seed1[b];
     utt[b].off = 0;
     utt[b].temperature = temp1[b];
     utt[b].top_k = top_k1 ? top_k1[b] : top_k;  // (no array of the caller's: the plan's)
+    utt[b].top_p = top_p1 ? top_p1[b] : top_p;
+    utt[b].pad = 0;
 }
 
 // Segment boundary of a resumed run (samplernn_generate_run_segment, resume = 1): the first launch of the segment, outside
@@ -262,7 +285,7 @@ __global__ __launch_bounds__(256) void sr_resume_kernel(const SrResumeArgs a) {
 // the learned h0, its row of the next frame's gate product = h0 . Wg (the copy run() kept), and the carry of its team
 // invalidated (the other rows of the team then read their true history from `samples` too).  With per-utterance draws
 // the stream's entry becomes (utt_seed[f][b], run index of the prefix slot = origin + (f - 1) BFS, utt_temp[f][b],
-// utt_top_k[f][b] or the plan's top_k).  Rows without a flag are not touched.
+// utt_top_k[f][b] or the plan's top_k, utt_top_p[f][b] or the plan's top_p).  Rows without a flag are not touched.
 struct SrStartArgs {
     const int* starts; const int* tbase;
     int* samples;
@@ -275,6 +298,7 @@ struct SrStartArgs {
     const unsigned long long* utt_seed; const float* utt_temp;  // [T][B] both, indexed like starts
     const unsigned long long* origin;
     const int* utt_top_k; int top_k;  // [T][B] like utt_temp, or null: every utterance takes the plan's top_k
+    const float* utt_top_p; float top_p;  // likewise (samplernn_generate_set_utterance_top_p, samplernn_generate_set_top_p)
 };
 
 __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
@@ -291,6 +315,7 @@ __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
         a.utt[b].off = a.origin[0] + (unsigned long long)(f - 1) * (unsigned long long)a.BFS;
         a.utt[b].temperature = a.utt_temp[(size_t)f * a.B + b];
         a.utt[b].top_k = a.utt_top_k ? a.utt_top_k[(size_t)f * a.B + b] : a.top_k;
+        a.utt[b].top_p = a.utt_top_p ? a.utt_top_p[(size_t)f * a.B + b] : a.top_p;
     }
 }
 
@@ -346,6 +371,10 @@ struct SrPlan {
     }
     // samplernn_generate_set_utterance_top_k: the caller's [T][B] truncations beside them (null: the plan's top_k for all)
     const int* utt_top_k = nullptr;
+    // samplernn_generate_set_top_p / _set_utterance_top_p: the plan's nucleus (0: off; the descriptor has no word for it) and
+    // the caller's [T][B] values (null: the plan's for all)
+    float top_p = 0.f;
+    const float* utt_top_p = nullptr;
     int make_origin() {
         if (hipMalloc(&origin, sizeof(unsigned long long)) != hipSuccess) { origin = nullptr; return 1; }
         return (int)hipMemset(origin, 0, sizeof(unsigned long long));
@@ -565,6 +594,7 @@ struct SrPlan {
         if (persist) a.carry = srp_carry_keys(d.persist_ws, d.D, d.Q, groups);
         a.utt = utt; a.utt_seed = utt_seed; a.utt_temp = utt_temp; a.origin = origin;
         a.utt_top_k = utt_top_k; a.top_k = d.top_k;
+        a.utt_top_p = utt_top_p; a.top_p = top_p;
         hipLaunchKernelGGL(sr_start_kernel, dim3(d.B), dim3(256), 0, st, a);
         return (int)hipGetLastError();
     }
@@ -669,7 +699,7 @@ struct SrPlan {
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
-                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode; sa.top_k = d.top_k;
+                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode; sa.top_k = srp_trunc_word(d.top_k, top_p, d.Q); sa.top_p = top_p;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -695,7 +725,7 @@ struct SrPlan {
                 SR_TRY(linear(d.o3, D, d.W4, d.Q, D, d.Q, d.b4, nullptr, 0, d.logits, d.Q, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
                                    d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode,
-                                   d.top_k);
+                                   d.top_k, top_p);
             }
         }
         hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
@@ -724,7 +754,8 @@ struct SrPlan {
             if (e != hipSuccess) return (int)e;
             if (utt) {  // every stream's first utterance: row 1 of the caller's arrays, prefix in slot 0
                 hipLaunchKernelGGL(sr_utt_init_kernel, dim3(ceil_div(d.B, 256)), dim3(256), 0, st, utt, utt_seed + d.B,
-                                   utt_temp + d.B, utt_top_k ? utt_top_k + d.B : (const int*)nullptr, d.top_k, d.B);
+                                   utt_temp + d.B, utt_top_k ? utt_top_k + d.B : (const int*)nullptr, d.top_k,
+                                   utt_top_p ? utt_top_p + d.B : (const float*)nullptr, top_p, d.B);
                 e = hipGetLastError();
                 if (e != hipSuccess) return (int)e;
             }
@@ -863,6 +894,26 @@ int samplernn_generate_set_utterance_top_k(void* plan, const int* utt_top_k) {
     if (p->has_run) return PARROT_ERR_BADARG;                    // the period graphs hold the pointers by value
     if (p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
     p->utt_top_k = utt_top_k;
+    return 0;
+}
+
+// The plan's nucleus.  (No HIP call: the value is handed to the kernels by the launches of the first run.)
+int samplernn_generate_set_top_p(void* plan, float top_p) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !(top_p >= 0.f)) return PARROT_ERR_BADARG;  // (a NaN compares false)
+    if (p->has_run) return PARROT_ERR_BADARG;             // the period graphs hold the arguments by value
+    if (top_p > 0.f && top_p < 1.f && p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
+    p->top_p = top_p;
+    return 0;
+}
+
+// (no HIP call either: the pointer is handed to the kernels that fill the entries)
+int samplernn_generate_set_utterance_top_p(void* plan, const float* utt_top_p) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !utt_top_p || !p->utt) return PARROT_ERR_BADARG;  // only after samplernn_generate_set_utterance_draws
+    if (p->has_run) return PARROT_ERR_BADARG;
+    if (p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
+    p->utt_top_p = utt_top_p;
     return 0;
 }
 

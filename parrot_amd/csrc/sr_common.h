@@ -66,6 +66,7 @@ struct SrpShared {
     // per-utterance draw entries of the group's rows (SrpArgs::utt; unused without): parked here, not in registers
     float utemp[SRP_ROWS];
     int utopk[SRP_ROWS];
+    float utopp[SRP_ROWS];
     int ulast[SRP_ROWS];  // the highest kept code of a truncated sequential draw (srp_kernel's pick)
     int upad;
     unsigned long long useed[SRP_ROWS], uoff[SRP_ROWS];
@@ -201,6 +202,70 @@ __device__ __forceinline__ int srp_topk_last(unsigned keep, const int (&idx)[N])
 #pragma unroll
     for (int j = 0; j < N; ++j) hi = (keep >> j) & 1u ? max(hi, idx[j]) : hi;
     return -srp_wave_min(-hi);
+}
+
+// Top-p (nucleus) truncation of a draw (samplernn_generate_set_top_p): among the codes K that top-k left (all of them without),
+// ordered as above, the kept set is the shortest prefix whose mass reaches p times the mass of K.  srp_wave_sum: the mass of
+// one term per lane as a fixed tree of round-to-nearest float32 adds, every lane receiving the same bits -- quad swaps, half-row
+// and row mirrors on the DPP path (both operands of each add hold the same two sub-sums, so the lanes of a row agree), then
+// rows 0+1 and 2+3 and the two halves with the gfx950 row / half-wave swaps: ((r0 + r1) + (r2 + r3)).
+__device__ __forceinline__ float srp_wave_sum(float v) {
+    // (every lane has a source under these four controls, so "0 where there is none" never applies: written that way, the
+    // DPP operand folds into the add -- one instruction per level instead of a copy, the DPP move and the add)
+    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true)));   // quad_perm [1,0,3,2]
+    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true)));   // quad_perm [2,3,0,1]
+    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true)));  // row_half_mirror
+    v = __fadd_rn(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true)));  // row_mirror
+    const unsigned u = __float_as_uint(v);
+    const auto q = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    const unsigned h = __float_as_uint(__fadd_rn(__uint_as_float(q[0]), __uint_as_float(q[1])));
+    const auto w = __builtin_amdgcn_permlane32_swap(h, h, false, false);
+    return __fadd_rn(__uint_as_float(w[0]), __uint_as_float(w[1]));
+}
+// (the sum as a scalar's bit pattern: sums of terms >= 0 compare as their patterns do as integers)
+__device__ __forceinline__ int srp_wave_mass(float v) { return __builtin_amdgcn_readfirstlane(__float_as_int(srp_wave_sum(v))); }
+// Selection by one whole wave, the sibling of srp_topk_keep and as indifferent to which codes a lane holds: f and idx as
+// there, e[j] = the term of the lane's j-th code with 0.0f already in place of every code outside K (and of "no code"),
+// 0 < p < 1 wave-uniform.  Returns the lane's kept codes, bit j.
+// The mass of a set S of codes is M(S) = srp_wave_sum(((e'_0 + e'_1) + ...) + e'_{N-1}), e'_j = e[j] for a code of S and 0.0f
+// for any other: the lane's codes left to right, then the tree above -- one fixed tree of round-to-nearest adds of terms
+// >= 0 for every S, so S within S' gives M(S) <= M(S'), and the search below is over a monotone predicate.  The bar is
+// need = p * M(K), one float32 product (> 0: the argmax code is in K and its term is 1).  32 rounds find V = the largest
+// image with M({image >= V}) >= need, then 8 rounds over srp_topk_keep's tie rank t find Y = the largest bound in 0 .. 255
+// with M({t > Y}) >= need; the kept codes are those with t > Y: every code above V and the lowest indices at V, the shortest
+// prefix of the order that reaches the bar, never empty.  Masses and the bar are non-negative floats, which compare as
+// their bit patterns do as integers: V, Y, the mass of a round and the bar are scalars, the control flow is uniform, no LDS.
+template <int N>
+__device__ __forceinline__ unsigned srp_topp_keep(const unsigned (&f)[N], const int (&idx)[N], const float (&e)[N], float p) {
+    float s = e[0];
+#pragma unroll
+    for (int j = 1; j < N; ++j) s = __fadd_rn(s, e[j]);
+    const int need = __float_as_int(p * __int_as_float(srp_wave_mass(s)));
+    unsigned v = 0;
+#pragma unroll 1
+    for (int bit = 31; bit >= 0; --bit) {
+        const unsigned x = v | (1u << bit);
+        s = f[0] >= x ? e[0] : 0.f;
+#pragma unroll
+        for (int j = 1; j < N; ++j) s = __fadd_rn(s, f[j] >= x ? e[j] : 0.f);
+        v = srp_wave_mass(s) >= need ? x : v;
+    }
+    unsigned t[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) t[j] = f[j] > v ? 511u : f[j] == v ? (unsigned)(256 - idx[j]) : 0u;
+    unsigned y = 0;
+#pragma unroll 1
+    for (int bit = 7; bit >= 0; --bit) {
+        const unsigned x = y | (1u << bit);
+        s = t[0] > x ? e[0] : 0.f;
+#pragma unroll
+        for (int j = 1; j < N; ++j) s = __fadd_rn(s, t[j] > x ? e[j] : 0.f);
+        y = srp_wave_mass(s) >= need ? x : y;
+    }
+    unsigned keep = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) keep |= t[j] > y ? 1u << j : 0u;
+    return keep;
 }
 
 // 24-bit uniform of a seeded draw: splitmix64 finaliser of key ^ K1 * counter, the middle of one of 2^24 cells of (0, 1)

@@ -8,9 +8,11 @@
 // term --, where off is the run index (origin + buffer index) of the first sample of the utterance's Q/2 prefix slot: the
 // counter is the sample's index in the utterance's own buffer, wherever the utterance sits.  temperature <= 0: argmax.
 // top_k: the utterance's truncation (samplernn_generate_set_utterance_top_k; the plan's without); outside 1 .. Q-1: none.
+// top_p: its nucleus (samplernn_generate_set_utterance_top_p; the plan's without); not strictly between 0 and 1: none.
 struct SrUttDraw {
     unsigned long long seed, off;
     float temperature; int top_k;
+    float top_p; int pad;
 };
 
 struct SrpArgs {
@@ -49,9 +51,19 @@ struct SrpArgs {
     // (sr_common.h, srp_scan_draw).  A uniform branch of the pick, like utt.
     int draw_mode;
     // SampleRnnGenDesc::top_k: a draw at temperature > 0 is taken among the k most likely codes (sr_common.h, srp_topk_keep);
-    // outside 1 .. Q-1: among all of them, by the instructions of the pick without this field.  With utt: the entry's top_k.
+    // 0: among all of them, by the instructions of the pick without this field.  With utt: the entry's top_k.  The launcher
+    // hands the kernel 0 for a value outside 1 .. Q-1, and sets SRP_NUCLEUS beside it when top_p is active: one word for the
+    // pick to test (srp_trunc_word).
     int top_k;
+    // samplernn_generate_set_top_p: a draw at temperature > 0 is taken among the nucleus of the codes top_k left (sr_common.h,
+    // srp_topp_keep); active strictly between 0 and 1 (top_k then carries SRP_NUCLEUS).  With utt: the entry's top_p.
+    float top_p;
 };
+
+constexpr int SRP_NUCLEUS = 1 << 16;  // in SrpArgs::top_k: the plan's top_p is active
+inline int srp_trunc_word(int top_k, float top_p, int Q) {
+    return (top_k > 0 && top_k < Q ? top_k : 0) | (top_p > 0.f && top_p < 1.f ? SRP_NUCLEUS : 0);
+}
 
 // PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8
 int srp_max_groups();

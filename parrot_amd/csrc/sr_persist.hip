@@ -20,8 +20,8 @@
 //     this kernel, of which 2.4 us were the four serialised L2 round trips;
 //   * the 4 streams of a team ride in the 4 lanes of an f32x4, the products run on the vector ALUs (a 4-row tile wastes
 //     3/4 of an MFMA; v_pk_fma_f32 has the same f32 peak as the matrix pipe);
-//   * the pick (argmax with lowest-index ties, or the seeded inverse-CDF draw, among all codes or the top_k most likely:
-//     sr_common.h, srp_topk_keep) is recomputed by every CU of the team from
+//   * the pick (argmax with lowest-index ties, or the seeded inverse-CDF draw, among all codes, the top_k most likely or
+//     their nucleus: sr_common.h, srp_topk_keep and srp_topp_keep) is recomputed by every CU of the team from
 //     the team's logits, so the new sample index is local knowledge everywhere and the embedding gather of the next step
 //     needs no further hand-off.
 // One launch covers the FRAME_SIZE steps between two frame-tier steps; the tiers above stay on the launch path.
@@ -232,8 +232,12 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
             const unsigned long long es = *(srp_cull)ea, eo = *(srp_cull)(ea + 8);
             const float et = *(srp_cfloat)(ea + 16);
             const int ek = *(srp_cint)(ea + 20);
-            if (lane == 0) { sh->useed[rw] = es; sh->uoff[rw] = eo; sh->utemp[rw] = et; sh->utopk[rw] = ek; }
+            const float ep = *(srp_cfloat)(ea + 24);
+            // (top_k parked as the pick reads it: 0 = no truncation of either kind, SRP_NUCLEUS set = the row has a nucleus)
+            const int ekn = (ek > 0 && ek < Q ? ek : 0) | (ep > 0.f && ep < 1.f ? SRP_NUCLEUS : 0);
+            if (lane == 0) { sh->useed[rw] = es; sh->uoff[rw] = eo; sh->utemp[rw] = et; sh->utopk[rw] = ekn; sh->utopp[rw] = ep; }
         }
+        if (!a.utt && tid < SRP_ROWS) sh->utopp[tid] = a.top_p;  // (no entries: every row draws with the plan's nucleus)
         __syncthreads();
         take_part();
         if (timing) stamps[81] = srp_clock();
@@ -308,11 +312,13 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                 // (the row's own temperature with per-utterance entries: rows of one team may mix argmax and draws)
                 const float temperature = a.utt ? sh->utemp[r] : a.temperature;
                 // (and its own truncation, asked for inside the draws only -- an argmax row runs what it always ran --: a uniform
-                // branch of both draws; 0 = off, and the draw runs the instructions it always ran)
-                auto row_top_k = [&]() {
-                    const int k = __builtin_amdgcn_readfirstlane(a.utt ? sh->utopk[r] : a.top_k);
-                    return k > 0 && k < Q ? k : 0;
-                };
+                // branch of both draws; 0 = off, and the draw runs the instructions it always ran.  One word says both kinds:
+                // the top_k in 1 .. Q-1 or 0, and SRP_NUCLEUS where the row has a nucleus -- SrpArgs::top_k comes that way from the
+                // plan, the entries are parked that way by the prologue -- so a draw without either pays one test for both.
+                // The nucleus itself is always read from the shared block, where the prologue parks the plan's value when
+                // there are no entries: an argument of the kernel read inside the step loop is one more scalar carried across it)
+                auto row_trunc = [&]() { return __builtin_amdgcn_readfirstlane(a.utt ? sh->utopk[r] : a.top_k); };
+                auto row_top_p = [&]() { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sh->utopp[r]))); };
                 if (temperature > 0.f && a.draw_mode == 1) {
                     // wave-parallel draw: lane l owns codes 4 l .. 4 l + 3, terms in registers, no LDS; the key, the counter
                     // and the uniform are the ones of the walk below
@@ -323,7 +329,9 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                     unsigned long long key = a.seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1));
                     unsigned long long ctr = draw0 + (unsigned long long)(t + 1);
                     if (a.utt) { key = sh->useed[r]; ctr -= sh->uoff[r]; }
-                    if (const int tk = row_top_k()) {
+                    if (const int tr = row_trunc()) {
+                        const int tk = tr & (SRP_NUCLEUS - 1);
+                        const float tp = tr & SRP_NUCLEUS ? row_top_p() : 0.f;
                         // the terms outside the kept set become 0.0f (adding them is exact: the tree and its bounds stand)
                         const unsigned f[4] = {srp_order_image(lg[4 * lane][r]), srp_order_image(lg[4 * lane + 1][r]),
                                                srp_order_image(lg[4 * lane + 2][r]), srp_order_image(lg[4 * lane + 3][r])};
@@ -332,8 +340,14 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                         int ln = lane;
                         asm volatile("" : "+v"(ln));
                         const int idx[4] = {4 * ln, 4 * ln + 1, 4 * ln + 2, 4 * ln + 3};
-                        const unsigned keep = srp_topk_keep<4>(f, idx, tk);
-                        const float m0 = keep & 1u ? e0 : 0.f, m1 = keep & 2u ? e1 : 0.f, m2 = keep & 4u ? e2 : 0.f, m3 = keep & 8u ? e3 : 0.f;
+                        unsigned keep = tk ? srp_topk_keep<4>(f, idx, tk) : 0xfu;
+                        float mk[4] = {keep & 1u ? e0 : 0.f, keep & 2u ? e1 : 0.f, keep & 4u ? e2 : 0.f, keep & 8u ? e3 : 0.f};
+                        if (tp != 0.f) {  // the nucleus of what top-k left: the shortest prefix with p of ITS mass
+                            keep &= srp_topp_keep<4>(f, idx, mk, tp);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) mk[j] = (keep >> j) & 1u ? mk[j] : 0.f;
+                        }
+                        const float m0 = mk[0], m1 = mk[1], m2 = mk[2], m3 = mk[3];
                         const int lk = keep ? 4 * lane + 31 - __clz((int)keep) : -1;
                         pick = srp_scan_draw<true>([&](int j) { return j == 0 ? m0 : j == 1 ? m1 : j == 2 ? m2 : m3; }, 4, lane,
                                                    srp_u01(key, ctr), lk);
@@ -343,14 +357,22 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                 } else if (temperature > 0.f) {
 #pragma unroll
                     for (int m = 0; m < Q / 64; ++m) ev[r * Q + lane + 64 * m] = expf((lg[lane + 64 * m][r] - best) / temperature);
-                    if (const int tk = row_top_k()) {
+                    if (const int tr = row_trunc()) {
+                        const int tk = tr & (SRP_NUCLEUS - 1);
+                        const float tp = tr & SRP_NUCLEUS ? row_top_p() : 0.f;
                         // the terms outside the kept set are overwritten with 0.0f: the walk adds them, exactly
                         unsigned f[Q / 64];
                         int idx[Q / 64], ln = lane;
                         asm volatile("" : "+v"(ln));  // (opaque: see the scan branch)
 #pragma unroll
                         for (int m = 0; m < Q / 64; ++m) { f[m] = srp_order_image(lg[lane + 64 * m][r]); idx[m] = ln + 64 * m; }
-                        const unsigned keep = srp_topk_keep<Q / 64>(f, idx, tk);
+                        unsigned keep = tk ? srp_topk_keep<Q / 64>(f, idx, tk) : (1u << (Q / 64)) - 1u;
+                        if (tp != 0.f) {  // the nucleus of what top-k left; the lane's terms are read back from where it put them
+                            float ek[Q / 64];
+#pragma unroll
+                            for (int m = 0; m < Q / 64; ++m) ek[m] = (keep >> m) & 1u ? ev[r * Q + lane + 64 * m] : 0.f;
+                            keep &= srp_topp_keep<Q / 64>(f, idx, ek, tp);
+                        }
 #pragma unroll
                         for (int m = 0; m < Q / 64; ++m)
                             if (!((keep >> m) & 1u)) ev[r * Q + lane + 64 * m] = 0.f;
@@ -384,7 +406,7 @@ __global__ __launch_bounds__(SRP_THREADS) void srp_kernel(const SrpArgs a) {
                     // A truncated walk never stops at a code outside the kept set (its term 0.0f does not move c), so Q - 1 from
                     // a kept set without it means that no code satisfied u < c (u01 can be exactly 1.0): the pick is the highest
                     // kept code.  (With Q - 1 kept that is Q - 1 itself.)  Behind the walk, whose text stays as it was.
-                    if (row_top_k() && lane == 0 && pick == Q - 1) pick = sh->ulast[r];
+                    if (row_trunc() && lane == 0 && pick == Q - 1) pick = sh->ulast[r];
                 }
                 if (lane == 0) {
                     sh->hist[r][a.FS + i] = pick;

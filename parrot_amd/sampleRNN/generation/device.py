@@ -8,15 +8,16 @@ from ... import _lib
 from ... import ops as hip
 from .. import lib
 from ..lib import ops as lops
-from .inputs import _seed_image, config, draw_mode_code, top_k_array, top_k_code
+from .inputs import _seed_image, config, draw_mode_code, top_k_array, top_k_code, top_p_array, top_p_code
 
 
-def device_loop_guard(draw_mode, top_k=0):
+def device_loop_guard(draw_mode, top_k=0, top_p=0.0):
     """What every entry to the device-resident loop checks before any device call: draw_mode's code (ValueError on an
-    unknown name), top_k (ValueError on a negative one), and that the model has no skip-connection stacks, which the loop
-    does not take."""
+    unknown name), top_k (ValueError on a negative one), top_p (ValueError on a negative one or a NaN), and that the model
+    has no skip-connection stacks, which the loop does not take."""
     mode = draw_mode_code(draw_mode)
     top_k_code(top_k)
+    top_p_code(top_p)
     if config().SKIP_CONN:
         raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
     return mode
@@ -26,7 +27,7 @@ class DeviceGenerator:
     """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
 
     def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
-                 draw_mode='sequential', top_k=0):
+                 draw_mode='sequential', top_k=0, top_p=0.0):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
         three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
 
@@ -49,10 +50,18 @@ class DeviceGenerator:
         first codes by logit descending, then by index ascending; every other code's term is 0 in the same sums, with the
         same uniforms, in both draw modes.  0 (default) or k >= Q_LEVELS: among all codes, the samples of every earlier
         version.  k = 1 picks the argmax.  With utterance_draws=True it is what an utterance draws with unless
-        generate(..., top_ks=) names its own.  Negative: ValueError."""
+        generate(..., top_ks=) names its own.  Negative: ValueError.
+
+        top_p = p strictly between 0 and 1: a draw at temperature > 0 is taken among the nucleus (samplernn_generate_set_top_p)
+        -- of the codes top_k left (all of them without), ordered the same way, the shortest prefix whose mass reaches p of
+        their mass; never empty, ties at the cut-off to the lower index, every other code's term 0 in the same sums: a draw
+        with top_p = p is a draw with top_k = the length of that prefix.  0 (default) or >= 1: no nucleus, the samples of
+        every earlier version.  A very small p picks the argmax.  With utterance_draws=True it is what an utterance draws
+        with unless generate(..., top_ps=) names its own.  Negative or NaN: ValueError."""
         self.draw_mode = draw_mode
-        mode = device_loop_guard(draw_mode, top_k)
+        mode = device_loop_guard(draw_mode, top_k, top_p)
         self.top_k = top_k_code(top_k)
+        self.top_p = top_p_code(top_p)
         self.B, self.T = batch, n_frames
         self.packed = bool(packed)
         self.utterance_draws = bool(utterance_draws)
@@ -144,6 +153,8 @@ class DeviceGenerator:
         self.desc = d
         self.plan = C.c_void_p()
         _lib.call('samplernn_generate_create', C.byref(d), C.byref(self.plan))
+        if 0.0 < self.top_p < 1.0:  # (the descriptor has no word for it; off is a new plan's state)
+            _lib.call('samplernn_generate_set_top_p', self.plan, C.c_float(self.top_p))
         self.persistent = bool(_lib.load().samplernn_generate_is_persistent(self.plan))
         # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
         self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
@@ -154,15 +165,19 @@ class DeviceGenerator:
             self.ws['utt_seed'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int64)
             self.ws['utt_temp'] = torch.zeros(n_frames, batch, **f)
             self.ws['utt_top_k'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int32)
+            self.ws['utt_top_p'] = torch.zeros(n_frames, batch, **f)
             self.set_utterance_draws()
 
     def set_utterance_draws(self):
-        """Hands the plan its per-utterance seed, temperature and top_k arrays; refused (HipCallError) once the plan has run."""
+        """Hands the plan its per-utterance seed, temperature, top_k and top_p arrays; refused (HipCallError) once the plan
+        has run."""
         _lib.call('samplernn_generate_set_utterance_draws', self.plan, self.ws['utt_seed'].data_ptr(),
                   self.ws['utt_temp'].data_ptr())
         _lib.call('samplernn_generate_set_utterance_top_k', self.plan, self.ws['utt_top_k'].data_ptr())
+        _lib.call('samplernn_generate_set_utterance_top_p', self.plan, self.ws['utt_top_p'].data_ptr())
 
-    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None):
+    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None,
+                 top_ps=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
         frame f, whose Q/2 prefix is slot f - 1.
@@ -182,16 +197,20 @@ class DeviceGenerator:
 
         top_ks (optional, accepted exactly where seeds is): integers of the same shape as seeds, or one integer for all --
         the top_k each utterance draws with (0 or >= Q_LEVELS: no truncation); omitted, every utterance takes the plan's
-        top_k.  A negative value or another shape: ValueError."""
-        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures, top_ks)
-        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks)
+        top_k.  A negative value or another shape: ValueError.
+
+        top_ps (optional, likewise): numbers of the same shape as seeds, or one number for all -- the top_p each utterance
+        draws with (0 or >= 1: no nucleus); omitted, every utterance takes the plan's top_p.  A negative value, a NaN or
+        another shape: ValueError."""
+        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures, top_ks, top_ps)
+        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks, top_ps)
         self._launch(segment, resume, k)
         if not segment:
             return self.ws['samples']
         BFS = config().BIG_FRAME_SIZE
         return self.ws['samples'][:, BFS * first:BFS * (k + 1)].clone()
 
-    def _resolve(self, starts, resume, n_frames, seeds, temperatures, top_ks=None):
+    def _resolve(self, starts, resume, n_frames, seeds, temperatures, top_ks=None, top_ps=None):
         """Which arguments this plan takes in which kind of run -> (segment, resume, k, rows, first): a run in segments or
         in one piece, k frames to generate, `rows` rows of input for the ring's slots from `first` on."""
         if (starts is not None) != self.packed:
@@ -204,6 +223,9 @@ class DeviceGenerator:
         if top_ks is not None and not takes_draws:
             raise ValueError("top_ks is accepted only where seeds is: on a plan built with utterance_draws=True (a plain "
                              "plan takes them with resume=False only)")
+        if top_ps is not None and not takes_draws:
+            raise ValueError("top_ps is accepted only where seeds is: on a plan built with utterance_draws=True (a plain "
+                             "plan takes them with resume=False only)")
         if resume and not self._has_run:
             raise ValueError("resume=True needs a run to continue: call generate(..., resume=False) first")
         k = self.T - 1 if n_frames is None else int(n_frames)
@@ -212,9 +234,11 @@ class DeviceGenerator:
         rows = k if resume else (k + 1 if n_frames is not None else self.T)
         if top_ks is not None:  # (its values and shape before anything is staged on the device)
             top_k_code(top_ks) if numpy.ndim(top_ks) == 0 else top_k_array(top_ks, (rows, self.B) if self.packed else (self.B,))
+        if top_ps is not None:
+            top_p_code(top_ps) if numpy.ndim(top_ps) == 0 else top_p_array(top_ps, (rows, self.B) if self.packed else (self.B,))
         return resume or n_frames is not None, resume, k, rows, 1 if resume else 0
 
-    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None):
+    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None, top_ps=None):
         """Checks the arrays' shapes and copies them into rows first .. first + rows - 1 of the workspace."""
         ws = self.ws
         feats = torch.as_tensor(features)
@@ -237,8 +261,13 @@ class DeviceGenerator:
                 tk = numpy.full(want, top_k_code(self.top_k if top_ks is None else top_ks), dtype=numpy.int32)
             else:
                 tk = top_k_array(top_ks, want)
+            if top_ps is None or numpy.ndim(top_ps) == 0:
+                pp = numpy.full(want, top_p_code(self.top_p if top_ps is None else top_ps), dtype=numpy.float32)
+            else:
+                pp = top_p_array(top_ps, want)
             # (a plain plan: one utterance per stream, prefix in slot 0 -- the row of slot 1, like a start flagged there)
             lo, hi = (first, first + rows) if self.packed else (1, 2)
+            ws['utt_top_p'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(pp).reshape(hi - lo, self.B)).to(ws['utt_top_p'].device))
             ws['utt_top_k'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tk).reshape(hi - lo, self.B)).to(ws['utt_top_k'].device))
             ws['utt_seed'][lo:hi].copy_(torch.from_numpy(sd.reshape(hi - lo, self.B)).to(ws['utt_seed'].device))
             ws['utt_temp'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tp).reshape(hi - lo, self.B)).to(ws['utt_temp'].device))

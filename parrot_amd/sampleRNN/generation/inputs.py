@@ -1,6 +1,6 @@
 """What a generation plan is fed, computed on the host with numpy alone (no torch, no device): the seeded draw in Python
 integers -- the hash sr_pick_kernel and srp_kernel key their uniforms with, a seed per utterance, the draw modes' names,
-the checks of a top_k --
+the checks of a top_k and a top_p --
 and where utterances go: into the streams of one packed plan (pack_utterances and the arrays of such a packing) and into
 the segments of a plan that never ends (schedule_segment)."""
 import numpy
@@ -90,6 +90,49 @@ def _per_utterance_top_k(top_ks, n, default_top_k):
     return [top_k_code(k) for k in top_ks]
 
 
+_TINY32 = float(numpy.finfo(numpy.float32).tiny)
+
+
+def top_p_code(top_p):
+    """The float a plan or an utterance is handed as its top_p (samplernn_generate_set_top_p): 0.0 or >= 1.0 = no nucleus,
+    strictly between = active; ValueError on a negative value, a NaN or anything that is not a real number (no device
+    call)."""
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float, numpy.integer, numpy.floating)):
+        raise ValueError("top_p must be a number in [0, 1] (0 or 1: no nucleus), got %r" % (top_p,))
+    if not top_p >= 0:
+        raise ValueError("top_p must be >= 0 and not NaN (0 or >= 1: no nucleus), got %r" % (top_p,))
+    # (as the float32 the device sees; a positive value below float32's normal range stays active: it keeps the argmax)
+    p = float(numpy.float32(min(float(top_p), 2.0)))
+    return max(p, _TINY32) if top_p > 0 else 0.0
+
+
+def top_p_active(top_p):
+    """Whether a checked top_p truncates: strictly between 0 and 1 as the float32 the device sees."""
+    return 0.0 < top_p_code(top_p) < 1.0
+
+
+def top_p_array(top_ps, shape):
+    """Per-utterance top_p values as the float32 array of `shape` a plan is fed: ValueError on another shape, a negative
+    value, a NaN or a non-numeric array (no device call).  Values >= 1 mean no nucleus, like 0."""
+    a = numpy.asarray(top_ps)
+    if a.dtype.kind not in 'iuf' or a.shape != tuple(shape):
+        raise ValueError("top_ps must be numbers of shape %s, got %s of %s" % (list(shape), a.dtype, list(a.shape)))
+    if a.size and not bool(numpy.all(a >= 0)):
+        raise ValueError("top_ps must be >= 0 and not NaN (0 or >= 1: no nucleus)")
+    a = a.astype(numpy.float64)
+    return numpy.where(a > 0, numpy.clip(a, _TINY32, 2.0), 0.0).astype(numpy.float32)
+
+
+def _per_utterance_top_p(top_ps, n, default_top_p):
+    """top_ps: one per utterance or a scalar; None = default_top_p for all."""
+    if top_ps is None:
+        top_ps = default_top_p
+    top_ps = [top_ps] * n if numpy.ndim(top_ps) == 0 else list(top_ps)
+    if len(top_ps) != n:
+        raise ValueError("%d utterances, but %d top_ps" % (n, len(top_ps)))
+    return [top_p_code(p) for p in top_ps]
+
+
 def _per_utterance(seeds, temperatures, n, default_temperature):
     """seeds: one per utterance; temperatures: one per utterance, a scalar, or None = default_temperature."""
     seeds = [u64(s) for s in seeds]
@@ -171,6 +214,19 @@ def build_packed_top_k(top_ks, stream, first_slot, T, n_streams):
         if row is not None:
             utt_top_k[row, b] = top_k_code(k)
     return utt_top_k
+
+
+def build_packed_top_p(top_ps, stream, first_slot, T, n_streams):
+    """utt_top_p [T, n_streams] float32 of a packing, the sibling of build_packed_top_k: utterance i's top_p on its
+    start_row; zeros (no nucleus) elsewhere."""
+    utt_top_p = numpy.zeros((T, n_streams), dtype=numpy.float32)
+    for p_, b, s in zip(top_ps, stream, first_slot):
+        if not (0 <= b < n_streams and 0 <= s < T):
+            raise ValueError("no slot %d in stream %d" % (s, b))
+        row = start_row(s, T)
+        if row is not None:
+            utt_top_p[row, b] = top_p_code(p_)
+    return utt_top_p
 
 
 def unpack_samples(samples, lengths, stream, first_slot):

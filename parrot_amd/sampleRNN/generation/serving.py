@@ -3,12 +3,13 @@ segments on a ring (generate_stream) and continuous admission on a plan that nev
 import numpy
 
 from .device import DeviceGenerator, device_loop_guard
-from .inputs import (_per_utterance, _per_utterance_top_k, build_packed_draws, build_packed_inputs, build_packed_top_k,
-                     config, pack_utterances, schedule_segment, start_row, top_k_code, u64, unpack_samples)
+from .inputs import (_per_utterance, _per_utterance_top_k, _per_utterance_top_p, build_packed_draws, build_packed_inputs,
+                     build_packed_top_k, build_packed_top_p, config, pack_utterances, schedule_segment, start_row,
+                     top_k_code, top_p_code, u64, unpack_samples)
 
 
 def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_graph=True, seeds=None,
-                    temperatures=None, draw_mode='sequential', top_k=0, top_ks=None):
+                    temperatures=None, draw_mode='sequential', top_k=0, top_ks=None, top_p=0.0, top_ps=None):
     """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
     utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
     n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
@@ -27,27 +28,34 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
     draw_mode: 'sequential' or 'scan', see DeviceGenerator.  (temperature's default: three_tier.TEMPERATURE as imported.)
 
     top_k: the draws at temperature > 0 are taken among the k most likely codes (0: among all; see DeviceGenerator).
-    top_ks = one top_k per utterance (needs `seeds`; default: `top_k` for all)."""
-    device_loop_guard(draw_mode, top_k)
+    top_ks = one top_k per utterance (needs `seeds`; default: `top_k` for all).
+
+    top_p: those draws are taken among the nucleus of the codes top_k left (0 or >= 1: no nucleus; see DeviceGenerator).
+    top_ps = one top_p per utterance (needs `seeds`; default: `top_p` for all)."""
+    device_loop_guard(draw_mode, top_k, top_p)
     utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
     if seeds is None and temperatures is not None:
         raise ValueError("temperatures per utterance need seeds per utterance")
     if seeds is None and top_ks is not None:
         raise ValueError("top_ks per utterance need seeds per utterance")
+    if seeds is None and top_ps is not None:
+        raise ValueError("top_ps per utterance need seeds per utterance")
     if seeds is not None:  # (before a plan is created)
         seeds, temperatures = _per_utterance(seeds, temperatures, len(utterances), temperature)
         top_ks = _per_utterance_top_k(top_ks, len(utterances), top_k)
+        top_ps = _per_utterance_top_p(top_ps, len(utterances), top_p)
     if not utterances:
         return []
     stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
     features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
     gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
-                          utterance_draws=seeds is not None, draw_mode=draw_mode, top_k=top_k)
+                          utterance_draws=seeds is not None, draw_mode=draw_mode, top_k=top_k, top_p=top_p)
     try:
         draws = {}
         if seeds is not None:
             draws['seeds'], draws['temperatures'] = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
             draws['top_ks'] = build_packed_top_k(top_ks, stream, first_slot, T, n_streams)
+            draws['top_ps'] = build_packed_top_p(top_ps, stream, first_slot, T, n_streams)
         samples = gen.generate(features, starts, **draws).cpu().numpy()
     finally:
         gen.close()
@@ -55,15 +63,16 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
 
 
 def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_graph=True, gen=None, draw_mode='sequential',
-                    top_k=0):
+                    top_k=0, top_p=0.0):
     """Generator over a rectangle features [N, B, 63] on a plan of segment_frames + 1 slots used as a ring: yields int32
     arrays [B, 80 n] -- the first one holds the Q/2 prefix and up to segment_frames frames, every later one up to
     segment_frames frames -- whose concatenation is the [B, 80 N] result of DeviceGenerator(B, N).generate(features), bit
     for bit, seeded draws included.  The plan does not grow with N, and the first samples are out after segment_frames
     periods.  gen: a plain DeviceGenerator(B, segment_frames + 1) of the caller's to run on (it is left open; temperature,
-    seed, use_graph, draw_mode and top_k are then the plan's); default: a plan of its own for this call, with draw_mode
-    'sequential' or 'scan' and top_k (see DeviceGenerator) and temperature's default as in generate_packed."""
-    device_loop_guard(draw_mode, top_k)
+    seed, use_graph, draw_mode, top_k and top_p are then the plan's); default: a plan of its own for this call, with
+    draw_mode 'sequential' or 'scan', top_k and top_p (see DeviceGenerator) and temperature's default as in
+    generate_packed."""
+    device_loop_guard(draw_mode, top_k, top_p)
     features = numpy.asarray(features, dtype='float32')
     S = int(segment_frames)
     if S < 1:
@@ -74,7 +83,7 @@ def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_gra
     own = gen is None
     if own:
         gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph, draw_mode=draw_mode,
-                              top_k=top_k)
+                              top_k=top_k, top_p=top_p)
     elif gen.packed or (gen.B, gen.T) != (B, S + 1):
         raise ValueError("gen must be a plain plan of %d streams and %d slots" % (B, S + 1))
     try:
@@ -116,13 +125,20 @@ class StreamingGenerator:
     top_k: the plan's truncation (see DeviceGenerator), what every utterance draws with unless submit(..., top_k=) names
     its own (utterance_draws=True only).  A generator that truncates -- its top_k is non-zero, or some utterance was
     submitted with one -- calls run_segment with one more keyword argument, top_ks [n, B] int32: the top_k of the utterance
-    whose start flag is on that row, zeros elsewhere.  A generator that does not calls it exactly as before."""
+    whose start flag is on that row, zeros elsewhere.  A generator that does not calls it exactly as before.
+
+    top_p: the plan's nucleus (see DeviceGenerator), what every utterance draws with unless submit(..., top_p=) names its
+    own (utterance_draws=True only).  Likewise, a generator that uses nucleus truncation -- its top_p is active, or some
+    utterance was submitted with one -- calls run_segment with one more keyword argument, top_ps [n, B] float32; a
+    generator that does not never passes it."""
 
     def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
-                 utterance_draws=False, draw_mode='sequential', top_k=0):
-        device_loop_guard(draw_mode, top_k)
+                 utterance_draws=False, draw_mode='sequential', top_k=0, top_p=0.0):
+        device_loop_guard(draw_mode, top_k, top_p)
         self.top_k = top_k_code(top_k)
         self._truncates = self.top_k != 0
+        self.top_p = top_p_code(top_p)
+        self._nucleus = 0.0 < self.top_p < 1.0
         self.B, self.S = int(n_streams), int(segment_frames)
         if self.B < 1:
             raise ValueError("n_streams must be at least 1")
@@ -134,7 +150,7 @@ class StreamingGenerator:
         if run_segment is None:
             self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
                                        packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode,
-                                       top_k=self.top_k)
+                                       top_k=self.top_k, top_p=self.top_p)
             run_segment = self._run_on_device
         self._run = run_segment
         self._resume = False
@@ -145,13 +161,16 @@ class StreamingGenerator:
         self._features = {}
         self._draws = {}               # ticket -> (seed, temperature), until the utterance's start flag has been placed
         self._top_ks = {}              # ticket -> top_k, likewise (utterance_draws only)
+        self._top_ps = {}              # ticket -> top_p, likewise
         self.record = {}
 
-    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None):
+    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None, top_ps=None):
         # (without utterance_draws the plan has no entries: every utterance draws with the plan's top_k)
         draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
         if seeds is not None and top_ks is not None:
             draws['top_ks'] = top_ks
+        if seeds is not None and top_ps is not None:
+            draws['top_ps'] = top_ps
         if resume:
             return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0], **draws).cpu().numpy()
         n = features.shape[0]  # the first segment: slot 0 is the run's prefix slot, no stream uses it
@@ -160,10 +179,10 @@ class StreamingGenerator:
         draws = {k: numpy.concatenate([numpy.zeros_like(v[:1]), v]) for k, v in draws.items()}
         return self.gen.generate(features, starts, n_frames=n, **draws).cpu().numpy()[:, config().BIG_FRAME_SIZE:]
 
-    def submit(self, features, seed=None, temperature=None, top_k=None):
+    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None):
         """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
-        seed (an unsigned 64-bit integer), temperature and top_k (defaults: the generator's): with utterance_draws=True
-        only, where the seed is required."""
+        seed (an unsigned 64-bit integer), temperature, top_k and top_p (defaults: the generator's): with
+        utterance_draws=True only, where the seed is required."""
         if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
             raise ValueError("a seed (and a temperature) per utterance is given exactly when the generator was built with "
                              "utterance_draws=True")
@@ -171,6 +190,10 @@ class StreamingGenerator:
             raise ValueError("a top_k per utterance needs a generator built with utterance_draws=True")
         if top_k is not None:
             top_k = top_k_code(top_k)
+        if top_p is not None and not self.utterance_draws:
+            raise ValueError("a top_p per utterance needs a generator built with utterance_draws=True")
+        if top_p is not None:
+            top_p = top_p_code(top_p)
         features = numpy.asarray(features, dtype='float32')
         if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
             raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
@@ -180,6 +203,8 @@ class StreamingGenerator:
             self._draws[ticket] = (u64(seed), self.temperature if temperature is None else float(temperature))
             self._top_ks[ticket] = self.top_k if top_k is None else top_k
             self._truncates = self._truncates or top_k is not None
+            self._top_ps[ticket] = self.top_p if top_p is None else top_p
+            self._nucleus = self._nucleus or top_p is not None
         self._features[ticket] = features
         self.queue.append((ticket, features.shape[0]))
         return ticket
@@ -218,6 +243,11 @@ class StreamingGenerator:
             for ticket, b, slot, frame, count in placements:
                 if frame <= 1 < frame + count:
                     draws['top_ks'][start_row(slot - frame, n + 1) - 1, b] = self._top_ks.get(ticket, self.top_k)
+        if self._nucleus:
+            draws['top_ps'] = numpy.zeros((n, self.B), dtype=numpy.float32)
+            for ticket, b, slot, frame, count in placements:
+                if frame <= 1 < frame + count:
+                    draws['top_ps'][start_row(slot - frame, n + 1) - 1, b] = self._top_ps.get(ticket, self.top_p)
         samples = numpy.asarray(self._run(feats, flags, self._resume, **draws))
         if samples.shape != (self.B, BFS * n):
             raise ValueError("the segment runner returned %s, not %s" % (samples.shape, (self.B, BFS * n)))
@@ -233,6 +263,7 @@ class StreamingGenerator:
                 del self._features[ticket]
                 self._draws.pop(ticket, None)
                 self._top_ks.pop(ticket, None)
+                self._top_ps.pop(ticket, None)
             out.append((ticket, chunk, done))
         return out
 

@@ -5,7 +5,7 @@ and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
 --device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames,
---utterance_seed, --draw_mode, --top_k.
+--utterance_seed, --draw_mode, --top_k, --top_p.
 """
 from __future__ import annotations
 
@@ -147,6 +147,11 @@ def sample_parse(argv=None):
                         help="K > 0 (with --raw_output): the SampleRNN vocoder's draws at temperature > 0 are taken among the "
                              "K most likely of the 256 codes (ties at the cut-off go to the lower code), in both draw modes; "
                              "0: among all of them (DESIGN.md 3.6)")
+    parser.add_argument('--top_p', type=float, default=0.0,
+                        help="P strictly between 0 and 1 (with --raw_output): the SampleRNN vocoder's draws at temperature > 0 "
+                             "are taken among the nucleus -- the most likely codes (of those --top_k left) that together "
+                             "hold P of the probability, ties at the cut-off to the lower code --, in both draw modes; 0 or "
+                             ">= 1: no nucleus (DESIGN.md 3.6)")
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
