@@ -253,6 +253,27 @@ int parrot_gmm_attention_bwd(const float* dw, const float* ctx, const float* a, 
                              float* dp, float* dh1, int B, int H, int A, int U, int E, int att_type, float eps,
                              void* stream);
 
+/* The same two steps with the window's support handed from one to the other, as the training scan does: _fwd_sup also
+ * writes sup [B,2] (int), the first / last context position whose window weight phi is not exactly 0 ((U, -1) when every
+ * weight is 0, (0, U-1) under PARROT_ATT_DENSE=1); _bwd_sup reads it (null: as parrot_gmm_attention_bwd) and skips the
+ * context rows outside it.  Same results as the plain entry points, bit for bit. */
+int parrot_gmm_attention_fwd_sup(const float* h1, const float* WattT, const float* batt, const float* kappa_prev,
+                                 const float* ctx, float* a, float* b, float* kappa, float* phi, float* w, int B,
+                                 int H, int A, int U, int E, int att_type, float eps, float alignment,
+                                 float sharpening, float timing, int* sup, void* stream);
+int parrot_gmm_attention_bwd_sup(const float* dw, const float* ctx, const float* a, const float* b,
+                                 const float* kappa, const float* kappa_prev, const float* WattT, float* dkappa,
+                                 float* dp, float* dh1, int B, int H, int A, int U, int E, int att_type, float eps,
+                                 const int* sup, void* stream);
+
+/* Which path the attention backward row block takes for a batch row whose saved support is [u_lo, u_hi] (introspection,
+ * as parrot_gemm_route; host arithmetic only): *route = 1 narrow (support present, 0 <= u_lo <= u_hi < U, at most
+ * PARROT_ATT_BWD_CAP rows wide, U <= 256, E <= 256, PARROT_ATT_BWD_NARROW not 0: only the support's context rows are
+ * fetched and reduced, the projection column is requested at entry), 0 wide (everything else; has_sup = 0: no support
+ * handed in).  Both paths give the same bits. */
+#define PARROT_ATT_BWD_CAP 64
+int parrot_att_bwd_route(int U, int E, int has_sup, int u_lo, int u_hi, int* route);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-window decoder scan for training: the theano.scan over `step` of Parrot.compute_cost
  * (model.py:651-737) and its reverse-mode gradient.  L in {1,2,3} GRU layers with the reference's

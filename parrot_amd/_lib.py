@@ -217,6 +217,9 @@ SIGNATURES = {
     "parrot_lstm_seq_destroy": (_i, [_vp]),
     "parrot_gmm_attention_fwd": (_i, [_vp] * 10 + [_i] * 6 + [_f] * 4 + [_vp]),
     "parrot_gmm_attention_bwd": (_i, [_vp] * 10 + [_i] * 6 + [_f, _vp]),
+    "parrot_gmm_attention_fwd_sup": (_i, [_vp] * 10 + [_i] * 6 + [_f] * 4 + [_vp, _vp]),
+    "parrot_gmm_attention_bwd_sup": (_i, [_vp] * 10 + [_i] * 6 + [_f, _vp, _vp]),
+    "parrot_att_bwd_route": (_i, [_i] * 5 + [_vp]),
     "parrot_decoder_create": (_i, [C.POINTER(DecoderDesc), C.POINTER(C.c_void_p)]),
     "parrot_decoder_persist_floats": (C.c_longlong, [C.POINTER(DecoderDesc)]),
     "parrot_decoder_is_persistent": (_i, [_vp]),

@@ -10,9 +10,15 @@
 
 constexpr int ATTB_THREADS = 1024;  // backward: one workgroup per batch row, 16 waves
 
+// Floats of the dw total's LDS row (it also holds s_part).  More than one per thread: the narrow path's store of the
+// total needs no guard (a guard around the only use of the share loads lets the compiler sink them into it, behind every
+// other request).
+__host__ __device__ inline int att_bwd_dwsz(int E) {
+    static_assert(16 * 3 * ATT_MAXA >= ATTB_THREADS, "one float per thread");
+    return ((E + 3) & ~3) > 16 * 3 * ATT_MAXA ? ((E + 3) & ~3) : 16 * 3 * ATT_MAXA;
+}
 static inline size_t att_bwd_lds(int U, int E) {
-    const int dwsz = ((E + 3) & ~3) > 16 * 3 * ATT_MAXA ? ((E + 3) & ~3) : 16 * 3 * ATT_MAXA;  // also holds s_part
-    return sizeof(float) * (6 * ATT_MAXA + 24 + dwsz + ((U + 3) & ~3));
+    return sizeof(float) * (6 * ATT_MAXA + 24 + att_bwd_dwsz(E) + ((U + 3) & ~3));
 }
 
 // Backward of one step for batch row b (one workgroup per row).
@@ -22,8 +28,15 @@ struct AttBwdNoLate { __device__ __forceinline__ void operator()() const {} };
 // late(): called once the context registers are dead (after the dphi phase): the caller requests what it needs behind the
 // attention backward there (layer 0's state-backward operands), where 64 VGPRs have just been freed -- requested at entry
 // they pushed the 1024-thread block over its 128 registers (84 bytes of scratch per lane).
-template <class LATE = AttBwdNoLate>
-__device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* sm, float* dh_io = nullptr, LATE late = LATE()) {
+//
+// NARROW (att_bwd_route, block-uniform, chosen before the first request): the saved support is at most ATTB_CAP rows wide,
+// so the waves fetch and reduce only those rows (ATTB_CAP / 16 per wave, 16 registers instead of 64) and the registers
+// this frees take the Watt column and late()'s operands at entry, behind the requests the first phases wait for: loads
+// return in order, so the counted waits of the dphi phase do not include them, and the dh1 phase finds them there.  A
+// row's dphi is the same bits on either path: same lane <-> column mapping, same segment order, same wave_sum.
+template <bool NARROW, class LATE>
+__device__ __forceinline__ bool att_bwd_row_impl(const AttBwdArgs& g, int b, float* sm, float* dh_io, LATE late, int u_lo,
+                                                 int u_hi) {
     const int A = g.A, U = g.U, E = g.E, H = g.H;
     float* s_a = sm;                  // [A]
     float* s_b = s_a + ATT_MAXA;
@@ -31,7 +44,7 @@ __device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* s
     float* s_dp = s_k + ATT_MAXA;     // [3A]
     float* s_red = s_dp + 3 * ATT_MAXA;  // [24]
     float* s_dw = s_red + 24;          // [E]
-    float* s_dphi = s_dw + (((E + 3) & ~3) > 16 * 3 * ATT_MAXA ? ((E + 3) & ~3) : 16 * 3 * ATT_MAXA);  // [U]
+    float* s_dphi = s_dw + att_bwd_dwsz(E);  // [U]
 
     const int t = threadIdx.x;
     const int lane = t & 63, wave = t >> 6;
@@ -43,19 +56,67 @@ __device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* s
     // chain of four dependent ones.
     constexpr int NWB = ATTB_THREADS / 64;
     constexpr int RPW = 16, SEG = 4;  // rows per wave / 64-float segments per row covered by the preload
-    const bool use_pre = (U <= NWB * RPW) && (E <= 64 * SEG);
-    // Support of the window saved by the forward step: outside [u_lo, u_hi] every exp(-b (kappa-u)^2) is exactly
-    // 0.0f, so dphi[u] is multiplied by zero in all three mixture gradients and its context row is not needed.
-    int u_lo = 0, u_hi = U - 1;
-    if (g.sup) {
-        u_lo = g.sup[2 * b];
-        u_hi = g.sup[2 * b + 1];
-    }
+    constexpr int NRW = ATTB_CAP / NWB;  // rows per wave on the narrow path
+    const bool use_pre = !NARROW && (U <= NWB * RPW) && (E <= 64 * SEG);
     // Round 6: every request below is unconditional and branch-free (indices clamped into what exists, absent gradient
     // shares re-read the first one and are dropped by a select later): under `cond ? p[i] : 0` / `if (g.dw3) v += ...`
     // the compiler ended each conditional load with s_waitcnt vmcnt(0) -- the six shares of dw alone were six dependent
     // round trips, 4.3 us from entry to the first barrier (tools/att_timing.py).  The sums keep their order.
-    float cpre[RPW][SEG];
+    float cpre[NARROW ? NRW : RPW][SEG];
+    constexpr int WPRE = 32;
+    const bool use_wpre = (H <= ATTB_THREADS) && (3 * A <= WPRE);
+    float wpre[WPRE];
+    // the carry of kappa's gradient and kappa_{t-1}: needed four phases later, requested now
+    const int ta = t < A ? t : A - 1;
+    float pre_dkappa, pre_kprev, pre_a, pre_b, pre_k;
+    auto request_pre = [&]() {
+        pre_dkappa = g.dkappa[(size_t)b * A + ta]; pre_kprev = g.kappa_prev[(size_t)b * A + ta];
+        pre_a = g.a[(size_t)b * A + ta]; pre_b = g.b[(size_t)b * A + ta]; pre_k = g.kappa[(size_t)b * A + ta];
+    };
+    if constexpr (NARROW) {
+        request_pre();
+        // dw shares and window parameters first (the first barrier waits for them), the support's rows behind them,
+        // then what only the last phases need.  E <= 256: one column per thread, index clamped.
+        const bool on2 = g.dw2 != nullptr, on3 = on2 && g.dw3, on4 = on2 && g.dw4, on5 = on2 && g.dw5, on6 = on2 && g.dw6;
+        const float* p2 = on2 ? g.dw2 : g.dw;
+        const float* p3 = on3 ? g.dw3 : g.dw;
+        const float* p4 = on4 ? g.dw4 : g.dw;
+        const float* p5 = on5 ? g.dw5 : g.dw;
+        const float* p6 = on6 ? g.dw6 : g.dw;
+        const size_t i = (size_t)b * g.lddw + (t < E ? t : E - 1);
+        const float x1 = g.dw[i], x2 = p2[i], x3 = p3[i], x4 = p4[i], x5 = p5[i], x6 = p6[i];
+        // (the scheduler otherwise moves some of the share loads behind the later groups, and the wait for the total then
+        // covers the Watt column as well: loads return in the order they were ISSUED)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < NRW; ++q) {
+            int u = u_lo + wave + q * NWB;
+            u = u > u_hi ? u_hi : u;  // (0 <= u_lo <= u_hi < U; rows past the support re-read its last row, never reduced)
+#pragma unroll
+            for (int sg = 0; sg < SEG; ++sg) {
+                const int e = lane + 64 * sg;
+                cpre[q][sg] = ctx[(size_t)u * E + (e < E ? e : E - 1)];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        {
+            const int tc = t < H ? t : H - 1, jmax = 3 * A - 1;
+#pragma unroll
+            for (int j = 0; j < WPRE; ++j) wpre[j] = g.WattT[(size_t)(j < jmax ? j : jmax) * H + tc];  // (rows >= 3A: never used)
+        }
+        late();
+        __builtin_amdgcn_sched_barrier(0);
+        // (the total as a select, not under `if (on2)`: the compiler sank the five share loads into that block, behind every
+        // other request, and closed it with vmcnt(0))
+        float vs = x1 + x2;
+        vs += on3 ? x3 : 0.f;
+        vs += on4 ? x4 : 0.f;
+        vs += on5 ? x5 : 0.f;
+        vs += on6 ? x6 : 0.f;
+        const float v = on2 ? vs : x1;
+        if (on2 && t < E) g.dw[i] = v;  // total, needed later for the deferred d(ctx) GEMM
+        s_dw[t] = v;  // (threads >= E: a copy of column E - 1 in the row's unused tail, see att_bwd_dwsz)
+    }
     if (use_pre) {
         const int hi_c = u_hi >= u_lo ? u_hi : u_lo;  // (empty support: u_lo = U, u_hi = -1 -> everything clamps to row U - 1 / 0)
 #pragma unroll
@@ -71,14 +132,8 @@ __device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* s
             }
         }
     }
-    constexpr int WPRE = 32;
-    const bool use_wpre = (H <= ATTB_THREADS) && (3 * A <= WPRE);
-    float wpre[WPRE];
-    // the carry of kappa's gradient and kappa_{t-1}: needed four phases later, requested now
-    const int ta = t < A ? t : A - 1;
-    const float pre_dkappa = g.dkappa[(size_t)b * A + ta], pre_kprev = g.kappa_prev[(size_t)b * A + ta];
-    const float pre_a = g.a[(size_t)b * A + ta], pre_b = g.b[(size_t)b * A + ta], pre_k = g.kappa[(size_t)b * A + ta];
-    {
+    if constexpr (!NARROW) {
+        request_pre();
         const bool on2 = g.dw2 != nullptr, on3 = on2 && g.dw3, on4 = on2 && g.dw4, on5 = on2 && g.dw5, on6 = on2 && g.dw6;
         const float* p2 = on2 ? g.dw2 : g.dw;
         const float* p3 = on3 ? g.dw3 : g.dw;
@@ -110,7 +165,22 @@ __device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* s
     ATT_STAMP(1, b, 2);
 
     // dphi[u] = sum_e dw[e] ctx[u][e]: one wave per u, lanes over e (coalesced row reads).
-    if (use_pre) {
+    if constexpr (NARROW) {
+        float dseg[SEG];
+#pragma unroll
+        for (int sg = 0; sg < SEG; ++sg) dseg[sg] = (lane + 64 * sg < E) ? s_dw[lane + 64 * sg] : 0.f;
+#pragma unroll
+        for (int q = 0; q < NRW; ++q) {
+            const int u = u_lo + wave + q * NWB;
+            float acc = 0.f;
+#pragma unroll
+            for (int sg = 0; sg < SEG; ++sg) acc += dseg[sg] * cpre[q][sg];
+            if (u <= u_hi) {  // wave-uniform; no load inside
+                const float r = wave_sum(acc);
+                if (lane == 0) s_dphi[u] = r;
+            }
+        }
+    } else if (use_pre) {
         float dseg[SEG];
 #pragma unroll
         for (int sg = 0; sg < SEG; ++sg) dseg[sg] = (lane + 64 * sg < E) ? s_dw[lane + 64 * sg] : 0.f;
@@ -148,8 +218,8 @@ __device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* s
 
     // The context registers are dead now: request this thread's column of the projection matrix (used by the
     // last phase) so that its latency hides behind the reductions below.
-    late();
-    if (use_wpre) {
+    if constexpr (!NARROW) late();
+    if (!NARROW && use_wpre) {
         const int tc = t < H ? t : H - 1, jmax = 3 * A - 1;
 #pragma unroll
         for (int j = 0; j < WPRE; ++j) wpre[j] = g.WattT[(size_t)(j < jmax ? j : jmax) * H + tc];  // (rows >= 3A: never used)
@@ -252,6 +322,20 @@ __device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* s
     return false;
 }
 
+template <class LATE = AttBwdNoLate>
+__device__ __forceinline__ bool att_bwd_row(const AttBwdArgs& g, int b, float* sm, float* dh_io = nullptr, LATE late = LATE()) {
+    // Support of the window saved by the forward step: outside [u_lo, u_hi] every exp(-b (kappa-u)^2) is exactly
+    // 0.0f, so dphi[u] is multiplied by zero in all three mixture gradients and its context row is not needed.
+    int u_lo = 0, u_hi = g.U - 1;
+    if (g.sup) {
+        u_lo = g.sup[2 * b];
+        u_hi = g.sup[2 * b + 1];
+    }
+    if (att_bwd_route(g.narrow, g.sup != nullptr, g.U, g.E, u_lo, u_hi) == ATTB_ROUTE_NARROW)
+        return att_bwd_row_impl<true>(g, b, sm, dh_io, late, u_lo, u_hi);
+    return att_bwd_row_impl<false>(g, b, sm, dh_io, late, u_lo, u_hi);
+}
+
 // One launch for the attention backward of layer 0's step AND the elementwise GRU state backward of every layer
 // active in this tick of the backward wavefront (plans.hip): blocks [0, att_rows) take one attention row each
 // and then, with the same threads (thread k updated dh1[b][k] itself), layer 0's state backward for that row;
@@ -293,7 +377,10 @@ __device__ __forceinline__ void att_state_bwd_block(const AttBwdArgs& g, const S
                 const float* q3 = reinterpret_cast<const float*>(a3 ? a3 : a1);
                 const float* q4 = reinterpret_cast<const float*>(a4 ? a4 : a1);
                 const float* q5 = reinterpret_cast<const float*>(a5 ? a5 : a1);
-                const float* qm = reinterpret_cast<const float*>(am ? am + 4ull * (unsigned)bx : (unsigned long long)c.z);
+                // (a global pointer by type: as a generic one its load was a flat load, and while one of those is in flight
+                // every wait for a vector load is compiled as vmcnt(0) -- the counted waits behind late() were all full ones)
+                typedef const __attribute__((address_space(1))) float* gfloat;
+                const gfloat qm = (gfloat)(am ? am + 4ull * (unsigned)bx : (unsigned long long)c.z);
                 float dh = 0.f, y2 = 0.f, y3 = 0.f, y4 = 0.f, y5 = 0.f, hp = 0.f, z = 0.f, cc = 0.f, dhp = 0.f, mkl = 1.f;
                 const bool got = att_bwd_row(g, bx, sm, &dh, [&]() {
                     dh = c.dh[ic];  // (= g.dh1[b][t]: the attention backward's accumulation target)

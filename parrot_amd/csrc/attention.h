@@ -48,7 +48,19 @@ struct AttBwdArgs {
     int B, H, A, U, E, att_type;
     float eps;
     const int* sup;  // [B,2] or null: the forward step's window support
+    int narrow;      // set by the launch functions (PARROT_ATT_BWD_NARROW): rows that att_bwd_route allows take the narrow path
 };
+
+// Which path of att_bwd_row a batch row takes (block-uniform, decided before the row block's first request; host
+// arithmetic as well: parrot_att_bwd_route).  Narrow: the saved support is present, lies inside the text and is at most
+// ATTB_CAP rows wide, and the shape is one the register preload covers; everything else runs the wide path.
+constexpr int ATTB_CAP = 64;  // a multiple of the row block's 16 waves
+constexpr int ATTB_ROUTE_WIDE = 0, ATTB_ROUTE_NARROW = 1;
+__host__ __device__ inline int att_bwd_route(int narrow_on, bool has_sup, int U, int E, int u_lo, int u_hi) {
+    const bool ok = narrow_on && has_sup && U <= 256 && E <= 256 && u_lo >= 0 && u_lo <= u_hi && u_hi < U &&
+                    u_hi - u_lo < ATTB_CAP;
+    return ok ? ATTB_ROUTE_NARROW : ATTB_ROUTE_WIDE;
+}
 
 int att_fwd_launch(const AttFwdArgs& g, hipStream_t stream);
 // Validates the arguments and sets `dense` from PARROT_ATT_DENSE (what att_fwd_launch does before it launches).

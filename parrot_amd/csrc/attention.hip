@@ -66,6 +66,7 @@ int att_fwd_launch(const AttFwdArgs& gin, hipStream_t stream) {
 
 int att_bwd_launch(const AttBwdArgs& gin, hipStream_t stream) {
     AttBwdArgs g = gin;
+    g.narrow = sw_att_bwd_narrow();  // read per launch, as PARROT_ATT_DENSE
     if (g.A < 1 || g.A > ATT_MAXA || g.B < 1 || g.U < 1 || g.E < 1) return PH_ERR_BADARG;
     const size_t lds = att_bwd_lds(g.U, g.E);
     if (lds > 160 * 1024) return PH_ERR_UNSUPPORTED;
@@ -80,6 +81,7 @@ static int att_state_bwd_launch_t(const AttBwdArgs* gin, const SA& sa, int l0_ch
     size_t lds = 0;
     if (gin) {
         g = *gin;
+        g.narrow = sw_att_bwd_narrow();
         if (g.A < 1 || g.A > ATT_MAXA || g.B < 1 || g.U < 1 || g.E < 1 || g.B != sa.B) return PH_ERR_BADARG;
         lds = att_bwd_lds(g.U, g.E);
         if (lds > 160 * 1024) return PH_ERR_UNSUPPORTED;

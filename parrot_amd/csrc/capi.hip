@@ -384,12 +384,13 @@ int parrot_gru_step_bwd(const float* dh_out, const float* h, const float* mask, 
     return sk_launch(L, st);
 }
 
-int parrot_gmm_attention_fwd(const float* h1, const float* WattT, const float* batt, const float* kappa_prev,
-                             const float* ctx, float* a, float* b, float* kappa, float* phi, float* w, int B,
-                             int H, int A, int U, int E, int att_type, float eps, float alignment,
-                             float sharpening, float timing, void* stream) { PH_ENTRY();
+static int gmm_attention_fwd_impl(const float* h1, const float* WattT, const float* batt, const float* kappa_prev,
+                                  const float* ctx, float* a, float* b, float* kappa, float* phi, float* w, int B,
+                                  int H, int A, int U, int E, int att_type, float eps, float alignment,
+                                  float sharpening, float timing, int* sup, void* stream) {
     if (!h1 || !WattT || !kappa_prev || !ctx || !a || !b || !kappa || !phi || !w) return PARROT_ERR_BADARG;
     AttFwdArgs g{};
+    g.sup_out = sup;
     g.h1 = h1; g.ldh = H; g.WattT = WattT; g.batt = batt; g.kappa_prev = kappa_prev; g.ctx = ctx;
     g.a_out = a; g.b_out = b; g.kappa_out = kappa; g.phi_out = phi; g.w_out = w; g.ldw = E;
     g.B = B; g.H = H; g.A = A; g.U = U; g.E = E; g.esplit = att_default_esplit(B, E);
@@ -397,17 +398,58 @@ int parrot_gmm_attention_fwd(const float* h1, const float* WattT, const float* b
     return att_fwd_launch(g, (hipStream_t)stream);
 }
 
-int parrot_gmm_attention_bwd(const float* dw, const float* ctx, const float* a, const float* b,
-                             const float* kappa, const float* kappa_prev, const float* WattT, float* dkappa,
-                             float* dp, float* dh1, int B, int H, int A, int U, int E, int att_type, float eps,
-                             void* stream) { PH_ENTRY();
+int parrot_gmm_attention_fwd(const float* h1, const float* WattT, const float* batt, const float* kappa_prev,
+                             const float* ctx, float* a, float* b, float* kappa, float* phi, float* w, int B,
+                             int H, int A, int U, int E, int att_type, float eps, float alignment,
+                             float sharpening, float timing, void* stream) { PH_ENTRY();
+    return gmm_attention_fwd_impl(h1, WattT, batt, kappa_prev, ctx, a, b, kappa, phi, w, B, H, A, U, E, att_type, eps, alignment,
+                                  sharpening, timing, nullptr, stream);
+}
+
+int parrot_gmm_attention_fwd_sup(const float* h1, const float* WattT, const float* batt, const float* kappa_prev,
+                                 const float* ctx, float* a, float* b, float* kappa, float* phi, float* w, int B,
+                                 int H, int A, int U, int E, int att_type, float eps, float alignment,
+                                 float sharpening, float timing, int* sup, void* stream) { PH_ENTRY();
+    if (!sup) return PARROT_ERR_BADARG;
+    return gmm_attention_fwd_impl(h1, WattT, batt, kappa_prev, ctx, a, b, kappa, phi, w, B, H, A, U, E, att_type, eps, alignment,
+                                  sharpening, timing, sup, stream);
+}
+
+static int gmm_attention_bwd_impl(const float* dw, const float* ctx, const float* a, const float* b,
+                                  const float* kappa, const float* kappa_prev, const float* WattT, float* dkappa,
+                                  float* dp, float* dh1, int B, int H, int A, int U, int E, int att_type, float eps,
+                                  const int* sup, void* stream) {
     if (!dw || !ctx || !a || !b || !kappa || !kappa_prev || !WattT || !dkappa || !dp || !dh1)
         return PARROT_ERR_BADARG;
     AttBwdArgs g{};
+    g.sup = sup;
     g.dw = const_cast<float*>(dw); g.dw2 = nullptr; g.lddw = E; g.ctx = ctx; g.a = a; g.b = b; g.kappa = kappa; g.kappa_prev = kappa_prev;
     g.WattT = WattT; g.dkappa = dkappa; g.dp_out = dp; g.dh1 = dh1; g.lddh = H;
     g.B = B; g.H = H; g.A = A; g.U = U; g.E = E; g.att_type = att_type; g.eps = eps;
     return att_bwd_launch(g, (hipStream_t)stream);
+}
+
+int parrot_gmm_attention_bwd(const float* dw, const float* ctx, const float* a, const float* b,
+                             const float* kappa, const float* kappa_prev, const float* WattT, float* dkappa,
+                             float* dp, float* dh1, int B, int H, int A, int U, int E, int att_type, float eps,
+                             void* stream) { PH_ENTRY();
+    return gmm_attention_bwd_impl(dw, ctx, a, b, kappa, kappa_prev, WattT, dkappa, dp, dh1, B, H, A, U, E, att_type, eps,
+                                  nullptr, stream);
+}
+
+int parrot_gmm_attention_bwd_sup(const float* dw, const float* ctx, const float* a, const float* b,
+                                 const float* kappa, const float* kappa_prev, const float* WattT, float* dkappa,
+                                 float* dp, float* dh1, int B, int H, int A, int U, int E, int att_type, float eps,
+                                 const int* sup, void* stream) { PH_ENTRY();
+    return gmm_attention_bwd_impl(dw, ctx, a, b, kappa, kappa_prev, WattT, dkappa, dp, dh1, B, H, A, U, E, att_type, eps, sup,
+                                  stream);
+}
+
+int parrot_att_bwd_route(int U, int E, int has_sup, int u_lo, int u_hi, int* route) {
+    // (no HIP call here: the query works without a device)
+    if (!route || U < 1 || E < 1) return PARROT_ERR_BADARG;
+    *route = att_bwd_route(sw_att_bwd_narrow(), has_sup != 0, U, E, u_lo, u_hi);
+    return 0;
 }
 
 int parrot_sumsq(const float* x, size_t n, float* out, void* stream) { PH_ENTRY();

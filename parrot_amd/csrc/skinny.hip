@@ -1472,6 +1472,7 @@ int sk_launch_bwd_fused(const SkLaunch& Lin, const AttBwdArgs* att, const LstmSt
         if (att->A < 1 || att->A > ATT_MAXA || att->B != sa.B || att->U < 1 || att->E < 1 || l0_chain < 0 || l0_chain >= sa.nchain)
             return PH_ERR_BADARG;
         P.att = *att;
+        P.att.narrow = sw_att_bwd_narrow();
         P.att_rows = att->B;
         P.l0_chain = l0_chain;
         plds = att_bwd_lds(att->U, att->E);
@@ -1640,6 +1641,7 @@ int sk_launch_bwd_hetero(const SkLaunch& Lin, const AttBwdArgs* att, const GruSt
     size_t alds = 0;
     if (att) {
         g = *att;
+        g.narrow = sw_att_bwd_narrow();
         if (g.A < 1 || g.A > ATT_MAXA || g.B < 1 || g.U < 1 || g.E < 1 || g.B != sa.B || l0_chain < 0 || l0_chain >= sa.nchain)
             return PH_ERR_BADARG;
         alds = att_bwd_lds(g.U, g.E);

@@ -25,6 +25,9 @@
 //                                   launch   columns, 2 whenever legal
 // PARROT_ATT_DENSE         0        plan,    1: the attention reads every context row instead of walking    bench.py, tests
 //                                   launch   its support (same result)
+// PARROT_ATT_BWD_NARROW    1        launch   0: the attention backward row block always fetches and reduces  tests, tools
+//                                            its full 16 context rows per wave (no narrow path for supports
+//                                            of at most 64 rows; same result, bit for bit)
 // PARROT_PM_DATAFLOW       0 / 1    plan     persistent machines: 1 = per-unit flags, 0 = grid barriers;    tests
 //                                            default 1 for the sampling plan cut in pieces and the LSTM
 //                                            sampling plan with one unit per workgroup, 0 otherwise
@@ -83,6 +86,7 @@ static inline const char* env_str(const char* name) { return getenv(name); }
 
 // Switches read in more than one place.
 static inline int sw_att_dense() { return env_int("PARROT_ATT_DENSE", 0); }
+static inline int sw_att_bwd_narrow() { return env_int("PARROT_ATT_BWD_NARROW", 1) != 0; }
 static inline int sw_pm_dataflow(int dflt) { return env_int("PARROT_PM_DATAFLOW", dflt); }
 static inline int sw_rg_waves() { return env_int("PARROT_RG_WAVES", 8); }
 static inline int sw_wk() { return env_int("PARROT_WK", 1); }

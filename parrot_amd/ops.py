@@ -856,8 +856,24 @@ def lstm_seq(pre_in, s0, c0, W):
 
 
 # ----------------------------------------------------------------------------- attention step
+ATT_BWD_WIDE, ATT_BWD_NARROW = 0, 1
+ATT_BWD_CAP = 64
+
+
+def att_bwd_route(U, E, support=None):
+    """Path the attention backward row block takes for a batch row (parrot_att_bwd_route): ATT_BWD_NARROW or ATT_BWD_WIDE.
+    support = (u_lo, u_hi) as the forward step saved it, None = no support handed in.  Host arithmetic only."""
+    import ctypes as C
+    route = C.c_int(-1)
+    lo, hi = (0, 0) if support is None else (int(support[0]), int(support[1]))
+    _lib.call("parrot_att_bwd_route", int(U), int(E), int(support is not None), lo, hi, C.byref(route))
+    return route.value
+
+
 def gmm_attention_fwd(h1, WattT, batt, kappa_prev, ctx, att_type=0, eps=1e-5, alignment=1.0,
-                      sharpening=1.0, timing=1.0):
+                      sharpening=1.0, timing=1.0, return_support=False):
+    """return_support: also return sup [B,2] int32, the first / last context position of non-zero window weight per row
+    (what the training scan hands to the backward step)."""
     B, H = h1.shape
     A = kappa_prev.shape[1]
     _, U, E = ctx.shape
@@ -865,6 +881,13 @@ def gmm_attention_fwd(h1, WattT, batt, kappa_prev, ctx, att_type=0, eps=1e-5, al
     a, b, k = (torch.empty((B, A), **f) for _ in range(3))
     phi = torch.empty((B, U), **f)
     w = torch.empty((B, E), **f)
+    if return_support:
+        sup = torch.empty((B, 2), device=h1.device, dtype=torch.int32)
+        _lib.call("parrot_gmm_attention_fwd_sup", ptr(h1, "h1"), ptr(WattT, "WattT"), ptr(batt, "batt"),
+                  ptr(kappa_prev, "kappa_prev"), ptr(ctx, "ctx"), ptr(a), ptr(b), ptr(k), ptr(phi), ptr(w),
+                  B, H, A, U, E, int(att_type), float(eps), float(alignment), float(sharpening), float(timing),
+                  ptr(sup, "sup", torch.int32), _stream())
+        return a, b, k, phi, w, sup
     _lib.call("parrot_gmm_attention_fwd", ptr(h1, "h1"), ptr(WattT, "WattT"), ptr(batt, "batt"),
               ptr(kappa_prev, "kappa_prev"), ptr(ctx, "ctx"), ptr(a), ptr(b), ptr(k), ptr(phi), ptr(w),
               B, H, A, U, E, int(att_type), float(eps), float(alignment), float(sharpening), float(timing),
@@ -872,12 +895,20 @@ def gmm_attention_fwd(h1, WattT, batt, kappa_prev, ctx, att_type=0, eps=1e-5, al
     return a, b, k, phi, w
 
 
-def gmm_attention_bwd(dw, ctx, a, b, kappa, kappa_prev, WattT, dkappa, dh1, att_type=0, eps=1e-5):
-    """dkappa [B,A] is updated in place (carry); dh1 [B,H] is accumulated; returns dp [B,3A]."""
+def gmm_attention_bwd(dw, ctx, a, b, kappa, kappa_prev, WattT, dkappa, dh1, att_type=0, eps=1e-5, support=None):
+    """dkappa [B,A] is updated in place (carry); dh1 [B,H] is accumulated; returns dp [B,3A].
+    support: sup [B,2] int32 of the forward step (gmm_attention_fwd(..., return_support=True)) or None."""
     B, H = dh1.shape
     A = kappa.shape[1]
     _, U, E = ctx.shape
     dp = torch.empty((B, 3 * A), device=dw.device, dtype=torch.float32)
+    if support is not None:
+        if support.dtype != torch.int32 or tuple(support.shape) != (B, 2) or not support.is_contiguous():
+            raise ValueError("gmm_attention_bwd: support must be a contiguous int32 [B,2] tensor")
+        _lib.call("parrot_gmm_attention_bwd_sup", ptr(dw, "dw"), ptr(ctx, "ctx"), ptr(a), ptr(b), ptr(kappa),
+                  ptr(kappa_prev), ptr(WattT), ptr(dkappa), ptr(dp), ptr(dh1), B, H, A, U, E, int(att_type),
+                  float(eps), ptr(support, "support", torch.int32), _stream())
+        return dp
     _lib.call("parrot_gmm_attention_bwd", ptr(dw, "dw"), ptr(ctx, "ctx"), ptr(a), ptr(b), ptr(kappa),
               ptr(kappa_prev), ptr(WattT), ptr(dkappa), ptr(dp), ptr(dh1), B, H, A, U, E, int(att_type),
               float(eps), _stream())
