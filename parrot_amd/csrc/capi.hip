@@ -172,12 +172,9 @@ static int gemm_impl(const float* A, int lda, int transA, const float* B, int ld
                                        gate != nullptr, gemm_mode_in_force());
     if (route == PARROT_GEMM_ROUTE_STEP) {
         SkJob j;
-        sk_job_init(j);
-        j.nseg = 1;
-        j.seg[0] = sk_seg(A, lda, B, ldb, K, transB ? 1 : 0);
-        j.M = M; j.N = N; j.H = N; j.epi = SK_EPI_LINEAR; j.act = act; j.accumulate = accumulate;
+        sk_linear_job(j, sk_seg(A, lda, B, ldb, K, transB ? 1 : 0), M, N, N, C, ldc, accumulate);
+        j.act = act;
         j.bias = bias;
-        j.out = C; j.ldo = ldc;
         SkLaunch L;
         int rc = sk_make_launch(L, &j, 1);
         if (rc) return rc;
@@ -235,13 +232,16 @@ int parrot_step_launch_mode(int njobs, const int* M, const int* N, const int* K,
     for (int q = 0; q < njobs; ++q) {
         if (M[q] < 1 || N[q] < 1 || K[q] < 1) return PARROT_ERR_BADARG;
         SkJob& j = jobs[q];
-        sk_job_init(j);
+        // (shapes only: the jobs are laid out by sk_prepare, never launched, so their buffers stay null)
+        if (lstm_H && lstm_H[q] > 0) {
+            sk_lstm_job(j, M[q], lstm_H[q], nullptr, nullptr, nullptr, nullptr);
+            j.N = N[q];  // (as given: sk_make_launch refuses a width other than 4 lstm_H)
+        } else {
+            sk_linear_job(j, M[q], N[q], N[q], nullptr, 0);
+        }
         const float* aligned_base = reinterpret_cast<const float*>(uintptr_t(4096));  // (inspected for alignment only)
         j.nseg = 1;
         j.seg[0] = sk_seg(aligned_base, (K[q] + 3) & ~3, aligned_base, (N[q] + 3) & ~3, K[q], 0);
-        j.M = M[q]; j.N = N[q];
-        j.H = lstm_H && lstm_H[q] > 0 ? lstm_H[q] : N[q];
-        j.epi = lstm_H && lstm_H[q] > 0 ? SK_EPI_LSTM : SK_EPI_LINEAR;
     }
     SkLaunch Lin, L;
     const int rc = sk_make_launch(Lin, jobs, njobs);
@@ -325,24 +325,19 @@ int parrot_gru_step_fwd(const float* h, const float* inputs, const float* gate_i
     hipStream_t st = (hipStream_t)stream;
     SkJob j;
     SkLaunch L;
-    sk_job_init(j);
+    sk_gru_gates_job(j, B, H, h, z, r, rh);
     j.nseg = 1;
     j.seg[0] = sk_seg(h, H, Wg, 2 * H, H, 0);
-    j.M = B; j.N = 2 * H; j.H = H; j.epi = SK_EPI_GRU_GATES;
     j.add = gate_inputs; j.ld_add = 2 * H;
-    j.e0 = h; j.lde0 = H;
-    j.o1 = z; j.ldo1 = H; j.o2 = r; j.ldo2 = H; j.out = rh; j.ldo = H;
     int rc = sk_make_launch(L, &j, 1);
     if (rc) return rc;
     rc = sk_launch(L, st);
     if (rc) return rc;
-    sk_job_init(j);
+    sk_gru_cand_job(j, B, H, h, z, c, h_out);
     j.nseg = 1;
     j.seg[0] = sk_seg(rh, H, Wc, H, H, 0);
-    j.M = B; j.N = H; j.H = H; j.epi = SK_EPI_GRU_CAND;
     j.add = inputs; j.ld_add = H;
-    j.e0 = h; j.lde0 = H; j.e1 = z; j.lde1 = H;
-    j.o1 = c; j.ldo1 = H; j.out = h_out; j.ldo = H; j.mask = mask;
+    j.mask = mask;
     rc = sk_make_launch(L, &j, 1);
     if (rc) return rc;
     return sk_launch(L, st);
@@ -364,21 +359,14 @@ int parrot_gru_step_bwd(const float* dh_out, const float* h, const float* mask, 
     if (rc) return rc;
     SkJob j;
     SkLaunch L;
-    sk_job_init(j);
+    sk_bwd_rh_job(j, B, H, h, r, d_gate_inputs + H, 2 * H, dh);
     j.nseg = 1;
     j.seg[0] = sk_seg(d_inputs, H, Wc, H, H, 1);
-    j.M = B; j.N = H; j.H = H; j.epi = SK_EPI_BWD_RH;
-    j.e0 = h; j.lde0 = H; j.e1 = r; j.lde1 = H;
-    j.out = d_gate_inputs + H; j.ldo = 2 * H; j.o1 = dh; j.ldo1 = H;
     rc = sk_make_launch(L, &j, 1);
     if (rc) return rc;
     rc = sk_launch(L, st);
     if (rc) return rc;
-    sk_job_init(j);
-    j.nseg = 1;
-    j.seg[0] = sk_seg(d_gate_inputs, 2 * H, Wg, 2 * H, 2 * H, 1);
-    j.M = B; j.N = H; j.H = H; j.epi = SK_EPI_LINEAR; j.accumulate = 1;
-    j.out = dh; j.ldo = H;
+    sk_linear_job(j, sk_seg(d_gate_inputs, 2 * H, Wg, 2 * H, 2 * H, 1), B, H, H, dh, H, 1);
     rc = sk_make_launch(L, &j, 1);
     if (rc) return rc;
     return sk_launch(L, st);

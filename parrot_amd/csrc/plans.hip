@@ -82,29 +82,19 @@ struct GruSeqPlan : PlanBase {
             for (int ch = 0; ch < d.nchain; ++ch) {
                 const int t = d.reverse[ch] ? d.T - 1 - s : s;
                 SkJob& j = jobs[ch];
-                sk_job_init(j);
+                sk_gru_gates_job(j, d.B, d.H, d.h[ch] + s * BH, d.z[ch] + t * BH, d.r[ch] + t * BH, d.rh[ch] + t * BH);
                 j.nseg = 1;
                 j.seg[0] = sk_seg(d.h[ch] + s * BH, d.H, d.Wg[ch], 2 * d.H, d.H, 0);
-                j.M = d.B; j.N = 2 * d.H; j.H = d.H; j.epi = SK_EPI_GRU_GATES;
                 j.add = d.gate_inputs[ch] ? d.gate_inputs[ch] + t * 2 * BH : nullptr; j.ld_add = 2 * d.H;
-                j.e0 = d.h[ch] + s * BH; j.lde0 = d.H;
-                j.o1 = d.z[ch] + t * BH; j.ldo1 = d.H;
-                j.o2 = d.r[ch] + t * BH; j.ldo2 = d.H;
-                j.out = d.rh[ch] + t * BH; j.ldo = d.H;
             }
             PL_TRY(launch_jobs(jobs, d.nchain, st));
             for (int ch = 0; ch < d.nchain; ++ch) {
                 const int t = d.reverse[ch] ? d.T - 1 - s : s;
                 SkJob& j = jobs[ch];
-                sk_job_init(j);
+                sk_gru_cand_job(j, d.B, d.H, d.h[ch] + s * BH, d.z[ch] + t * BH, d.c[ch] + t * BH, d.h[ch] + (s + 1) * BH);
                 j.nseg = 1;
                 j.seg[0] = sk_seg(d.rh[ch] + t * BH, d.H, d.Wc[ch], d.H, d.H, 0);
-                j.M = d.B; j.N = d.H; j.H = d.H; j.epi = SK_EPI_GRU_CAND;
                 j.add = d.inputs[ch] ? d.inputs[ch] + t * BH : nullptr; j.ld_add = d.H;
-                j.e0 = d.h[ch] + s * BH; j.lde0 = d.H;
-                j.e1 = d.z[ch] + t * BH; j.lde1 = d.H;
-                j.o1 = d.c[ch] + t * BH; j.ldo1 = d.H;
-                j.out = d.h[ch] + (s + 1) * BH; j.ldo = d.H;
                 j.mask = d.mask ? d.mask + (size_t)t * d.B : nullptr;
             }
             PL_TRY(launch_jobs(jobs, d.nchain, st));
@@ -132,21 +122,14 @@ struct GruSeqPlan : PlanBase {
                 c.dhprev = d.dh[ch] + s * BH;
 
                 SkJob& x = jx[ch];
-                sk_job_init(x);
+                sk_bwd_rh_job(x, d.B, d.H, d.h[ch] + s * BH, d.r[ch] + t * BH, d.dG[ch] + t * 2 * BH + d.H, 2 * d.H,
+                              d.dh[ch] + s * BH);
                 x.nseg = 1;
                 x.seg[0] = sk_seg(d.dC[ch] + t * BH, d.H, d.Wc[ch], d.H, d.H, 1);
-                x.M = d.B; x.N = d.H; x.H = d.H; x.epi = SK_EPI_BWD_RH;
-                x.e0 = d.h[ch] + s * BH; x.lde0 = d.H;
-                x.e1 = d.r[ch] + t * BH; x.lde1 = d.H;
-                x.out = d.dG[ch] + t * 2 * BH + d.H; x.ldo = 2 * d.H;
-                x.o1 = d.dh[ch] + s * BH; x.ldo1 = d.H;
 
                 SkJob& y = jy[ch];
-                sk_job_init(y);
-                y.nseg = 1;
-                y.seg[0] = sk_seg(d.dG[ch] + t * 2 * BH, 2 * d.H, d.Wg[ch], 2 * d.H, 2 * d.H, 1);
-                y.M = d.B; y.N = d.H; y.H = d.H; y.epi = SK_EPI_LINEAR; y.accumulate = 1;
-                y.out = d.dh[ch] + s * BH; y.ldo = d.H;
+                sk_linear_job(y, sk_seg(d.dG[ch] + t * 2 * BH, 2 * d.H, d.Wg[ch], 2 * d.H, 2 * d.H, 1), d.B, d.H, d.H,
+                              d.dh[ch] + s * BH, d.H, 1);
             }
             PL_TRY(gru_state_bwd_launch(ga, st));
             PL_TRY(launch_jobs(jx, d.nchain, st));
@@ -165,15 +148,10 @@ struct LstmSeqPlan : PlanBase {
         const size_t BH = (size_t)d.B * d.H;
         for (int t = 0; t < d.T; ++t) {
             SkJob j;
-            sk_job_init(j);
+            sk_lstm_job(j, d.B, d.H, d.c + t * BH, d.c + (t + 1) * BH, d.gates + (size_t)t * 4 * BH, d.s + (t + 1) * BH);
             j.nseg = 1;
             j.seg[0] = sk_seg(d.s + t * BH, d.H, d.W, 4 * d.H, d.H, 0);
-            j.M = d.B; j.N = 4 * d.H; j.H = d.H; j.epi = SK_EPI_LSTM;
             j.add = d.pre_in + (size_t)t * 4 * BH; j.ld_add = 4 * d.H;
-            j.e1 = d.c + t * BH; j.lde1 = d.H;
-            j.o1 = d.c + (t + 1) * BH; j.ldo1 = d.H;
-            j.o2 = d.gates + (size_t)t * 4 * BH; j.ldo2 = 4 * d.H;
-            j.out = d.s + (t + 1) * BH; j.ldo = d.H;
             PL_TRY(launch_jobs(&j, 1, st));
         }
         return 0;
@@ -185,11 +163,8 @@ struct LstmSeqPlan : PlanBase {
             PL_TRY(lstm_state_bwd_launch(d.dS + (t + 1) * BH, nullptr, d.dc, d.gates + (size_t)t * 4 * BH, d.c + t * BH,
                                          d.c + (t + 1) * BH, d.dP + (size_t)t * 4 * BH, d.B, d.H, st));
             SkJob y;
-            sk_job_init(y);
-            y.nseg = 1;
-            y.seg[0] = sk_seg(d.dP + (size_t)t * 4 * BH, 4 * d.H, d.W, 4 * d.H, 4 * d.H, 1);
-            y.M = d.B; y.N = d.H; y.H = d.H; y.epi = SK_EPI_LINEAR; y.accumulate = 1;
-            y.out = d.dS + t * BH; y.ldo = d.H;
+            sk_linear_job(y, sk_seg(d.dP + (size_t)t * 4 * BH, 4 * d.H, d.W, 4 * d.H, 4 * d.H, 1), d.B, d.H, d.H, d.dS + t * BH,
+                          d.H, 1);
             PL_TRY(launch_jobs(&y, 1, st));
         }
         return 0;
@@ -332,41 +307,26 @@ struct DecoderPlan : PlanBase {
     // ---- job and chain builders ---------------------------------------------------------------------------------------
     void gates_job(SkJob& j, int l, int t) const {
         const size_t BH = (size_t)d.B * d.H;
-        sk_job_init(j);
+        sk_gru_gates_job(j, d.B, d.H, d.h[l] + t * BH, d.z[l] + t * BH, d.r[l] + t * BH, d.rh[l] + t * BH);
         layer_segs(j, l, t, d.h[l] + t * BH, 0, 2 * d.H);
-        j.M = d.B; j.N = 2 * d.H; j.H = d.H; j.epi = SK_EPI_GRU_GATES;
         j.bias = d.bg[l];
         j.add = has_seq(l, d.seq_g[l]) ? d.seq_g[l] + t * 2 * BH : nullptr; j.ld_add = 2 * d.H;
-        j.e0 = d.h[l] + t * BH; j.lde0 = d.H;
-        j.o1 = d.z[l] + t * BH; j.ldo1 = d.H;
-        j.o2 = d.r[l] + t * BH; j.ldo2 = d.H;
-        j.out = d.rh[l] + t * BH; j.ldo = d.H;
     }
 
     void cand_job(SkJob& j, int l, int t) const {
         const size_t BH = (size_t)d.B * d.H;
-        sk_job_init(j);
+        sk_gru_cand_job(j, d.B, d.H, d.h[l] + t * BH, d.z[l] + t * BH, d.c[l] + t * BH, d.h[l] + (t + 1) * BH);
         layer_segs(j, l, t, d.rh[l] + t * BH, 1, d.H);
-        j.M = d.B; j.N = d.H; j.H = d.H; j.epi = SK_EPI_GRU_CAND;
         j.bias = d.bc[l];
         j.add = has_seq(l, d.seq_c[l]) ? d.seq_c[l] + t * BH : nullptr; j.ld_add = d.H;
-        j.e0 = d.h[l] + t * BH; j.lde0 = d.H;
-        j.e1 = d.z[l] + t * BH; j.lde1 = d.H;
-        j.o1 = d.c[l] + t * BH; j.ldo1 = d.H;
-        j.out = d.h[l] + (t + 1) * BH; j.ldo = d.H;
     }
 
     void lstm_job(SkJob& j, int l, int t) const {
         const size_t BH = (size_t)d.B * d.H;
-        sk_job_init(j);
+        sk_lstm_job(j, d.B, d.H, d.cst[l] + t * BH, d.cst[l] + (t + 1) * BH, d.gate4[l] + t * 4 * BH, d.h[l] + (t + 1) * BH);
         layer_segs(j, l, t, d.h[l] + t * BH, 0, 4 * d.H);
-        j.M = d.B; j.N = 4 * d.H; j.H = d.H; j.epi = SK_EPI_LSTM;
         j.bias = d.bg[l];
         j.add = has_seq(l, d.seq_g[l]) ? d.seq_g[l] + t * 4 * BH : nullptr; j.ld_add = 4 * d.H;
-        j.e1 = d.cst[l] + t * BH; j.lde1 = d.H;
-        j.o1 = d.cst[l] + (t + 1) * BH; j.ldo1 = d.H;
-        j.o2 = d.gate4[l] + t * 4 * BH; j.ldo2 = 4 * d.H;
-        j.out = d.h[l] + (t + 1) * BH; j.ldo = d.H;
     }
 
     // Input projection of layer l >= 1 for step t (schedule 5): [w_{t+1} ; h_0 .. h_{l-1}] . W[H:, :] into the layer's
@@ -376,7 +336,9 @@ struct DecoderPlan : PlanBase {
     void input_job(SkJob& j, int l, int t, int g, int part = 0, bool no_w = false) const {
         const size_t BH = (size_t)d.B * d.H, BE = (size_t)d.B * d.E;
         const int wd = d.cell == 1 ? 4 * d.H : (g == 0 ? 2 * d.H : d.H);  // LSTM layers: one 4H-wide matrix (g = 0)
-        sk_job_init(j);
+        // (accumulate: part 2 onto part 1; otherwise onto caller data -- feedback / speaker terms -- already there)
+        sk_linear_job(j, d.B, wd, d.H, (g == 0 ? d.seq_g[l] : d.seq_c[l]) + (size_t)t * d.B * wd, wd,
+                      part == 2 ? 1 : ((d.seq_init >> l) & 1));
         j.colmode = d.cell == 1 && tiled ? 1 : 0;  // (the tiled copies of LSTM matrices keep the gate-interleaved tile order)
         int n = 0;
         if (part != 2 && !no_w) j.seg[n++] = fseg(d.w + (size_t)(t + 1) * BE, d.E, l, g, d.H, d.E, wd);
@@ -385,10 +347,6 @@ struct DecoderPlan : PlanBase {
             j.seg[n++] = fseg(d.h[q] + (size_t)(t + 1) * BH, d.H, l, g, d.H + d.E + q * d.H, d.H, wd);
         }
         j.nseg = n;
-        j.M = d.B; j.N = wd; j.H = d.H; j.epi = SK_EPI_LINEAR;
-        float* sq = (g == 0 ? d.seq_g[l] : d.seq_c[l]) + (size_t)t * d.B * wd;
-        j.out = sq; j.ldo = wd;
-        j.accumulate = part == 2 ? 1 : ((d.seq_init >> l) & 1);  // caller data (feedback / speaker terms) already there
     }
 
     AttFwdArgs att_fwd_args(int t) const {
@@ -459,25 +417,14 @@ struct DecoderPlan : PlanBase {
     void rh_job(SkJob& x, int l, int t) const {
         const size_t BH = (size_t)d.B * d.H;
         const int H = d.H;
-        sk_job_init(x);
+        sk_bwd_rh_job(x, d.B, H, d.h[l] + t * BH, d.r[l] + t * BH, d.dG[l] + t * 2 * BH + H, 2 * H, d.dh[l] + t * BH);
         x.nseg = 1;
         x.seg[0] = rseg(d.dC[l] + t * BH, l, 1, 0, H);
-        x.M = d.B; x.N = H; x.H = H; x.epi = SK_EPI_BWD_RH;
-        x.e0 = d.h[l] + t * BH; x.lde0 = H;
-        x.e1 = d.r[l] + t * BH; x.lde1 = H;
-        x.out = d.dG[l] + t * 2 * BH + H; x.ldo = 2 * H;
-        x.o1 = d.dh[l] + t * BH; x.ldo1 = H;
     }
-    // One transposed product into a gradient buffer: out (+)= sg.A . sg.B^T, [M, N].
-    static void lin_job(SkJob& j, const SkSeg& sg, int M, int N, int H, float* out, int ldo, int accumulate) {
-        sk_job_init(j);
-        j.nseg = 1;
-        j.seg[0] = sg;
-        j.M = M; j.N = N; j.H = H; j.epi = SK_EPI_LINEAR; j.accumulate = accumulate;
-        j.out = out; j.ldo = ldo;
-    }
+    // The transposed products into gradient buffers, out (+)= sg.A . sg.B^T, are single-segment sk_linear_job()s.
     // ... in two K halves (bwd_ksplit): the second half's sums go to `second`, stored, or added when several jobs of a
-    // window share the destination (`added`; such a buffer is caller-zeroed)
+    // window share the destination (`added`; such a buffer is caller-zeroed).  Not an epilogue's wiring: a split LINEAR job
+    // reuses o1 / ldo1 for the second half's destination and ldo2 as the `added` flag (skinny.h, ksplit), so it stays here.
     static void ksplit2(SkJob& j, float* second, int ld, int added) {
         j.ksplit = 2;
         j.o1 = second; j.ldo1 = ld;
@@ -830,15 +777,15 @@ struct DecoderPlan : PlanBase {
                     float* dP = d.dG[l] + (size_t)t * 4 * BH;
                     const int first = nl;
                     SkJob& jh = jl[nl++];  // previous state of this layer
-                    lin_job(jh, rseg(dP, l, 0, 0, 4 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
+                    sk_linear_job(jh, rseg(dP, l, 0, 0, 4 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
                     if (bwd_ksplit) ksplit2(jh, d.dh_b[l] + t * BH, H, 0);
                     SkJob& jw = jl[nl++];  // attention context
-                    lin_job(jw, rseg(dP, l, 0, H, 4 * H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
+                    sk_linear_job(jw, rseg(dP, l, 0, H, 4 * H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
                     // dw_b[t + 1] collects every upper layer's share: added (caller-zeroed)
                     if (bwd_ksplit) ksplit2(jw, dctx(d.dw0_b, d.dw_b, l, t), E, l == 0 ? 0 : 1);
                     for (int p = 0; p < l; ++p) {  // lower layers' states of the same step
                         SkJob& j = jl[nl++];
-                        lin_job(j, rseg(dP, l, 0, H + E + p * H, 4 * H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
+                        sk_linear_job(j, rseg(dP, l, 0, H + E + p * H, 4 * H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
                         if (bwd_ksplit) ksplit2(j, d.dhup_b[p] + (t + 1) * BH, H, 1);  // (added: all layers above p)
                     }
                     if (bwd_fused)  // the products of a layer read what its chain's rows publish inside the launch
@@ -888,13 +835,13 @@ struct DecoderPlan : PlanBase {
                 const float* dG = d.dG[l] + t * 2 * BH;
                 const float* dC = d.dC[l] + t * BH;
                 // previous state of this layer: only the gate GEMM (rh part handled by X's epilogue)
-                lin_job(jy[ny++], rseg(dG, l, 0, 0, 2 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
+                sk_linear_job(jy[ny++], rseg(dG, l, 0, 0, 2 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
                 // attention context
-                lin_job(jy[ny++], rseg(dG, l, 0, H, 2 * H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
-                lin_job(jx[nx++], rseg(dC, l, 1, H, H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
+                sk_linear_job(jy[ny++], rseg(dG, l, 0, H, 2 * H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
+                sk_linear_job(jx[nx++], rseg(dC, l, 1, H, H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
                 for (int p = 0; p < l; ++p) {  // lower layers' states of the same step (separate buffer: no two jobs share a tile)
-                    lin_job(jy[ny++], rseg(dG, l, 0, H + E + p * H, 2 * H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
-                    lin_job(jx[nx++], rseg(dC, l, 1, H + E + p * H, H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
+                    sk_linear_job(jy[ny++], rseg(dG, l, 0, H + E + p * H, 2 * H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
+                    sk_linear_job(jx[nx++], rseg(dC, l, 1, H + E + p * H, H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
                 }
             }
             if (ga.nchain == 0) continue;
@@ -961,11 +908,11 @@ struct DecoderPlan : PlanBase {
                 if (s < 0 || s >= d.T) continue;
                 const float* dG = d.dG[l] + (size_t)s * 2 * BH;
                 for (int p = 0; p < l; ++p) {
-                    lin_job(js[ns++], rseg_k(dG, l, 0, H + E + p * H, 2 * H, 0, H), d.B, H, H, d.dhup_b[p] + (s + 1) * BH, H, 1);
-                    lin_job(js[ns++], rseg_k(dG, l, 0, H + E + p * H, 2 * H, H, H), d.B, H, H, d.dhup_c[p] + (s + 1) * BH, H, 1);
+                    sk_linear_job(js[ns++], rseg_k(dG, l, 0, H + E + p * H, 2 * H, 0, H), d.B, H, H, d.dhup_b[p] + (s + 1) * BH, H, 1);
+                    sk_linear_job(js[ns++], rseg_k(dG, l, 0, H + E + p * H, 2 * H, H, H), d.B, H, H, d.dhup_c[p] + (s + 1) * BH, H, 1);
                 }
-                lin_job(js[ns++], rseg_k(dG, l, 0, H, 2 * H, 0, H), d.B, E, H, d.dw_b + (size_t)(s + 1) * BE, E, 1);
-                lin_job(js[ns++], rseg_k(dG, l, 0, H, 2 * H, H, H), d.B, E, H, d.dw_c + (size_t)(s + 1) * BE, E, 1);
+                sk_linear_job(js[ns++], rseg_k(dG, l, 0, H, 2 * H, 0, H), d.B, E, H, d.dw_b + (size_t)(s + 1) * BE, E, 1);
+                sk_linear_job(js[ns++], rseg_k(dG, l, 0, H, 2 * H, H, H), d.B, E, H, d.dw_c + (size_t)(s + 1) * BE, E, 1);
             }
             // ---- X: d(r*h) (epilogue: dG_r, dh_prev += d(rh) * r) and the update-gate half of dG -> dh_prev (own buffer)
             // ---- Y: the reset-gate half of dG -> dh_prev, layer 0's context shares, the upper layers' dC shares downward
@@ -975,16 +922,16 @@ struct DecoderPlan : PlanBase {
                 const float* dG = d.dG[l] + (size_t)t * 2 * BH;
                 const float* dC = d.dC[l] + t * BH;
                 rh_job(jx[nx++], l, t);
-                lin_job(jx[nx++], rseg_k(dG, l, 0, 0, 2 * H, 0, H), d.B, H, H, d.dh_b[l] + t * BH, H, 0);
-                ymov[ny] = false; lin_job(jy[ny++], rseg_k(dG, l, 0, 0, 2 * H, H, H), d.B, H, H, d.dh[l] + t * BH, H, 1);
-                ymov[ny] = true;  lin_job(jy[ny++], rseg(dC, l, 1, H, H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
+                sk_linear_job(jx[nx++], rseg_k(dG, l, 0, 0, 2 * H, 0, H), d.B, H, H, d.dh_b[l] + t * BH, H, 0);
+                ymov[ny] = false; sk_linear_job(jy[ny++], rseg_k(dG, l, 0, 0, 2 * H, H, H), d.B, H, H, d.dh[l] + t * BH, H, 1);
+                ymov[ny] = true;  sk_linear_job(jy[ny++], rseg(dC, l, 1, H, H), d.B, E, H, dctx(d.dw0, d.dw, l, t), E, 1);
                 if (l == 0) {
-                    ymov[ny] = true;  lin_job(jy[ny++], rseg_k(dG, 0, 0, H, 2 * H, 0, H), d.B, E, H, d.dw0_b + (size_t)t * BE, E, 0);
-                    ymov[ny] = false; lin_job(jy[ny++], rseg_k(dG, 0, 0, H, 2 * H, H, H), d.B, E, H, d.dw0_c + (size_t)t * BE, E, 0);
+                    ymov[ny] = true;  sk_linear_job(jy[ny++], rseg_k(dG, 0, 0, H, 2 * H, 0, H), d.B, E, H, d.dw0_b + (size_t)t * BE, E, 0);
+                    ymov[ny] = false; sk_linear_job(jy[ny++], rseg_k(dG, 0, 0, H, 2 * H, H, H), d.B, E, H, d.dw0_c + (size_t)t * BE, E, 0);
                 }
                 for (int p = 0; p < l; ++p) {
                     ymov[ny] = true;
-                    lin_job(jy[ny++], rseg(dC, l, 1, H + E + p * H, H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
+                    sk_linear_job(jy[ny++], rseg(dC, l, 1, H + E + p * H, H), d.B, H, H, d.dhup[p] + (t + 1) * BH, H, 1);
                 }
             }
             while (ns > SK_MAXJOB) { ymov[ny] = true; jy[ny++] = js[--ns]; }  // (a tick old: movable further, too)
@@ -1038,18 +985,18 @@ struct DecoderPlan : PlanBase {
                     if (d.cell == 1) {
                         const LstmStateBwdChain c = lstm_chain(l, t);
                         PL_TRY(lstm_state_bwd_launch(c.dh, c.dh2, c.dc, c.gates, c.c_prev, c.c_new, c.dP, d.B, H, st));
-                        lin_job(jy[ny++], rseg(c.dP, l, 0, 0, 4 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
-                        if (l == 0) lin_job(jy[ny++], rseg(c.dP, 0, 0, H, 4 * H), d.B, E, H, d.dw0 + (size_t)t * BE, E, 1);
+                        sk_linear_job(jy[ny++], rseg(c.dP, l, 0, 0, 4 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
+                        if (l == 0) sk_linear_job(jy[ny++], rseg(c.dP, 0, 0, H, 4 * H), d.B, E, H, d.dw0 + (size_t)t * BE, E, 1);
                         continue;
                     }
                     ga.chain[ga.nchain++] = gru_chain(l, t);
                     rh_job(jx[nx++], l, t);
                     const float* dG = d.dG[l] + t * 2 * BH;
                     const float* dC = d.dC[l] + t * BH;
-                    lin_job(jy[ny++], rseg(dG, l, 0, 0, 2 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
+                    sk_linear_job(jy[ny++], rseg(dG, l, 0, 0, 2 * H), d.B, H, H, d.dh[l] + t * BH, H, 1);
                     if (l == 0) {  // layer 0's context share: the dG and dC products as the two segments of one job
                         SkJob& j = jy[ny++];
-                        lin_job(j, rseg(dG, 0, 0, H, 2 * H), d.B, E, H, d.dw0 + (size_t)t * BE, E, 1);
+                        sk_linear_job(j, rseg(dG, 0, 0, H, 2 * H), d.B, E, H, d.dw0 + (size_t)t * BE, E, 1);
                         j.seg[j.nseg++] = rseg(dC, 0, 1, H, H);
                     }
                 }

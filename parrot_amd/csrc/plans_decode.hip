@@ -942,23 +942,16 @@ struct SamplePlan : PlanBase {
             G.dst = tmp(g, 4);
             if (Wf) {
                 SkJob& j = jobs[nj++];
-                sk_job_init(j);
-                j.nseg = 1;
-                j.seg[0] = sk_seg(d.x + (size_t)t * d.B * d.ldx, d.ldx, Wf, wd, d.O, 0);
-                j.M = d.B; j.N = wd; j.H = d.H; j.epi = SK_EPI_LINEAR;
+                sk_linear_job(j, sk_seg(d.x + (size_t)t * d.B * d.ldx, d.ldx, Wf, wd, d.O, 0), d.B, wd, d.H, tmp(g, G.nsrc), wd);
                 j.bias = g == 0 ? d.bfg[l] : d.bfc[l];
-                j.out = tmp(g, G.nsrc); j.ldo = wd;
                 G.src[G.nsrc++] = j.out;
             }
             for (int q = 0; q < l; ++q) {
                 SkJob& j = jobs[nj++];
-                sk_job_init(j);
-                j.nseg = 1;
-                j.seg[0] = sk_seg(d.h[q] + nxt * BH, d.H, W + (size_t)(d.H + d.E + q * d.H) * wd, wd, d.H, 0);
-                j.M = d.B; j.N = wd; j.H = d.H; j.epi = SK_EPI_LINEAR;
+                sk_linear_job(j, sk_seg(d.h[q] + nxt * BH, d.H, W + (size_t)(d.H + d.E + q * d.H) * wd, wd, d.H, 0), d.B, wd, d.H,
+                              tmp(g, G.nsrc), wd);
                 const int pj = l * PARROT_MAX_LAYERS + q;
                 j.bias = g == 0 ? d.ln_bg[pj] : d.ln_bc[pj];
-                j.out = tmp(g, G.nsrc); j.ldo = wd;
                 G.src[G.nsrc++] = j.out;
             }
         }
@@ -979,21 +972,13 @@ struct SamplePlan : PlanBase {
         G.nsrc = 0; G.N = d.R; G.base = rtmp(d.L); G.dst = d.readout;
         for (int l = 0; l < d.L; ++l) {
             SkJob& j = jobs[l];
-            sk_job_init(j);
-            j.nseg = 1;
-            j.seg[0] = sk_seg(d.h[l] + nxt * BH, d.H, d.Wr + (size_t)l * d.H * d.R, d.R, d.H, 0);
-            j.M = d.B; j.N = d.R; j.H = d.H; j.epi = SK_EPI_LINEAR;
+            sk_linear_job(j, sk_seg(d.h[l] + nxt * BH, d.H, d.Wr + (size_t)l * d.H * d.R, d.R, d.H, 0), d.B, d.R, d.H, rtmp(l), d.R);
             j.bias = d.br_l[l];
-            j.out = rtmp(l); j.ldo = d.R;
             G.src[G.nsrc++] = j.out;
         }
         SkJob& b = jobs[d.L];
-        sk_job_init(b);
-        b.nseg = 1;
-        b.seg[0] = sk_seg(d.w + (t + 1) * BE, d.E, d.Wr + (size_t)d.L * d.H * d.R, d.R, d.E, 0);
-        b.M = d.B; b.N = d.R; b.H = d.H; b.epi = SK_EPI_LINEAR;
+        sk_linear_job(b, sk_seg(d.w + (t + 1) * BE, d.E, d.Wr + (size_t)d.L * d.H * d.R, d.R, d.E, 0), d.B, d.R, d.H, rtmp(d.L), d.R);
         b.bias = d.br; b.add = d.radd; b.ld_add = d.R;
-        b.out = rtmp(d.L); b.ldo = d.R;
         PL_TRY(launch_jobs(jobs, d.L + 1, st));
         return norm_sum_launch(&G, 1, d.B, PARROT_NORM_EPS, st);
     }
@@ -1009,38 +994,23 @@ struct SamplePlan : PlanBase {
                 const float* addc = d.seq_c[l];
                 if (d.layer_norm) PL_TRY(ln_layer_inputs(l, t, st, addg, addc));
                 if (d.cell == 1) {
-                    sk_job_init(j);
+                    sk_lstm_job(j, d.B, H, d.cwork[l] + cur * BH, d.cwork[l] + nxt * BH, d.gwork, d.h[l] + nxt * BH);
                     layer_segs(j, l, t, d.h[l] + cur * BH, d.Wg[l], 4 * H, d.Wfg[l]);
-                    j.M = d.B; j.N = 4 * H; j.H = H; j.epi = SK_EPI_LSTM;
                     j.bias = d.bg[l];
                     j.add = addg; j.ld_add = 4 * H;
-                    j.e1 = d.cwork[l] + cur * BH; j.lde1 = H;
-                    j.o1 = d.cwork[l] + nxt * BH; j.ldo1 = H;
-                    j.o2 = d.gwork; j.ldo2 = 4 * H;
-                    j.out = d.h[l] + nxt * BH; j.ldo = H;
                     PL_TRY(launch_jobs(&j, 1, st));
                 } else {
-                sk_job_init(j);
-                layer_segs(j, l, t, d.h[l] + cur * BH, d.Wg[l], 2 * H, d.Wfg[l]);
-                j.M = d.B; j.N = 2 * H; j.H = H; j.epi = SK_EPI_GRU_GATES;
-                j.bias = d.bg[l];
-                j.add = addg; j.ld_add = 2 * H;
-                j.e0 = d.h[l] + cur * BH; j.lde0 = H;
-                j.o1 = d.zwork; j.ldo1 = H;
-                j.o2 = d.rwork; j.ldo2 = H;
-                j.out = d.rhwork; j.ldo = H;
-                PL_TRY(launch_jobs(&j, 1, st));
+                    sk_gru_gates_job(j, d.B, H, d.h[l] + cur * BH, d.zwork, d.rwork, d.rhwork);
+                    layer_segs(j, l, t, d.h[l] + cur * BH, d.Wg[l], 2 * H, d.Wfg[l]);
+                    j.bias = d.bg[l];
+                    j.add = addg; j.ld_add = 2 * H;
+                    PL_TRY(launch_jobs(&j, 1, st));
 
-                sk_job_init(j);
-                layer_segs(j, l, t, d.rhwork, d.Wc[l], H, d.Wfc[l]);
-                j.M = d.B; j.N = H; j.H = H; j.epi = SK_EPI_GRU_CAND;
-                j.bias = d.bc[l];
-                j.add = addc; j.ld_add = H;
-                j.e0 = d.h[l] + cur * BH; j.lde0 = H;
-                j.e1 = d.zwork; j.lde1 = H;
-                j.o1 = nullptr;
-                j.out = d.h[l] + nxt * BH; j.ldo = H;
-                PL_TRY(launch_jobs(&j, 1, st));
+                    sk_gru_cand_job(j, d.B, H, d.h[l] + cur * BH, d.zwork, nullptr, d.h[l] + nxt * BH);
+                    layer_segs(j, l, t, d.rhwork, d.Wc[l], H, d.Wfc[l]);
+                    j.bias = d.bc[l];
+                    j.add = addc; j.ld_add = H;
+                    PL_TRY(launch_jobs(&j, 1, st));
                 }
 
                 if (l == 0) {
@@ -1063,15 +1033,13 @@ struct SamplePlan : PlanBase {
             if (d.layer_norm) {
                 PL_TRY(ln_readout(t, st));
             } else {
-                sk_job_init(j);
+                sk_linear_job(j, d.B, d.R, H, d.readout, d.R);
                 int n = 0;
                 for (int l = 0; l < d.L; ++l)
                     j.seg[n++] = sk_seg(d.h[l] + nxt * BH, H, d.Wr + (size_t)l * H * d.R, d.R, H, 0);
                 j.seg[n++] = sk_seg(d.w + (t + 1) * BE, d.E, d.Wr + (size_t)d.L * H * d.R, d.R, d.E, 0);
                 j.nseg = n;
-                j.M = d.B; j.N = d.R; j.H = H; j.epi = SK_EPI_LINEAR;
                 j.bias = d.br; j.add = d.radd; j.ld_add = d.R;
-                j.out = d.readout; j.ldo = d.R;
                 PL_TRY(launch_jobs(&j, 1, st));
             }
 
@@ -1085,12 +1053,8 @@ struct SamplePlan : PlanBase {
                 float* os[3] = {d.gmm_mu, d.gmm_sig, d.gmm_co};
                 const int ns[3] = {OK, OK, d.gmm_K};
                 for (int q = 0; q < 3; ++q) {
-                    sk_job_init(g3[q]);
-                    g3[q].nseg = 1;
-                    g3[q].seg[0] = sk_seg(d.readout, d.R, Ws[q], ns[q], d.R, 0);
-                    g3[q].M = d.B; g3[q].N = ns[q]; g3[q].H = H; g3[q].epi = SK_EPI_LINEAR;
+                    sk_linear_job(g3[q], sk_seg(d.readout, d.R, Ws[q], ns[q], d.R, 0), d.B, ns[q], H, os[q], ns[q]);
                     g3[q].bias = bs[q]; g3[q].add = as[q]; g3[q].ld_add = ns[q];
-                    g3[q].out = os[q]; g3[q].ldo = ns[q];
                 }
                 PL_TRY(launch_jobs(g3, 3, st));
                 PL_TRY(gmm_sample_launch(d.gmm_mu, d.gmm_sig, d.gmm_co, d.B, d.O, d.gmm_K, d.sampling_bias, d.eps,
@@ -1099,12 +1063,8 @@ struct SamplePlan : PlanBase {
                                          d.pi_out ? d.pi_out + (size_t)t * d.B * d.gmm_K : nullptr, st));
                 continue;
             }
-            sk_job_init(j);
-            j.nseg = 1;
-            j.seg[0] = sk_seg(d.readout, d.R, d.Wo, d.O, d.R, 0);
-            j.M = d.B; j.N = d.O; j.H = H; j.epi = SK_EPI_LINEAR;
+            sk_linear_job(j, sk_seg(d.readout, d.R, d.Wo, d.O, d.R, 0), d.B, d.O, H, d.x + (size_t)(t + 1) * d.B * d.ldx, d.ldx);
             j.bias = d.bo; j.add = d.oadd; j.ld_add = d.O;
-            j.out = d.x + (size_t)(t + 1) * d.B * d.ldx; j.ldo = d.ldx;
             PL_TRY(launch_jobs(&j, 1, st));
         }
         return 0;

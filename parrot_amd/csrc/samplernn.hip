@@ -460,100 +460,70 @@ struct SrPlan {
         if (utt) (void)hipFree(utt);
     }
 
-    int linear(const float* A, int lda, const float* W, int ldw, int K, int N, const float* bias, const float* add,
-               int ld_add, float* out, int ldo, int act, hipStream_t st, const float* A2 = nullptr, int lda2 = 0,
-               const float* W2 = nullptr, int K2 = 0, const float* Wt = nullptr) {
-        SkJob j;
-        sk_job_init(j);
-        j.nseg = 1;
-        j.seg[0] = Wt ? sk_seg(A, lda, Wt, (K >> 4) * 256, K, 2) : sk_seg(A, lda, W, ldw, K, 0);
-        if (A2) { j.seg[1] = sk_seg(A2, lda2, W2, ldw, K2, 0); j.nseg = 2; }
-        j.M = d.B; j.N = N; j.H = N; j.epi = SK_EPI_LINEAR; j.act = act;
-        j.bias = bias; j.add = add; j.ld_add = ld_add;
-        j.out = out; j.ldo = ldo;
+    int launch(const SkJob* jobs, int n, hipStream_t st, int force_tile = 0) {
         SkLaunch L;
-        SR_TRY(sk_make_launch(L, &j, 1));
+        SR_TRY(sk_make_launch(L, jobs, n));
+        L.force_tile = force_tile;
         return sk_launch(L, st);
+    }
+
+    // K segment A [B, K] . W[:, n0:] of a row-major [K, ldw] matrix, read from its fragment-major copy Wt where the plan
+    // has one ((K >> 4) * 256 floats per 16-column tile)
+    static SkSeg seg(const float* A, int K, const float* W, int ldw, const float* Wt, int n0 = 0) {
+        const int blk = (K >> 4) * 256;
+        return Wt ? sk_seg(A, K, Wt + (size_t)(n0 >> 4) * blk, blk, K, 2) : sk_seg(A, K, W + n0, ldw, K, 0);
+    }
+
+    // out [B, N] = act(A [B, K] . W [K, N] + bias)
+    int linear(const float* A, int K, const float* W, const float* Wt, int N, const float* bias, float* out, int act,
+               hipStream_t st) {
+        SkJob j;
+        sk_linear_job(j, seg(A, K, W, N, Wt), d.B, N, N, out, N);
+        j.act = act;
+        j.bias = bias;
+        return launch(&j, 1, st);
     }
 
     // GRU step of a tier (ops.py:356-393): gates = sigm(h.Wg + x.U[:, :2D] + b[:2D]); cand = tanh((r*h).Wc + x.U[:, 2D:] +
     // b[2D:]); in-place h.  The Input linear rides in the step GEMMs as a second K segment: two launches, not three.
+    // pre: x . U + bU arrives precomputed ([B, 3D]: gates | candidate) and only the recurrent product is left;
+    // gates_done: the previous frame's sample kernel has left z and r*h already.
     int gru(const float* x, const float* U, const float* bU, const float* Wg, const float* Wc, float* h, hipStream_t st,
-            const Tiled* t = nullptr, const float* pre = nullptr, bool gates_done = false) {
+            const Tiled& t, const float* pre = nullptr, bool gates_done = false) {
         const int D = d.D;
-        const int blk = (D >> 4) * 256;  // floats per column tile of a [D, *] fragment-major copy
-        const bool tl = t && t->U;
         SkJob j;
-        SkLaunch L;
-        sk_job_init(j);
-        if (pre) {  // x . U + bU arrives precomputed ([B, 3D]: gates | candidate): only the recurrent product is left
-            if (!gates_done) {  // (gates_done: the previous frame's sample kernel has left z and r*h already)
-                j.nseg = 1;
-                j.seg[0] = tl ? sk_seg(h, D, t->Wg, blk, D, 2) : sk_seg(h, D, Wg, 2 * D, D, 0);
-                j.M = d.B; j.N = 2 * D; j.H = D; j.epi = SK_EPI_GRU_GATES;
-                j.add = pre; j.ld_add = 3 * D;
-                j.e0 = h; j.lde0 = D;
-                j.o1 = d.z; j.ldo1 = D; j.o2 = d.r; j.ldo2 = D; j.out = d.rh; j.ldo = D;
-                SR_TRY(sk_make_launch(L, &j, 1));
-                SR_TRY(sk_launch(L, st));
-            }
-            sk_job_init(j);
-            j.nseg = 1;
-            j.seg[0] = tl ? sk_seg(d.rh, D, t->Wc, blk, D, 2) : sk_seg(d.rh, D, Wc, D, D, 0);
-            j.M = d.B; j.N = D; j.H = D; j.epi = SK_EPI_GRU_CAND;
-            j.add = pre + 2 * D; j.ld_add = 3 * D;
-            j.e0 = h; j.lde0 = D; j.e1 = d.z; j.lde1 = D;
-            j.o1 = nullptr; j.out = h; j.ldo = D;
-            SR_TRY(sk_make_launch(L, &j, 1));
-            return sk_launch(L, st);
+        if (!gates_done) {
+            sk_gru_gates_job(j, d.B, D, h, d.z, d.r, d.rh);
+            j.seg[j.nseg++] = seg(h, D, Wg, 2 * D, t.Wg);
+            if (pre) { j.add = pre; j.ld_add = 3 * D; }
+            else { j.seg[j.nseg++] = seg(x, D, U, 3 * D, t.U); j.bias = bU; }
+            SR_TRY(launch(&j, 1, st));
         }
-        j.nseg = 2;
-        j.seg[0] = tl ? sk_seg(h, D, t->Wg, blk, D, 2) : sk_seg(h, D, Wg, 2 * D, D, 0);
-        j.seg[1] = tl ? sk_seg(x, D, t->U, blk, D, 2) : sk_seg(x, D, U, 3 * D, D, 0);
-        j.M = d.B; j.N = 2 * D; j.H = D; j.epi = SK_EPI_GRU_GATES;
-        j.bias = bU;
-        j.e0 = h; j.lde0 = D;
-        j.o1 = d.z; j.ldo1 = D; j.o2 = d.r; j.ldo2 = D; j.out = d.rh; j.ldo = D;
-        SR_TRY(sk_make_launch(L, &j, 1));
-        SR_TRY(sk_launch(L, st));
-        sk_job_init(j);
-        j.nseg = 2;
-        j.seg[0] = tl ? sk_seg(d.rh, D, t->Wc, blk, D, 2) : sk_seg(d.rh, D, Wc, D, D, 0);
-        j.seg[1] = tl ? sk_seg(x, D, t->U + (size_t)(2 * D >> 4) * blk, blk, D, 2) : sk_seg(x, D, U + 2 * D, 3 * D, D, 0);
-        j.M = d.B; j.N = D; j.H = D; j.epi = SK_EPI_GRU_CAND;
-        j.bias = bU + 2 * D;
-        j.e0 = h; j.lde0 = D; j.e1 = d.z; j.lde1 = D;
-        j.o1 = nullptr; j.out = h; j.ldo = D;
-        SR_TRY(sk_make_launch(L, &j, 1));
-        return sk_launch(L, st);
+        sk_gru_cand_job(j, d.B, D, h, d.z, nullptr, h);
+        j.seg[j.nseg++] = seg(d.rh, D, Wc, D, t.Wc);
+        if (pre) { j.add = pre + 2 * D; j.ld_add = 3 * D; }
+        else { j.seg[j.nseg++] = seg(x, D, U, 3 * D, t.U, 2 * D); j.bias = bU + 2 * D; }
+        return launch(&j, 1, st);
     }
 
     // LSTM step of a tier layer (ops.py:505-553): pre = x . Win + b; gates = s . Wrec + pre (i | f | o | g);
     // c' = c*f + g*i; s' = tanh(c')*o.  s is the A operand of the step GEMM, so s' goes to a temporary first.
     int lstm_layer(const float* x, const float* Win, const float* b, const float* Wrec, float* s, float* c, hipStream_t st) {
         const int D = d.D;
-        SR_TRY(linear(x, D, Win, 4 * D, D, 4 * D, b, nullptr, 0, d.P, 4 * D, 0, st));
+        SR_TRY(linear(x, D, Win, nullptr, 4 * D, b, d.P, 0, st));
         SkJob j;
-        SkLaunch L;
-        sk_job_init(j);
-        j.nseg = 1;
-        j.seg[0] = sk_seg(s, D, Wrec, 4 * D, D, 0);
-        j.M = d.B; j.N = 4 * D; j.H = D; j.epi = SK_EPI_LSTM;
+        sk_lstm_job(j, d.B, D, c, c, d.gate_ws, d.layer_tmp);
+        j.seg[j.nseg++] = seg(s, D, Wrec, 4 * D, nullptr);
         j.add = d.P; j.ld_add = 4 * D;
-        j.e1 = c; j.lde1 = D;
-        j.o1 = c; j.ldo1 = D;
-        j.o2 = d.gate_ws; j.ldo2 = 4 * D;
-        j.out = d.layer_tmp; j.ldo = D;
-        SR_TRY(sk_make_launch(L, &j, 1));
-        SR_TRY(sk_launch(L, st));
+        SR_TRY(launch(&j, 1, st));
         return (int)hipMemcpyAsync(s, d.layer_tmp, (size_t)d.B * D * sizeof(float), hipMemcpyDeviceToDevice, st);
     }
 
     // One step of a tier's RNN stack on input x [B,D]; returns the top layer's output (state) pointer.
     int stack_step(bool big, const float* x, const float** top, hipStream_t st) {
         if (d.n_rnn == 0) {  // single GRU layer, original fields
-            if (big) SR_TRY(gru(x, d.big_U, d.big_bU, d.big_Wg, d.big_Wc, d.big_h, st, &t_big));
-            else SR_TRY(gru(x, d.frm_U, d.frm_bU, d.frm_Wg, d.frm_Wc, d.frm_h, st, &t_frm));
+            if (big) SR_TRY(gru(x, d.big_U, d.big_bU, d.big_Wg, d.big_Wc, d.big_h, st, t_big));
+            else SR_TRY(gru(x, d.frm_U, d.frm_bU, d.frm_Wg, d.frm_Wc, d.frm_h, st, t_frm));
             *top = big ? d.big_h : d.frm_h;
             return 0;
         }
@@ -561,7 +531,7 @@ struct SrPlan {
             const float* const* Lk = big ? d.big_L[k] : d.frm_L[k];
             float* hs = big ? d.big_hs[k] : d.frm_hs[k];
             if (d.lstm) SR_TRY(lstm_layer(x, Lk[0], Lk[1], Lk[2], hs, big ? d.big_cs[k] : d.frm_cs[k], st));
-            else SR_TRY(gru(x, Lk[0], Lk[1], Lk[2], Lk[3], hs, st));
+            else SR_TRY(gru(x, Lk[0], Lk[1], Lk[2], Lk[3], hs, st, Tiled()));
             x = hs;
         }
         *top = x;
@@ -609,12 +579,15 @@ struct SrPlan {
             const int n = B * (BFS > d.feat_dim ? BFS : d.feat_dim);
             hipLaunchKernelGGL(sr_prep_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, d.samples, len, d.tbase, 0, BFS,
                                half_q, d.xf_big, B, d.features, d.feat_cur, d.feat_dim, BFS);
-            SR_TRY(linear(d.xf_big, BFS, d.big_Win_frames, D, BFS, D, d.big_bin, nullptr, 0, d.gru_in, D, 0, st,
-                          d.feat_cur, d.feat_dim, d.big_Win_feats, d.feat_dim));
+            SkJob in;  // gru_in = [xf_big | feat_cur] . [Win_frames ; Win_feats] + bin
+            sk_linear_job(in, B, D, D, d.gru_in, D);
+            in.seg[in.nseg++] = seg(d.xf_big, BFS, d.big_Win_frames, D, nullptr);
+            in.seg[in.nseg++] = seg(d.feat_cur, d.feat_dim, d.big_Win_feats, D, nullptr);
+            in.bias = d.big_bin;
+            SR_TRY(launch(&in, 1, st));
             const float* top = nullptr;
             SR_TRY(stack_step(true, d.gru_in, &top, st));
-            SR_TRY(linear(top, D, d.big_Wout, nfr * D, D, nfr * D, d.big_bout, nullptr, 0, d.big_out, nfr * D, 0, st,
-                          nullptr, 0, nullptr, 0, t_big.Wout));
+            SR_TRY(linear(top, D, d.big_Wout, t_big.Wout, nfr * D, d.big_bout, d.big_out, 0, st));
             if (winu) {  // the big tier's share of every frame's pre-activations: pbig[(b, f)] = big_out[b, f*D : (f+1)*D] . U +
                          // (bin . U + bU), one step-kernel launch with one job per frame (the LDS-tiled GEMM would put the
                          // [B nfr, 3D] product on 48 workgroups of 128 x 128 x K: measured 75 us per period)
@@ -622,22 +595,15 @@ struct SrPlan {
                 // to 64 consecutive rows each (the step kernel's tallest tile), every job streaming U once -- 12 MB x
                 // B nfr / 64 per period where one job per frame (32 rows) read it nfr times
                 SkJob jobs[SK_MAXJOB];
-                const int blk = (D >> 4) * 256, rows = B * nfr, RJ = 64;
+                const int rows = B * nfr, RJ = 64;
                 for (int r0 = 0; r0 < rows; r0 += RJ * SK_MAXJOB) {
                     int nj = 0;
                     for (int r = r0; r < rows && nj < SK_MAXJOB; r += RJ, ++nj) {
-                        SkJob& j = jobs[nj];
-                        sk_job_init(j);
-                        j.nseg = 1;
-                        j.seg[0] = t_frm.U ? sk_seg(d.big_out + (size_t)r * D, D, t_frm.U, blk, D, 2)
-                                           : sk_seg(d.big_out + (size_t)r * D, D, d.frm_U, 3 * D, D, 0);
-                        j.M = rows - r < RJ ? rows - r : RJ; j.N = 3 * D; j.H = 3 * D; j.epi = SK_EPI_LINEAR;
-                        j.bias = pbias;
-                        j.out = pbig + (size_t)r * 3 * D; j.ldo = 3 * D;
+                        sk_linear_job(jobs[nj], seg(d.big_out + (size_t)r * D, D, d.frm_U, 3 * D, t_frm.U),
+                                      rows - r < RJ ? rows - r : RJ, 3 * D, 3 * D, pbig + (size_t)r * 3 * D, 3 * D);
+                        jobs[nj].bias = pbias;
                     }
-                    SkLaunch L;
-                    SR_TRY(sk_make_launch(L, jobs, nj));
-                    SR_TRY(sk_launch(L, st));
+                    SR_TRY(launch(jobs, nj, st));
                 }
             }
         }
@@ -658,7 +624,7 @@ struct SrPlan {
                     hipLaunchKernelGGL(sr_frame_in_kernel, dim3(ceil_div(3 * D, 256), B), dim3(256), 0, st, d.samples, len,
                                        d.tbase, toff, FS, half_q, winu, (const float*)nullptr, pbig + (size_t)f * 3 * D,
                                        nfr * 3 * D, pin, 3 * D, (const float*)gpre, (const float*)d.frm_h, d.z, d.rh, D);
-                SR_TRY(gru(nullptr, d.frm_U, d.frm_bU, d.frm_Wg, d.frm_Wc, d.frm_h, st, &t_frm, pin, persist));
+                SR_TRY(gru(nullptr, d.frm_U, d.frm_bU, d.frm_Wg, d.frm_Wc, d.frm_h, st, t_frm, pin, persist));
                 ftop = d.frm_h;
             } else {
                 if (!persist || f == 0)
@@ -670,26 +636,14 @@ struct SrPlan {
                 // the projection and, beside it, the recurrent product of the NEXT frame's gates (h' . Wg: it does not wait for
                 // the frame's samples); the sample kernel finishes those gates at its end
                 SkJob jobs[2];
-                const int blk = (D >> 4) * 256;
-                sk_job_init(jobs[0]);
-                jobs[0].nseg = 1;
-                jobs[0].seg[0] = t_frm.Wout ? sk_seg(ftop, D, t_frm.Wout, blk, D, 2) : sk_seg(ftop, D, Pout, FS * D, D, 0);
-                jobs[0].M = B; jobs[0].N = FS * D; jobs[0].H = FS * D; jobs[0].epi = SK_EPI_LINEAR;
-                jobs[0].bias = cb; jobs[0].out = d.frame_out; jobs[0].ldo = FS * D;
-                sk_job_init(jobs[1]);
-                jobs[1].nseg = 1;
-                jobs[1].seg[0] = t_frm.Wg ? sk_seg(ftop, D, t_frm.Wg, blk, D, 2) : sk_seg(ftop, D, d.frm_Wg, 2 * D, D, 0);
-                jobs[1].M = B; jobs[1].N = 2 * D; jobs[1].H = 2 * D; jobs[1].epi = SK_EPI_LINEAR;
-                jobs[1].out = gpre; jobs[1].ldo = 2 * D;
-                SkLaunch L;
-                SR_TRY(sk_make_launch(L, jobs, 2));
+                sk_linear_job(jobs[0], seg(ftop, D, Pout, FS * D, t_frm.Wout), B, FS * D, FS * D, d.frame_out, FS * D);
+                jobs[0].bias = cb;
+                sk_linear_job(jobs[1], seg(ftop, D, d.frm_Wg, 2 * D, t_frm.Wg), B, 2 * D, 2 * D, gpre, 2 * D);
                 // (FS + 2) D columns = 768 column tiles at D = 1024: 16-column workgroups are three per CU; the heuristic's
                 // 32-column ones (384) leave half the CUs with two streams and half with one (8.17 vs 8.07 us per sample)
-                L.force_tile = 21;
-                SR_TRY(sk_launch(L, st));
+                SR_TRY(launch(jobs, 2, st, 21));
             } else {
-                SR_TRY(linear(ftop, D, persist ? Pout : d.frm_Wout, FS * D, D, FS * D, persist ? cb : d.frm_bout, nullptr, 0,
-                              d.frame_out, FS * D, 0, st, nullptr, 0, nullptr, 0, t_frm.Wout));
+                SR_TRY(linear(ftop, D, persist ? Pout : d.frm_Wout, t_frm.Wout, FS * D, persist ? cb : d.frm_bout, d.frame_out, 0, st));
             }
             if (persist) {
                 // ---- all FS sample steps of this frame in one launch: XCD-local persistent-thread kernel
@@ -720,9 +674,9 @@ struct SrPlan {
                 const int to = toff + i;
                 hipLaunchKernelGGL(sr_embed_sum_kernel, dim3(ceil_div(D / 4, 256), B), dim3(256), 0, st, d.samples, len,
                                    d.tbase, to, FS, d.Q, D, d.emb_tbl, d.frame_out + (size_t)i * D, FS * D, d.o1);
-                SR_TRY(linear(d.o1, D, d.W2, D, D, D, d.b2, nullptr, 0, d.o2, D, SK_ACT_RELU, st));
-                SR_TRY(linear(d.o2, D, d.W3, D, D, D, d.b3, nullptr, 0, d.o3, D, SK_ACT_RELU, st));
-                SR_TRY(linear(d.o3, D, d.W4, d.Q, D, d.Q, d.b4, nullptr, 0, d.logits, d.Q, 0, st));
+                SR_TRY(linear(d.o1, D, d.W2, nullptr, D, d.b2, d.o2, SK_ACT_RELU, st));
+                SR_TRY(linear(d.o2, D, d.W3, nullptr, D, d.b3, d.o3, SK_ACT_RELU, st));
+                SR_TRY(linear(d.o3, D, d.W4, nullptr, d.Q, d.b4, d.logits, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
                                    d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode,
                                    d.top_k, top_p);
@@ -760,8 +714,7 @@ struct SrPlan {
                 if (e != hipSuccess) return (int)e;
             }
             if (persist && winu)  // h0 . Wg: the gates' recurrent product of the very first frame (see period())
-                SR_TRY(linear(d.frm_h, d.D, d.frm_Wg, 2 * d.D, d.D, 2 * d.D, nullptr, nullptr, 0, gpre, 2 * d.D, 0, st, nullptr, 0,
-                              nullptr, 0, t_frm.Wg));
+                SR_TRY(linear(d.frm_h, d.D, d.frm_Wg, t_frm.Wg, 2 * d.D, nullptr, gpre, 0, st));
             if (persist && winu && d.starts)
                 SR_TRY((int)hipMemcpyAsync(gpre0, gpre, (size_t)d.B * 2 * d.D * sizeof(float), hipMemcpyDeviceToDevice, st));
         }

@@ -115,6 +115,52 @@ int sk_tile_weights_bf16_launch(const float* W, int rows, int cols, int ld, void
                                 hipStream_t stream);
 void sk_job_init(SkJob& j);
 void sk_finalize_job(SkJob& j);  // computes `aligned`
+
+// Job builders: the one place that knows which fields an epilogue reads and writes (SkEpi above).  Each begins a job --
+// zeroed as by sk_job_init, then shape, epilogue and the epilogue's buffers; every buffer of a cell job is [M, H] with
+// leading dimension H (the LSTM's saved activations [M, 4H]) -- and the caller adds what is its own: the K segments
+// (seg / nseg), bias, add / ld_add, mask, act, colmode, ksplit, wait_*.
+// out (+)= act(acc + bias + add), [M, N].  H only matters with colmode = 1.
+static inline void sk_linear_job(SkJob& j, int M, int N, int H, float* out, int ldo, int accumulate = 0) {
+    sk_job_init(j);
+    j.M = M; j.N = N; j.H = H; j.epi = SK_EPI_LINEAR; j.accumulate = accumulate;
+    j.out = out; j.ldo = ldo;
+}
+// ... over one K segment
+static inline void sk_linear_job(SkJob& j, const SkSeg& sg, int M, int N, int H, float* out, int ldo, int accumulate = 0) {
+    sk_linear_job(j, M, N, H, out, ldo, accumulate);
+    j.nseg = 1;
+    j.seg[0] = sg;
+}
+// pre = [z | r] columns: z, r = sigmoid(pre), rh = r * h_prev
+static inline void sk_gru_gates_job(SkJob& j, int M, int H, const float* h_prev, float* z, float* r, float* rh) {
+    sk_job_init(j);
+    j.M = M; j.N = 2 * H; j.H = H; j.epi = SK_EPI_GRU_GATES;
+    j.e0 = h_prev; j.lde0 = H;
+    j.o1 = z; j.ldo1 = H; j.o2 = r; j.ldo2 = H; j.out = rh; j.ldo = H;
+}
+// c = tanh(pre) -> c_out (or null: not kept), h_next = z * c + (1 - z) * h_prev
+static inline void sk_gru_cand_job(SkJob& j, int M, int H, const float* h_prev, const float* z, float* c_out, float* h_next) {
+    sk_job_init(j);
+    j.M = M; j.N = H; j.H = H; j.epi = SK_EPI_GRU_CAND;
+    j.e0 = h_prev; j.lde0 = H; j.e1 = z; j.lde1 = H;
+    j.o1 = c_out; j.ldo1 = H; j.out = h_next; j.ldo = H;
+}
+// gate-interleaved columns of [M, 4H]: activations -> gates_out (or null), c_next = c_prev * f + g * i, s_next = tanh(c_next) * o
+static inline void sk_lstm_job(SkJob& j, int M, int H, const float* c_prev, float* c_next, float* gates_out, float* s_next) {
+    sk_job_init(j);
+    j.M = M; j.N = 4 * H; j.H = H; j.epi = SK_EPI_LSTM;
+    j.e1 = c_prev; j.lde1 = H;
+    j.o1 = c_next; j.ldo1 = H; j.o2 = gates_out; j.ldo2 = 4 * H; j.out = s_next; j.ldo = H;
+}
+// acc = d(r * h_prev): dG_r = acc * h_prev * r (1 - r) (leading dimension ldg: the r half of a [M, 2H] buffer),
+// dh_prev += acc * r
+static inline void sk_bwd_rh_job(SkJob& j, int M, int H, const float* h_prev, const float* r, float* dG_r, int ldg, float* dh_prev) {
+    sk_job_init(j);
+    j.M = M; j.N = H; j.H = H; j.epi = SK_EPI_BWD_RH;
+    j.e0 = h_prev; j.lde0 = H; j.e1 = r; j.lde1 = H;
+    j.out = dG_r; j.ldo = ldg; j.o1 = dh_prev; j.ldo1 = H;
+}
 int sk_make_launch(SkLaunch& L, const SkJob* jobs, int njobs);
 
 // bf16 launches: would the wide step kernel (wk_kernel) take jobs of M rows, ncols columns in total, K segments of H / E?
