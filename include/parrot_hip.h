@@ -1010,6 +1010,23 @@ int samplernn_generate_set_top_p(void* plan, float top_p);
  * samplernn_generate_set_utterance_draws, and refused once the plan has run (PARROT_ERR_BADARG for either, and for a null
  * plan or pointer; no device call); PARROT_ERR_UNSUPPORTED when Q > 256.  Without it every utterance takes the plan's top_p. */
 int samplernn_generate_set_utterance_top_p(void* plan, const float* utt_top_p);
+/* Forced samples (teacher forcing, priming).  forced [B][BFS * T] (int): device memory, owned by the caller for the plan's
+ * life, indexed exactly like `samples` -- the same ring and the same buffer index t; a run in segments restages it per
+ * segment, as it restages `features`.  Where forced[b][t] lies in 0 .. Q-1 the sample step at buffer index t of stream b
+ * computes its logits as always and then takes forced[b][t] as the sample instead of its pick: that code is written to
+ * `samples` and enters the following steps, the frame and big-frame tiers and a resumed segment like any sample.  Any other
+ * value (-1 is the documented one) means that the step picks freely; an out-of-range value never indexes a table.  Slot 0
+ * of a run (the prefix slot) is never read.  The draw counter stays the sample's index: a forced step consumes no uniform,
+ * a free step after a prompt uses the uniform of its own index, so forcing a run's own earlier output reproduces that run
+ * bit for bit.  Independent of every draw setting and of samplernn_generate_set_log_probs.  PARROT_ERR_BADARG for a null plan
+ * or pointer and for a plan that has run (the period graphs hold the pointer by value); no device call. */
+int samplernn_generate_set_forced(void* plan, const int* forced);
+/* Per-sample log-probabilities.  logp [B][BFS * T] (float): device memory, owned and indexed like `forced`.  Every sample
+ * step writes logp[b][t] = logits[s] - max - log(sum_q exp(logits[q] - max)), s = the code the step wrote to `samples`
+ * (forced or picked): the natural logarithm, in float32, of the MODEL's probability of s -- temperature 1, no truncation,
+ * whatever the step draws with; the quantity the training cost averages.  Slot 0 is not written.  PARROT_ERR_BADARG for a
+ * null plan or pointer and for a plan that has run; no device call. */
+int samplernn_generate_set_log_probs(void* plan, float* logp);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

@@ -267,6 +267,8 @@ SIGNATURES = {
     "samplernn_generate_set_utterance_top_k": (_i, [_vp, _vp]),
     "samplernn_generate_set_top_p": (_i, [_vp, C.c_float]),
     "samplernn_generate_set_utterance_top_p": (_i, [_vp, _vp]),
+    "samplernn_generate_set_forced": (_i, [_vp, _vp]),
+    "samplernn_generate_set_log_probs": (_i, [_vp, _vp]),
     "samplernn_persist_floats": (C.c_longlong, [C.POINTER(SampleRnnGenDesc)]),
     "samplernn_generate_is_persistent": (_i, [_vp]),
     "samplernn_generate_persist_groups": (_i, [_vp]),

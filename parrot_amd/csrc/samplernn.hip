@@ -63,16 +63,30 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 // temperature-scaled multinomial draw from a counter-based generator when temperature > 0 -- among all Q codes, or among
 // the top_k most likely ones (SampleRnnGenDesc::top_k: terms 0.0f outside the kept set, same sums, same uniform), or among
 // the nucleus of those (samplernn_generate_set_top_p: the shortest prefix of the same order with top_p of their mass).
+// forced (samplernn_generate_set_forced, or null): where forced[b][t] is a code in 0 .. Q-1 it is the sample, whatever was
+// picked; any other value leaves the pick.  logp (samplernn_generate_set_log_probs, or null): logp[b][t] = the natural
+// logarithm of softmax(logits)[sample] at temperature 1, without truncation.  Both through emit(), which every branch
+// ends in; both for any Q.
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
                                                       unsigned long long seed, const unsigned long long* __restrict__ origin,
                                                       const SrUttDraw* __restrict__ utt, int draw_mode, int top_k,
-                                                      float top_p) {
+                                                      float top_p, const int* __restrict__ forced, float* __restrict__ logp) {
     __shared__ float sv[256];
     __shared__ int si[256];
+    __shared__ float se[256];
     const int t = tbase[0] + toff;
     const int b = blockIdx.x, tid = threadIdx.x;
     const float* lg = logits + (size_t)b * Q;
+    // (a value that is no code never indexes anything: it means "free")
+    const int fv = forced ? forced[(size_t)b * len + t] : -1;
+    const bool is_forced = (unsigned)fv < (unsigned)Q;
+    float lse = 0.f;  // log sum_q exp(logits[q] - max), with logp only
+    auto emit = [&](int pick) {
+        const int s = is_forced ? fv : pick;
+        samples[(size_t)b * len + t] = s;
+        if (logp) logp[(size_t)b * len + t] = lg[s] - sv[0] - lse;
+    };
     // key = what the draw's counter is hashed with: the plan's seed and the stream, or (per-utterance entries, a uniform
     // branch) the utterance's seed alone, with its own temperature and its counter taken back by the run index of its prefix
     unsigned long long key = seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1)), off = 0;
@@ -101,8 +115,20 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
         }
         __syncthreads();
     }
+    if (logp) {  // (a uniform branch) the block's fixed tree over the threads' partial sums
+        const float mx = sv[0];
+        float e = 0.f;
+        for (int q = tid; q < Q; q += 256) e += expf(lg[q] - mx);
+        se[tid] = e;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) se[tid] += se[tid + s];
+            __syncthreads();
+        }
+        lse = logf(se[0]);
+    }
     if (temperature <= 0.f) {
-        if (tid == 0) samples[(size_t)b * len + t] = si[0];
+        if (tid == 0) emit(si[0]);
         return;
     }
     if (draw_mode == 1) {
@@ -131,7 +157,7 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
             } else {
                 pick = srp_scan_draw([&](int j) { return expf((lg[n * tid + j] - mx) / temperature); }, n, tid, u01);
             }
-            if (tid == 0) samples[(size_t)b * len + t] = pick;
+            if (tid == 0) emit(pick);
         }
         return;
     }
@@ -169,7 +195,7 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
                     c += si[q] ? expf((lg[q] - mx) / temperature) : 0.f;
                     if (u < c) { pick = q; break; }
                 }
-                samples[(size_t)b * len + t] = pick;
+                emit(pick);
             }
         }
         return;
@@ -187,7 +213,7 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
             c += expf((lg[q] - mx) / temperature);
             if (u < c) { pick = q; break; }
         }
-        samples[(size_t)b * len + t] = pick;
+        emit(pick);
     }
 }
 
@@ -375,6 +401,10 @@ struct SrPlan {
     // the caller's [T][B] values (null: the plan's for all)
     float top_p = 0.f;
     const float* utt_top_p = nullptr;
+    // samplernn_generate_set_forced / _set_log_probs: the caller's [B][BFS * T] arrays, indexed like d.samples (null: off).
+    // Indexed by buffer index, so a resumed segment needs no state of theirs: the host stages them per segment, like features.
+    const int* forced = nullptr;
+    float* logp = nullptr;
     int make_origin() {
         if (hipMalloc(&origin, sizeof(unsigned long long)) != hipSuccess) { origin = nullptr; return 1; }
         return (int)hipMemset(origin, 0, sizeof(unsigned long long));
@@ -654,6 +684,7 @@ struct SrPlan {
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
                 sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode; sa.top_k = srp_trunc_word(d.top_k, top_p, d.Q); sa.top_p = top_p;
+                sa.forced = forced; sa.logp = logp;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -679,7 +710,7 @@ struct SrPlan {
                 SR_TRY(linear(d.o3, D, d.W4, nullptr, d.Q, d.b4, d.logits, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
                                    d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode,
-                                   d.top_k, top_p);
+                                   d.top_k, top_p, forced, logp);
             }
         }
         hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
@@ -867,6 +898,24 @@ int samplernn_generate_set_utterance_top_p(void* plan, const float* utt_top_p) {
     if (p->has_run) return PARROT_ERR_BADARG;
     if (p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
     p->utt_top_p = utt_top_p;
+    return 0;
+}
+
+// Forced samples and per-sample log-probabilities.  (No HIP call: the pointers are handed to the sample kernels of both
+// paths by the launches of the first run.)
+int samplernn_generate_set_forced(void* plan, const int* forced) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !forced) return PARROT_ERR_BADARG;
+    if (p->has_run) return PARROT_ERR_BADARG;  // the period graphs hold the pointers by value
+    p->forced = forced;
+    return 0;
+}
+
+int samplernn_generate_set_log_probs(void* plan, float* logp) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !logp) return PARROT_ERR_BADARG;
+    if (p->has_run) return PARROT_ERR_BADARG;
+    p->logp = logp;
     return 0;
 }
 

@@ -70,6 +70,9 @@ struct SrpShared {
     int ulast[SRP_ROWS];  // the highest kept code of a truncated sequential draw (srp_kernel's pick)
     int upad;
     unsigned long long useed[SRP_ROWS], uoff[SRP_ROWS];
+    // forced codes of the launch's steps for the group's rows (SrpArgs::forced; unused without), -1 = the step picks freely.
+    // Behind everything else: the offsets of the fields above are the ones they had.
+    int forced[SRP_ROWS][SRP_MAXHIST];
 };
 static_assert(sizeof(SrpShared) % 8 == 0, "SrpShared holds 64-bit words");
 

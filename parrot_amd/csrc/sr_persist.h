@@ -58,6 +58,14 @@ struct SrpArgs {
     // samplernn_generate_set_top_p: a draw at temperature > 0 is taken among the nucleus of the codes top_k left (sr_common.h,
     // srp_topp_keep); active strictly between 0 and 1 (top_k then carries SRP_NUCLEUS).  With utt: the entry's top_p.
     float top_p;
+    // samplernn_generate_set_forced: [B][len] like samples, or null.  Where forced[b][t] is a code in 0 .. Q-1 the step at
+    // buffer index t of stream b computes its logits and its pick as always and then takes that code as the sample -- into
+    // samples, the history of the following steps, the carry and the next frame's input; any other value (-1): the pick.
+    // A forced step consumes no uniform: the draw counter is the sample's index.
+    const int* forced;
+    // samplernn_generate_set_log_probs: [B][len] like samples, or null.  Every step writes the natural logarithm of the
+    // model's probability (temperature 1, no truncation) of the sample it wrote: logits[s] - max - log(sum exp(logits - max)).
+    float* logp;
 };
 
 constexpr int SRP_NUCLEUS = 1 << 16;  // in SrpArgs::top_k: the plan's top_p is active

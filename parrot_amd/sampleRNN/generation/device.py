@@ -8,7 +8,7 @@ from ... import _lib
 from ... import ops as hip
 from .. import lib
 from ..lib import ops as lops
-from .inputs import _seed_image, config, draw_mode_code, top_k_array, top_k_code, top_p_array, top_p_code
+from .inputs import FREE, _seed_image, config, draw_mode_code, forced_array, top_k_array, top_k_code, top_p_array, top_p_code
 
 
 def device_loop_guard(draw_mode, top_k=0, top_p=0.0):
@@ -26,8 +26,11 @@ def device_loop_guard(draw_mode, top_k=0, top_p=0.0):
 class DeviceGenerator:
     """Device-resident generation loop (samplernn_generate_*, include/parrot_hip.h)."""
 
+    forcing = False    # (a plan takes forced samples / returns log-probabilities only when it was built that way)
+    log_probs = False
+
     def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
-                 draw_mode='sequential', top_k=0, top_p=0.0):
+                 draw_mode='sequential', top_k=0, top_p=0.0, forcing=False, log_probs=False):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
         three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
 
@@ -57,7 +60,20 @@ class DeviceGenerator:
         their mass; never empty, ties at the cut-off to the lower index, every other code's term 0 in the same sums: a draw
         with top_p = p is a draw with top_k = the length of that prefix.  0 (default) or >= 1: no nucleus, the samples of
         every earlier version.  A very small p picks the argmax.  With utterance_draws=True it is what an utterance draws
-        with unless generate(..., top_ps=) names its own.  Negative or NaN: ValueError."""
+        with unless generate(..., top_ps=) names its own.  Negative or NaN: ValueError.
+
+        forcing=True: the plan takes forced samples (samplernn_generate_set_forced): generate(..., forced=) names, per
+        stream and sample, a code the sample step takes instead of its pick, or -1 where it picks freely.  The step computes
+        its logits either way, and the forced code is what every later step, both tiers above and a resumed segment see.
+        The draw counter stays the sample's index (a forced step consumes no uniform), so forcing a run's own earlier
+        output reproduces that run bit for bit, in every draw setting.  Priming, teacher forcing.
+
+        log_probs=True: generate returns (samples, logp), logp [B, 80 T] float32 (samplernn_generate_set_log_probs): the
+        natural logarithm of the MODEL's probability of each sample it wrote, forced or picked -- temperature 1, no
+        truncation, whatever the step draws with; the quantity compute_cost averages.  The prefix slot holds zeros.
+
+        Both are independent of each other and of every other setting; a plan built with neither runs the kernels it ran
+        before they existed."""
         self.draw_mode = draw_mode
         mode = device_loop_guard(draw_mode, top_k, top_p)
         self.top_k = top_k_code(top_k)
@@ -65,6 +81,7 @@ class DeviceGenerator:
         self.B, self.T = batch, n_frames
         self.packed = bool(packed)
         self.utterance_draws = bool(utterance_draws)
+        self.forcing, self.log_probs = bool(forcing), bool(log_probs)
         dev = lib.device()
         f = dict(device=dev, dtype=torch.float32)
         tt = config()
@@ -159,6 +176,12 @@ class DeviceGenerator:
         # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
         self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
         self._has_run = False
+        if self.forcing:  # [B, 80 T] like samples; -1 = free
+            self.ws['forced'] = torch.full((batch, BFS * n_frames), FREE, device=dev, dtype=torch.int32)
+            _lib.call('samplernn_generate_set_forced', self.plan, self.ws['forced'].data_ptr())
+        if self.log_probs:
+            self.ws['logp'] = torch.zeros(batch, BFS * n_frames, **f)
+            _lib.call('samplernn_generate_set_log_probs', self.plan, self.ws['logp'].data_ptr())
         if self.utterance_draws:
             # [T, B] like starts (ring rows): row f = what an utterance that begins at big frame f draws with; utt_seed is the
             # two's-complement image of the unsigned 64-bit seed
@@ -177,7 +200,7 @@ class DeviceGenerator:
         _lib.call('samplernn_generate_set_utterance_top_p', self.plan, self.ws['utt_top_p'].data_ptr())
 
     def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None,
-                 top_ps=None):
+                 top_ps=None, forced=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
         frame f, whose Q/2 prefix is slot f - 1.
@@ -201,14 +224,30 @@ class DeviceGenerator:
 
         top_ps (optional, likewise): numbers of the same shape as seeds, or one number for all -- the top_p each utterance
         draws with (0 or >= 1: no nucleus); omitted, every utterance takes the plan's top_p.  A negative value, a NaN or
-        another shape: ValueError."""
+        another shape: ValueError.
+
+        forced (plans built with forcing=True only, and required there): integers [B, 80 rows], aligned with the rows of
+        `features` of this call -- [B, 80 T] for a run in one piece (its first 80 columns, the prefix slot, are ignored),
+        [B, 80 k] for a segment that resumes.  A code in 0 .. Q_LEVELS-1 is the sample of that step; -1: the step picks.
+        Another shape, a non-integer dtype or any other value: ValueError, before anything is staged.
+
+        A plan built with log_probs=True returns (samples, logp): logp float32, sliced like samples and, like them, a
+        copy when the run is in segments."""
         segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures, top_ks, top_ps)
+        if (forced is not None) != self.forcing:
+            raise ValueError("forced must be given exactly when the plan was built with forcing=True")
+        if forced is not None:  # (its values and shape before anything is staged on the device)
+            forced = forced_array(forced, (self.B, config().BIG_FRAME_SIZE * rows))
         self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks, top_ps)
-        self._launch(segment, resume, k)
-        if not segment:
-            return self.ws['samples']
         BFS = config().BIG_FRAME_SIZE
-        return self.ws['samples'][:, BFS * first:BFS * (k + 1)].clone()
+        if forced is not None:
+            fo = self.ws['forced']
+            fo[:, BFS * first:BFS * (first + rows)].copy_(torch.from_numpy(forced).to(fo.device))
+        self._launch(segment, resume, k)
+        cut = (lambda x: x) if not segment else (lambda x: x[:, BFS * first:BFS * (k + 1)].clone())
+        if self.log_probs:
+            return cut(self.ws['samples']), cut(self.ws['logp'])
+        return cut(self.ws['samples'])
 
     def _resolve(self, starts, resume, n_frames, seeds, temperatures, top_ks=None, top_ps=None):
         """Which arguments this plan takes in which kind of run -> (segment, resume, k, rows, first): a run in segments or

@@ -229,6 +229,63 @@ def build_packed_top_p(top_ps, stream, first_slot, T, n_streams):
     return utt_top_p
 
 
+FREE = -1  # in a forced array: the step picks freely
+
+
+def forced_array(forced, shape):
+    """Forced samples as the int32 array of `shape` a plan is fed (samplernn_generate_set_forced): ValueError on another
+    shape, a non-integer array or a value that is neither -1 (free) nor a code in 0 .. Q_LEVELS-1 (no device call)."""
+    a = numpy.asarray(forced)
+    if a.dtype.kind not in 'iu' or a.shape != tuple(shape):
+        raise ValueError("forced must be integers of shape %s, got %s of %s" % (list(shape), a.dtype, list(a.shape)))
+    Q = config().Q_LEVELS
+    if a.size and (a.min() < FREE or a.max() >= Q):
+        raise ValueError("forced values must be -1 (free) or codes in 0 .. %d" % (Q - 1))
+    return a.astype(numpy.int32)
+
+
+def _per_utterance_prompts(prompts, lengths):
+    """prompts: per utterance None or an integer array of at most 80 * (n_i - 1) codes in 0 .. Q_LEVELS-1; None = no prompt
+    for anybody.  Returns one int32 array per utterance (empty: no prompt).  ValueError otherwise (no device call)."""
+    tt = config()
+    n = len(lengths)
+    prompts = [None] * n if prompts is None else list(prompts)
+    if len(prompts) != n:
+        raise ValueError("%d utterances, but %d prompts" % (n, len(prompts)))
+    out = []
+    for p, frames in zip(prompts, lengths):
+        a = numpy.zeros(0, dtype=numpy.int32) if p is None else numpy.asarray(p)
+        if a.ndim != 1 or (a.size and a.dtype.kind not in 'iu'):
+            raise ValueError("a prompt is a one-dimensional integer array, got %s of %s" % (a.dtype, list(a.shape)))
+        if a.size > tt.BIG_FRAME_SIZE * (int(frames) - 1):
+            raise ValueError("a prompt of %d codes is longer than the %d samples its utterance of %d frames generates"
+                             % (a.size, tt.BIG_FRAME_SIZE * (int(frames) - 1), frames))
+        if a.size and (a.min() < 0 or a.max() >= tt.Q_LEVELS):
+            raise ValueError("prompt codes must lie in 0 .. %d" % (tt.Q_LEVELS - 1))
+        out.append(a.astype(numpy.int32))
+    return out
+
+
+def build_packed_prompts(prompts, lengths, stream, first_slot, T, n_streams):
+    """forced [n_streams, 80 T] int32 of a packing, the counterpart of build_packed_inputs on the sample grid: code j of
+    utterance i's prompt at sample 80 + j of its own buffer, i.e. column 80 (first_slot[i] + 1) + j of stream[i]; -1 (free)
+    everywhere else -- prefix slots and idle slots included.  unpack_samples cuts it back into the utterances' pieces."""
+    BFS = config().BIG_FRAME_SIZE
+    forced = numpy.full((n_streams, BFS * T), FREE, dtype=numpy.int32)
+    for p, n, b, s in zip(_per_utterance_prompts(prompts, lengths), lengths, stream, first_slot):
+        if not (0 <= b < n_streams and 0 <= s and s + n <= T):
+            raise ValueError("utterance of %d frames does not fit at slot %d of stream %d" % (n, s, b))
+        forced[b, BFS * (s + 1):BFS * (s + 1) + p.size] = p
+    return forced
+
+
+def unpack_log_probs(logp, lengths, stream, first_slot):
+    """The utterances' pieces of a packed run's log-probabilities [B, 80 T]: per utterance the float32 values of its samples
+    80 .. 80 n_i - 1 (the prefix slot has none)."""
+    BFS = config().BIG_FRAME_SIZE
+    return [numpy.array(logp[b, BFS * (s + 1):BFS * (s + n)], dtype='float32') for n, b, s in zip(lengths, stream, first_slot)]
+
+
 def unpack_samples(samples, lengths, stream, first_slot):
     """The utterances' pieces of a packed run's samples [B, 80 T].  (The prefix of a one-frame utterance in the last slot
     of the plan has no period behind it that would write it: it is Q/2 by definition.)"""

@@ -3,13 +3,15 @@ segments on a ring (generate_stream) and continuous admission on a plan that nev
 import numpy
 
 from .device import DeviceGenerator, device_loop_guard
-from .inputs import (_per_utterance, _per_utterance_top_k, _per_utterance_top_p, build_packed_draws, build_packed_inputs,
-                     build_packed_top_k, build_packed_top_p, config, pack_utterances, schedule_segment, start_row,
-                     top_k_code, top_p_code, u64, unpack_samples)
+from .inputs import (FREE, _per_utterance, _per_utterance_prompts, _per_utterance_top_k, _per_utterance_top_p,
+                     build_packed_draws, build_packed_inputs, build_packed_prompts, build_packed_top_k, build_packed_top_p,
+                     config, pack_utterances, schedule_segment, start_row, top_k_code, top_p_code, u64, unpack_log_probs,
+                     unpack_samples)
 
 
 def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_graph=True, seeds=None,
-                    temperatures=None, draw_mode='sequential', top_k=0, top_ks=None, top_p=0.0, top_ps=None):
+                    temperatures=None, draw_mode='sequential', top_k=0, top_ks=None, top_p=0.0, top_ps=None, prompts=None,
+                    log_probs=False):
     """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
     utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
     n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
@@ -31,9 +33,20 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
     top_ks = one top_k per utterance (needs `seeds`; default: `top_k` for all).
 
     top_p: those draws are taken among the nucleus of the codes top_k left (0 or >= 1: no nucleus; see DeviceGenerator).
-    top_ps = one top_p per utterance (needs `seeds`; default: `top_p` for all)."""
+    top_ps = one top_p per utterance (needs `seeds`; default: `top_p` for all).
+
+    prompts = per utterance None or an integer array of at most 80 * (n_i - 1) codes in 0 .. Q_LEVELS-1: code j is sample
+    80 + j of that utterance's own buffer, whatever the model would have picked there (DeviceGenerator(forcing=True)); the
+    utterance goes on freely behind its prompt, drawing with the uniforms of its own sample indices.  A longer prompt, a
+    non-integer array or another value: ValueError, before a plan is created.
+
+    log_probs=True: returns (samples_list, logp_list), logp_list[i] = float32 [80 * (n_i - 1)], the natural logarithm of the
+    model's probability (temperature 1, no truncation) of samples 80 .. of utterance i (DeviceGenerator(log_probs=True))."""
     device_loop_guard(draw_mode, top_k, top_p)
     utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
+    lengths = [u.shape[0] for u in utterances]
+    if prompts is not None:  # (before a plan is created)
+        prompts = _per_utterance_prompts(prompts, lengths)
     if seeds is None and temperatures is not None:
         raise ValueError("temperatures per utterance need seeds per utterance")
     if seeds is None and top_ks is not None:
@@ -45,21 +58,48 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
         top_ks = _per_utterance_top_k(top_ks, len(utterances), top_k)
         top_ps = _per_utterance_top_p(top_ps, len(utterances), top_p)
     if not utterances:
-        return []
-    stream, first_slot, T = pack_utterances([u.shape[0] for u in utterances], n_streams)
+        return ([], []) if log_probs else []
+    stream, first_slot, T = pack_utterances(lengths, n_streams)
     features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
     gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
-                          utterance_draws=seeds is not None, draw_mode=draw_mode, top_k=top_k, top_p=top_p)
+                          utterance_draws=seeds is not None, draw_mode=draw_mode, top_k=top_k, top_p=top_p,
+                          forcing=prompts is not None, log_probs=log_probs)
     try:
         draws = {}
         if seeds is not None:
             draws['seeds'], draws['temperatures'] = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
             draws['top_ks'] = build_packed_top_k(top_ks, stream, first_slot, T, n_streams)
             draws['top_ps'] = build_packed_top_p(top_ps, stream, first_slot, T, n_streams)
-        samples = gen.generate(features, starts, **draws).cpu().numpy()
+        if prompts is not None:
+            draws['forced'] = build_packed_prompts(prompts, lengths, stream, first_slot, T, n_streams)
+        out = gen.generate(features, starts, **draws)
+        samples, logp = (out[0].cpu().numpy(), out[1].cpu().numpy()) if log_probs else (out.cpu().numpy(), None)
     finally:
         gen.close()
-    return unpack_samples(samples, [u.shape[0] for u in utterances], stream, first_slot)
+    pieces = unpack_samples(samples, lengths, stream, first_slot)
+    return (pieces, unpack_log_probs(logp, lengths, stream, first_slot)) if log_probs else pieces
+
+
+def score_utterances(utterances, samples, n_streams=32):
+    """Log-probabilities of given audio under the model, at generation speed: generate_packed with every sample forced and
+    log_probs=True.  utterances = [n_i, 63] conditioning frames each, samples = per utterance the integer codes [80 * n_i] of
+    its buffer, prefix slot included (its 80 values are not looked at), or the [80 * (n_i - 1)] codes behind it.  Returns,
+    per utterance, the float32 array of the natural log-probabilities of samples 80 ..; minus their mean times log2(e) is
+    the bits per sample compute_cost reports."""
+    BFS = config().BIG_FRAME_SIZE
+    utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
+    samples = list(samples)
+    if len(samples) != len(utterances):
+        raise ValueError("%d utterances, but %d sample arrays" % (len(utterances), len(samples)))
+    prompts = []
+    for u, s in zip(utterances, samples):
+        s = numpy.asarray(s)
+        gen_len = BFS * (u.shape[0] - 1)
+        if s.ndim != 1 or s.shape[0] not in (gen_len, gen_len + BFS):
+            raise ValueError("an utterance of %d frames is scored on %d samples (or %d with its prefix slot), got %s"
+                             % (u.shape[0], gen_len, gen_len + BFS, list(s.shape)))
+        prompts.append(s[s.shape[0] - gen_len:])
+    return generate_packed(utterances, n_streams=n_streams, temperature=0.0, prompts=prompts, log_probs=True)[1]
 
 
 def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_graph=True, gen=None, draw_mode='sequential',
@@ -130,11 +170,24 @@ class StreamingGenerator:
     top_p: the plan's nucleus (see DeviceGenerator), what every utterance draws with unless submit(..., top_p=) names its
     own (utterance_draws=True only).  Likewise, a generator that uses nucleus truncation -- its top_p is active, or some
     utterance was submitted with one -- calls run_segment with one more keyword argument, top_ps [n, B] float32; a
-    generator that does not never passes it."""
+    generator that does not never passes it.
+
+    Prompts: submit(..., prompt=) primes an utterance with up to 80 * (n - 1) codes, the samples 80 .. of its own buffer;
+    the prompt is cut across segment boundaries as the features are and may end mid-frame.  From the first utterance
+    submitted with a prompt on, run_segment is called with one more keyword argument, forced [B, 80 n] int32, aligned with
+    the samples it returns: the code of each forced sample, -1 where the step picks freely (prefix slots and idle slots
+    included).  log_probs=True: run_segment must return (samples, logp), logp [B, 80 n] float32, and step() hands out
+    (ticket, chunk, logp_chunk, done) -- logp_chunk aligned with chunk, zeros on the prefix slot.  A generator in which no
+    utterance has a prompt and log_probs is off calls run_segment exactly as before.  forcing=True builds the generator's own
+    device plan so that it takes prompts (DeviceGenerator(forcing=True)), which a plan cannot learn once it has run: on the
+    device, submit refuses a prompt without it; a plan built without it runs the kernels it always ran."""
 
     def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
-                 utterance_draws=False, draw_mode='sequential', top_k=0, top_p=0.0):
+                 utterance_draws=False, draw_mode='sequential', top_k=0, top_p=0.0, log_probs=False, forcing=False):
         device_loop_guard(draw_mode, top_k, top_p)
+        self.log_probs = bool(log_probs)
+        self.forcing = bool(forcing)   # the generator's own device plan takes prompts (a runner of the caller's always may)
+        self._forcing = False          # some utterance was submitted with a prompt
         self.top_k = top_k_code(top_k)
         self._truncates = self.top_k != 0
         self.top_p = top_p_code(top_p)
@@ -150,7 +203,7 @@ class StreamingGenerator:
         if run_segment is None:
             self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
                                        packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode,
-                                       top_k=self.top_k, top_p=self.top_p)
+                                       top_k=self.top_k, top_p=self.top_p, forcing=self.forcing, log_probs=self.log_probs)
             run_segment = self._run_on_device
         self._run = run_segment
         self._resume = False
@@ -162,27 +215,37 @@ class StreamingGenerator:
         self._draws = {}               # ticket -> (seed, temperature), until the utterance's start flag has been placed
         self._top_ks = {}              # ticket -> top_k, likewise (utterance_draws only)
         self._top_ps = {}              # ticket -> top_p, likewise
+        self._prompts = {}             # ticket -> its prompt, until the utterance is done
         self.record = {}
 
-    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None, top_ps=None):
+    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None, top_ps=None, forced=None):
         # (without utterance_draws the plan has no entries: every utterance draws with the plan's top_k)
         draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
         if seeds is not None and top_ks is not None:
             draws['top_ks'] = top_ks
         if seeds is not None and top_ps is not None:
             draws['top_ps'] = top_ps
+        n, BFS = features.shape[0], config().BIG_FRAME_SIZE
+        # (a plan built to take forced samples is handed them in every call: all free until some utterance has a prompt)
+        if self.forcing and forced is None:
+            forced = numpy.full((self.B, BFS * n), FREE, dtype=numpy.int32)
+        more = {} if forced is None else dict(forced=forced)
+        host = lambda out, cut: tuple(o.cpu().numpy()[:, cut:] for o in out) if self.log_probs else out.cpu().numpy()[:, cut:]
         if resume:
-            return self.gen.generate(features, starts, resume=True, n_frames=features.shape[0], **draws).cpu().numpy()
-        n = features.shape[0]  # the first segment: slot 0 is the run's prefix slot, no stream uses it
+            return host(self.gen.generate(features, starts, resume=True, n_frames=n, **more, **draws), 0)
+        # the first segment: slot 0 is the run's prefix slot, no stream uses it
         features = numpy.concatenate([numpy.zeros_like(features[:1]), features])
         starts = numpy.concatenate([numpy.zeros_like(starts[:1]), starts])
         draws = {k: numpy.concatenate([numpy.zeros_like(v[:1]), v]) for k, v in draws.items()}
-        return self.gen.generate(features, starts, n_frames=n, **draws).cpu().numpy()[:, config().BIG_FRAME_SIZE:]
+        if forced is not None:
+            more['forced'] = numpy.concatenate([numpy.full((self.B, BFS), FREE, dtype=numpy.int32), forced], axis=1)
+        return host(self.gen.generate(features, starts, n_frames=n, **more, **draws), BFS)
 
-    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None):
+    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None, prompt=None):
         """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
         seed (an unsigned 64-bit integer), temperature, top_k and top_p (defaults: the generator's): with
-        utterance_draws=True only, where the seed is required."""
+        utterance_draws=True only, where the seed is required.  prompt: up to 80 * (n - 1) integer codes in
+        0 .. Q_LEVELS-1, the utterance's samples 80 ..: it goes on freely behind them."""
         if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
             raise ValueError("a seed (and a temperature) per utterance is given exactly when the generator was built with "
                              "utterance_draws=True")
@@ -197,8 +260,15 @@ class StreamingGenerator:
         features = numpy.asarray(features, dtype='float32')
         if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
             raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
+        if prompt is not None:
+            if self.gen is not None and not self.forcing:
+                raise ValueError("a prompt needs a generator built with forcing=True: its device plan is built to take them")
+            prompt = _per_utterance_prompts([prompt], [features.shape[0]])[0]
         ticket = self._next_ticket
         self._next_ticket += 1
+        if prompt is not None:
+            self._prompts[ticket] = prompt
+            self._forcing = True
         if self.utterance_draws:
             self._draws[ticket] = (u64(seed), self.temperature if temperature is None else float(temperature))
             self._top_ks[ticket] = self.top_k if top_k is None else top_k
@@ -213,7 +283,8 @@ class StreamingGenerator:
         return not self.queue and all(r is None for r in self.running)
 
     def step(self):
-        """Runs one segment; returns [(ticket, chunk int32 [80 k], done)] for every utterance that had slots in it."""
+        """Runs one segment; returns [(ticket, chunk int32 [80 k], done)] for every utterance that had slots in it --
+        (ticket, chunk, logp_chunk float32 [80 k], done) with log_probs=True."""
         placements, starts, n, self.running, self.queue = schedule_segment(self.running, self.queue, self.B, self.S)
         if n == 0:
             return []
@@ -248,7 +319,25 @@ class StreamingGenerator:
             for ticket, b, slot, frame, count in placements:
                 if frame <= 1 < frame + count:
                     draws['top_ps'][start_row(slot - frame, n + 1) - 1, b] = self._top_ps.get(ticket, self.top_p)
-        samples = numpy.asarray(self._run(feats, flags, self._resume, **draws))
+        if self._forcing:  # sample j of an utterance's buffer is column 80 (slot - 1) + (j - 80 frame) of this segment
+            draws['forced'] = numpy.full((self.B, BFS * n), FREE, dtype=numpy.int32)
+            for ticket, b, slot, frame, count in placements:
+                p = self._prompts.get(ticket)
+                if p is None:
+                    continue
+                lo, hi = max(BFS * frame, BFS), min(BFS * (frame + count), BFS + p.size)  # the prompt's share, buffer indices
+                if lo < hi:
+                    col = BFS * (slot - 1) - BFS * frame
+                    draws['forced'][b, col + lo:col + hi] = p[lo - BFS:hi - BFS]
+        got = self._run(feats, flags, self._resume, **draws)
+        logp = None
+        if self.log_probs:
+            if not isinstance(got, (tuple, list)) or len(got) != 2:
+                raise ValueError("with log_probs=True the segment runner returns (samples, logp)")
+            got, logp = got[0], numpy.asarray(got[1], dtype='float32')
+            if logp.shape != (self.B, BFS * n):
+                raise ValueError("the segment runner returned log-probabilities %s, not %s" % (logp.shape, (self.B, BFS * n)))
+        samples = numpy.asarray(got)
         if samples.shape != (self.B, BFS * n):
             raise ValueError("the segment runner returned %s, not %s" % (samples.shape, (self.B, BFS * n)))
         self._resume = True
@@ -264,7 +353,14 @@ class StreamingGenerator:
                 self._draws.pop(ticket, None)
                 self._top_ks.pop(ticket, None)
                 self._top_ps.pop(ticket, None)
-            out.append((ticket, chunk, done))
+                self._prompts.pop(ticket, None)
+            if logp is None:
+                out.append((ticket, chunk, done))
+                continue
+            lchunk = numpy.array(logp[b, BFS * (slot - 1):BFS * (slot - 1 + count)], dtype='float32')
+            if frame == 0:
+                lchunk[:BFS] = 0.0  # (the prefix slot: nothing was asked of the model there)
+            out.append((ticket, chunk, lchunk, done))
         return out
 
     def drain(self):

@@ -200,8 +200,11 @@ from ...generation.inputs import (DRAW_K1, DRAW_K2, DRAW_MODES, _M64, _per_utter
                                   build_packed_inputs, build_packed_top_k, build_packed_top_p, draw_mode_code,
                                   pack_utterances, schedule_segment, top_k_array, top_k_code, top_p_active, top_p_array,
                                   top_p_code, unpack_samples, utterance_draw_u01, utterance_seed)
+from ...generation.inputs import (_per_utterance_prompts, build_packed_prompts, forced_array,  # noqa: E402,F401
+                                  unpack_log_probs)
 from ...generation.device import DeviceGenerator  # noqa: E402
-from ...generation.serving import StreamingGenerator, generate_packed, generate_stream  # noqa: E402,F401
+from ...generation.serving import (StreamingGenerator, generate_packed, generate_stream,  # noqa: E402,F401
+                                   score_utterances)
 
 
 def write_audio_file(name, data, path_to_save):

@@ -9,7 +9,8 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          decode_gmm_gru2_1024, decode_gmm_lstm2_1024, decode_bf16_gru2_1024,
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
                                          samplernn_cfg5, samplernn_groups, samplernn_packed, samplernn_stream,
-                                         samplernn_utt_draws, samplernn_draw_scan, samplernn_top_k, samplernn_top_p, mulaw)
+                                         samplernn_utt_draws, samplernn_draw_scan, samplernn_top_k, samplernn_top_p,
+                                         samplernn_forced, mulaw)
   bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
                                          SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
                                          kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
@@ -67,6 +68,15 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          in the same alternation, bit identity included, and the bar "scan at p = 0.9 stays
                                          faster than the parent's untruncated sequential draw"; the result also goes to FILE
                                          (default profiles/samplernn_top_p.json)
+  bench_extra.py --only samplernn_forced [--reps N] [--forced-json FILE] [--parent-lib FILE]
+                                         SampleRNN at D = 1024 and B = 32, 8000 samples per stream: the default plan at
+                                         temperature 0 and 1, a forcing plan with every code -1, a forcing plan with every
+                                         sample forced (DeviceGenerator(forcing=True)) and a plan with log_probs=True, the
+                                         three at both temperatures; N alternations in one process, each with its spread; what
+                                         forcing and the log-probability cost per sample step (no bar of their own); with
+                                         --parent-lib (the parent commit's libparrot_hip.so) the default plan of both
+                                         libraries at temperature 0 and 1 in the same alternation, bit identity included;
+                                         the result also goes to FILE (default profiles/samplernn_forced.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -91,7 +101,7 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "mulaw")
+       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_forced", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1012,6 +1022,111 @@ if "samplernn_top_p" in only:
             "sum_of_the_two_spreads_us": round(both, 3),
             "holds": bool(med["parent_sequential_t1"] - med["scan_t1_p90"] > both)}
     record("samplernn_top_p", "--top-p-json", res)
+
+# ---- SampleRNN D=1024, B=32: forced samples and per-sample log-probabilities (samplernn_generate_set_forced / _set_log_probs,
+# DeviceGenerator(forcing=, log_probs=)) -- the default plan at temperature 0 and 1, a forcing plan with every code -1, a
+# forcing plan with every sample forced, a plan with log_probs=True, the three at both temperatures --; and, with
+# --parent-lib, the default plan against the parent commit's library.  All plans alive in one process and run alternately,
+# as samplernn_top_p.  No mode has a bar of its own: the leg reports what forcing and the log-probability cost per step.
+if "samplernn_forced" in only:
+    import contextlib
+    import ctypes
+    from parrot_amd import _lib as plib
+    tt = samplernn_d1024()
+    T, SEED, reps = 101, 234, int(_arg("--reps", "5"))
+    nsamp = (T - 1) * 80
+    feats = torch.randn(T, 32, 63, generator=g).numpy()
+    free = np.full((32, 80 * T), -1, dtype=np.int32)
+    codes = np.random.RandomState(SEED).randint(0, 256, size=(32, 80 * T)).astype(np.int32)
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            if hasattr(parent_lib, name):  # (the parent has neither new setter: its plans never call them)
+                fn = getattr(parent_lib, name)
+                fn.restype = res_
+                fn.argtypes = args_
+
+    @contextlib.contextmanager
+    def under(which):  # every call of a plan goes to the library that made it
+        plib._lib = which
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+
+    def plan(which=this_lib, **kw):
+        with under(which):
+            return tt.DeviceGenerator(32, T, seed=SEED, **kw)
+
+    # name: (plan, its library, generate's keywords)
+    plans = {}
+    for tag, temp in (("argmax", 0.0), ("sequential_t1", 1.0)):
+        plans[tag] = (plan(temperature=temp), this_lib, {})
+        plans[tag + "_forcing_all_free"] = (plan(temperature=temp, forcing=True), this_lib, dict(forced=free))
+        plans[tag + "_forcing_all_forced"] = (plan(temperature=temp, forcing=True), this_lib, dict(forced=codes))
+        plans[tag + "_log_probs"] = (plan(temperature=temp, log_probs=True), this_lib, {})
+    if parent_lib is not None:
+        plans["parent_argmax"] = (plan(which=parent_lib, temperature=0.0), parent_lib, {})
+        plans["parent_sequential_t1"] = (plan(which=parent_lib, temperature=1.0), parent_lib, {})
+        # (a second plan of each kind, created in the other order: the floor under any difference between the libraries)
+        plans["argmax_again"] = (plan(temperature=0.0), this_lib, {})
+        plans["sequential_t1_again"] = (plan(temperature=1.0), this_lib, {})
+        plans["parent_sequential_t1_again"] = (plan(which=parent_lib, temperature=1.0), parent_lib, {})
+        plans["parent_argmax_again"] = (plan(which=parent_lib, temperature=0.0), parent_lib, {})
+    assert all(gen.persist_groups == 1 for gen, _, _ in plans.values())
+    times, samples, logps = {k: [] for k in plans}, {}, {}
+    keys = list(plans)
+    for rep_ in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+        for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:  # (no plan always runs behind the same other one)
+            gen, which, kw = plans[k]
+            with under(which):
+                torch.cuda.synchronize(); t0 = time.time()
+                s = gen.generate(feats, **kw)
+                torch.cuda.synchronize(); dt = time.time() - t0
+                if isinstance(s, tuple):
+                    s, logps[k] = s[0], s[1].cpu().numpy().copy()
+                samples[k] = s.cpu().numpy().copy()
+            if rep_:
+                times[k].append(dt)
+    for gen, which, _ in plans.values():
+        with under(which):
+            gen.close()
+    us = {k: [1e6 * dt / nsamp for dt in v] for k, v in times.items()}
+    med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+    spread = {k: max(v) - min(v) for k, v in us.items()}
+    base = ("argmax", "sequential_t1")
+    res = {"dim": 1024, "streams": 32, "alternations": reps, "samples_per_stream": nsamp,
+           "timed": "call to device idle (host-side input copies included: a forcing plan also copies its [32, 8080] codes)",
+           "runs": {k: {"us_per_sample_step": [round(x, 3) for x in us[k]], "us_per_sample_step_median": round(med[k], 3),
+                        "spread_max_minus_min": round(spread[k], 3)} for k in plans},
+           "cost_us_per_sample_step": {t: {m: round(med[t + "_" + m] - med[t], 3)
+                                           for m in ("forcing_all_free", "forcing_all_forced", "log_probs")} for t in base},
+           "all_free_bit_identical_to_default": {t: bool(np.array_equal(samples[t + "_forcing_all_free"], samples[t])) for t in base},
+           "log_probs_bit_identical_to_default": {t: bool(np.array_equal(samples[t + "_log_probs"], samples[t])) for t in base},
+           "all_forced_returns_the_codes": {t: bool(np.array_equal(samples[t + "_forcing_all_forced"][:, 80:], codes[:, 80:])) for t in base},
+           "mean_bits_per_sample_of_the_default_runs": {t: round(float(-logps[t + "_log_probs"][:, 80:].mean() * np.log2(np.e)), 4) for t in base},
+           "not_measured": ["row groups", "the launch path's timing", "the streaming generator end to end",
+                            "D = 256 and D = 512", "both facilities on one plan, the scan draw and truncated draws with either"]}
+    if parent_lib is not None:
+        def pair(t):  # the bar of the issue (the two first plans, the sum of their spreads) and the four plans' picture beside it
+            a, b = (med[t], med[t + "_again"]), (med["parent_" + t], med["parent_" + t + "_again"])
+            both = spread[t] + spread["parent_" + t]
+            return {"this_us": [round(x, 3) for x in a], "parent_us": [round(x, 3) for x in b],
+                    "this_minus_parent_us": round(a[0] - b[0], 3), "sum_of_the_two_spreads_us": round(both, 3),
+                    "bar_default_within_the_sum_of_both_spreads": bool(abs(a[0] - b[0]) <= both),
+                    "mean_of_two_plans_this_minus_parent_us": round(sum(a) / 2 - sum(b) / 2, 3),
+                    "largest_difference_between_two_plans_of_one_library_us": round(max(abs(a[0] - a[1]), abs(b[0] - b[1])), 3)}
+        res["default_path_against_parent_commit"] = {
+            "how": "this build and the parent commit's library loaded in one process, two plans of each per temperature (the "
+                   "second pair created in the other order), all in the same alternation; the bar compares the first plan of "
+                   "each library against the sum of their spreads (max - min over the alternations)",
+            "bit_identical_t0": bool(np.array_equal(samples["argmax"], samples["parent_argmax"])),
+            "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
+            "t0": pair("argmax"), "t1": pair("sequential_t1")}
+    record("samplernn_forced", "--forced-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
