@@ -733,6 +733,8 @@ int parrot_mu2linear(const int32_t* q, size_t n, float* out, void* stream);
  * The backward is a SEGMENTED sum, no scatter-add: perm [J,N] lists, per j, the rows sorted by (idx[.,j], row) (a stable
  * sort, so the order of the addends depends on the indices only) and offs [J,Q+1] the first position of every bin in that
  * order (offs[j][Q] = N).  ws: parrot_gather_sum_bwd_ws_floats(N,J,Q,D) floats of scratch.  D % 4 == 0, 16-byte aligned.
+ * N == 0: the forward returns 0 and writes nothing; the backward returns PARROT_ERR_BADARG (there are no bins to sum:
+ * it neither zeroes dtbl nor launches anything).
  *
  * Softmax cross-entropy with integer targets (three_tier.py:565-584, T.nnet.categorical_crossentropy(softmax(.), target)):
  *   parrot_softmax_ce_fwd:  lse[i] = log sum_q exp(logits[i,q]),  ce[i] = lse[i] - logits[i, target[i]]

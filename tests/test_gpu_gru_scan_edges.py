@@ -11,19 +11,16 @@ the other path would otherwise be compared with itself.  Results of table cases 
 by the tests that need them."""
 import contextlib
 import ctypes as C
-import math
 import os
 
 import pytest
 import torch
 
 from tests import gru_scan_cases as G
-from tests.util import assert_close, rel_err
+from tests.util import FRAME_BITS, PAD, Framed, _bits, assert_close, rel_err  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-PAD = 64                 # floats (256 bytes: a framed view stays 16-byte aligned)
-FRAME_BITS = 0x7FC0BEEF  # a quiet NaN no arithmetic produces
 BADARG = 10001
 PATHS = [(G.ROWWISE, 4), (G.ROWWISE, 8), (G.SWITCH, 0)]
 PATH_IDS = ["rowwise-w4", "rowwise-w8", "launch"]
@@ -32,32 +29,6 @@ PATH_IDS = ["rowwise-w4", "rowwise-w8", "launch"]
 def SHAPES(T, B, H):
     return dict(h=(T + 1, B, H), z=(T, B, H), r=(T, B, H), rh=(T, B, H), c=(T, B, H), inputs=(T, B, H),
                 gate_inputs=(T, B, 2 * H), dh=(T + 1, B, H), dG=(T, B, 2 * H), dC=(T, B, H))
-
-
-def _bits(t):
-    """The tensor's words, flat."""
-    return t.contiguous().view(torch.int32).reshape(-1)
-
-
-class Framed:
-    """`view`: a tensor of `shape` inside a larger allocation, `off` floats past a 16-byte aligned address."""
-
-    def __init__(self, shape, dev, off=0):
-        self.n, self.lo = math.prod(shape), PAD + off
-        self.big = torch.full((self.n + 2 * PAD + off,), FRAME_BITS, dtype=torch.int32, device=dev).view(torch.float32)
-        self.view = self.big[self.lo:self.lo + self.n].view(shape)
-        assert self.view.data_ptr() % 16 == 4 * (off % 4)
-        self.before = None
-
-    def snapshot(self):
-        self.before = _bits(self.big).clone()
-
-    def frame_untouched(self):
-        now, hi = _bits(self.big), self.lo + self.n
-        return torch.equal(now[:self.lo], self.before[:self.lo]) and torch.equal(now[hi:], self.before[hi:])
-
-    def untouched(self):
-        return torch.equal(_bits(self.big), self.before)
 
 
 @contextlib.contextmanager

@@ -1,6 +1,11 @@
 """Shared helpers for the parity tests (oracle = checker, parrot_amd = product)."""
+import math
+
 import numpy as np
 import torch
+
+PAD = 64                 # floats (256 bytes: a framed view stays 16-byte aligned)
+FRAME_BITS = 0x7FC0BEEF  # a quiet NaN no arithmetic produces
 
 
 def rel_err(a, b):
@@ -48,3 +53,29 @@ def make_batch(cfg, T, B, U, seed=0, ragged=False, dtype=torch.float64, speaker=
             lmask[b, ul:] = 0
     spk = torch.randint(0, cfg['num_speakers'], (B, 1), generator=g) if speaker else None
     return feat, fmask, labels, lmask, spk
+
+
+def _bits(t):
+    """The tensor's words, flat."""
+    return t.contiguous().view(torch.int32).reshape(-1)
+
+
+class Framed:
+    """`view`: a tensor of `shape` inside a larger allocation, `off` floats past a 16-byte aligned address."""
+
+    def __init__(self, shape, dev, off=0):
+        self.n, self.lo = math.prod(shape), PAD + off
+        self.big = torch.full((self.n + 2 * PAD + off,), FRAME_BITS, dtype=torch.int32, device=dev).view(torch.float32)
+        self.view = self.big[self.lo:self.lo + self.n].view(shape)
+        assert self.view.data_ptr() % 16 == 4 * (off % 4)
+        self.before = None
+
+    def snapshot(self):
+        self.before = _bits(self.big).clone()
+
+    def frame_untouched(self):
+        now, hi = _bits(self.big), self.lo + self.n
+        return torch.equal(now[:self.lo], self.before[:self.lo]) and torch.equal(now[hi:], self.before[hi:])
+
+    def untouched(self):
+        return torch.equal(_bits(self.big), self.before)
