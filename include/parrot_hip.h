@@ -910,7 +910,8 @@ typedef struct SampleRnnGenDesc {
     float* big_out; float* frame_out; float* o1; float* o2; float* o3; float* logits;
     int* tbase;
     /* Stacked / LSTM tiers (three_tier.py:147-169 allows RNN_TYPE = 'LSTM' and N_RNN in 1..5; stackedGRU / stackedLSTM,
-     * sampleRNN/lib/ops.py:612-777, 823-989, without skip connections).  n_rnn = 0 keeps the single-GRU fields above.
+     * sampleRNN/lib/ops.py:612-777, 823-989; with skip connections: samplernn_generate_set_skip_stacks below).  n_rnn = 0
+     * keeps the single-GRU fields above.
      * Otherwise, per tier and layer k < n_rnn, four pointers:
      *   GRU  (lstm = 0): { Input.W [D,3D], Input.b [3D], Recurrent_Gates [D,2D], Recurrent_Candidate [D,D] }
      *   LSTM (lstm = 1): { Input.W [D,4D], b [4D], Recurrent_Gates [D,4D], NULL }   (gate order i | f | o | g)
@@ -1029,6 +1030,29 @@ int samplernn_generate_set_forced(void* plan, const int* forced);
  * whatever the step draws with; the quantity the training cost averages.  Slot 0 is not written.  PARROT_ERR_BADARG for a
  * null plan or pointer and for a plan that has run; no device call. */
 int samplernn_generate_set_log_probs(void* plan, float* logp);
+/* Skip-connection stacks (--skip_conn True: Graves' stacks, sampleRNN/lib/ops.py:650-695, 861-880).  In such a stack every
+ * layer above the first reads [h_{k-1} ; x], x = the stack's input, and the stack's output is sum_k h_k . S_k + bS instead
+ * of the top layer's state.  The descriptor does not change; a plan with n_rnn >= 2 takes the rest through this struct:
+ *   big_S / frm_S [k], k < n_rnn: [D, D] the effective (weight-norm folded) out-skip matrix of layer k + 1
+ *     ('<tier>.GRU.outskip<k+1>y', '<tier>.LSTM<k+1>.outskip<k+1>y');
+ *   big_bS / frm_bS: [D] the bias of the first out-skip (the others have none);
+ *   big_sum / frm_sum: [B, D] scratch for the summed output, owned by the caller for the plan's life.
+ * With the setter in force, slot 0 of big_L[k] / frm_L[k] for k >= 1 is the [2D, N] Input matrix of
+ * '<tier>.GRU<k+1>+inpskip' / '<tier>.LSTM<k+1>+inpskip' (N = 3D for GRU, 4D for LSTM): rows 0 .. D-1 multiply h_{k-1},
+ * rows D .. 2D-1 multiply x.  Weight norm scales each column over all 2D rows: fold it as one matrix.  The step jobs of
+ * those layers carry one more K segment, and one more job per tier step makes the sum (f32) into big_sum / frm_sum, which
+ * the tier's output projection then reads in place of the top state.  Everything else -- the sample steps, the draws,
+ * packing, segments, forcing, log-probabilities -- is what it is without the setter.
+ * PARROT_ERR_BADARG for a null plan, struct or pointer (S of layers >= n_rnn are not read); PARROT_ERR_UNSUPPORTED for a
+ * plan with n_rnn < 2 (the single-GRU plan has n_rnn = 0, and no one-layer stack has skip connections);
+ * PARROT_ERR_BADARG for a plan that has run (the period graphs hold the pointers by value).  A refused call leaves the plan
+ * as it was.  No device call. */
+typedef struct SampleRnnSkipStacks {
+    const float* big_S[5]; const float* frm_S[5];
+    const float* big_bS; const float* frm_bS;
+    float* big_sum; float* frm_sum;
+} SampleRnnSkipStacks;
+int samplernn_generate_set_skip_stacks(void* plan, const SampleRnnSkipStacks* skip);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

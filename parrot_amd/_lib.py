@@ -173,6 +173,11 @@ class SampleRnnGenDesc(C.Structure):
                  ("starts", C.c_void_p), ("big_h0", C.c_void_p), ("frm_h0", C.c_void_p)])
 
 
+class SampleRnnSkipStacks(C.Structure):
+    _fields_ = [("big_S", C.c_void_p * 5), ("frm_S", C.c_void_p * 5), ("big_bS", C.c_void_p), ("frm_bS", C.c_void_p),
+                ("big_sum", C.c_void_p), ("frm_sum", C.c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/parrot_hip.h declares must be listed here
 # (tests/test_capi_cpu.py cross-checks this table against the header).
 _vp, _i, _f, _ll, _sz = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
@@ -269,6 +274,7 @@ SIGNATURES = {
     "samplernn_generate_set_utterance_top_p": (_i, [_vp, _vp]),
     "samplernn_generate_set_forced": (_i, [_vp, _vp]),
     "samplernn_generate_set_log_probs": (_i, [_vp, _vp]),
+    "samplernn_generate_set_skip_stacks": (_i, [_vp, C.POINTER(SampleRnnSkipStacks)]),
     "samplernn_persist_floats": (C.c_longlong, [C.POINTER(SampleRnnGenDesc)]),
     "samplernn_generate_is_persistent": (_i, [_vp]),
     "samplernn_generate_persist_groups": (_i, [_vp]),

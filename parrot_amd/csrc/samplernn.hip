@@ -405,6 +405,10 @@ struct SrPlan {
     // Indexed by buffer index, so a resumed segment needs no state of theirs: the host stages them per segment, like features.
     const int* forced = nullptr;
     float* logp = nullptr;
+    // samplernn_generate_set_skip_stacks: Graves' stacks (ops.py:650-695, 861-880).  Layer k >= 1 reads [h_{k-1} ; x] through
+    // its [2D, N] Input matrix (slot 0 of big_L[k] / frm_L[k]) and the tier's output is sum_k h_k . S_k + bS.
+    SampleRnnSkipStacks skip{};
+    bool has_skip = false;
     int make_origin() {
         if (hipMalloc(&origin, sizeof(unsigned long long)) != hipSuccess) { origin = nullptr; return 1; }
         return (int)hipMemset(origin, 0, sizeof(unsigned long long));
@@ -518,29 +522,44 @@ struct SrPlan {
     // b[2D:]); in-place h.  The Input linear rides in the step GEMMs as a second K segment: two launches, not three.
     // pre: x . U + bU arrives precomputed ([B, 3D]: gates | candidate) and only the recurrent product is left;
     // gates_done: the previous frame's sample kernel has left z and r*h already.
+    // xs (skip stacks, layers above the first): U is [2D, 3D] and its rows D .. 2D-1 multiply the stack's input xs -- one
+    // more K segment in both jobs, still two launches.
     int gru(const float* x, const float* U, const float* bU, const float* Wg, const float* Wc, float* h, hipStream_t st,
-            const Tiled& t, const float* pre = nullptr, bool gates_done = false) {
+            const Tiled& t, const float* pre = nullptr, bool gates_done = false, const float* xs = nullptr) {
         const int D = d.D;
+        const float* Us = xs ? U + (size_t)D * 3 * D : nullptr;
         SkJob j;
         if (!gates_done) {
             sk_gru_gates_job(j, d.B, D, h, d.z, d.r, d.rh);
             j.seg[j.nseg++] = seg(h, D, Wg, 2 * D, t.Wg);
             if (pre) { j.add = pre; j.ld_add = 3 * D; }
             else { j.seg[j.nseg++] = seg(x, D, U, 3 * D, t.U); j.bias = bU; }
+            if (xs) j.seg[j.nseg++] = seg(xs, D, Us, 3 * D, nullptr);
             SR_TRY(launch(&j, 1, st));
         }
         sk_gru_cand_job(j, d.B, D, h, d.z, nullptr, h);
         j.seg[j.nseg++] = seg(d.rh, D, Wc, D, t.Wc);
         if (pre) { j.add = pre + 2 * D; j.ld_add = 3 * D; }
         else { j.seg[j.nseg++] = seg(x, D, U, 3 * D, t.U, 2 * D); j.bias = bU + 2 * D; }
+        if (xs) j.seg[j.nseg++] = seg(xs, D, Us, 3 * D, nullptr, 2 * D);
         return launch(&j, 1, st);
     }
 
     // LSTM step of a tier layer (ops.py:505-553): pre = x . Win + b; gates = s . Wrec + pre (i | f | o | g);
     // c' = c*f + g*i; s' = tanh(c')*o.  s is the A operand of the step GEMM, so s' goes to a temporary first.
-    int lstm_layer(const float* x, const float* Win, const float* b, const float* Wrec, float* s, float* c, hipStream_t st) {
+    // xs (skip stacks, layers above the first): Win is [2D, 4D], rows D .. 2D-1 multiply the stack's input xs.
+    int lstm_layer(const float* x, const float* Win, const float* b, const float* Wrec, float* s, float* c, hipStream_t st,
+                   const float* xs = nullptr) {
         const int D = d.D;
-        SR_TRY(linear(x, D, Win, nullptr, 4 * D, b, d.P, 0, st));
+        if (!xs) {
+            SR_TRY(linear(x, D, Win, nullptr, 4 * D, b, d.P, 0, st));
+        } else {
+            SkJob in;
+            sk_linear_job(in, seg(x, D, Win, 4 * D, nullptr), d.B, 4 * D, 4 * D, d.P, 4 * D);
+            in.seg[in.nseg++] = seg(xs, D, Win + (size_t)D * 4 * D, 4 * D, nullptr);
+            in.bias = b;
+            SR_TRY(launch(&in, 1, st));
+        }
         SkJob j;
         sk_lstm_job(j, d.B, D, c, c, d.gate_ws, d.layer_tmp);
         j.seg[j.nseg++] = seg(s, D, Wrec, 4 * D, nullptr);
@@ -557,12 +576,24 @@ struct SrPlan {
             *top = big ? d.big_h : d.frm_h;
             return 0;
         }
+        const float* const xs = x;  // the stack's input: what every layer above the first of a skip stack reads too
         for (int k = 0; k < d.n_rnn; ++k) {
             const float* const* Lk = big ? d.big_L[k] : d.frm_L[k];
             float* hs = big ? d.big_hs[k] : d.frm_hs[k];
-            if (d.lstm) SR_TRY(lstm_layer(x, Lk[0], Lk[1], Lk[2], hs, big ? d.big_cs[k] : d.frm_cs[k], st));
-            else SR_TRY(gru(x, Lk[0], Lk[1], Lk[2], Lk[3], hs, st, Tiled()));
+            const float* in2 = has_skip && k > 0 ? xs : nullptr;
+            if (d.lstm) SR_TRY(lstm_layer(x, Lk[0], Lk[1], Lk[2], hs, big ? d.big_cs[k] : d.frm_cs[k], st, in2));
+            else SR_TRY(gru(x, Lk[0], Lk[1], Lk[2], Lk[3], hs, st, Tiled(), nullptr, false, in2));
             x = hs;
+        }
+        if (has_skip) {  // out = sum_k h_k . S_k + bS: one job, one K segment per layer (f32 sums inside the job)
+            const float* const* S = big ? skip.big_S : skip.frm_S;
+            float* out = big ? skip.big_sum : skip.frm_sum;
+            SkJob j;
+            sk_linear_job(j, d.B, d.D, d.D, out, d.D);
+            for (int k = 0; k < d.n_rnn; ++k) j.seg[j.nseg++] = seg(big ? d.big_hs[k] : d.frm_hs[k], d.D, S[k], d.D, nullptr);
+            j.bias = big ? skip.big_bS : skip.frm_bS;
+            SR_TRY(launch(&j, 1, st));
+            x = out;
         }
         *top = x;
         return 0;
@@ -916,6 +947,20 @@ int samplernn_generate_set_log_probs(void* plan, float* logp) {
     if (!p || !logp) return PARROT_ERR_BADARG;
     if (p->has_run) return PARROT_ERR_BADARG;
     p->logp = logp;
+    return 0;
+}
+
+// Skip-connection stacks.  (No HIP call: the pointers are handed to the step jobs by the launches of the first run.)
+int samplernn_generate_set_skip_stacks(void* plan, const SampleRnnSkipStacks* skip) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !skip) return PARROT_ERR_BADARG;
+    if (p->d.n_rnn < 2) return PARROT_ERR_UNSUPPORTED;  // (the single-GRU plan has n_rnn = 0; no one-layer skip stack exists)
+    if (p->has_run) return PARROT_ERR_BADARG;           // the period graphs hold the pointers by value
+    if (!skip->big_bS || !skip->frm_bS || !skip->big_sum || !skip->frm_sum) return PARROT_ERR_BADARG;
+    for (int k = 0; k < p->d.n_rnn; ++k)
+        if (!skip->big_S[k] || !skip->frm_S[k]) return PARROT_ERR_BADARG;
+    p->skip = *skip;
+    p->has_skip = true;
     return 0;
 }
 

@@ -67,6 +67,11 @@
 // PARROT_BF16_DW           1        step     0: bf16 decoders' weight gradients from f32 operands            tests
 // PARROT_BF16_READOUT      1        step     0: bf16 decoders' readout stack on f32 operands                 tests, tools
 // PARROT_BF16_DG16         1        alloc    0: LSTM backward scan leaves f32 pre-activation gradients       tools
+// PARROT_SR_SKIP_STACKS    0        call     1: SampleRNN's device-resident generator takes skip-connection  tests, tools
+//                                            stacks (SKIP_CONN, N_RNN >= 2): Python gathers the +inpskip /
+//                                            outskip parameters and calls samplernn_generate_set_skip_stacks;
+//                                            0: refused, generate_and_save_samples runs the literal loop.
+//                                            The library itself does not read it: the setter is the switch
 // PARROT_SKIP_INDEX_CHECK  0        import   1: embedding index bounds are not checked on the host           development
 // PARROT_DP_BUCKETS        1        Trainer  0: gradient all-reduce in one bucket                            development
 // PARROT_ALLREDUCE_BF16    0        Trainer  1: bf16 on the wire                                             development

@@ -8,18 +8,24 @@ from ... import _lib
 from ... import ops as hip
 from .. import lib
 from ..lib import ops as lops
-from .inputs import FREE, _seed_image, config, draw_mode_code, forced_array, top_k_array, top_k_code, top_p_array, top_p_code
+from .inputs import (FREE, _seed_image, config, draw_mode_code, forced_array, skip_stacks_enabled, stack_param_names,
+                     top_k_array, top_k_code, top_p_array, top_p_code)
 
 
 def device_loop_guard(draw_mode, top_k=0, top_p=0.0):
     """What every entry to the device-resident loop checks before any device call: draw_mode's code (ValueError on an
-    unknown name), top_k (ValueError on a negative one), top_p (ValueError on a negative one or a NaN), and that the model
-    has no skip-connection stacks, which the loop does not take."""
+    unknown name), top_k (ValueError on a negative one), top_p (ValueError on a negative one or a NaN), and the model's
+    stacks: skip-connection stacks (SKIP_CONN) are taken only with PARROT_SR_SKIP_STACKS=1, read here at call time, and only
+    with N_RNN >= 2 (the reference asserts that no one-layer stack has skip connections); NotImplementedError otherwise."""
     mode = draw_mode_code(draw_mode)
     top_k_code(top_k)
     top_p_code(top_p)
     if config().SKIP_CONN:
-        raise NotImplementedError("the device-resident generator does not take skip-connection stacks")
+        if not skip_stacks_enabled():
+            raise NotImplementedError("the device-resident generator takes skip-connection stacks only with "
+                                      "PARROT_SR_SKIP_STACKS=1")
+        if config().N_RNN < 2:
+            raise NotImplementedError("a single-layer stack cannot have skip connections")
     return mode
 
 
@@ -31,8 +37,11 @@ class DeviceGenerator:
 
     def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
                  draw_mode='sequential', top_k=0, top_p=0.0, forcing=False, log_probs=False):
-        """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections run on the literal
-        three-function loop (generate_and_save_samples(..., use_device_loop=False) is chosen automatically).
+        """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections (SKIP_CONN, 2..5
+        layers) are taken with PARROT_SR_SKIP_STACKS=1 (samplernn_generate_set_skip_stacks: one more K segment in the step
+        jobs of the layers above the first, one more job per tier step for the summed out-skips; everything below is the
+        same for them); without the switch they are refused (NotImplementedError) and generate_and_save_samples runs them
+        on the literal three-function loop.
 
         packed=True: the plan takes per-stream utterance starts (SampleRnnGenDesc::starts): generate(features, starts)
         then begins a new utterance in stream b at big frame f wherever starts[f][b] != 0 (see generate_packed).
@@ -107,17 +116,20 @@ class DeviceGenerator:
                 hip.gemm(emb, W1[pos * tt.EMB_SIZE:(pos + 1) * tt.EMB_SIZE], out=tbl[pos])
             w['emb_tbl'] = tbl
             # the RNN stacks of the two tiers: per layer (Input.W, Input.b | b, Recurrent_Gates, Recurrent_Candidate | -)
+            # (skip stacks: the Input of a layer above the first is [2 D, N], folded as ONE matrix -- weight norm scales a
+            # column over all its rows --, and every layer has an out-skip matrix, the first one a bias)
             self.layers = {}
+            self.skip = bool(tt.SKIP_CONN)
+            self.outskips = {}
             for tier, tag in (('BigFrameLevel', 'big'), ('FrameLevel', 'frm')):
-                for k in range(1, N_RNN + 1):
+                names, outskips, outskip_bias = stack_param_names(tier, RNN_TYPE, N_RNN, self.skip)
+                for k, nm in enumerate(names):
+                    layer = [ew(nm['input']), lib.param(nm['bias']).detach().contiguous(), ew(nm['gates'])]
                     if RNN_TYPE == 'GRU':
-                        pre = f'{tier}.GRU{k}.Step'
-                        self.layers[(tag, k - 1)] = [ew(pre + '.Input'), pb(pre + '.Input'), ew(pre + '.Recurrent_Gates'),
-                                                     ew(pre + '.Recurrent_Candidate')]
-                    else:
-                        pre = f'{tier}.LSTM{k}.Step'
-                        self.layers[(tag, k - 1)] = [ew(pre + '.Input'), lib.param(pre + '.b').detach().contiguous(),
-                                                     ew(pre + '.Recurrent_Gates')]
+                        layer.append(ew(nm['candidate']))
+                    self.layers[(tag, k)] = layer
+                if self.skip:
+                    self.outskips[tag] = ([ew(n) for n in outskips], lib.param(outskip_bias).detach().contiguous())
             if single:
                 for tag in ('big', 'frm'):
                     U_, bU_, Wg_, Wc_ = self.layers[(tag, 0)]
@@ -172,6 +184,8 @@ class DeviceGenerator:
         _lib.call('samplernn_generate_create', C.byref(d), C.byref(self.plan))
         if 0.0 < self.top_p < 1.0:  # (the descriptor has no word for it; off is a new plan's state)
             _lib.call('samplernn_generate_set_top_p', self.plan, C.c_float(self.top_p))
+        if self.skip:
+            self.set_skip_stacks()
         self.persistent = bool(_lib.load().samplernn_generate_is_persistent(self.plan))
         # row groups of 32 streams per launch of that kernel (PARROT_SR_PERSIST_GROUPS lifts the limit of one); 0: launches
         self.persist_groups = int(_lib.load().samplernn_generate_persist_groups(self.plan))
@@ -190,6 +204,25 @@ class DeviceGenerator:
             self.ws['utt_top_k'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int32)
             self.ws['utt_top_p'] = torch.zeros(n_frames, batch, **f)
             self.set_utterance_draws()
+
+    def set_skip_stacks(self):
+        """Hands the plan the out-skip matrices, their bias and the [B, DIM] scratch of the summed output per tier
+        (samplernn_generate_set_skip_stacks); refused (HipCallError) once the plan has run."""
+        _lib.call('samplernn_generate_set_skip_stacks', self.plan, C.byref(self.skip_struct()))
+
+    def skip_struct(self):
+        """The SampleRnnSkipStacks of this plan's model; the scratch buffers live in the workspace."""
+        s = _lib.SampleRnnSkipStacks()
+        for tag in ('big', 'frm'):
+            mats, bias = self.outskips[tag]
+            for k, m in enumerate(mats):
+                getattr(s, tag + '_S')[k] = m.data_ptr()
+            setattr(s, tag + '_bS', bias.data_ptr())
+            key = tag + '_skip_sum'
+            if key not in self.ws:
+                self.ws[key] = torch.zeros(self.B, config().DIM, device=bias.device, dtype=torch.float32)
+            setattr(s, tag + '_sum', self.ws[key].data_ptr())
+        return s
 
     def set_utterance_draws(self):
         """Hands the plan its per-utterance seed, temperature, top_k and top_p arrays; refused (HipCallError) once the plan

@@ -13,6 +13,41 @@ def config():
     return three_tier
 
 
+SKIP_SWITCH = "PARROT_SR_SKIP_STACKS"
+
+
+def skip_stacks_enabled():
+    """PARROT_SR_SKIP_STACKS (csrc/switches.h), read when called: 1 = the device-resident loop takes skip-connection
+    stacks."""
+    from ...utils import env_int
+    return env_int(SKIP_SWITCH, 0) != 0
+
+
+def stack_param_names(tier, rnn_type, n_rnn, skip_conn):
+    """The reference's names of a tier's RNN stack ('BigFrameLevel' / 'FrameLevel'; ops.py:612-777, 823-989), no device:
+    (layers, outskips, outskip_bias).  layers[k-1] = the Linear names (each has '.W0' and, under weight norm, '.g0') and the
+    bias parameter of layer k: dict(input=, gates=, candidate= (GRU only), bias=) -- GRU: '<Input>.b', LSTM: '<Step>.b'.
+    With skip_conn the layers above the first are '<tier>.GRU<k>+inpskip' / '<tier>.LSTM<k>+inpskip' (their Input is
+    [2 DIM, N]: h_{k-1} rows first, then the stack's input), outskips[k-1] = '<tier>.GRU.outskip<k>y' /
+    '<tier>.LSTM<k>.outskip<k>y' and outskip_bias = the first one's '.b', the only one there is; without it outskips is
+    empty and outskip_bias None."""
+    if rnn_type not in ('GRU', 'LSTM'):
+        raise ValueError("rnn_type must be 'GRU' or 'LSTM', got %r" % (rnn_type,))
+    if skip_conn and n_rnn < 2:
+        raise ValueError("a single-layer stack has no skip connections")
+    lstm = rnn_type == 'LSTM'
+    layers, outskips = [], []
+    for k in range(1, int(n_rnn) + 1):
+        step = '%s.%s%d%s.Step' % (tier, rnn_type, k, '+inpskip' if skip_conn and k > 1 else '')
+        names = dict(input=step + '.Input', gates=step + '.Recurrent_Gates', bias=step + ('.b' if lstm else '.Input.b'))
+        if not lstm:
+            names['candidate'] = step + '.Recurrent_Candidate'
+        layers.append(names)
+        if skip_conn:
+            outskips.append('%s.LSTM%d.outskip%dy' % (tier, k, k) if lstm else '%s.GRU.outskip%dy' % (tier, k))
+    return layers, outskips, (outskips[0] + '.b' if skip_conn else None)
+
+
 _M64 = (1 << 64) - 1
 DRAW_K1, DRAW_K2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9
 DRAW_MODES = {'sequential': 0, 'scan': 1}

@@ -202,6 +202,7 @@ from ...generation.inputs import (DRAW_K1, DRAW_K2, DRAW_MODES, _M64, _per_utter
                                   top_p_code, unpack_samples, utterance_draw_u01, utterance_seed)
 from ...generation.inputs import (_per_utterance_prompts, build_packed_prompts, forced_array,  # noqa: E402,F401
                                   unpack_log_probs)
+from ...generation.inputs import skip_stacks_enabled, stack_param_names  # noqa: E402,F401
 from ...generation.device import DeviceGenerator  # noqa: E402
 from ...generation.serving import (StreamingGenerator, generate_packed, generate_stream,  # noqa: E402,F401
                                    score_utterances)
@@ -234,7 +235,9 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
                               use_device_loop=True, pack_streams=0, stream_frames=0, utterance_seed=None,
                               draw_mode='sequential', top_k=0, top_p=0.0):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
-    (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.
+    (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.  Models with
+    skip-connection stacks (SKIP_CONN) take the device loop with PARROT_SR_SKIP_STACKS=1 and the literal loop, with its
+    own limits (no seeds, truncation, packing or streaming), without it.
 
     pack_streams = N > 0 with features_length given: row i's first features_length[i] frames form utterance i, the
     utterances run through generate_packed on N streams and the wav files are written from the returned pieces (the
@@ -258,7 +261,8 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
     in all three modes; 0 (default) or >= 1: no nucleus.  An active top_p needs the device loop -- the literal
     three-function loop refuses it --; a negative one or a NaN is a ValueError."""
     total_time = time()
-    device_loop = use_device_loop and not SKIP_CONN  # (the device loop does not take the skip-connection stacks)
+    # (the device loop takes skip-connection stacks only with PARROT_SR_SKIP_STACKS=1, read here at call time)
+    device_loop = use_device_loop and (not SKIP_CONN or (_inputs.skip_stacks_enabled() and N_RNN >= 2))
     if draw_mode_code(draw_mode) != 0 and not device_loop:
         raise ValueError("draw_mode='scan' needs the device-resident generator")
     if top_k_code(top_k) != 0 and not device_loop:

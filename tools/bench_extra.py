@@ -10,7 +10,7 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
                                          samplernn_cfg5, samplernn_groups, samplernn_packed, samplernn_stream,
                                          samplernn_utt_draws, samplernn_draw_scan, samplernn_top_k, samplernn_top_p,
-                                         samplernn_forced, mulaw)
+                                         samplernn_forced, samplernn_skip, mulaw)
   bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
                                          SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
                                          kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
@@ -77,6 +77,15 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          --parent-lib (the parent commit's libparrot_hip.so) the default plan of both
                                          libraries at temperature 0 and 1 in the same alternation, bit identity included;
                                          the result also goes to FILE (default profiles/samplernn_forced.json)
+  bench_extra.py --only samplernn_skip [--reps N] [--skip-json FILE] [--parent-lib FILE]
+                                         SampleRNN at D = 1024 and B = 32 with PARROT_SR_SKIP_STACKS=1: a (GRU, 2) model with
+                                         skip connections on the device loop (8000 samples per stream) against the literal
+                                         three-function loop on the same model (160 samples per stream), the same plan against
+                                         a (GRU, 2) plan without skip connections, and the default single-GRU plan at
+                                         temperature 0 and 1; N alternations in one process, each with its spread; with
+                                         --parent-lib (the parent commit's libparrot_hip.so) the default plan of both
+                                         libraries in the same alternation, bit identity included; the result also goes to
+                                         FILE (default profiles/samplernn_skip.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -101,7 +110,7 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_forced", "mulaw")
+       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_forced", "samplernn_skip", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1127,6 +1136,149 @@ if "samplernn_forced" in only:
             "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
             "t0": pair("argmax"), "t1": pair("sequential_t1")}
     record("samplernn_forced", "--forced-json", res)
+
+# ---- SampleRNN D=1024, B=32: skip-connection stacks on the device loop (PARROT_SR_SKIP_STACKS=1,
+# samplernn_generate_set_skip_stacks) -- a (GRU, 2) model with skip connections on the device loop and on the literal
+# three-function loop, a (GRU, 2) model without them (the price of the extra K segments and the out-skip job), and the default
+# single-GRU plan at temperature 0 and 1; with --parent-lib, that default plan against the parent commit's library.  All
+# plans alive in one process and run alternately, as samplernn_forced; the three models' parameters are swapped in and out of
+# the registry outside the timed region (a plan reads the learned h0 from it when a run starts).
+if "samplernn_skip" in only:
+    import contextlib
+    import ctypes
+    import io
+    from parrot_amd import _lib as plib
+    from parrot_amd.sampleRNN import lib as slib
+    from parrot_amd.sampleRNN.models.conditional import three_tier as tt
+    os.environ["PARROT_SR_SKIP_STACKS"] = "1"
+    T, T_LIT, SEED, reps = 101, 3, 234, int(_arg("--reps", "5"))
+    feats = torch.randn(T, 32, 63, generator=g).numpy()
+    MODELS = {"skip_gru2": dict(RNN_TYPE='GRU', N_RNN=2, SKIP_CONN=True), "plain_gru2": dict(RNN_TYPE='GRU', N_RNN=2, SKIP_CONN=False),
+              "default": dict(RNN_TYPE='GRU', N_RNN=1, SKIP_CONN=False)}
+    registry = {}
+
+    def select(model):
+        """The model's configuration and parameters in place (created with the reference initialisation the first time)."""
+        slib._params.clear()
+        tt.configure(DIM=1024, EMB_SIZE=256, **MODELS[model])
+        if model in registry:
+            slib._params.update(registry[model])
+            return
+        slib.set_device(dev)
+        n = MODELS[model]["N_RNN"]
+        seq = torch.randint(0, 256, (2, 160 + 80), generator=g).to(dev)
+        with torch.no_grad():
+            tt.compute_cost(seq, torch.randn(2, 2, 63, device=dev), torch.zeros(2, n, 1024, device=dev),
+                            torch.zeros(2, n, 1024, device=dev), 1, torch.ones(2, 240, device=dev))
+        registry[model] = slib.named_params()
+
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            if hasattr(parent_lib, name):  # (the parent has no samplernn_generate_set_skip_stacks: its plans never call it)
+                fn = getattr(parent_lib, name)
+                fn.restype = res_
+                fn.argtypes = args_
+
+    @contextlib.contextmanager
+    def under(which):  # every call of a plan goes to the library that made it
+        plib._lib = which
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+
+    def plan(model, which=this_lib, **kw):
+        select(model)
+        with under(which):
+            return tt.DeviceGenerator(32, T, seed=SEED, **kw)
+
+    # name: (model, plan or None = the literal loop, its library)
+    plans = {"skip_gru2_device": ("skip_gru2", plan("skip_gru2", temperature=0.0), this_lib),
+             "skip_gru2_literal": ("skip_gru2", None, this_lib),
+             "plain_gru2_device": ("plain_gru2", plan("plain_gru2", temperature=0.0), this_lib),
+             "argmax": ("default", plan("default", temperature=0.0), this_lib),
+             "sequential_t1": ("default", plan("default", temperature=1.0), this_lib)}
+    if parent_lib is not None:
+        plans["parent_argmax"] = ("default", plan("default", which=parent_lib, temperature=0.0), parent_lib)
+        plans["parent_sequential_t1"] = ("default", plan("default", which=parent_lib, temperature=1.0), parent_lib)
+        # (a second plan of each kind, created in the other order: the floor under any difference between the libraries)
+        plans["argmax_again"] = ("default", plan("default", temperature=0.0), this_lib)
+        plans["sequential_t1_again"] = ("default", plan("default", temperature=1.0), this_lib)
+        plans["parent_sequential_t1_again"] = ("default", plan("default", which=parent_lib, temperature=1.0), parent_lib)
+        plans["parent_argmax_again"] = ("default", plan("default", which=parent_lib, temperature=0.0), parent_lib)
+    assert plans["skip_gru2_device"][1].skip and plans["skip_gru2_device"][1].persistent
+    assert all(gen is None or gen.persist_groups == 1 for _, gen, _ in plans.values())
+    nsamp = {k: ((T if gen is not None else T_LIT) - 1) * 80 for k, (_, gen, _) in plans.items()}
+    times, samples = {k: [] for k in plans}, {}
+    keys = list(plans)
+    for rep_ in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+        for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:  # (no plan always runs behind the same other one)
+            model, gen, which = plans[k]
+            select(model)
+            with under(which):
+                if gen is None:
+                    fns = tt.getting_generation_functions()
+                    with contextlib.redirect_stdout(io.StringIO()):
+                        torch.cuda.synchronize(); t0 = time.time()
+                        s = tt.generate_and_save_samples("bench", None, feats[:T_LIT], None, 0., *fns, temperature=0.0,
+                                                         use_device_loop=False)
+                        torch.cuda.synchronize(); dt = time.time() - t0
+                    samples[k] = np.asarray(s).copy()
+                else:
+                    torch.cuda.synchronize(); t0 = time.time()
+                    s = gen.generate(feats)
+                    torch.cuda.synchronize(); dt = time.time() - t0
+                    samples[k] = s.cpu().numpy().copy()
+            if rep_:
+                times[k].append(dt)
+    for _, gen, which in plans.values():
+        if gen is not None:
+            with under(which):
+                gen.close()
+    slib._params.clear()
+    tt.configure(DIM=1024, EMB_SIZE=256, RNN_TYPE='GRU', N_RNN=1, SKIP_CONN=False)
+    us = {k: [1e6 * dt / nsamp[k] for dt in v] for k, v in times.items()}
+    med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+    spread = {k: max(v) - min(v) for k, v in us.items()}
+    lit, devs = samples["skip_gru2_literal"], samples["skip_gru2_device"][:, :80 * T_LIT]
+    res = {"dim": 1024, "streams": 32, "alternations": reps, "samples_per_stream": nsamp,
+           "timed": "call to device idle (host-side input copies included); the literal loop runs %d frames per call, the "
+                    "device plans %d" % (T_LIT - 1, T - 1),
+           "runs": {k: {"us_per_sample_step": [round(x, 3) for x in us[k]], "us_per_sample_step_median": round(med[k], 3),
+                        "spread_max_minus_min": round(spread[k], 3)} for k in plans},
+           "skip_gru2_device_loop_against_literal_loop": {
+               "device_us": round(med["skip_gru2_device"], 3), "literal_us": round(med["skip_gru2_literal"], 3),
+               "sum_of_the_two_spreads_us": round(spread["skip_gru2_device"] + spread["skip_gru2_literal"], 3),
+               "literal_over_device": round(med["skip_gru2_literal"] / med["skip_gru2_device"], 1),
+               "greedy_rows_identical_over_the_literal_loops_frames": int(sum(np.array_equal(a, b) for a, b in zip(lit, devs))),
+               "rows": int(lit.shape[0])},
+           "price_of_the_skip_connections_gru2": {
+               "skip_us": round(med["skip_gru2_device"], 3), "plain_us": round(med["plain_gru2_device"], 3),
+               "skip_minus_plain_us": round(med["skip_gru2_device"] - med["plain_gru2_device"], 3),
+               "sum_of_the_two_spreads_us": round(spread["skip_gru2_device"] + spread["plain_gru2_device"], 3)},
+           "not_measured": ["row groups", "the streaming generator end to end", "LSTM skip stacks at D = 1024",
+                            "deeper stacks (N_RNN 3 .. 5)", "the launch path's timing"]}
+    if parent_lib is not None:
+        def pair(t):  # the standing bar (the two first plans, the sum of their spreads) and the four plans' picture beside it
+            a, b = (med[t], med[t + "_again"]), (med["parent_" + t], med["parent_" + t + "_again"])
+            both = spread[t] + spread["parent_" + t]
+            return {"this_us": [round(x, 3) for x in a], "parent_us": [round(x, 3) for x in b],
+                    "this_minus_parent_us": round(a[0] - b[0], 3), "sum_of_the_two_spreads_us": round(both, 3),
+                    "bar_default_within_the_sum_of_both_spreads": bool(abs(a[0] - b[0]) <= both),
+                    "mean_of_two_plans_this_minus_parent_us": round(sum(a) / 2 - sum(b) / 2, 3),
+                    "largest_difference_between_two_plans_of_one_library_us": round(max(abs(a[0] - a[1]), abs(b[0] - b[1])), 3)}
+        res["default_path_against_parent_commit"] = {
+            "how": "this build and the parent commit's library loaded in one process, two plans of each per temperature (the "
+                   "second pair created in the other order), all in the same alternation; the bar compares the first plan of "
+                   "each library against the sum of their spreads (max - min over the alternations)",
+            "bit_identical_t0": bool(np.array_equal(samples["argmax"], samples["parent_argmax"])),
+            "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
+            "t0": pair("argmax"), "t1": pair("sequential_t1")}
+    record("samplernn_skip", "--skip-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
