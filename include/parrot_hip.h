@@ -1013,6 +1013,31 @@ int samplernn_generate_set_top_p(void* plan, float top_p);
  * samplernn_generate_set_utterance_draws, and refused once the plan has run (PARROT_ERR_BADARG for either, and for a null
  * plan or pointer; no device call); PARROT_ERR_UNSUPPORTED when Q > 256.  Without it every utterance takes the plan's top_p. */
 int samplernn_generate_set_utterance_top_p(void* plan, const float* utt_top_p);
+/* The plan's min_p (a new plan's is 0.0 = off).  For one draw with float32 logits lg[0..Q-1], temperature T > 0 and
+ * 0 < min_p <= 1:
+ *   1. e_q = expf((lg_q - best) / T) as the draw computes it, in float32; a code is kept iff e_q >= min_p, a float32 compare.
+ *      The argmax has e = 1.0f exactly, so the set is never empty; min_p = 1 keeps exactly the codes whose term is 1.0f (the
+ *      maxima);
+ *   2. composition: the kept set is top_k's set, intersected with the nucleus of top_k's set, intersected with min-p's set.
+ *      The nucleus is computed exactly as without min_p; min-p is applied last (temperature -> top-k -> top-p -> min-p).
+ *      e_q / e_max does not change under renormalisation, so min-p commutes with top-k.  In exact arithmetic each of the
+ *      three sets is a prefix of the order "logit descending, index ascending", so the intersection is the shortest of them:
+ *      a draw with any combination is a draw with top_k = m;
+ *   3. every code outside the kept set gets the term 0.0f in the same sums, with the same uniform, in both draw modes, and
+ *      the fall-through picks go to the highest kept code, exactly as for top_k.
+ *   The kept set equals the exact one whenever every ratio e_q / e_max lies farther than 2^-18 (relative) from min_p.
+ *   0.0: off, and the pick runs the instructions of a build without it (the kernels treat any value outside (0, 1] as off).
+ *   < 0, > 1 or NaN: PARROT_ERR_BADARG, as for a null plan and for a plan that has run (the period graphs hold the value);
+ *   active with Q > 256: PARROT_ERR_UNSUPPORTED.  At temperature <= 0 the pick is the argmax and min_p is ignored.  No device
+ *   call. */
+int samplernn_generate_set_min_p(void* plan, float min_p);
+/* Per-utterance min_p.  utt_min_p [T][B] (float): device memory, indexed and owned like utt_top_p; row f holds the min_p of
+ * an utterance that begins at big frame f (outside (0, 1]: off).  The entry of a stream takes it wherever it takes the seed,
+ * the temperature, top_k and top_p, so the four rows of one team of the persistent kernel may mix every kind of truncation.
+ * Valid only after samplernn_generate_set_utterance_draws, and refused once the plan has run (PARROT_ERR_BADARG for either,
+ * and for a null plan or pointer; no device call); PARROT_ERR_UNSUPPORTED when Q > 256.  Without it every utterance takes
+ * the plan's min_p. */
+int samplernn_generate_set_utterance_min_p(void* plan, const float* utt_min_p);
 /* Forced samples (teacher forcing, priming).  forced [B][BFS * T] (int): device memory, owned by the caller for the plan's
  * life, indexed exactly like `samples` -- the same ring and the same buffer index t; a run in segments restages it per
  * segment, as it restages `features`.  Where forced[b][t] lies in 0 .. Q-1 the sample step at buffer index t of stream b
@@ -1030,6 +1055,17 @@ int samplernn_generate_set_forced(void* plan, const int* forced);
  * whatever the step draws with; the quantity the training cost averages.  Slot 0 is not written.  PARROT_ERR_BADARG for a
  * null plan or pointer and for a plan that has run; no device call. */
 int samplernn_generate_set_log_probs(void* plan, float* logp);
+/* What each draw kept.  draw_logp [B][BFS * T] (float) and kept [B][BFS * T] (int): device memory, owned and indexed like
+ * `logp`; both required.  Every sample step writes kept[b][t] = the size of the set its pick was drawn from -- 1 on an argmax
+ * step (temperature <= 0), Q on an untruncated draw, else the number of codes top_k, top_p and min_p left; a forced step
+ * reports the set its pick was drawn from, like any other -- and draw_logp[b][t] = (logits[s] - max) / T - log(sum of the kept
+ * codes' terms), s = the code the step wrote to `samples`: the natural logarithm, in float32, of the probability of s under
+ * the distribution the step drew from.  -inf where s is outside the kept set (a forced code the truncation dropped, or a
+ * forced code that is not the argmax on an argmax step), 0 for the argmax on an argmax step.  The mass is a fixed tree of
+ * float32 adds, so the same logits and settings give the same bits.  Slot 0 is not written.  On the launch path: any Q
+ * untruncated, Q <= 256 truncated.  Independent of every draw setting, of forced samples and of log_probs.
+ * PARROT_ERR_BADARG for a null plan or pointer and for a plan that has run; no device call. */
+int samplernn_generate_set_draw_stats(void* plan, float* draw_logp, int* kept);
 /* Skip-connection stacks (--skip_conn True: Graves' stacks, sampleRNN/lib/ops.py:650-695, 861-880).  In such a stack every
  * layer above the first reads [h_{k-1} ; x], x = the stack's input, and the stack's output is sum_k h_k . S_k + bS instead
  * of the top layer's state.  The descriptor does not change; a plan with n_rnn >= 2 takes the rest through this struct:

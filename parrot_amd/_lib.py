@@ -272,6 +272,9 @@ SIGNATURES = {
     "samplernn_generate_set_utterance_top_k": (_i, [_vp, _vp]),
     "samplernn_generate_set_top_p": (_i, [_vp, C.c_float]),
     "samplernn_generate_set_utterance_top_p": (_i, [_vp, _vp]),
+    "samplernn_generate_set_min_p": (_i, [_vp, C.c_float]),
+    "samplernn_generate_set_draw_stats": (_i, [_vp, _vp, _vp]),
+    "samplernn_generate_set_utterance_min_p": (_i, [_vp, _vp]),
     "samplernn_generate_set_forced": (_i, [_vp, _vp]),
     "samplernn_generate_set_log_probs": (_i, [_vp, _vp]),
     "samplernn_generate_set_skip_stacks": (_i, [_vp, C.POINTER(SampleRnnSkipStacks)]),

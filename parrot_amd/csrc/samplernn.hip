@@ -62,16 +62,22 @@ __global__ __launch_bounds__(256) void sr_embed_sum_kernel(const int* __restrict
 // samples[b][t] = argmax_q logits[b][q] (lowest index on ties, like numpy / Theano argmax), or a
 // temperature-scaled multinomial draw from a counter-based generator when temperature > 0 -- among all Q codes, or among
 // the top_k most likely ones (SampleRnnGenDesc::top_k: terms 0.0f outside the kept set, same sums, same uniform), or among
-// the nucleus of those (samplernn_generate_set_top_p: the shortest prefix of the same order with top_p of their mass).
+// the nucleus of those (samplernn_generate_set_top_p: the shortest prefix of the same order with top_p of their mass), and of
+// what both left the codes whose term is >= min_p (samplernn_generate_set_min_p).
 // forced (samplernn_generate_set_forced, or null): where forced[b][t] is a code in 0 .. Q-1 it is the sample, whatever was
 // picked; any other value leaves the pick.  logp (samplernn_generate_set_log_probs, or null): logp[b][t] = the natural
 // logarithm of softmax(logits)[sample] at temperature 1, without truncation.  Both through emit(), which every branch
-// ends in; both for any Q.
+// ends in; both for any Q.  dlogp / kept (samplernn_generate_set_draw_stats, or both null): what the step drew from -- the
+// size of the kept set (1 on an argmax step, Q untruncated) and the log of the sample's probability under the draw's own
+// temperature and kept set (-inf outside it).  Through emit() where the set is all codes or the argmax (any Q), through
+// stats() by wave 0 behind a truncated draw (Q <= 256): the kept terms' mass is srp_wave_sum's fixed tree.
 __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ logits, int Q, int* __restrict__ samples,
                                                       int len, const int* __restrict__ tbase, int toff, float temperature,
                                                       unsigned long long seed, const unsigned long long* __restrict__ origin,
                                                       const SrUttDraw* __restrict__ utt, int draw_mode, int top_k,
-                                                      float top_p, const int* __restrict__ forced, float* __restrict__ logp) {
+                                                      float top_p, float min_p, const int* __restrict__ forced,
+                                                      float* __restrict__ logp, float* __restrict__ dlogp,
+                                                      int* __restrict__ kept) {
     __shared__ float sv[256];
     __shared__ int si[256];
     __shared__ float se[256];
@@ -82,15 +88,45 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
     const int fv = forced ? forced[(size_t)b * len + t] : -1;
     const bool is_forced = (unsigned)fv < (unsigned)Q;
     float lse = 0.f;  // log sum_q exp(logits[q] - max), with logp only
+    float dlse = 0.f;  // log sum_q exp((logits[q] - max) / temperature), with dlogp on an untruncated draw only
+    bool full = true;  // the step draws among all codes or takes the argmax: emit() writes the statistics
     auto emit = [&](int pick) {
         const int s = is_forced ? fv : pick;
         samples[(size_t)b * len + t] = s;
         if (logp) logp[(size_t)b * len + t] = lg[s] - sv[0] - lse;
+        if (dlogp && full) {
+            const bool greedy = temperature <= 0.f;
+            dlogp[(size_t)b * len + t] = greedy ? (s == si[0] ? 0.f : -INFINITY) : (lg[s] - sv[0]) / temperature - dlse;
+            kept[(size_t)b * len + t] = greedy ? 1 : Q;
+        }
+    };
+    // the statistics of a truncated draw, by all of wave 0 behind it: lane `lane` holds n <= 4 codes code(j) with kept bits
+    // keep, `pick` is lane 0's
+    auto stats = [&](unsigned keep, int n, int pick, auto code) {
+        if (!dlogp) return;
+        const int s = __builtin_amdgcn_readfirstlane(is_forced ? fv : pick);
+        float m = 0.f;
+        int cnt = 0;
+        bool in = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool k = j < n && ((keep >> j) & 1u);
+            const float e = k ? expf((lg[min(code(j), Q - 1)] - sv[0]) / temperature) : 0.f;
+            m = j == 0 ? e : __fadd_rn(m, e);
+            cnt += (int)__popcll(__ballot(k));
+            in = in || (k && code(j) == s);
+        }
+        const float tot = srp_wave_sum(m);
+        const bool any = __ballot(in) != 0ull;
+        if (threadIdx.x == 0) {
+            dlogp[(size_t)b * len + t] = any ? (lg[s] - sv[0]) / temperature - logf(tot) : -INFINITY;
+            kept[(size_t)b * len + t] = cnt;
+        }
     };
     // key = what the draw's counter is hashed with: the plan's seed and the stream, or (per-utterance entries, a uniform
     // branch) the utterance's seed alone, with its own temperature and its counter taken back by the run index of its prefix
     unsigned long long key = seed ^ (0xBF58476D1CE4E5B9ull * (unsigned long long)(b + 1)), off = 0;
-    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; top_k = utt[b].top_k; top_p = utt[b].top_p; }
+    if (utt) { key = utt[b].seed; off = utt[b].off; temperature = utt[b].temperature; top_k = utt[b].top_k; top_p = utt[b].top_p; min_p = utt[b].min_p; }
     // top-k truncation (a uniform branch of both draws; create admits it for Q <= 256 only): wave 0 selects the kept set with
     // the persistent kernel's helper, four codes per lane at most; off, a draw runs the instructions it always ran
     top_k = __builtin_amdgcn_readfirstlane(top_k);
@@ -98,7 +134,10 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
     // the nucleus, behind top-k when both are active (the setters admit it for Q <= 256 only): srp_topp_keep, same lanes
     top_p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(top_p)));
     const bool use_p = top_p > 0.f && top_p < 1.f && Q <= 256;
-    const bool trunc = use_k || use_p;
+    // min-p, behind both (Q <= 256 only, like them): srp_minp_keep on the same lanes' terms
+    min_p = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(min_p)));
+    const bool use_m = min_p > 0.f && min_p <= 1.f && Q <= 256;
+    const bool trunc = use_k || use_p || use_m;
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int q = tid; q < Q; q += 256) {
@@ -131,6 +170,20 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
         if (tid == 0) emit(si[0]);
         return;
     }
+    full = !trunc;
+    if (dlogp && full) {  // (a uniform branch) the mass of all codes at the draw's temperature, the same fixed tree
+        __syncthreads();  // (se may still be read for lse)
+        const float mx = sv[0];
+        float e = 0.f;
+        for (int q = tid; q < Q; q += 256) e += expf((lg[q] - mx) / temperature);
+        se[tid] = e;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) se[tid] += se[tid + s];
+            __syncthreads();
+        }
+        dlse = logf(se[0]);
+    }
     if (draw_mode == 1) {
         // wave-parallel draw (a uniform branch; create has checked that Q is a multiple of 64): wave 0, lane l owns the
         // Q / 64 contiguous codes from l Q / 64 on; same terms, key, counter and uniform as the walk below
@@ -151,9 +204,18 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
                     for (int j = 0; j < 4; ++j) ek[j] = (keep >> j) & 1u ? expf((lg[min(idx[j], Q - 1)] - mx) / temperature) : 0.f;
                     keep &= srp_topp_keep<4>(f, idx, ek, top_p);
                 }
+                if (use_m) {
+                    float ek[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) ek[j] = (keep >> j) & 1u ? expf((lg[min(idx[j], Q - 1)] - mx) / temperature) : 0.f;
+                    keep &= srp_minp_keep<4>(ek, min_p);
+                }
                 const int lk = keep ? n * tid + 31 - __clz((int)keep) : -1;
                 pick = srp_scan_draw<true>([&](int j) { return (keep >> j) & 1u ? expf((lg[n * tid + j] - mx) / temperature) : 0.f; },
                                            n, tid, u01, lk);
+                if (tid == 0) emit(pick);
+                stats(keep, n, pick, [&](int j) { return n * tid + j; });
+                return;
             } else {
                 pick = srp_scan_draw([&](int j) { return expf((lg[n * tid + j] - mx) / temperature); }, n, tid, u01);
             }
@@ -179,24 +241,31 @@ __global__ __launch_bounds__(256) void sr_pick_kernel(const float* __restrict__ 
                 for (int m = 0; m < 4; ++m) ek[m] = (keep >> m) & 1u ? expf((lg[min(idx[m], Q - 1)] - sv[0]) / temperature) : 0.f;
                 keep &= srp_topp_keep<4>(f, idx, ek, top_p);
             }
+            if (use_m) {
+                float ek[4];
+#pragma unroll
+                for (int m = 0; m < 4; ++m) ek[m] = (keep >> m) & 1u ? expf((lg[min(idx[m], Q - 1)] - sv[0]) / temperature) : 0.f;
+                keep &= srp_minp_keep<4>(ek, min_p);
+            }
             const int last = srp_topk_last<4>(keep, idx);
 #pragma unroll
             for (int m = 0; m < 4; ++m) si[idx[m]] = (int)((keep >> m) & 1u);
             __builtin_amdgcn_wave_barrier();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            int pick = last;
             if (tid == 0) {
                 const float mx = sv[0];
                 float tot = 0.f;
                 for (int q = 0; q < Q; ++q) tot += si[q] ? expf((lg[q] - mx) / temperature) : 0.f;
                 const float u = srp_u01(key, origin[0] + (unsigned long long)(t + 1) - off) * tot;
                 float c = 0.f;
-                int pick = last;
                 for (int q = 0; q < Q; ++q) {
                     c += si[q] ? expf((lg[q] - mx) / temperature) : 0.f;
                     if (u < c) { pick = q; break; }
                 }
                 emit(pick);
             }
+            stats(keep, 4, pick, [&](int m) { return tid + 64 * m; });
         }
         return;
     }
@@ -260,7 +329,8 @@ __global__ void sr_tick_kernel(int* tbase, int inc, int set, unsigned long long*
 // tbase; a start flagged at frame 1 then rewrites the same values.
 __global__ __launch_bounds__(256) void sr_utt_init_kernel(SrUttDraw* __restrict__ utt, const unsigned long long* __restrict__ seed1,
                                                           const float* __restrict__ temp1, const int* __restrict__ top_k1,
-                                                          int top_k, const float* __restrict__ top_p1, float top_p, int B) {
+                                                          int top_k, const float* __restrict__ top_p1, float top_p,
+                                                          const float* __restrict__ min_p1, float min_p, int B) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     utt[b].seed = seed1[b];
@@ -268,7 +338,7 @@ __global__ __launch_bounds__(256) void sr_utt_init_kernel(SrUttDraw* __restrict_
     utt[b].temperature = temp1[b];
     utt[b].top_k = top_k1 ? top_k1[b] : top_k;  // (no array of the caller's: the plan's)
     utt[b].top_p = top_p1 ? top_p1[b] : top_p;
-    utt[b].pad = 0;
+    utt[b].min_p = min_p1 ? min_p1[b] : min_p;
 }
 
 // Segment boundary of a resumed run (samplernn_generate_run_segment, resume = 1): the first launch of the segment, outside
@@ -311,7 +381,7 @@ __global__ __launch_bounds__(256) void sr_resume_kernel(const SrResumeArgs a) {
 // the learned h0, its row of the next frame's gate product = h0 . Wg (the copy run() kept), and the carry of its team
 // invalidated (the other rows of the team then read their true history from `samples` too).  With per-utterance draws
 // the stream's entry becomes (utt_seed[f][b], run index of the prefix slot = origin + (f - 1) BFS, utt_temp[f][b],
-// utt_top_k[f][b] or the plan's top_k, utt_top_p[f][b] or the plan's top_p).  Rows without a flag are not touched.
+// utt_top_k[f][b] or the plan's top_k, utt_top_p[f][b] or the plan's top_p, utt_min_p[f][b] or the plan's min_p).  Rows without a flag are not touched.
 struct SrStartArgs {
     const int* starts; const int* tbase;
     int* samples;
@@ -325,6 +395,7 @@ struct SrStartArgs {
     const unsigned long long* origin;
     const int* utt_top_k; int top_k;  // [T][B] like utt_temp, or null: every utterance takes the plan's top_k
     const float* utt_top_p; float top_p;  // likewise (samplernn_generate_set_utterance_top_p, samplernn_generate_set_top_p)
+    const float* utt_min_p; float min_p;  // likewise (samplernn_generate_set_utterance_min_p, samplernn_generate_set_min_p)
 };
 
 __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
@@ -342,6 +413,7 @@ __global__ __launch_bounds__(256) void sr_start_kernel(const SrStartArgs a) {
         a.utt[b].temperature = a.utt_temp[(size_t)f * a.B + b];
         a.utt[b].top_k = a.utt_top_k ? a.utt_top_k[(size_t)f * a.B + b] : a.top_k;
         a.utt[b].top_p = a.utt_top_p ? a.utt_top_p[(size_t)f * a.B + b] : a.top_p;
+        a.utt[b].min_p = a.utt_min_p ? a.utt_min_p[(size_t)f * a.B + b] : a.min_p;
     }
 }
 
@@ -401,10 +473,16 @@ struct SrPlan {
     // the caller's [T][B] values (null: the plan's for all)
     float top_p = 0.f;
     const float* utt_top_p = nullptr;
+    // samplernn_generate_set_min_p / _set_utterance_min_p: likewise the plan's min_p (0: off) and the caller's [T][B] values
+    float min_p = 0.f;
+    const float* utt_min_p = nullptr;
     // samplernn_generate_set_forced / _set_log_probs: the caller's [B][BFS * T] arrays, indexed like d.samples (null: off).
     // Indexed by buffer index, so a resumed segment needs no state of theirs: the host stages them per segment, like features.
     const int* forced = nullptr;
     float* logp = nullptr;
+    // samplernn_generate_set_draw_stats: likewise, both or neither
+    float* dlogp = nullptr;
+    int* kept = nullptr;
     // samplernn_generate_set_skip_stacks: Graves' stacks (ops.py:650-695, 861-880).  Layer k >= 1 reads [h_{k-1} ; x] through
     // its [2D, N] Input matrix (slot 0 of big_L[k] / frm_L[k]) and the tier's output is sum_k h_k . S_k + bS.
     SampleRnnSkipStacks skip{};
@@ -626,6 +704,7 @@ struct SrPlan {
         a.utt = utt; a.utt_seed = utt_seed; a.utt_temp = utt_temp; a.origin = origin;
         a.utt_top_k = utt_top_k; a.top_k = d.top_k;
         a.utt_top_p = utt_top_p; a.top_p = top_p;
+        a.utt_min_p = utt_min_p; a.min_p = min_p;
         hipLaunchKernelGGL(sr_start_kernel, dim3(d.B), dim3(256), 0, st, a);
         return (int)hipGetLastError();
     }
@@ -714,8 +793,9 @@ struct SrPlan {
                 sa.t2tbl = t2tbl; sa.frame_out = d.frame_out; sa.ldf = FS * D;
                 sa.W3 = d.W3; sa.b3 = d.b3; sa.W4 = d.W4; sa.b4 = d.b4;
                 sa.logits = d.logits; sa.ws = d.persist_ws; sa.temperature = d.temperature; sa.seed = d.seed;
-                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode; sa.top_k = srp_trunc_word(d.top_k, top_p, d.Q); sa.top_p = top_p;
-                sa.forced = forced; sa.logp = logp;
+                sa.origin = origin; sa.utt = utt; sa.draw_mode = d.draw_mode; sa.top_k = srp_trunc_word(d.top_k, top_p, min_p, d.Q); sa.top_p = top_p;
+                sa.min_p = min_p;
+                sa.forced = forced; sa.logp = logp; sa.dlogp = dlogp; sa.kept = kept;
                 if (f + 1 < nfr && winu) {  // the next frame of this period: its big-tier share is already known
                     sa.next_in = pin; sa.next_Win = winu; sa.next_bias = nullptr;
                     sa.next_add = pbig + (size_t)(f + 1) * 3 * D; sa.next_ld_add = nfr * 3 * D; sa.next_n = 3 * D;
@@ -741,7 +821,7 @@ struct SrPlan {
                 SR_TRY(linear(d.o3, D, d.W4, nullptr, d.Q, d.b4, d.logits, 0, st));
                 hipLaunchKernelGGL(sr_pick_kernel, dim3(B), dim3(256), 0, st, d.logits, d.Q, d.samples, len, d.tbase, to,
                                    d.temperature, d.seed, (const unsigned long long*)origin, (const SrUttDraw*)utt, d.draw_mode,
-                                   d.top_k, top_p, forced, logp);
+                                   d.top_k, top_p, min_p, forced, logp, dlogp, kept);
             }
         }
         hipLaunchKernelGGL(sr_tick_kernel, dim3(1), dim3(64), 0, st, d.tbase, BFS, 0, (unsigned long long*)nullptr);
@@ -771,7 +851,8 @@ struct SrPlan {
             if (utt) {  // every stream's first utterance: row 1 of the caller's arrays, prefix in slot 0
                 hipLaunchKernelGGL(sr_utt_init_kernel, dim3(ceil_div(d.B, 256)), dim3(256), 0, st, utt, utt_seed + d.B,
                                    utt_temp + d.B, utt_top_k ? utt_top_k + d.B : (const int*)nullptr, d.top_k,
-                                   utt_top_p ? utt_top_p + d.B : (const float*)nullptr, top_p, d.B);
+                                   utt_top_p ? utt_top_p + d.B : (const float*)nullptr, top_p,
+                                   utt_min_p ? utt_min_p + d.B : (const float*)nullptr, min_p, d.B);
                 e = hipGetLastError();
                 if (e != hipSuccess) return (int)e;
             }
@@ -950,6 +1031,16 @@ int samplernn_generate_set_log_probs(void* plan, float* logp) {
     return 0;
 }
 
+// What each draw kept.  (No HIP call, like the two above.)
+int samplernn_generate_set_draw_stats(void* plan, float* draw_logp, int* kept) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !draw_logp || !kept) return PARROT_ERR_BADARG;
+    if (p->has_run) return PARROT_ERR_BADARG;
+    p->dlogp = draw_logp;
+    p->kept = kept;
+    return 0;
+}
+
 // Skip-connection stacks.  (No HIP call: the pointers are handed to the step jobs by the launches of the first run.)
 int samplernn_generate_set_skip_stacks(void* plan, const SampleRnnSkipStacks* skip) {
     SrPlan* p = static_cast<SrPlan*>(plan);
@@ -961,6 +1052,26 @@ int samplernn_generate_set_skip_stacks(void* plan, const SampleRnnSkipStacks* sk
         if (!skip->big_S[k] || !skip->frm_S[k]) return PARROT_ERR_BADARG;
     p->skip = *skip;
     p->has_skip = true;
+    return 0;
+}
+
+// The plan's min_p.  (No HIP call, like the nucleus.)
+int samplernn_generate_set_min_p(void* plan, float min_p) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !(min_p >= 0.f && min_p <= 1.f)) return PARROT_ERR_BADARG;  // (a NaN compares false)
+    if (p->has_run) return PARROT_ERR_BADARG;                             // the period graphs hold the arguments by value
+    if (min_p > 0.f && p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
+    p->min_p = min_p;
+    return 0;
+}
+
+// (no HIP call either: the pointer is handed to the kernels that fill the entries)
+int samplernn_generate_set_utterance_min_p(void* plan, const float* utt_min_p) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !utt_min_p || !p->utt) return PARROT_ERR_BADARG;  // only after samplernn_generate_set_utterance_draws
+    if (p->has_run) return PARROT_ERR_BADARG;
+    if (p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
+    p->utt_min_p = utt_min_p;
     return 0;
 }
 

@@ -73,6 +73,14 @@ struct SrpShared {
     // forced codes of the launch's steps for the group's rows (SrpArgs::forced; unused without), -1 = the step picks freely.
     // Behind everything else: the offsets of the fields above are the ones they had.
     int forced[SRP_ROWS][SRP_MAXHIST];
+    // the rows' min_p (samplernn_generate_set_min_p: the entries', or the plan's without entries), written by every prologue
+    float uminp[SRP_ROWS];
+    // the kept set of a truncated sequential draw as the ballots of the lanes' kept bits (word m, bit l: code l + 64 m), parked
+    // for the statistics behind the pick (SrpArgs::dlogp; srp_fx_kernel only)
+    unsigned long long ukeepm[SRP_ROWS][SRP_Q / 64];
+    // SrpArgs::dlogp / kept as the prologue parks them: read from here inside the step loop, not from the arguments
+    float* dlogp;
+    int* kept;
 };
 static_assert(sizeof(SrpShared) % 8 == 0, "SrpShared holds 64-bit words");
 
@@ -268,6 +276,19 @@ __device__ __forceinline__ unsigned srp_topp_keep(const unsigned (&f)[N], const 
     unsigned keep = 0;
 #pragma unroll
     for (int j = 0; j < N; ++j) keep |= t[j] > y ? 1u << j : 0u;
+    return keep;
+}
+
+// Min-p truncation of a draw (samplernn_generate_set_min_p): a code is kept iff its term e = expf((lg - max) / T), as the draw
+// computes it, is >= min_p -- the argmax's term is exactly 1.0f, so with 0 < min_p <= 1 the set is never empty.  e[j] = the
+// term of the lane's j-th code, 0.0f already in place of a code the truncations in front dropped (and of "no code"): 0 < min_p
+// fails those, so the result is the intersection.  min_p wave-uniform.  Returns the lane's kept codes, bit j.  N compares:
+// no rounds, no LDS, no cross-lane traffic.
+template <int N>
+__device__ __forceinline__ unsigned srp_minp_keep(const float (&e)[N], float min_p) {
+    unsigned keep = 0;
+#pragma unroll
+    for (int j = 0; j < N; ++j) keep |= e[j] >= min_p ? 1u << j : 0u;
     return keep;
 }
 

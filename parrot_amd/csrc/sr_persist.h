@@ -9,11 +9,13 @@
 // counter is the sample's index in the utterance's own buffer, wherever the utterance sits.  temperature <= 0: argmax.
 // top_k: the utterance's truncation (samplernn_generate_set_utterance_top_k; the plan's without); outside 1 .. Q-1: none.
 // top_p: its nucleus (samplernn_generate_set_utterance_top_p; the plan's without); not strictly between 0 and 1: none.
+// min_p: its min-p bar (samplernn_generate_set_utterance_min_p; the plan's without); outside (0, 1]: none.
 struct SrUttDraw {
     unsigned long long seed, off;
     float temperature; int top_k;
-    float top_p; int pad;
+    float top_p; float min_p;
 };
+static_assert(sizeof(SrUttDraw) == 32, "the kernels read an entry's fields at fixed byte offsets");
 
 struct SrpArgs {
     const int* tbase; int toff;        // first sample index of this launch: tbase[0] + toff
@@ -52,12 +54,15 @@ struct SrpArgs {
     int draw_mode;
     // SampleRnnGenDesc::top_k: a draw at temperature > 0 is taken among the k most likely codes (sr_common.h, srp_topk_keep);
     // 0: among all of them, by the instructions of the pick without this field.  With utt: the entry's top_k.  The launcher
-    // hands the kernel 0 for a value outside 1 .. Q-1, and sets SRP_NUCLEUS beside it when top_p is active: one word for the
-    // pick to test (srp_trunc_word).
+    // hands the kernel 0 for a value outside 1 .. Q-1, and sets SRP_NUCLEUS beside it when top_p is active and SRP_MINP when
+    // min_p is: one word for the pick to test (srp_trunc_word).
     int top_k;
     // samplernn_generate_set_top_p: a draw at temperature > 0 is taken among the nucleus of the codes top_k left (sr_common.h,
     // srp_topp_keep); active strictly between 0 and 1 (top_k then carries SRP_NUCLEUS).  With utt: the entry's top_p.
     float top_p;
+    // samplernn_generate_set_min_p: of the codes both left, a draw keeps those whose term is >= min_p (sr_common.h,
+    // srp_minp_keep); active in (0, 1] (top_k then carries SRP_MINP).  With utt: the entry's min_p.
+    float min_p;
     // samplernn_generate_set_forced: [B][len] like samples, or null.  Where forced[b][t] is a code in 0 .. Q-1 the step at
     // buffer index t of stream b computes its logits and its pick as always and then takes that code as the sample -- into
     // samples, the history of the following steps, the carry and the next frame's input; any other value (-1): the pick.
@@ -66,11 +71,18 @@ struct SrpArgs {
     // samplernn_generate_set_log_probs: [B][len] like samples, or null.  Every step writes the natural logarithm of the
     // model's probability (temperature 1, no truncation) of the sample it wrote: logits[s] - max - log(sum exp(logits - max)).
     float* logp;
+    // samplernn_generate_set_draw_stats: [B][len] both like samples, or both null.  Every step writes kept = the size of the
+    // set its pick was drawn from (1 on an argmax step, Q on an untruncated draw) and dlogp = the natural logarithm of the
+    // probability of the sample it wrote under the distribution it drew from: (logits[s] - max) / T - log(sum of the kept
+    // terms), -inf for a sample outside the kept set (a forced one), 0 for the argmax on an argmax step.
+    float* dlogp; int* kept;
 };
 
 constexpr int SRP_NUCLEUS = 1 << 16;  // in SrpArgs::top_k: the plan's top_p is active
-inline int srp_trunc_word(int top_k, float top_p, int Q) {
-    return (top_k > 0 && top_k < Q ? top_k : 0) | (top_p > 0.f && top_p < 1.f ? SRP_NUCLEUS : 0);
+constexpr int SRP_MINP = 1 << 17;     // ... and its min_p
+inline int srp_trunc_word(int top_k, float top_p, float min_p, int Q) {
+    return (top_k > 0 && top_k < Q ? top_k : 0) | (top_p > 0.f && top_p < 1.f ? SRP_NUCLEUS : 0) |
+           (min_p > 0.f && min_p <= 1.f ? SRP_MINP : 0);
 }
 
 // PARROT_SR_PERSIST_GROUPS (switches.h): the largest number of row groups a launch may take, clamped to 1 .. 8

@@ -20,8 +20,8 @@
 //     this kernel, of which 2.4 us were the four serialised L2 round trips;
 //   * the 4 streams of a team ride in the 4 lanes of an f32x4, the products run on the vector ALUs (a 4-row tile wastes
 //     3/4 of an MFMA; v_pk_fma_f32 has the same f32 peak as the matrix pipe);
-//   * the pick (argmax with lowest-index ties, or the seeded inverse-CDF draw, among all codes, the top_k most likely or
-//     their nucleus: sr_common.h, srp_topk_keep and srp_topp_keep) is recomputed by every CU of the team from
+//   * the pick (argmax with lowest-index ties, or the seeded inverse-CDF draw, among all codes, the top_k most likely, their
+//     nucleus or the codes above the min-p bar: sr_common.h, srp_topk_keep, srp_topp_keep and srp_minp_keep) is recomputed by every CU of the team from
 //     the team's logits, so the new sample index is local knowledge everywhere and the embedding gather of the next step
 //     needs no further hand-off.
 // One launch covers the FRAME_SIZE steps between two frame-tier steps; the tiers above stay on the launch path.
@@ -51,13 +51,14 @@ namespace {
 // below holds per group.  MG = false is the one-group kernel, instruction for instruction what it was before the loop
 // existed (srp_launch takes it whenever ngroups == 1); profiles/samplernn_groups_kernel_resources.txt has both sets.
 //
-// FX = true (srp_fx_kernel<D, MG>, taken when SrpArgs::forced or SrpArgs::logp is set): the body that can take a step's
-// sample from the caller and that writes the log-probability of every sample.  Kernels of their own, not branches of the
+// FX = true (srp_fx_kernel<D, MG>, taken when SrpArgs::forced, SrpArgs::logp or SrpArgs::dlogp is set): the body that can take
+// a step's sample from the caller, that writes the log-probability of every sample and that writes what every step drew from.  Kernels of their own, not branches of the
 // one kernel: FX = false (srp_kernel<D, MG>, under the name it always had) compiles no line of either facility, so a plan
 // that uses neither runs the step loop it ran before they existed (the sequential walk has measured 1.9 us per step slower
 // for one store added in front of the loop: the top-p record), and srp_kernel<1024, true>, which already spills, is not asked
-// for another scalar across its loop -- srp_fx_kernel<1024, true> is, and spills five VGPRs where that one spills three
-// (profiles/samplernn_forced_kernel_resources.txt).  Inside FX = true the two are uniform branches.  The forced codes are
+// for another scalar across its loop -- srp_fx_kernel<1024, true> is, and spills thirteen VGPRs where that one spills three
+// (profiles/samplernn_forced_kernel_resources.txt, profiles/samplernn_min_p_kernel_resources.txt).  Inside FX = true the
+// three are uniform branches.  The forced codes are
 // team-local knowledge like the pick they replace: the prologue parks the launch's nsteps codes of the group's rows in the
 // shared block (anything outside 0 .. Q-1 as -1 = free), as it parks the per-utterance entries, and the step chain reads
 // them from there -- no global load in it.  The body is sr_persist_body.h, included once per kernel name.
@@ -147,7 +148,7 @@ int srp_prepare_width(int lds) {
 // instantiations that know them, and only then
 template <int D>
 void srp_launch_width(const SrpArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t stream) {
-    const bool fx = a.forced || a.logp;
+    const bool fx = a.forced || a.logp || a.dlogp;
     if (a.ngroups > 1 && fx) hipLaunchKernelGGL((srp_fx_kernel<D, true>), grid, block, lds, stream, a);
     else if (a.ngroups > 1) hipLaunchKernelGGL((srp_kernel<D, true>), grid, block, lds, stream, a);
     else if (fx) hipLaunchKernelGGL((srp_fx_kernel<D, false>), grid, block, lds, stream, a);

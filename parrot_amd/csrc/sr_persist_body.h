@@ -1,6 +1,6 @@
 // The body of the SampleRNN persistent sample kernel, included twice by sr_persist.hip (which describes it): once as
 // srp_kernel<D, MG> (SRP_FX false: the kernel as it always was, under the name it always had) and once as
-// srp_fx_kernel<D, MG> (SRP_FX true: forced samples and per-sample log-probabilities compiled in).  Two texts for the
+// srp_fx_kernel<D, MG> (SRP_FX true: forced samples, per-sample log-probabilities and the draw statistics compiled in).  Two texts for the
 // compiler, not one function called from two kernels: a shared __device__ body changed the register allocation of the
 // kernels that use neither facility (srp_kernel<1024, true> went from 16 to 36 bytes of scratch).
 template <int D, bool MG>
@@ -187,12 +187,22 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
             const float et = *(srp_cfloat)(ea + 16);
             const int ek = *(srp_cint)(ea + 20);
             const float ep = *(srp_cfloat)(ea + 24);
-            // (top_k parked as the pick reads it: 0 = no truncation of either kind, SRP_NUCLEUS set = the row has a nucleus)
-            const int ekn = (ek > 0 && ek < Q ? ek : 0) | (ep > 0.f && ep < 1.f ? SRP_NUCLEUS : 0);
-            if (lane == 0) { sh->useed[rw] = es; sh->uoff[rw] = eo; sh->utemp[rw] = et; sh->utopk[rw] = ekn; sh->utopp[rw] = ep; }
+            const float em = *(srp_cfloat)(ea + 28);
+            // (top_k parked as the pick reads it: 0 = no truncation of any kind, SRP_NUCLEUS set = the row has a nucleus,
+            // SRP_MINP set = it has a min_p)
+            const int ekn = (ek > 0 && ek < Q ? ek : 0) | (ep > 0.f && ep < 1.f ? SRP_NUCLEUS : 0) |
+                            (em > 0.f && em <= 1.f ? SRP_MINP : 0);
+            if (lane == 0) {
+                sh->useed[rw] = es; sh->uoff[rw] = eo; sh->utemp[rw] = et; sh->utopk[rw] = ekn; sh->utopp[rw] = ep;
+                sh->uminp[rw] = em;
+            }
         }
-        if (!a.utt && tid < SRP_ROWS) sh->utopp[tid] = a.top_p;  // (no entries: every row draws with the plan's nucleus)
+        // (no entries: every row draws with the plan's nucleus and the plan's min_p; both stores unconditional)
+        if (!a.utt && tid < SRP_ROWS) { sh->utopp[tid] = a.top_p; sh->uminp[tid] = a.min_p; }
         if constexpr (FX) {
+            // (the two pointers of the draw statistics, parked like the plan's nucleus: an argument read inside the step
+            // loop is scalars carried across it, which srp_fx_kernel<1024, true> pays for in spilled VGPRs)
+            if (tid == 0) { sh->dlogp = a.dlogp; sh->kept = a.kept; }
             // the forced codes of this launch's steps, rows past B like every other per-row load here; a value that is no code
             // is parked as -1, so nothing out of range ever reaches the history or a table
             if (a.forced) {
@@ -277,13 +287,16 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
                 // (the row's own temperature with per-utterance entries: rows of one team may mix argmax and draws)
                 const float temperature = a.utt ? sh->utemp[r] : a.temperature;
                 // (and its own truncation, asked for inside the draws only -- an argmax row runs what it always ran --: a uniform
-                // branch of both draws; 0 = off, and the draw runs the instructions it always ran.  One word says both kinds:
-                // the top_k in 1 .. Q-1 or 0, and SRP_NUCLEUS where the row has a nucleus -- SrpArgs::top_k comes that way from the
-                // plan, the entries are parked that way by the prologue -- so a draw without either pays one test for both.
-                // The nucleus itself is always read from the shared block, where the prologue parks the plan's value when
-                // there are no entries: an argument of the kernel read inside the step loop is one more scalar carried across it)
+                // branch of both draws; 0 = off, and the draw runs the instructions it always ran.  One word says all three kinds:
+                // the top_k in 1 .. Q-1 or 0, SRP_NUCLEUS where the row has a nucleus, SRP_MINP where it has a min_p --
+                // SrpArgs::top_k comes that way from the plan, the entries are parked that way by the prologue -- so a draw
+                // without any pays one test for all.  The nucleus and the min_p themselves are always read from the shared
+                // block, where the prologue parks the plan's values when there are no entries: an argument of the kernel read
+                // inside the step loop is one more scalar carried across it)
                 auto row_trunc = [&]() { return __builtin_amdgcn_readfirstlane(a.utt ? sh->utopk[r] : a.top_k); };
                 auto row_top_p = [&]() { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sh->utopp[r]))); };
+                auto row_min_p = [&]() { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sh->uminp[r]))); };
+                unsigned dkeep = 0xfu;  // (FX, the statistics behind the pick: the lane's kept bits of a scan draw)
                 if (temperature > 0.f && a.draw_mode == 1) {
                     // wave-parallel draw: lane l owns codes 4 l .. 4 l + 3, terms in registers, no LDS; the key, the counter
                     // and the uniform are the ones of the walk below
@@ -297,6 +310,7 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
                     if (const int tr = row_trunc()) {
                         const int tk = tr & (SRP_NUCLEUS - 1);
                         const float tp = tr & SRP_NUCLEUS ? row_top_p() : 0.f;
+                        const float tm = tr & SRP_MINP ? row_min_p() : 0.f;
                         // the terms outside the kept set become 0.0f (adding them is exact: the tree and its bounds stand)
                         const unsigned f[4] = {srp_order_image(lg[4 * lane][r]), srp_order_image(lg[4 * lane + 1][r]),
                                                srp_order_image(lg[4 * lane + 2][r]), srp_order_image(lg[4 * lane + 3][r])};
@@ -312,8 +326,14 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
 #pragma unroll
                             for (int j = 0; j < 4; ++j) mk[j] = (keep >> j) & 1u ? mk[j] : 0.f;
                         }
+                        if (tm != 0.f) {  // min-p last: of what is left, the codes whose term reaches the bar (one compare each)
+                            keep &= srp_minp_keep<4>(mk, tm);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) mk[j] = (keep >> j) & 1u ? mk[j] : 0.f;
+                        }
                         const float m0 = mk[0], m1 = mk[1], m2 = mk[2], m3 = mk[3];
                         const int lk = keep ? 4 * lane + 31 - __clz((int)keep) : -1;
+                        if constexpr (FX) dkeep = keep;
                         pick = srp_scan_draw<true>([&](int j) { return j == 0 ? m0 : j == 1 ? m1 : j == 2 ? m2 : m3; }, 4, lane,
                                                    srp_u01(key, ctr), lk);
                     } else {
@@ -325,6 +345,7 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
                     if (const int tr = row_trunc()) {
                         const int tk = tr & (SRP_NUCLEUS - 1);
                         const float tp = tr & SRP_NUCLEUS ? row_top_p() : 0.f;
+                        const float tm = tr & SRP_MINP ? row_min_p() : 0.f;
                         // the terms outside the kept set are overwritten with 0.0f: the walk adds them, exactly
                         unsigned f[Q / 64];
                         int idx[Q / 64], ln = lane;
@@ -338,6 +359,12 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
                             for (int m = 0; m < Q / 64; ++m) ek[m] = (keep >> m) & 1u ? ev[r * Q + lane + 64 * m] : 0.f;
                             keep &= srp_topp_keep<Q / 64>(f, idx, ek, tp);
                         }
+                        if (tm != 0.f) {  // min-p last: of what is left, the codes whose term reaches the bar (one compare each)
+                            float ek[Q / 64];
+#pragma unroll
+                            for (int m = 0; m < Q / 64; ++m) ek[m] = (keep >> m) & 1u ? ev[r * Q + lane + 64 * m] : 0.f;
+                            keep &= srp_minp_keep<Q / 64>(ek, tm);
+                        }
 #pragma unroll
                         for (int m = 0; m < Q / 64; ++m)
                             if (!((keep >> m) & 1u)) ev[r * Q + lane + 64 * m] = 0.f;
@@ -346,6 +373,17 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
                         // spilled VGPR)
                         const int last = srp_topk_last<Q / 64>(keep, idx);
                         if (lane == 0) sh->ulast[r] = last;
+                        if constexpr (FX) {
+                            // (the set itself, for the statistics behind the pick: a kept code's term may underflow to 0, so
+                            // neither the count nor membership can be read back from the terms)
+                            if (sh->dlogp) {
+#pragma unroll
+                                for (int m = 0; m < Q / 64; ++m) {
+                                    const unsigned long long bm = __ballot((keep >> m) & 1u);
+                                    if (lane == 0) sh->ukeepm[r][m] = bm;
+                                }
+                            }
+                        }
                     }
                     __builtin_amdgcn_wave_barrier();
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -398,6 +436,48 @@ __global__ __launch_bounds__(SRP_THREADS) void SRP_KERNEL(const SrpArgs a) {
                         const float tot = srp_wave_sum(__fadd_rn(e01, e23));
                         const int b = srow + r;
                         if (lane == 0 && b < a.B) a.logp[(size_t)b * a.len + t] = lg[sc][r] - best - logf(tot);
+                    }
+                }
+                if constexpr (FX) {
+                    // what the step drew from (samplernn_generate_set_draw_stats): the size of the kept set and the log of the
+                    // written sample's probability under it.  Behind the pick, whose instructions stay as they are: the lane
+                    // takes four codes in the draw's own layout (4 l + j in the scan, l + 64 j in the walk), their kept bits
+                    // from the register the scan left or from the ballots the walk's selection parked, recomputes the terms
+                    // (the same expf of the same argument) and the mass is srp_wave_sum's fixed tree.  One CU writes.
+                    if (sh->dlogp && cu == 0) {
+                        static_assert(Q == 256, "four codes per lane");
+                        const int sc = __builtin_amdgcn_readfirstlane(pick);  // (lane 0 holds the sample in every mode)
+                        float dl;
+                        int cnt;
+                        if (temperature > 0.f) {
+                            // (a rolled loop, one code at a time: the weights of both layers are live here, and four
+                            // expf side by side spilled 18 more VGPRs in srp_fx_kernel<1024, true>)
+                            const bool scan = a.draw_mode == 1;
+                            const int tr = row_trunc();
+                            const unsigned* km = reinterpret_cast<const unsigned*>(sh->ukeepm[r]);
+                            float s = 0.f;  // (0 + e is exact: the lane's terms left to right)
+                            bool in = false;
+                            cnt = 0;
+#pragma unroll 1
+                            for (int j = 0; j < 4; ++j) {
+                                const int code = scan ? 4 * lane + j : lane + 64 * j;
+                                bool k = true;
+                                if (tr) k = scan ? (dkeep >> j) & 1u : (km[2 * j + (lane >> 5)] >> (lane & 31)) & 1u;
+                                s = __fadd_rn(s, k ? expf((lg[code][r] - best) / temperature) : 0.f);
+                                cnt += (int)__popcll(__ballot(k));
+                                in = in || (k && code == sc);
+                            }
+                            const float tot = srp_wave_sum(s);
+                            dl = __ballot(in) != 0ull ? (lg[sc][r] - best) / temperature - logf(tot) : -INFINITY;
+                        } else {
+                            cnt = 1;
+                            dl = sc == bi ? 0.f : -INFINITY;
+                        }
+                        const int b = srow + r;
+                        if (lane == 0 && b < a.B) {
+                            sh->dlogp[(size_t)b * a.len + t] = dl;
+                            sh->kept[(size_t)b * a.len + t] = cnt;
+                        }
                     }
                 }
             }

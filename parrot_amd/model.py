@@ -1869,7 +1869,7 @@ class SampleRnn(Brick):
         return self.three_tier.compute_cost(sequences, features, h0, big_h0, reset, mask)
 
     def sample_raw(self, test_feats, features_length, tag, path_to_save, pack_streams=0, stream_frames=0, utterance_seed=None,
-                   draw_mode='sequential', top_k=0, top_p=0.0):
+                   draw_mode='sequential', top_k=0, top_p=0.0, min_p=0.0):
         """pack_streams = N > 0: the utterances (row i cut at features_length[i]) are packed one after the other into N
         streams of one generation plan (three_tier.generate_packed) instead of one rectangle of num_steps frames.
         stream_frames = S > 0: they run through a three_tier.StreamingGenerator (pack_streams or 32 streams) in segments of
@@ -1880,14 +1880,17 @@ class SampleRnn(Brick):
         top_k = k > 0: the draws at temperature > 0 are taken among the k most likely codes (three_tier.DeviceGenerator); 0:
         among all; ValueError on a negative one, before any device call.
         top_p = p strictly between 0 and 1: those draws are taken among the nucleus of the codes top_k left
-        (three_tier.DeviceGenerator); 0 or >= 1: no nucleus; ValueError on a negative one or a NaN, before any device call."""
+        (three_tier.DeviceGenerator); 0 or >= 1: no nucleus; ValueError on a negative one or a NaN, before any device call.
+        min_p in (0, 1]: of the codes both left, those draws keep the ones at least min_p times as likely as the most likely
+        code (three_tier.DeviceGenerator); 0: off; ValueError outside [0, 1] or on a NaN, before any device call."""
         tt = self.three_tier
         tt.draw_mode_code(draw_mode)
         tt.top_k_code(top_k)
         tt.top_p_code(top_p)
+        tt.min_p_code(min_p)
         fns = tt.getting_generation_functions(None, None, None, None, None)
         return tt.generate_and_save_samples(
             tag, path_to_save=path_to_save, features=test_feats, features_length=features_length,
             noise_level=0., big_frame_level_generate_fn=fns[0], frame_level_generate_fn=fns[1],
             sample_level_generate_fn=fns[2], npy_address=None, pack_streams=pack_streams, stream_frames=stream_frames,
-            utterance_seed=utterance_seed, draw_mode=draw_mode, top_k=top_k, top_p=top_p)
+            utterance_seed=utterance_seed, draw_mode=draw_mode, top_k=top_k, top_p=top_p, min_p=min_p)

@@ -8,18 +8,19 @@ from ... import _lib
 from ... import ops as hip
 from .. import lib
 from ..lib import ops as lops
-from .inputs import (FREE, _seed_image, config, draw_mode_code, forced_array, skip_stacks_enabled, stack_param_names,
-                     top_k_array, top_k_code, top_p_array, top_p_code)
+from .inputs import (FREE, _seed_image, config, draw_mode_code, forced_array, min_p_array, min_p_code, skip_stacks_enabled,
+                     stack_param_names, top_k_array, top_k_code, top_p_array, top_p_code)
 
 
-def device_loop_guard(draw_mode, top_k=0, top_p=0.0):
+def device_loop_guard(draw_mode, top_k=0, top_p=0.0, min_p=0.0):
     """What every entry to the device-resident loop checks before any device call: draw_mode's code (ValueError on an
-    unknown name), top_k (ValueError on a negative one), top_p (ValueError on a negative one or a NaN), and the model's
+    unknown name), top_k (ValueError on a negative one), top_p (ValueError on a negative one or a NaN), min_p (ValueError outside [0, 1] or a NaN), and the model's
     stacks: skip-connection stacks (SKIP_CONN) are taken only with PARROT_SR_SKIP_STACKS=1, read here at call time, and only
     with N_RNN >= 2 (the reference asserts that no one-layer stack has skip connections); NotImplementedError otherwise."""
     mode = draw_mode_code(draw_mode)
     top_k_code(top_k)
     top_p_code(top_p)
+    min_p_code(min_p)
     if config().SKIP_CONN:
         if not skip_stacks_enabled():
             raise NotImplementedError("the device-resident generator takes skip-connection stacks only with "
@@ -34,9 +35,11 @@ class DeviceGenerator:
 
     forcing = False    # (a plan takes forced samples / returns log-probabilities only when it was built that way)
     log_probs = False
+    draw_stats = False
 
     def __init__(self, batch, n_frames, temperature=0.0, seed=234, use_graph=True, packed=False, utterance_draws=False,
-                 draw_mode='sequential', top_k=0, top_p=0.0, forcing=False, log_probs=False):
+                 draw_mode='sequential', top_k=0, top_p=0.0, forcing=False, log_probs=False, min_p=0.0,
+                 draw_stats=False):
         """GRU or LSTM tiers, 1..5 stacked layers (three_tier.py:147-169).  Stacks with skip connections (SKIP_CONN, 2..5
         layers) are taken with PARROT_SR_SKIP_STACKS=1 (samplernn_generate_set_skip_stacks: one more K segment in the step
         jobs of the layers above the first, one more job per tier step for the summed out-skips; everything below is the
@@ -71,6 +74,14 @@ class DeviceGenerator:
         every earlier version.  A very small p picks the argmax.  With utterance_draws=True it is what an utterance draws
         with unless generate(..., top_ps=) names its own.  Negative or NaN: ValueError.
 
+        min_p in (0, 1]: a draw at temperature > 0 is taken among the codes whose probability is at least min_p times the
+        most likely code's (samplernn_generate_set_min_p) -- those whose float32 term expf((logit - max) / temperature) is
+        >= min_p; never empty.  Applied last: the kept set is top_k's set, its nucleus and this set intersected, every
+        other code's term 0 in the same sums, so such a draw is again a draw with top_k = the size of what is left.
+        min_p = 1 keeps the maxima only.  0 (default): off, the samples of every earlier version.  With
+        utterance_draws=True it is what an utterance draws with unless generate(..., min_ps=) names its own.  Negative,
+        above 1 or NaN: ValueError.
+
         forcing=True: the plan takes forced samples (samplernn_generate_set_forced): generate(..., forced=) names, per
         stream and sample, a code the sample step takes instead of its pick, or -1 where it picks freely.  The step computes
         its logits either way, and the forced code is what every later step, both tiers above and a resumed segment see.
@@ -81,16 +92,26 @@ class DeviceGenerator:
         natural logarithm of the MODEL's probability of each sample it wrote, forced or picked -- temperature 1, no
         truncation, whatever the step draws with; the quantity compute_cost averages.  The prefix slot holds zeros.
 
-        Both are independent of each other and of every other setting; a plan built with neither runs the kernels it ran
+        draw_stats=True: generate returns two more arrays of the samples' shape behind (samples[, logp]), draw_logp float32
+        and kept int32 (samplernn_generate_set_draw_stats): what each step drew from.  kept = the size of the set the step's
+        pick was drawn from -- 1 on an argmax step (temperature <= 0), Q_LEVELS on an untruncated draw, else what top_k,
+        top_p and min_p left, forced step or not.  draw_logp = the natural logarithm of the probability of the sample that
+        was written under the step's own temperature and kept set, (logit - max) / temperature - log(sum of the kept
+        terms): -inf for a (forced) sample outside the kept set or off the argmax of an argmax step, 0 for the argmax of an
+        argmax step.  The prefix slot holds zeros in both.
+
+        All three are independent of each other and of every other setting; a plan built with none runs the kernels it ran
         before they existed."""
         self.draw_mode = draw_mode
-        mode = device_loop_guard(draw_mode, top_k, top_p)
+        mode = device_loop_guard(draw_mode, top_k, top_p, min_p)
         self.top_k = top_k_code(top_k)
         self.top_p = top_p_code(top_p)
+        self.min_p = min_p_code(min_p)
         self.B, self.T = batch, n_frames
         self.packed = bool(packed)
         self.utterance_draws = bool(utterance_draws)
         self.forcing, self.log_probs = bool(forcing), bool(log_probs)
+        self.draw_stats = bool(draw_stats)
         dev = lib.device()
         f = dict(device=dev, dtype=torch.float32)
         tt = config()
@@ -184,6 +205,8 @@ class DeviceGenerator:
         _lib.call('samplernn_generate_create', C.byref(d), C.byref(self.plan))
         if 0.0 < self.top_p < 1.0:  # (the descriptor has no word for it; off is a new plan's state)
             _lib.call('samplernn_generate_set_top_p', self.plan, C.c_float(self.top_p))
+        if self.min_p > 0.0:
+            _lib.call('samplernn_generate_set_min_p', self.plan, C.c_float(self.min_p))
         if self.skip:
             self.set_skip_stacks()
         self.persistent = bool(_lib.load().samplernn_generate_is_persistent(self.plan))
@@ -196,6 +219,11 @@ class DeviceGenerator:
         if self.log_probs:
             self.ws['logp'] = torch.zeros(batch, BFS * n_frames, **f)
             _lib.call('samplernn_generate_set_log_probs', self.plan, self.ws['logp'].data_ptr())
+        if self.draw_stats:
+            self.ws['draw_logp'] = torch.zeros(batch, BFS * n_frames, **f)
+            self.ws['kept'] = torch.zeros(batch, BFS * n_frames, device=dev, dtype=torch.int32)
+            _lib.call('samplernn_generate_set_draw_stats', self.plan, self.ws['draw_logp'].data_ptr(),
+                      self.ws['kept'].data_ptr())
         if self.utterance_draws:
             # [T, B] like starts (ring rows): row f = what an utterance that begins at big frame f draws with; utt_seed is the
             # two's-complement image of the unsigned 64-bit seed
@@ -203,6 +231,7 @@ class DeviceGenerator:
             self.ws['utt_temp'] = torch.zeros(n_frames, batch, **f)
             self.ws['utt_top_k'] = torch.zeros(n_frames, batch, device=dev, dtype=torch.int32)
             self.ws['utt_top_p'] = torch.zeros(n_frames, batch, **f)
+            self.ws['utt_min_p'] = torch.zeros(n_frames, batch, **f)
             self.set_utterance_draws()
 
     def set_skip_stacks(self):
@@ -225,15 +254,16 @@ class DeviceGenerator:
         return s
 
     def set_utterance_draws(self):
-        """Hands the plan its per-utterance seed, temperature, top_k and top_p arrays; refused (HipCallError) once the plan
+        """Hands the plan its per-utterance seed, temperature, top_k, top_p and min_p arrays; refused (HipCallError) once the plan
         has run."""
         _lib.call('samplernn_generate_set_utterance_draws', self.plan, self.ws['utt_seed'].data_ptr(),
                   self.ws['utt_temp'].data_ptr())
         _lib.call('samplernn_generate_set_utterance_top_k', self.plan, self.ws['utt_top_k'].data_ptr())
         _lib.call('samplernn_generate_set_utterance_top_p', self.plan, self.ws['utt_top_p'].data_ptr())
+        _lib.call('samplernn_generate_set_utterance_min_p', self.plan, self.ws['utt_min_p'].data_ptr())
 
     def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None,
-                 top_ps=None, forced=None):
+                 top_ps=None, forced=None, min_ps=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
         frame f, whose Q/2 prefix is slot f - 1.
@@ -259,30 +289,38 @@ class DeviceGenerator:
         draws with (0 or >= 1: no nucleus); omitted, every utterance takes the plan's top_p.  A negative value, a NaN or
         another shape: ValueError.
 
+        min_ps (optional, likewise): numbers of the same shape as seeds, or one number for all -- the min_p each utterance
+        draws with (0: off); omitted, every utterance takes the plan's min_p.  A value outside [0, 1], a NaN or another
+        shape: ValueError.
+
         forced (plans built with forcing=True only, and required there): integers [B, 80 rows], aligned with the rows of
         `features` of this call -- [B, 80 T] for a run in one piece (its first 80 columns, the prefix slot, are ignored),
         [B, 80 k] for a segment that resumes.  A code in 0 .. Q_LEVELS-1 is the sample of that step; -1: the step picks.
         Another shape, a non-integer dtype or any other value: ValueError, before anything is staged.
 
         A plan built with log_probs=True returns (samples, logp): logp float32, sliced like samples and, like them, a
-        copy when the run is in segments."""
-        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures, top_ks, top_ps)
+        copy when the run is in segments.  A plan built with draw_stats=True returns (samples[, logp], draw_logp, kept),
+        sliced and copied the same way."""
+        segment, resume, k, rows, first = self._resolve(starts, resume, n_frames, seeds, temperatures, top_ks, top_ps, min_ps)
         if (forced is not None) != self.forcing:
             raise ValueError("forced must be given exactly when the plan was built with forcing=True")
         if forced is not None:  # (its values and shape before anything is staged on the device)
             forced = forced_array(forced, (self.B, config().BIG_FRAME_SIZE * rows))
-        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks, top_ps)
+        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks, top_ps, min_ps)
         BFS = config().BIG_FRAME_SIZE
         if forced is not None:
             fo = self.ws['forced']
             fo[:, BFS * first:BFS * (first + rows)].copy_(torch.from_numpy(forced).to(fo.device))
         self._launch(segment, resume, k)
         cut = (lambda x: x) if not segment else (lambda x: x[:, BFS * first:BFS * (k + 1)].clone())
+        out = (cut(self.ws['samples']),)
         if self.log_probs:
-            return cut(self.ws['samples']), cut(self.ws['logp'])
-        return cut(self.ws['samples'])
+            out += (cut(self.ws['logp']),)
+        if self.draw_stats:
+            out += (cut(self.ws['draw_logp']), cut(self.ws['kept']))
+        return out if len(out) > 1 else out[0]
 
-    def _resolve(self, starts, resume, n_frames, seeds, temperatures, top_ks=None, top_ps=None):
+    def _resolve(self, starts, resume, n_frames, seeds, temperatures, top_ks=None, top_ps=None, min_ps=None):
         """Which arguments this plan takes in which kind of run -> (segment, resume, k, rows, first): a run in segments or
         in one piece, k frames to generate, `rows` rows of input for the ring's slots from `first` on."""
         if (starts is not None) != self.packed:
@@ -298,6 +336,9 @@ class DeviceGenerator:
         if top_ps is not None and not takes_draws:
             raise ValueError("top_ps is accepted only where seeds is: on a plan built with utterance_draws=True (a plain "
                              "plan takes them with resume=False only)")
+        if min_ps is not None and not takes_draws:
+            raise ValueError("min_ps is accepted only where seeds is: on a plan built with utterance_draws=True (a plain "
+                             "plan takes them with resume=False only)")
         if resume and not self._has_run:
             raise ValueError("resume=True needs a run to continue: call generate(..., resume=False) first")
         k = self.T - 1 if n_frames is None else int(n_frames)
@@ -308,9 +349,11 @@ class DeviceGenerator:
             top_k_code(top_ks) if numpy.ndim(top_ks) == 0 else top_k_array(top_ks, (rows, self.B) if self.packed else (self.B,))
         if top_ps is not None:
             top_p_code(top_ps) if numpy.ndim(top_ps) == 0 else top_p_array(top_ps, (rows, self.B) if self.packed else (self.B,))
+        if min_ps is not None:
+            min_p_code(min_ps) if numpy.ndim(min_ps) == 0 else min_p_array(min_ps, (rows, self.B) if self.packed else (self.B,))
         return resume or n_frames is not None, resume, k, rows, 1 if resume else 0
 
-    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None, top_ps=None):
+    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None, top_ps=None, min_ps=None):
         """Checks the arrays' shapes and copies them into rows first .. first + rows - 1 of the workspace."""
         ws = self.ws
         feats = torch.as_tensor(features)
@@ -337,8 +380,13 @@ class DeviceGenerator:
                 pp = numpy.full(want, top_p_code(self.top_p if top_ps is None else top_ps), dtype=numpy.float32)
             else:
                 pp = top_p_array(top_ps, want)
+            if min_ps is None or numpy.ndim(min_ps) == 0:
+                mp = numpy.full(want, min_p_code(self.min_p if min_ps is None else min_ps), dtype=numpy.float32)
+            else:
+                mp = min_p_array(min_ps, want)
             # (a plain plan: one utterance per stream, prefix in slot 0 -- the row of slot 1, like a start flagged there)
             lo, hi = (first, first + rows) if self.packed else (1, 2)
+            ws['utt_min_p'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(mp).reshape(hi - lo, self.B)).to(ws['utt_min_p'].device))
             ws['utt_top_p'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(pp).reshape(hi - lo, self.B)).to(ws['utt_top_p'].device))
             ws['utt_top_k'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tk).reshape(hi - lo, self.B)).to(ws['utt_top_k'].device))
             ws['utt_seed'][lo:hi].copy_(torch.from_numpy(sd.reshape(hi - lo, self.B)).to(ws['utt_seed'].device))

@@ -1,6 +1,6 @@
 """What a generation plan is fed, computed on the host with numpy alone (no torch, no device): the seeded draw in Python
 integers -- the hash sr_pick_kernel and srp_kernel key their uniforms with, a seed per utterance, the draw modes' names,
-the checks of a top_k and a top_p --
+the checks of a top_k, a top_p and a min_p --
 and where utterances go: into the streams of one packed plan (pack_utterances and the arrays of such a packing) and into
 the segments of a plan that never ends (schedule_segment)."""
 import numpy
@@ -168,6 +168,47 @@ def _per_utterance_top_p(top_ps, n, default_top_p):
     return [top_p_code(p) for p in top_ps]
 
 
+def min_p_code(min_p):
+    """The float a plan or an utterance is handed as its min_p (samplernn_generate_set_min_p): 0.0 = off, in (0, 1] = active
+    (1.0 keeps the most likely codes only); ValueError on a negative value, a value above 1, a NaN or anything that is not a
+    real number (no device call)."""
+    if isinstance(min_p, bool) or not isinstance(min_p, (int, float, numpy.integer, numpy.floating)):
+        raise ValueError("min_p must be a number in [0, 1] (0: off), got %r" % (min_p,))
+    if not 0 <= min_p <= 1:
+        raise ValueError("min_p must be in [0, 1] and not NaN (0: off), got %r" % (min_p,))
+    # (as the float32 the device sees; a positive value below float32's normal range stays active: it keeps every code
+    # whose term does not underflow)
+    p = float(numpy.float32(float(min_p)))
+    return max(p, _TINY32) if min_p > 0 else 0.0
+
+
+def min_p_active(min_p):
+    """Whether a checked min_p truncates: in (0, 1] as the float32 the device sees."""
+    return 0.0 < min_p_code(min_p) <= 1.0
+
+
+def min_p_array(min_ps, shape):
+    """Per-utterance min_p values as the float32 array of `shape` a plan is fed: ValueError on another shape, a negative
+    value, a value above 1, a NaN or a non-numeric array (no device call)."""
+    a = numpy.asarray(min_ps)
+    if a.dtype.kind not in 'iuf' or a.shape != tuple(shape):
+        raise ValueError("min_ps must be numbers of shape %s, got %s of %s" % (list(shape), a.dtype, list(a.shape)))
+    if a.size and not bool(numpy.all((a >= 0) & (a <= 1))):
+        raise ValueError("min_ps must be in [0, 1] and not NaN (0: off)")
+    a = a.astype(numpy.float64)
+    return numpy.where(a > 0, numpy.clip(a, _TINY32, 1.0), 0.0).astype(numpy.float32)
+
+
+def _per_utterance_min_p(min_ps, n, default_min_p):
+    """min_ps: one per utterance or a scalar; None = default_min_p for all."""
+    if min_ps is None:
+        min_ps = default_min_p
+    min_ps = [min_ps] * n if numpy.ndim(min_ps) == 0 else list(min_ps)
+    if len(min_ps) != n:
+        raise ValueError("%d utterances, but %d min_ps" % (n, len(min_ps)))
+    return [min_p_code(p) for p in min_ps]
+
+
 def _per_utterance(seeds, temperatures, n, default_temperature):
     """seeds: one per utterance; temperatures: one per utterance, a scalar, or None = default_temperature."""
     seeds = [u64(s) for s in seeds]
@@ -314,11 +355,24 @@ def build_packed_prompts(prompts, lengths, stream, first_slot, T, n_streams):
     return forced
 
 
-def unpack_log_probs(logp, lengths, stream, first_slot):
+def unpack_log_probs(logp, lengths, stream, first_slot, dtype='float32'):
     """The utterances' pieces of a packed run's log-probabilities [B, 80 T]: per utterance the float32 values of its samples
-    80 .. 80 n_i - 1 (the prefix slot has none)."""
+    80 .. 80 n_i - 1 (the prefix slot has none).  (Any per-step array is cut this way: dtype='int32' for the kept counts.)"""
     BFS = config().BIG_FRAME_SIZE
-    return [numpy.array(logp[b, BFS * (s + 1):BFS * (s + n)], dtype='float32') for n, b, s in zip(lengths, stream, first_slot)]
+    return [numpy.array(logp[b, BFS * (s + 1):BFS * (s + n)], dtype=dtype) for n, b, s in zip(lengths, stream, first_slot)]
+
+
+def build_packed_min_p(min_ps, stream, first_slot, T, n_streams):
+    """utt_min_p [T, n_streams] float32 of a packing, the sibling of build_packed_top_p: utterance i's min_p on its
+    start_row; zeros (off) elsewhere."""
+    utt_min_p = numpy.zeros((T, n_streams), dtype=numpy.float32)
+    for p_, b, s in zip(min_ps, stream, first_slot):
+        if not (0 <= b < n_streams and 0 <= s < T):
+            raise ValueError("no slot %d in stream %d" % (s, b))
+        row = start_row(s, T)
+        if row is not None:
+            utt_min_p[row, b] = min_p_code(p_)
+    return utt_min_p
 
 
 def unpack_samples(samples, lengths, stream, first_slot):

@@ -3,15 +3,15 @@ segments on a ring (generate_stream) and continuous admission on a plan that nev
 import numpy
 
 from .device import DeviceGenerator, device_loop_guard
-from .inputs import (FREE, _per_utterance, _per_utterance_prompts, _per_utterance_top_k, _per_utterance_top_p,
-                     build_packed_draws, build_packed_inputs, build_packed_prompts, build_packed_top_k, build_packed_top_p,
-                     config, pack_utterances, schedule_segment, start_row, top_k_code, top_p_code, u64, unpack_log_probs,
-                     unpack_samples)
+from .inputs import (FREE, _per_utterance, _per_utterance_min_p, _per_utterance_prompts, _per_utterance_top_k,
+                     _per_utterance_top_p, build_packed_draws, build_packed_inputs, build_packed_min_p, build_packed_prompts,
+                     build_packed_top_k, build_packed_top_p, config, min_p_code, pack_utterances, schedule_segment, start_row,
+                     top_k_code, top_p_code, u64, unpack_log_probs, unpack_samples)
 
 
 def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_graph=True, seeds=None,
                     temperatures=None, draw_mode='sequential', top_k=0, top_ks=None, top_p=0.0, top_ps=None, prompts=None,
-                    log_probs=False):
+                    log_probs=False, min_p=0.0, min_ps=None, draw_stats=False):
     """Generates a list of utterances ([n_i, 63] conditioning frames each) on `n_streams` streams of ONE plan, several
     utterances one after the other per stream (pack_utterances), instead of one rectangle of max(n_i) frames per
     n_streams utterances.  Returns a list of int32 arrays [80 * n_i], the Q/2 prefix included.
@@ -35,14 +35,20 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
     top_p: those draws are taken among the nucleus of the codes top_k left (0 or >= 1: no nucleus; see DeviceGenerator).
     top_ps = one top_p per utterance (needs `seeds`; default: `top_p` for all).
 
+    min_p: of the codes both left, those draws keep the ones at least min_p times as likely as the most likely code (0: off;
+    in (0, 1]; see DeviceGenerator).  min_ps = one min_p per utterance (needs `seeds`; default: `min_p` for all).
+
     prompts = per utterance None or an integer array of at most 80 * (n_i - 1) codes in 0 .. Q_LEVELS-1: code j is sample
     80 + j of that utterance's own buffer, whatever the model would have picked there (DeviceGenerator(forcing=True)); the
     utterance goes on freely behind its prompt, drawing with the uniforms of its own sample indices.  A longer prompt, a
     non-integer array or another value: ValueError, before a plan is created.
 
     log_probs=True: returns (samples_list, logp_list), logp_list[i] = float32 [80 * (n_i - 1)], the natural logarithm of the
-    model's probability (temperature 1, no truncation) of samples 80 .. of utterance i (DeviceGenerator(log_probs=True))."""
-    device_loop_guard(draw_mode, top_k, top_p)
+    model's probability (temperature 1, no truncation) of samples 80 .. of utterance i (DeviceGenerator(log_probs=True)).
+
+    draw_stats=True: two more lists behind (samples_list[, logp_list]), draw_logp_list[i] float32 and kept_list[i] int32, both
+    [80 * (n_i - 1)] and cut like logp_list: what each of utterance i's steps drew from (DeviceGenerator(draw_stats=True))."""
+    device_loop_guard(draw_mode, top_k, top_p, min_p)
     utterances = [numpy.asarray(u, dtype='float32') for u in utterances]
     lengths = [u.shape[0] for u in utterances]
     if prompts is not None:  # (before a plan is created)
@@ -53,31 +59,37 @@ def generate_packed(utterances, n_streams=32, temperature=1.0, seed=234, use_gra
         raise ValueError("top_ks per utterance need seeds per utterance")
     if seeds is None and top_ps is not None:
         raise ValueError("top_ps per utterance need seeds per utterance")
+    if seeds is None and min_ps is not None:
+        raise ValueError("min_ps per utterance need seeds per utterance")
     if seeds is not None:  # (before a plan is created)
         seeds, temperatures = _per_utterance(seeds, temperatures, len(utterances), temperature)
         top_ks = _per_utterance_top_k(top_ks, len(utterances), top_k)
         top_ps = _per_utterance_top_p(top_ps, len(utterances), top_p)
+        min_ps = _per_utterance_min_p(min_ps, len(utterances), min_p)
     if not utterances:
-        return ([], []) if log_probs else []
+        return ([],) * (1 + bool(log_probs) + 2 * bool(draw_stats)) if log_probs or draw_stats else []
     stream, first_slot, T = pack_utterances(lengths, n_streams)
     features, starts = build_packed_inputs(utterances, stream, first_slot, T, n_streams)
     gen = DeviceGenerator(n_streams, T, temperature=temperature, seed=seed, use_graph=use_graph, packed=True,
                           utterance_draws=seeds is not None, draw_mode=draw_mode, top_k=top_k, top_p=top_p,
-                          forcing=prompts is not None, log_probs=log_probs)
+                          forcing=prompts is not None, log_probs=log_probs, min_p=min_p, draw_stats=draw_stats)
     try:
         draws = {}
         if seeds is not None:
             draws['seeds'], draws['temperatures'] = build_packed_draws(seeds, temperatures, stream, first_slot, T, n_streams)
             draws['top_ks'] = build_packed_top_k(top_ks, stream, first_slot, T, n_streams)
             draws['top_ps'] = build_packed_top_p(top_ps, stream, first_slot, T, n_streams)
+            draws['min_ps'] = build_packed_min_p(min_ps, stream, first_slot, T, n_streams)
         if prompts is not None:
             draws['forced'] = build_packed_prompts(prompts, lengths, stream, first_slot, T, n_streams)
         out = gen.generate(features, starts, **draws)
-        samples, logp = (out[0].cpu().numpy(), out[1].cpu().numpy()) if log_probs else (out.cpu().numpy(), None)
+        out = [o.cpu().numpy() for o in (out if isinstance(out, tuple) else (out,))]
     finally:
         gen.close()
-    pieces = unpack_samples(samples, lengths, stream, first_slot)
-    return (pieces, unpack_log_probs(logp, lengths, stream, first_slot)) if log_probs else pieces
+    # (the per-step arrays behind the samples are all cut as the log-probabilities are)
+    res = (unpack_samples(out[0], lengths, stream, first_slot),) + \
+        tuple(unpack_log_probs(o, lengths, stream, first_slot, dtype=o.dtype) for o in out[1:])
+    return res if len(res) > 1 else res[0]
 
 
 def score_utterances(utterances, samples, n_streams=32):
@@ -103,16 +115,16 @@ def score_utterances(utterances, samples, n_streams=32):
 
 
 def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_graph=True, gen=None, draw_mode='sequential',
-                    top_k=0, top_p=0.0):
+                    top_k=0, top_p=0.0, min_p=0.0):
     """Generator over a rectangle features [N, B, 63] on a plan of segment_frames + 1 slots used as a ring: yields int32
     arrays [B, 80 n] -- the first one holds the Q/2 prefix and up to segment_frames frames, every later one up to
     segment_frames frames -- whose concatenation is the [B, 80 N] result of DeviceGenerator(B, N).generate(features), bit
     for bit, seeded draws included.  The plan does not grow with N, and the first samples are out after segment_frames
     periods.  gen: a plain DeviceGenerator(B, segment_frames + 1) of the caller's to run on (it is left open; temperature,
-    seed, use_graph, draw_mode, top_k and top_p are then the plan's); default: a plan of its own for this call, with
-    draw_mode 'sequential' or 'scan', top_k and top_p (see DeviceGenerator) and temperature's default as in
+    seed, use_graph, draw_mode, top_k, top_p and min_p are then the plan's); default: a plan of its own for this call, with
+    draw_mode 'sequential' or 'scan', top_k, top_p and min_p (see DeviceGenerator) and temperature's default as in
     generate_packed."""
-    device_loop_guard(draw_mode, top_k, top_p)
+    device_loop_guard(draw_mode, top_k, top_p, min_p)
     features = numpy.asarray(features, dtype='float32')
     S = int(segment_frames)
     if S < 1:
@@ -123,7 +135,7 @@ def generate_stream(features, segment_frames, temperature=1.0, seed=234, use_gra
     own = gen is None
     if own:
         gen = DeviceGenerator(B, S + 1, temperature=temperature, seed=seed, use_graph=use_graph, draw_mode=draw_mode,
-                              top_k=top_k, top_p=top_p)
+                              top_k=top_k, top_p=top_p, min_p=min_p)
     elif gen.packed or (gen.B, gen.T) != (B, S + 1):
         raise ValueError("gen must be a plain plan of %d streams and %d slots" % (B, S + 1))
     try:
@@ -172,6 +184,11 @@ class StreamingGenerator:
     utterance was submitted with one -- calls run_segment with one more keyword argument, top_ps [n, B] float32; a
     generator that does not never passes it.
 
+    min_p: the plan's min-p bar (see DeviceGenerator), what every utterance draws with unless submit(..., min_p=) names its
+    own (utterance_draws=True only).  Likewise, a generator that uses it -- its min_p is active, or some utterance was
+    submitted with one -- calls run_segment with one more keyword argument, min_ps [n, B] float32; a generator that does
+    not never passes it.
+
     Prompts: submit(..., prompt=) primes an utterance with up to 80 * (n - 1) codes, the samples 80 .. of its own buffer;
     the prompt is cut across segment boundaries as the features are and may end mid-frame.  From the first utterance
     submitted with a prompt on, run_segment is called with one more keyword argument, forced [B, 80 n] int32, aligned with
@@ -183,8 +200,9 @@ class StreamingGenerator:
     device, submit refuses a prompt without it; a plan built without it runs the kernels it always ran."""
 
     def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
-                 utterance_draws=False, draw_mode='sequential', top_k=0, top_p=0.0, log_probs=False, forcing=False):
-        device_loop_guard(draw_mode, top_k, top_p)
+                 utterance_draws=False, draw_mode='sequential', top_k=0, top_p=0.0, log_probs=False, forcing=False,
+                 min_p=0.0):
+        device_loop_guard(draw_mode, top_k, top_p, min_p)
         self.log_probs = bool(log_probs)
         self.forcing = bool(forcing)   # the generator's own device plan takes prompts (a runner of the caller's always may)
         self._forcing = False          # some utterance was submitted with a prompt
@@ -192,6 +210,8 @@ class StreamingGenerator:
         self._truncates = self.top_k != 0
         self.top_p = top_p_code(top_p)
         self._nucleus = 0.0 < self.top_p < 1.0
+        self.min_p = min_p_code(min_p)
+        self._min_p = self.min_p > 0.0
         self.B, self.S = int(n_streams), int(segment_frames)
         if self.B < 1:
             raise ValueError("n_streams must be at least 1")
@@ -203,7 +223,8 @@ class StreamingGenerator:
         if run_segment is None:
             self.gen = DeviceGenerator(self.B, self.S + 1, temperature=temperature, seed=seed, use_graph=use_graph,
                                        packed=True, utterance_draws=self.utterance_draws, draw_mode=draw_mode,
-                                       top_k=self.top_k, top_p=self.top_p, forcing=self.forcing, log_probs=self.log_probs)
+                                       top_k=self.top_k, top_p=self.top_p, forcing=self.forcing, log_probs=self.log_probs,
+                                       min_p=self.min_p)
             run_segment = self._run_on_device
         self._run = run_segment
         self._resume = False
@@ -215,16 +236,20 @@ class StreamingGenerator:
         self._draws = {}               # ticket -> (seed, temperature), until the utterance's start flag has been placed
         self._top_ks = {}              # ticket -> top_k, likewise (utterance_draws only)
         self._top_ps = {}              # ticket -> top_p, likewise
+        self._min_ps = {}              # ticket -> min_p, likewise
         self._prompts = {}             # ticket -> its prompt, until the utterance is done
         self.record = {}
 
-    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None, top_ps=None, forced=None):
+    def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None, top_ps=None, forced=None,
+                       min_ps=None):
         # (without utterance_draws the plan has no entries: every utterance draws with the plan's top_k)
         draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
         if seeds is not None and top_ks is not None:
             draws['top_ks'] = top_ks
         if seeds is not None and top_ps is not None:
             draws['top_ps'] = top_ps
+        if seeds is not None and min_ps is not None:
+            draws['min_ps'] = min_ps
         n, BFS = features.shape[0], config().BIG_FRAME_SIZE
         # (a plan built to take forced samples is handed them in every call: all free until some utterance has a prompt)
         if self.forcing and forced is None:
@@ -241,9 +266,9 @@ class StreamingGenerator:
             more['forced'] = numpy.concatenate([numpy.full((self.B, BFS), FREE, dtype=numpy.int32), forced], axis=1)
         return host(self.gen.generate(features, starts, n_frames=n, **more, **draws), BFS)
 
-    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None, prompt=None):
+    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None, prompt=None, min_p=None):
         """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
-        seed (an unsigned 64-bit integer), temperature, top_k and top_p (defaults: the generator's): with
+        seed (an unsigned 64-bit integer), temperature, top_k, top_p and min_p (defaults: the generator's): with
         utterance_draws=True only, where the seed is required.  prompt: up to 80 * (n - 1) integer codes in
         0 .. Q_LEVELS-1, the utterance's samples 80 ..: it goes on freely behind them."""
         if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
@@ -257,6 +282,10 @@ class StreamingGenerator:
             raise ValueError("a top_p per utterance needs a generator built with utterance_draws=True")
         if top_p is not None:
             top_p = top_p_code(top_p)
+        if min_p is not None and not self.utterance_draws:
+            raise ValueError("a min_p per utterance needs a generator built with utterance_draws=True")
+        if min_p is not None:
+            min_p = min_p_code(min_p)
         features = numpy.asarray(features, dtype='float32')
         if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
             raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
@@ -275,6 +304,8 @@ class StreamingGenerator:
             self._truncates = self._truncates or top_k is not None
             self._top_ps[ticket] = self.top_p if top_p is None else top_p
             self._nucleus = self._nucleus or top_p is not None
+            self._min_ps[ticket] = self.min_p if min_p is None else min_p
+            self._min_p = self._min_p or min_p is not None
         self._features[ticket] = features
         self.queue.append((ticket, features.shape[0]))
         return ticket
@@ -319,6 +350,11 @@ class StreamingGenerator:
             for ticket, b, slot, frame, count in placements:
                 if frame <= 1 < frame + count:
                     draws['top_ps'][start_row(slot - frame, n + 1) - 1, b] = self._top_ps.get(ticket, self.top_p)
+        if self._min_p:
+            draws['min_ps'] = numpy.zeros((n, self.B), dtype=numpy.float32)
+            for ticket, b, slot, frame, count in placements:
+                if frame <= 1 < frame + count:
+                    draws['min_ps'][start_row(slot - frame, n + 1) - 1, b] = self._min_ps.get(ticket, self.min_p)
         if self._forcing:  # sample j of an utterance's buffer is column 80 (slot - 1) + (j - 80 frame) of this segment
             draws['forced'] = numpy.full((self.B, BFS * n), FREE, dtype=numpy.int32)
             for ticket, b, slot, frame, count in placements:
@@ -353,6 +389,7 @@ class StreamingGenerator:
                 self._draws.pop(ticket, None)
                 self._top_ks.pop(ticket, None)
                 self._top_ps.pop(ticket, None)
+                self._min_ps.pop(ticket, None)
                 self._prompts.pop(ticket, None)
             if logp is None:
                 out.append((ticket, chunk, done))

@@ -196,8 +196,9 @@ def getting_generation_functions(sequences=None, h0=None, big_h0=None, reset=Non
 # the generation package's names, as they always were here (it reads the configuration above from this module when called)
 from ...generation import inputs as _inputs  # noqa: E402
 from ...generation.inputs import (DRAW_K1, DRAW_K2, DRAW_MODES, _M64, _per_utterance, _seed_image,  # noqa: E402,F401
-                                  _per_utterance_top_k, _per_utterance_top_p, _splitmix64, build_packed_draws,
-                                  build_packed_inputs, build_packed_top_k, build_packed_top_p, draw_mode_code,
+                                  _per_utterance_min_p, _per_utterance_top_k, _per_utterance_top_p, _splitmix64,
+                                  build_packed_draws, build_packed_inputs, build_packed_min_p, build_packed_top_k,
+                                  build_packed_top_p, draw_mode_code, min_p_active, min_p_array, min_p_code,
                                   pack_utterances, schedule_segment, top_k_array, top_k_code, top_p_active, top_p_array,
                                   top_p_code, unpack_samples, utterance_draw_u01, utterance_seed)
 from ...generation.inputs import (_per_utterance_prompts, build_packed_prompts, forced_array,  # noqa: E402,F401
@@ -233,7 +234,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
                               big_frame_level_generate_fn=None, frame_level_generate_fn=None,
                               sample_level_generate_fn=None, npy_address=None, temperature=TEMPERATURE,
                               use_device_loop=True, pack_streams=0, stream_frames=0, utterance_seed=None,
-                              draw_mode='sequential', top_k=0, top_p=0.0):
+                              draw_mode='sequential', top_k=0, top_p=0.0, min_p=0.0):
     """three_tier.py:750-851.  With use_device_loop (default) the per-sample loop runs on the GPU
     (DeviceGenerator); otherwise the reference's three-function Python loop is executed literally.  Models with
     skip-connection stacks (SKIP_CONN) take the device loop with PARROT_SR_SKIP_STACKS=1 and the literal loop, with its
@@ -259,7 +260,11 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
 
     top_p = p strictly between 0 and 1: those draws are taken among the nucleus of the codes top_k left (DeviceGenerator),
     in all three modes; 0 (default) or >= 1: no nucleus.  An active top_p needs the device loop -- the literal
-    three-function loop refuses it --; a negative one or a NaN is a ValueError."""
+    three-function loop refuses it --; a negative one or a NaN is a ValueError.
+
+    min_p in (0, 1]: of the codes both left, those draws keep the ones at least min_p times as likely as the most likely code
+    (DeviceGenerator), in all three modes; 0 (default): off.  An active min_p needs the device loop -- the literal loop
+    refuses it --; a value outside [0, 1] or a NaN is a ValueError."""
     total_time = time()
     # (the device loop takes skip-connection stacks only with PARROT_SR_SKIP_STACKS=1, read here at call time)
     device_loop = use_device_loop and (not SKIP_CONN or (_inputs.skip_stacks_enabled() and N_RNN >= 2))
@@ -269,6 +274,8 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         raise ValueError("top_k needs the device-resident generator")
     if top_p_active(top_p) and not device_loop:
         raise ValueError("top_p needs the device-resident generator")
+    if min_p_active(min_p) and not device_loop:
+        raise ValueError("min_p needs the device-resident generator")
     per_utt = utterance_seed is not None
     if per_utt and not device_loop:
         raise ValueError("utterance_seed needs the device-resident generator")
@@ -288,7 +295,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
     if placed and stream_frames > 0:
         n_streams = int(pack_streams) if pack_streams > 0 else 32
         sg = StreamingGenerator(n_streams, int(stream_frames), temperature=temperature, utterance_draws=per_utt,
-                                draw_mode=draw_mode, top_k=top_k, top_p=top_p)
+                                draw_mode=draw_mode, top_k=top_k, top_p=top_p, min_p=min_p)
         chunks = [[] for _ in range(n_seqs)]
         pieces = [None] * n_seqs
         try:
@@ -309,7 +316,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         return pieces
     if placed:
         pieces = generate_packed(utts, n_streams=int(pack_streams), temperature=temperature, seeds=seeds,
-                                 draw_mode=draw_mode, top_k=top_k, top_p=top_p)
+                                 draw_mode=draw_mode, top_k=top_k, top_p=top_p, min_p=min_p)
         total_time = time() - total_time
         print("{} samples of {} seconds in all generated in {} seconds ({} packed streams).".format(
             n_seqs, seconds, total_time, int(pack_streams)))
@@ -318,7 +325,7 @@ def generate_and_save_samples(tag, path_to_save=None, features=None, features_le
         return pieces
     if device_loop:
         gen = DeviceGenerator(n_seqs, n_frames, temperature=temperature, utterance_draws=per_utt, draw_mode=draw_mode,
-                              top_k=top_k, top_p=top_p)
+                              top_k=top_k, top_p=top_p, min_p=min_p)
         draws = dict(seeds=seeds, temperatures=float(temperature)) if per_utt else {}
         samples = gen.generate(test_feats, **draws).cpu().numpy()
         gen.close()

@@ -5,7 +5,7 @@ and out of scope.
 
 Extra flags (not in the reference): --num_layers, --cell_type, --compute_dtype, --encoder_literal, --synthetic_examples, --max_steps,
 --device, --use_graph; sample.py: --decode_dtype, --stop_at_end, --pack_streams, --stream_frames,
---utterance_seed, --draw_mode, --top_k, --top_p.
+--utterance_seed, --draw_mode, --top_k, --top_p, --min_p.
 """
 from __future__ import annotations
 
@@ -152,6 +152,10 @@ def sample_parse(argv=None):
                              "are taken among the nucleus -- the most likely codes (of those --top_k left) that together "
                              "hold P of the probability, ties at the cut-off to the lower code --, in both draw modes; 0 or "
                              ">= 1: no nucleus (DESIGN.md 3.6)")
+    parser.add_argument('--min_p', type=float, default=0.0,
+                        help="M in (0, 1] (with --raw_output): of the codes --top_k and --top_p left, the SampleRNN vocoder's "
+                             "draws at temperature > 0 keep those at least M times as likely as the most likely code, in both "
+                             "draw modes; 0: off (DESIGN.md 3.6)")
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:

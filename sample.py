@@ -96,7 +96,8 @@ def main(argv=None):
         parrot.sampleRnn.sample_raw(gen_x.swapaxes(0, 1).copy(), features_lengths, args.samples_name, to_save_path,
                                    pack_streams=args.pack_streams, stream_frames=args.stream_frames,
                                    utterance_seed=args.utterance_seed if args.utterance_seed >= 0 else None,
-                                   draw_mode=args.draw_mode, top_k=args.top_k, top_p=args.top_p)
+                                   draw_mode=args.draw_mode, top_k=args.top_k, top_p=args.top_p,
+                                   min_p=args.min_p)
         print("Successfully sampled raw audio...")
     out_dir = os.path.join(args.save_dir, 'samples')
     for idx, this_sample in enumerate(gen_x):

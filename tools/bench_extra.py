@@ -10,7 +10,7 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          decode_bf16_gru3_1024, decode_bf16_gru2_1536, decode_bf16_gru3_1536,
                                          samplernn_cfg5, samplernn_groups, samplernn_packed, samplernn_stream,
                                          samplernn_utt_draws, samplernn_draw_scan, samplernn_top_k, samplernn_top_p,
-                                         samplernn_forced, samplernn_skip, mulaw)
+                                         samplernn_min_p, samplernn_forced, samplernn_skip, mulaw)
   bench_extra.py --only samplernn_groups [--reps N] [--groups-json FILE]
                                          SampleRNN at D = 1024 and B = 32 (anchor), 64, 128, 200: the persistent sample
                                          kernel in row groups (PARROT_SR_PERSIST_GROUPS=8) against the launch path, N
@@ -68,6 +68,17 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          in the same alternation, bit identity included, and the bar "scan at p = 0.9 stays
                                          faster than the parent's untruncated sequential draw"; the result also goes to FILE
                                          (default profiles/samplernn_top_p.json)
+  bench_extra.py --only samplernn_min_p [--reps N] [--min-p-json FILE] [--parent-lib FILE]
+                                         SampleRNN at D = 1024 and B = 32, 8000 samples per stream: argmax; at temperature 1
+                                         the sequential and the wave-parallel draw, each among all codes, with min_p = 0.1
+                                         (DeviceGenerator(min_p=0.1)) from the plan's value and from per-utterance entries
+                                         (generate(..., min_ps=)), with top_k = 64 and with top_p = 0.9; a draw_stats=True plan
+                                         beside a forcing=True, log_probs=True plan; N alternations in one process, each with
+                                         its spread; the cost of each selection per mode and the bar "a min_p draw costs less
+                                         than a top_k = 64 draw in the same mode"; with --parent-lib (the parent commit's
+                                         libparrot_hip.so) the default path of both libraries at temperature 0 and 1 in the
+                                         same alternation, bit identity included; the result also goes to FILE (default
+                                         profiles/samplernn_min_p.json)
   bench_extra.py --only samplernn_forced [--reps N] [--forced-json FILE] [--parent-lib FILE]
                                          SampleRNN at D = 1024 and B = 32, 8000 samples per stream: the default plan at
                                          temperature 0 and 1, a forcing plan with every code -1, a forcing plan with every
@@ -110,7 +121,7 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_forced", "samplernn_skip", "mulaw")
+       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_min_p", "samplernn_forced", "samplernn_skip", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1031,6 +1042,132 @@ if "samplernn_top_p" in only:
             "sum_of_the_two_spreads_us": round(both, 3),
             "holds": bool(med["parent_sequential_t1"] - med["scan_t1_p90"] > both)}
     record("samplernn_top_p", "--top-p-json", res)
+
+# ---- SampleRNN D=1024, B=32: min-p draws (samplernn_generate_set_min_p, DeviceGenerator(min_p=)) at temperature 1 in both draw
+# modes -- untruncated, min_p = 0.1 with the plan's value and with per-utterance entries, and in the same run top_k = 64 and
+# top_p = 0.9 --; a draw_stats=True plan against a forcing=True, log_probs=True plan; and, with --parent-lib, the default path
+# against the parent commit's library.  All plans alive in one process and run alternately, as samplernn_top_p.
+if "samplernn_min_p" in only:
+    import contextlib
+    import ctypes
+    from parrot_amd import _lib as plib
+    tt = samplernn_d1024()
+    T, SEED, K, P, M, reps = 101, 234, 64, 0.9, 0.1, int(_arg("--reps", "5"))
+    nsamp = (T - 1) * 80
+    feats = torch.randn(T, 32, 63, generator=g).numpy()
+    free = np.full((32, 80 * T), -1, dtype=np.int32)
+    key_seeds = [(SEED ^ (tt.DRAW_K2 * (b + 1))) & (2 ** 64 - 1) for b in range(32)]
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            if hasattr(parent_lib, name):  # (the parent has none of the new setters: its plans never call them)
+                fn = getattr(parent_lib, name)
+                fn.restype = res_
+                fn.argtypes = args_
+
+    @contextlib.contextmanager
+    def under(which):  # every call of a plan goes to the library that made it
+        plib._lib = which
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+
+    def plan(which=this_lib, **kw):
+        with under(which):
+            return tt.DeviceGenerator(32, T, seed=SEED, **kw)
+
+    draws = dict(seeds=key_seeds, temperatures=1.0)
+    # name: (plan, its library, generate's keywords)
+    plans = {"argmax": (plan(temperature=0.0), this_lib, {})}
+    for mode in ("sequential", "scan"):
+        plans[mode + "_t1"] = (plan(temperature=1.0, draw_mode=mode), this_lib, {})
+        plans[mode + "_t1_m10"] = (plan(temperature=1.0, draw_mode=mode, min_p=M), this_lib, {})
+        plans[mode + "_t1_k64"] = (plan(temperature=1.0, draw_mode=mode, top_k=K), this_lib, {})
+        plans[mode + "_t1_p90"] = (plan(temperature=1.0, draw_mode=mode, top_p=P), this_lib, {})
+        plans["utt_" + mode + "_t1"] = (plan(utterance_draws=True, draw_mode=mode), this_lib, draws)
+        plans["utt_" + mode + "_t1_m10"] = (plan(utterance_draws=True, draw_mode=mode), this_lib, dict(draws, min_ps=[M] * 32))
+        plans[mode + "_t1_m10_draw_stats"] = (plan(temperature=1.0, draw_mode=mode, min_p=M, draw_stats=True), this_lib, {})
+        plans[mode + "_t1_m10_forcing_log_probs"] = (plan(temperature=1.0, draw_mode=mode, min_p=M, forcing=True, log_probs=True),
+                                                     this_lib, dict(forced=free))
+    if parent_lib is not None:
+        plans["parent_argmax"] = (plan(which=parent_lib, temperature=0.0), parent_lib, {})
+        plans["parent_sequential_t1"] = (plan(which=parent_lib, temperature=1.0), parent_lib, {})
+        # (a second plan of each kind, created in the other order: the floor under any difference between the libraries)
+        plans["argmax_again"] = (plan(temperature=0.0), this_lib, {})
+        plans["sequential_t1_again"] = (plan(temperature=1.0), this_lib, {})
+        plans["parent_sequential_t1_again"] = (plan(which=parent_lib, temperature=1.0), parent_lib, {})
+        plans["parent_argmax_again"] = (plan(which=parent_lib, temperature=0.0), parent_lib, {})
+    assert all(gen.persist_groups == 1 for gen, _, _ in plans.values())
+    times, samples, extra = {k: [] for k in plans}, {}, {}
+    keys = list(plans)
+    for rep_ in range(reps + 1):  # (the first alternation captures the graphs: not counted)
+        for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:  # (no plan always runs behind the same other one)
+            gen, which, kw = plans[k]
+            with under(which):
+                torch.cuda.synchronize(); t0 = time.time()
+                s = gen.generate(feats, **kw)
+                torch.cuda.synchronize(); dt = time.time() - t0
+                if isinstance(s, tuple):
+                    s, extra[k] = s[0], [x.cpu().numpy().copy() for x in s[1:]]
+                samples[k] = s.cpu().numpy().copy()
+            if rep_:
+                times[k].append(dt)
+    for gen, which, _ in plans.values():
+        with under(which):
+            gen.close()
+    us = {k: [1e6 * dt / nsamp for dt in v] for k, v in times.items()}
+    med = {k: sorted(v)[len(v) // 2] for k, v in us.items()}
+    spread = {k: max(v) - min(v) for k, v in us.items()}
+    two = ("sequential", "scan")
+
+    def cheaper(mode, other):  # bar (i): against something measured in this same run
+        a, b = mode + "_t1_m10", mode + "_t1_" + other
+        return {"min_p_us": round(med[a], 3), other + "_us": round(med[b], 3), "min_p_minus_" + other + "_us": round(med[a] - med[b], 3),
+                "sum_of_the_two_spreads_us": round(spread[a] + spread[b], 3), "min_p_costs_less": bool(med[a] < med[b])}
+
+    res = {"dim": 1024, "streams": 32, "min_p": M, "top_k": K, "top_p": P, "alternations": reps, "samples_per_stream": nsamp,
+           "timed": "call to device idle (host-side input copies included)",
+           "runs": {k: {"us_per_sample_step": [round(x, 3) for x in us[k]], "us_per_sample_step_median": round(med[k], 3),
+                        "spread_max_minus_min": round(spread[k], 3)} for k in plans},
+           "cost_of_the_selection_us_per_sample_step": {
+               "min_p": {m: round(med[m + "_t1_m10"] - med[m + "_t1"], 3) for m in two + ("utt_sequential", "utt_scan")},
+               "top_k": {m: round(med[m + "_t1_k64"] - med[m + "_t1"], 3) for m in two},
+               "top_p": {m: round(med[m + "_t1_p90"] - med[m + "_t1"], 3) for m in two}},
+           "bar_i_min_p_costs_less_than_top_k": {m: cheaper(m, "k64") for m in two},
+           "min_p_against_top_p": {m: cheaper(m, "p90") for m in two},
+           "min_p_samples_that_differ_from_untruncated": {m: int((samples[m + "_t1_m10"] != samples[m + "_t1"]).sum()) for m in two},
+           "utt_bit_identical_to_plan": {m: bool(np.array_equal(samples["utt_" + m + "_t1_m10"], samples[m + "_t1_m10"])) for m in two},
+           "draw_stats_against_forcing_and_log_probs": {
+               m: {"draw_stats_us": round(med[m + "_t1_m10_draw_stats"], 3),
+                   "forcing_log_probs_us": round(med[m + "_t1_m10_forcing_log_probs"], 3),
+                   "plain_min_p_us": round(med[m + "_t1_m10"], 3),
+                   "samples_bit_identical_to_plain": bool(np.array_equal(samples[m + "_t1_m10_draw_stats"], samples[m + "_t1_m10"])),
+                   "kept_min_median_max": [int(np.min(extra[m + "_t1_m10_draw_stats"][1][:, 80:])),
+                                           int(np.median(extra[m + "_t1_m10_draw_stats"][1][:, 80:])),
+                                           int(np.max(extra[m + "_t1_m10_draw_stats"][1][:, 80:]))]} for m in two},
+           "not_measured": ["row groups (two and eight)", "the launch path's timing", "the streaming generator end to end",
+                            "D = 256 and D = 512", "min_p other than 0.1, combinations of the three truncations"]}
+    if parent_lib is not None:
+        def pair(t):  # the bar of the issue (the two first plans, the sum of their spreads) and the four plans' picture beside it
+            a, b = (med[t], med[t + "_again"]), (med["parent_" + t], med["parent_" + t + "_again"])
+            both = spread[t] + spread["parent_" + t]
+            return {"this_us": [round(x, 3) for x in a], "parent_us": [round(x, 3) for x in b],
+                    "this_minus_parent_us": round(a[0] - b[0], 3), "sum_of_the_two_spreads_us": round(both, 3),
+                    "bar_default_within_the_sum_of_both_spreads": bool(abs(a[0] - b[0]) <= both),
+                    "mean_of_two_plans_this_minus_parent_us": round(sum(a) / 2 - sum(b) / 2, 3),
+                    "largest_difference_between_two_plans_of_one_library_us": round(max(abs(a[0] - a[1]), abs(b[0] - b[1])), 3)}
+        res["default_path_against_parent_commit"] = {
+            "how": "this build and the parent commit's library loaded in one process, two plans of each per temperature (the "
+                   "second pair created in the other order), all in the same alternation; the bar compares the first plan of "
+                   "each library against the sum of their spreads (max - min over the alternations)",
+            "bit_identical_t0": bool(np.array_equal(samples["argmax"], samples["parent_argmax"])),
+            "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
+            "t0": pair("argmax"), "t1": pair("sequential_t1")}
+    record("samplernn_min_p", "--min-p-json", res)
 
 # ---- SampleRNN D=1024, B=32: forced samples and per-sample log-probabilities (samplernn_generate_set_forced / _set_log_probs,
 # DeviceGenerator(forcing=, log_probs=)) -- the default plan at temperature 0 and 1, a forcing plan with every code -1, a
