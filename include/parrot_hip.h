@@ -315,8 +315,14 @@ typedef struct ParrotDecoderDesc {
     float* a; float* b;            /* [T,B,A] */
     float* phi;                    /* [T,B,U] */
     /* backward */
-    float* dh[PARROT_MAX_LAYERS];  /* [T+1,B,H] in: gradient from the readouts per slot; out: total */
-    float* dw;                     /* [T+1,B,E] in: gradient from att_to_readout per slot; out: total */
+    float* dh[PARROT_MAX_LAYERS];  /* [T+1,B,H] in: gradient from the readouts per slot (slot 0 included: it is added to).
+                                      out: slot 0 = total wrt the state entering the window (plus dh_b[l][0] when given);
+                                      slots s >= 1 = a partial sum: the total wrt h_l[s] is dh[l][s] + dhup[l][s]
+                                      (+ dh_b[l][s] + dhup_b[l][s] + dhup_c[l][s] when given), which the state backward
+                                      of step s-1 forms while it reads and never writes back */
+    float* dw;                     /* [T+1,B,E] in: gradient from att_to_readout per slot; out: slots s >= 1 = total wrt
+                                      w[s]; slot 0 keeps its in-value: the total wrt w[0] is dw[0] + dw0[0] (+ slot 0 of
+                                      dw_b, dw_c, dw0_b, dw0_c when given) */
     float* dw0;                    /* [T+1,B,E] scratch, zero-filled by the caller: layer-0 share of dw */
     float* dhup[PARROT_MAX_LAYERS];/* [T+1,B,H] scratch, zero-filled by the caller: share of dh[l] that comes from
                                       the layers above (needed for l < L-1) */
@@ -361,7 +367,8 @@ typedef struct ParrotDecoderDesc {
     const float* Wc_r[PARROT_MAX_LAYERS];
     /* Optional [T,B,2] int32 scratch: per step and row the first / last context position whose window weight phi is
      * not exactly 0.0f (written by seq_fwd, read by seq_bwd).  Rows outside it are multiplied by exact zeros in
-     * model.py:675-690 and its gradient, so the scan does not read them; NULL: all U rows are read. */
+     * model.py:675-690 and its gradient, so the scan does not read them; NULL: all U rows are read.  An all-zero row saves
+     * the empty support (U, -1); under PARROT_ATT_DENSE=1 every row saves the full range (0, U-1). */
     int* att_sup;
     /* Optional workspace of the persistent forward scan (PARROT_SCHEDULE=4): at least
      * parrot_decoder_persist_floats(desc) floats, ZERO-FILLED by the caller once.  It holds the machine's
@@ -409,7 +416,8 @@ int parrot_decoder_is_persistent(void* plan);
 int parrot_decoder_schedule(void* plan);
 /* Which backward tick the plan runs: 8 = the K-balanced tick with the downward products of the upper layers inside the
  * attention launch (GRU stacks of 2 or 3 layers, f32: reference depth model.py:312-347), 7 = the fused LSTM tick of
- * bf16-operand decoders, 0 = three launches per tick (attention + state backward, X, Y). */
+ * bf16-operand decoders, 0 = three launches per tick (attention + state backward, X, Y); schedule 3 runs the mirror of its
+ * chunked forward pipeline and reports 0 whatever accumulators it is given. */
 int parrot_decoder_backward_tick(void* plan);
 /* Schedule tracing (test infrastructure of the library itself; runs without a GPU): instead of launching, the plan
  * records for every launch of direction `which` (0 forward, 1 backward) and every job in it the byte ranges of the

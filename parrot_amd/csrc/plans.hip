@@ -1247,9 +1247,9 @@ struct DecoderPlan : PlanBase {
         // -- schedule 4: persist_ok stays false when the shape / workspace does not qualify
         if (want_persist && d.cell == 0 && !d.layer_norm && !d.bf16) build_persist();
         // -- the K-balanced backward tick (bwd8): f32 GRU decoders of 2 or 3 layers with fragment-major weights and all
-        // accumulators (PARROT_BWD_HETERO=0 opts out)
+        // accumulators (PARROT_BWD_HETERO=0 opts out).  Schedule 3 runs its own backward (bwd_skew), whatever it is given.
         {
-            bool ok = d.cell == 0 && (L == 2 || L == 3) && !d.bf16 && !d.layer_norm && tiled && B <= 64 &&
+            bool ok = d.cell == 0 && (L == 2 || L == 3) && !d.bf16 && !d.layer_norm && tiled && B <= 64 && schedule != 3 &&
                       d.dw_b && d.dw_c && d.dw0_b && d.dw0_c && env_int("PARROT_BWD_HETERO", 1) != 0;
             for (int l = 0; l < L; ++l)
                 if (!d.dh_b[l] || (l + 1 < L && (!d.dhup_b[l] || !d.dhup_c[l]))) ok = false;

@@ -16,6 +16,8 @@ import os
 
 import pytest
 
+from tests.decoder_scan_cases import arena_descriptor
+
 
 def _lib():
     from parrot_amd import _lib as L
@@ -25,25 +27,12 @@ def _lib():
         pytest.skip("libparrot_hip.so not built")
 
 
-class _Arena:
-    """Fake device address space: distinct, 4 KB aligned ranges; name -> (lo, hi)."""
-
-    def __init__(self):
-        self.top = 0x10000000
-        self.ranges = {}
-
-    def take(self, name, nbytes):
-        lo = self.top
-        self.top = (lo + max(nbytes, 16) + 4095) // 4096 * 4096 + 4096
-        self.ranges[name] = (lo, lo + nbytes)
-        return lo
-
-
 def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, E=16, A=4, U=7, bf16=0, hetero=False,
                layer_norm=0, ln_buffers=True, accum=None, expect_rc=0):
     """accum: None = the accumulators the descriptor's own backward tick wants (second for bf16 LSTM stacks, second and
     third with `hetero`); 0 / 1 / 2 = none / second / second and third, whatever the descriptor.  expect_rc != 0: the
-    create call must refuse with that code (returns no plan)."""
+    create call must refuse with that code (returns no plan).  The descriptor on fake addresses is
+    tests.decoder_scan_cases.arena_descriptor's."""
     if accum is None:
         accum = 2 if hetero else (1 if (bf16 and cell == 1) else 0)
     if sched is None:
@@ -51,73 +40,8 @@ def _make_plan(L, lib, sched, cell, nl, seq_init, monkeypatch, T=5, B=20, H=32, 
     else:
         monkeypatch.setenv("PARROT_SCHEDULE", str(sched))
     monkeypatch.setenv("PARROT_TRACE_ONLY", "1")
-    ar = _Arena()
-    d = L.DecoderDesc()
-    d.T, d.B, d.H, d.E, d.A, d.U, d.L = T, B, H, E, A, U, nl
-    d.cell, d.use_graph, d.seq_init, d.bf16, d.layer_norm = cell, 0, seq_init, bf16, layer_norm
-    d.eps, d.alignment, d.sharpening, d.timing = 1e-5, 1.0, 1.0, 1.0
-    f = 4
-    gw = 4 * H if cell == 1 else 2 * H
-    for l in range(nl):
-        K = H + E + l * H
-        d.Wg[l] = ar.take(f"Wg{l}", K * gw * f)
-        d.bg[l] = ar.take(f"bg{l}", gw * f)
-        d.Wg_f[l] = ar.take(f"Wg_f{l}", K * gw * f)
-        d.Wg_r[l] = ar.take(f"Wg_r{l}", K * gw * f)
-        d.h[l] = ar.take(f"h{l}", (T + 1) * B * H * f)
-        d.dh[l] = ar.take(f"dh{l}", (T + 1) * B * H * f)
-        d.dG[l] = ar.take(f"dG{l}", T * B * gw * f)
-        if l < nl - 1:
-            d.dhup[l] = ar.take(f"dhup{l}", (T + 1) * B * H * f)
-        if bf16 and cell == 1:  # bf16 copies of the pre-activation gradients, written by the fused backward tick (round 5)
-            d.dG16[l] = ar.take(f"dG16_{l}", T * B * gw * 2)
-        if accum >= 1:  # second (and third) accumulators: the backward products run as K parts
-            d.dh_b[l] = ar.take(f"dh_b{l}", (T + 1) * B * H * f)
-            if l < nl - 1:
-                d.dhup_b[l] = ar.take(f"dhup_b{l}", (T + 1) * B * H * f)
-                if accum >= 2:
-                    d.dhup_c[l] = ar.take(f"dhup_c{l}", (T + 1) * B * H * f)
-        if l >= 1 or (seq_init >> l) & 1:
-            d.seq_g[l] = ar.take(f"seq_g{l}", T * B * gw * f)
-        if cell == 0:
-            d.Wc[l] = ar.take(f"Wc{l}", K * H * f)
-            d.bc[l] = ar.take(f"bc{l}", H * f)
-            d.Wc_f[l] = ar.take(f"Wc_f{l}", K * H * f)
-            d.Wc_r[l] = ar.take(f"Wc_r{l}", K * H * f)
-            for n in ("z", "r", "rh", "c"):
-                getattr(d, n)[l] = ar.take(f"{n}{l}", T * B * H * f)
-            d.dC[l] = ar.take(f"dC{l}", T * B * H * f)
-            if l >= 1 or (seq_init >> l) & 1:
-                d.seq_c[l] = ar.take(f"seq_c{l}", T * B * H * f)
-        else:
-            d.cst[l] = ar.take(f"cst{l}", (T + 1) * B * H * f)
-            d.gate4[l] = ar.take(f"gate4{l}", T * B * 4 * H * f)
-            d.dcell[l] = ar.take(f"dcell{l}", B * H * f)
-        for j in range(l if (layer_norm and ln_buffers) else 0):  # layer_norm: the normalised projection of h_j into layer l
-            pj = l * len(d.Wg) + j
-            for g, wd in (("g", gw),) + ((("c", H),) if cell == 0 else ()):
-                getattr(d, f"ln_y{g}")[pj] = ar.take(f"ln_y{g}{l}{j}", T * B * wd * f)
-                getattr(d, f"ln_s{g}")[pj] = ar.take(f"ln_s{g}{l}{j}", T * B * f)
-                getattr(d, f"ln_b{g}")[pj] = ar.take(f"ln_b{g}{l}{j}", wd * f)
-    d.WattT = ar.take("WattT", 3 * A * H * f)
-    d.batt = ar.take("batt", 3 * A * f)
-    d.ctx = ar.take("ctx", B * U * E * f)
-    d.w = ar.take("w", (T + 1) * B * E * f)
-    d.kappa = ar.take("kappa", (T + 1) * B * A * f)
-    d.a = ar.take("a", T * B * A * f)
-    d.b = ar.take("b", T * B * A * f)
-    d.phi = ar.take("phi", T * B * U * f)
-    d.dw = ar.take("dw", (T + 1) * B * E * f)
-    d.dw0 = ar.take("dw0", (T + 1) * B * E * f)
-    if accum >= 1:
-        d.dw_b = ar.take("dw_b", (T + 1) * B * E * f)
-        d.dw0_b = ar.take("dw0_b", (T + 1) * B * E * f)
-        if accum >= 2:
-            d.dw_c = ar.take("dw_c", (T + 1) * B * E * f)
-            d.dw0_c = ar.take("dw0_c", (T + 1) * B * E * f)
-    d.dkappa = ar.take("dkappa", B * A * f)
-    d.dp = ar.take("dp", T * B * 3 * A * f)
-    d.att_sup = ar.take("att_sup", T * B * 2 * 4)
+    ar, d = arena_descriptor(L, cell, nl, seq_init, T=T, B=B, H=H, E=E, A=A, U=U, bf16=bf16, layer_norm=layer_norm,
+                             ln_buffers=ln_buffers, accum=accum)
     plan = C.c_void_p()
     rc = lib.parrot_decoder_create(C.byref(d), C.byref(plan))
     assert rc == expect_rc, rc
