@@ -119,6 +119,25 @@ int parrot_gemm_route(const float* A, int lda, int transA, const float* B, int l
  * which takes some bf16-operand launches instead, is not part of the query. */
 int parrot_step_launch_mode(int njobs, const int* M, const int* N, const int* K, const int* lstm_H, int* info);
 
+/* ONE step-kernel job as one launch of its own (the scan plans build their launches themselves; this is the kernel alone,
+ * for tests and probes): acc[M, N] = sum over nseg (1..5) K segments of A[s][M, K[s]] (row-major, leading dimension
+ * lda[s]) times the segment's weights, then the epilogue `epi`.  layout, one for all segments: 0 = B[s][k * ldb + n],
+ * 1 = B[s][n * ldb + k], 2 = fragment-major copy (parrot_tile_weights; ldb[s] = floats between consecutive column tiles
+ * = K[s] / 16 * 256), 3 = its bf16 twin (parrot_tile_weights_bf16; ldb[s] = K[s] / 32 * 256, counted in 4-byte units).
+ * M <= 64 rows per 64-row grid row as in the plans; force_tile = 10 * MB + NB asks for (16 MB) x (16 NB) tiles where
+ * legal (0: the host's choice).  Epilogues (every cell buffer [M, H] with leading dimension H):
+ *   0 linear:     out[M, N] (ld ldo) (+)= act(acc + bias + add)   (accumulate adds the prior content AFTER act)
+ *   1 GRU gates:  N = 2 H: z = sigmoid(.) -> o1, r = sigmoid(.) -> o2, r * e0 (h_prev) -> out
+ *   2 GRU cand.:  N = H:   c = tanh(.) -> o1 (or NULL), e1 (z) * c + (1 - e1) * e0 (h_prev) -> out
+ *   3 backward:   N = H:   acc = d(r * h_prev): acc * e0 (h_prev) * e1 (r) * (1 - e1) -> out (ld ldo), o1 += acc * e1
+ *   4 LSTM cell:  N = 4 H gate-interleaved columns: activations -> o2 [M, 4H] (or NULL), e1 (c_prev) * f + g * i -> o1,
+ *                 tanh(o1) * o -> out
+ * bias [N] and add [M, N] (ld ld_add) may be NULL. */
+int parrot_step_job(int epi, int M, int N, int H, int nseg, const float* const* A, const int* lda, const void* const* B,
+                    const int* ldb, const int* K, int layout, int act, int accumulate, int force_tile, const float* bias,
+                    const float* add, int ld_add, float* out, int ldo, const float* e0, const float* e1, float* o1, float* o2,
+                    void* stream);
+
 /* bf16-IN weight-gradient product (round 4): C[M,N] (+)= A^T . B with A [K, M] and B [K, N] ALREADY bf16 in device
  * memory (row-major, leading dimensions in elements, both multiples of 8; M, N multiples of 8; 16-byte aligned),
  * f32 accumulation, f32 C; deterministic split-K as parrot_gemm (split_k = 0: automatic).  parrot_to_bf16 makes the

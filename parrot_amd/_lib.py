@@ -191,6 +191,8 @@ SIGNATURES = {
     "parrot_gemm_route": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _ll, _ll, _i, _i,
                                C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "parrot_step_launch_mode": (_i, [_i] + [C.POINTER(C.c_int)] * 5),
+    "parrot_step_job": (_i, [_i, _i, _i, _i, _i, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i),
+                             _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "parrot_gather_sum_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _ll, _i, _i, _i, _vp]),
     "parrot_gather_sum_bwd_ws_floats": (C.c_longlong, [_ll, _i, _i, _i]),
     "parrot_gather_sum_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _ll, _ll, _i, _i, _i, _i, _vp]),

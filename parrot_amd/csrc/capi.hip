@@ -255,6 +255,50 @@ int parrot_step_launch_mode(int njobs, const int* M, const int* N, const int* K,
     return 0;
 }
 
+int parrot_step_job(int epi, int M, int N, int H, int nseg, const float* const* A, const int* lda, const void* const* B,
+                    const int* ldb, const int* K, int layout, int act, int accumulate, int force_tile, const float* bias,
+                    const float* add, int ld_add, float* out, int ldo, const float* e0, const float* e1, float* o1, float* o2,
+                    void* stream) { PH_ENTRY();
+    if (!A || !lda || !B || !ldb || !K || !out || nseg < 1 || nseg > SK_MAXSEG || M < 1 || N < 1 || H < 1 || layout < 0 ||
+        layout > 3 || act < 0 || act > SK_ACT_SIGMOID)
+        return PARROT_ERR_BADARG;
+    SkJob j;
+    switch (epi) {
+        case SK_EPI_LINEAR: sk_linear_job(j, M, N, H, out, ldo, accumulate ? 1 : 0); break;
+        case SK_EPI_GRU_GATES:
+            if (!e0 || !o1 || !o2 || N != 2 * H) return PARROT_ERR_BADARG;
+            sk_gru_gates_job(j, M, H, e0, o1, o2, out);
+            break;
+        case SK_EPI_GRU_CAND:
+            if (!e0 || !e1 || N != H) return PARROT_ERR_BADARG;
+            sk_gru_cand_job(j, M, H, e0, e1, o1, out);
+            break;
+        case SK_EPI_BWD_RH:
+            if (!e0 || !e1 || !o1 || N != H) return PARROT_ERR_BADARG;
+            sk_bwd_rh_job(j, M, H, e0, e1, out, ldo, o1);
+            break;
+        case SK_EPI_LSTM:
+            if (!e1 || !o1 || N != 4 * H) return PARROT_ERR_BADARG;
+            sk_lstm_job(j, M, H, e1, o1, o2, out);
+            break;
+        default: return PARROT_ERR_BADARG;
+    }
+    j.nseg = nseg;
+    for (int s = 0; s < nseg; ++s) {
+        if (!A[s] || !B[s] || K[s] < 1) return PARROT_ERR_BADARG;
+        j.seg[s] = sk_seg(A[s], lda[s], static_cast<const float*>(B[s]), ldb[s], K[s], layout);
+    }
+    j.act = act;
+    j.bias = bias;
+    j.add = add;
+    j.ld_add = ld_add;
+    SkLaunch L;
+    const int rc = sk_make_launch(L, &j, 1);
+    if (rc) return rc;
+    L.force_tile = force_tile;
+    return sk_launch(L, (hipStream_t)stream);
+}
+
 int parrot_to_bf16(const float* x, void* y, long long n, void* stream) { PH_ENTRY();
     if (!x || !y || n < 0) return PARROT_ERR_BADARG;
     return bg_to_bf16_launch(x, y, n, (hipStream_t)stream);

@@ -8,10 +8,19 @@
 #pragma once
 #include "common.h"
 
-#ifndef SK_NWAVES
-#define SK_NWAVES 8
+// SK_NW / SK_THREADS: the eight waves the wide bf16 kernels (wk_*) and the attention forward block are written for.
+// SK_KW / SK_KTHREADS: the waves that share the K range of a split-K step workgroup (sk_body), a build constant.  ONE deal
+// for every kernel that runs sk_body (sk_kernel, ska_kernel, skb_kernel): the partial tiles are added in wave order, so a
+// wave count that differed by launch type would give the same product other bits at a window's edge ticks than in its
+// steady state.  Sixteen (four waves per SIMD: -DSK_KWAVES=16 builds and passes the tests, except that the 64 x 32 tile
+// nothing selects then spills) was measured on MI355X and lost: 9.6 - 9.8 us per gate / candidate launch against 9.2 - 9.4
+// at eight.  The K loop itself ends earlier on the first waves, but a SIMD's four waves finish one after the other (its
+// matrix pipe is what they share), the workgroup meets when the last is done -- no earlier than with eight -- and twice the
+// waves run the scalar prologue and add twice the partial tiles (profiles/step_refill_fence_sixteen_waves_timers.txt).
+#ifndef SK_KWAVES
+#define SK_KWAVES 8
 #endif
-enum { SK_MAXSEG = 5, SK_MAXJOB = 9, SK_NW = SK_NWAVES, SK_THREADS = SK_NW * 64 };
+enum { SK_MAXSEG = 5, SK_MAXJOB = 9, SK_NW = 8, SK_THREADS = SK_NW * 64, SK_KW = SK_KWAVES, SK_KTHREADS = SK_KW * 64 };
 
 enum SkEpi {
     SK_EPI_LINEAR = 0,     // out = act(acc + bias + add) (optionally accumulated into out)

@@ -7,17 +7,18 @@
 // launch, no LDS staging (nothing is shared between waves), f32 MFMA 16x16x4 does the math
 // (exact f32, the reference computes in floatX = float32, model.py:21).
 //
-// Decomposition (wave64, 8 waves = 512 threads per workgroup):
+// Decomposition (wave64, SK_KW = 8 waves = 512 threads per workgroup; sixteen -- four per SIMD -- build and were measured
+// slower, skinny.h):
 //   * one workgroup owns a 64(M) x 16(N) output tile; grid.x enumerates the 16-column tiles of
 //     up to four independent jobs (e.g. the gate GEMMs of different layers), grid.y the 64-row
 //     chunks of the batch;
-//   * the K range is split round-robin in 16-deep chunks over the 8 waves (intra-workgroup
+//   * the K range is split round-robin in 16-deep chunks over the SK_KW waves (intra-workgroup
 //     split-K); every wave keeps MB (<=4) 16x16 accumulators = all 64 rows of the tile;
 //   * per chunk a lane (kk = lane>>4, i = lane&15) loads one 16-byte vector of A per 16-row block
 //     (row i, k = kc+4kk..+3) and the matching B values, then issues 4*MB MFMAs, using vector
 //     component u as the k = kc+4kk+u step.  Any bijection k <-> (step, kk) is legal because the
 //     MFMA sums over kk and we sum over steps;
-//   * partial tiles are reduced through LDS (32 KiB), then 256 threads run the fused epilogue:
+//   * partial tiles are reduced through LDS (32 KiB for 32 x 32), then the fused epilogue runs, dealt over the waves:
 //     sigmoid / tanh / state blend of the GRU (Blocks GatedRecurrent; twin in
 //     sampleRNN/lib/ops.py:364-393), its backward counterpart, or the LSTM cell (ops.py:505-553).
 #include "skinny.h"
@@ -84,6 +85,21 @@ __device__ __forceinline__ void sk_fetch(const SkSeg& sg, int kc, int m0, int M,
 // not help (the clamped tail refills add traffic), so the ping-pong pair stays.
 #ifndef SK_DEPTH
 #define SK_DEPTH 2
+#endif
+
+// SK_REFILL_FENCE = 1 pins every refill of the K loop's ring where the source issues it (a scheduling barrier behind the
+// loads).  Left alone, the scheduler sinks a slot's refill behind the NEXT slot's MFMAs, to the end of the loop body, where
+// both slots' loads are requested together just before the wave waits for them with a full vmcnt(0): nothing of a wave's
+// own matrix work then covers its loads.  Pinned, slot 0's refill flies during slot 1's 16 MFMAs and the body's waits are
+// counted (profiles/step_refill_fence_kloop_isa.txt).  Measured: headline step 54.80 -> 53.31 ms
+// (profiles/step_refill_fence_ab_bench.jsonl), same bits.
+#ifndef SK_REFILL_FENCE
+#define SK_REFILL_FENCE 1
+#endif
+#if SK_REFILL_FENCE
+#define SK_PIN_REFILL() __builtin_amdgcn_sched_barrier(0)
+#else
+#define SK_PIN_REFILL() do { } while (0)
 #endif
 
 template <int MB>
@@ -230,7 +246,7 @@ __constant__ unsigned long long* sk_timer_buf = nullptr;  // (constant address s
 // epilogue's ~30 addresses per wave sit on the critical path in front of the K loop and behind the LDS meeting point.
 __device__ __forceinline__ unsigned sk_off(int m, int ld, int c) { return __umul24((unsigned)m, (unsigned)ld) + (unsigned)c; }
 
-// One workgroup: (16*MB rows) x (16*NB columns) output tile, K split over the SK_NW waves.
+// One workgroup: (16*MB rows) x (16*NB columns) output tile, K split over the SK_KW waves.
 template <int MB, int NB, bool FAST>
 __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red) {
     const int tid = threadIdx.x;
@@ -271,7 +287,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
     // rest exit: half the instructions on the tail's critical path (1.1 us from the LDS meeting point to the last store
     // at 32 x 32 tiles, one wave per SIMD), half the request instructions in front of every wave's K loop, all waves alike.
     constexpr int NBLK = MB * NB;
-    constexpr int EG = (SK_NW % NBLK == 0) ? (SK_NW / NBLK > 4 ? 4 : SK_NW / NBLK) : 1;
+    constexpr int EG = (SK_KW % NBLK == 0) ? (SK_KW / NBLK > 4 ? 4 : SK_KW / NBLK) : 1;
     constexpr int RPW = 4 / EG, EWAVES = NBLK * EG;
     const int eblk = wave % NBLK, er0 = (wave / NBLK) * RPW;  // this wave's block and first row (of a lane's four)
     float p_bias = 0.f, p_add[RPW], p_e0[RPW], p_e1[RPW], p_oc[RPW];
@@ -340,13 +356,13 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
             ncl[nb] = min(sk_jcol(job, tile0 + nb, i), N - 1);
             btile[nb] = min(tile0 + nb, ((N + 15) >> 4) - 1);
         }
-        const int mine = (total - wave + SK_NW - 1) / SK_NW;  // chunks of this wave (dealt round-robin)
+        const int mine = (total - wave + SK_KW - 1) / SK_KW;  // chunks of this wave (dealt round-robin)
         const int first = wave;
-        const int last = wave + (mine - 1) * SK_NW;
-        constexpr int STR = SK_NW;
+        const int last = wave + (mine - 1) * SK_KW;
+        constexpr int STR = SK_KW;
         auto run = [&](auto kc_tag) {
             constexpr int BM = decltype(kc_tag)::value;
-            auto fetch = [&](int g, f32x4 (&a)[MB], f32x4 (&b)[NB]) {
+            auto fetch = [&](int g, f32x4 (&a)[MB], f32x4 (&b)[NB]) __attribute__((always_inline)) {
                 const float* A = sA[0];
                 const float* B = sB[0];
                 int lda = slda[0], ldb = sldb[0], beg = 0;
@@ -358,10 +374,19 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                 }
                 sk_fetch_fast<MB, NB, BM>(A, lda, B, ldb, (g - beg) << 4, mrow, ncl, btile, kk, a, b);
             };
-            // Ring of SK_DEPTH register buffers, SK_DEPTH chunks per iteration, each slot refilled right after
-            // it has fed the MFMAs: no register copies, so nothing in the body waits for loads it has just
-            // issued, and SK_DEPTH chunks stay in flight per wave.
+            // Ring of SK_DEPTH register buffers, SK_DEPTH chunks per iteration, each slot refilled right after it has
+            // fed the MFMAs (SK_PIN_REFILL keeps the refill there): no register copies, so nothing in the body waits for
+            // loads it has just issued, and SK_DEPTH chunks stay in flight per wave.  The refills are unconditional, their
+            // index clamped to the wave's last chunk: the last SK_DEPTH of a wave re-request that chunk and feed nothing.
+            // Peeling them off (a final group that refills only what the remainder reads, picked by a uniform branch)
+            // was measured SLOWER: 9.5 - 9.6 us per gate / candidate launch against 9.3 - 9.4, and no gain with the
+            // refills pinned either (profiles/step_refill_fence_*): the re-requested lines are in flight or in L1 already,
+            // the extra copies of the loop's tail are not free.
             f32x4 ra[SK_DEPTH][MB], rb_[SK_DEPTH][NB];
+            auto consume = [&](f32x4 (&a)[MB], f32x4 (&b)[NB]) __attribute__((always_inline)) {
+                sk_a_unpermute<MB>(a);
+                sk_mma2<MB, NB>(a, b, acc);
+            };
 #pragma unroll
             for (int dd = 0; dd < SK_DEPTH; ++dd) fetch(min(first + dd * STR, last), ra[dd], rb_[dd]);
             int g = first;
@@ -369,22 +394,19 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
             for (int gr = 0; gr < ngroups; ++gr) {
 #pragma unroll
                 for (int dd = 0; dd < SK_DEPTH; ++dd) {
-                    sk_a_unpermute<MB>(ra[dd]);
-                    sk_mma2<MB, NB>(ra[dd], rb_[dd], acc);
+                    consume(ra[dd], rb_[dd]);
                     fetch(min(g + (SK_DEPTH + dd) * STR, last), ra[dd], rb_[dd]);
+                    SK_PIN_REFILL();
                 }
                 g += SK_DEPTH * STR;
             }
             const int rem = mine - ngroups * SK_DEPTH;
 #pragma unroll
             for (int dd = 0; dd < SK_DEPTH - 1; ++dd)
-                if (dd < rem) {
-                    sk_a_unpermute<MB>(ra[dd]);
-                    sk_mma2<MB, NB>(ra[dd], rb_[dd], acc);
-                }
+                if (dd < rem) consume(ra[dd], rb_[dd]);
         };
         auto run_bf16 = [&]() {
-            auto fetch = [&](int g, f32x4 (&a)[MB][2], f32x4 (&b)[NB]) {
+            auto fetch = [&](int g, f32x4 (&a)[MB][2], f32x4 (&b)[NB]) __attribute__((always_inline)) {
                 const float* A = sA[0];
                 const float* B = sB[0];
                 int lda = slda[0], ldb = sldb[0], beg = 0;
@@ -397,6 +419,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                 sk_fetch_bf16<MB, NB>(A, lda, B, ldb, (g - beg) << 5, mrow, btile, a, b);
             };
             f32x4 ra[SK_DEPTH][MB][2], rb_[SK_DEPTH][NB];
+            auto consume = [&](f32x4 (&a)[MB][2], f32x4 (&b)[NB]) __attribute__((always_inline)) { sk_mma_bf16<MB, NB>(a, b, acc); };
 #pragma unroll
             for (int dd = 0; dd < SK_DEPTH; ++dd) fetch(min(first + dd * STR, last), ra[dd], rb_[dd]);
             int g = first;
@@ -404,15 +427,16 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
             for (int gr = 0; gr < ngroups; ++gr) {
 #pragma unroll
                 for (int dd = 0; dd < SK_DEPTH; ++dd) {
-                    sk_mma_bf16<MB, NB>(ra[dd], rb_[dd], acc);
+                    consume(ra[dd], rb_[dd]);
                     fetch(min(g + (SK_DEPTH + dd) * STR, last), ra[dd], rb_[dd]);
+                    SK_PIN_REFILL();
                 }
                 g += SK_DEPTH * STR;
             }
             const int rem = mine - ngroups * SK_DEPTH;
 #pragma unroll
             for (int dd = 0; dd < SK_DEPTH - 1; ++dd)
-                if (dd < rem) sk_mma_bf16<MB, NB>(ra[dd], rb_[dd], acc);
+                if (dd < rem) consume(ra[dd], rb_[dd]);
         };
         SK_STAMP(1);
         if (mine > 0) {
@@ -423,7 +447,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
         }
         if (flagged) {
             // Tail segment (fragment-major weights, quad-contiguous activation loads as in sk_fetch_fast): its chunks are
-            // dealt round-robin like the main ring's, so with a main ring of a multiple of SK_NW chunks every wave adds
+            // dealt round-robin like the main ring's, so with a main ring of a multiple of SK_KW chunks every wave adds
             // exactly the terms, in exactly the order, of the unflagged kernel.
             // ONE poller per workgroup (a thousand waves polling one word saturate its memory channel and slow the
             // producers down: measured 36 ms instead of 26 ms per forward scan), behind a workgroup barrier
@@ -433,7 +457,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
             const SkSeg& sg = job.seg[job.nseg - 1];
             const int ntail = sg.K >> 4;
             const __amdgpu_buffer_rsrc_t rs = sk_rsrc(sg.A);
-            for (int c = wave; c < ntail; c += SK_NW) {
+            for (int c = wave; c < ntail; c += SK_KW) {
                 f32x4 a[MB], b[NB];
 #pragma unroll
                 for (int rb = 0; rb < MB; ++rb)
@@ -458,11 +482,11 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
         for (int s = 0; s < job.nseg; ++s) {
             const SkSeg sg = job.seg[s];
             const int nch = (sg.K + 15) >> 4;
-            int c = (wave - (base % SK_NW) + SK_NW) % SK_NW;
+            int c = (wave - (base % SK_KW) + SK_KW) % SK_KW;
             f32x4 a_cur[MB], b_cur;
             if (c < nch) sk_fetch<MB, false>(sg, c * 16, m0, M, ncol, ncol_ok, kk, i, a_cur, b_cur);
             while (c < nch) {
-                const int cn = c + SK_NW;
+                const int cn = c + SK_KW;
                 f32x4 a_nxt[MB], b_nxt;
                 if (cn < nch) sk_fetch<MB, false>(sg, cn * 16, m0, M, ncol, ncol_ok, kk, i, a_nxt, b_nxt);
                 sk_mma<MB>(a_cur, b_cur, accg);
@@ -503,7 +527,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
 #pragma unroll
         for (int r = 0; r < RPW; ++r) v[r] = rp[(blk * 64 + lane) * 4 + r];
 #pragma unroll
-        for (int w = 1; w < SK_NW; ++w)
+        for (int w = 1; w < SK_KW; ++w)
 #pragma unroll
             for (int r = 0; r < RPW; ++r) v[r] += rp[((w * NBLK + blk) * 64 + lane) * 4 + r];
     }
@@ -628,7 +652,7 @@ __device__ __forceinline__ int sk_find_job(const SkLaunch& L, int& bx) {
 // did not need the header).  Otherwise the workgroups of the jobs are laid out back to back along x and the job is found
 // in the prefix table (a z-grid sized for the largest job was measured slower there: 59 -> 65 ms backward at cfg2).
 template <int MB, int NB, bool ZMODE>
-__global__ __launch_bounds__(SK_THREADS) void sk_kernel(const SkLaunch L) {
+__global__ __launch_bounds__(SK_KTHREADS) void sk_kernel(const SkLaunch L) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];
     f32x4* red = reinterpret_cast<f32x4*>(sk_smem);
     int j = blockIdx.z, bx = blockIdx.x;
@@ -640,7 +664,8 @@ __global__ __launch_bounds__(SK_THREADS) void sk_kernel(const SkLaunch L) {
 }
 
 // Heterogeneous step launch: the first natt_x workgroups of every grid row carry the attention forward step
-// (att_fwd_body.h; one (batch row, column slice) pair each, on all eight waves), the others are
+// (att_fwd_body.h; one (batch row, column slice) pair each, on eight waves: in a build with more K waves the others exit
+// before the block's first barrier), the others are
 // step-GEMM workgroups as in sk_kernel (jobs found through the workgroup prefix table).  The attention of a tick is a
 // chain of dependent round trips that leaves the chip idle; here independent GEMM jobs (the upper layers' input
 // projections, plans.hip schedule 5) run in its shadow.
@@ -648,7 +673,7 @@ __global__ __launch_bounds__(SK_THREADS) void sk_kernel(const SkLaunch L) {
 #define SKA_PROJ_UNROLL 4  // 8 (the stand-alone kernel's) would cost the GEMM side its second workgroup per CU
 #endif
 template <int MB, int NB>
-__global__ __launch_bounds__(SK_THREADS, 4) void ska_kernel(const SkLaunch L, const AttFwdArgs g, const int natt_x,
+__global__ __launch_bounds__(SK_KTHREADS, SK_KW > 8 ? 1 : 4) void ska_kernel(const SkLaunch L, const AttFwdArgs g, const int natt_x,
                                                          const int att_last) {
     extern __shared__ __attribute__((aligned(16))) char sk_smem[];
     int bx = blockIdx.x;
@@ -667,6 +692,8 @@ __global__ __launch_bounds__(SK_THREADS, 4) void ska_kernel(const SkLaunch L, co
         if (att_last == 2 && blockIdx.y != 0) return;
         const int id = att_last == 2 ? bx : blockIdx.y * natt_x + bx;
         if (id >= g.B * g.esplit) return;
+        static_assert(SK_KTHREADS >= SK_THREADS, "the attention block needs its eight waves");
+        if (threadIdx.x >= SK_THREADS) return;  // (before the block's first barrier: s_barrier counts the live waves only)
         att_fwd_block<SK_THREADS, SKA_PROJ_UNROLL>(g, id / g.esplit, id % g.esplit, reinterpret_cast<float*>(sk_smem));
         return;
     }
@@ -681,7 +708,7 @@ __global__ __launch_bounds__(SK_THREADS, 4) void ska_kernel(const SkLaunch L, co
 
 // Heterogeneous BACKWARD launch (plans.hip bwd8, GRU layers): the attention backward + state backward row blocks of
 // att_state_bwd_kernel (1024 threads) lead the grid, the other workgroups are step-GEMM workgroups as in sk_kernel on
-// eight of the block's sixteen waves (the others exit at once).  The row blocks are a chain of dependent round trips on
+// SK_KW of the block's sixteen waves (the others exit at once).  The row blocks are a chain of dependent round trips on
 // 64-128 CUs; the GEMM jobs riding here are products nothing in this launch depends on (the downward products of the
 // upper layers' previous tick), so the idle CUs of that chain do work that used to lengthen the next two launches.
 template <int MB, int NB>
@@ -700,7 +727,8 @@ __global__ __launch_bounds__(ATTB_THREADS) void skb_kernel(const SkLaunch L, con
         att_state_bwd_block(g, sa, att_rows, l0_chain, id, reinterpret_cast<float*>(sk_smem), rpb);
         return;
     }
-    if (threadIdx.x >= SK_THREADS) return;
+    static_assert(SK_KTHREADS <= ATTB_THREADS, "the step-GEMM workgroups run inside the row blocks' block size");
+    if (threadIdx.x >= SK_KTHREADS) return;
     bx -= nlead_x;
     f32x4* red = reinterpret_cast<f32x4*>(sk_smem);
     const int j = sk_find_job(L, bx);
@@ -1560,7 +1588,7 @@ void sk_prepare(const SkLaunch& Lin, SkLaunch& L, dim3& grid_out, size_t& lds_ou
     }
     L.zmode = equal ? 1 : 0;
     grid_out = dim3(equal ? wmax : t, ceil_div(maxM, 16 * mb), equal ? L.njobs : 1);
-    lds_out = (size_t)SK_NW * mb * nb * 64 * sizeof(f32x4);
+    lds_out = (size_t)SK_KW * mb * nb * 64 * sizeof(f32x4);  // the split-K meeting: one partial tile per wave
     mbnb_out = mb * 10 + nb;
 }
 
@@ -1580,8 +1608,9 @@ int sk_launch(const SkLaunch& Lin, hipStream_t stream) {
     sk_prepare(Lin, L, grid, lds, mbnb);
     sk_with_tile(mbnb, [&](auto mb, auto nb) {
         constexpr int MB = decltype(mb)::value, NB = decltype(nb)::value;
-        if (L.zmode) sk_enqueue<sk_kernel<MB, NB, true>, false>(L, 0, grid, dim3(SK_THREADS), lds, stream, L);
-        else sk_enqueue<sk_kernel<MB, NB, false>, false>(L, 0, grid, dim3(SK_THREADS), lds, stream, L);
+        // (BIG_LDS: at sixteen waves the partial tiles of a 48 x 32 workgroup are 96 KiB)
+        if (L.zmode) sk_enqueue<sk_kernel<MB, NB, true>, true>(L, 0, grid, dim3(SK_KTHREADS), lds, stream, L);
+        else sk_enqueue<sk_kernel<MB, NB, false>, true>(L, 0, grid, dim3(SK_KTHREADS), lds, stream, L);
     });
     return (int)hipGetLastError();
 }
@@ -1623,7 +1652,7 @@ int sk_launch_att(const SkLaunch& Lin, const AttFwdArgs& att, hipStream_t stream
     // waits for the attention needs its producers dispatched first, and all of them in grid row 0.
     const int att_last = flagged ? 2 : 1;
     sk_with_tile(mbnb, [&](auto mb, auto nb) {
-        sk_enqueue<ska_kernel<decltype(mb)::value, decltype(nb)::value>, true>(L, 1, grid, dim3(SK_THREADS), lds, stream, L, g,
+        sk_enqueue<ska_kernel<decltype(mb)::value, decltype(nb)::value>, true>(L, 1, grid, dim3(SK_KTHREADS), lds, stream, L, g,
                                                                                 natt_x, att_last);
     });
     return (int)hipGetLastError();

@@ -115,7 +115,7 @@ int main(int argc, char** argv) {
             if (v.empty()) continue;
             std::sort(v.begin(), v.end());
             printf("  [%d] %-36s n=%5zu  %6.2f %6.2f %6.2f %6.2f %6.2f", ph, names[ph], v.size(), v.front(), v[v.size() / 4], v[v.size() / 2], v[3 * v.size() / 4], v.back());
-            for (int wv = 0; wv < 8; ++wv) {  // median per wave index
+            for (int wv = 0; wv < SK_KW; ++wv) {  // median per wave index
                 std::vector<double> u;
                 for (size_t w = wv; w < NW / 8; w += 16) if (hb[w * 8 + ph] && hb[w * 8] && hb[w * 8 + ph] >= t0 && hb[w * 8 + ph] - t0 < 100000) u.push_back((double)(hb[w * 8 + ph] - t0) * 0.01);
                 std::sort(u.begin(), u.end());
