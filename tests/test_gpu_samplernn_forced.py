@@ -35,9 +35,14 @@ def _run(gen, feats, **kw):
     return out.cpu().numpy().copy()
 
 
-def _full_forcing_parity(tt, kind, B, groups, what, **kw):
-    p, feats, forced, want = FC.case(kind, B)
+def _full_forcing_parity(tt, kind, B, groups, what, ref=None, **kw):
+    """ref: (params, features, codes, float64 log-probabilities) of another reference than FC.case(kind, B)'s, in its
+    layout (tests/samplernn_width_cases.py).  Returns the relative error of each call."""
+    p, feats, forced, want = FC.case(kind, B) if ref is None else ref
+    assert forced.shape == (B, 80 * FC.REF_T) and want.shape == (B, 80 * (FC.REF_T - 1))
+    errs = []
     with _plan(tt, B, FC.REF_T, groups, temperature=0.0, forcing=True, log_probs=True, **kw) as gen:
+        assert gen.forcing and gen.log_probs
         for call in range(2):           # the second call meets the carry the first one left
             samples, logp = _run(gen, feats, forced=forced)
             assert samples.dtype == np.int32 and logp.dtype == np.float32 and logp.shape == samples.shape
@@ -47,6 +52,8 @@ def _full_forcing_parity(tt, kind, B, groups, what, **kw):
                              f"log-probabilities, {what}")
             print(f"FORCED-GPU {what} call {call}: relative error {e:.3e}, largest difference "
                   f"{np.abs(logp[:, 80:] - want).max():.3e}")
+            errs.append(e)
+    return errs
 
 
 # ---- 1. oracle parity under full forcing ---------------------------------------------------------------------------------

@@ -22,7 +22,8 @@ SWITCH = "PARROT_SR_PERSIST_GROUPS"
 
 @contextlib.contextmanager
 def _model(dev, p, **cfg):
-    """The generator's module at DIM 256 / EMB 32 with the parameters p registered; defaults restored afterwards."""
+    """The generator's module at DIM 256 / EMB 32 (or the width and frame size cfg names) with the parameters p
+    registered; defaults restored afterwards."""
     from parrot_amd.sampleRNN import lib
     from parrot_amd.sampleRNN.models.conditional import three_tier as tt
     lib.delete_all_params()
@@ -33,7 +34,7 @@ def _model(dev, p, **cfg):
         yield tt
     finally:
         lib.delete_all_params()
-        tt.configure(DIM=1024, EMB_SIZE=256, RNN_TYPE='GRU', N_RNN=1)
+        tt.configure(DIM=1024, EMB_SIZE=256, RNN_TYPE='GRU', N_RNN=1, FRAME_SIZE=10)
 
 
 @contextlib.contextmanager
