@@ -698,6 +698,18 @@ int parrot_sample_stops_early(void* plan);
  * early, S for every other plan. */
 int parrot_sample_steps_run(void* plan, int* steps);
 
+/* Per-row decode controls: row b of every later run decodes with timing[b] / sharpening[b] / sampling_bias[b] in place of
+ * ParrotSampleDesc::timing / sharpening / sampling_bias -- b = exp(b_hat) * sharpening[b] + eps, kappa = kappa_prev +
+ * alignment * exp(k_hat) / timing[b], exp(sig_hat - bias[b]) + eps, co_hat * (1 + bias[b]) -- on whichever path the plan
+ * decodes (the persistent machine or the per-step launches), with the end-of-utterance stop as without it.  Each argument
+ * is a device array of B floats, or NULL: that control stays the descriptor's scalar for every row.  The caller owns the
+ * arrays, keeps them alive as long as the plan, and rewrites their CONTENTS between runs as it likes; the values must be
+ * finite, timing and sharpening > 0 (not checked).  All three NULL: no controls, the plan is what parrot_sample_create
+ * made.  Call it before the plan's first parrot_sample_run: afterwards it returns PARROT_ERR_BADARG (a captured graph
+ * holds the pointers by value).  sampling_bias != NULL on a plan without a GMM head (gmm_K = 0): PARROT_ERR_BADARG.
+ * Equal values give equal bits: row b decodes exactly as it does under a descriptor that carries its three values. */
+int parrot_sample_set_row_controls(void* plan, const float* timing, const float* sharpening, const float* sampling_bias);
+
 int parrot_sample_create(const ParrotSampleDesc* desc, void** plan);
 int parrot_sample_run(void* plan, void* stream);
 int parrot_sample_destroy(void* plan);

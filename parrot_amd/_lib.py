@@ -250,6 +250,7 @@ SIGNATURES = {
     "parrot_sample_status": (_i, [_vp]),
     "parrot_sample_stops_early": (_i, [_vp]),
     "parrot_sample_steps_run": (_i, [_vp, C.POINTER(C.c_int)]),
+    "parrot_sample_set_row_controls": (_i, [_vp, _vp, _vp, _vp]),
     "parrot_decoder_status": (_i, [_vp]),
     "parrot_sample_run": (_i, [_vp, _vp]),
     "parrot_sample_destroy": (_i, [_vp]),

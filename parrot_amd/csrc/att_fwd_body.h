@@ -20,8 +20,11 @@ constexpr int ATT_MAXA = 32;  // attention_size limit (reference default 10)
 constexpr int ATT_THREADS_MAX = 512;  // the heterogeneous step launch runs the block on all eight waves of its workgroups
 static inline size_t att_fwd_lds(int U) { return sizeof(float) * (6 * ATT_MAXA + 8 + ((U + 3) & ~3) + 2 * ATT_THREADS_MAX); }
 
-template <int NT, int PROJ_UNROLL>
-__device__ __forceinline__ void att_fwd_block(const AttFwdArgs& g, const int b, const int es, float* sm) {
+// ROWC (the decode planner's launches with per-row controls, AttRowCtl): sharpening and timing are row b's own values
+// instead of the scalars of AttFwdArgs; false: rc is not read and the block is what it was before they existed.
+template <int NT, int PROJ_UNROLL, bool ROWC = false>
+__device__ __forceinline__ void att_fwd_block(const AttFwdArgs& g, const int b, const int es, float* sm,
+                                              const AttRowCtl rc = AttRowCtl{nullptr, nullptr}) {
     const int A = g.A, U = g.U, E = g.E, H = g.H;
     float* s_p = sm;                 // [3A] projection
     float* s_a = s_p + 3 * ATT_MAXA; // [A]
@@ -63,6 +66,11 @@ __device__ __forceinline__ void att_fwd_block(const AttFwdArgs& g, const int b, 
     // kappa_{t-1}: needed two phases later, requested now (one dependent round trip less)
     const int ta_ = t < A ? t : A - 1;
     const float pre_kprev = g.kappa_prev[(size_t)b * A + ta_];
+    float sharpening = g.sharpening, timing = g.timing;
+    if (ROWC) {  // (asked for here, with kappa_{t-1}: not on the chain in front of the exponentials)
+        sharpening = rc.sharpening[b];
+        timing = rc.timing[b];
+    }
 
     // 1) projection p[j] = sum_k h[k] * Watt[k][j] + batt[j]; wave w handles j = w, w+NW, ...
     // Round 6: 16-byte loads, every load of a pass requested before the first is used, no conditional loads (outputs past
@@ -145,8 +153,8 @@ __device__ __forceinline__ void att_fwd_block(const AttFwdArgs& g, const int b, 
         float av;
         if (g.att_type == 1) av = expf(s_p[t] - s_red[4]) / s_red[5] + g.eps;
         else av = expf(s_p[t]) + g.eps;
-        const float bv = expf(s_p[A + t]) * g.sharpening + g.eps;
-        const float kv = pre_kprev + g.alignment * expf(s_p[2 * A + t]) / g.timing;
+        const float bv = expf(s_p[A + t]) * sharpening + g.eps;
+        const float kv = pre_kprev + g.alignment * expf(s_p[2 * A + t]) / timing;
         s_a[t] = av;
         s_b[t] = bv;
         s_k[t] = kv;

@@ -32,6 +32,12 @@ struct AttFwdArgs {
                      // its slice is out, so that workgroups of the SAME launch can consume w (skinny.hip, SkJob::wait_flag)
 };
 
+// Per-row sharpening / timing of a decode launch ([B] device arrays, both set): a second kernel argument of
+// att_fwd_rows_kernel, so AttFwdArgs and the kernels that take it alone stay what they are.
+struct AttRowCtl {
+    const float* sharpening; const float* timing;
+};
+
 struct AttBwdArgs {
     float* dw; int lddw;           // [B,E] gradient wrt w_t (in; the total is written back when dw2 != null)
     const float* dw2;              // [B,E] optional second share of the gradient (layer-0 path) or null
@@ -63,6 +69,8 @@ __host__ __device__ inline int att_bwd_route(int narrow_on, bool has_sup, int U,
 }
 
 int att_fwd_launch(const AttFwdArgs& g, hipStream_t stream);
+// The same row blocks with row b's own sharpening[b] / timing[b] (decode with per-row controls); g's two scalars are unused.
+int att_fwd_rows_launch(const AttFwdArgs& g, const AttRowCtl& rc, hipStream_t stream);
 // Validates the arguments and sets `dense` from PARROT_ATT_DENSE (what att_fwd_launch does before it launches).
 int att_fwd_check(AttFwdArgs& g);
 int att_bwd_launch(const AttBwdArgs& g, hipStream_t stream);

@@ -33,6 +33,12 @@ __global__ __launch_bounds__(ATT_THREADS) void att_fwd_kernel(const AttFwdArgs g
     att_fwd_block<ATT_THREADS, ATT_PROJ_UNROLL>(g, blockIdx.x, blockIdx.y, sm);
 }
 
+// decode with per-row controls: the same row block, sharpening / timing of batch row blockIdx.x from rc
+__global__ __launch_bounds__(ATT_THREADS) void att_fwd_rows_kernel(const AttFwdArgs g, const AttRowCtl rc) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    att_fwd_block<ATT_THREADS, ATT_PROJ_UNROLL, true>(g, blockIdx.x, blockIdx.y, sm, rc);
+}
+
 __global__ __launch_bounds__(ATTB_THREADS) void att_bwd_kernel(const AttBwdArgs g) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     att_bwd_row(g, blockIdx.x, sm);
@@ -61,6 +67,16 @@ int att_fwd_launch(const AttFwdArgs& gin, hipStream_t stream) {
     if (rc != 0) return rc;
     const size_t lds = att_fwd_lds(g.U);
     hipLaunchKernelGGL(att_fwd_kernel, dim3(g.B, g.esplit), dim3(ATT_THREADS), lds, stream, g);
+    return (int)hipGetLastError();
+}
+
+int att_fwd_rows_launch(const AttFwdArgs& gin, const AttRowCtl& rows, hipStream_t stream) {
+    AttFwdArgs g = gin;
+    const int rc = att_fwd_check(g);
+    if (rc != 0) return rc;
+    if (!rows.sharpening || !rows.timing || g.flag) return PH_ERR_BADARG;
+    const size_t lds = att_fwd_lds(g.U);
+    hipLaunchKernelGGL(att_fwd_rows_kernel, dim3(g.B, g.esplit), dim3(ATT_THREADS), lds, stream, g, rows);
     return (int)hipGetLastError();
 }
 

@@ -157,7 +157,7 @@ int adam_clip_launch(float* p, const float* g, float* m, float* v, size_t n, con
 // GMM output head of the sampling step (model.py:1024-1033, sample_gmm model.py:94-118).
 int gmm_sample_launch(const float* mu, const float* sig_hat, const float* co_hat, int B, int O, int K, float bias,
                       float eps, const float* unif, const float* noise, float* x, int ldx, float* pi_out,
-                      hipStream_t stream);
+                      hipStream_t stream, const float* bias_rows = nullptr);  // bias_rows: [B], row b's own bias; null: `bias`
 
 struct LstmStateBwdChain {
     const float* dh;      // [B,H] gradient wrt s_t

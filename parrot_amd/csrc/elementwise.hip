@@ -149,13 +149,17 @@ __global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p, c
 
 // One workgroup per batch row: pi = softmax(co_hat (1 + bias)) + eps; component = first k with
 // cumsum(pi) > u (Theano multinomial); x[o] = mu[o,k] + (exp(sig_hat[o,k] - bias) + eps) * noise[o].
+// ROWB (decode with per-row controls): bias is the row's own bias_rows[b]; false: bias_rows is not read.
+template <bool ROWB>
 __global__ __launch_bounds__(64) void gmm_sample_kernel(const float* __restrict__ mu, const float* __restrict__ sig_hat,
-                                                        const float* __restrict__ co_hat, int O, int K, float bias,
+                                                        const float* __restrict__ co_hat, int O, int K, float bias_all,
+                                                        const float* __restrict__ bias_rows,
                                                         float eps, const float* __restrict__ unif,
                                                         const float* __restrict__ noise, float* __restrict__ x, int ldx,
                                                         float* __restrict__ pi_out) {
     __shared__ int s_pick;
     const int b = blockIdx.x, t = threadIdx.x;
+    const float bias = ROWB ? bias_rows[b] : bias_all;
     if (t == 0) {
         const float* c = co_hat + (size_t)b * K;
         const float sc = 1.f + bias;
@@ -335,9 +339,13 @@ int lstm_state_bwd_launch(const float* dh, const float* dh2, float* dc, const fl
 
 int gmm_sample_launch(const float* mu, const float* sig_hat, const float* co_hat, int B, int O, int K, float bias,
                       float eps, const float* unif, const float* noise, float* x, int ldx, float* pi_out,
-                      hipStream_t stream) {
-    hipLaunchKernelGGL(gmm_sample_kernel, dim3(B), dim3(64), 0, stream, mu, sig_hat, co_hat, O, K, bias, eps, unif, noise,
-                       x, ldx, pi_out);
+                      hipStream_t stream, const float* bias_rows) {
+    if (bias_rows)
+        hipLaunchKernelGGL(gmm_sample_kernel<true>, dim3(B), dim3(64), 0, stream, mu, sig_hat, co_hat, O, K, bias, bias_rows, eps,
+                           unif, noise, x, ldx, pi_out);
+    else
+        hipLaunchKernelGGL(gmm_sample_kernel<false>, dim3(B), dim3(64), 0, stream, mu, sig_hat, co_hat, O, K, bias, bias_rows, eps,
+                           unif, noise, x, ldx, pi_out);
     return (int)hipGetLastError();
 }
 

@@ -176,7 +176,15 @@ enum { PM_S_XCNT = 0, PM_S_XGEN = 256, PM_S_TOP = 512, PM_S_CENSUS = 544, PM_S_T
 enum { PM_EOU_MIN_EXTRA = 8 };
 #define PM_EMPTY 0x7FC0DEADu
 
-int pm_launch(const PmProgram& prog, hipStream_t stream);
+// Per-row decode controls (parrot_sample_set_row_controls): [B] device arrays that take the place of PmAtt::sharpening /
+// PmAtt::timing and PmSamp::bias, row b reading element b.  A second kernel argument, not part of PmProgram: a program
+// without them keeps its records and its digest, and the kernels launched without them (ROW = false) never read it.  With
+// them all of timing / sharpening are set, and bias whenever the program has sampling units.
+struct PmRows {
+    const float* timing; const float* sharpening; const float* bias;
+};
+
+int pm_launch(const PmProgram& prog, hipStream_t stream, const PmRows* rows = nullptr);
 // synchronises; frames the last launch completed: T, or fewer when the end-of-utterance stop ended it (PmAtt::eou_extra > 0)
 int pm_steps_run(const PmProgram& prog, int* steps);
 int pm_status(const PmProgram& prog);  // synchronises; 0, or non-zero when a launch on this program's workspace gave up

@@ -524,10 +524,17 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
 // GMM-window attention of batch row b at step t (model.py:664-690) by the whole workgroup (512 threads):
 // projection h1 . Watt, window parameters, phi over the context, w = sum_u phi[u] ctx[b,u,:] over the support of the
 // window.  Same formulas as att_fwd_kernel (attention.hip); the summation order over u differs (two row groups).
-template <bool DF, bool EOU>
-__device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* sm, float* fm_base, unsigned* sync, int T,
-                                           int drain) {
+// ROW: the window's sharpening and timing are the row's own (PmRows, persist.h) instead of PmAtt's scalars: one load each,
+// asked for here with the row's other early operands and used behind the projection.
+template <bool DF, bool EOU, bool ROW>
+__device__ __forceinline__ void pm_att_row(const PmAtt& g, const PmRows& R, int b, int t, float* sm, float* fm_base,
+                                           unsigned* sync, int T, int drain) {
     const int A = g.A, U = g.U, E = g.E, H = g.H;
+    float sharpening = g.sharpening, timing = g.timing;
+    if (ROW) {
+        sharpening = R.sharpening[b];
+        timing = R.timing[b];
+    }
     // end-of-utterance stop: the row's two indices (wave-uniform), asked for now and used behind the w stores
     int eou_pos = 0, eou_ncmp = 0;
     if (EOU) {
@@ -652,9 +659,9 @@ __device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* 
         float av;
         if (g.att_type == 1) av = expf(s_p[tid] - s_red[4]) / s_red[5] + g.eps;
         else av = expf(s_p[tid]) + g.eps;
-        const float bv = expf(s_p[A + tid]) * g.sharpening + g.eps;
+        const float bv = expf(s_p[A + tid]) * sharpening + g.eps;
         const float kp = kp_pre;
-        const float kv = kp + g.alignment * expf(s_p[2 * A + tid]) / g.timing;
+        const float kv = kp + g.alignment * expf(s_p[2 * A + tid]) / timing;
         s_a[tid] = av; s_b[tid] = bv; s_k[tid] = kv;
         g.a[(size_t)t * BA + (size_t)b * A + tid] = av;
         g.b[(size_t)t * BA + (size_t)b * A + tid] = bv;
@@ -810,9 +817,10 @@ __device__ __forceinline__ void pm_att_row(const PmAtt& g, int b, int t, float* 
 __device__ __forceinline__ float pm_sel4(const f32x4& v, unsigned i) {  // (a run-time vector index would go through scratch)
     return i == 0u ? v[0] : (i == 1u ? v[1] : (i == 2u ? v[2] : v[3]));
 }
-template <bool DF>
-__device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmUnit& u, int t, float* lds_red, float* fm_base,
-                                              unsigned* sync) {
+// ROW: the sampling bias is the row's own (PmRows::bias), asked for beside the row's uniform number and noise.
+template <bool DF, bool ROW>
+__device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmRows& R, const PmUnit& u, int t, float* lds_red,
+                                              float* fm_base, unsigned* sync) {
     const int tid = threadIdx.x, lane = tid & 63;
     if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
         const int b = __builtin_amdgcn_readfirstlane(u.row), K = g.K, O = g.O, OK = O * K;
@@ -824,6 +832,7 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmUnit& u, 
         f32x4 vc = pm_ld16(hr, (col_c & ~3u) << 2);
         const float uu = g.unif[tb];
         const float nz = g.noise[tb * O + oc];
+        const float bias = ROW ? R.bias[b] : g.bias;
         if (DF) {
             unsigned n = 0;
             while (__builtin_amdgcn_ballot_w64(pm_is_empty(vc)) != 0ull) {
@@ -837,7 +846,7 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmUnit& u, 
         }
         // pi = softmax(c_hat (1 + bias)) + eps; the pick = the first k with cumsum(pi)_k > u, else K - 1
         const bool comp = lane < K;
-        const float v = comp ? pm_sel4(vc, col_c & 3u) * (1.f + g.bias) : -INFINITY;
+        const float v = comp ? pm_sel4(vc, col_c & 3u) * (1.f + bias) : -INFINITY;
         float mx = v;
 #pragma unroll
         for (int sh = 32; sh > 0; sh >>= 1) mx = fmaxf(mx, __shfl_xor(mx, sh, 64));
@@ -867,7 +876,7 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmUnit& u, 
                 vs = pm_ld16(hr, (col_s & ~3u) << 2);
             }
         }
-        const float xo = lane < O ? pm_sel4(vm, col_m & 3u) + (expf(pm_sel4(vs, col_s & 3u) - g.bias) + g.eps) * nz : 0.f;
+        const float xo = lane < O ? pm_sel4(vm, col_m & 3u) + (expf(pm_sel4(vs, col_s & 3u) - bias) + g.eps) * nz : 0.f;
         // the frame (64 columns, zeros from O on) through LDS into 16 quads: one 16-byte write-through store per quad into
         // row-major x[t + 1] and into every fragment-major destination (block (b / 16, chunk + e / 16), lane
         // (e % 16) / 4 * 16 + b % 16 holds columns e .. e + 3, as the attention row's w); 16 lanes per destination
@@ -899,8 +908,9 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmUnit& u, 
 // W16: the program has PM_GEMM16 units (PmProgram::w16); false: the kernel is what it was before they existed
 // EOU: the program asks for the end-of-utterance stop (PmAtt::eou_extra > 0); false: the kernel is what it was before that
 // SMP: the program has PM_SAMPLE units (PmSamp::K > 0, a GMM head); false: the kernel is what it was before they existed
-template <int MB, bool DF, bool LS, bool W16, bool EOU, bool SMP>
-__global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
+// ROW: the launch carries per-row decode controls (PmRows); false: R is not read and the kernel is what it was before them
+template <int MB, bool DF, bool LS, bool W16, bool EOU, bool SMP, bool ROW>
+__global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P, const PmRows R) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lds_w = lds;
     float* lds_red = lds + PM_LDS_W;
@@ -1019,8 +1029,8 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P) {
                 if (t < 0 || t >= P.T) continue;
                 if (kind == PM_GEMM) pm_gemm<MB, DF, LS, false>(u, t, lds_w, lds_red, fmr, stage, sync);
                 else if (W16 && kind == PM_GEMM16) pm_gemm<MB, DF, LS, true>(u, t, lds_w, lds_red, fmr, stage, sync);
-                else if (SMP && kind == PM_SAMPLE) pm_sample_row<DF>(P.samp, u, t, lds_red, P.fm_base, sync);
-                else pm_att_row<DF, EOU>(P.att, u.row, t, lds_att, P.fm_base, sync, P.T, P.n_ticks - P.T);
+                else if (SMP && kind == PM_SAMPLE) pm_sample_row<DF, ROW>(P.samp, R, u, t, lds_red, P.fm_base, sync);
+                else pm_att_row<DF, EOU, ROW>(P.att, R, u.row, t, lds_att, P.fm_base, sync, P.T, P.n_ticks - P.T);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             const unsigned long long tb = pm_clock();
@@ -1117,7 +1127,7 @@ int pm_steps_run(const PmProgram& P, int* steps) {
     return 0;
 }
 
-int pm_launch(const PmProgram& P, hipStream_t stream) {
+int pm_launch(const PmProgram& P, hipStream_t stream, const PmRows* rows) {
     if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
         P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL)
         return PH_ERR_BADARG;
@@ -1126,6 +1136,7 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
                           !P.samp.noise || !P.samp.x || !P.samp.pi))
         return PH_ERR_BADARG;
     if (P.att.U > PM_ATT_MAXU || P.att.A > PM_ATT_MAXA) return PH_ERR_UNSUPPORTED;
+    if (rows && (!rows->timing || !rows->sharpening || (P.samp.K != 0 && !rows->bias))) return PH_ERR_BADARG;
     if (P.att.eou_extra != 0 && (P.att.eou_extra < PM_EOU_MIN_EXTRA || !P.att.eou_pos || !P.att.eou_ncmp || !P.att.eou_first ||
                                  P.att.B < 1 || P.att.B > 64))
         return PH_ERR_BADARG;
@@ -1149,11 +1160,13 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
             PH_CHECK(hipGetLastError());
         }
     const size_t lds = (size_t)PM_LDS_FLOATS * sizeof(float);
-    static bool attr_done = false;
-    if (!attr_done) {
+    // per launch flavour (ROW: with per-row decode controls) the attribute is set once, before that flavour's first launch
+    static bool attr_done[2] = {false, false};
+    auto set_attrs = [&](auto row) -> int {
+        constexpr bool ROW_ = decltype(row)::value;
         const int l = (int)lds;
 #define PM_ATTR1(MB_, DF_, LS_, W16_, EOU_) \
-    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_, EOU_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, W16_, EOU_, false, ROW_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
 #define PM_ATTR(EOU_) \
     PM_ATTR1(1, false, false, false, EOU_); PM_ATTR1(2, false, false, false, EOU_); PM_ATTR1(4, false, false, false, EOU_); \
     PM_ATTR1(1, true, false, false, EOU_); PM_ATTR1(2, true, false, false, EOU_); PM_ATTR1(4, true, false, false, EOU_); \
@@ -1168,7 +1181,7 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
 #undef PM_ATTR1
         // behind them the kernels with the sampling row (GMM head: GRU and LSTM programs, f32 operands)
 #define PM_ATTRS(MB_, DF_, LS_, EOU_) \
-    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, false, EOU_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, false, EOU_, true, ROW_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
 #define PM_ATTRS6(LS_, EOU_) \
     PM_ATTRS(1, false, LS_, EOU_); PM_ATTRS(2, false, LS_, EOU_); PM_ATTRS(4, false, LS_, EOU_); \
     PM_ATTRS(1, true, LS_, EOU_); PM_ATTRS(2, true, LS_, EOU_); PM_ATTRS(4, true, LS_, EOU_)
@@ -1178,24 +1191,36 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
 #undef PM_ATTRS
         // behind them the kernels of the GRU programs with bf16 layer units (no LSTM epilogue, the bf16 K loop)
 #define PM_ATTRG(MB_, DF_, EOU_) \
-    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, false, true, EOU_, false>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, false, true, EOU_, false, ROW_>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
 #define PM_ATTRG6(EOU_) \
     PM_ATTRG(1, false, EOU_); PM_ATTRG(2, false, EOU_); PM_ATTRG(4, false, EOU_); \
     PM_ATTRG(1, true, EOU_); PM_ATTRG(2, true, EOU_); PM_ATTRG(4, true, EOU_)
         PM_ATTRG6(false); PM_ATTRG6(true);
 #undef PM_ATTRG6
 #undef PM_ATTRG
-        attr_done = true;
+        return 0;
+    };
+    if (!attr_done[rows ? 1 : 0]) {
+        // (the kernels without the controls are instantiated first: they keep their place in the code object)
+        const int rc = !rows ? set_attrs(std::false_type{}) : set_attrs(std::true_type{});
+        if (rc != 0) return rc;
+        attr_done[rows ? 1 : 0] = true;
     }
     const dim3 grid(P.nwg), block(PM_THREADS);
+    const PmRows R = rows ? *rows : PmRows{nullptr, nullptr, nullptr};
+#define PM_GO2(MB_, DF_, EOU_, ROW_) \
+    do { \
+        if (P.samp.K > 0 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, true, ROW_>), grid, block, lds, stream, P, R); \
+        else if (P.samp.K > 0) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, true, ROW_>), grid, block, lds, stream, P, R); \
+        else if (P.w16 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_, false, ROW_>), grid, block, lds, stream, P, R); \
+        else if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, true, EOU_, false, ROW_>), grid, block, lds, stream, P, R); \
+        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, false, ROW_>), grid, block, lds, stream, P, R); \
+        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, false, ROW_>), grid, block, lds, stream, P, R); \
+    } while (0)
 #define PM_GO1(MB_, DF_, EOU_) \
     do { \
-        if (P.samp.K > 0 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, true>), grid, block, lds, stream, P); \
-        else if (P.samp.K > 0) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, true>), grid, block, lds, stream, P); \
-        else if (P.w16 && P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, true, EOU_, false>), grid, block, lds, stream, P); \
-        else if (P.w16) hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, true, EOU_, false>), grid, block, lds, stream, P); \
-        else if (P.lstm) hipLaunchKernelGGL((pm_kernel<MB_, DF_, true, false, EOU_, false>), grid, block, lds, stream, P); \
-        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, false, false, EOU_, false>), grid, block, lds, stream, P); \
+        if (rows) PM_GO2(MB_, DF_, EOU_, true); \
+        else PM_GO2(MB_, DF_, EOU_, false); \
     } while (0)
 #define PM_GO(MB_, DF_) \
     do { \
@@ -1213,5 +1238,6 @@ int pm_launch(const PmProgram& P, hipStream_t stream) {
     }
 #undef PM_GO
 #undef PM_GO1
+#undef PM_GO2
     return (int)hipGetLastError();
 }

@@ -139,7 +139,43 @@ struct SamplePlan : PlanBase {
     ParrotSampleDesc d;
     int esplit = 1;
 
-    int enqueue(int, hipStream_t s) override { return live ? run_persist(s) : run_all(s); }
+    int enqueue(int, hipStream_t s) override {
+        has_run = true;
+        return live ? run_persist(s) : run_all(s);
+    }
+
+    // ---- per-row controls (parrot_sample_set_row_controls) --------------------------------------------------------------
+    // Not part of the descriptor and not of pm_prog: a plan without them is, record for record, the plan it was.  With them
+    // every consumer of d.timing / d.sharpening / d.sampling_bias reads element b of an array instead, on both paths; a
+    // control the caller left null reads an array of the plan's own that holds the descriptor's scalar B times, so the
+    // kernels have one flavour with the controls and one without.
+    PmRows rows = {nullptr, nullptr, nullptr};
+    bool has_rows = false, has_run = false;
+    float* rows_own = nullptr;  // [3][B]: timing | sharpening | bias
+    ~SamplePlan() override {
+        if (rows_own) hipFree(rows_own);
+    }
+    int set_row_controls(const float* timing, const float* sharpening, const float* bias) {
+        if (has_run) return PARROT_ERR_BADARG;  // a captured graph holds the pointers by value
+        if (bias && d.gmm_K <= 0) return PARROT_ERR_BADARG;
+        if (!timing && !sharpening && !bias) {
+            has_rows = false;
+            return 0;
+        }
+        if (!rows_own) {
+            PH_CHECK(hipMalloc(reinterpret_cast<void**>(&rows_own), (size_t)3 * d.B * sizeof(float)));
+            std::vector<float> host((size_t)3 * d.B);
+            for (int b = 0; b < d.B; ++b) {
+                host[b] = d.timing; host[(size_t)d.B + b] = d.sharpening; host[(size_t)2 * d.B + b] = d.sampling_bias;
+            }
+            PH_CHECK(hipMemcpy(rows_own, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        rows.timing = timing ? timing : rows_own;
+        rows.sharpening = sharpening ? sharpening : rows_own + d.B;
+        rows.bias = bias ? bias : rows_own + (size_t)2 * d.B;
+        has_rows = true;
+        return 0;
+    }
 
     // ---- persistent phase machine for the decode loop (persist.h) ------------------------------------------------
     // One resident kernel runs all S steps; a step = 2L + 3 phases: G_0, C_0, ATT, (G_l, C_l for l >= 1), readout,
@@ -537,7 +573,7 @@ struct SamplePlan : PlanBase {
             PL_TRY((int)hipMemcpyAsync(sl.h[l], d.h[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
             if (sl.c[l]) PL_TRY((int)hipMemcpyAsync(sl.c[l], d.cwork[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
-        return pm_launch(pm_prog, st);
+        return pm_launch(pm_prog, st, has_rows ? &rows : nullptr);
     }
 
     // ---- LSTM stacks on the machine ----------------------------------------------------------------------------------
@@ -1025,7 +1061,8 @@ struct SamplePlan : PlanBase {
                     g.B = d.B; g.H = H; g.A = d.A; g.U = d.U; g.E = d.E; g.esplit = esplit;
                     g.att_type = d.att_type; g.eps = d.eps; g.alignment = d.alignment;
                     g.sharpening = d.sharpening; g.timing = d.timing;
-                    PL_TRY(att_fwd_launch(g, st));
+                    if (has_rows) PL_TRY(att_fwd_rows_launch(g, AttRowCtl{rows.sharpening, rows.timing}, st));
+                    else PL_TRY(att_fwd_launch(g, st));
                 }
             }
             // readouts (model.py:992-1006) and output (model.py:1008-1013)
@@ -1060,7 +1097,8 @@ struct SamplePlan : PlanBase {
                 PL_TRY(gmm_sample_launch(d.gmm_mu, d.gmm_sig, d.gmm_co, d.B, d.O, d.gmm_K, d.sampling_bias, d.eps,
                                          d.unif + (size_t)t * d.B, d.noise + (size_t)t * d.B * d.O,
                                          d.x + (size_t)(t + 1) * d.B * d.ldx, d.ldx,
-                                         d.pi_out ? d.pi_out + (size_t)t * d.B * d.gmm_K : nullptr, st));
+                                         d.pi_out ? d.pi_out + (size_t)t * d.B * d.gmm_K : nullptr, st,
+                                         has_rows ? rows.bias : nullptr));
                 continue;
             }
             sk_linear_job(j, sk_seg(d.readout, d.R, d.Wo, d.O, d.R, 0), d.B, d.O, H, d.x + (size_t)(t + 1) * d.B * d.ldx, d.ldx);
@@ -1093,6 +1131,9 @@ int parrot_sample_status(void* plan) { PH_ENTRY(); return plan ? static_cast<Sam
 int parrot_sample_stops_early(void* plan) {
     const SamplePlan* p = static_cast<SamplePlan*>(plan);
     return (p && p->stops_early()) ? 1 : 0;
+}
+int parrot_sample_set_row_controls(void* plan, const float* timing, const float* sharpening, const float* sampling_bias) { PH_ENTRY();
+    return plan ? static_cast<SamplePlan*>(plan)->set_row_controls(timing, sharpening, sampling_bias) : PARROT_ERR_BADARG;
 }
 int parrot_sample_steps_run(void* plan, int* steps) { PH_ENTRY();
     return plan ? static_cast<SamplePlan*>(plan)->steps_run(steps) : PARROT_ERR_BADARG;

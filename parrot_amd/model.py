@@ -1564,8 +1564,71 @@ class Parrot(Brick):
             _lib.load().parrot_sample_destroy(plan)
             raise ValueError("sample_until_end: the plan the library built does not stop at the end of the utterance")
         ws['plan'], ws['desc'] = plan, d
+        # per-row controls (parrot_sample_set_row_controls): the arrays live here and the plan is given them before its
+        # first run; every call writes all of them -- the caller's values, or else the model's scalars (_write_row_controls)
+        ws['row_timing'], ws['row_sharpening'] = torch.empty(N, **f), torch.empty(N, **f)
+        ws['row_bias'] = torch.empty(N, **f) if gmm else None
+        try:
+            _lib.call('parrot_sample_set_row_controls', plan, ws['row_timing'].data_ptr(), ws['row_sharpening'].data_ptr(),
+                      ws['row_bias'].data_ptr() if gmm else None)
+        except _lib.HipCallError:
+            _lib.load().parrot_sample_destroy(plan)
+            raise
         self._sample_ws[ws_key] = ws  # (`key` is the group key of the loops above)
         return ws
+
+    def _check_row_controls(self, N, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
+        """Validates the per-utterance arguments of the decode calls without touching the device (a model that was never
+        allocated can be asked): returns (controls, speaker_weights) -- controls maps 'timing' / 'sharpening' / 'bias' to a
+        float32 numpy array of N values, or to None where the model's scalar holds for every row; speaker_weights is a float32
+        [N, num_speakers] numpy array or None.  ValueError on a wrong length, a non-finite value, a timing or sharpening
+        coefficient <= 0, biases on a model without a GMM head, weights on a model without speakers."""
+        ctl = {}
+        for name, key, vals in (('timing_coeffs', 'timing', timing_coeffs), ('sharpening_coeffs', 'sharpening', sharpening_coeffs),
+                                ('sampling_biases', 'bias', sampling_biases)):
+            if vals is None:
+                ctl[key] = None
+                continue
+            if key == 'bias' and self.which_cost != 'GMM':
+                raise ValueError(f"sampling_biases needs which_cost='GMM': the {self.which_cost} head has no sampling bias")
+            if torch.is_tensor(vals):
+                vals = vals.detach().cpu().numpy()
+            a = numpy.asarray(vals, dtype=numpy.float64)
+            if a.shape != (N,):
+                raise ValueError(f"{name} needs {N} values (one per utterance), got shape {tuple(a.shape)}")
+            a32 = a.astype(numpy.float32)
+            if not numpy.all(numpy.isfinite(a32)):
+                raise ValueError(f"{name} must be finite, got {a.tolist()}")
+            if key != 'bias' and not numpy.all(a32 > 0):
+                raise ValueError(f"{name} must be > 0, got {a.tolist()}")
+            ctl[key] = a32
+        sw = None
+        if speaker_weights is not None:
+            if not self.use_speaker:
+                raise ValueError("speaker_weights needs use_speaker=True: this model has no speaker table to blend")
+            if torch.is_tensor(speaker_weights):
+                speaker_weights = speaker_weights.detach().cpu().numpy()
+            sw = numpy.asarray(speaker_weights, dtype=numpy.float32)
+            if sw.shape != (N, self.num_speakers):
+                raise ValueError(f"speaker_weights needs shape ({N}, {self.num_speakers}) = (utterances, num_speakers), "
+                                 f"got {tuple(sw.shape)}")
+            if not numpy.all(numpy.isfinite(sw)):
+                raise ValueError("speaker_weights must be finite")
+        return ctl, sw
+
+    def _write_row_controls(self, ws, ctl):
+        """Every decode call writes all of the workspace's control arrays: a call without controls after one with them
+        decodes with the model's scalars again."""
+        ctl = ctl or {}
+        for key, scalar in (('timing', self.timing_coeff), ('sharpening', self.sharpening_coeff), ('bias', self.sampling_bias)):
+            t = ws['row_' + key]
+            if t is None:
+                continue
+            vals = ctl.get(key)
+            if vals is None:
+                t.fill_(float(scalar))
+            else:
+                t.copy_(torch.from_numpy(numpy.ascontiguousarray(vals)))
 
     def _decode_machine_refusal(self, N):
         """Why this model / batch does not decode on the persistent machine ('' when it does).  The one statement of the
@@ -1613,14 +1676,17 @@ class Parrot(Brick):
         return self._decode_machine_refusal(N)
 
     def sample_until_end_device(self, labels, labels_mask, speaker, num_samples, max_steps, extra=40, unif=None, noise=None,
-                                seed=None):
+                                seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None,
+                                speaker_weights=None):
         """sample_model_device that stops at the end of the utterance INSIDE the decode kernel instead of decoding
         max_steps frames and cutting afterwards.  The rule is end_of_utterance's (reference sample.py:145-163): a row ends
         `extra` frames after the first step whose window weight on the position just past its text beats the weight on every
         real character.  Returns (outs, lengths): the six tensors of sample_model_device cut to steps_run = max(lengths)
         along time -- bit-identical to the first steps_run steps of sample_model_device(.., max_steps) -- and lengths [N]
-        (int64, on the device) = what end_of_utterance gives for each row of the full-length phi."""
+        (int64, on the device) = what end_of_utterance gives for each row of the full-length phi.
+        timing_coeffs / sharpening_coeffs / sampling_biases / speaker_weights: as sample_model_device."""
         from .utils import end_of_utterance_args
+        ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
         why = self._decode_stop_refusal(num_samples, extra)  # (before anything is keyed on `extra` or allocated)
         if why:
             raise ValueError("sample_until_end " + why)
@@ -1631,7 +1697,7 @@ class Parrot(Brick):
         pos, ncmp = end_of_utterance_args(lm.detach().cpu().numpy(), U)
         ws['eou_pos'].copy_(torch.from_numpy(pos))
         ws['eou_ncmp'].copy_(torch.from_numpy(ncmp))
-        outs = self._sample_device(ws, labels, labels_mask, speaker, num_samples, max_steps, unif, noise, seed)
+        outs = self._sample_device(ws, labels, labels_mask, speaker, num_samples, max_steps, unif, noise, seed, ctl)
         steps = C.c_int(0)
         _lib.call('parrot_sample_steps_run', ws['plan'], C.byref(steps))
         first = ws['eou_first'].long()
@@ -1641,22 +1707,34 @@ class Parrot(Brick):
             raise RuntimeError(f"the decode machine completed {steps.value} frames, the rows' lengths ask for {steps_run}")
         return [o[:steps_run] for o in outs], lengths
 
-    def sample_until_end(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, max_steps, extra=40):
+    def sample_until_end(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, max_steps, extra=40,
+                         timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
         """numpy twin of sample_until_end_device (as sample_model is of sample_model_device): (list of numpy arrays,
         numpy lengths [N])."""
-        outs, lengths = self.sample_until_end_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, max_steps, extra)
+        outs, lengths = self.sample_until_end_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, max_steps, extra,
+                                                     timing_coeffs=timing_coeffs, sharpening_coeffs=sharpening_coeffs,
+                                                     sampling_biases=sampling_biases, speaker_weights=speaker_weights)
         return [o.detach().cpu().numpy().copy() for o in outs], lengths.cpu().numpy()
 
     def sample_model_device(self, labels, labels_mask, speaker, num_samples, num_steps, unif=None, noise=None,
-                            seed=None):
+                            seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
         """Device-resident version of sample_model: returns torch tensors
         [sample_x [S,N,O], k [S,N,A], w [S,N,E], pi, phi [S,N,U], pi_att [S,N,A]].
         GMM head: the component choice / Gaussian noise come from `unif` [S,N] and `noise` [S,N,O] if given,
-        else from torch's generator (`seed`); Theano's MRG stream itself is not reproducible."""
-        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed)
+        else from torch's generator (`seed`); Theano's MRG stream itself is not reproducible.
+        Per utterance (all None: the model's scalars and the indexed speakers, bit for bit what the call was without them):
+        timing_coeffs / sharpening_coeffs / sampling_biases -- N floats each, row b decodes with its own value in place of
+        timing_coeff / sharpening_coeff / sampling_bias, on whichever path decodes the model (decode_path);
+        speaker_weights [N, num_speakers] -- row b's speaker embedding is speaker_weights[b] @ lookuptable.W (one f32
+        product) instead of the looked-up row; `speaker` is then not read.  ValueError (before anything is allocated) on a
+        wrong length, non-finite values, timing / sharpening <= 0, biases on an MSE model, weights without use_speaker."""
+        ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
+        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl)
 
-    def _sample_device(self, ws, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed):
-        """One decode call on the workspace `ws` (None: the plain workspace of the shape)."""
+    def _sample_device(self, ws, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl=None):
+        """One decode call on the workspace `ws` (None: the plain workspace of the shape).  ctl: what _check_row_controls
+        returned (None: no per-utterance arguments)."""
+        controls, speaker_weights = ctl if ctl is not None else (None, None)
         self.allocate()
         dev = self._dev()
         labels = torch.as_tensor(labels).to(dev)
@@ -1676,9 +1754,14 @@ class Parrot(Brick):
         for l in range(1, L + 1):
             if not self.layer_norm:
                 ws['br'].add_(self._p(f'/h{l}_to_readout.b'))
+        self._write_row_controls(ws, controls)
         if self.use_speaker:
-            speaker = torch.as_tensor(speaker).to(dev)
-            emb = self._p('/lookuptable.W')[speaker[:, 0].long()].contiguous()
+            if speaker_weights is not None:  # a blend of the table's rows in place of one of them
+                with ops.gemm_precision(ops.PRECISION_F32):
+                    emb = ops.gemm(torch.from_numpy(speaker_weights).to(dev).contiguous(), self._p('/lookuptable.W'))
+            else:
+                speaker = torch.as_tensor(speaker).to(dev)
+                emb = self._p('/lookuptable.W')[speaker[:, 0].long()].contiguous()
             for l in range(1, L + 1):
                 for key, wd, suf, mat, rec in self._groups:
                     ops.gemm(emb, self._p(f'/speaker_to_h{l}/fork_rnn{l}_{suf}.W'),
@@ -1788,10 +1871,14 @@ class Parrot(Brick):
             cat[H + E + 64:].copy_((A_last @ base[H + E:H + E + 64].double()).float())
             tile(cat, pm['tiled'][('x', key)])
 
-    def sample_model(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, num_steps):
+    def sample_model(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, num_steps,
+                     timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
         """Parrot.sample_model (model.py:1061-1083): numpy in, list of numpy arrays out
-        [sample_x, k, w, pi, phi, pi_att], all time-major (the caller swaps axes, sample.py:142-143)."""
-        outs = self.sample_model_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, num_steps)
+        [sample_x, k, w, pi, phi, pi_att], all time-major (the caller swaps axes, sample.py:142-143).  The four keyword
+        arguments: per utterance, as sample_model_device."""
+        outs = self.sample_model_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, num_steps,
+                                        timing_coeffs=timing_coeffs, sharpening_coeffs=sharpening_coeffs,
+                                        sampling_biases=sampling_biases, speaker_weights=speaker_weights)
         return [o.detach().cpu().numpy().copy() for o in outs]
 
     def sample_using_input(self, data_tr, num_samples):

@@ -156,11 +156,82 @@ def sample_parse(argv=None):
                         help="M in (0, 1] (with --raw_output): of the codes --top_k and --top_p left, the SampleRNN vocoder's "
                              "draws at temperature > 0 keep those at least M times as likely as the most likely code, in both "
                              "draw modes; 0: off (DESIGN.md 3.6)")
+    parser.add_argument('--timing_coeffs', type=str, default=None,
+                        help='comma-separated list of exactly --num_samples values: utterance i decodes with its own '
+                             'speaking rate in place of --timing_coeff (Parrot.sample_model(timing_coeffs=..))')
+    parser.add_argument('--sharpening_coeffs', type=str, default=None,
+                        help='comma-separated list of exactly --num_samples values: utterance i decodes with its own window '
+                             'sharpening in place of --sharpening_coeff')
+    parser.add_argument('--sampling_biases', type=str, default=None,
+                        help='comma-separated list of exactly --num_samples values (GMM head): utterance i samples with its '
+                             'own bias in place of --sampling_bias')
+    parser.add_argument('--mix_speakers', type=str, default='15,11',
+                        help='A,B: the two speakers --mix blends, m * W[A] + (1 - m) * W[B] (the pair of sample.py:81-85)')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
         args.save_dir = os.path.join(args.save_dir, args.dataset)
+    for flag in ('timing_coeffs', 'sharpening_coeffs', 'sampling_biases'):
+        if getattr(args, flag) is not None:
+            setattr(args, flag, parse_float_list(getattr(args, flag), args.num_samples, '--' + flag))
+    args.mix_speakers = parse_speaker_pair(args.mix_speakers)
     return args
+
+
+def parse_float_list(text, count, flag):
+    """'0.8,1,1.25' -> [0.8, 1.0, 1.25]; SystemExit naming both numbers unless there are exactly `count` values."""
+    items = [x.strip() for x in str(text).split(',') if x.strip()]
+    try:
+        vals = [float(x) for x in items]
+    except ValueError:
+        raise SystemExit("%s: %r is not a comma-separated list of numbers" % (flag, text))
+    if len(vals) != count:
+        raise SystemExit("%s has %d values, --num_samples is %d: one value per utterance" % (flag, len(vals), count))
+    return vals
+
+
+def parse_speaker_pair(text):
+    try:
+        a, b = (int(x) for x in str(text).split(','))
+    except ValueError:
+        raise SystemExit("--mix_speakers: %r is not a pair of speaker indices A,B" % (text,))
+    return a, b
+
+
+def mix_speaker_weights(mix, pair, num_speakers, num_samples):
+    """The blend of sample.py:81-85 as Parrot.sample_model's speaker_weights: every row mix * W[pair[0]] +
+    (1 - mix) * W[pair[1]], float32 [num_samples, num_speakers].  The checkpoint's table stays as it is."""
+    import numpy
+    a, b = pair
+    if not (0 <= a < num_speakers and 0 <= b < num_speakers):
+        raise SystemExit("--mix_speakers %d,%d: the model has %d speakers" % (a, b, num_speakers))
+    w = numpy.zeros((num_samples, num_speakers), dtype=numpy.float32)
+    w[:, a] += numpy.float32(mix)
+    w[:, b] += numpy.float32(1. - mix)
+    return w
+
+
+def phrase_labels(phrase, dataset, num_samples, data_path=None):
+    """sample.py:68-76: the phrase's characters through $FUEL_DATA_PATH/<dataset>/char2code.pkl, tiled to num_samples rows,
+    with a mask of ones.  SystemExit naming a missing file or an unknown character."""
+    import pickle
+
+    import numpy
+    if data_path is None:
+        data_path = os.environ.get('FUEL_DATA_PATH')
+        if not data_path:
+            raise SystemExit("--phrase needs FUEL_DATA_PATH: char2code.pkl is read from $FUEL_DATA_PATH/%s/" % dataset)
+    path = os.path.join(data_path, dataset, 'char2code.pkl')
+    if not os.path.isfile(path):
+        raise SystemExit("--phrase: %s not found (the dataset's own character table)" % path)
+    with open(path, 'rb') as f:
+        char2code = pickle.load(f)
+    for ch in phrase:
+        if ch not in char2code:
+            raise SystemExit("--phrase: character %r is not in %s" % (ch, path))
+    labels = numpy.array([char2code[ch] for ch in phrase], dtype='int32')
+    labels = numpy.tile(labels, (num_samples, 1))
+    return labels, numpy.ones(labels.shape, dtype='float32')
 
 
 def end_of_utterance(phi, labels_length, num_steps, extra=40):

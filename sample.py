@@ -11,7 +11,7 @@ from parrot_amd.checkpoint import load_parameters
 from parrot_amd.datasets import parrot_stream
 from parrot_amd.generate import generate_wav
 from parrot_amd.model import Parrot
-from parrot_amd.utils import end_of_utterance, sample_parse
+from parrot_amd.utils import end_of_utterance, mix_speaker_weights, phrase_labels, sample_parse
 
 
 def main(argv=None):
@@ -41,8 +41,22 @@ def main(argv=None):
     if args.random_speaker:
         numpy.random.seed(1)
         speaker_tr = numpy.random.randint(1, saved_args.num_speakers, (args.num_samples, 1)).astype('int32')
+    if args.phrase is not None:  # sample.py:68-76
+        labels_tr, labels_mask_tr = phrase_labels(args.phrase, args.dataset, args.num_samples)
     if args.speaker_id and saved_args.use_speaker:
         speaker_tr = speaker_tr * 0 + args.speaker_id
+    # sample.py:81-85 blends two rows of the speaker table into row 0 of the checkpoint; here the blend is the call's
+    # speaker_weights and the table stays as it was loaded
+    speaker_weights = None
+    if args.mix:
+        if saved_args.use_speaker:
+            speaker_weights = mix_speaker_weights(args.mix, args.mix_speakers, saved_args.num_speakers, args.num_samples)
+            print("--mix %g: every utterance decodes with %g * speaker %d + %g * speaker %d"
+                  % (args.mix, args.mix, args.mix_speakers[0], 1. - args.mix, args.mix_speakers[1]))
+        else:
+            print("--mix %g ignored: the experiment was trained without speakers" % args.mix)
+    row_controls = dict(timing_coeffs=args.timing_coeffs, sharpening_coeffs=args.sharpening_coeffs,
+                        sampling_biases=args.sampling_biases, speaker_weights=speaker_weights)
 
     device = torch.device(args.device)
     parrot = Parrot(
@@ -75,10 +89,10 @@ def main(argv=None):
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_using_input(data_tr, args.num_samples)
     elif args.stop_at_end:  # the kernel applies the end-of-utterance rule itself and decodes no frame beyond it
         (gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att), stop_lengths = parrot.sample_until_end(
-            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps)
+            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps, **row_controls)
     else:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_model(
-            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps)
+            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps, **row_controls)
     print("Successfully sampled the parrot.")
 
     gen_x, gen_phi = gen_x.swapaxes(0, 1), gen_phi.swapaxes(0, 1)

@@ -97,6 +97,13 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          --parent-lib (the parent commit's libparrot_hip.so) the default plan of both
                                          libraries in the same alternation, bit identity included; the result also goes to
                                          FILE (default profiles/samplernn_skip.json)
+  bench_extra.py --only decode_row_controls [--reps N] [--row-controls-json FILE] [--parent-lib FILE]
+                                         decode with per-utterance controls (Parrot.sample_model_device(timing_coeffs=, ..)):
+                                         configs[2] and the 2 x LSTM-1024 plan at batch 16, 1000 frames -- the default call and
+                                         the call with all controls given, N alternations in one process, each with its spread;
+                                         with --parent-lib (the parent commit's libparrot_hip.so) the default call of both
+                                         libraries in the same alternation, bit identity included; the result also goes to FILE
+                                         (default profiles/decode_row_controls.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -121,7 +128,8 @@ def _arg(name, dflt=None):
 
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
-       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_min_p", "samplernn_forced", "samplernn_skip", "mulaw")
+       "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_min_p", "samplernn_forced", "samplernn_skip",
+       "decode_row_controls", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1416,6 +1424,95 @@ if "samplernn_skip" in only:
             "bit_identical_t1": bool(np.array_equal(samples["sequential_t1"], samples["parent_sequential_t1"])),
             "t0": pair("argmax"), "t1": pair("sequential_t1")}
     record("samplernn_skip", "--skip-json", res)
+
+# ---- decode with per-utterance controls (parrot_sample_set_row_controls): configs[2] (2 x GRU-1024) and 2 x LSTM-1024 at
+# batch 16, 1000 frames.  Per shape a model whose calls pass no controls, a model whose calls pass all of them and, with
+# --parent-lib, a model on the parent commit's library (which has no such entry: its plan decodes with the descriptor's
+# scalars, as every plan did), all alive in one process and run alternately.
+if "decode_row_controls" in only:
+    import contextlib
+    import ctypes
+    from parrot_amd import _lib as plib
+    from parrot_amd.model import Parrot
+    reps = int(_arg("--reps", "5"))
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            if hasattr(parent_lib, name):
+                fn = getattr(parent_lib, name)
+                fn.restype = res_
+                fn.argtypes = args_
+        parent_lib.parrot_sample_set_row_controls = lambda *a: 0  # (the parent's plans have no controls to be given)
+
+    @contextlib.contextmanager
+    def under(which):  # every call of a model goes to the library that made its plan
+        plib._lib = which
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+
+    N, U, S = 16, 100, 1000
+    gen = torch.Generator().manual_seed(0)
+    lab = torch.randint(0, 43, (N, U), generator=gen)
+    lm = torch.ones(N, U)
+    cyc = lambda v: (v * 4)[:N]
+    rows = dict(timing_coeffs=cyc([1.0, 0.8, 1.25, 2.0, 0.5]), sharpening_coeffs=cyc([1.0, 1.5, 0.7, 1.0, 2.0]))
+    shapes = {"cfg3_gru2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='gru'),
+              "lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='lstm')}
+    res = {"batch": N, "frames": S, "alternations": reps, "timed": "call to device idle (host-side preparation included)",
+           "controls": rows, "shapes": {}}
+    for sname, kw in shapes.items():
+        def model(which):
+            with under(which):
+                return Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, seed=1234, **kw).initialize()
+        runs = {"default": (model(this_lib), this_lib, {}), "row_controls": (model(this_lib), this_lib, rows)}
+        if parent_lib is not None:
+            runs["parent_default"] = (model(parent_lib), parent_lib, {})
+            runs["default_again"] = (model(this_lib), this_lib, {})
+            runs["parent_default_again"] = (model(parent_lib), parent_lib, {})
+        times, frames = {k: [] for k in runs}, {}
+        keys = list(runs)
+        for rep_ in range(reps + 1):  # (the first alternation builds the plans and captures the graphs: not counted)
+            for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:
+                m, which, ckw = runs[k]
+                with under(which):
+                    torch.cuda.synchronize(); t0 = time.time()
+                    outs = m.sample_model_device(lab, lm, None, N, S, **ckw)
+                    torch.cuda.synchronize(); dt = time.time() - t0
+                    frames[k] = outs[0].cpu().numpy().copy()
+                if rep_:
+                    times[k].append(1e6 * dt / S)
+        machine = {}
+        for k, (m, which, _) in runs.items():
+            with under(which):
+                machine[k] = int(which.parrot_sample_is_persistent(m._sample_ws[(S, N, U)]['plan']))
+                m.close()
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        spread = {k: max(v) - min(v) for k, v in times.items()}
+        one = {"runs": {k: {"machine": machine[k], "us_per_step": [round(x, 2) for x in times[k]], "us_per_step_median": round(med[k], 2),
+                            "spread_max_minus_min": round(spread[k], 2)} for k in runs},
+               "row_controls_minus_default_us": round(med["row_controls"] - med["default"], 2),
+               "row_controls_frames_differ_from_default": bool((frames["row_controls"] != frames["default"]).any())}
+        if parent_lib is not None:
+            both = spread["default"] + spread["parent_default"]
+            one["default_path_against_parent_commit"] = {
+                "how": "this build and the parent commit's library loaded in one process, two models of each (the second pair "
+                       "created in the other order), all in the same alternation; the bar compares the first model of each "
+                       "library against the sum of their spreads (max - min over the alternations)",
+                "bit_identical": bool(np.array_equal(frames["default"], frames["parent_default"])),
+                "this_us": [round(med["default"], 2), round(med["default_again"], 2)],
+                "parent_us": [round(med["parent_default"], 2), round(med["parent_default_again"], 2)],
+                "this_minus_parent_us": round(med["default"] - med["parent_default"], 2),
+                "sum_of_the_two_spreads_us": round(both, 2),
+                "bar_default_not_slower_by_more_than_the_sum_of_both_spreads": bool(med["default"] - med["parent_default"] <= both)}
+        res["shapes"][sname] = one
+    res["not_measured"] = ["B > 16", "the H = 1536 LSTM plan with two units per workgroup", "the launch path's timing",
+                           "a GMM head with per-utterance biases"]
+    record("decode_row_controls", "--row-controls-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
