@@ -714,6 +714,39 @@ int parrot_sample_create(const ParrotSampleDesc* desc, void** plan);
 int parrot_sample_run(void* plan, void* stream);
 int parrot_sample_destroy(void* plan);
 
+/* Forced frames (priming), per row: a decode descriptor with three fields behind it.  While t < n_forced[b] the frame fed
+ * back into step t + 1 of row b is forced[t, b] instead of the model's own -- x[t + 1, b] = forced[t, b]; an MSE head's
+ * output frame is replaced, a GMM head's draw.  From step n_forced[b] on the row decodes as ever, from the state (layers,
+ * kappa, w) the prompt left.  Rows are independent; n_forced[b] = 0 is a free row.
+ *   base:     the decode descriptor, every field as above (its offsets are ParrotSampleDesc's: base is the first member).
+ *   forced:   [S, B, ldx] f32, device.  Columns >= O are not read: they are fed back, and written to x, as zero.
+ *   n_forced: [B] int32, device, 0 <= n_forced[b] <= S (not checked).
+ *   own_x:    [S, B, ldx] f32, device, output: what the model computed (MSE) or drew (GMM) at step t BEFORE the select;
+ *             equal to x[t + 1] wherever the row is not forced.
+ * The three fields follow the END of ParrotSampleDesc in a type of their own, not inside it: the library copies a descriptor
+ * by value, so a ParrotSampleDesc that grew would make it read past the buffer of every caller built against this header
+ * as it was, and parrot_sample_create keeps taking exactly the bytes it took.
+ * All three NULL: no forcing, the plan is parrot_sample_create(&base)'s; otherwise all three must be given
+ * (PARROT_ERR_BADARG).  Forcing is a property of the plan: a forced plan cannot take the fed-back frame out of the step's
+ * chain (x[t + 1] = x_pre + h_{L-1} . A does not hold on a forced step), so Wgx_t / Wcx_t are not taken and a GRU stack with
+ * an MSE head decodes on the 2L + 2 phases that PARROT_PM_FBC=0 gives; the attention fold (Watt_t) does not depend on the
+ * composed path and stays.  The pointers are held by value (a captured graph replays with them); their CONTENTS may be
+ * rewritten between runs.  Every path takes them: the persistent machine (GRU and LSTM programs, MSE and GMM heads, the
+ * end-of-utterance stop, the row controls) and the per-step launches.  base.bf16 = 1 with forcing: PARROT_ERR_UNSUPPORTED. */
+typedef struct ParrotSampleForcedDesc {
+    ParrotSampleDesc base;
+    const float* forced;
+    const int* n_forced;
+    float* own_x;
+} ParrotSampleForcedDesc;
+/* parrot_sample_create / parrot_sample_persist_floats / the two dry entries below, for a descriptor with forced frames: the
+ * plan, the workspace size, info16 and the digest of the FORCED plan (info16[15] bit 0 is clear: no composition).  The
+ * plan is run, queried and destroyed like any other (parrot_sample_run, _status, _steps_run, _set_row_controls, _destroy). */
+int parrot_sample_create_forced(const ParrotSampleForcedDesc* desc, void** plan);
+long long parrot_sample_persist_floats_forced(const ParrotSampleForcedDesc* desc);
+int parrot_sample_plan_pieces_dry_forced(const ParrotSampleForcedDesc* desc, int nwg, int* info16);
+int parrot_sample_plan_digest_dry_forced(const ParrotSampleForcedDesc* desc, int nwg, unsigned long long* digest);
+
 int parrot_plan_last_error(void* plan);
 
 /* ------------------------------------------------------------------------------------------

@@ -153,6 +153,12 @@ class SampleDesc(C.Structure):
     ]
 
 
+class SampleForcedDesc(C.Structure):
+    """ParrotSampleForcedDesc: the decode descriptor (its fields read and written as this object's own) and the forced frames."""
+    _anonymous_ = ("base",)
+    _fields_ = [("base", SampleDesc), ("forced", C.c_void_p), ("n_forced", C.c_void_p), ("own_x", C.c_void_p)]
+
+
 class SampleRnnGenDesc(C.Structure):
     # (top_k shares the four bytes that were `int use_graph`: the descriptor has no spare word, see the header)
     _fields_ = ([(n, C.c_int) for n in ("B", "D", "T", "Q", "FS", "BFS", "feat_dim")] +
@@ -243,6 +249,10 @@ SIGNATURES = {
     "parrot_readout_composed_bwd": (_i, [C.POINTER(ReadoutComposedDesc), _vp, _vp]),
     "parrot_sample_create": (_i, [C.POINTER(SampleDesc), C.POINTER(C.c_void_p)]),
     "parrot_sample_persist_floats": (C.c_longlong, [C.POINTER(SampleDesc)]),
+    "parrot_sample_create_forced": (_i, [C.POINTER(SampleForcedDesc), C.POINTER(C.c_void_p)]),
+    "parrot_sample_persist_floats_forced": (C.c_longlong, [C.POINTER(SampleForcedDesc)]),
+    "parrot_sample_plan_pieces_dry_forced": (_i, [C.POINTER(SampleForcedDesc), _i, C.POINTER(C.c_int)]),
+    "parrot_sample_plan_digest_dry_forced": (_i, [C.POINTER(SampleForcedDesc), _i, C.POINTER(C.c_ulonglong)]),
     "parrot_sample_is_persistent": (_i, [_vp]),
     "parrot_sample_is_bf16": (_i, [_vp]),
     "parrot_sample_plan_pieces_dry": (_i, [C.POINTER(SampleDesc), _i, C.POINTER(C.c_int)]),

@@ -20,11 +20,11 @@ OBJDIR = os.path.join(CSRC, "build")
 ARCH = "gfx950"
 
 SOURCES = ["skinny.hip", "biggemm.hip", "attention.hip", "elementwise.hip", "quantize.hip",
-           "plans.hip", "plans_decode.hip", "capi.hip", "samplernn.hip", "persist.hip", "sr_persist.hip", "rowgru.hip", "trainops.hip", "readout.hip",
+           "plans.hip", "plans_decode.hip", "capi.hip", "samplernn.hip", "persist.hip", "persist_forced.hip", "sr_persist.hip", "rowgru.hip", "trainops.hip", "readout.hip",
            "gmmcost.hip", "labeltables.hip"]
 EXTRA_FLAGS = {"quantize.hip": ["-ffp-contract=off"]}
 if env_str("PARROT_PM_DEPTH"):  # development: ring depth of the persistent machine's K loop
-    EXTRA_FLAGS["persist.hip"] = ["-DPM_DEPTH=" + env_str("PARROT_PM_DEPTH")]
+    EXTRA_FLAGS["persist.hip"] = EXTRA_FLAGS["persist_forced.hip"] = ["-DPM_DEPTH=" + env_str("PARROT_PM_DEPTH")]
 
 
 def _hipcc() -> str:

@@ -159,6 +159,10 @@ int gmm_sample_launch(const float* mu, const float* sig_hat, const float* co_hat
                       float eps, const float* unif, const float* noise, float* x, int ldx, float* pi_out,
                       hipStream_t stream, const float* bias_rows = nullptr);  // bias_rows: [B], row b's own bias; null: `bias`
 
+// Forced frames of the decode's per-step launches: x [B, ldx] = the frame step t has just written; own <- x, and
+// x <- forced where t < n[b] (own / forced: the [B, ldx] rows of step t; columns >= O zero).
+int frame_force_launch(float* x, float* own, const float* forced, const int* n, int t, int B, int O, int ldx, hipStream_t stream);
+
 struct LstmStateBwdChain {
     const float* dh;      // [B,H] gradient wrt s_t
     const float* dh2;     // [B,H] optional second share of it or null

@@ -187,6 +187,19 @@ __global__ __launch_bounds__(64) void gmm_sample_kernel(const float* __restrict_
     }
 }
 
+// Forced frames of the decode's per-step launches (ParrotSampleForcedDesc::forced): x = the frame the step has just written
+// (x[t + 1], [B, ldx]), by either head.  own[b] keeps it; while t < n[b] the row's forced frame takes its place.  Columns
+// >= O: zero in own, and zero in x where the row is forced.
+__global__ __launch_bounds__(256) void frame_force_kernel(float* __restrict__ x, float* __restrict__ own,
+                                                          const float* __restrict__ forced, const int* __restrict__ n, int t,
+                                                          int B, int O, int ldx) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * ldx) return;
+    const int b = i / ldx, o = i % ldx;
+    own[i] = o < O ? x[i] : 0.f;
+    if (t < n[b]) x[i] = o < O ? forced[i] : 0.f;
+}
+
 __global__ __launch_bounds__(256) void lstm_state_bwd_kernel(const float* __restrict__ dh,
                                                              const float* __restrict__ dh2, float* __restrict__ dc,
                                                              const float* __restrict__ gates,
@@ -346,6 +359,11 @@ int gmm_sample_launch(const float* mu, const float* sig_hat, const float* co_hat
     else
         hipLaunchKernelGGL(gmm_sample_kernel<false>, dim3(B), dim3(64), 0, stream, mu, sig_hat, co_hat, O, K, bias, bias_rows, eps,
                            unif, noise, x, ldx, pi_out);
+    return (int)hipGetLastError();
+}
+
+int frame_force_launch(float* x, float* own, const float* forced, const int* n, int t, int B, int O, int ldx, hipStream_t stream) {
+    hipLaunchKernelGGL(frame_force_kernel, dim3((B * ldx + 255) / 256), dim3(256), 0, stream, x, own, forced, n, t, B, O, ldx);
     return (int)hipGetLastError();
 }
 

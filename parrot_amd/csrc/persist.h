@@ -60,7 +60,8 @@ struct PmUnit {
     unsigned a_off, a_st;        // the activation slab the unit reads
     int a_nch, a_c0;             // chunks per row block of that slab / the unit's first chunk in it (K/16 chunks are read)
     const float* W;              // fragment-major weights of the unit: [K/16][256] floats (PM_GEMM16: [K/32][512] bf16)
-    int epi, M, rtile, row;      // rtile: GATES tile of the reset gate (LSTM: the tile's quarter of a block, below); row: batch row of an ATT unit
+    int epi, M, rtile, row;      // rtile: GATES tile of the reset gate (LSTM: the tile's quarter of a block, below; LINEAR: 1 + the
+                                 // frame's column tile on the unit a forced program selects in, PmForce); row: batch row of an ATT unit
     const float* bias;           // 16 floats (the tile's columns) or null
     PmRM add[4];                 // additive pre-activation inputs (p == null: unused)
     PmRM e0, e1;                 // GATES (r tile): e0 = h_prev;  CAND: e0 = h_prev, e1 = z
@@ -184,7 +185,26 @@ struct PmRows {
     const float* timing; const float* sharpening; const float* bias;
 };
 
+// Forced frames (decode, ParrotSampleForcedDesc::forced / n_forced / own_x): while t < n[b] the frame fed back into step t + 1 of
+// row b is forced[t, b] instead of what the model emitted (MSE head) or drew (GMM head).  The unit that produces the frame
+// does the select in its epilogue, in front of its stores: a LINEAR unit of a forced program whose PmUnit::rtile is 1 + ct
+// owns columns 16 ct .. 16 ct + 15 of the frame (rtile is 0 on every other LINEAR unit and in every program without
+// forcing); a PM_SAMPLE unit owns the whole row.  The value computed BEFORE the select goes to own_x[t, b] (row-major, a
+// plain store: nothing inside the launch reads it); the selected value goes to x[t + 1] and to every PmDst copy, so a slab
+// holds the bits the row-major frame holds.  Columns >= O of a forced frame are not read and are fed back as zero.  A
+// third kernel argument, as PmRows is the second and for the same reason: a program without forcing keeps its records and
+// its digest, and the kernels compiled without it (FRC = false) never read it.  The kernels with it always carry the row
+// controls too (ROW = true): the forced launcher takes both.
+struct PmForce {
+    const float* forced;  // [T, B, ldx]
+    const int* n;         // [B], 0 <= n[b] <= T
+    float* own_x;         // [T, B, ldx]
+    int B, O, ldx, pad;
+};
+
 int pm_launch(const PmProgram& prog, hipStream_t stream, const PmRows* rows = nullptr);
+// the same launch with forced frames: the kernels of persist_forced.hip (f32 operands only: prog.w16 == 0)
+int pm_launch_forced(const PmProgram& prog, hipStream_t stream, const PmRows& rows, const PmForce& force);
 // synchronises; frames the last launch completed: T, or fewer when the end-of-utterance stop ended it (PmAtt::eou_extra > 0)
 int pm_steps_run(const PmProgram& prog, int* steps);
 int pm_status(const PmProgram& prog);  // synchronises; 0, or non-zero when a launch on this program's workspace gave up

@@ -181,9 +181,12 @@ __device__ __forceinline__ f32x4 pm_sigmoid4(f32x4 x) {
 // programs (LS = false) compile to what they were before the LSTM epilogue existed.
 // W16: the unit is a PM_GEMM16 (persist.h): bf16 weight slab, 32-deep steps, one v_mfma_f32_16x16x32_bf16 per step.  Also
 // a template parameter: only the kernels of the programs that have such units (PmProgram::w16) carry the second K loop.
-template <int MB, bool DF, bool LS, bool W16>
+// FRC: the launch carries forced frames (PmForce, persist.h): the LINEAR unit that produces the fed-back frame keeps what it
+// computed in own_x and publishes the forced quad instead while the row's prompt lasts.  false: F is not read.
+template <int MB, bool DF, bool LS, bool W16, bool FRC = false>
 __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds_w, float* lds_red,
-                                        const __amdgpu_buffer_rsrc_t fm, unsigned long long* stage, unsigned* sync) {
+                                        const __amdgpu_buffer_rsrc_t fm, unsigned long long* stage, unsigned* sync,
+                                        const PmForce& F) {
     const unsigned long long ts0 = pm_clock();
     constexpr int KS = 8 / MB;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -243,6 +246,12 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
         if (u.e0.p) p_e0 = pm_rm_load(u.e0, t, m, n0);
         if (u.e1.p) p_e1 = pm_rm_load(u.e1, t, m, ne);
     }
+    // forced frames: the frame's unit (rtile = 1 + its column tile) asks for the row's prompt length now, beside the other
+    // epilogue operands (written before the launch).  The forced quad itself is asked for in the epilogue, by the rows whose
+    // prompt still lasts: held across the K loop its four registers went to scratch, and a free row never needs it.
+    const int f_ct = FRC ? __builtin_amdgcn_readfirstlane(u.epi == PM_EPI_LINEAR ? u.rtile : 0) - 1 : -1;
+    int f_n = 0;
+    if (FRC && f_ct >= 0 && fin && row_ok) f_n = F.n[m];
 
     const unsigned long long ts1 = pm_clock();
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -453,7 +462,17 @@ __device__ __forceinline__ void pm_gemm(const PmUnit& u, int t, const float* lds
             const f32x4 pre = v + p_bias + p_add;
             if (u.epi == PM_EPI_LINEAR) {
                 fmv = pre;
-                pm_rm_store<true>(u.out, t, m, n0, pre);
+                if (FRC && f_ct >= 0) {  // the select, in front of the write-through store and of every slab copy
+                    const int f_col = 16 * f_ct + n0;
+                    const size_t f_at = ((size_t)t * F.B + m) * F.ldx + f_col;
+                    *reinterpret_cast<f32x4*>(F.own_x + f_at) = pre;
+                    if (t < f_n) {
+                        const f32x4 f_v = *reinterpret_cast<const f32x4*>(F.forced + f_at);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) fmv[i] = f_col + i < F.O ? f_v[i] : 0.f;
+                    }
+                }
+                pm_rm_store<true>(u.out, t, m, n0, fmv);
             } else if (u.epi == PM_EPI_GATES) {
                 const f32x4 gt = pm_sigmoid4(pre);
                 if (!u.rtile) {
@@ -818,9 +837,11 @@ __device__ __forceinline__ float pm_sel4(const f32x4& v, unsigned i) {  // (a ru
     return i == 0u ? v[0] : (i == 1u ? v[1] : (i == 2u ? v[2] : v[3]));
 }
 // ROW: the sampling bias is the row's own (PmRows::bias), asked for beside the row's uniform number and noise.
-template <bool DF, bool ROW>
-__device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmRows& R, const PmUnit& u, int t, float* lds_red,
-                                              float* fm_base, unsigned* sync) {
+// FRC: forced frames (PmForce, persist.h): the draw goes to own_x, and while the row's prompt lasts the forced frame takes
+// its place in x[t + 1] and in every slab copy.  The prompt length and the forced column are asked for beside the noise.
+template <bool DF, bool ROW, bool FRC>
+__device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmRows& R, const PmForce& F, const PmUnit& u, int t,
+                                              float* lds_red, float* fm_base, unsigned* sync) {
     const int tid = threadIdx.x, lane = tid & 63;
     if (__builtin_amdgcn_readfirstlane(tid >> 6) == 0) {
         const int b = __builtin_amdgcn_readfirstlane(u.row), K = g.K, O = g.O, OK = O * K;
@@ -833,6 +854,12 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmRows& R, 
         const float uu = g.unif[tb];
         const float nz = g.noise[tb * O + oc];
         const float bias = ROW ? R.bias[b] : g.bias;
+        int f_n = 0;
+        float f_v = 0.f;
+        if (FRC) {
+            f_n = F.n[b];
+            f_v = F.forced[tb * F.ldx + oc];
+        }
         if (DF) {
             unsigned n = 0;
             while (__builtin_amdgcn_ballot_w64(pm_is_empty(vc)) != 0ull) {
@@ -880,13 +907,16 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmRows& R, 
         // the frame (64 columns, zeros from O on) through LDS into 16 quads: one 16-byte write-through store per quad into
         // row-major x[t + 1] and into every fragment-major destination (block (b / 16, chunk + e / 16), lane
         // (e % 16) / 4 * 16 + b % 16 holds columns e .. e + 3, as the attention row's w); 16 lanes per destination
-        lds_red[lane] = xo;
+        // (FRC) the select, in front of the staging: the draw is staged beside the fed-back frame and leaves as own_x
+        lds_red[lane] = (FRC && t < f_n) ? (lane < O ? f_v : 0.f) : xo;
+        if (FRC) lds_red[64 + lane] = xo;
         __builtin_amdgcn_wave_barrier();
         const int e4 = 4 * (lane & 15);
         const f32x4 quad = *reinterpret_cast<const f32x4*>(lds_red + e4);
         if (lane < 16) {
             float* p = g.x + ((size_t)t * g.B + b) * g.ldx + e4;
             asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(quad) : "memory");
+            if (FRC) *reinterpret_cast<f32x4*>(F.own_x + tb * F.ldx + e4) = *reinterpret_cast<const f32x4*>(lds_red + 64 + e4);
         }
         const int ndst = __builtin_amdgcn_readfirstlane(u.ndst);
         for (int q0 = 0; q0 < ndst && q0 < PM_MAXDST; q0 += 4) {
@@ -909,8 +939,18 @@ __device__ __forceinline__ void pm_sample_row(const PmSamp& g, const PmRows& R, 
 // EOU: the program asks for the end-of-utterance stop (PmAtt::eou_extra > 0); false: the kernel is what it was before that
 // SMP: the program has PM_SAMPLE units (PmSamp::K > 0, a GMM head); false: the kernel is what it was before they existed
 // ROW: the launch carries per-row decode controls (PmRows); false: R is not read and the kernel is what it was before them
-template <int MB, bool DF, bool LS, bool W16, bool EOU, bool SMP, bool ROW>
-__global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P, const PmRows R) {
+// FRC: the launch carries forced frames (PmForce): the second argument is then the row controls AND the forced frames
+// (PmRowsF); false: it is PmRows and the kernel is what it was before forcing existed
+struct PmRowsF : PmRows {
+    PmForce f;
+};
+__device__ __forceinline__ const PmForce& pm_force_of(const PmRowsF& r, const PmForce&) { return r.f; }
+__device__ __forceinline__ const PmForce& pm_force_of(const PmRows&, const PmForce& none) { return none; }
+
+template <int MB, bool DF, bool LS, bool W16, bool EOU, bool SMP, bool ROW, bool FRC = false>
+__global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P, const std::conditional_t<FRC, PmRowsF, PmRows> R) {
+    const PmForce no_force = {nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const PmForce& F = pm_force_of(R, no_force);
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* lds_w = lds;
     float* lds_red = lds + PM_LDS_W;
@@ -1027,9 +1067,9 @@ __global__ __launch_bounds__(PM_THREADS) void pm_kernel(const PmProgram P, const
                 if (kind == PM_NONE) continue;
                 const int t = tick - __builtin_amdgcn_readfirstlane(u.lag);
                 if (t < 0 || t >= P.T) continue;
-                if (kind == PM_GEMM) pm_gemm<MB, DF, LS, false>(u, t, lds_w, lds_red, fmr, stage, sync);
-                else if (W16 && kind == PM_GEMM16) pm_gemm<MB, DF, LS, true>(u, t, lds_w, lds_red, fmr, stage, sync);
-                else if (SMP && kind == PM_SAMPLE) pm_sample_row<DF, ROW>(P.samp, R, u, t, lds_red, P.fm_base, sync);
+                if (kind == PM_GEMM) pm_gemm<MB, DF, LS, false, FRC>(u, t, lds_w, lds_red, fmr, stage, sync, F);
+                else if (W16 && kind == PM_GEMM16) pm_gemm<MB, DF, LS, true>(u, t, lds_w, lds_red, fmr, stage, sync, F);
+                else if (SMP && kind == PM_SAMPLE) pm_sample_row<DF, ROW, FRC>(P.samp, R, F, u, t, lds_red, P.fm_base, sync);
                 else pm_att_row<DF, EOU, ROW>(P.att, R, u.row, t, lds_att, P.fm_base, sync, P.T, P.n_ticks - P.T);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1081,7 +1121,104 @@ __global__ __launch_bounds__(256) void pm_clear_kernel(unsigned* a, int na, unsi
 __global__ __launch_bounds__(64) void pm_eou_reset_kernel(int* first, int n) {
     if ((int)threadIdx.x < n) first[threadIdx.x] = -1;
 }
+
+// What every launch does first, with or without forced frames: the argument checks, the cleared words, the EMPTY fills.
+int pm_prelaunch(const PmProgram& P, hipStream_t stream, const PmRows* rows) {
+    if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
+        P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL)
+        return PH_ERR_BADARG;
+    if (P.samp.K != 0 && (P.w16 || P.samp.K < 1 || P.samp.K > 64 || P.samp.O < 1 || P.samp.O > 64 || P.samp.ldx < 64 || (P.samp.ldx % 4) ||
+                          (P.samp.head.ld % 4) || P.samp.head.ld < 2 * P.samp.O * P.samp.K + P.samp.K || !P.samp.head.p || !P.samp.unif ||
+                          !P.samp.noise || !P.samp.x || !P.samp.pi))
+        return PH_ERR_BADARG;
+    if (P.att.U > PM_ATT_MAXU || P.att.A > PM_ATT_MAXA) return PH_ERR_UNSUPPORTED;
+    if (rows && (!rows->timing || !rows->sharpening || (P.samp.K != 0 && !rows->bias))) return PH_ERR_BADARG;
+    if (P.att.eou_extra != 0 && (P.att.eou_extra < PM_EOU_MIN_EXTRA || !P.att.eou_pos || !P.att.eou_ncmp || !P.att.eou_first ||
+                                 P.att.B < 1 || P.att.B > 64))
+        return PH_ERR_BADARG;
+    // barrier / census / abort words and the timers are cleared; the sticky words at the end of the sync area are not
+    // (cleared by a kernel of our own, not by hipMemsetAsync: as graph memset nodes replayed on the default stream the
+    // two memsets were seen to leave a non-zero pattern in the words when earlier work was still in flight -- every
+    // barrier of the launch then found the abort word set; tests/test_gpu_persist.py, L = 3 / B = 64)
+    hipLaunchKernelGGL(pm_clear_kernel, dim3(8), dim3(256), 0, stream, P.sync, (int)PM_S_STICKY, P.sync + PM_SYNC_WORDS,
+                       (int)PM_DBG_WORDS);
+    PH_CHECK(hipGetLastError());
+    if (P.att.eou_extra > 0) {  // (the stop word, the counts and the tick record are words of the area just cleared)
+        hipLaunchKernelGGL(pm_eou_reset_kernel, dim3(1), dim3(64), 0, stream, P.att.eou_first, P.att.B);
+        PH_CHECK(hipGetLastError());
+    }
+    if (P.dataflow)
+        for (int q = 0; q < P.nfill; ++q) {
+            const long long n = P.fill[q].bytes / 4;
+            const int blocks = (int)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256 + 1);
+            hipLaunchKernelGGL(pm_fill_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<unsigned*>(P.fill[q].p), n,
+                               (unsigned)PM_EMPTY);
+            PH_CHECK(hipGetLastError());
+        }
+    return 0;
+}
 }  // namespace
+
+#ifdef PM_FORCED_TU
+// ------------------------------------------------------------------------------------------------ forced frames
+// This file compiled a second time (persist_forced.hip): the kernels with FRC = true and their launcher, nothing else.  They
+// always carry the row controls (ROW = true) and never bf16 units, so there are 48: MB x DF x LS x EOU x SMP.  A
+// translation unit of their own: the two compile side by side, and the kernels of the first keep the company they had.
+int pm_launch_forced(const PmProgram& P, hipStream_t stream, const PmRows& rows, const PmForce& force) {
+    if (P.w16 || !force.forced || !force.n || !force.own_x || force.B != P.M || force.O < 1 || force.O > 64 || force.ldx < 64 ||
+        (force.ldx % 4))
+        return PH_ERR_BADARG;
+    const int rc0 = pm_prelaunch(P, stream, &rows);
+    if (rc0 != 0) return rc0;
+    const size_t lds = (size_t)PM_LDS_FLOATS * sizeof(float);
+    static bool attr_done = false;
+    if (!attr_done) {
+        const int l = (int)lds;
+#define PM_ATTRF(MB_, DF_, LS_, EOU_, SMP_) \
+    PH_CHECK(hipFuncSetAttribute((const void*)pm_kernel<MB_, DF_, LS_, false, EOU_, SMP_, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, l))
+#define PM_ATTRF6(LS_, EOU_, SMP_) \
+    PM_ATTRF(1, false, LS_, EOU_, SMP_); PM_ATTRF(2, false, LS_, EOU_, SMP_); PM_ATTRF(4, false, LS_, EOU_, SMP_); \
+    PM_ATTRF(1, true, LS_, EOU_, SMP_); PM_ATTRF(2, true, LS_, EOU_, SMP_); PM_ATTRF(4, true, LS_, EOU_, SMP_)
+        PM_ATTRF6(false, false, false); PM_ATTRF6(true, false, false); PM_ATTRF6(false, true, false); PM_ATTRF6(true, true, false);
+        PM_ATTRF6(false, false, true); PM_ATTRF6(true, false, true); PM_ATTRF6(false, true, true); PM_ATTRF6(true, true, true);
+#undef PM_ATTRF6
+#undef PM_ATTRF
+        attr_done = true;
+    }
+    const dim3 grid(P.nwg), block(PM_THREADS);
+    PmRowsF R;
+    R.timing = rows.timing; R.sharpening = rows.sharpening; R.bias = rows.bias;
+    R.f = force;
+#define PM_GOF3(MB_, DF_, LS_, EOU_) \
+    do { \
+        if (P.samp.K > 0) hipLaunchKernelGGL((pm_kernel<MB_, DF_, LS_, false, EOU_, true, true, true>), grid, block, lds, stream, P, R); \
+        else hipLaunchKernelGGL((pm_kernel<MB_, DF_, LS_, false, EOU_, false, true, true>), grid, block, lds, stream, P, R); \
+    } while (0)
+#define PM_GOF2(MB_, DF_, LS_) \
+    do { \
+        if (P.att.eou_extra > 0) PM_GOF3(MB_, DF_, LS_, true); \
+        else PM_GOF3(MB_, DF_, LS_, false); \
+    } while (0)
+#define PM_GOF(MB_, DF_) \
+    do { \
+        if (P.lstm) PM_GOF2(MB_, DF_, true); \
+        else PM_GOF2(MB_, DF_, false); \
+    } while (0)
+    switch (P.MB * 2 + (P.dataflow ? 1 : 0)) {
+        case 2: PM_GOF(1, false); break;
+        case 3: PM_GOF(1, true); break;
+        case 4: PM_GOF(2, false); break;
+        case 5: PM_GOF(2, true); break;
+        case 8: PM_GOF(4, false); break;
+        case 9: PM_GOF(4, true); break;
+        default: return PH_ERR_BADARG;
+    }
+#undef PM_GOF
+#undef PM_GOF2
+#undef PM_GOF3
+    return (int)hipGetLastError();
+}
+#else
 
 int pm_max_workgroups() {
     static int n = -1;
@@ -1128,37 +1265,8 @@ int pm_steps_run(const PmProgram& P, int* steps) {
 }
 
 int pm_launch(const PmProgram& P, hipStream_t stream, const PmRows* rows) {
-    if (P.nwg < 1 || P.nwg > pm_max_workgroups() || !P.units || !P.sync || P.n_slots < 1 || P.n_slots > PM_MAXSLOTS ||
-        P.maxu < 1 || P.n_slots * P.maxu > PM_MAXENT || P.nfill < 0 || P.nfill > PM_MAXFILL)
-        return PH_ERR_BADARG;
-    if (P.samp.K != 0 && (P.w16 || P.samp.K < 1 || P.samp.K > 64 || P.samp.O < 1 || P.samp.O > 64 || P.samp.ldx < 64 || (P.samp.ldx % 4) ||
-                          (P.samp.head.ld % 4) || P.samp.head.ld < 2 * P.samp.O * P.samp.K + P.samp.K || !P.samp.head.p || !P.samp.unif ||
-                          !P.samp.noise || !P.samp.x || !P.samp.pi))
-        return PH_ERR_BADARG;
-    if (P.att.U > PM_ATT_MAXU || P.att.A > PM_ATT_MAXA) return PH_ERR_UNSUPPORTED;
-    if (rows && (!rows->timing || !rows->sharpening || (P.samp.K != 0 && !rows->bias))) return PH_ERR_BADARG;
-    if (P.att.eou_extra != 0 && (P.att.eou_extra < PM_EOU_MIN_EXTRA || !P.att.eou_pos || !P.att.eou_ncmp || !P.att.eou_first ||
-                                 P.att.B < 1 || P.att.B > 64))
-        return PH_ERR_BADARG;
-    // barrier / census / abort words and the timers are cleared; the sticky words at the end of the sync area are not
-    // (cleared by a kernel of our own, not by hipMemsetAsync: as graph memset nodes replayed on the default stream the
-    // two memsets were seen to leave a non-zero pattern in the words when earlier work was still in flight -- every
-    // barrier of the launch then found the abort word set; tests/test_gpu_persist.py, L = 3 / B = 64)
-    hipLaunchKernelGGL(pm_clear_kernel, dim3(8), dim3(256), 0, stream, P.sync, (int)PM_S_STICKY, P.sync + PM_SYNC_WORDS,
-                       (int)PM_DBG_WORDS);
-    PH_CHECK(hipGetLastError());
-    if (P.att.eou_extra > 0) {  // (the stop word, the counts and the tick record are words of the area just cleared)
-        hipLaunchKernelGGL(pm_eou_reset_kernel, dim3(1), dim3(64), 0, stream, P.att.eou_first, P.att.B);
-        PH_CHECK(hipGetLastError());
-    }
-    if (P.dataflow)
-        for (int q = 0; q < P.nfill; ++q) {
-            const long long n = P.fill[q].bytes / 4;
-            const int blocks = (int)((n / 4 + 255) / 256 > 4096 ? 4096 : (n / 4 + 255) / 256 + 1);
-            hipLaunchKernelGGL(pm_fill_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<unsigned*>(P.fill[q].p), n,
-                               (unsigned)PM_EMPTY);
-            PH_CHECK(hipGetLastError());
-        }
+    const int rc0 = pm_prelaunch(P, stream, rows);
+    if (rc0 != 0) return rc0;
     const size_t lds = (size_t)PM_LDS_FLOATS * sizeof(float);
     // per launch flavour (ROW: with per-row decode controls) the attribute is set once, before that flavour's first launch
     static bool attr_done[2] = {false, false};
@@ -1241,3 +1349,4 @@ int pm_launch(const PmProgram& P, hipStream_t stream, const PmRows* rows) {
 #undef PM_GO2
     return (int)hipGetLastError();
 }
+#endif  // PM_FORCED_TU

@@ -135,8 +135,18 @@ int check_pieces(const std::vector<PmMeta>& metas, const std::vector<PmAccess>& 
 }
 
 // ----------------------------------------------------------------------------- decoder (sampling)
+// A decode descriptor as the planners see it: ParrotSampleDesc and, behind it, the forced frames of a ParrotSampleForcedDesc
+// (all null: none).  parrot_sample_create and its kin plan the first, their _forced twins the second, through the same code.
+struct SampleDescX : ParrotSampleDesc {
+    const float* forced = nullptr;
+    const int* n_forced = nullptr;
+    float* own_x = nullptr;
+    SampleDescX() : ParrotSampleDesc() {}
+    SampleDescX(const ParrotSampleDesc& b) : ParrotSampleDesc(b) {}
+    SampleDescX(const ParrotSampleForcedDesc& f) : ParrotSampleDesc(f.base), forced(f.forced), n_forced(f.n_forced), own_x(f.own_x) {}
+};
 struct SamplePlan : PlanBase {
-    ParrotSampleDesc d;
+    SampleDescX d;
     int esplit = 1;
 
     int enqueue(int, hipStream_t s) override {
@@ -162,14 +172,8 @@ struct SamplePlan : PlanBase {
             has_rows = false;
             return 0;
         }
-        if (!rows_own) {
-            PH_CHECK(hipMalloc(reinterpret_cast<void**>(&rows_own), (size_t)3 * d.B * sizeof(float)));
-            std::vector<float> host((size_t)3 * d.B);
-            for (int b = 0; b < d.B; ++b) {
-                host[b] = d.timing; host[(size_t)d.B + b] = d.sharpening; host[(size_t)2 * d.B + b] = d.sampling_bias;
-            }
-            PH_CHECK(hipMemcpy(rows_own, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
+        const int rc = own_rows();
+        if (rc != 0) return rc;
         rows.timing = timing ? timing : rows_own;
         rows.sharpening = sharpening ? sharpening : rows_own + d.B;
         rows.bias = bias ? bias : rows_own + (size_t)2 * d.B;
@@ -194,7 +198,27 @@ struct SamplePlan : PlanBase {
     int pieces_info[16] = {0};
     unsigned long long plan_digest = 0;  // PmBuilder::digest of the program; 0: none
 
-    static bool persist_eligible_shape(const ParrotSampleDesc& d) {  // (no device query: the CPU tests plan too)
+    // ---- forced frames (ParrotSampleForcedDesc::forced / n_forced / own_x; PmForce, persist.h) --------------------------------
+    // A property of the plan: the unit that produces the fed-back frame selects between its own value and the forced one
+    // (linear_tiles marks it; the sampling rows of a GMM head need no mark), so the frame must be ON the step's chain --
+    // fbc_wanted refuses, and a GRU stack with an MSE head gets the 2L + 2 phases of PARROT_PM_FBC=0.  The attention fold does
+    // not depend on the composed path (attfold_wanted; the candidate units of either cut carry it) and stays.  The kernels
+    // with forcing always carry the row controls: a plan the caller gave none reads arrays of the descriptor's scalars.
+    static bool forced(const SampleDescX& d) { return d.forced || d.n_forced || d.own_x; }
+    PmForce force() const { return PmForce{d.forced, d.n_forced, d.own_x, d.B, d.O, d.ldx, 0}; }
+    int own_rows() {
+        if (rows_own) return 0;
+        PH_CHECK(hipMalloc(reinterpret_cast<void**>(&rows_own), (size_t)3 * d.B * sizeof(float)));
+        std::vector<float> host((size_t)3 * d.B);
+        for (int b = 0; b < d.B; ++b) {
+            host[b] = d.timing; host[(size_t)d.B + b] = d.sharpening; host[(size_t)2 * d.B + b] = d.sampling_bias;
+        }
+        PH_CHECK(hipMemcpy(rows_own, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
+
+    static bool persist_eligible_shape(const SampleDescX& d) {  // (no device query: the CPU tests plan too)
+        if (d.bf16 && forced(d)) return false;  // (the kernels with forcing have no bf16 K loop: refused, parrot_sample_create)
         if (d.layer_norm || (d.gmm_K > 0 && !gmm_eligible(d)) || d.B > 64 || (d.H % 16) || (d.E % 16) || (d.R % 16) ||
             d.U > PM_ATT_MAXU || d.A > PM_ATT_MAXA || d.S < 1 || d.O > 64 || d.ldx < 64 || (d.ldx % 4))
             return false;
@@ -208,22 +232,22 @@ struct SamplePlan : PlanBase {
     // as NH16 / 16 plain LINEAR units into a write-once head history [S, B, NH16]; one PM_SAMPLE unit per batch row (persist.h)
     // then picks the component and writes x[t + 1].  The two whole-K programs take it (build_persist_whole,
     // build_persist_lstm); the step cut along K does not (sampling is not linear in h: no Wgx_t / Wcx_t, no attention fold).
-    static bool gmm_eligible(const ParrotSampleDesc& d) {
+    static bool gmm_eligible(const SampleDescX& d) {
         if (env_int("PARROT_PM_GMM", 0) == 0) return false;
         if (d.bf16 || d.gmm_K > 64 || !d.Wrh_t || !d.rh_const || (d.rh_cols % 16) || d.rh_cols < 2 * d.O * d.gmm_K + d.gmm_K) return false;
         return d.unif && d.noise && d.pi_out;
     }
-    static int lstm_maxu(const ParrotSampleDesc& d, int nwg) { return std::max(d.H / 4, d.B) <= nwg ? 1 : 2; }
+    static int lstm_maxu(const SampleDescX& d, int nwg) { return std::max(d.H / 4, d.B) <= nwg ? 1 : 2; }
     // the head's column tiles need a place each in their phase (256 workgroups take K = 20: 159 tiles; 64 take K <= 8)
-    static bool head_fits(const ParrotSampleDesc& d, int nwg) {
+    static bool head_fits(const SampleDescX& d, int nwg) {
         return d.gmm_K <= 0 || d.rh_cols / 16 <= nwg * (d.cell == 1 ? lstm_maxu(d, nwg) : 1);
     }
-    static long long head_floats(const ParrotSampleDesc& d) { return d.gmm_K > 0 ? (long long)d.S * d.B * d.rh_cols + 16 : 0; }
+    static long long head_floats(const SampleDescX& d) { return d.gmm_K > 0 ? (long long)d.S * d.B * d.rh_cols + 16 : 0; }
     // bf16 operands (ParrotSampleDesc::bf16): 32-deep K steps, the bf16 copies in place of Wg_t (GRU: and Wc_t).  LSTM
     // stacks; GRU stacks are opt-in through PARROT_PM_GRU_BF16=1 -- read HERE and nowhere else in the library -- with an MSE
     // head (a GMM head never qualifies under bf16: gmm_eligible; layer_norm never reaches this).  A descriptor that asks for
     // bf16 operands and does not qualify gets NO machine plan -- parrot_sample_create then refuses it.
-    static bool bf16_eligible(const ParrotSampleDesc& d) {
+    static bool bf16_eligible(const SampleDescX& d) {
         if ((d.cell != 0 && d.cell != 1) || (d.H % 32) || (d.E % 32)) return false;
         if (d.cell == 0 && (env_int("PARROT_PM_GRU_BF16", 0) == 0 || d.gmm_K > 0 || d.layer_norm)) return false;
         for (int l = 0; l < d.L; ++l)
@@ -239,23 +263,23 @@ struct SamplePlan : PlanBase {
         return w32(kind == 0 ? d.Wg_t[l] : d.Wc_t[l]);
     }
     // LSTM stacks (cell == 1): one phase per layer, readout and output composed (Wro_t / ro_const) -- build_persist_lstm
-    static bool lstm_eligible(const ParrotSampleDesc& d) {
+    static bool lstm_eligible(const SampleDescX& d) {
         if (d.gmm_K > 0) return d.cell == 1 && d.L + 3 <= PM_MAXSLOTS;  // (persist_eligible_shape: Wrh_t / rh_const are there)
         return d.cell == 1 && d.Wro_t && d.ro_const && d.L + 2 <= PM_MAXSLOTS;
     }
-    static bool whole_eligible(const ParrotSampleDesc& d) {  // GRU, whole-K phases -- build_persist_whole
+    static bool whole_eligible(const SampleDescX& d) {  // GRU, whole-K phases -- build_persist_whole
         if (d.gmm_K > 0) return 2 * d.L + 3 <= PM_MAXSLOTS;  // (head and sampling phases in place of readout and output)
         if (2 * d.L + 3 > PM_MAXSLOTS || !d.Wr_t || !d.Wo_t || !d.bo_pad) return false;
         return (d.oadd != nullptr) == (d.oadd_pad != nullptr);
     }
-    static bool persist_eligible(const ParrotSampleDesc& d) {
+    static bool persist_eligible(const SampleDescX& d) {
         if (!persist_eligible_shape(d)) return false;
         if (d.cell == 1 ? !lstm_eligible(d) : !(whole_eligible(d) || pieces_wanted(d))) return false;
         return pm_max_workgroups() >= 64 && head_fits(d, pm_max_workgroups());
     }
-    static int fb_rows(const ParrotSampleDesc& d, int l) { return d.Wfg[l] ? 64 : 0; }
-    static long long kslab(const ParrotSampleDesc& d, int l) { return d.H + d.E + (long long)l * d.H + fb_rows(d, l); }
-    static long long persist_floats(const ParrotSampleDesc& d, int nwg) {
+    static int fb_rows(const SampleDescX& d, int l) { return d.Wfg[l] ? 64 : 0; }
+    static long long kslab(const SampleDescX& d, int l) { return d.H + d.E + (long long)l * d.H + fb_rows(d, l); }
+    static long long persist_floats(const SampleDescX& d, int nwg) {
         const long long rows = pm_rows(d.B), S = d.S;
         if (d.cell == 1) {  // one slab per layer, the composed output's slab, h and c histories (build_persist_lstm)
             long long n = pm_header_floats((long long)(d.L + 2 + (d.gmm_K > 0 ? 1 : 0)) * nwg * 2);
@@ -303,7 +327,7 @@ struct SamplePlan : PlanBase {
     // End-of-utterance stop (ParrotSampleDesc::eou_extra > 0): a property of the launch, not of a program -- every program
     // above gets it the same way, through PmAtt (persist.h).  A descriptor that asks for it and does not qualify gets NO
     // machine plan, and parrot_sample_create then refuses it: the per-step launches cannot stop.
-    static bool stop_eligible(const ParrotSampleDesc& d) {
+    static bool stop_eligible(const SampleDescX& d) {
         return d.eou_extra >= PM_EOU_MIN_EXTRA && d.eou_pos && d.eou_ncmp && d.eou_first;
     }
     bool stops_early() const { return live && pm_prog.att.eou_extra > 0; }
@@ -441,6 +465,7 @@ struct SamplePlan : PlanBase {
             u.bias = bias ? bias + 16 * ct : nullptr;
             if (add) pb.add_operand(u, pm_rm(add + 16 * ct, 0, N));
             u.epi = PM_EPI_LINEAR;
+            if (forced(d) && wr.res == RES_X) u.rtile = 1 + ct;  // the frame's unit of a forced plan does the select (PmForce)
             u.out = pm_rm(out.p + 16 * ct, out.st, out.ld);
             add_tos(pb, u, tos, ct);
             pb.push(q);
@@ -573,6 +598,10 @@ struct SamplePlan : PlanBase {
             PL_TRY((int)hipMemcpyAsync(sl.h[l], d.h[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
             if (sl.c[l]) PL_TRY((int)hipMemcpyAsync(sl.c[l], d.cwork[l], BH * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
+        if (forced(d)) {  // (parrot_sample_create made rows_own for a forced plan)
+            const PmRows own = {rows_own, rows_own + d.B, rows_own + (size_t)2 * d.B};
+            return pm_launch_forced(pm_prog, st, has_rows ? rows : own, force());
+        }
         return pm_launch(pm_prog, st, has_rows ? &rows : nullptr);
     }
 
@@ -667,7 +696,7 @@ struct SamplePlan : PlanBase {
     // in the previous tick (lag 0), so the launch has S + 1 ticks.  check_pieces() replays the table symbolically (every
     // read satisfied by a write of a strictly earlier phase, every buffer element written once) before it is used.
     // Round 5: the attention projection folded into layer 0's candidate units (PmUnit::pw / pp, persist.hip)
-    static bool attfold_wanted(const ParrotSampleDesc& d) {
+    static bool attfold_wanted(const SampleDescX& d) {
         // (bf16 operands: not taken -- the oracle's projection is an exact product of h_1, and the f32-only fold of
         // pm_gemm is not part of a PM_GEMM16 unit)
         return !d.bf16 && d.Watt_t && d.B <= 16 && 3 * d.A <= 32 && env_int("PARROT_PM_ATTFOLD", 1) != 0;
@@ -677,21 +706,22 @@ struct SamplePlan : PlanBase {
     // h_{L-1} . (A . Wfg)  -- the caller composes A . Wfg / A . Wfc and appends them to layer 0's matrices (Wgx_t / Wcx_t).
     // The output product then feeds nothing inside the loop: it runs beside the next step's gate phase, and a step is
     // 2L + 1 dependent phases (G_0 with K = H critical instead of K = 64, but one phase of ~5 us less).
-    static bool fbc_wanted(const ParrotSampleDesc& d) {
+    static bool fbc_wanted(const SampleDescX& d) {
         if (env_int("PARROT_PM_FBC", 1) == 0) return false;
+        if (forced(d)) return false;  // x[t+1] = x_pre + h_{L-1} . A does not hold on a forced step: the frame stays on the chain
         if (d.bf16) return false;  // composed rows A . Wf would round at other points than the oracle's x . Wf
         if (d.L < 2 || !d.Wgx_t[0] || !d.Wcx_t[0] || !fb_rows(d, 0)) return false;
         for (int l = 1; l < d.L; ++l)
             if (fb_rows(d, l)) return false;
         return 2 * d.L + 1 <= PM_MAXSLOTS;
     }
-    static long long kslab_p(const ParrotSampleDesc& d, int l, bool fbc) { return kslab(d, l) + ((fbc && l == 0) ? d.H : 0); }
-    static int n_phases(const ParrotSampleDesc& d, bool fbc) { return fbc ? 2 * d.L + 1 : 2 * d.L + 2; }
-    static int slot_pre(const ParrotSampleDesc& d) { return std::max(slotC(d.L - 2), 2) + 1; }  // (fbc) after x_pre's last operand
-    static bool pieces_wanted(const ParrotSampleDesc& d) {
+    static long long kslab_p(const SampleDescX& d, int l, bool fbc) { return kslab(d, l) + ((fbc && l == 0) ? d.H : 0); }
+    static int n_phases(const SampleDescX& d, bool fbc) { return fbc ? 2 * d.L + 1 : 2 * d.L + 2; }
+    static int slot_pre(const SampleDescX& d) { return std::max(slotC(d.L - 2), 2) + 1; }  // (fbc) after x_pre's last operand
+    static bool pieces_wanted(const SampleDescX& d) {
         return d.gmm_K <= 0 && d.Wro_t && d.ro_const && env_int("PARROT_PM_PIECES", 1) != 0 && 2 * d.L + 2 <= PM_MAXSLOTS;
     }
-    static bool piece_groups(const ParrotSampleDesc& d, std::vector<PmGroup>& gs, bool fbc) {
+    static bool piece_groups(const SampleDescX& d, std::vector<PmGroup>& gs, bool fbc) {
         const int H = d.H, E = d.E, L = d.L, n = n_phases(d, fbc), sATT = 2, sOUT = fbc ? 0 : 2 * L + 1;
         const int hc = H / 16, ec = E / 16;
         auto pos = [&](int delta, int slot) { return (1 + delta) * n + slot; };
@@ -757,7 +787,7 @@ struct SamplePlan : PlanBase {
     }
     // the phase of every non-critical piece: most constrained first; a phase may not take more units than workgroups, and
     // a piece should not outlast the critical units of its phase (unit cost as in pm_place)
-    static bool piece_slots(const ParrotSampleDesc& d, std::vector<PmGroup>& gs, int nwg, bool fbc) {
+    static bool piece_slots(const SampleDescX& d, std::vector<PmGroup>& gs, int nwg, bool fbc) {
         const int n = n_phases(d, fbc);
         auto cost = [](int K) { return 3.5 + 3.5 * K / 1024.0; };
         std::vector<int> cnt(n, 0);
@@ -823,7 +853,7 @@ struct SamplePlan : PlanBase {
         g.pc.erase(g.pc.begin() + bi + 1);
         return true;
     }
-    static long long piece_floats(const ParrotSampleDesc& d) {  // the partial-sum buffers of the pieces (an upper bound:
+    static long long piece_floats(const SampleDescX& d) {  // the partial-sum buffers of the pieces (an upper bound:
         std::vector<PmGroup> gs;                                 // before any capacity-driven joins)
         const bool fbc = fbc_wanted(d);
         if (!pieces_wanted(d) || !piece_groups(d, gs, fbc)) return 0;
@@ -1019,6 +1049,13 @@ struct SamplePlan : PlanBase {
         return norm_sum_launch(&G, 1, d.B, PARROT_NORM_EPS, st);
     }
 
+    // forced frames on the launches: the select behind the step's last kernel, in front of everything that reads x[t + 1]
+    int force_frame(int t, hipStream_t st) const {
+        if (!forced(d)) return 0;
+        const size_t o = (size_t)t * d.B * d.ldx;
+        return frame_force_launch(d.x + o + (size_t)d.B * d.ldx, d.own_x + o, d.forced + o, d.n_forced, t, d.B, d.O, d.ldx, st);
+    }
+
     int run_all(hipStream_t st) {
         const size_t BH = (size_t)d.B * d.H, BE = (size_t)d.B * d.E, BA = (size_t)d.B * d.A;
         const int H = d.H;
@@ -1099,11 +1136,13 @@ struct SamplePlan : PlanBase {
                                          d.x + (size_t)(t + 1) * d.B * d.ldx, d.ldx,
                                          d.pi_out ? d.pi_out + (size_t)t * d.B * d.gmm_K : nullptr, st,
                                          has_rows ? rows.bias : nullptr));
+                PL_TRY(force_frame(t, st));
                 continue;
             }
             sk_linear_job(j, sk_seg(d.readout, d.R, d.Wo, d.O, d.R, 0), d.B, d.O, H, d.x + (size_t)(t + 1) * d.B * d.ldx, d.ldx);
             j.bias = d.bo; j.add = d.oadd; j.ld_add = d.O;
             PL_TRY(launch_jobs(&j, 1, st));
+            PL_TRY(force_frame(t, st));
         }
         return 0;
     }
@@ -1117,6 +1156,11 @@ extern "C" {
 long long parrot_sample_persist_floats(const ParrotSampleDesc* desc) { PH_ENTRY();
     if (!desc || !SamplePlan::persist_eligible(*desc)) return 0;
     return SamplePlan::persist_floats(*desc, pm_max_workgroups());
+}
+long long parrot_sample_persist_floats_forced(const ParrotSampleForcedDesc* desc) { PH_ENTRY();
+    if (!desc) return 0;
+    const SampleDescX d(*desc);
+    return SamplePlan::persist_eligible(d) ? SamplePlan::persist_floats(d, pm_max_workgroups()) : 0;
 }
 int parrot_sample_is_persistent(void* plan) {
     const SamplePlan* p = static_cast<SamplePlan*>(plan);
@@ -1139,9 +1183,12 @@ int parrot_sample_steps_run(void* plan, int* steps) { PH_ENTRY();
     return plan ? static_cast<SamplePlan*>(plan)->steps_run(steps) : PARROT_ERR_BADARG;
 }
 
-int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY();
+// (the entries below and their _forced twins: one body each, on the planners' own descriptor)
+static int sample_create(const SampleDescX* desc, void** plan) {
     if (!desc || !plan || desc->S < 1 || desc->B < 1 || bad_dims(desc->L) || desc->ldx < desc->O || desc->eou_extra < 0)
         return PARROT_ERR_BADARG;
+    if (SamplePlan::forced(*desc) && (!desc->forced || !desc->n_forced || !desc->own_x)) return PARROT_ERR_BADARG;
+    if (SamplePlan::forced(*desc) && desc->bf16) return PARROT_ERR_UNSUPPORTED;  // the kernels with forcing have no bf16 K loop
     SamplePlan* p = new (std::nothrow) SamplePlan();
     if (!p) return PARROT_ERR_BADARG;
     p->d = *desc;
@@ -1156,6 +1203,10 @@ int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY()
         }
     }
     p->build_persist();  // decode on the persistent phase machine when the configuration qualifies
+    if (SamplePlan::forced(*desc) && p->live && p->own_rows() != 0) {  // (the kernels with forcing read the row controls)
+        delete p;
+        return PARROT_ERR_BADARG;
+    }
     if (desc->bf16 && !parrot_sample_is_bf16(p)) {  // no machine plan with bf16 operands: refused, never a silent f32 decode
         delete p;
         return PARROT_ERR_UNSUPPORTED;
@@ -1167,7 +1218,7 @@ int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY()
     *plan = p;
     return 0;
 }
-int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* info16) { PH_ENTRY();
+static int sample_plan_pieces_dry(const SampleDescX* desc, int nwg, int* info16) {
     if (!desc || !info16 || nwg < 1 || desc->S < 1 || desc->B < 1 || bad_dims(desc->L)) return PARROT_ERR_BADARG;
     std::unique_ptr<SamplePlan> p(new (std::nothrow) SamplePlan());
     if (!p) return PARROT_ERR_BADARG;
@@ -1176,7 +1227,7 @@ int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* in
     for (int i = 0; i < 16; ++i) info16[i] = p->pieces_info[i];
     return p->program != SamplePlan::NONE ? 0 : PARROT_ERR_UNSUPPORTED;
 }
-int parrot_sample_plan_digest_dry(const ParrotSampleDesc* desc, int nwg, unsigned long long* digest) { PH_ENTRY();
+static int sample_plan_digest_dry(const SampleDescX* desc, int nwg, unsigned long long* digest) {
     if (!desc || !digest || nwg < 1 || desc->S < 1 || desc->B < 1 || bad_dims(desc->L)) return PARROT_ERR_BADARG;
     std::unique_ptr<SamplePlan> p(new (std::nothrow) SamplePlan());
     if (!p) return PARROT_ERR_BADARG;
@@ -1184,6 +1235,36 @@ int parrot_sample_plan_digest_dry(const ParrotSampleDesc* desc, int nwg, unsigne
     p->plan_persist(true, nwg);
     *digest = p->plan_digest;
     return p->program != SamplePlan::NONE ? 0 : PARROT_ERR_UNSUPPORTED;
+}
+int parrot_sample_create(const ParrotSampleDesc* desc, void** plan) { PH_ENTRY();
+    if (!desc) return PARROT_ERR_BADARG;
+    const SampleDescX d(*desc);
+    return sample_create(&d, plan);
+}
+int parrot_sample_create_forced(const ParrotSampleForcedDesc* desc, void** plan) { PH_ENTRY();
+    if (!desc) return PARROT_ERR_BADARG;
+    const SampleDescX d(*desc);
+    return sample_create(&d, plan);
+}
+int parrot_sample_plan_pieces_dry(const ParrotSampleDesc* desc, int nwg, int* info16) { PH_ENTRY();
+    if (!desc) return PARROT_ERR_BADARG;
+    const SampleDescX d(*desc);
+    return sample_plan_pieces_dry(&d, nwg, info16);
+}
+int parrot_sample_plan_pieces_dry_forced(const ParrotSampleForcedDesc* desc, int nwg, int* info16) { PH_ENTRY();
+    if (!desc) return PARROT_ERR_BADARG;
+    const SampleDescX d(*desc);
+    return sample_plan_pieces_dry(&d, nwg, info16);
+}
+int parrot_sample_plan_digest_dry(const ParrotSampleDesc* desc, int nwg, unsigned long long* digest) { PH_ENTRY();
+    if (!desc) return PARROT_ERR_BADARG;
+    const SampleDescX d(*desc);
+    return sample_plan_digest_dry(&d, nwg, digest);
+}
+int parrot_sample_plan_digest_dry_forced(const ParrotSampleForcedDesc* desc, int nwg, unsigned long long* digest) { PH_ENTRY();
+    if (!desc) return PARROT_ERR_BADARG;
+    const SampleDescX d(*desc);
+    return sample_plan_digest_dry(&d, nwg, digest);
 }
 int parrot_sample_run(void* plan, void* stream) { PH_ENTRY(); return static_cast<PlanBase*>(plan)->run(0, (hipStream_t)stream); }
 int parrot_sample_destroy(void* plan) { PH_ENTRY();

@@ -1387,9 +1387,12 @@ class Parrot(Brick):
         self._weight_grad_rows(ws, save, T, B, 0, T)
 
     # ------------------------------------------------------------------ sampling
-    def _sample_workspace(self, S, N, U, stop_extra=0):
-        # (a plan that stops at the end of the utterance is another plan: a workspace key of its own)
+    def _sample_workspace(self, S, N, U, stop_extra=0, forced=False):
+        # (a plan that stops at the end of the utterance is another plan: a workspace key of its own; so is a plan with
+        # forced frames -- a call without them keeps the key, and the plan, it had)
         ws_key = ('stop', S, N, U, stop_extra) if stop_extra else (S, N, U)
+        if forced:
+            ws_key = ('forced',) + ws_key
         ws = self._sample_ws.get(ws_key)
         if ws is not None:
             return ws
@@ -1426,7 +1429,9 @@ class Parrot(Brick):
                       add_mu=torch.zeros(N, O * K, **f) if self.use_speaker else None,
                       add_sig=torch.zeros(N, O * K, **f) if self.use_speaker else None,
                       add_co=torch.zeros(N, K, **f) if self.use_speaker else None)
-        d = _lib.SampleDesc()
+        # (forced frames: the descriptor with the three fields behind it, ParrotSampleForcedDesc; d is its decode descriptor)
+        fd = _lib.SampleForcedDesc() if forced else None
+        d = fd.base if forced else _lib.SampleDesc()
         d.S, d.B, d.H, d.E, d.A, d.U, d.L, d.O, d.R, d.ldx = S, N, H, E, A, U, L, O, R, ldx
         d.att_type = 1 if self.attention_type == 'softmax' else 0
         d.use_graph = int(self.use_graph)
@@ -1490,6 +1495,10 @@ class Parrot(Brick):
             ws.update(eou_pos=torch.zeros(N, **i32), eou_ncmp=torch.zeros(N, **i32), eou_first=torch.full((N,), -1, **i32))
             d.eou_pos, d.eou_ncmp, d.eou_first = (ws[k].data_ptr() for k in ('eou_pos', 'eou_ncmp', 'eou_first'))
             d.eou_extra = int(stop_extra)
+        if forced:  # ParrotSampleForcedDesc::forced / n_forced / own_x: filled per call (_sample_device), held by the plan by value
+            ws.update(forced=torch.zeros(S, N, ldx, **f), n_forced=torch.zeros(N, device=self._dev(), dtype=torch.int32),
+                      own_x=torch.zeros(S, N, ldx, **f))
+            fd.forced, fd.n_forced, fd.own_x = (ws[k].data_ptr() for k in ('forced', 'n_forced', 'own_x'))
         if not self._decode_machine_refusal(N):
             pm = dict(cat={}, tiled={})
             for l in range(L):
@@ -1534,21 +1543,26 @@ class Parrot(Brick):
                     d.Watt_t = pm['Watt_t'].data_ptr()
                 # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
                 # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
-                if (not lstm and not self.decode_bf16 and L >= 2 and self._fb_layers == [1]
+                # (a forced plan keeps the frame on the chain and does not take them)
+                if (not lstm and not self.decode_bf16 and not forced and L >= 2 and self._fb_layers == [1]
                         and env_int('PARROT_PM_FBC', 1) != 0):
                     for key, wd, suf, mat, rec in self._groups:
                         rows = H + E + 64 + H
                         pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)
                         pm['tiled'][('x', key)] = torch.empty(rows, wd, **f)
                         getattr(d, f'W{key}x_t')[0] = pm['tiled'][('x', key)].data_ptr()
-            n = int(_lib.load().parrot_sample_persist_floats(C.byref(d)))
+            n = int(_lib.load().parrot_sample_persist_floats_forced(C.byref(fd)) if forced
+                    else _lib.load().parrot_sample_persist_floats(C.byref(d)))
             if n > 0:
                 pm['ws'] = torch.zeros(n, **f)
                 d.persist_ws, d.persist_ws_floats = pm['ws'].data_ptr(), n
                 ws['pm'] = pm
         plan = C.c_void_p()
         try:
-            _lib.call('parrot_sample_create', C.byref(d), C.byref(plan))
+            if forced:
+                _lib.call('parrot_sample_create_forced', C.byref(fd), C.byref(plan))
+            else:
+                _lib.call('parrot_sample_create', C.byref(d), C.byref(plan))
         except _lib.HipCallError as e:
             if stop_extra:
                 raise ValueError(f"sample_until_end: the library did not build a decode machine that stops early for S={S}, "
@@ -1563,7 +1577,7 @@ class Parrot(Brick):
         if stop_extra and _lib.load().parrot_sample_stops_early(plan) != 1:
             _lib.load().parrot_sample_destroy(plan)
             raise ValueError("sample_until_end: the plan the library built does not stop at the end of the utterance")
-        ws['plan'], ws['desc'] = plan, d
+        ws['plan'], ws['desc'] = plan, (fd if forced else d)
         # per-row controls (parrot_sample_set_row_controls): the arrays live here and the plan is given them before its
         # first run; every call writes all of them -- the caller's values, or else the model's scalars (_write_row_controls)
         ws['row_timing'], ws['row_sharpening'] = torch.empty(N, **f), torch.empty(N, **f)
@@ -1616,6 +1630,43 @@ class Parrot(Brick):
                 raise ValueError("speaker_weights must be finite")
         return ctl, sw
 
+    def _check_forced(self, N, S, forced_frames=None, n_forced=None):
+        """Validates the forced frames of a decode call without touching the device: returns None (no forcing), or
+        (frames, n) -- frames a float32 numpy array [P, N, O] (time-major, P <= S), n an int32 numpy array of N prompt
+        lengths, 0 <= n[b] <= P.  ValueError when only one of the two is given, on a wrong shape, P > S, a non-finite frame,
+        a length that is no integer or lies outside 0 .. P, and on a model that decodes with bf16 operands."""
+        if forced_frames is None and n_forced is None:
+            return None
+        if forced_frames is None or n_forced is None:
+            raise ValueError("forced_frames and n_forced go together: got only "
+                             + ("n_forced" if forced_frames is None else "forced_frames"))
+        why = self._decode_forced_refusal()
+        if why:
+            raise ValueError("forced_frames " + why)
+        O = self.output_dim
+        if torch.is_tensor(forced_frames):
+            forced_frames = forced_frames.detach().cpu().numpy()
+        if torch.is_tensor(n_forced):
+            n_forced = n_forced.detach().cpu().numpy()
+        fr = numpy.asarray(forced_frames, dtype=numpy.float64)
+        if fr.ndim != 3 or fr.shape[1:] != (N, O):
+            raise ValueError(f"forced_frames needs shape (P, {N}, {O}) = (frames, utterances, output_dim), time-major, "
+                             f"got {tuple(fr.shape)}")
+        P = fr.shape[0]
+        if P > S:
+            raise ValueError(f"forced_frames holds {P} frames, the call decodes {S} steps: needs P <= {S}")
+        fr32 = fr.astype(numpy.float32)
+        if not numpy.all(numpy.isfinite(fr32)):
+            raise ValueError("forced_frames must be finite")
+        n = numpy.asarray(n_forced)
+        if n.shape != (N,):
+            raise ValueError(f"n_forced needs {N} values (one per utterance), got shape {tuple(n.shape)}")
+        if not numpy.all(numpy.isfinite(n.astype(numpy.float64))) or not numpy.all(n == numpy.floor(n)):
+            raise ValueError(f"n_forced must be whole numbers, got {n.tolist()}")
+        if not numpy.all((n >= 0) & (n <= P)):
+            raise ValueError(f"n_forced must lie in 0 .. {P} (the frames given), got {n.tolist()}")
+        return fr32, n.astype(numpy.int32)
+
     def _write_row_controls(self, ws, ctl):
         """Every decode call writes all of the workspace's control arrays: a call without controls after one with them
         decodes with the model's scalars again."""
@@ -1667,6 +1718,14 @@ class Parrot(Brick):
                     f"steps of 32), got {H} and {E}")
         return why
 
+    def _decode_forced_refusal(self):
+        """Why this model cannot decode with forced frames ('' when it can): the machine's kernels with forcing have f32
+        operands only."""
+        if self.decode_bf16:
+            return ("does not cover decode_dtype='bf16': forced frames decode with f32 operands only "
+                    "(the bf16 programs have no kernels with forcing)")
+        return ''
+
     def _decode_stop_refusal(self, N, extra):
         """Why this model / batch cannot stop at the end of the utterance ('' when it can): the stop lives inside the
         persistent machine, so whatever decodes as per-step launches cannot have it."""
@@ -1677,27 +1736,29 @@ class Parrot(Brick):
 
     def sample_until_end_device(self, labels, labels_mask, speaker, num_samples, max_steps, extra=40, unif=None, noise=None,
                                 seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None,
-                                speaker_weights=None):
+                                speaker_weights=None, forced_frames=None, n_forced=None):
         """sample_model_device that stops at the end of the utterance INSIDE the decode kernel instead of decoding
         max_steps frames and cutting afterwards.  The rule is end_of_utterance's (reference sample.py:145-163): a row ends
         `extra` frames after the first step whose window weight on the position just past its text beats the weight on every
         real character.  Returns (outs, lengths): the six tensors of sample_model_device cut to steps_run = max(lengths)
         along time -- bit-identical to the first steps_run steps of sample_model_device(.., max_steps) -- and lengths [N]
         (int64, on the device) = what end_of_utterance gives for each row of the full-length phi.
-        timing_coeffs / sharpening_coeffs / sampling_biases / speaker_weights: as sample_model_device."""
+        timing_coeffs / sharpening_coeffs / sampling_biases / speaker_weights / forced_frames / n_forced: as
+        sample_model_device (with forcing outs has the seventh tensor, own_x, cut like the others; the rule reads phi only)."""
         from .utils import end_of_utterance_args
         ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
+        forced = self._check_forced(num_samples, max_steps, forced_frames, n_forced)
         why = self._decode_stop_refusal(num_samples, extra)  # (before anything is keyed on `extra` or allocated)
         if why:
             raise ValueError("sample_until_end " + why)
         self.allocate()
         lm = torch.as_tensor(labels_mask)
         U = lm.shape[1]
-        ws = self._sample_workspace(max_steps, num_samples, U, stop_extra=int(extra))
+        ws = self._sample_workspace(max_steps, num_samples, U, stop_extra=int(extra), forced=forced is not None)
         pos, ncmp = end_of_utterance_args(lm.detach().cpu().numpy(), U)
         ws['eou_pos'].copy_(torch.from_numpy(pos))
         ws['eou_ncmp'].copy_(torch.from_numpy(ncmp))
-        outs = self._sample_device(ws, labels, labels_mask, speaker, num_samples, max_steps, unif, noise, seed, ctl)
+        outs = self._sample_device(ws, labels, labels_mask, speaker, num_samples, max_steps, unif, noise, seed, ctl, forced)
         steps = C.c_int(0)
         _lib.call('parrot_sample_steps_run', ws['plan'], C.byref(steps))
         first = ws['eou_first'].long()
@@ -1708,16 +1769,19 @@ class Parrot(Brick):
         return [o[:steps_run] for o in outs], lengths
 
     def sample_until_end(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, max_steps, extra=40,
-                         timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
+                         timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
+                         forced_frames=None, n_forced=None):
         """numpy twin of sample_until_end_device (as sample_model is of sample_model_device): (list of numpy arrays,
         numpy lengths [N])."""
         outs, lengths = self.sample_until_end_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, max_steps, extra,
                                                      timing_coeffs=timing_coeffs, sharpening_coeffs=sharpening_coeffs,
-                                                     sampling_biases=sampling_biases, speaker_weights=speaker_weights)
+                                                     sampling_biases=sampling_biases, speaker_weights=speaker_weights,
+                                                     forced_frames=forced_frames, n_forced=n_forced)
         return [o.detach().cpu().numpy().copy() for o in outs], lengths.cpu().numpy()
 
     def sample_model_device(self, labels, labels_mask, speaker, num_samples, num_steps, unif=None, noise=None,
-                            seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
+                            seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
+                            forced_frames=None, n_forced=None):
         """Device-resident version of sample_model: returns torch tensors
         [sample_x [S,N,O], k [S,N,A], w [S,N,E], pi, phi [S,N,U], pi_att [S,N,A]].
         GMM head: the component choice / Gaussian noise come from `unif` [S,N] and `noise` [S,N,O] if given,
@@ -1727,13 +1791,22 @@ class Parrot(Brick):
         timing_coeff / sharpening_coeff / sampling_bias, on whichever path decodes the model (decode_path);
         speaker_weights [N, num_speakers] -- row b's speaker embedding is speaker_weights[b] @ lookuptable.W (one f32
         product) instead of the looked-up row; `speaker` is then not read.  ValueError (before anything is allocated) on a
-        wrong length, non-finite values, timing / sharpening <= 0, biases on an MSE model, weights without use_speaker."""
+        wrong length, non-finite values, timing / sharpening <= 0, biases on an MSE model, weights without use_speaker.
+        Forced frames (priming; both None: the call as it is without them, on the same workspace): forced_frames [P, N, O]
+        time-major, P <= num_steps, and n_forced, N ints with 0 <= n <= P.  While t < n_forced[b] the frame fed back into
+        step t + 1 of row b is forced_frames[t, b] and not the model's (MSE: the output frame; GMM: the draw); from step
+        n_forced[b] on the row decodes freely from the state the prompt left.  The list then has a seventh tensor, own_x
+        [S, N, O]: what the model emitted or drew at every step; sample_x holds the fed-back (forced) frames in the forced
+        region and equals own_x elsewhere.  Composes with the four arguments above.  ValueError (before anything is
+        allocated) on a wrong shape, P > num_steps, non-finite frames, n outside 0 .. P, and with decode_dtype='bf16'."""
         ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
-        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl)
+        forced = self._check_forced(num_samples, num_steps, forced_frames, n_forced)
+        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl, forced)
 
-    def _sample_device(self, ws, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl=None):
+    def _sample_device(self, ws, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl=None,
+                       forced=None):
         """One decode call on the workspace `ws` (None: the plain workspace of the shape).  ctl: what _check_row_controls
-        returned (None: no per-utterance arguments)."""
+        returned (None: no per-utterance arguments); forced: what _check_forced returned (None: no forced frames)."""
         controls, speaker_weights = ctl if ctl is not None else (None, None)
         self.allocate()
         dev = self._dev()
@@ -1743,7 +1816,12 @@ class Parrot(Brick):
         assert N == num_samples
         S, L, H, O = num_steps, self.num_layers, self.rnn_h_dim, self.output_dim
         if ws is None:
-            ws = self._sample_workspace(S, N, U)
+            ws = self._sample_workspace(S, N, U, forced=forced is not None)
+        if forced is not None:  # every call rewrites both arrays whole: nothing of an earlier prompt survives
+            frames, n = forced
+            ws['forced'].zero_()
+            ws['forced'][:frames.shape[0], :, :O].copy_(torch.from_numpy(frames))
+            ws['n_forced'].copy_(torch.from_numpy(n))
         ws['ctx'].copy_(self._encoder_forward(labels, labels_mask, None))
         self._sum_layer_biases(ws, extra_fb=not self.layer_norm)
         for l in range(1, L + 1):
@@ -1794,7 +1872,8 @@ class Parrot(Brick):
         self._decode_path = 'machine' if _lib.load().parrot_sample_is_persistent(ws['plan']) else 'launches'
         sx = ws['x'][1:, :, :O]
         pi = ws['pi_out'] if self.which_cost == 'GMM' else sx
-        return [sx, ws['kappa'][1:], ws['w'][1:], pi, ws['phi'], ws['a']]
+        outs = [sx, ws['kappa'][1:], ws['w'][1:], pi, ws['phi'], ws['a']]
+        return outs + [ws['own_x'][:, :, :O]] if forced is not None else outs
 
     @property
     def decode_path(self):
@@ -1872,13 +1951,15 @@ class Parrot(Brick):
             tile(cat, pm['tiled'][('x', key)])
 
     def sample_model(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, num_steps,
-                     timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None):
+                     timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
+                     forced_frames=None, n_forced=None):
         """Parrot.sample_model (model.py:1061-1083): numpy in, list of numpy arrays out
-        [sample_x, k, w, pi, phi, pi_att], all time-major (the caller swaps axes, sample.py:142-143).  The four keyword
-        arguments: per utterance, as sample_model_device."""
+        [sample_x, k, w, pi, phi, pi_att], all time-major (the caller swaps axes, sample.py:142-143).  The keyword
+        arguments: per utterance, as sample_model_device (forced_frames / n_forced: a seventh array, own_x)."""
         outs = self.sample_model_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, num_steps,
                                         timing_coeffs=timing_coeffs, sharpening_coeffs=sharpening_coeffs,
-                                        sampling_biases=sampling_biases, speaker_weights=speaker_weights)
+                                        sampling_biases=sampling_biases, speaker_weights=speaker_weights,
+                                        forced_frames=forced_frames, n_forced=n_forced)
         return [o.detach().cpu().numpy().copy() for o in outs]
 
     def sample_using_input(self, data_tr, num_samples):

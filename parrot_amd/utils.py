@@ -167,15 +167,36 @@ def sample_parse(argv=None):
                              'own bias in place of --sampling_bias')
     parser.add_argument('--mix_speakers', type=str, default='15,11',
                         help='A,B: the two speakers --mix blends, m * W[A] + (1 - m) * W[B] (the pair of sample.py:81-85)')
+    parser.add_argument('--prime_frames', type=int, default=0,
+                        help="N > 0: every test utterance is primed with its own first min(N, length) feature frames -- they "
+                             "are fed back in place of the decoder's while they last, then it continues freely "
+                             "(Parrot.sample_model(forced_frames=.., n_forced=..)); not with --phrase, whose text has no frames")
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
         args.save_dir = os.path.join(args.save_dir, args.dataset)
+    if args.prime_frames < 0:
+        raise SystemExit("--prime_frames %d: the number of frames cannot be negative" % args.prime_frames)
+    if args.prime_frames and args.phrase is not None:
+        raise SystemExit("--prime_frames primes each test utterance with its own feature frames; --phrase replaces the text, "
+                         "and the frames would belong to other words: give one of the two")
+    if args.prime_frames and args.sample_one_step:
+        raise SystemExit("--prime_frames has no meaning with --sample_one_step, which forces every frame already")
     for flag in ('timing_coeffs', 'sharpening_coeffs', 'sampling_biases'):
         if getattr(args, flag) is not None:
             setattr(args, flag, parse_float_list(getattr(args, flag), args.num_samples, '--' + flag))
     args.mix_speakers = parse_speaker_pair(args.mix_speakers)
     return args
+
+
+def prime_frames(features, features_mask, count, num_steps):
+    """--prime_frames: (forced_frames [P, N, O], n_forced [N]) from a batch's own time-major features [T, N, O] and mask
+    [T, N]: utterance b is primed with its first min(count, its length) frames, P = min(count, T, num_steps)."""
+    import numpy
+    features, features_mask = numpy.asarray(features), numpy.asarray(features_mask)
+    P = int(min(count, features.shape[0], num_steps))
+    lengths = features_mask.sum(axis=0).astype('int64')
+    return features[:P].astype('float32'), numpy.minimum(lengths, P).astype('int32')
 
 
 def parse_float_list(text, count, flag):

@@ -11,7 +11,7 @@ from parrot_amd.checkpoint import load_parameters
 from parrot_amd.datasets import parrot_stream
 from parrot_amd.generate import generate_wav
 from parrot_amd.model import Parrot
-from parrot_amd.utils import end_of_utterance, mix_speaker_weights, phrase_labels, sample_parse
+from parrot_amd.utils import end_of_utterance, mix_speaker_weights, phrase_labels, prime_frames, sample_parse
 
 
 def main(argv=None):
@@ -57,6 +57,10 @@ def main(argv=None):
             print("--mix %g ignored: the experiment was trained without speakers" % args.mix)
     row_controls = dict(timing_coeffs=args.timing_coeffs, sharpening_coeffs=args.sharpening_coeffs,
                         sampling_biases=args.sampling_biases, speaker_weights=speaker_weights)
+    if args.prime_frames:  # every utterance continues its own first frames (sample_parse refuses the flag with --phrase)
+        forced_frames, n_forced = prime_frames(data_tr['features'], features_mask_tr, args.prime_frames, args.num_steps)
+        row_controls.update(forced_frames=forced_frames, n_forced=n_forced)
+        print("--prime_frames %d: forcing %s frames of the utterances' own features" % (args.prime_frames, n_forced.tolist()))
 
     device = torch.device(args.device)
     parrot = Parrot(
@@ -88,11 +92,12 @@ def main(argv=None):
     if args.sample_one_step:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_using_input(data_tr, args.num_samples)
     elif args.stop_at_end:  # the kernel applies the end-of-utterance rule itself and decodes no frame beyond it
-        (gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att), stop_lengths = parrot.sample_until_end(
+        outs, stop_lengths = parrot.sample_until_end(
             labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps, **row_controls)
+        gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = outs[:6]  # (with --prime_frames a seventh follows: own_x)
     else:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_model(
-            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps, **row_controls)
+            labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps, **row_controls)[:6]
     print("Successfully sampled the parrot.")
 
     gen_x, gen_phi = gen_x.swapaxes(0, 1), gen_phi.swapaxes(0, 1)

@@ -104,6 +104,14 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          with --parent-lib (the parent commit's libparrot_hip.so) the default call of both
                                          libraries in the same alternation, bit identity included; the result also goes to FILE
                                          (default profiles/decode_row_controls.json)
+  bench_extra.py --only decode_forced [--reps N] [--forced-decode-json FILE] [--parent-lib FILE]
+                                         decode with forced frames (Parrot.sample_model_device(forced_frames=, n_forced=)):
+                                         configs[2] and the 2 x LSTM-1024 plan at batch 16, 1000 frames -- the default plan, the
+                                         forced plan with n = 0 everywhere, the forced plan with 200 forced frames of 1000 and
+                                         (GRU) the default plan under PARROT_PM_FBC=0, N alternations in one process, each with
+                                         its spread; with --parent-lib (the parent commit's libparrot_hip.so) the default plan
+                                         of both libraries in the same alternation, bit identity included; the result also goes
+                                         to FILE (default profiles/decode_forced.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -129,7 +137,7 @@ def _arg(name, dflt=None):
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
        "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_min_p", "samplernn_forced", "samplernn_skip",
-       "decode_row_controls", "mulaw")
+       "decode_row_controls", "decode_forced", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1513,6 +1521,115 @@ if "decode_row_controls" in only:
     res["not_measured"] = ["B > 16", "the H = 1536 LSTM plan with two units per workgroup", "the launch path's timing",
                            "a GMM head with per-utterance biases"]
     record("decode_row_controls", "--row-controls-json", res)
+
+# ---- decode with forced frames (ParrotSampleForcedDesc::forced / n_forced / own_x): configs[2] (2 x GRU-1024) and 2 x LSTM-1024 at
+# batch 16, 1000 frames.  Per shape a model whose calls force nothing (the default plan), a model on the forced plan with
+# n = 0 everywhere, a model on the forced plan with 200 forced frames of 1000 (seeded N(0, 1) frames), a model on the default
+# plan under PARROT_PM_FBC=0 (what the forced GRU plan is expected to cost) and, with --parent-lib, a model on the parent
+# commit's library, all alive in one process and run alternately.  The switch is read when a plan is made: it is set around
+# every call of its model and of no other.
+if "decode_forced" in only:
+    import contextlib
+    import ctypes
+    from parrot_amd import _lib as plib
+    from parrot_amd.model import Parrot
+    reps = int(_arg("--reps", "5"))
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            if hasattr(parent_lib, name):
+                fn = getattr(parent_lib, name)
+                fn.restype = res_
+                fn.argtypes = args_
+
+    @contextlib.contextmanager
+    def under(which, env):  # every call of a model goes to the library that made its plan, under the model's switches
+        plib._lib = which
+        saved = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+
+    N, U, S, P = 16, 100, 1000, 200
+    gen = torch.Generator().manual_seed(0)
+    lab = torch.randint(0, 43, (N, U), generator=gen)
+    lm = torch.ones(N, U)
+    prompt = torch.randn(P, N, 63, generator=gen)
+    forced0 = dict(forced_frames=prompt, n_forced=[0] * N)
+    forced200 = dict(forced_frames=prompt, n_forced=[P] * N)
+    shapes = {"cfg3_gru2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='gru'),
+              "lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='lstm')}
+    res = {"batch": N, "frames": S, "forced_frames": P, "alternations": reps,
+           "timed": "call to device idle (host-side preparation included)", "shapes": {}}
+    for sname, kw in shapes.items():
+        def model(which):
+            with under(which, {}):
+                return Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, seed=1234, **kw).initialize()
+        runs = {"default": (model(this_lib), this_lib, {}, {}, False),
+                "forced_n0": (model(this_lib), this_lib, forced0, {}, True),
+                "forced_200_of_1000": (model(this_lib), this_lib, forced200, {}, True)}
+        if kw['cell_type'] == 'gru':
+            runs["default_fbc0"] = (model(this_lib), this_lib, {}, {"PARROT_PM_FBC": "0"}, False)
+        if parent_lib is not None:
+            runs["parent_default"] = (model(parent_lib), parent_lib, {}, {}, False)
+            runs["default_again"] = (model(this_lib), this_lib, {}, {}, False)
+            runs["parent_default_again"] = (model(parent_lib), parent_lib, {}, {}, False)
+        times, frames = {k: [] for k in runs}, {}
+        keys = list(runs)
+        for rep_ in range(reps + 1):  # (the first alternation builds the plans and captures the graphs: not counted)
+            for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:
+                m, which, ckw, env, _ = runs[k]
+                with under(which, env):
+                    torch.cuda.synchronize(); t0 = time.time()
+                    outs = m.sample_model_device(lab, lm, None, N, S, **ckw)
+                    torch.cuda.synchronize(); dt = time.time() - t0
+                    frames[k] = outs[0].cpu().numpy().copy()
+                if rep_:
+                    times[k].append(1e6 * dt / S)
+        machine = {}
+        for k, (m, which, _, env, forced_) in runs.items():
+            with under(which, env):
+                key_ = (('forced',) if forced_ else ()) + (S, N, U)
+                machine[k] = int(which.parrot_sample_is_persistent(m._sample_ws[key_]['plan']))
+                m.close()
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        spread = {k: max(v) - min(v) for k, v in times.items()}
+        one = {"runs": {k: {"machine": machine[k], "us_per_step": [round(x, 2) for x in times[k]], "us_per_step_median": round(med[k], 2),
+                            "spread_max_minus_min": round(spread[k], 2)} for k in runs},
+               "forced_n0_minus_default_us": round(med["forced_n0"] - med["default"], 2),
+               "forced_200_minus_default_us": round(med["forced_200_of_1000"] - med["default"], 2),
+               "forced_n0_frames_equal_default": bool(np.array_equal(frames["forced_n0"], frames["default"])),
+               "forced_200_prompt_is_in_the_frames": bool(np.array_equal(frames["forced_200_of_1000"][:P], prompt.numpy()))}
+        if "default_fbc0" in runs:
+            one["forced_n0_minus_default_fbc0_us"] = round(med["forced_n0"] - med["default_fbc0"], 2)
+            one["forced_n0_frames_equal_default_fbc0"] = bool(np.array_equal(frames["forced_n0"], frames["default_fbc0"]))
+        if parent_lib is not None:
+            both = spread["default"] + spread["parent_default"]
+            gap = med["default"] - med["parent_default"]
+            one["default_path_against_parent_commit"] = {
+                "how": "this build and the parent commit's library loaded in one process, two models of each (the second pair "
+                       "created in the other order), all in the same alternation; the bar compares the first model of each "
+                       "library against the sum of their spreads (max - min over the alternations)",
+                "bit_identical": bool(np.array_equal(frames["default"], frames["parent_default"])),
+                "this_us": [round(med["default"], 2), round(med["default_again"], 2)],
+                "parent_us": [round(med["parent_default"], 2), round(med["parent_default_again"], 2)],
+                "this_minus_parent_us": round(gap, 2),
+                "sum_of_the_two_spreads_us": round(both, 2),
+                "bar_default_within_the_sum_of_both_spreads": "met" if abs(gap) <= both else "not met"}
+        res["shapes"][sname] = one
+    res["not_measured"] = ["B > 16", "the H = 1536 LSTM plan with two units per workgroup", "the launch path's timing",
+                           "a GMM head with forced frames", "forcing together with the end-of-utterance stop"]
+    record("decode_forced", "--forced-decode-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
