@@ -102,6 +102,20 @@ __device__ __forceinline__ void sk_fetch(const SkSeg& sg, int kc, int m0, int M,
 #define SK_PIN_REFILL() do { } while (0)
 #endif
 
+// The tail of a launch, from the first wave's exit of the K loop to the last store (what each of these measured, per phase
+// stamp and per launch: DESIGN 3.1 item 6, profiles/step_tail_sk_phase_timers_*.txt):
+//   SK_TAIL_FIELDS = 1  the descriptor fields the epilogue reads come with the entry batch and are kept in scalar registers
+//                       over the K loop; 0: they are requested again in front of the LDS meeting point, a cold scalar round
+//                       trip that only the waves which wait at the barrier get for nothing.
+// Tried on the same probe and dropped: the epilogue operands requested behind the ring's first fetches instead of in front
+// of them (+0.35 us per launch: the ring's counted waits then also wait for those seventeen loads), and an issue priority
+// for the younger half of the waves that changes over its walk (s_setprio raised from the middle or from 3/4 of the walk
+// on: the meeting point 0.28 us LATER; raised at entry and dropped at 1/4, 1/2, 3/4: the older half slows down by what the
+// younger gains, the meeting point moves by -0.08 .. +0.08 us and the launch is up to 0.24 us slower).
+#ifndef SK_TAIL_FIELDS
+#define SK_TAIL_FIELDS 1
+#endif
+
 template <int MB>
 __device__ __forceinline__ void sk_mma(const f32x4 (&a)[MB], const f32x4& b, f32x4 (&acc)[MB]) {
 #pragma unroll
@@ -254,7 +268,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kk = lane >> 4, i = lane & 15;
     const int m0 = blockIdx.y * (16 * MB);  // the launch picks MB / NB
-    const int M = job.M, N = job.N;
+    int M = job.M, N = job.N;
     SK_STAMP(0);
     // The descriptor fields the prologue needs, pulled into scalar registers in one batch: read where the code first
     // needs them they arrive through five or six dependent s_load / s_waitcnt rounds (a cold kernel-argument line
@@ -264,7 +278,21 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                  "s"(job.bias), "s"(job.add), "s"(job.out), "s"(job.e0), "s"(job.e1), "s"(job.o1), "s"(job.ld_add),
                  "s"(job.ldo), "s"(job.lde0), "s"(job.lde1), "s"(job.ldo1), "s"(job.wait_flag), "s"(job.seg[0].A),
                  "s"(job.seg[0].B), "s"(job.seg[0].lda), "s"(job.seg[0].ldb), "s"(job.seg[0].K), "s"(job.seg[0].b_kcontig),
-                 "s"(job.seg[1].A), "s"(job.seg[1].B), "s"(job.seg[1].lda), "s"(job.seg[1].ldb), "s"(job.seg[1].K));
+                 "s"(job.seg[1].A), "s"(job.seg[1].B), "s"(job.seg[1].lda), "s"(job.seg[1].ldb), "s"(job.seg[1].K),
+                 "s"(job.act), "s"(job.o2), "s"(job.mask), "s"(job.ldo2));
+    // The fields the epilogue reads ride in that batch and STAY in scalar registers over the K loop (SK_TAIL_FIELDS, above):
+    // behind the pin the compiler no longer knows them to be reloadable, so it cannot drop them and fetch them again.
+    int f_epi = job.epi, f_act = job.act, f_acc = job.accumulate, f_H = job.H, f_colmode = job.colmode;
+    int f_ldo = job.ldo, f_ldo1 = job.ldo1, f_ldo2 = job.ldo2;
+    // (global address space spelled out: behind the pin the compiler cannot trace the pointers back to the kernel argument)
+    typedef __attribute__((address_space(1))) float gfloat;
+    const gfloat* f_bias = (const gfloat*)job.bias;
+    const gfloat* f_mask = (const gfloat*)job.mask;
+    gfloat *f_out = (gfloat*)job.out, *f_o1 = (gfloat*)job.o1, *f_o2 = (gfloat*)job.o2;
+#if SK_TAIL_FIELDS
+    asm volatile("" : "+s"(M), "+s"(N), "+s"(f_epi), "+s"(f_act), "+s"(f_acc), "+s"(f_H), "+s"(f_colmode), "+s"(f_ldo),
+                 "+s"(f_ldo1), "+s"(f_ldo2), "+s"(f_bias), "+s"(f_mask), "+s"(f_out), "+s"(f_o1), "+s"(f_o2));
+#endif
     if (m0 >= M) return;
 
     f32x4 acc[MB][NB];
@@ -294,12 +322,13 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
 #pragma unroll
     for (int r = 0; r < RPW; ++r) p_add[r] = p_e0[r] = p_e1[r] = p_oc[r] = 0.f;
     const bool has_add = job.add != nullptr;
+    auto jcol = [&](int tile, int jj) { return sk_col(f_colmode == 1 ? (int)SK_EPI_LSTM : f_epi, f_H, tile, jj); };
     if (wave < EWAVES) {
         const int rb_ = eblk / NB, tile_ = tile0 + eblk % NB;
         const int g_ = lane >> 4, jj_ = lane & 15;
-        const int epi_ = job.epi, H_ = job.H;
-        const int n_ = min(sk_jcol(job, tile_, jj_), N - 1);
-        const float* dummy = epi_ == SK_EPI_BWD_RH ? job.o1 : job.out;  // (always a live buffer of this job)
+        const int epi_ = f_epi, H_ = f_H;
+        const int n_ = min(jcol(tile_, jj_), N - 1);
+        const float* dummy = (const float*)(epi_ == SK_EPI_BWD_RH ? f_o1 : f_out);  // (always a live buffer of this job)
         const float* q_add = has_add ? job.add : dummy;
         const int l_add = has_add ? job.ld_add : 0, c_add = has_add ? n_ : 0;
         const bool on0 = epi_ == SK_EPI_GRU_GATES || epi_ == SK_EPI_GRU_CAND || epi_ == SK_EPI_BWD_RH;
@@ -310,12 +339,12 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
         const float* q_e1 = on1 ? job.e1 : dummy;
         const int l_e1 = on1 ? job.lde1 : 0;
         const int c_e1 = !on1 ? 0 : (epi_ == SK_EPI_LSTM ? ((jj_ >> 2) == 0 ? min(n_, H_ - 1) : 0) : n_);
-        const bool onc = (epi_ == SK_EPI_LINEAR && job.accumulate == 1) || epi_ == SK_EPI_BWD_RH;
-        const float* q_oc = !onc ? dummy : (epi_ == SK_EPI_BWD_RH ? job.o1 : job.out);
-        const int l_oc = !onc ? 0 : (epi_ == SK_EPI_BWD_RH ? job.ldo1 : job.ldo);
+        const bool onc = (epi_ == SK_EPI_LINEAR && f_acc == 1) || epi_ == SK_EPI_BWD_RH;
+        const float* q_oc = !onc ? dummy : (const float*)(epi_ == SK_EPI_BWD_RH ? f_o1 : f_out);
+        const int l_oc = !onc ? 0 : (epi_ == SK_EPI_BWD_RH ? f_ldo1 : f_ldo);
         const int c_oc = onc ? n_ : 0;
-        const float* q_b = job.bias ? job.bias : dummy;
-        p_bias = q_b[job.bias ? n_ : 0];
+        const float* q_b = f_bias ? (const float*)f_bias : dummy;
+        p_bias = q_b[f_bias ? n_ : 0];
 #pragma unroll
         for (int r = 0; r < RPW; ++r) {
             const int m = min(m0 + rb_ * 16 + 4 * g_ + er0 + r, M - 1);
@@ -353,7 +382,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
         for (int rb = 0; rb < MB; ++rb) mrow[rb] = min(m0 + rb * 16 + ((lane >> 2) & 15), M - 1);
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
-            ncl[nb] = min(sk_jcol(job, tile0 + nb, i), N - 1);
+            ncl[nb] = min(jcol(tile0 + nb, i), N - 1);
             btile[nb] = min(tile0 + nb, ((N + 15) >> 4) - 1);
         }
         const int mine = (total - wave + SK_KW - 1) / SK_KW;  // chunks of this wave (dealt round-robin)
@@ -509,12 +538,16 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
     for (int rb = 0; rb < MB; ++rb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) red[((wave * MB + rb) * NB + nb) * 64 + lane] = acc[rb][nb];
+#if !SK_TAIL_FIELDS
     // The descriptor fields the epilogue reads, requested in one batch BEFORE the meeting point: the entry batch's registers
     // do not survive the K loop, and read where the epilogue first needs them they came back one conditional block at a
     // time -- four dependent s_load / s_waitcnt rounds between the barrier and the first store.  Here their latency lies
-    // under the barrier wait and they are live behind it.  (Still no local copy of the descriptor: DESIGN 3.1 item 2.)
+    // under the barrier wait of the waves that arrive early; the last to arrive, whose time is the launch's, wait for it.
     asm volatile("" ::"s"(job.epi), "s"(job.act), "s"(job.accumulate), "s"(job.H), "s"(job.colmode), "s"(job.bias), "s"(job.out),
                  "s"(job.o1), "s"(job.o2), "s"(job.mask), "s"(job.ldo), "s"(job.ldo1), "s"(job.ldo2), "s"(job.N), "s"(job.M));
+#endif
+    // (SK_TAIL_FIELDS: nothing is requested here; the epilogue's fields have sat in scalar registers since the entry batch.
+    // Still no local copy of the descriptor: DESIGN 3.1 item 2.)
     __syncthreads();
     SK_STAMP(3);
     if (wave >= EWAVES) return;
@@ -534,16 +567,18 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
 
     // Fused epilogue.  MFMA C/D layout (16x16): column = lane & 15, row = (lane >> 4) * 4 + reg.
     const int g = lane >> 4, jj = lane & 15;
-    const int n = sk_jcol(job, tile, jj);
-    const bool n_ok = n < N;
-    const float bias = job.bias ? p_bias : 0.f;
-    const int H = job.H;
+    const int n = jcol(tile, jj);
+    // (gate-interleaved columns: a 32-column workgroup behind an odd number of 4-unit tiles has no columns of its own in its
+    // second tile, whatever n says)
+    const bool n_ok = n < N && !((f_epi == SK_EPI_LSTM || f_colmode == 1) && tile * 4 >= f_H);
+    const float bias = f_bias ? p_bias : 0.f;
+    const int H = f_H;
     if (!has_add) {
 #pragma unroll
         for (int r = 0; r < RPW; ++r) p_add[r] = 0.f;
     }
 
-    if (job.epi == SK_EPI_LSTM) {
+    if (f_epi == SK_EPI_LSTM) {
         // Gates of hidden unit j live in lanes jj = q*4 + (j&3), q = 0..3 (i, f, o, g order,
         // ops.py:523-541).  Gather them with wave shuffles; lanes with q == 0 do the cell update.
 #pragma unroll
@@ -553,7 +588,7 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
             const float pre = v[r] + bias + p_add[r];
             const int q = jj >> 2;
             const float gate = (q == 3) ? tanhf(pre) : ph_sigmoid(pre);
-            if (job.o2 && ok) job.o2[sk_off(m, job.ldo2, n)] = gate;  // saved activations [M,4H]
+            if (f_o2 && ok) f_o2[sk_off(m, f_ldo2, n)] = gate;  // saved activations [M,4H]
             const int src = (lane & ~12);
             const float gi = __shfl(gate, src | 0, 64);
             const float gf = __shfl(gate, src | 4, 64);
@@ -563,8 +598,8 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                 const int j = n;  // q == 0 -> n = hidden index
                 const float cp = p_e1[r];
                 const float cn = cp * gf + gg * gi;
-                job.o1[sk_off(m, job.ldo1, j)] = cn;
-                job.out[sk_off(m, job.ldo, j)] = tanhf(cn) * go;
+                f_o1[sk_off(m, f_ldo1, j)] = cn;
+                f_out[sk_off(m, f_ldo, j)] = tanhf(cn) * go;
             }
         }
         SK_STAMP(4);
@@ -576,25 +611,25 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
         const int m = m0 + rb * 16 + 4 * g + er0 + r;
         if (m >= M || !n_ok) continue;
         float x = v[r];
-        switch (job.epi) {
+        switch (f_epi) {
             case SK_EPI_LINEAR: {
                 x += bias + p_add[r];
-                if (job.act == SK_ACT_RELU) x = fmaxf(x, 0.f);
-                else if (job.act == SK_ACT_TANH) x = tanhf(x);
-                else if (job.act == SK_ACT_SIGMOID) x = ph_sigmoid(x);
-                float* o = job.out + sk_off(m, job.ldo, n);
-                if (job.accumulate == 1) x += p_oc[r];  // exclusive owner of the tile: no two jobs of a launch share one
+                if (f_act == SK_ACT_RELU) x = fmaxf(x, 0.f);
+                else if (f_act == SK_ACT_TANH) x = tanhf(x);
+                else if (f_act == SK_ACT_SIGMOID) x = ph_sigmoid(x);
+                gfloat* o = f_out + sk_off(m, f_ldo, n);
+                if (f_acc == 1) x += p_oc[r];  // exclusive owner of the tile: no two jobs of a launch share one
                 *o = x;
             } break;
             case SK_EPI_GRU_GATES: {
                 x += bias + p_add[r];
                 const float gt = ph_sigmoid(x);
                 if (n < H) {
-                    job.o1[sk_off(m, job.ldo1, n)] = gt;  // update gate z
+                    f_o1[sk_off(m, f_ldo1, n)] = gt;  // update gate z
                 } else {
                     const int j = n - H;
-                    job.o2[sk_off(m, job.ldo2, j)] = gt;  // reset gate r
-                    job.out[sk_off(m, job.ldo, j)] = gt * p_e0[r];
+                    f_o2[sk_off(m, f_ldo2, j)] = gt;  // reset gate r
+                    f_out[sk_off(m, f_ldo, j)] = gt * p_e0[r];
                 }
             } break;
             case SK_EPI_GRU_CAND: {
@@ -603,19 +638,19 @@ __device__ __forceinline__ void sk_body(const SkJob& job, int tile0, f32x4* red)
                 const float z = p_e1[r];
                 const float hp = p_e0[r];
                 float hn = z * c + (1.f - z) * hp;
-                if (job.mask) {
-                    const float mk = job.mask[m];
+                if (f_mask) {
+                    const float mk = f_mask[m];
                     hn = mk * hn + (1.f - mk) * hp;
                 }
-                if (job.o1) job.o1[sk_off(m, job.ldo1, n)] = c;
-                job.out[sk_off(m, job.ldo, n)] = hn;
+                if (f_o1) f_o1[sk_off(m, f_ldo1, n)] = c;
+                f_out[sk_off(m, f_ldo, n)] = hn;
             } break;
             case SK_EPI_BWD_RH: {
                 // x = d(r*h_prev)[m][n]
                 const float r_ = p_e1[r];
                 const float hp = p_e0[r];
-                job.out[sk_off(m, job.ldo, n)] = x * hp * r_ * (1.f - r_);  // dG_r
-                job.o1[sk_off(m, job.ldo1, n)] = p_oc[r] + x * r_;          // dh_prev +=
+                f_out[sk_off(m, f_ldo, n)] = x * hp * r_ * (1.f - r_);  // dG_r
+                f_o1[sk_off(m, f_ldo1, n)] = p_oc[r] + x * r_;          // dh_prev +=
             } break;
             default: break;
         }
