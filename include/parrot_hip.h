@@ -747,6 +747,27 @@ long long parrot_sample_persist_floats_forced(const ParrotSampleForcedDesc* desc
 int parrot_sample_plan_pieces_dry_forced(const ParrotSampleForcedDesc* desc, int nwg, int* info16);
 int parrot_sample_plan_digest_dry_forced(const ParrotSampleForcedDesc* desc, int nwg, unsigned long long* digest);
 
+/* Decode state: resumable decode calls.  A state is one packed device buffer [B, W] of f32, row-major; row b holds what
+ * utterance b carries from frame t to frame t + 1,
+ *   [ x (ldx) | kappa (A) | w (E) | h_0 (H) .. h_{L-1} (H) | c_0 .. c_{L-1} (H each, cell = 1 only) ],
+ * so admitting or evicting an utterance is a row copy.  States are f32 on every plan (bf16 operands included).
+ * parrot_sample_state_floats: W = ldx + A + E + L H (1 + cell); it reads the descriptor's integers only and touches no
+ *   device (0 for a NULL descriptor).
+ * parrot_sample_load_state: scatters `state` into the slots the next parrot_sample_run enters through -- slot 0 of x, kappa,
+ *   w, h[l] and cwork[l] -- on the stream; the run then decodes frames t .. t + S - 1 of every row exactly as a longer
+ *   call would have, provided the plan keeps the fed-back frame on the step's chain (no Wgx_t / Wcx_t: with them the first
+ *   step of a call rounds x[0] . Wf differently from a step inside one, and a cut shows in the last bits).
+ * parrot_sample_save_state: gathers the state after frame S of the plan's last run -- x[S], kappa[S], w[S]; the layers'
+ *   states and cells from row S of the machine's histories, on the per-step launches from the ping-pong slot the run ended
+ *   on -- into `state`, on the stream.  After a parrot_sample_load_state that no run has followed it returns the loaded
+ *   state.  PARROT_ERR_UNSUPPORTED on a plan that stops early (eou_extra > 0: frame S need not exist); PARROT_ERR_BADARG on
+ *   a plan that has neither run nor been loaded.
+ * Both work on every plan parrot_sample_create and parrot_sample_create_forced make, and return PARROT_ERR_BADARG on a
+ * NULL argument.  Without a load a run enters through whatever the caller wrote into the same slots, as it always has. */
+long long parrot_sample_state_floats(const ParrotSampleDesc* desc);
+int parrot_sample_save_state(void* plan, float* state, void* stream);
+int parrot_sample_load_state(void* plan, const float* state, void* stream);
+
 int parrot_plan_last_error(void* plan);
 
 /* ------------------------------------------------------------------------------------------

@@ -261,6 +261,9 @@ SIGNATURES = {
     "parrot_sample_stops_early": (_i, [_vp]),
     "parrot_sample_steps_run": (_i, [_vp, C.POINTER(C.c_int)]),
     "parrot_sample_set_row_controls": (_i, [_vp, _vp, _vp, _vp]),
+    "parrot_sample_state_floats": (C.c_longlong, [C.POINTER(SampleDesc)]),
+    "parrot_sample_save_state": (_i, [_vp, _vp, _vp]),
+    "parrot_sample_load_state": (_i, [_vp, _vp, _vp]),
     "parrot_decoder_status": (_i, [_vp]),
     "parrot_sample_run": (_i, [_vp, _vp]),
     "parrot_sample_destroy": (_i, [_vp]),

@@ -21,7 +21,7 @@ ARCH = "gfx950"
 
 SOURCES = ["skinny.hip", "biggemm.hip", "attention.hip", "elementwise.hip", "quantize.hip",
            "plans.hip", "plans_decode.hip", "capi.hip", "samplernn.hip", "persist.hip", "persist_forced.hip", "sr_persist.hip", "rowgru.hip", "trainops.hip", "readout.hip",
-           "gmmcost.hip", "labeltables.hip"]
+           "gmmcost.hip", "labeltables.hip", "decode_state.hip"]
 EXTRA_FLAGS = {"quantize.hip": ["-ffp-contract=off"]}
 if env_str("PARROT_PM_DEPTH"):  # development: ring depth of the persistent machine's K loop
     EXTRA_FLAGS["persist.hip"] = EXTRA_FLAGS["persist_forced.hip"] = ["-DPM_DEPTH=" + env_str("PARROT_PM_DEPTH")]

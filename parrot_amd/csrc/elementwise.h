@@ -163,6 +163,22 @@ int gmm_sample_launch(const float* mu, const float* sig_hat, const float* co_hat
 // x <- forced where t < n[b] (own / forced: the [B, ldx] rows of step t; columns >= O zero).
 int frame_force_launch(float* x, float* own, const float* forced, const int* n, int t, int B, int O, int ldx, hipStream_t stream);
 
+// Decode state (parrot_sample_save_state / _load_state, decode_state.hip): the packed buffer [B, W] and the row-major
+// [B, wd[k]] buffers its row is made of, in the row's order -- piece k lies at columns off[k] .. off[k] + wd[k].
+#define DECODE_STATE_MAXSEG 16  // x, kappa, w, then a state and (LSTM) a cell per layer (plans_decode.hip asserts the bound)
+struct DecodeStateSegs {
+    int n = 0, B = 0, W = 0;
+    float* p[DECODE_STATE_MAXSEG];
+    int wd[DECODE_STATE_MAXSEG], off[DECODE_STATE_MAXSEG];
+    void add(const float* buf, int width) {  // (a launch checks n against DECODE_STATE_MAXSEG and the widths)
+        if (n < DECODE_STATE_MAXSEG) { p[n] = const_cast<float*>(buf); wd[n] = width; off[n] = W; }
+        ++n;
+        W += width;
+    }
+};
+int decode_state_gather_launch(const DecodeStateSegs& s, float* state, hipStream_t stream);         // pieces -> state
+int decode_state_scatter_launch(const DecodeStateSegs& s, const float* state, hipStream_t stream);  // state -> pieces
+
 struct LstmStateBwdChain {
     const float* dh;      // [B,H] gradient wrt s_t
     const float* dh2;     // [B,H] optional second share of it or null

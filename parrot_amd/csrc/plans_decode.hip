@@ -592,6 +592,46 @@ struct SamplePlan : PlanBase {
         return 0;
     }
 
+    // ---- decode state out and in (parrot_sample_save_state / _load_state; the kernels: decode_state.hip) -------------------
+    // What a row carries from frame t to frame t + 1, packed [B, W]: x, kappa, w, the layers' states, an LSTM's cells.  Every
+    // path ENTERS through slot 0 of d.x / d.kappa / d.w / d.h[l] / d.cwork[l] (tail(): the init records; run_persist; run_all),
+    // so loading is one scatter into them.  After frame S the first three lie in slot S of their histories; states and cells
+    // in row S of the machine's histories (sl.h / sl.c), on the launches in the ping-pong slot the run ended on (S & 1).
+    // at_entry: a state was loaded and no run has followed -- then THE state of the plan is the one in the entering slots.
+    bool at_entry = false;
+    int run(int which, hipStream_t s) override {
+        at_entry = false;
+        return PlanBase::run(which, s);
+    }
+    static long long state_floats(const ParrotSampleDesc& d) {
+        return (long long)d.ldx + d.A + d.E + (long long)d.L * d.H * (d.cell == 1 ? 2 : 1);
+    }
+    DecodeStateSegs state_segs(bool entry) const {
+        static_assert(3 + 2 * PARROT_MAX_LAYERS <= DECODE_STATE_MAXSEG, "a decode state has more pieces than DecodeStateSegs holds");
+        const size_t t = entry ? 0 : (size_t)d.S, BH = (size_t)d.B * d.H;
+        DecodeStateSegs s;
+        s.B = d.B;
+        s.add(d.x + t * d.B * d.ldx, d.ldx);
+        s.add(d.kappa + t * d.B * d.A, d.A);
+        s.add(d.w + t * d.B * d.E, d.E);
+        for (int l = 0; l < d.L; ++l) s.add(entry ? d.h[l] : live ? sl.h[l] + t * BH : d.h[l] + (d.S & 1) * BH, d.H);
+        for (int l = 0; l < d.L && d.cell == 1; ++l)
+            s.add(entry ? d.cwork[l] : live ? sl.c[l] + t * BH : d.cwork[l] + (d.S & 1) * BH, d.H);
+        return s;
+    }
+    int save_state(float* state, hipStream_t st) const {
+        if (!state) return PARROT_ERR_BADARG;
+        if (d.eou_extra > 0) return PARROT_ERR_UNSUPPORTED;  // a run that stopped early need not have a frame S
+        if (!has_run && !at_entry) return PARROT_ERR_BADARG;  // neither a run nor a load: there is no state yet
+        return decode_state_gather_launch(state_segs(at_entry), state, st);
+    }
+    int load_state(const float* state, hipStream_t st) {
+        if (!state) return PARROT_ERR_BADARG;
+        const int rc = decode_state_scatter_launch(state_segs(true), state, st);
+        at_entry = at_entry || rc == 0;
+        return rc;
+    }
+
     int run_persist(hipStream_t st) {
         const size_t BH = (size_t)d.B * d.H;
         for (int l = 0; l < d.L; ++l) {  // row-major initial state for the epilogues (r * h_prev, state blend; LSTM: cells)
@@ -1181,6 +1221,13 @@ int parrot_sample_set_row_controls(void* plan, const float* timing, const float*
 }
 int parrot_sample_steps_run(void* plan, int* steps) { PH_ENTRY();
     return plan ? static_cast<SamplePlan*>(plan)->steps_run(steps) : PARROT_ERR_BADARG;
+}
+long long parrot_sample_state_floats(const ParrotSampleDesc* desc) { return desc ? SamplePlan::state_floats(*desc) : 0; }
+int parrot_sample_save_state(void* plan, float* state, void* stream) { PH_ENTRY();
+    return plan ? static_cast<SamplePlan*>(plan)->save_state(state, (hipStream_t)stream) : PARROT_ERR_BADARG;
+}
+int parrot_sample_load_state(void* plan, const float* state, void* stream) { PH_ENTRY();
+    return plan ? static_cast<SamplePlan*>(plan)->load_state(state, (hipStream_t)stream) : PARROT_ERR_BADARG;
 }
 
 // (the entries below and their _forced twins: one body each, on the planners' own descriptor)

@@ -19,8 +19,8 @@ def _as_numpy(x):
 
 
 class _DecodeMixin:
-    def _sample_workspace(self, S, N, U, stop_extra=0, forced=False):
-        ws_key = self._sample_ws_key(S, N, U, stop_extra, forced)
+    def _sample_workspace(self, S, N, U, stop_extra=0, forced=False, carry=False):
+        ws_key = self._sample_ws_key(S, N, U, stop_extra, forced, carry)
         ws = self._sample_ws.get(ws_key)
         if ws is not None:
             return ws
@@ -29,17 +29,19 @@ class _DecodeMixin:
             raise ValueError("decode_dtype='bf16' " + why)
         ws = self._sample_buffers(S, N, U, stop_extra, forced)
         fd, d = self._sample_descriptor(ws, S, N, U, stop_extra, forced)
-        self._sample_machine_operands(ws, d, fd, N, forced)
+        self._sample_machine_operands(ws, d, fd, N, forced, carry)
         self._sample_create_plan(ws, d, fd, S, N, U, stop_extra)
         self._sample_ws[ws_key] = ws
         return ws
 
     @staticmethod
-    def _sample_ws_key(S, N, U, stop_extra, forced):
+    def _sample_ws_key(S, N, U, stop_extra, forced, carry=False):
         """A plan that stops at the end of the utterance is another plan: a workspace key of its own; so is a plan with
-        forced frames -- a call without them keeps the key, and the plan, it had."""
+        forced frames -- a call without them keeps the key, and the plan, it had -- and so is a carry plan (state= /
+        return_state=, decode_segments): ('carry', ...) in front of the rest, 'forced' included."""
         key = ('stop', S, N, U, stop_extra) if stop_extra else (S, N, U)
-        return ('forced',) + key if forced else key
+        key = ('forced',) + key if forced else key
+        return ('carry',) + key if carry else key
 
     def _sample_buffers(self, S, N, U, stop_extra, forced):
         """Every tensor of the workspace but the machine's operand copies (ws['pm'])."""
@@ -150,7 +152,7 @@ class _DecodeMixin:
             fd.forced, fd.n_forced, fd.own_x = (ws[k].data_ptr() for k in ('forced', 'n_forced', 'own_x'))
         return fd, d
 
-    def _sample_machine_operands(self, ws, d, fd, N, forced):
+    def _sample_machine_operands(self, ws, d, fd, N, forced, carry=False):
         """Persistent phase machine (csrc/persist.h): the decode loop as one resident kernel.  It wants fragment-major
         copies of the packed layer matrices with the fed-back-output rows appended (padded to 64 rows), of the readout
         stack and of the output projection (63 -> 64 columns); sample_model_device refreshes them per call.  LSTM decoders:
@@ -205,8 +207,9 @@ class _DecodeMixin:
                 d.Watt_t = pm['Watt_t'].data_ptr()
             # round 5: the fed-back frame out of the step's chain (weak feedback, L >= 2): layer 0's matrices with the rows
             # A . Wf appended, A = the last layer's rows of Wr . Wo (ParrotSampleDesc::Wgx_t / Wcx_t)
-            # (a forced plan keeps the frame on the chain and does not take them)
-            if f32_gru and not forced and L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
+            # (a forced plan keeps the frame on the chain and does not take them; nor does a carry plan: the first step of
+            # a call takes x[0] . Wf, a step inside one x_pre . Wf + h_{L-1} . (A . Wf) -- a cut would show in the bits)
+            if f32_gru and not forced and not carry and L >= 2 and self._fb_layers == [1] and env_int('PARROT_PM_FBC', 1) != 0:
                 for key, wd, suf, mat, rec in self._groups:
                     rows = H + E + 64 + H
                     pm['cat'][('x', key)] = torch.zeros(rows, wd, **f)
@@ -389,7 +392,7 @@ class _DecodeMixin:
 
     def sample_until_end_device(self, labels, labels_mask, speaker, num_samples, max_steps, extra=40, unif=None, noise=None,
                                 seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None,
-                                speaker_weights=None, forced_frames=None, n_forced=None):
+                                speaker_weights=None, forced_frames=None, n_forced=None, state=None, return_state=False):
         """sample_model_device that stops at the end of the utterance INSIDE the decode kernel instead of decoding
         max_steps frames and cutting afterwards.  The rule is end_of_utterance's (reference sample.py:145-163): a row ends
         `extra` frames after the first step whose window weight on the position just past its text beats the weight on every
@@ -399,6 +402,10 @@ class _DecodeMixin:
         timing_coeffs / sharpening_coeffs / sampling_biases / speaker_weights / forced_frames / n_forced: as
         sample_model_device (with forcing outs has the seventh tensor, own_x, cut like the others; the rule reads phi only)."""
         from .utils import end_of_utterance_args
+        if state is not None or return_state:
+            raise ValueError("sample_until_end does not resume: the stop lives inside one launch of the machine and the frame "
+                             "a state would be taken after need not exist; decode_segments(stop_at_end=True) stops between "
+                             "segments instead")
         ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
         forced = self._check_forced(num_samples, max_steps, forced_frames, n_forced)
         why = self._decode_stop_refusal(num_samples, extra)  # (before anything is keyed on `extra` or allocated)
@@ -423,16 +430,17 @@ class _DecodeMixin:
 
     def sample_until_end(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, max_steps, extra=40,
                          timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
-                         forced_frames=None, n_forced=None):
+                         forced_frames=None, n_forced=None, state=None, return_state=False):
         """numpy twin of sample_until_end_device (as sample_model is of sample_model_device): (list of numpy arrays,
         numpy lengths [N])."""
         kw = {k: v for k, v in locals().items() if k in _PER_UTTERANCE}
-        outs, lengths = self.sample_until_end_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, max_steps, extra, **kw)
+        outs, lengths = self.sample_until_end_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, max_steps, extra,
+                                                     state=state, return_state=return_state, **kw)
         return [o.detach().cpu().numpy().copy() for o in outs], lengths.cpu().numpy()
 
     def sample_model_device(self, labels, labels_mask, speaker, num_samples, num_steps, unif=None, noise=None,
                             seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
-                            forced_frames=None, n_forced=None):
+                            forced_frames=None, n_forced=None, state=None, return_state=False):
         """Device-resident version of sample_model: returns torch tensors
         [sample_x [S,N,O], k [S,N,A], w [S,N,E], pi, phi [S,N,U], pi_att [S,N,A]].
         GMM head: the component choice / Gaussian noise come from `unif` [S,N] and `noise` [S,N,O] if given,
@@ -449,36 +457,54 @@ class _DecodeMixin:
         n_forced[b] on the row decodes freely from the state the prompt left.  The list then has a seventh tensor, own_x
         [S, N, O]: what the model emitted or drew at every step; sample_x holds the fed-back (forced) frames in the forced
         region and equals own_x elsewhere.  Composes with the four arguments above.  ValueError (before anything is
-        allocated) on a wrong shape, P > num_steps, non-finite frames, n outside 0 .. P, and with decode_dtype='bf16'."""
+        allocated) on a wrong shape, P > num_steps, non-finite frames, n outside 0 .. P, and with decode_dtype='bf16'.
+        Resuming (both left alone: the call as it is without them, on the same workspace): state -- a DecodeState
+        (initial_decode_state, or what an earlier call returned): the call decodes frames t .. t + num_steps - 1 of every row
+        from it instead of starting at frame 0 from the learned initial states; unif / noise / forced_frames / n_forced then
+        count from the call's first frame.  return_state=True, or a state given: returns (outs, DecodeState) -- the state
+        after the call's last frame.  Such a call runs on a carry plan (workspace key ('carry', ...)), which keeps the
+        fed-back frame on the step's chain, so calls chained over any cut give the bits of the one carry call over all the
+        frames; for a two- or three-layer GRU stack with an MSE head that is the program of PARROT_PM_FBC=0, not the default
+        call's, every other configuration keeps its program.  ValueError (before anything is allocated) on a state that is
+        no DecodeState, of another N or W, on another device, or not finite."""
         ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
         forced = self._check_forced(num_samples, num_steps, forced_frames, n_forced)
-        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl, forced)
+        carry = state is not None or bool(return_state)
+        self._check_state(num_samples, state)
+        return self._sample_device(None, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl, forced,
+                                   state=state, carry=carry)
 
     def _sample_device(self, ws, labels, labels_mask, speaker, num_samples, num_steps, unif, noise, seed, ctl=None,
-                       forced=None):
-        """One decode call on the workspace `ws` (None: the plain workspace of the shape).  ctl: what _check_row_controls
-        returned (None: no per-utterance arguments); forced: what _check_forced returned (None: no forced frames)."""
-        controls, speaker_weights = ctl if ctl is not None else (None, None)
+                       forced=None, state=None, carry=False):
+        """One decode call on the workspace `ws` (None: the plain workspace of the shape; carry: the carry workspace).
+        ctl: what _check_row_controls returned (None: no per-utterance arguments); forced: what _check_forced returned
+        (None: no forced frames); state: the DecodeState the call enters through (None: the learned initial states).
+        Two parts: what depends on the utterances and the parameters (_decode_setup), then the run (_decode_run) --
+        decode_segments does the first once and the second per segment.  carry: returns (outs, DecodeState)."""
         self.allocate()
+        N, U = int(numpy.shape(labels)[0]), int(numpy.shape(labels)[1])
+        assert N == num_samples
+        if ws is None:
+            ws = self._sample_workspace(num_steps, N, U, forced=forced is not None, carry=carry)
+        self._decode_setup(ws, labels, labels_mask, speaker, ctl)
+        outs = self._decode_run(ws, num_steps, unif, noise, seed, forced, state)
+        if not carry:
+            return outs
+        done = numpy.zeros(N, dtype=numpy.int64) if state is None else state.frames_done
+        return outs, self._save_decode_state(ws, done + num_steps)
+
+    def _decode_setup(self, ws, labels, labels_mask, speaker, ctl=None, weights=True):
+        """Everything of a decode call that depends on the utterances and the parameters and not on where in the utterance
+        the run starts: encoder, bias sums, row controls, speaker terms, the machine's weight copies and constant rows.
+        weights=False (StreamingDecoder, when a slot gets a new utterance and the parameters are what they were): the
+        fragment-major weight copies stay; only what depends on the utterances is written again."""
+        controls, speaker_weights = ctl if ctl is not None else (None, None)
         dev = self._dev()
         labels = torch.as_tensor(labels).to(dev)
         labels_mask = torch.as_tensor(labels_mask).to(dev, torch.float32)
-        N, U = labels.shape[0], labels.shape[1]
-        assert N == num_samples
-        S, L, H, O = num_steps, self.num_layers, self.rnn_h_dim, self.output_dim
-        if ws is None:
-            ws = self._sample_workspace(S, N, U, forced=forced is not None)
-        if forced is not None:  # every call rewrites both arrays whole: nothing of an earlier prompt survives
-            frames, n = forced
-            ws['forced'].zero_()
-            ws['forced'][:frames.shape[0], :, :O].copy_(torch.from_numpy(frames))
-            ws['n_forced'].copy_(torch.from_numpy(n))
+        L = self.num_layers
         ws['ctx'].copy_(self._encoder_forward(labels, labels_mask, None))
         self._sum_layer_biases(ws, extra_fb=not self.layer_norm)
-        for l in range(1, L + 1):
-            ws['h'][l - 1][0].copy_(self._p(f'/rnn{l}.initial_state').unsqueeze(0).expand(N, -1))
-            if self.cell_type == 'lstm':
-                ws['cwork'][l - 1][0].copy_(self._p(f'/rnn{l}.initial_cells').unsqueeze(0).expand(N, -1))
         ws['br'].copy_(self._p('/att_to_readout.b'))
         for l in range(1, L + 1):
             if not self.layer_norm:
@@ -504,19 +530,44 @@ class _DecodeMixin:
                 for nm, key in _GMM_HEADS:
                     ops.gemm(emb, self._p(f'/speaker_to_output/fork_{key}.W'),
                              bias=self._p(f'/speaker_to_output/fork_{key}.b'), out=ws['add_' + nm])
-        ws['x'][0].zero_()  # initial_x, model.py:834-835
+        if 'pm' in ws:
+            self._refresh_sample_machine_weights(ws, tiles=weights)
+
+    def _write_initial_state(self, ws):
+        """The learned initial states into the entering slots (slot 0) of the workspace; x[0] = 0, model.py:834-835."""
+        N = ws['x'].shape[1]
+        for l in range(1, self.num_layers + 1):
+            ws['h'][l - 1][0].copy_(self._p(f'/rnn{l}.initial_state').unsqueeze(0).expand(N, -1))
+            if self.cell_type == 'lstm':
+                ws['cwork'][l - 1][0].copy_(self._p(f'/rnn{l}.initial_cells').unsqueeze(0).expand(N, -1))
+        ws['x'][0].zero_()
         ws['w'][0].copy_(self._p('.initial_w').unsqueeze(0).expand(N, -1))
         ws['kappa'][0].zero_()
+
+    def _decode_run(self, ws, num_steps, unif, noise, seed, forced=None, state=None, n_valid=None):
+        """The run of a decode call on a workspace that _decode_setup has prepared: forced frames, the entering state,
+        the randomness, the plan.  num_steps: the plan's S.  n_valid (decode_segments' last segment): unif / noise / the
+        forced frames cover the first n_valid steps only, the rest run on zeros and are cut by the caller."""
+        dev = self._dev()
+        S, O = num_steps, self.output_dim
+        if forced is not None:  # every call rewrites both arrays whole: nothing of an earlier prompt survives
+            frames, n = forced
+            ws['forced'].zero_()
+            ws['forced'][:frames.shape[0], :, :O].copy_(torch.as_tensor(frames))
+            ws['n_forced'].copy_(torch.as_tensor(n))
+        if state is None:
+            self._write_initial_state(ws)
+        else:
+            _lib.call('parrot_sample_load_state', ws['plan'], state.tensor.data_ptr(), ops._stream())
         if self.which_cost == 'GMM':
             if unif is None or noise is None:
-                g = torch.Generator(device=dev)
-                g.manual_seed(int(self.seed if seed is None else seed))
-                unif = torch.rand(S, N, device=dev, generator=g)
-                noise = torch.randn(S, N, O, device=dev, generator=g)
-            ws['unif'].copy_(torch.as_tensor(unif).to(dev, torch.float32))
-            ws['noise'].copy_(torch.as_tensor(noise).to(dev, torch.float32))
-        if 'pm' in ws:
-            self._refresh_sample_machine_weights(ws)
+                unif, noise = self._decode_randomness(S, ws['x'].shape[1], seed)
+            k = S if n_valid is None else n_valid
+            if k < S:
+                ws['unif'][k:].zero_()
+                ws['noise'][k:].zero_()
+            ws['unif'][:k].copy_(torch.as_tensor(unif).to(dev, torch.float32))
+            ws['noise'][:k].copy_(torch.as_tensor(noise).to(dev, torch.float32))
         _lib.call('parrot_sample_run', ws['plan'], ops._stream())
         if 'pm' in ws:  # persistent machine: a launch that gave up leaves invalid frames -- fail loudly (synchronises)
             _lib.call('parrot_sample_status', ws['plan'])
@@ -525,6 +576,84 @@ class _DecodeMixin:
         pi = ws['pi_out'] if self.which_cost == 'GMM' else sx
         outs = [sx, ws['kappa'][1:], ws['w'][1:], pi, ws['phi'], ws['a']]
         return outs + [ws['own_x'][:, :, :O]] if forced is not None else outs
+
+    def _decode_randomness(self, S, N, seed):
+        """unif [S, N] and noise [S, N, O] of a GMM head from torch's generator (`seed`, else the model's)."""
+        g = torch.Generator(device=self._dev())
+        g.manual_seed(int(self.seed if seed is None else seed))
+        unif = torch.rand(S, N, device=self._dev(), generator=g)
+        return unif, torch.randn(S, N, self.output_dim, device=self._dev(), generator=g)
+
+    # ---- resumable decoding: the state a call hands on (parrot_sample_save_state / _load_state) ----------------------------
+    def _decode_state_pieces(self):
+        """[(name, width)] of a decode state's row, in the library's order (include/parrot_hip.h): x (ldx) | kappa (A) | w (E)
+        | h_0 .. h_{L-1} (H each) | c_0 .. c_{L-1} (H each, LSTM only)."""
+        H, L = self.rnn_h_dim, self.num_layers
+        pieces = [('x', (self.output_dim + 3) // 4 * 4), ('kappa', self.attention_size), ('w', self.encoded_input_dim)]
+        pieces += [(('h', l), H) for l in range(L)]
+        return pieces + [(('c', l), H) for l in range(L)] if self.cell_type == 'lstm' else pieces
+
+    def decode_state_floats(self):
+        """W: the floats one utterance carries from frame to frame (parrot_sample_state_floats of the decode descriptor)."""
+        return sum(wd for _, wd in self._decode_state_pieces())
+
+    def initial_decode_state(self, num_samples):
+        """The DecodeState every utterance starts from: the learned initial states and cells, initial_w, zero kappa, zero x."""
+        self.allocate()
+        st = DecodeState(self, torch.zeros(int(num_samples), self.decode_state_floats(), device=self._dev(), dtype=torch.float32))
+        st.reset_rows(range(int(num_samples)))
+        return st
+
+    def _check_state(self, N, state):
+        """Refuses a state the call cannot enter through, without touching the workspace: ValueError on something that is no
+        DecodeState, another N, another W, another device, a non-finite value."""
+        if state is None:
+            return
+        if not isinstance(state, DecodeState):
+            raise ValueError(f"state must be a DecodeState (Parrot.initial_decode_state, or what a call returned), "
+                             f"got {type(state).__name__}")
+        t, W, dev = state.tensor, self.decode_state_floats(), self._dev()
+        if t.dim() != 2 or t.shape[0] != N:
+            raise ValueError(f"state holds {tuple(t.shape)[0] if t.dim() else 0} utterances, the call decodes N = {N}")
+        if t.shape[1] != W:
+            raise ValueError(f"state rows hold {t.shape[1]} floats, this model carries W = {W} per utterance")
+        if t.device.type != dev.type or (dev.index is not None and t.device.index != dev.index):
+            raise ValueError(f"state lives on device {t.device}, the model decodes on {dev}")
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("state must be a contiguous float32 tensor [N, W]")
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("state must be finite")
+
+    def _save_decode_state(self, ws, frames_done):
+        """The state after the last frame of the workspace's last run, as a new DecodeState."""
+        t = torch.empty(ws['x'].shape[1], self.decode_state_floats(), device=self._dev(), dtype=torch.float32)
+        _lib.call('parrot_sample_save_state', ws['plan'], t.data_ptr(), ops._stream())
+        return DecodeState(self, t, frames_done)
+
+    def decode_segments(self, labels, labels_mask, speaker, num_samples, num_steps, segment_frames, unif=None, noise=None,
+                        seed=None, timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
+                        forced_frames=None, n_forced=None, stop_at_end=False, extra=40, state=None):
+        """sample_model_device in segments of `segment_frames` frames, handed out as each completes: iterating yields
+        (t0, outs) -- the tensors of sample_model_device for frames t0 .. t0 + len - 1 (own copies; with forcing the seventh,
+        own_x).  One carry plan of segment_frames steps runs every segment; encoder, speaker terms and weight copies are made
+        once, a boundary saves and loads the state and slices unif / noise / the forced frames (n_forced - t0, clamped to the
+        segment).  The last, shorter segment runs whole and is cut.  The frames are, bit for bit, those of the one carry call
+        over num_steps frames (sample_model_device(.., return_state=True)).
+        The end-of-utterance rule runs per segment on the device (segment_end_of_utterance: end_of_utterance_args' strict
+        predicate; the first firing step of a row is carried across segments): `.first` [N] (-1: not yet) and `.lengths` [N]
+        (first + extra, at most num_steps; num_steps where the row never fired) are current after every segment.
+        stop_at_end=True: the iteration ends after the segment in which the longest row's first + extra falls -- the
+        overshoot is less than one segment.  `.state`: the DecodeState after the last segment RUN (a cut last segment has
+        run segment_frames frames: .state.frames_done says so).  unif / noise: [num_steps, N(, O)], else from `seed` as
+        sample_model_device draws them; state: enter through a DecodeState instead of the learned initial states.
+        ValueError before anything is allocated, as sample_model_device, and on segment_frames < 1."""
+        if int(segment_frames) < 1:
+            raise ValueError(f"segment_frames must be >= 1, got {segment_frames}")
+        ctl = self._check_row_controls(num_samples, timing_coeffs, sharpening_coeffs, sampling_biases, speaker_weights)
+        forced = self._check_forced(num_samples, num_steps, forced_frames, n_forced)
+        self._check_state(num_samples, state)
+        return DecodeSegments(self, labels, labels_mask, speaker, int(num_samples), int(num_steps), int(segment_frames), unif,
+                              noise, seed, ctl, forced, bool(stop_at_end), int(extra), state)
 
     @property
     def decode_path(self):
@@ -539,13 +668,14 @@ class _DecodeMixin:
         _lib.call('parrot_tile_weights_bf16' if bf16 else 'parrot_tile_weights', W.data_ptr(), W.shape[0], W.shape[1],
                   W.shape[1], out.data_ptr(), 2 if bf16 else 0, lstm_H, ops._stream())
 
-    def _refresh_sample_machine_weights(self, ws):
-        """Fragment-major weight copies of the decode machine from the current parameters."""
+    def _refresh_sample_machine_weights(self, ws, tiles=True):
+        """Fragment-major weight copies of the decode machine from the current parameters, and the constant rows that carry
+        the speaker terms (ro_const / rh_const / oadd_pad).  tiles=False: the constant rows only."""
         pm, st = ws['pm'], self.store.storage
         H, E, L, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.output_dim
         lstm_H = H if self.cell_type == 'lstm' else 0
         with torch.no_grad():
-            for l in range(L):
+            for l in range(L if tiles else 0):
                 for key, wd, suf, mat, rec in self._groups:
                     cat = pm['cat'][(l, key)]
                     kl = H + E + l * H
@@ -564,17 +694,24 @@ class _DecodeMixin:
                         ch[:, col:col + n].add_(ws['add_' + nm])
                     col += n
                 Wrh, c = compose_readout_output(st['dec.Wr'], Wh, ws['br'], ws['radd'], torch.zeros_like(ch[0]), ch, ch.shape[0])
-                pm['Wrh'].copy_(Wrh)
-                self._tile_machine_weight(pm['Wrh'], pm['Wrh_t'])
+                if tiles:
+                    pm['Wrh'].copy_(Wrh)
+                    self._tile_machine_weight(pm['Wrh'], pm['Wrh_t'])
                 pm['rh_const'].copy_(c)
             else:
-                self._refresh_mse_head_weights(ws)
+                self._refresh_mse_head_weights(ws, tiles)
 
-    def _refresh_mse_head_weights(self, ws):
+    def _refresh_mse_head_weights(self, ws, tiles=True):
         """The MSE head's part of _refresh_sample_machine_weights: readout stack, output projection, their composition, the
         folded attention projection and the composed feedback rows (called under no_grad)."""
         pm, st = ws['pm'], self.store.storage
         H, E, L, O = self.rnn_h_dim, self.encoded_input_dim, self.num_layers, self.output_dim
+        if not tiles:  # the constant rows from the padded copies as they stand (the parameters have not changed)
+            if 'oadd_pad' in pm:
+                pm['oadd_pad'][:, :O].copy_(ws['oadd'])
+            pm['ro_const'].copy_(compose_readout_output(st['dec.Wr'], pm['Wo_pad'], ws['br'], ws['radd'], pm['bo_pad'],
+                                                        pm.get('oadd_pad'), pm['ro_const'].shape[0])[1])
+            return
         self._tile_machine_weight(st['dec.Wr'], pm['Wr_t'])
         pm['Wo_pad'][:, :O].copy_(self._p('/readout_to_output.W'))
         self._tile_machine_weight(pm['Wo_pad'], pm['Wo_t'])
@@ -602,12 +739,16 @@ class _DecodeMixin:
 
     def sample_model(self, labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, num_samples, num_steps,
                      timing_coeffs=None, sharpening_coeffs=None, sampling_biases=None, speaker_weights=None,
-                     forced_frames=None, n_forced=None):
+                     forced_frames=None, n_forced=None, state=None, return_state=False):
         """Parrot.sample_model (model.py:1061-1083): numpy in, list of numpy arrays out
         [sample_x, k, w, pi, phi, pi_att], all time-major (the caller swaps axes, sample.py:142-143).  The keyword
-        arguments: per utterance, as sample_model_device (forced_frames / n_forced: a seventh array, own_x)."""
+        arguments: per utterance, as sample_model_device (forced_frames / n_forced: a seventh array, own_x); state /
+        return_state: as there -- (list of numpy arrays, DecodeState), the state stays on the device."""
         kw = {k: v for k, v in locals().items() if k in _PER_UTTERANCE}
-        outs = self.sample_model_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, num_steps, **kw)
+        outs = self.sample_model_device(labels_tr, labels_mask_tr, speaker_tr, num_samples, num_steps, state=state,
+                                        return_state=return_state, **kw)
+        if state is not None or return_state:
+            return [o.detach().cpu().numpy().copy() for o in outs[0]], outs[1]
         return [o.detach().cpu().numpy().copy() for o in outs]
 
 
@@ -624,3 +765,291 @@ def compose_readout_output(Wr, Wo_pad, br, radd, bo_pad, oadd_pad, n_rows):
     if oadd_pad is not None:
         c = c + oadd_pad.double()
     return Wro.float(), c.expand(n_rows, Wo_pad.shape[1]).float().contiguous()
+
+
+class DecodeState:
+    """What a decode call hands to the next: one packed float32 tensor [N, W] on the model's device, row b = everything
+    utterance b carries from frame t to frame t + 1 (the library's layout, include/parrot_hip.h), so admitting or evicting
+    an utterance is a row copy.  Named views into it: x [N, ldx], kappa [N, A], w [N, E], h[l] and (LSTM) c[l] [N, H].
+    frames_done: int64 numpy array [N], the frames each row has decoded since its initial state."""
+
+    def __init__(self, parrot, tensor, frames_done=None):
+        self._parrot, self.tensor = parrot, tensor
+        N = tensor.shape[0]
+        self.frames_done = (numpy.zeros(N, dtype=numpy.int64) if frames_done is None
+                            else numpy.array(frames_done, dtype=numpy.int64).reshape(N))
+        self.h, self.c, col = [], [], 0
+        for name, wd in parrot._decode_state_pieces():
+            view = tensor[:, col:col + wd]
+            col += wd
+            if isinstance(name, tuple):
+                getattr(self, name[0]).append(view)
+            else:
+                setattr(self, name, view)
+
+    def reset_rows(self, rows):
+        """The learned initial state into the given rows: initial states and cells, initial_w, zero kappa, zero x."""
+        p = self._parrot
+        rows = [int(r) for r in rows]
+        idx = torch.as_tensor(rows, device=self.tensor.device, dtype=torch.long)
+        with torch.no_grad():
+            self.x[idx] = 0.
+            self.kappa[idx] = 0.
+            self.w[idx] = p._p('.initial_w').to(self.tensor.device)
+            for l in range(len(self.h)):
+                self.h[l][idx] = p._p(f'/rnn{l + 1}.initial_state').to(self.tensor.device)
+            for l in range(len(self.c)):
+                self.c[l][idx] = p._p(f'/rnn{l + 1}.initial_cells').to(self.tensor.device)
+        self.frames_done[rows] = 0
+        return self
+
+    def clone(self):
+        return DecodeState(self._parrot, self.tensor.clone(), self.frames_done.copy())
+
+
+def segment_end_of_utterance(phi, pos, ncmp, first, t0):
+    """The end-of-utterance rule on one segment, on phi's device: phi [F, N, U] are frames t0 .. t0 + F - 1 (t0: an int, or
+    int64 [N] where every row counts its own frames), pos / ncmp [N]
+    what utils.end_of_utterance_args gives, first [N] (int64) the first firing step of each row so far, -1: none.  A step
+    fires when phi[pos] > phi[j] for EVERY j < ncmp (strict, as end_of_utterance and the decode machine's PmAtt).  Returns
+    the new `first`: rows that had fired keep their step, the others get t0 + their first firing step of this segment."""
+    F, N, U = phi.shape
+    at = phi.gather(2, pos.long().view(1, N, 1).expand(F, N, 1))
+    ignore = torch.arange(U, device=phi.device).view(1, U) >= ncmp.long().view(N, 1)
+    fires = ((at > phi) | ignore.unsqueeze(0)).all(dim=2)                     # [F, N]
+    step = torch.where(fires, torch.arange(F, device=phi.device).view(F, 1).expand(F, N),
+                       torch.full((F, N), F, device=phi.device)).min(dim=0).values
+    t0 = t0.to(phi.device).long() if torch.is_tensor(t0) else int(t0)  # (a tensor [N]: every row counts from its own frame)
+    return torch.where((first < 0) & (step < F), step + t0, first)
+
+
+class DecodeSegments:
+    """The iteration Parrot.decode_segments returns: yields (t0, outs) per segment; .first / .lengths / .state follow it."""
+
+    def __init__(self, parrot, labels, labels_mask, speaker, N, S, F, unif, noise, seed, ctl, forced, stop, extra, state):
+        self._m, self._args = parrot, (labels, labels_mask, speaker, unif, noise, seed, ctl, forced, state)
+        self.num_samples, self.num_steps, self.segment_frames, self.stop_at_end, self.extra = N, S, F, stop, extra
+        self.state, self.first, self.frames = state, None, 0
+        self._it = self._run()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._it)
+
+    @property
+    def lengths(self):
+        """[N] int64 on the device: first + extra cut at num_steps, num_steps for a row that has not fired."""
+        if self.first is None:
+            return None
+        S = self.num_steps
+        return torch.where(self.first >= 0, (self.first + self.extra).clamp(max=S), torch.full_like(self.first, S))
+
+    def _run(self):
+        from .utils import end_of_utterance_args
+        m, N, S, F = self._m, self.num_samples, self.num_steps, self.segment_frames
+        labels, labels_mask, speaker, unif, noise, seed, ctl, forced, state = self._args
+        m.allocate()
+        dev = m._dev()
+        lm = torch.as_tensor(labels_mask)
+        U = lm.shape[1]
+        ws = m._sample_workspace(F, N, U, forced=forced is not None, carry=True)
+        m._decode_setup(ws, labels, labels_mask, speaker, ctl)
+        gmm = m.which_cost == 'GMM'
+        if gmm:  # the whole call's randomness once, as the one-piece call draws it; a segment takes its slice
+            if unif is None or noise is None:
+                unif, noise = m._decode_randomness(S, N, seed)
+            unif, noise = torch.as_tensor(unif).to(dev, torch.float32), torch.as_tensor(noise).to(dev, torch.float32)
+        pos, ncmp = (torch.from_numpy(a).to(dev) for a in end_of_utterance_args(lm.detach().cpu().numpy(), U))
+        self.first = torch.full((N,), -1, device=dev, dtype=torch.long)
+        done = numpy.zeros(N, dtype=numpy.int64) if state is None else state.frames_done
+        for t0 in range(0, S, F):
+            r = min(F, S - t0)
+            seg_forced = None
+            if forced is not None:
+                frames, n = forced
+                seg_forced = (frames[t0:t0 + r], numpy.clip(n.astype(numpy.int64) - t0, 0, r).astype(numpy.int32))
+            outs = m._decode_run(ws, F, unif[t0:t0 + r] if gmm else None, noise[t0:t0 + r] if gmm else None, None,
+                                 seg_forced, self.state, n_valid=r)
+            self.state = m._save_decode_state(ws, done + t0 + F)
+            outs = [o[:r].clone() for o in outs]  # (the next segment overwrites the workspace)
+            self.first = segment_end_of_utterance(outs[4], pos, ncmp, self.first, t0)
+            self.frames = t0 + r
+            yield t0, outs
+            if self.stop_at_end and bool((self.first >= 0).all()) and int(self.first.max()) + self.extra <= t0 + r:
+                break
+
+
+class StreamingDecoder:
+    """Continuous admission for the decoder: `slots` utterances decode side by side on ONE carry plan of `segment_frames`
+    steps; between segments a finished utterance is handed out and its slot goes to the next one queued.
+      submit(labels, ...) -> id       queue one utterance (labels: 1 .. max_text label indices)
+      run()                           yields (id, frames [length, O], phi [length, max_text]) as utterances end
+    An utterance ends `extra` frames after the end-of-utterance rule first fires on its phi (segment_end_of_utterance, per
+    segment, on the device), at max_frames at the latest; length is what utils.end_of_utterance gives for its full phi with
+    num_steps = max_frames.  A plain boundary saves and loads the state and slices the rows' randomness and prompts.  A
+    boundary that admits utterances also writes the learned initial state into their rows (DecodeState.reset_rows), runs
+    the encoder and the speaker products for the batch again -- with the batch size the plan has, so a row's context has
+    the bits it would have in any other call of this shape; the rows in flight get their own values again -- and rewrites
+    the label mask's indices, the constant rows and the row controls.  The fragment-major weight copies are made once; they
+    are made again when the parameter buffer was written through torch since (its version counter), or after
+    refresh_parameters().  Idle slots decode a one-character dummy whose frames nobody reads.  A row's frames are, bit for
+    bit, those of Parrot.decode_segments with the utterance in the same slot of a batch of this shape.  Rows must not see one
+    another: a model whose encoder recurs along the batch axis (encoder_literal=True, the reference's) is refused."""
+
+    def __init__(self, parrot, slots, segment_frames, max_text, max_frames, extra=40):
+        import collections
+        for name, v in (('slots', slots), ('segment_frames', segment_frames), ('max_text', max_text), ('max_frames', max_frames)):
+            if int(v) < 1:
+                raise ValueError(f"{name} must be >= 1, got {v}")
+        if int(extra) < 0:
+            raise ValueError(f"extra must be >= 0, got {extra}")
+        if parrot.encoder_type is not None and parrot.encoder_literal:
+            raise ValueError("StreamingDecoder needs encoder_literal=False: the literal encoder (the reference's) recurs along "
+                             "the batch axis, so a row's context depends on its neighbours and would change when one is admitted")
+        self._m, self.slots, self.segment_frames = parrot, int(slots), int(segment_frames)
+        self.max_text, self.max_frames, self.extra = int(max_text), int(max_frames), int(extra)
+        self._queue, self._next_id, self._stale = collections.deque(), 0, True
+        self.segments_run = self.setups_run = self.tilings_run = 0
+        self.placements = {}   # id -> (slot, the segment it was admitted in front of)
+
+    def refresh_parameters(self):
+        """The parameters were written behind torch's back (a fused optimiser step): tile the weights again at the next boundary."""
+        self._stale = True
+
+    def submit(self, labels, speaker=None, timing_coeff=None, sharpening_coeff=None, sampling_bias=None, speaker_weights=None,
+               seed=None, unif=None, noise=None, forced_frames=None):
+        """Queues one utterance; returns its id.  labels: 1 .. max_text label indices; speaker: its index (use_speaker);
+        timing_coeff / sharpening_coeff / sampling_bias: its own value in place of the model's scalar; speaker_weights
+        [num_speakers]: a blend of the speaker table in place of `speaker`; GMM head: unif [max_frames] and noise
+        [max_frames, O], else drawn from `seed` (default: the model's seed + id); forced_frames [P, O], P <= max_frames:
+        the utterance is primed with them.  ValueError on what the decode calls refuse (_check_row_controls, _check_forced)."""
+        m, O = self._m, self._m.output_dim
+        lab = numpy.asarray(_as_numpy(labels)).reshape(-1)
+        if not 1 <= lab.shape[0] <= self.max_text:
+            raise ValueError(f"labels needs 1 .. {self.max_text} entries (max_text), got {lab.shape[0]}")
+        one = lambda v: None if v is None else [v]
+        ctl, sw = m._check_row_controls(1, one(timing_coeff), one(sharpening_coeff), one(sampling_bias),
+                                        None if speaker_weights is None else numpy.asarray(_as_numpy(speaker_weights))[None])
+        if m.use_speaker and speaker is None and sw is None:
+            raise ValueError("this model has speakers: submit needs speaker= or speaker_weights=")
+        prompt = None
+        if forced_frames is not None:
+            fr = numpy.asarray(_as_numpy(forced_frames))
+            if fr.ndim != 2:
+                raise ValueError(f"forced_frames needs shape (P, {O}) = (frames, output_dim), got {tuple(fr.shape)}")
+            prompt = m._check_forced(1, self.max_frames, fr[:, None, :], [fr.shape[0]])[0][:, 0]
+        rnd = None
+        if m.which_cost == 'GMM' and unif is not None and noise is not None:
+            u, z = (numpy.asarray(_as_numpy(a), dtype=numpy.float32) for a in (unif, noise))
+            if u.shape != (self.max_frames,) or z.shape != (self.max_frames, O):
+                raise ValueError(f"unif / noise need shapes ({self.max_frames},) and ({self.max_frames}, {O}), "
+                                 f"got {tuple(u.shape)} and {tuple(z.shape)}")
+            rnd = (u, z)
+        uid = self._next_id
+        self._next_id += 1
+        self._queue.append(dict(id=uid, labels=lab.astype(numpy.int64), speaker=0 if speaker is None else int(speaker),
+                                ctl=ctl, sw=None if sw is None else sw[0], seed=seed, rnd=rnd, prompt=prompt))
+        return uid
+
+    def _admit(self, slot, u, host):
+        """The queued utterance u into row `slot` of the host-side batch."""
+        m, T = self._m, self.max_frames
+        host['labels'][slot] = 0
+        host['mask'][slot] = 0.
+        host['labels'][slot, :len(u['labels'])] = u['labels']
+        host['mask'][slot, :len(u['labels'])] = 1.
+        host['speaker'][slot, 0] = u['speaker']
+        for key, scalar in (('timing', m.timing_coeff), ('sharpening', m.sharpening_coeff), ('bias', m.sampling_bias)):
+            if host[key] is not None:  # (no bias array without a GMM head: _check_row_controls has refused a bias)
+                host[key][slot] = scalar if u['ctl'][key] is None else u['ctl'][key][0]
+        if u['sw'] is not None or host['blend']:
+            if not host['blend']:  # the first blended utterance: from here on every row is a row of weights (one-hot: the index)
+                host['blend'] = True
+                host['sw'][:] = 0.
+                host['sw'][numpy.arange(self.slots), host['speaker'][:, 0]] = 1.
+            host['sw'][slot] = 0.
+            if u['sw'] is not None:
+                host['sw'][slot] = u['sw']
+            else:
+                host['sw'][slot, u['speaker']] = 1.
+        if m.which_cost == 'GMM':
+            if u['rnd'] is None:
+                a, b = m._decode_randomness(T, 1, m.seed + u['id'] if u['seed'] is None else u['seed'])
+                u['rnd'] = (a[:, 0].cpu().numpy(), b[:, 0].cpu().numpy())
+        return dict(u, t=0, first=-1, frames=[], phi=[])
+
+    def run(self):
+        """Decodes everything queued (utterances submitted while it runs included); yields (id, frames [length, O],
+        phi [length, max_text]) -- device tensors -- as each utterance ends."""
+        from .utils import end_of_utterance_args
+        m, N, F, U, T, O = self._m, self.slots, self.segment_frames, self.max_text, self.max_frames, self._m.output_dim
+        m.allocate()
+        dev = m._dev()
+        forced, gmm = not m.decode_bf16, m.which_cost == 'GMM'   # (the bf16 programs have no kernels with forcing)
+        ws = m._sample_workspace(F, N, U, forced=forced, carry=True)
+        host = dict(labels=numpy.zeros((N, U), dtype=numpy.int64), mask=numpy.zeros((N, U), dtype=numpy.float32),
+                    speaker=numpy.zeros((N, 1), dtype=numpy.int64), blend=False,
+                    sw=numpy.zeros((N, m.num_speakers), dtype=numpy.float32) if m.use_speaker else None,
+                    timing=numpy.full(N, m.timing_coeff, dtype=numpy.float32),
+                    sharpening=numpy.full(N, m.sharpening_coeff, dtype=numpy.float32),
+                    bias=numpy.full(N, m.sampling_bias, dtype=numpy.float32) if gmm else None)
+        host['mask'][:, 0] = 1.   # idle slots: a one-character dummy
+        rows = [None] * N
+        state = m.initial_decode_state(N)
+        pos = ncmp = None
+        version = None
+        while self._queue or any(r is not None for r in rows):
+            admitted = []
+            for b in range(N):
+                if rows[b] is None and self._queue:
+                    u = self._queue.popleft()
+                    if u['prompt'] is not None and not forced:
+                        raise ValueError("forced_frames " + m._decode_forced_refusal())
+                    rows[b] = self._admit(b, u, host)
+                    self.placements[u['id']] = (b, self.segments_run)
+                    admitted.append(b)
+            if admitted or pos is None:
+                stale = self._stale or version != m.store.flat._version
+                ctl = dict(timing=host['timing'], sharpening=host['sharpening'], bias=host['bias'])
+                m._decode_setup(ws, host['labels'], host['mask'], host['speaker'], (ctl, host['sw'] if host['blend'] else None),
+                                weights=stale)
+                self._stale, version = False, m.store.flat._version
+                self.setups_run += 1
+                self.tilings_run += int(stale)
+                state.reset_rows(admitted)
+                pos, ncmp = (torch.from_numpy(a).to(dev) for a in end_of_utterance_args(host['mask'], U))
+            unif = noise = seg_forced = None
+            if gmm:
+                unif, noise = numpy.zeros((F, N), dtype=numpy.float32), numpy.zeros((F, N, O), dtype=numpy.float32)
+            if forced:
+                frames, n = numpy.zeros((F, N, O), dtype=numpy.float32), numpy.zeros(N, dtype=numpy.int32)
+                seg_forced = (frames, n)
+            t0 = numpy.zeros(N, dtype=numpy.int64)
+            for b, r in enumerate(rows):
+                if r is None:
+                    continue
+                t0[b] = t = r['t']
+                k = min(F, T - t)
+                if gmm:
+                    unif[:k, b], noise[:k, b] = r['rnd'][0][t:t + k], r['rnd'][1][t:t + k]
+                if r['prompt'] is not None and t < r['prompt'].shape[0]:
+                    seg = r['prompt'][t:t + F]
+                    frames[:seg.shape[0], b], n[b] = seg, seg.shape[0]
+            outs = m._decode_run(ws, F, unif, noise, None, seg_forced, state)
+            state = m._save_decode_state(ws, state.frames_done + F)
+            self.segments_run += 1
+            sx, phi = outs[0].clone(), outs[4].clone()
+            first = torch.tensor([-1 if r is None else r['first'] for r in rows], device=dev, dtype=torch.long)
+            first = segment_end_of_utterance(phi, pos, ncmp, first, torch.from_numpy(t0)).cpu().tolist()
+            for b, r in enumerate(rows):
+                if r is None:
+                    continue
+                r['frames'].append(sx[:, b])
+                r['phi'].append(phi[:, b])
+                r['first'], r['t'] = first[b], r['t'] + F
+                length = T if r['first'] < 0 else min(r['first'] + self.extra, T)
+                if r['t'] >= length:
+                    rows[b] = None
+                    yield r['id'], torch.cat(r['frames'])[:length], torch.cat(r['phi'])[:length]

@@ -171,6 +171,11 @@ def sample_parse(argv=None):
                         help="N > 0: every test utterance is primed with its own first min(N, length) feature frames -- they "
                              "are fed back in place of the decoder's while they last, then it continues freely "
                              "(Parrot.sample_model(forced_frames=.., n_forced=..)); not with --phrase, whose text has no frames")
+    parser.add_argument('--segment_frames', type=int, default=0,
+                        help='F > 0: the decoder runs in segments of F frames on one resumable plan and hands each on as it '
+                             'completes (Parrot.decode_segments; same feature files); --stop_at_end 1 then ends after the '
+                             'segment in which the longest utterance ends; 0: one call for all --num_steps frames; not with '
+                             '--sample_one_step')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
     if args.dataset not in args.save_dir:
@@ -182,6 +187,11 @@ def sample_parse(argv=None):
                          "and the frames would belong to other words: give one of the two")
     if args.prime_frames and args.sample_one_step:
         raise SystemExit("--prime_frames has no meaning with --sample_one_step, which forces every frame already")
+    if args.segment_frames < 0:
+        raise SystemExit("--segment_frames %d: the number of frames cannot be negative" % args.segment_frames)
+    if args.segment_frames and args.sample_one_step:
+        raise SystemExit("--segment_frames cuts the free-running decode into segments; --sample_one_step decodes no such loop: "
+                         "give one of the two")
     for flag in ('timing_coeffs', 'sharpening_coeffs', 'sampling_biases'):
         if getattr(args, flag) is not None:
             setattr(args, flag, parse_float_list(getattr(args, flag), args.num_samples, '--' + flag))

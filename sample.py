@@ -3,6 +3,7 @@ test batch, run Parrot.sample_model (autoregressive decode, one hipGraph) or sam
 apply the end-of-utterance heuristic (sample.py:145-163) and hand the frames to generate_wav."""
 import os
 import pickle
+import time
 
 import numpy
 import torch
@@ -91,6 +92,18 @@ def main(argv=None):
 
     if args.sample_one_step:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_using_input(data_tr, args.num_samples)
+    elif args.segment_frames:  # segments of one resumable plan; --stop_at_end ends after the longest utterance's segment
+        started = time.perf_counter()
+        run = parrot.decode_segments(labels_tr, labels_mask_tr, speaker_tr, args.num_samples, args.num_steps,
+                                     args.segment_frames, stop_at_end=bool(args.stop_at_end), **row_controls)
+        parts = []
+        for t0, seg in run:
+            parts.append([o.detach().cpu().numpy() for o in seg])
+            if t0 == 0:
+                print("--segment_frames %d: the first segment was on the host after %.1f ms"
+                      % (args.segment_frames, 1e3 * (time.perf_counter() - started)))
+        gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = (numpy.concatenate(p, axis=0) for p in list(zip(*parts))[:6])
+        stop_lengths = run.lengths.cpu().numpy()
     elif args.stop_at_end:  # the kernel applies the end-of-utterance rule itself and decodes no frame beyond it
         outs, stop_lengths = parrot.sample_until_end(
             labels_tr, labels_mask_tr, features_mask_tr, speaker_tr, args.num_samples, args.num_steps, **row_controls)
@@ -103,7 +116,7 @@ def main(argv=None):
     gen_x, gen_phi = gen_x.swapaxes(0, 1), gen_phi.swapaxes(0, 1)
     features_lengths = []
     for idx in range(args.num_samples):
-        if args.stop_at_end and not args.sample_one_step:
+        if (args.stop_at_end or args.segment_frames) and not args.sample_one_step:
             features_lengths.append(int(stop_lengths[idx]))
             continue
         ll = int(labels_mask_tr[idx].sum())

@@ -112,6 +112,14 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          its spread; with --parent-lib (the parent commit's libparrot_hip.so) the default plan
                                          of both libraries in the same alternation, bit identity included; the result also goes
                                          to FILE (default profiles/decode_forced.json)
+  bench_extra.py --only decode_segments [--reps N] [--segments-json FILE] [--parent-lib FILE]
+                                         resumable decode (Parrot.decode_segments, sample_model_device(return_state=True)):
+                                         configs[2] and the 2 x LSTM-1024 plan at batch 16, 1000 frames -- the plain call, the
+                                         one-piece carry call, segments of 50 and of 10 frames, N >= 3 alternations in one
+                                         process, each with its spread: total time, host time to the first segment, cost per
+                                         boundary; with --parent-lib (the parent commit's libparrot_hip.so) the plain call of
+                                         both libraries in the same alternation, bit identity included; the result also goes
+                                         to FILE (default profiles/decode_segments.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -137,7 +145,7 @@ def _arg(name, dflt=None):
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
        "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_min_p", "samplernn_forced", "samplernn_skip",
-       "decode_row_controls", "decode_forced", "mulaw")
+       "decode_row_controls", "decode_forced", "decode_segments", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1630,6 +1638,125 @@ if "decode_forced" in only:
     res["not_measured"] = ["B > 16", "the H = 1536 LSTM plan with two units per workgroup", "the launch path's timing",
                            "a GMM head with forced frames", "forcing together with the end-of-utterance stop"]
     record("decode_forced", "--forced-decode-json", res)
+
+# ---- resumable decode (parrot_sample_save_state / _load_state, Parrot.decode_segments): configs[2] (2 x GRU-1024) and
+# 2 x LSTM-1024 at batch 16, 1000 frames.  Per shape a model for the plain call, one for the one-piece carry call
+# (return_state=True), one decoding in segments of 50 frames and one in segments of 10, and, with --parent-lib, a model on the
+# parent commit's library, all alive in one process and run alternately.  A segmented run is timed from the call to the last
+# segment on the host side of the device (device idle), and to its FIRST segment (yielded and synchronised); the cost of a
+# boundary is (segmented total - one-piece carry total) / (segments - 1).
+if "decode_segments" in only:
+    import contextlib
+    import ctypes
+    from parrot_amd import _lib as plib
+    from parrot_amd.model import Parrot
+    reps = max(3, int(_arg("--reps", "5")))
+    this_lib = plib.load()
+    parent_path = _arg("--parent-lib")
+    parent_lib = None
+    if parent_path:
+        parent_lib = ctypes.CDLL(os.path.abspath(parent_path))
+        for name, (res_, args_) in plib.SIGNATURES.items():
+            if hasattr(parent_lib, name):
+                fn = getattr(parent_lib, name)
+                fn.restype = res_
+                fn.argtypes = args_
+
+    @contextlib.contextmanager
+    def under(which):  # every call of a model goes to the library that made its plan
+        plib._lib = which
+        try:
+            yield
+        finally:
+            plib._lib = this_lib
+
+    N, U, S = 16, 100, 1000
+    gen = torch.Generator().manual_seed(0)
+    lab = torch.randint(0, 43, (N, U), generator=gen)
+    lm = torch.ones(N, U)
+    shapes = {"cfg3_gru2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='gru'),
+              "lstm2_1024": dict(num_layers=2, rnn_h_dim=1024, readouts_dim=1024, cell_type='lstm')}
+    res = {"batch": N, "frames": S, "alternations": reps,
+           "timed": "call to device idle, host-side preparation included; first_segment_ms: call to the first segment "
+                    "yielded and the device idle", "shapes": {}}
+
+    def whole(m, **kw):
+        outs = m.sample_model_device(lab, lm, None, N, S, **kw)
+        torch.cuda.synchronize()
+        return (outs[0] if kw else outs)[0], None
+
+    def segmented(F):
+        def fn(m):
+            t0, first, parts = time.time(), None, []
+            for _, seg in m.decode_segments(lab, lm, None, N, S, F):
+                if first is None:
+                    torch.cuda.synchronize()
+                    first = time.time() - t0
+                parts.append(seg[0])
+            torch.cuda.synchronize()
+            return torch.cat(parts), first
+        return fn
+
+    for sname, kw in shapes.items():
+        def model(which):
+            with under(which):
+                return Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, seed=1234, **kw).initialize()
+        runs = {"plain": (model(this_lib), this_lib, whole),
+                "carry_one_piece": (model(this_lib), this_lib, lambda m: whole(m, return_state=True)),
+                "segments_50": (model(this_lib), this_lib, segmented(50)),
+                "segments_10": (model(this_lib), this_lib, segmented(10))}
+        if parent_lib is not None:
+            runs["parent_plain"] = (model(parent_lib), parent_lib, whole)
+            runs["plain_again"] = (model(this_lib), this_lib, whole)
+            runs["parent_plain_again"] = (model(parent_lib), parent_lib, whole)
+        times, firsts, frames = {k: [] for k in runs}, {k: [] for k in runs}, {}
+        keys = list(runs)
+        for rep_ in range(reps + 1):  # (the first alternation builds the plans and captures the graphs: not counted)
+            for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:
+                m, which, fn = runs[k]
+                with under(which):
+                    torch.cuda.synchronize(); t0 = time.time()
+                    x, first = fn(m)
+                    dt = time.time() - t0
+                    frames[k] = x.cpu().numpy().copy()
+                if rep_:
+                    times[k].append(1e3 * dt)
+                    if first is not None:
+                        firsts[k].append(1e3 * first)
+        machine = {}
+        for k, (m, which, _) in runs.items():
+            with under(which):
+                machine[k] = sorted(int(which.parrot_sample_is_persistent(ws['plan'])) for ws in m._sample_ws.values())
+                m.close()
+        med = lambda v: sorted(v)[len(v) // 2]
+        one = {"runs": {k: {"machine": machine[k], "total_ms": [round(x, 3) for x in times[k]], "total_ms_median": round(med(times[k]), 3),
+                            "spread_max_minus_min_ms": round(max(times[k]) - min(times[k]), 3),
+                            "us_per_step_median": round(1e3 * med(times[k]) / S, 2)} for k in runs}}
+        for k, F_ in (("segments_50", 50), ("segments_10", 10)):
+            one["runs"][k].update(first_segment_ms=[round(x, 3) for x in firsts[k]], first_segment_ms_median=round(med(firsts[k]), 3),
+                                  segments=S // F_,
+                                  us_per_boundary=round(1e3 * (med(times[k]) - med(times["carry_one_piece"])) / (S // F_ - 1), 2))
+        one["carry_minus_plain_us_per_step"] = round(1e3 * (med(times["carry_one_piece"]) - med(times["plain"])) / S, 2)
+        one["segments_equal_carry_one_piece"] = bool(np.array_equal(frames["segments_50"], frames["carry_one_piece"])
+                                                     and np.array_equal(frames["segments_10"], frames["carry_one_piece"]))
+        one["carry_frames_equal_plain"] = bool(np.array_equal(frames["carry_one_piece"], frames["plain"]))
+        if parent_lib is not None:
+            sp = lambda k: max(times[k]) - min(times[k])
+            both, gap = sp("plain") + sp("parent_plain"), med(times["plain"]) - med(times["parent_plain"])
+            one["default_path_against_parent_commit"] = {
+                "how": "this build and the parent commit's library loaded in one process, two models of each (the second pair "
+                       "created in the other order), all in the same alternation; the bar compares the first model of each "
+                       "library against the sum of their spreads (max - min over the alternations)",
+                "bit_identical": bool(np.array_equal(frames["plain"], frames["parent_plain"])),
+                "this_us_per_step": [round(1e3 * med(times[k]) / S, 2) for k in ("plain", "plain_again")],
+                "parent_us_per_step": [round(1e3 * med(times[k]) / S, 2) for k in ("parent_plain", "parent_plain_again")],
+                "this_minus_parent_us_per_step": round(1e3 * gap / S, 2),
+                "sum_of_the_two_spreads_us_per_step": round(1e3 * both / S, 2),
+                "bar_default_within_the_sum_of_both_spreads": "met" if abs(gap) <= both else "not met"}
+        res["shapes"][sname] = one
+    res["not_measured"] = ["B > 16", "the H = 1536 LSTM plan with two units per workgroup", "the launch path's timing",
+                           "StreamingDecoder: admission under load"]
+    record("decode_segments", "--segments-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
