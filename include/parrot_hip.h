@@ -1182,6 +1182,18 @@ typedef struct SampleRnnSkipStacks {
     float* big_sum; float* frm_sum;
 } SampleRnnSkipStacks;
 int samplernn_generate_set_skip_stacks(void* plan, const SampleRnnSkipStacks* skip);
+/* Conditioning frames from device memory.  src [src_rows][src_ld] (float, src_ld >= feat_dim; a decoder's frame rows have
+ * src_ld = 64) and index [rows][B] (int): device memory.  For every r < rows and b < B, features[first + r][b][0 .. feat_dim)
+ * of the plan's own `features` buffer (SampleRnnGenDesc::features) becomes src[index[r][b] * src_ld + 0 .. feat_dim), a
+ * bit-exact copy, where 0 <= index[r][b] < src_rows, and zeros otherwise: a negative entry is the documented "idle slot",
+ * and no entry, whatever it holds, makes the kernel read outside src.  Nothing outside rows first .. first + rows - 1 is
+ * written.  One launch on `stream`, ordered like any other work there: stage, then run the segment that reads the rows.
+ * Because the plan's buffer is written, every generation path sees the frames (persistent kernel, row groups, launches,
+ * resumed segments); the entry may be called at any time in a plan's life, and SampleRnnGenDesc is unchanged.
+ * PARROT_ERR_BADARG, before any device call, for a null plan, src or index, first < 0, rows < 1, first + rows > T,
+ * src_ld < feat_dim, src_rows < 1. */
+int samplernn_generate_stage_features(void* plan, const float* src, long long src_rows, int src_ld, const int* index, int first,
+                                      int rows, void* stream);
 /* 1 when the plan's sample steps run on the persistent-thread kernel. */
 int samplernn_generate_is_persistent(void* plan);
 /* Waits for the device and returns 0, or a non-zero fault code when a persistent sample kernel gave up (a team of

@@ -294,6 +294,7 @@ SIGNATURES = {
     "samplernn_generate_set_forced": (_i, [_vp, _vp]),
     "samplernn_generate_set_log_probs": (_i, [_vp, _vp]),
     "samplernn_generate_set_skip_stacks": (_i, [_vp, C.POINTER(SampleRnnSkipStacks)]),
+    "samplernn_generate_stage_features": (_i, [_vp, _vp, _ll, _i, _vp, _i, _i, _vp]),
     "samplernn_persist_floats": (C.c_longlong, [C.POINTER(SampleRnnGenDesc)]),
     "samplernn_generate_is_persistent": (_i, [_vp]),
     "samplernn_generate_persist_groups": (_i, [_vp]),

@@ -20,7 +20,7 @@ OBJDIR = os.path.join(CSRC, "build")
 ARCH = "gfx950"
 
 SOURCES = ["skinny.hip", "biggemm.hip", "attention.hip", "elementwise.hip", "quantize.hip",
-           "plans.hip", "plans_decode.hip", "capi.hip", "samplernn.hip", "persist.hip", "persist_forced.hip", "sr_persist.hip", "rowgru.hip", "trainops.hip", "readout.hip",
+           "plans.hip", "plans_decode.hip", "capi.hip", "samplernn.hip", "persist.hip", "persist_forced.hip", "sr_persist.hip", "sr_stage.hip", "rowgru.hip", "trainops.hip", "readout.hip",
            "gmmcost.hip", "labeltables.hip", "decode_state.hip"]
 EXTRA_FLAGS = {"quantize.hip": ["-ffp-contract=off"]}
 if env_str("PARROT_PM_DEPTH"):  # development: ring depth of the persistent machine's K loop

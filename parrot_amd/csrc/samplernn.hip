@@ -19,6 +19,7 @@
 #include "skinny.h"
 #include "sr_common.h"
 #include "sr_persist.h"
+#include "sr_stage.h"
 #include "switches.h"
 
 namespace {
@@ -1073,6 +1074,19 @@ int samplernn_generate_set_utterance_min_p(void* plan, const float* utt_min_p) {
     if (p->d.Q > 256) return PARROT_ERR_UNSUPPORTED;
     p->utt_min_p = utt_min_p;
     return 0;
+}
+
+// Conditioning frames from device memory into rows first .. first + rows - 1 of the plan's features (sr_stage.hip).  (The
+// argument checks in front of any HIP call: they are testable on a machine without a device.)  The descriptor declares
+// `features` const because the generation kernels only read it; the buffer is the caller's and writable.
+int samplernn_generate_stage_features(void* plan, const float* src, long long src_rows, int src_ld, const int* index, int first,
+                                      int rows, void* stream) {
+    SrPlan* p = static_cast<SrPlan*>(plan);
+    if (!p || !src || !index || first < 0 || rows < 1 || (long long)first + rows > p->d.T) return PARROT_ERR_BADARG;
+    if (src_ld < p->d.feat_dim || src_rows < 1) return PARROT_ERR_BADARG;
+    PH_ENTRY();
+    return sr_stage_features(const_cast<float*>(p->d.features), p->d.B, p->d.feat_dim, src, src_rows, src_ld, index, first, rows,
+                             (hipStream_t)stream);
 }
 
 int samplernn_generate_run(void* plan, void* stream) {

@@ -655,6 +655,30 @@ class _DecodeMixin:
         return DecodeSegments(self, labels, labels_mask, speaker, int(num_samples), int(num_steps), int(segment_frames), unif,
                               noise, seed, ctl, forced, bool(stop_at_end), int(extra), state)
 
+    def synthesize_segments(self, labels, labels_mask, speaker, num_samples, num_steps, segment_frames, stream_frames,
+                            n_streams=32, temperature=0.0, seeds=None, draw_mode='sequential', top_k=0, top_p=0.0, min_p=0.0,
+                            stop_at_end=True, extra=40, **decode_args):
+        """Text to audio for a fixed batch: decode_segments(stop_at_end=...) whose segments feed a SampleRNN
+        StreamingGenerator with open utterances (n_streams streams, segments of stream_frames frames) on the device, so the
+        vocoder runs an utterance's first frames while the decoder is at its later ones.  Iterating yields (i, samples int32
+        [80 k], done) for row i as they are produced; row i's first 80 samples are its Q/2 prefix, and its samples add up to
+        80 * max(its length, 1), the length decode_segments' end-of-utterance rule gives.  Row i is closed as soon as the rule
+        has fixed its length and the frames up to it are fed.  seeds = one per row: per-utterance draws at `temperature`
+        (StreamingGenerator(utterance_draws=True)); draw_mode, top_k, top_p, min_p: the vocoder's.  decode_args:
+        decode_segments' (the per-utterance controls, forced_frames / n_forced, unif / noise / seed).  The iteration has
+        `.decode` (the DecodeSegments: .lengths, .first), `.outs` (every segment's output tensors, on the device),
+        `.vocoder` and `.first_audio_s`.  Takes what decode_segments takes, the literal encoder included; ValueError before
+        anything runs on what either half refuses, and on output_dim != the vocoder's FEAT_DIM."""
+        F = _vocoder_feat_dim()
+        if self.output_dim != F:
+            raise ValueError(f"the vocoder is conditioned on frames of {F} floats, this model's output_dim is {self.output_dim}")
+        if seeds is not None and len(seeds) != int(num_samples):
+            raise ValueError(f"seeds needs one entry per utterance ({num_samples}), got {len(seeds)}")
+        run = self.decode_segments(labels, labels_mask, speaker, num_samples, num_steps, segment_frames,
+                                   stop_at_end=stop_at_end, extra=extra, **decode_args)
+        return SynthesisSegments(run, int(stream_frames), int(n_streams), seeds,
+                                 dict(temperature=temperature, draw_mode=draw_mode, top_k=top_k, top_p=top_p, min_p=min_p))
+
     @property
     def decode_path(self):
         """What the last decode call (sample_model*, sample_until_end*) ran on: 'machine' (the persistent phase machine), or
@@ -881,11 +905,67 @@ class DecodeSegments:
                 break
 
 
+class SynthesisSegments:
+    """The iteration Parrot.synthesize_segments returns: yields (i, samples, done); .decode, .outs, .vocoder, .first_audio_s."""
+
+    def __init__(self, run, stream_frames, n_streams, seeds, vocoder_args):
+        from .sampleRNN.generation.serving import StreamingGenerator
+        self.decode, self.outs, self.first_audio_s, self._seeds = run, [], None, seeds
+        self.vocoder = StreamingGenerator(n_streams, stream_frames, utterance_draws=seeds is not None, open_utterances=True,
+                                          max_frames=run.num_steps, store_utterances=run.num_samples, **vocoder_args)
+        self._it = self._run()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        return next(self._it)
+
+    def _feed(self, t0, frames, fed, closed):
+        """The new frames of every open row into the vocoder; a row is closed with the last frame of its length."""
+        run, S = self.decode, self.decode.num_steps
+        first = run.first.cpu().tolist()
+        for i in range(run.num_samples):
+            if closed[i]:
+                continue
+            length = S if first[i] < 0 else max(min(first[i] + run.extra, S), 1)
+            hi = min(t0 + frames.shape[0], length)
+            closed[i] = hi == length
+            self.vocoder.feed(i, frames[fed[i] - t0:hi - t0, i], last=closed[i])
+            fed[i] = hi
+
+    def _run(self):
+        import time
+        from .sampleRNN.generation.inputs import config
+        start, sg, run, prefix = time.perf_counter(), self.vocoder, self.decode, config().BIG_FRAME_SIZE
+        N = run.num_samples
+        try:
+            for i in range(N):
+                assert sg.open(**({} if self._seeds is None else dict(seed=self._seeds[i]))) == i
+            fed, closed, heard, decoding = [0] * N, [False] * N, set(), True
+            while not sg.idle():
+                while decoding and sg.short_of_segment():
+                    seg = next(run, None)
+                    decoding = seg is not None
+                    if decoding:
+                        self.outs.append(seg[1])
+                        self._feed(seg[0], seg[1][0], fed, closed)
+                assert decoding or all(closed), "the decoder ended with an utterance open"
+                for i, chunk, done in sg.step():
+                    if self.first_audio_s is None and chunk.size and (i in heard or chunk.size > prefix):
+                        self.first_audio_s = time.perf_counter() - start
+                    heard.add(i)
+                    yield i, chunk, done
+        finally:
+            sg.close()
+
+
 class StreamingDecoder:
     """Continuous admission for the decoder: `slots` utterances decode side by side on ONE carry plan of `segment_frames`
     steps; between segments a finished utterance is handed out and its slot goes to the next one queued.
       submit(labels, ...) -> id       queue one utterance (labels: 1 .. max_text label indices)
       run()                           yields (id, frames [length, O], phi [length, max_text]) as utterances end
+      run_segments()                  yields (id, t0, frames [k, O], done) per utterance in flight after every segment
     An utterance ends `extra` frames after the end-of-utterance rule first fires on its phi (segment_end_of_utterance, per
     segment, on the device), at max_frames at the latest; length is what utils.end_of_utterance gives for its full phi with
     num_steps = max_frames.  A plain boundary saves and loads the state and slices the rows' randomness and prompts.  A
@@ -913,6 +993,12 @@ class StreamingDecoder:
         self._queue, self._next_id, self._stale = collections.deque(), 0, True
         self.segments_run = self.setups_run = self.tilings_run = 0
         self.placements = {}   # id -> (slot, the segment it was admitted in front of)
+        self._rows = []        # the utterances in flight, per slot, of the loop that is running
+
+    @property
+    def busy(self):
+        """Whether an utterance is queued or in flight: whether another segment would decode anything."""
+        return bool(self._queue) or any(r is not None for r in self._rows)
 
     def refresh_parameters(self):
         """The parameters were written behind torch's back (a fused optimiser step): tile the weights again at the next boundary."""
@@ -983,6 +1069,20 @@ class StreamingDecoder:
     def run(self):
         """Decodes everything queued (utterances submitted while it runs included); yields (id, frames [length, O],
         phi [length, max_text]) -- device tensors -- as each utterance ends."""
+        for batch in self._segments(False, True):
+            yield from batch
+
+    def run_segments(self, with_phi=False):
+        """run(), handing the frames out as they are decoded: after every segment yields, for each utterance in flight,
+        (id, t0, frames [k, O], done) -- the new device frames t0 .. t0 + k - 1 (k = segment_frames; in the utterance's last
+        yield, done=True, they are trimmed so that the total is its length, run()'s rule: first + extra, at most
+        max_frames).  with_phi=True: (id, t0, frames, phi [k, max_text], done).  Concatenated per id the frames (and phi) are
+        run()'s, bit for bit."""
+        for batch in self._segments(True, with_phi):
+            yield from batch
+
+    def _segments(self, per_segment, with_phi):
+        """The loop behind run() and run_segments(): one list per decoder segment of what they yield for it."""
         from .utils import end_of_utterance_args
         m, N, F, U, T, O = self._m, self.slots, self.segment_frames, self.max_text, self.max_frames, self._m.output_dim
         m.allocate()
@@ -996,7 +1096,7 @@ class StreamingDecoder:
                     sharpening=numpy.full(N, m.sharpening_coeff, dtype=numpy.float32),
                     bias=numpy.full(N, m.sampling_bias, dtype=numpy.float32) if gmm else None)
         host['mask'][:, 0] = 1.   # idle slots: a one-character dummy
-        rows = [None] * N
+        rows = self._rows = [None] * N
         state = m.initial_decode_state(N)
         pos = ncmp = None
         version = None
@@ -1043,13 +1143,122 @@ class StreamingDecoder:
             sx, phi = outs[0].clone(), outs[4].clone()
             first = torch.tensor([-1 if r is None else r['first'] for r in rows], device=dev, dtype=torch.long)
             first = segment_end_of_utterance(phi, pos, ncmp, first, torch.from_numpy(t0)).cpu().tolist()
+            batch = []
             for b, r in enumerate(rows):
                 if r is None:
                     continue
-                r['frames'].append(sx[:, b])
-                r['phi'].append(phi[:, b])
-                r['first'], r['t'] = first[b], r['t'] + F
+                t_seg = r['t']
+                r['first'], r['t'] = first[b], t_seg + F
                 length = T if r['first'] < 0 else min(r['first'] + self.extra, T)
-                if r['t'] >= length:
+                done = r['t'] >= length
+                if per_segment:
+                    k = max(0, min(F, length - t_seg)) if done else F
+                    batch.append((r['id'], t_seg, sx[:k, b]) + ((phi[:k, b],) if with_phi else ()) + (done,))
+                else:
+                    r['frames'].append(sx[:, b])
+                    r['phi'].append(phi[:, b])
+                    if done:
+                        batch.append((r['id'], torch.cat(r['frames'])[:length], torch.cat(r['phi'])[:length]))
+                if done:
                     rows[b] = None
-                    yield r['id'], torch.cat(r['frames'])[:length], torch.cat(r['phi'])[:length]
+            yield batch
+
+
+def _vocoder_feat_dim():
+    from .sampleRNN.generation.inputs import config
+    return config().FEAT_DIM
+
+
+class TextToAudio:
+    """Text to audio in one stream: a StreamingDecoder (`.decoder`) whose segments feed a SampleRNN StreamingGenerator with
+    open utterances (`.vocoder`), so the audio of an utterance's first frames is out while its later frames are decoded.
+      submit(labels, ...) -> id       StreamingDecoder.submit's arguments, and seed= / temperature= / top_k= / top_p= /
+                                      min_p= of the vocoder's draws (StreamingGenerator.open's rules); the seed of a GMM
+                                      head's own randomness, StreamingDecoder.submit's seed=, is decoder_seed= here
+      run()                           yields (id, samples int32 [80 k], done) as they are produced; an utterance's first 80
+                                      samples are its Q/2 prefix
+    A decoded segment is copied on the device into the vocoder's frame store and fed as device tensors: no frame visits the
+    host.  The policy is deterministic: before each vocoder step, decoder segments run until no utterance the vocoder is
+    running or would place next is short of a full vocoder segment, or every such utterance is closed, or the decoder has
+    nothing in flight; then one vocoder step runs.  A text enters the decoder only while the vocoder's store has a free row
+    (pool_utterances rows, default decoder_slots + vocoder_streams; a row frees when the vocoder reports its utterance
+    done).  `.decoder.placements[id]` and `.vocoder.record[.tickets[id]]` say where each utterance ran: its samples are those of the
+    vocoder's standalone run, in that stream, of the frames Parrot.decode_segments gives it in that slot (temperature 0,
+    or utterance_draws=True).  `.first_audio_s`: seconds from run()'s start to the first chunk that holds samples behind a
+    prefix.  Refuses what its two halves refuse -- the literal encoder among them -- and a model whose output_dim is not
+    the vocoder's FEAT_DIM."""
+
+    def __init__(self, parrot, decoder_slots, decoder_segment_frames, max_text, max_frames, vocoder_streams,
+                 vocoder_segment_frames, extra=40, pool_utterances=None, temperature=0.0, utterance_draws=False,
+                 draw_mode='sequential', top_k=0, top_p=0.0, min_p=0.0, run_segment=None):
+        import collections
+        F = _vocoder_feat_dim()
+        if parrot.output_dim != F:
+            raise ValueError(f"the vocoder is conditioned on frames of {F} floats, this model's output_dim is {parrot.output_dim}")
+        self.decoder = StreamingDecoder(parrot, decoder_slots, decoder_segment_frames, max_text, max_frames, extra=extra)
+        pool = int(decoder_slots) + int(vocoder_streams) if pool_utterances is None else int(pool_utterances)
+        if pool < 1:
+            raise ValueError(f"pool_utterances must be >= 1, got {pool_utterances}")
+        from .sampleRNN.generation.serving import StreamingGenerator
+        self.vocoder = StreamingGenerator(vocoder_streams, vocoder_segment_frames, temperature=temperature,
+                                          utterance_draws=utterance_draws, draw_mode=draw_mode, top_k=top_k, top_p=top_p,
+                                          min_p=min_p, open_utterances=True, max_frames=max_frames, store_utterances=pool,
+                                          run_segment=run_segment)
+        self._pending = collections.deque()   # (the decoder's queue entry, the vocoder's draw arguments): not yet admitted
+        self.tickets, self._uid = {}, {}      # id -> the vocoder's ticket (kept), and back from admission until done
+        self._segments = None
+        self.first_audio_s = None
+
+    def submit(self, labels, speaker=None, seed=None, temperature=None, top_k=None, top_p=None, min_p=None,
+               decoder_seed=None, **decoder_args):
+        draws = dict(seed=seed, temperature=temperature, top_k=top_k, top_p=top_p, min_p=min_p)
+        self.vocoder._check_draws(**draws)
+        uid = self.decoder.submit(labels, speaker=speaker, seed=decoder_seed, **decoder_args)
+        self._pending.append((self.decoder._queue.pop(), draws))  # (held back until a store row is free)
+        return uid
+
+    def _admit(self):
+        while self._pending and self.vocoder.free_rows:
+            u, draws = self._pending.popleft()
+            ticket = self.vocoder.open(**draws)
+            self.tickets[u['id']], self._uid[ticket] = ticket, u['id']
+            self.decoder._queue.append(u)
+
+    def _decode_segment(self):
+        """One decoder segment, its frames fed to the vocoder; False when the decoder has nothing to decode."""
+        if not self.decoder.busy:
+            return False
+        if self._segments is None:
+            self._segments = self.decoder._segments(True, False)
+        batch = next(self._segments, None)
+        if batch is None:  # (the loop had ended before these texts were admitted: a new one)
+            self._segments = self.decoder._segments(True, False)
+            batch = next(self._segments)
+        for uid, t0, frames, done in batch:
+            self.vocoder.feed(self.tickets[uid], frames, last=done)
+        return True
+
+    def close(self):
+        self.vocoder.close()
+
+    def run(self):
+        """Runs everything submitted (texts submitted while it runs included); yields (id, samples int32 [80 k], done)."""
+        import time
+        from .sampleRNN.generation.inputs import config
+        start, heard, prefix = time.perf_counter(), set(), config().BIG_FRAME_SIZE
+        self.first_audio_s = None
+        while self._pending or self.decoder.busy or not self.vocoder.idle():
+            self._admit()
+            while self.vocoder.short_of_segment() and self._decode_segment():
+                pass
+            chunks = self.vocoder.step()
+            if not chunks and self.vocoder.starved is not None:
+                raise RuntimeError("the vocoder starves with nothing left to decode: " + self.vocoder.starved)
+            for ticket, chunk, done in chunks:
+                uid = self._uid[ticket]
+                if self.first_audio_s is None and chunk.size and (uid in heard or chunk.size > prefix):
+                    self.first_audio_s = time.perf_counter() - start
+                heard.add(uid)
+                if done:
+                    del self._uid[ticket]
+                yield uid, chunk, done

@@ -262,8 +262,8 @@ class DeviceGenerator:
         _lib.call('samplernn_generate_set_utterance_top_p', self.plan, self.ws['utt_top_p'].data_ptr())
         _lib.call('samplernn_generate_set_utterance_min_p', self.plan, self.ws['utt_min_p'].data_ptr())
 
-    def generate(self, features, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None,
-                 top_ps=None, forced=None, min_ps=None):
+    def generate(self, features=None, starts=None, resume=False, n_frames=None, seeds=None, temperatures=None, top_ks=None,
+                 top_ps=None, forced=None, min_ps=None, gather=None):
         """features [T, B, 63] time-major (what generate_and_save_samples receives) -> samples [B, 80*T] int32.
         starts [T, B] (packed plans only, and required there): non-zero where stream b begins a new utterance at big
         frame f, whose Q/2 prefix is slot f - 1.
@@ -298,6 +298,14 @@ class DeviceGenerator:
         [B, 80 k] for a segment that resumes.  A code in 0 .. Q_LEVELS-1 is the sample of that step; -1: the step picks.
         Another shape, a non-integer dtype or any other value: ValueError, before anything is staged.
 
+        gather=(src, index), in place of `features` (exactly one of the two): the rows `features` would have held are
+        gathered on the device (samplernn_generate_stage_features) from src, a float32 tensor [R, ld] on the plan's device
+        with ld >= 63 and unit column stride (its first 63 columns are the frame), through index, an int32 array [rows, B]
+        with the `rows` of this call (T, k + 1 or k): row index[r][b] of src, or zeros where the entry is negative (an idle
+        slot) or >= R.  No frame visits the host; everything else about the call is what it is with `features`.  Another
+        shape or dtype, a src on another device or narrower than 63, both or neither of features and gather: ValueError,
+        before anything is staged.
+
         A plan built with log_probs=True returns (samples, logp): logp float32, sliced like samples and, like them, a
         copy when the run is in segments.  A plan built with draw_stats=True returns (samples[, logp], draw_logp, kept),
         sliced and copied the same way."""
@@ -306,7 +314,9 @@ class DeviceGenerator:
             raise ValueError("forced must be given exactly when the plan was built with forcing=True")
         if forced is not None:  # (its values and shape before anything is staged on the device)
             forced = forced_array(forced, (self.B, config().BIG_FRAME_SIZE * rows))
-        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks, top_ps, min_ps)
+        if gather is not None or features is None:
+            gather = self._check_gather(features, gather, rows)
+        self._stage(features, starts, seeds, temperatures, segment, rows, first, top_ks, top_ps, min_ps, gather)
         BFS = config().BIG_FRAME_SIZE
         if forced is not None:
             fo = self.ws['forced']
@@ -353,11 +363,36 @@ class DeviceGenerator:
             min_p_code(min_ps) if numpy.ndim(min_ps) == 0 else min_p_array(min_ps, (rows, self.B) if self.packed else (self.B,))
         return resume or n_frames is not None, resume, k, rows, 1 if resume else 0
 
-    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None, top_ps=None, min_ps=None):
-        """Checks the arrays' shapes and copies them into rows first .. first + rows - 1 of the workspace."""
+    def _check_gather(self, features, gather, rows):
+        """gather=(src, index) of generate as (src, index int32 [rows, B]); ValueError on anything the staging entry cannot
+        take, and on both or neither of features and gather."""
+        if (features is None) == (gather is None):
+            raise ValueError("exactly one of features and gather=(src, index) must be given")
+        F = config().FEAT_DIM
+        try:
+            src, index = gather
+        except (TypeError, ValueError):
+            raise ValueError("gather must be (src, index)") from None
+        dev = self.ws['features'].device
+        if not torch.is_tensor(src) or src.dtype != torch.float32 or src.dim() != 2 or src.shape[0] < 1:
+            raise ValueError("gather's src must be a float32 tensor [R, ld] with R >= 1")
+        if src.shape[1] < F or src.stride(1) != 1 or src.stride(0) < src.shape[1]:
+            raise ValueError("gather's src needs rows of ld >= %d floats with unit column stride, got shape %s, strides %s"
+                             % (F, tuple(src.shape), tuple(src.stride())))
+        if src.device != dev:
+            raise ValueError("gather's src lives on %s, the plan on %s" % (src.device, dev))
+        index = numpy.asarray(index)
+        if index.dtype != numpy.int32 or index.shape != (rows, self.B):
+            raise ValueError("gather's index must be int32 [%d, %d], got %s %s" % (rows, self.B, index.dtype, index.shape))
+        return src, numpy.ascontiguousarray(index)
+
+    def _stage(self, features, starts, seeds, temperatures, segment, rows, first, top_ks=None, top_ps=None, min_ps=None,
+               gather=None):
+        """Checks the arrays' shapes and copies them into rows first .. first + rows - 1 of the workspace (gather: the
+        features by samplernn_generate_stage_features, from device memory)."""
         ws = self.ws
-        feats = torch.as_tensor(features)
-        if segment and (feats.dim() != 3 or tuple(feats.shape[:2]) != (rows, self.B)):
+        feats = None if gather is not None else torch.as_tensor(features)
+        if feats is not None and segment and (feats.dim() != 3 or tuple(feats.shape[:2]) != (rows, self.B)):
             raise ValueError("features must be [%d, %d, %d], got %s" % (rows, self.B, config().FEAT_DIM, tuple(feats.shape)))
         if self.packed:
             st = torch.as_tensor(numpy.asarray(starts))
@@ -391,6 +426,12 @@ class DeviceGenerator:
             ws['utt_top_k'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tk).reshape(hi - lo, self.B)).to(ws['utt_top_k'].device))
             ws['utt_seed'][lo:hi].copy_(torch.from_numpy(sd.reshape(hi - lo, self.B)).to(ws['utt_seed'].device))
             ws['utt_temp'][lo:hi].copy_(torch.from_numpy(numpy.ascontiguousarray(tp).reshape(hi - lo, self.B)).to(ws['utt_temp'].device))
+        if gather is not None:
+            src, index = gather
+            index = torch.from_numpy(index).to(ws['features'].device)
+            _lib.call('samplernn_generate_stage_features', self.plan, src.data_ptr(), src.shape[0], src.stride(0),
+                      index.data_ptr(), first, rows, hip._stream())
+            return
         ws['features'][first:first + rows].copy_(feats.to(ws['features'].device, torch.float32))
 
     def _launch(self, segment, resume, k):

@@ -1,6 +1,7 @@
 """Entry points on top of the device plan: a list of utterances packed into one run (generate_packed), a rectangle in
 segments on a ring (generate_stream) and continuous admission on a plan that never ends (StreamingGenerator)."""
 import numpy
+import torch
 
 from .device import DeviceGenerator, device_loop_guard
 from .inputs import (FREE, _per_utterance, _per_utterance_min_p, _per_utterance_prompts, _per_utterance_top_k,
@@ -197,12 +198,38 @@ class StreamingGenerator:
     (ticket, chunk, logp_chunk, done) -- logp_chunk aligned with chunk, zeros on the prefix slot.  A generator in which no
     utterance has a prompt and log_probs is off calls run_segment exactly as before.  forcing=True builds the generator's own
     device plan so that it takes prompts (DeviceGenerator(forcing=True)), which a plan cannot learn once it has run: on the
-    device, submit refuses a prompt without it; a plan built without it runs the kernels it always ran."""
+    device, submit refuses a prompt without it; a plan built without it runs the kernels it always ran.
+
+    open_utterances=True: utterances whose frames arrive while they run.  open(...) -> ticket opens one, feed(ticket,
+    frames [k, 63], last=False) appends frames (a numpy array is uploaded once, at feed time; a float32 tensor on the plan's
+    device, row stride 63 or 64, stays there), last=True or close(ticket) ends it; submit(features, ...) is open, one feed
+    and the close.  The frames live in a store of the generator's, on the plan's device: store_utterances rows (default:
+    2 n_streams) of max_frames frames of 64 floats; an utterance holds a row from open() until it is reported done, open()
+    raises RuntimeError while none is free (free_rows) and feed ValueError when the row would overflow.  step() hands the
+    plan an index table into the store (DeviceGenerator.generate(gather=)), so no frame visits the host; a run_segment of
+    the caller's gets the gathered host array, as before.  Prompts and log_probs are for submit only.  The schedule:
+      1. no slot runs a frame that has not been fed;
+      2. a stream never idles inside an utterance: a segment is cut to the frames every unfinished open utterance placed
+         in it can supply, and while some running open utterance has nothing new no segment runs -- step() returns [] (or
+         only the reports of rule 5) and `starved` says why (None after a step that was not starved);
+      3. an utterance is placed only once its frame 0, the prefix slot, has been fed (a later one that has it goes first);
+      4. when every utterance is closed before its first placement the placements are schedule_segment's;
+      5. an utterance closed after all its frames were placed is reported done by the next step() with an empty chunk;
+      6. once every open utterance is closed drain() terminates (while one starves it raises RuntimeError).
+    It is schedule_segment on a shortened segment, with the length of an utterance whose end is unknown one past what has
+    been fed.  At temperature 0, or with utterance_draws=True, the concatenated chunks of an utterance are bit for bit those
+    of submit() of its whole features, whatever the feeds were and whenever they came."""
 
     def __init__(self, n_streams, segment_frames, temperature=0.0, seed=234, use_graph=True, run_segment=None,
                  utterance_draws=False, draw_mode='sequential', top_k=0, top_p=0.0, log_probs=False, forcing=False,
-                 min_p=0.0):
+                 min_p=0.0, open_utterances=False, max_frames=1024, store_utterances=None):
         device_loop_guard(draw_mode, top_k, top_p, min_p)
+        self.open_utterances = bool(open_utterances)
+        if self.open_utterances:
+            self.max_frames = int(max_frames)
+            n_rows = 2 * int(n_streams) if store_utterances is None else int(store_utterances)
+            if self.max_frames < 1 or n_rows < 1:
+                raise ValueError("max_frames and store_utterances must be at least 1")
         self.log_probs = bool(log_probs)
         self.forcing = bool(forcing)   # the generator's own device plan takes prompts (a runner of the caller's always may)
         self._forcing = False          # some utterance was submitted with a prompt
@@ -239,9 +266,29 @@ class StreamingGenerator:
         self._min_ps = {}              # ticket -> min_p, likewise
         self._prompts = {}             # ticket -> its prompt, until the utterance is done
         self.record = {}
+        self._starved = None
+        if self.open_utterances:
+            # the frame store, [store row * max_frames + frame][64]: on the plan's device, or on the host for a runner of
+            # the caller's; ticket -> {row, fed, closed} from open() until the utterance is reported done
+            if self.gen is not None:
+                self._store = torch.zeros(n_rows * self.max_frames, 64, device=self.gen.ws['features'].device)
+            else:
+                self._store = numpy.zeros((n_rows * self.max_frames, 64), dtype='float32')
+            self._free_rows = list(range(n_rows))
+            self._open = {}
+
+    @property
+    def starved(self):
+        """Why the last step() ran no segment although utterances are waiting (a string), or None."""
+        return self._starved
+
+    @property
+    def free_rows(self):
+        """Store rows no utterance holds: how many more open() will take (open_utterances=True)."""
+        return len(self._free_rows) if self.open_utterances else 0
 
     def _run_on_device(self, features, starts, resume, seeds=None, temperatures=None, top_ks=None, top_ps=None, forced=None,
-                       min_ps=None):
+                       min_ps=None, index=None):
         # (without utterance_draws the plan has no entries: every utterance draws with the plan's top_k)
         draws = {} if seeds is None else dict(seeds=seeds, temperatures=temperatures)
         if seeds is not None and top_ks is not None:
@@ -250,27 +297,29 @@ class StreamingGenerator:
             draws['top_ps'] = top_ps
         if seeds is not None and min_ps is not None:
             draws['min_ps'] = min_ps
-        n, BFS = features.shape[0], config().BIG_FRAME_SIZE
+        n, BFS = starts.shape[0], config().BIG_FRAME_SIZE
         # (a plan built to take forced samples is handed them in every call: all free until some utterance has a prompt)
         if self.forcing and forced is None:
             forced = numpy.full((self.B, BFS * n), FREE, dtype=numpy.int32)
         more = {} if forced is None else dict(forced=forced)
         host = lambda out, cut: tuple(o.cpu().numpy()[:, cut:] for o in out) if self.log_probs else out.cpu().numpy()[:, cut:]
+        if index is not None:  # (open utterances: the frames are gathered from the store on the device; -1 = an idle slot)
+            if not resume:
+                index = numpy.concatenate([numpy.full_like(index[:1], -1), index])
+            more['gather'] = (self._store, index)
         if resume:
             return host(self.gen.generate(features, starts, resume=True, n_frames=n, **more, **draws), 0)
         # the first segment: slot 0 is the run's prefix slot, no stream uses it
-        features = numpy.concatenate([numpy.zeros_like(features[:1]), features])
+        if features is not None:
+            features = numpy.concatenate([numpy.zeros_like(features[:1]), features])
         starts = numpy.concatenate([numpy.zeros_like(starts[:1]), starts])
         draws = {k: numpy.concatenate([numpy.zeros_like(v[:1]), v]) for k, v in draws.items()}
         if forced is not None:
             more['forced'] = numpy.concatenate([numpy.full((self.B, BFS), FREE, dtype=numpy.int32), forced], axis=1)
         return host(self.gen.generate(features, starts, n_frames=n, **more, **draws), BFS)
 
-    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None, prompt=None, min_p=None):
-        """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
-        seed (an unsigned 64-bit integer), temperature, top_k, top_p and min_p (defaults: the generator's): with
-        utterance_draws=True only, where the seed is required.  prompt: up to 80 * (n - 1) integer codes in
-        0 .. Q_LEVELS-1, the utterance's samples 80 ..: it goes on freely behind them."""
+    def _check_draws(self, seed, temperature, top_k, top_p, min_p):
+        """What submit and open refuse about an utterance's draw arguments; returns the codes of (top_k, top_p, min_p)."""
         if (seed is not None) != self.utterance_draws or (temperature is not None and not self.utterance_draws):
             raise ValueError("a seed (and a temperature) per utterance is given exactly when the generator was built with "
                              "utterance_draws=True")
@@ -286,13 +335,10 @@ class StreamingGenerator:
             raise ValueError("a min_p per utterance needs a generator built with utterance_draws=True")
         if min_p is not None:
             min_p = min_p_code(min_p)
-        features = numpy.asarray(features, dtype='float32')
-        if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
-            raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
-        if prompt is not None:
-            if self.gen is not None and not self.forcing:
-                raise ValueError("a prompt needs a generator built with forcing=True: its device plan is built to take them")
-            prompt = _per_utterance_prompts([prompt], [features.shape[0]])[0]
+        return top_k, top_p, min_p
+
+    def _ticket(self, seed, temperature, top_k, top_p, min_p, prompt=None):
+        """The next ticket, with the (checked) draw arguments and prompt of its utterance on record."""
         ticket = self._next_ticket
         self._next_ticket += 1
         if prompt is not None:
@@ -306,25 +352,192 @@ class StreamingGenerator:
             self._nucleus = self._nucleus or top_p is not None
             self._min_ps[ticket] = self.min_p if min_p is None else min_p
             self._min_p = self._min_p or min_p is not None
+        return ticket
+
+    def submit(self, features, seed=None, temperature=None, top_k=None, top_p=None, prompt=None, min_p=None):
+        """features [n, 63], n >= 1 (frame 0 is the prefix slot) -> the utterance's ticket, numbered in submission order.
+        seed (an unsigned 64-bit integer), temperature, top_k, top_p and min_p (defaults: the generator's): with
+        utterance_draws=True only, where the seed is required.  prompt: up to 80 * (n - 1) integer codes in
+        0 .. Q_LEVELS-1, the utterance's samples 80 ..: it goes on freely behind them."""
+        top_k, top_p, min_p = self._check_draws(seed, temperature, top_k, top_p, min_p)
+        features = numpy.asarray(features, dtype='float32')
+        if features.ndim != 2 or features.shape[0] < 1 or features.shape[1] != config().FEAT_DIM:
+            raise ValueError("an utterance is [n, %d] conditioning frames with n >= 1, got %s" % (config().FEAT_DIM, features.shape))
+        if prompt is not None:
+            if self.gen is not None and not self.forcing:
+                raise ValueError("a prompt needs a generator built with forcing=True: its device plan is built to take them")
+            prompt = _per_utterance_prompts([prompt], [features.shape[0]])[0]
+        if self.open_utterances:  # open, one feed, close -- refused as a whole where either would be
+            if features.shape[0] > self.max_frames:
+                raise ValueError("an utterance of %d frames overflows a store row of max_frames = %d"
+                                 % (features.shape[0], self.max_frames))
+            ticket = self._open_ticket(seed, temperature, top_k, top_p, min_p, prompt)
+            self.feed(ticket, features, last=True)
+            return ticket
+        ticket = self._ticket(seed, temperature, top_k, top_p, min_p, prompt)
         self._features[ticket] = features
         self.queue.append((ticket, features.shape[0]))
         return ticket
 
+    def _need_open(self):
+        if not self.open_utterances:
+            raise ValueError("open, feed and close need a generator built with open_utterances=True")
+
+    def _open_ticket(self, seed, temperature, top_k, top_p, min_p, prompt=None):
+        if not self._free_rows:
+            raise RuntimeError("every row of the frame store holds an utterance (store_utterances = %d): wait for one to be "
+                               "reported done" % (self._store.shape[0] // self.max_frames))
+        ticket = self._ticket(seed, temperature, top_k, top_p, min_p, prompt)
+        self._open[ticket] = dict(row=self._free_rows.pop(0), fed=0, closed=False)
+        self.queue.append((ticket, None))  # (its length is read from the record above at every step)
+        return ticket
+
+    def open(self, seed=None, temperature=None, top_k=None, top_p=None, min_p=None):
+        """Opens an utterance whose frames arrive through feed() -> its ticket.  The draw arguments follow submit's rules."""
+        self._need_open()
+        if self.log_probs:
+            raise ValueError("log_probs are handed out for submitted utterances only, not for open ones")
+        return self._open_ticket(seed, temperature, *self._check_draws(seed, temperature, top_k, top_p, min_p))
+
+    def feed(self, ticket, frames, last=False):
+        """Appends frames [k, 63], k >= 0, to an open utterance: a numpy array (uploaded now), or a float32 tensor on the
+        plan's device with row stride 63 or 64 (copied on the device).  last=True closes the utterance: its length is then
+        known, and it needs at least its frame 0.  ValueError on another shape, an unknown or closed ticket, and when the
+        utterance's store row (max_frames) would overflow; nothing is stored then."""
+        self._need_open()
+        u = self._open.get(ticket)
+        if u is None or u['closed']:
+            raise ValueError("ticket %r is not an open utterance" % (ticket,))
+        F = config().FEAT_DIM
+        if torch.is_tensor(frames):
+            if frames.dtype != torch.float32:
+                raise ValueError("frames on the device must be float32, got %s" % frames.dtype)
+            if isinstance(self._store, numpy.ndarray) or frames.device.type == 'cpu':  # (taken like an array)
+                frames = frames.detach().cpu().numpy()
+            elif frames.device != self._store.device:
+                raise ValueError("frames live on %s, the plan on %s" % (frames.device, self._store.device))
+        if not torch.is_tensor(frames):
+            frames = numpy.asarray(frames, dtype='float32')
+        if frames.ndim != 2 or frames.shape[1] != F:
+            raise ValueError("frames are [k, %d], got %s" % (F, tuple(frames.shape)))
+        k = int(frames.shape[0])
+        if u['fed'] + k > self.max_frames:
+            raise ValueError("%d more frames overflow the utterance's store row: %d fed, max_frames = %d"
+                             % (k, u['fed'], self.max_frames))
+        if last and u['fed'] + k < 1:
+            raise ValueError("every utterance needs at least one frame (its prefix slot)")
+        if k:
+            lo = u['row'] * self.max_frames + u['fed']
+            if isinstance(self._store, numpy.ndarray):
+                self._store[lo:lo + k, :F] = frames
+            else:
+                if not torch.is_tensor(frames):
+                    frames = torch.from_numpy(numpy.ascontiguousarray(frames))
+                self._store[lo:lo + k, :F].copy_(frames)
+            u['fed'] += k
+        u['closed'] = bool(last)
+
+    def close(self, ticket=None):
+        """close(ticket): feed with no frames and last=True.  close(): releases the generator's device plan."""
+        if ticket is not None:
+            return self.feed(ticket, numpy.zeros((0, config().FEAT_DIM), dtype='float32'), last=True)
+        if self.gen is not None:
+            self.gen.close()
+            self.gen = None
+
     def idle(self):
         return not self.queue and all(r is None for r in self.running)
+
+    def short_of_segment(self):
+        """Whether some open utterance that is running, or that the next step could place (the oldest queued ones, one per
+        idle stream), has not been closed and holds fewer unplaced frames than a full segment: feeding it first lets the
+        next step run longer, or at all."""
+        self._need_open()
+        short = lambda t, placed: not self._open[t]['closed'] and self._open[t]['fed'] - placed < self.S
+        if any(r is not None and short(r[0], r[1]) for r in self.running):
+            return True
+        n_idle = sum(r is None for r in self.running)
+        return any(short(t, 0) for t, _ in self.queue[:n_idle])
 
     def step(self):
         """Runs one segment; returns [(ticket, chunk int32 [80 k], done)] for every utterance that had slots in it --
         (ticket, chunk, logp_chunk float32 [80 k], done) with log_probs=True."""
+        if self.open_utterances:
+            return self._step_open()
         placements, starts, n, self.running, self.queue = schedule_segment(self.running, self.queue, self.B, self.S)
         if n == 0:
             return []
-        tt = config()
-        BFS = tt.BIG_FRAME_SIZE
-        feats = numpy.zeros((n, self.B, tt.FEAT_DIM), dtype='float32')
-        flags = numpy.zeros((n, self.B), dtype='int32')
+        feats = numpy.zeros((n, self.B, config().FEAT_DIM), dtype='float32')
         for ticket, b, slot, frame, count in placements:
             feats[slot - 1:slot - 1 + count, b] = self._features[ticket][frame:frame + count]
+        return self._run_placements(placements, starts, n, feats, None,
+                                    lambda ticket, placed: placed == self._features[ticket].shape[0])
+
+    def _step_open(self):
+        """step() with open utterances: the rules of the class's docstring."""
+        self._starved = None
+        out, S = [], self.S
+        length = lambda t: self._open[t]['fed'] + (not self._open[t]['closed'])  # (end unknown: one past what has been fed)
+        running = []
+        for b, r in enumerate(self.running):
+            if r is not None and self._open[r[0]]['closed'] and r[1] == self._open[r[0]]['fed']:  # rule 5
+                empty = numpy.zeros(0, dtype='int32')
+                out.append((r[0], empty, numpy.zeros(0, dtype='float32'), True) if self.log_probs else (r[0], empty, True))
+                self._forget(r[0])
+                r = self.running[b] = None
+            running.append(None if r is None else (r[0], r[1], length(r[0])))
+        for r in running:
+            if r is not None and r[1] == self._open[r[0]]['fed']:  # rule 2: (not closed, or rule 5 had taken it)
+                self._starved = "utterance %d has run all %d frames it was fed and is not closed" % (r[0], r[1])
+                return out
+        queue = [(t, length(t)) for t, _ in self.queue if self._open[t]['fed'] >= 1]  # rule 3
+        while True:  # rules 1 and 2: no open utterance may reach the length it was lent, so it ends at the segment's last slot
+            placements, starts, n, running_after, _ = schedule_segment(running, queue, self.B, S)
+            cut = S
+            for ticket, b, slot, frame, count in placements:
+                u = self._open[ticket]
+                if not u['closed'] and frame + count > u['fed']:
+                    cut = min(cut, slot + (u['fed'] - frame) - 1)
+            if cut == S:
+                break
+            S = cut
+        if n == 0:
+            if self.queue:
+                self._starved = "no queued utterance has been fed its frame 0"
+            return out
+        placed = set(p[0] for p in placements)
+        self.running = running_after
+        self.queue = [q for q in self.queue if q[0] not in placed]
+        index = numpy.full((n, self.B), -1, dtype=numpy.int32)
+        for ticket, b, slot, frame, count in placements:
+            lo = self._open[ticket]['row'] * self.max_frames + frame
+            index[slot - 1:slot - 1 + count, b] = numpy.arange(lo, lo + count)
+        feats = None
+        if self.gen is None:  # a runner of the caller's: the gathered host array
+            feats = numpy.where((index >= 0)[:, :, None], self._store[numpy.maximum(index, 0), :config().FEAT_DIM], 0.)
+            feats = feats.astype('float32')
+        return out + self._run_placements(placements, starts, n, feats, index if self.gen is not None else None,
+                                          lambda t, n_placed: self._open[t]['closed'] and n_placed == self._open[t]['fed'])
+
+    def _forget(self, ticket):
+        """Drops what the generator holds for an utterance that is done; its store row is free again."""
+        self._features.pop(ticket, None)
+        self._draws.pop(ticket, None)
+        self._top_ks.pop(ticket, None)
+        self._top_ps.pop(ticket, None)
+        self._min_ps.pop(ticket, None)
+        self._prompts.pop(ticket, None)
+        if self.open_utterances:
+            self._free_rows.append(self._open.pop(ticket)['row'])
+            self._free_rows.sort()
+
+    def _run_placements(self, placements, starts, n, feats, index, finished):
+        """Runs the segment schedule_segment laid out -- feats [n, B, 63], or on the device index [n, B] into the frame
+        store -- and cuts its samples into the utterances' chunks; finished(ticket, frames placed) says who is done."""
+        tt = config()
+        BFS = tt.BIG_FRAME_SIZE
+        flags = numpy.zeros((n, self.B), dtype='int32')
+        for ticket, b, slot, frame, count in placements:
             if frame == 0:
                 self.record[ticket] = (b, self._slots_run + slot)
         for slot, b in starts:
@@ -365,6 +578,8 @@ class StreamingGenerator:
                 if lo < hi:
                     col = BFS * (slot - 1) - BFS * frame
                     draws['forced'][b, col + lo:col + hi] = p[lo - BFS:hi - BFS]
+        if index is not None:
+            draws['index'] = index
         got = self._run(feats, flags, self._resume, **draws)
         logp = None
         if self.log_probs:
@@ -383,14 +598,9 @@ class StreamingGenerator:
             chunk = numpy.array(samples[b, BFS * (slot - 1):BFS * (slot - 1 + count)], dtype='int32')
             if frame == 0:
                 chunk[:BFS] = tt.Q_ZERO  # (the period that would write it may lie in the next segment)
-            done = frame + count == self._features[ticket].shape[0]
+            done = finished(ticket, frame + count)
             if done:
-                del self._features[ticket]
-                self._draws.pop(ticket, None)
-                self._top_ks.pop(ticket, None)
-                self._top_ps.pop(ticket, None)
-                self._min_ps.pop(ticket, None)
-                self._prompts.pop(ticket, None)
+                self._forget(ticket)
             if logp is None:
                 out.append((ticket, chunk, done))
                 continue
@@ -401,13 +611,11 @@ class StreamingGenerator:
         return out
 
     def drain(self):
-        """Steps until nothing is queued or running; returns the chunks of all those steps in order."""
+        """Steps until nothing is queued or running; returns the chunks of all those steps in order.  (Open utterances:
+        RuntimeError when a step starves -- an utterance that is not closed waits for frames nobody can feed here.)"""
         out = []
         while not self.idle():
             out += self.step()
+            if self._starved is not None:
+                raise RuntimeError("drain() cannot go on: " + self._starved)
         return out
-
-    def close(self):
-        if self.gen is not None:
-            self.gen.close()
-            self.gen = None

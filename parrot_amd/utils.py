@@ -176,8 +176,24 @@ def sample_parse(argv=None):
                              'completes (Parrot.decode_segments; same feature files); --stop_at_end 1 then ends after the '
                              'segment in which the longest utterance ends; 0: one call for all --num_steps frames; not with '
                              '--sample_one_step')
+    parser.add_argument('--stream_audio', type=int, default=0,
+                        help='1 (a --raw_output experiment, with --segment_frames F and --stream_frames S): text to audio in '
+                             'one stream -- every decoder segment is handed to the SampleRNN vocoder on the device as it '
+                             'completes (Parrot.synthesize_segments), so the first audio is out after one decoder segment and '
+                             'one vocoder segment; the same wav and feature files; composes with --pack_streams, '
+                             '--utterance_seed, --draw_mode, --top_k, --top_p, --min_p and the per-utterance decode controls; '
+                             'not with --sample_one_step; 0: decode everything, then the vocoder')
     parser.add_argument('--synthetic_examples', type=int, default=64)
     args = parser.parse_args(argv)
+    if args.stream_audio not in (0, 1):
+        raise SystemExit("--stream_audio %d: 0 or 1" % args.stream_audio)
+    if args.stream_audio and args.sample_one_step:
+        raise SystemExit("--stream_audio hands the segments of the free-running decode to the vocoder; --sample_one_step "
+                         "decodes no such loop: give one of the two")
+    if args.stream_audio and args.segment_frames < 1:
+        raise SystemExit("--stream_audio needs --segment_frames F > 0: the decoder segments it hands to the vocoder")
+    if args.stream_audio and args.stream_frames < 1:
+        raise SystemExit("--stream_audio needs --stream_frames S > 0: the vocoder segments that take them")
     if args.dataset not in args.save_dir:
         args.save_dir = os.path.join(args.save_dir, args.dataset)
     if args.prime_frames < 0:

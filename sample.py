@@ -90,8 +90,33 @@ def main(argv=None):
         srn_lib.set_params(srn_parameters)
     print("Successfully loaded the parameters.")
 
+    streamed_audio = None
+    if args.stream_audio and not raw_output:
+        raise SystemExit("--stream_audio streams the SampleRNN vocoder's audio: the experiment was trained without --raw_output")
     if args.sample_one_step:
         gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = parrot.sample_using_input(data_tr, args.num_samples)
+    elif args.stream_audio:  # text to audio in one stream: the vocoder runs each decoder segment as it completes
+        tt = parrot.sampleRnn.three_tier
+        per_utt = args.utterance_seed >= 0
+        run = parrot.synthesize_segments(
+            labels_tr, labels_mask_tr, speaker_tr, args.num_samples, args.num_steps, args.segment_frames, args.stream_frames,
+            n_streams=args.pack_streams if args.pack_streams > 0 else 32, temperature=tt.TEMPERATURE,
+            seeds=[tt.utterance_seed(args.utterance_seed, i) for i in range(args.num_samples)] if per_utt else None,
+            draw_mode=args.draw_mode, top_k=args.top_k, top_p=args.top_p, min_p=args.min_p,
+            stop_at_end=bool(args.stop_at_end), **row_controls)
+        to_save_path = os.path.join(args.save_dir, 'samples', 'new_raw')
+        os.makedirs(to_save_path, exist_ok=True)
+        chunks = [[] for _ in range(args.num_samples)]
+        for idx, chunk, done in run:
+            chunks[idx].append(chunk)
+            if done:  # each wav as its utterance finishes, as --stream_frames writes them
+                tt._write_piece(args.samples_name, idx, numpy.concatenate(chunks[idx]), to_save_path)
+        if run.first_audio_s is not None:  # (None: no utterance went beyond its prefix slot)
+            print("--stream_audio: the first audio was out after %.1f ms" % (1e3 * run.first_audio_s))
+        streamed_audio = True
+        gen_x, gen_k, gen_w, gen_pi, gen_phi, gen_pi_att = (
+            torch.cat(p, dim=0).detach().cpu().numpy() for p in list(zip(*run.outs))[:6])
+        stop_lengths = run.decode.lengths.cpu().numpy()
     elif args.segment_frames:  # segments of one resumable plan; --stop_at_end ends after the longest utterance's segment
         started = time.perf_counter()
         run = parrot.decode_segments(labels_tr, labels_mask_tr, speaker_tr, args.num_samples, args.num_steps,
@@ -121,7 +146,7 @@ def main(argv=None):
             continue
         ll = int(labels_mask_tr[idx].sum())
         features_lengths.append(end_of_utterance(gen_phi[idx], min(ll, gen_phi.shape[2] - 1), args.num_steps))
-    if raw_output:  # sample.py:165-173: SampleRNN vocoder on the generated frames
+    if raw_output and not streamed_audio:  # sample.py:165-173: SampleRNN vocoder on the generated frames
         print("Sampling and saving raw audio...")
         to_save_path = os.path.join(args.save_dir, 'samples', 'new_raw')
         os.makedirs(to_save_path, exist_ok=True)

@@ -120,6 +120,15 @@ configs[4] SampleRNN sample loop, mu-law quantiser bandwidth).  Development / do
                                          boundary; with --parent-lib (the parent commit's libparrot_hip.so) the plain call of
                                          both libraries in the same alternation, bit identity included; the result also goes
                                          to FILE (default profiles/decode_segments.json)
+  bench_extra.py --only text_to_audio [--text-to-audio-json FILE]
+                                         text to audio in one stream (parrot_amd.decode.TextToAudio): configs[2] decoder, DIM
+                                         1024 vocoder, 16 texts of 20 .. 100 characters (the end-of-utterance rule sets their
+                                         frames, at most 1000), 16 decoder slots and 16 vocoder streams, vocoder segments of 8,
+                                         decoder segments of 10 and of 50 -- time to first audio and total time against the
+                                         staged path (StreamingDecoder.run() to the end, then StreamingGenerator.submit of whole
+                                         utterances), the three alternating in one process, three runs each, with spreads; and
+                                         the per-step cost of samplernn_generate_stage_features against the host-array upload
+                                         it replaces; the result also goes to FILE (default profiles/text_to_audio.json)
   bench_extra.py --kappa-bias B          decode_stop: fork_kappa.b of the randomly initialised model (default -1.0: how fast
                                          the window walks over the text, i.e. after how many steps the utterance ends)
   bench_extra.py --dump-sample FILE      decode_cfg3 also saves sample_x (numpy) -- bit-identity checks between builds
@@ -145,7 +154,7 @@ def _arg(name, dflt=None):
 ALL = ("decode_cfg3", "decode_stop", "decode_lstm2_1024", "decode_lstm3_1536", "decode_gmm_gru2_1024", "decode_gmm_lstm2_1024",
        "decode_bf16_gru2_1024", "decode_bf16_gru3_1024", "decode_bf16_gru2_1536", "decode_bf16_gru3_1536", "samplernn_cfg5", "samplernn_groups",
        "samplernn_packed", "samplernn_stream", "samplernn_utt_draws", "samplernn_draw_scan", "samplernn_top_k", "samplernn_top_p", "samplernn_min_p", "samplernn_forced", "samplernn_skip",
-       "decode_row_controls", "decode_forced", "decode_segments", "mulaw")
+       "decode_row_controls", "decode_forced", "decode_segments", "text_to_audio", "mulaw")
 only =tuple(_arg("--only", ",".join(ALL)).split(","))
 assert all(n in ALL for n in only), only
 LSTM_SHAPES = {  # configs[2]'s shape with LSTM cells; the 3 x LSTM-1536 model of BASELINE configs[3]
@@ -1757,6 +1766,117 @@ if "decode_segments" in only:
     res["not_measured"] = ["B > 16", "the H = 1536 LSTM plan with two units per workgroup", "the launch path's timing",
                            "StreamingDecoder: admission under load"]
     record("decode_segments", "--segments-json", res)
+
+# ---- text to audio in one stream (parrot_amd.decode.TextToAudio): the decoder's segments feed the vocoder's ring on the device.
+# Against the staged path of the parent commit: every frame decoded (StreamingDecoder.run()), copied to the host, then whole
+# utterances submitted to a StreamingGenerator.  All three keep their plans alive in one process and alternate; a run is timed
+# from its first call to the last chunk on the host, "first audio" to the first chunk that holds samples behind a prefix.
+if "text_to_audio" in only:
+    from parrot_amd import _lib as plib
+    from parrot_amd import ops as hip
+    from parrot_amd.decode import StreamingDecoder, TextToAudio
+    from parrot_amd.model import Parrot
+    tt = samplernn_d1024()
+    N, U, T, Bv, Sv, extra, runs_each = 16, 100, 1000, 16, 8, 40, 3
+    m = Parrot(device=dev, encoder_type='bidirectional', weak_feedback=True, use_graph=True, num_layers=2, rnn_h_dim=1024,
+               readouts_dim=1024, encoder_literal=False, seed=1234).initialize()
+    # (kappa bias -2.2: the window walks about 0.1 characters per frame, so texts of 20 .. 100 characters end after some 200 ..
+    # 1000 frames; --kappa-bias B sets another pace)
+    m._p('/h1_to_att/fork_kappa.b').fill_(float(_arg("--kappa-bias", "-2.2")))
+    gen_ = torch.Generator().manual_seed(0)
+    texts = [torch.randint(0, 43, (20 + (80 * i) // (N - 1),), generator=gen_) for i in range(N)]
+
+    def pipeline(F):
+        tta = TextToAudio(m, N, F, U, T, Bv, Sv, extra=extra)
+
+        def run():
+            for t in texts:
+                tta.submit(t)
+            pieces = {}
+            for uid, chunk, done in tta.run():
+                pieces.setdefault(uid, []).append(chunk)
+            ids = sorted(pieces)
+            return tta.first_audio_s, [np.concatenate(pieces[i]) for i in ids]
+        return run, tta.close
+
+    def staged(F):
+        sd = StreamingDecoder(m, N, F, U, T, extra=extra)
+        sg = tt.StreamingGenerator(Bv, Sv, temperature=0.0)
+
+        def run():
+            t0 = time.time()
+            ids = [sd.submit(t) for t in texts]
+            frames = {uid: fr.cpu().numpy() for uid, fr, _ in sd.run()}
+            tickets = {sg.submit(frames[uid]): k for k, uid in enumerate(ids)}
+            pieces, first = {}, None
+            while not sg.idle():
+                for ticket, chunk, done in sg.step():
+                    if first is None and (ticket in pieces or chunk.size > 80):
+                        first = time.time() - t0
+                    pieces.setdefault(ticket, []).append(chunk)
+            return first, [np.concatenate(pieces[t]) for t in sorted(pieces, key=tickets.get)]
+        return run, sg.close
+
+    legs = {"pipeline_decoder_segments_10": pipeline(10), "pipeline_decoder_segments_50": pipeline(50),
+            "staged_decoder_segments_50": staged(50)}
+    totals, firsts, samples = {k: [] for k in legs}, {k: [] for k in legs}, {}
+    keys = list(legs)
+    for rep_ in range(runs_each + 1):  # (the first round builds the plans and captures the graphs: not counted)
+        for k in keys[rep_ % len(keys):] + keys[:rep_ % len(keys)]:
+            torch.cuda.synchronize(); t0 = time.time()
+            first, samples[k] = legs[k][0]()
+            torch.cuda.synchronize(); dt = time.time() - t0
+            if rep_:
+                totals[k].append(1e3 * dt)
+                firsts[k].append(1e3 * first)
+    for run_, close_ in legs.values():
+        close_()
+    med = lambda v: sorted(v)[len(v) // 2]
+    lengths = [int(s.size) // 80 for s in samples["staged_decoder_segments_50"]]
+    res = {"decoder": "configs[2]: 2 x GRU-1024, MSE head, %d slots" % N, "vocoder": "DIM 1024, %d streams, segments of %d" % (Bv, Sv),
+           "utterances": N, "frames_per_utterance": lengths, "runs_each": runs_each,
+           "timed": "first submit to the last chunk on the host; first_audio_ms: to the first chunk with samples behind a prefix",
+           "legs": {k: {"total_ms": [round(x, 2) for x in totals[k]], "total_ms_median": round(med(totals[k]), 2),
+                        "total_spread_max_minus_min_ms": round(max(totals[k]) - min(totals[k]), 2),
+                        "first_audio_ms": [round(x, 2) for x in firsts[k]], "first_audio_ms_median": round(med(firsts[k]), 2),
+                        "first_audio_spread_max_minus_min_ms": round(max(firsts[k]) - min(firsts[k]), 2)} for k in legs},
+           "pipeline_samples_equal_staged": {k: bool(all(a.shape == b.shape and np.array_equal(a, b) for a, b in
+                                                         zip(samples[k], samples["staged_decoder_segments_50"])))
+                                             for k in keys[:2]}}
+    m.close()
+    # the staging call against the host-array upload it replaces: one vocoder segment of Sv frames on Bv streams
+    sgen = tt.DeviceGenerator(Bv, Sv + 1, temperature=0.0, packed=True)
+    store = torch.randn(32 * T, 64, generator=g).to(dev)
+    index = torch.randint(0, 32 * T, (Sv, Bv), generator=g, dtype=torch.int32).numpy()
+    host = store.cpu().numpy()[index.reshape(-1), :63].reshape(Sv, Bv, 63).copy()
+    fbuf = sgen.ws['features']
+
+    def upload():
+        fbuf[1:Sv + 1].copy_(torch.as_tensor(host).to(fbuf.device, torch.float32))
+
+    def stage():
+        idx = torch.from_numpy(index).to(dev)
+        plib.call('samplernn_generate_stage_features', sgen.plan, store.data_ptr(), store.shape[0], 64, idx.data_ptr(), 1, Sv,
+                  hip._stream())
+
+    per_call = {"host_array_upload": [], "stage_features": []}
+    for rep_ in range(runs_each + 1):
+        for k, fn in (("host_array_upload", upload), ("stage_features", stage))[::1 if rep_ % 2 else -1]:
+            torch.cuda.synchronize(); t0 = time.time()
+            for _ in range(200):
+                fn()
+                torch.cuda.synchronize()
+            if rep_:
+                per_call[k].append(1e6 * (time.time() - t0) / 200)
+    stage()
+    torch.cuda.synchronize()
+    res["staging_call"] = {"shape": "%d frames x %d streams x 63 floats, call to device idle, 200 calls per run" % (Sv, Bv),
+                           "us_per_call": {k: [round(x, 1) for x in v] for k, v in per_call.items()},
+                           "staged_rows_equal_uploaded": bool(np.array_equal(fbuf[1:Sv + 1].cpu().numpy(), host))}
+    sgen.close()
+    res["not_measured"] = ["admission under load (texts arriving while the pipeline runs)", "a pool smaller than the traffic",
+                           "GMM-head decoders", "per-utterance draws at temperature > 0", "more than 16 utterances in flight"]
+    record("text_to_audio", "--text-to-audio-json", res)
 
 # ---- mu-law quantiser: x ~ N(0,1) [32, 16000*8]
 if "mulaw" in only:
